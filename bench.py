@@ -12,9 +12,11 @@ ranks never exchange data on the path; for N > 1 each step ends with the RCCL ga
 rank 0 -- two regular collectives, no host synchronisation.
   --scaling weak   (default; what the driver's N = 1 line and its scaling curve use): every GPU gets its own --batch images;
   --scaling strong (BASELINE configs[4] as written): the SAME --batch images are split over the ranks, contiguous shards.
-Rank 0 prints ONE JSON line.  Outside the timed region (N = 1, unless --no-cpu-baseline): the targets north_star names on
-mapValue_map1 (512 x replicated map1 -> lines/s; one host-ABI call createMapCache + myLineSegmentDetector), the
-single-image latency, the device copy ceiling and the CPU baseline (SURVEY 8d protocol).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline figure (with
+--dump-outputs DIR it first writes what the last timed step computed).  With --full, after the timed region: one step at a time
+(per-kernel times, roofline, region-stage cycles), the strong split and the check of the gathered results (N > 1), and (N = 1,
+unless --no-cpu-baseline) the targets north_star names on mapValue_map1 (512 x replicated map1 -> lines/s; one host-ABI call
+createMapCache + myLineSegmentDetector), the single-image latency, the device copy ceiling and the CPU baseline (SURVEY 8d protocol).
 """
 import argparse
 import importlib
@@ -295,6 +297,57 @@ def fit_depth(depth, need_per_slot, need_fixed, free_bytes, floor=4):
                  % (depth, (depth * need_per_slot + need_fixed) / 1e9, need_per_slot / 1e9, free_bytes / 1e9, new))
 
 
+DUMP_BYTES = 64 << 20                                   # --dump-outputs writes at most this much in all
+LINE_FIELDS = ("k", "b", "dx", "dy", "x1", "y1", "x2", "y2", "len", "orient")
+NONFINITE_FIELDS = ("k", "b")                           # slope and intercept: +-inf (or NaN) for a vertical line, as the reference keeps them
+
+
+def dump_outputs(path, lsd, slot, n, max_lines):
+    """--dump-outputs: what the caller of the timed path received from one step (`slot` = its line records, counts and lineIm
+    buffers on the device), as .npy files two builds can be compared by, at most DUMP_BYTES in all:
+      counts.npy         float64 [n]         the library's line count per image (above max_lines: the list overflowed; -1: given up)
+      lines.npy          float64 [rows, 13]  image index, then k b dx dy x1 y1 x2 y2 len orient of every stored line record, images in order,
+                                             then the class of k and of b: 0 finite, 1 +inf, -1 -inf, 2 NaN (k or b is 0 where not finite)
+      line_im.npy        float32 [k, H, W]   the lineIm rasters (0 / 255) of k images drawn with a fixed seed, as many as the budget holds
+      line_im_index.npy  float64 [k]         which images those are
+    Should the line records take more than half the budget (not at the default sizes), they are kept for a seeded sample of images."""
+    d_lines, d_counts, d_ims = slot
+    os.makedirs(path, exist_ok=True)
+    order = np.random.default_rng(0).permutation(n)
+    counts = d_counts[:n].cpu().numpy().astype(np.float64)
+    rows = np.clip(counts, 0, max_lines).astype(np.int64)
+    rec = d_lines[:n].cpu().numpy().view(lsd.LINE_DTYPE).reshape(n, max_lines)
+    keep = np.zeros(n, bool)
+    keep[order[np.cumsum(rows[order] * 8 * (1 + len(LINE_FIELDS) + len(NONFINITE_FIELDS))) <= DUMP_BYTES // 2]] = True
+    idx = np.flatnonzero(keep)
+    recs = np.concatenate([rec[i, :rows[i]] for i in idx] + [np.zeros(0, lsd.LINE_DTYPE)])
+    fin = {f: np.isfinite(recs[f]) for f in NONFINITE_FIELDS}
+    lines = np.column_stack([np.repeat(idx, rows[idx])] + [np.where(fin[f], recs[f], 0.0) if f in fin else recs[f] for f in LINE_FIELDS] +
+                            [np.select([fin[f], np.isposinf(recs[f]), np.isneginf(recs[f])], [0.0, 1.0, -1.0], 2.0) for f in NONFINITE_FIELDS]).astype(np.float64)
+    np.save(os.path.join(path, "counts.npy"), counts)
+    np.save(os.path.join(path, "lines.npy"), lines)
+    if d_ims is not None:
+        per_image = 4 * d_ims.shape[1] * d_ims.shape[2]
+        k = int(min(n, (DUMP_BYTES - (1 << 12) - 8 * n - counts.nbytes - lines.nbytes) // per_image))
+        sel = np.sort(order[:max(k, 0)])
+        ims = np.zeros((len(sel),) + tuple(d_ims.shape[1:]), np.float32)
+        for j, i in enumerate(sel):
+            ims[j] = d_ims[int(i)].cpu().numpy()
+        np.save(os.path.join(path, "line_im.npy"), ims)
+        np.save(os.path.join(path, "line_im_index.npy"), sel.astype(np.float64))
+
+
+def dumped_line_records(lines, lsd):
+    """lines.npy of dump_outputs back to (image index per record, LINE_DTYPE records), k and b +-inf / NaN again where they were."""
+    rec = np.zeros(len(lines), lsd.LINE_DTYPE)
+    for c, f in enumerate(LINE_FIELDS):
+        rec[f] = lines[:, 1 + c]
+    for c, f in enumerate(NONFINITE_FIELDS):
+        cls = lines[:, 1 + len(LINE_FIELDS) + c]
+        rec[f] = np.select([cls == 1, cls == -1, cls == 2], [np.inf, -np.inf, np.nan], rec[f])
+    return lines[:, 0].astype(np.int64), rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -306,7 +359,13 @@ def main():
     ap.add_argument("--size", type=int, default=2048)
     ap.add_argument("--max-lines", type=int, default=1024)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip everything outside the timed region (CPU baseline, map1 targets, single-image latency, copy ceiling): what the profiling passes use")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, measure and check everything else after the timed region: one step at a time "
+                    "(per-kernel times, roofline, region-stage cycles), the strong split and the gathered results (N > 1), and, unless --no-cpu-baseline, "
+                    "the CPU baseline, map1 targets, reference maps, single-image latency, strong-scaling projection and copy ceiling")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, map1 targets, reference maps, single-image latency, "
+                    "strong-scaling projection and copy ceiling (what the profiling passes use)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed region, write what rank 0's last timed step computed to DIR/*.npy (float64 / float32, "
+                    "at most 64 MB): counts, every line record and the lineIm rasters of a fixed, seeded sample of images")
     ap.add_argument("--no-lineim", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="exercise the RCCL gather path even with one rank (testing)")
     ap.add_argument("--pipeline", type=int, default=8, help="steps in flight: step i runs on context / stream i %% depth, so that the tail of one step's region stage "
@@ -319,6 +378,8 @@ def main():
                     "step will come to fill the CUs their last images leave idle); measured with 20 steps at depth 8: 0 / 4 / 7 / 8 -> 44.9 / 45.3 / 46.8 / 68.4 ms per step")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no WORLD_SIZE in the environment: print the command that would start the ranks and exit")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` started the way `--gpus 1` is (no torch.distributed.run around it): start the ranks ourselves, as a
     # child job, BEFORE anything here touches the GPU
@@ -443,12 +504,14 @@ def main():
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                       # (before anything below runs on the slots' output buffers)
+        dump_outputs(a.dump_outputs, lsd, outs[(a.steps - 1) % depth], n, a.max_lines)
     # The strong split next to the weak line (N > 1, --scaling weak): the SAME --batch images (rank 0's) split over the ranks in contiguous
     # shards (BASELINE configs[4], the split north_star's "1 -> 8 GPUs on a 512-image batch" means), same contexts, same depth, same
     # protocol (barrier, K steps, barrier, max over ranks).  A shard is 1/N of the images, so a rank's GPU is 1/N as full as in the weak
     # job: DESIGN.md section 6 says what that costs and what a rank that keeps N x as many steps in flight gets back.
     strong_dt = None
-    if use_dist and a.scaling == "weak":                       # (use_dist: world > 1, or one rank under --force-dist -- the tests' way into this path)
+    if a.full and use_dist and a.scaling == "weak":            # (use_dist: world > 1, or one rank under --force-dist -- the tests' way into this path)
         lo_s, hi_s = ldist.shard_range(a.batch, world, rank)
         strong_err = torch.zeros(1, dtype=torch.int32, device=dev)
         try:
@@ -478,16 +541,16 @@ def main():
         del d_shard
     # the front end inside the timed region: HIP events of every slot's LAST step, event to event -- with several steps in flight that
     # includes the wait for room beside the region stage's workgroups (one step at a time: kernel_ms below)
-    tr_front = [c_.timings() for c_ in ctxs[:min(depth, a.steps)]] if depth > 1 else []
+    tr_front = [c_.timings() for c_ in ctxs[:min(depth, a.steps)]] if a.full and depth > 1 else []
     last = outs[(a.steps - 1) % depth]
     w_, h_ = lsd.scaled_size(size, size)
-    timed_cyc = np.array([ctxs[(a.steps - 1) % depth].fetch(i, lsd.DBG_STATS, (w_, h_))["cycles_total"] for i in range(n)], np.float64) if rank == 0 else None
+    timed_cyc = np.array([ctxs[(a.steps - 1) % depth].fetch(i, lsd.DBG_STATS, (w_, h_))["cycles_total"] for i in range(n)], np.float64) if a.full and rank == 0 else None
     if timed_cyc is not None and (timed_cyc > 0).any():
         timed_cyc = timed_cyc[timed_cyc > 0]
     # One step at a time, after the timed region when that ran with several in flight: the per-kernel figures (inside an
     # overlapped region a launch's HIP events also time its wait for a CU) and the step time of a single batch, help on.
     un_steps, un_dt, hist_dt = a.steps, dt, None
-    if depth > 1:
+    if a.full and depth > 1:
         ctx.set_region_help(-1)
         ctx.set_region_waves(0)
         un_steps = min(a.steps, 5)
@@ -524,44 +587,8 @@ def main():
     overflow = int((last[1] > a.max_lines).sum().item())
 
     if rank == 0:
-        if use_dist:                                       # the gathered results of the last step of EVERY slot in flight: every line arrived, nothing overflowed
-            per, _ = lsd.gather_layout(n_total, world)
-            for j, rj in sorted(res_slot.items()):
-                counts_all, slabs = rj
-                assert int(counts_all[:, :per].sum().item()) == int(total_lines) == int(counts_all[:, per].sum().item()), "lsd_gather_lines lost lines (slot %d)" % j
-                assert not bool(counts_all[:, per + 1].any().item()), "lsd_gather_lines: a slab overflowed or an image was given up (slot %d)" % j
         step_s = dt / a.steps
         mpix = n_total * size * size / 1e6
-        grad_ms = kt["gradient"] / un_steps
-        un_step_s = un_dt / un_steps
-        grad_bytes = GRAD_BYTES_PER_PX * w * h * n
-        achieved = grad_bytes / (grad_ms * 1e-3) / 1e9 if grad_ms > 0 else 0.0
-        traffic, traffic_all, traffic_src = None, {}, None
-        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-        if os.path.exists(tpath) and n == 512 and size == 2048:
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get("k_gradient_bytes_per_launch")
-                traffic_all = {k: v["hbm_bytes_per_launch"] for k, v in tj.get("kernels", {}).items()}
-                same = tj.get("source_sha") == source_sha()
-                traffic_src = "profiles/traffic_latest.json (%s, kernel sources %s): separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, not this run" % (
-                    tj.get("build", "build not recorded"), "identical to this run's (sha %s)" % source_sha() if same else "DIFFERENT from this run's: sha %s vs %s" % (tj.get("source_sha"), source_sha()))
-            except Exception:
-                traffic = None
-        # per-image cycles of the region stage (s_memtime, read after the timed region): the batch time is its heaviest images
-        stats = [ctx.fetch(i, lsd.DBG_STATS, (w, h)) for i in range(n)]
-        ties = ctx.last_sensitivity(n)                      # decisions within the noise of the reference's libm, per image (lsd_last_sensitivity)
-        cyc_raw = np.array([x["cycles_total"] for x in stats], np.int64)
-        # (a record that is not a positive clock count is left out of the statistics and listed.  The count is a difference of the shader clock,
-        #  s_memtime, which is a counter of the XCD: a workgroup that was preempted -- more hardware queues in use than the device has, e.g. this
-        #  process beside another -- and resumed elsewhere read another counter; the kernel falls back to the constant 100 MHz clock then, so
-        #  that none should show up here any more)
-        bad_cyc = [(int(i), int(v)) for i, v in enumerate(cyc_raw) if v <= 0]
-        cyc = cyc_raw[cyc_raw > 0].astype(np.float64) if (cyc_raw > 0).any() else np.ones(1)
-        nb_mean = float(np.mean([ctx.fetch(i, lsd.DBG_NB, (w, h)) for i in range(0, n, max(1, n // 32))]))
-        # SURVEY 8d algorithmic bytes of the whole path per image: K1 W*H + 8wh, K2 25wh, K3 8wh + 12 nb, K5 W*H (K4: latency-bound, none)
-        alg_img = 2.0 * size * size + (8 + 25 + 8) * w * h + 12.0 * nb_mean
-        reg_ms = kt["region"] / un_steps
         out = {
             "metric": "Mpixels/sec LSD (grad+grow+NFA)", "value": mpix / step_s, "unit": "Mpix/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True,
@@ -580,54 +607,93 @@ def main():
                        # the steps in flight share one resident input, so the timed region runs WITHOUT LSD_FLAG_WRITEBACK_MAP: the
                        # observable in-place remap of the caller's maps (myLSD.cpp:135-142; ~0.3 ms of byte writes per step) is not in it
                        "writeback_map": False},
-            # the timed region keeps `steps_in_flight` steps in flight (one context, stream and set of output buffers each);
-            # `one_step_at_a_time` is the same step run alone, measured right after it -- the source of every per-kernel figure below
-            "one_step_at_a_time": {"steps": un_steps, "ms_per_step": un_step_s * 1e3, "value": mpix / un_step_s, "unit": "Mpix/s",
-                                   "note": "a batch alone on the GPU, the library's defaults (8 waves per image as persistent workgroups, help across workgroups off); kernel_ms, roofline and dominant_kernel are from these steps "
-                                           "(HIP events of a launch inside an overlapped region also time its wait for a CU)" if depth > 1 else "identical to the timed region"},
-            "one_step_at_a_time_with_cost_history": ({"ms_per_step": hist_dt / un_steps * 1e3, "value": mpix / (hist_dt / un_steps), "unit": "Mpix/s",
-                                                     "note": "lsd_set_cost_history(1): the same batch again, its images started in the order of their cost in the previous "
-                                                             "step (a caller re-extracting one site's maps); rank 0's clock, not part of `value`"} if hist_dt else None),
             "lines_per_s": total_lines / step_s, "lines_per_step": total_lines, "line_overflow_images": overflow,
-            # images of rank 0's batch with at least one decision inside the libm's noise (lsd_last_sensitivity): on the others any libm within
-            # one ulp of correct rounding gives the reference's result; and the number of such decisions over the batch
-            "libm_sensitive_images": int((ties > 0).sum()), "libm_near_ties": int(ties.sum()),
-            # N > 1 only: the same --batch images split over the ranks (the strong split), timed like the weak job right after it
-            "strong_split": ({"scaling": "strong", "images_total": a.batch, "ms_per_step": strong_dt / a.steps * 1e3,
-                              "value": a.batch * size * size / 1e6 / (strong_dt / a.steps), "unit": "Mpix/s", "steps": a.steps,
-                              "steps_in_flight": depth,
-                              "note": "rank 0's %d images in contiguous shards over the %d ranks, RCCL gather of the line lists in every step; same contexts and "
-                                      "depth as the weak job, max over ranks; compare with the N = 1 line's value" % (a.batch, world)} if strong_dt else None),
-            "kernel_ms": {k: v / un_steps for k, v in kt.items()},
-            # the same kernels inside the timed region, event to event (mean over the slots' last steps): what the front end of a step
-            # takes while the region stages of the other steps in flight hold the CUs
-            "kernel_ms_in_timed_region": ({k: float(np.mean([t[k] for t in tr_front])) for k in ("gauss", "gradient", "sort", "region", "lines")} if tr_front else None),
-            # informational: every kernel's HBM traffic (PMC, profiles/traffic_latest.json) over its live launch time
-            "kernel_hbm_GBs": {k: traffic_all["k_" + k] / (kt[k] / un_steps * 1e-3) / 1e9
-                               for k in ("gauss", "gradient", "sort", "region", "lines") if ("k_" + k) in traffic_all and kt[k] > 0},
-            # the kernel north_star prices: the gradient pass, algorithmic bytes over its HIP-event launch time of THIS run
-            "roofline": {"kernel": "k_gradient", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": grad_bytes, "avg_launch_ms": grad_ms,
-                         "note": "k_gradient is the pass north_star prices, not the dominant kernel: see dominant_kernel / roofline_pipeline"},
-            # ... and the whole truth next to it: the step is the region stage, a serial-latency / instruction-issue bound kernel
-            "dominant_kernel": {"name": "k_region", "ms": reg_ms, "share_of_step": reg_ms / (un_step_s * 1e3),
-                                "Mpix_per_s": n * size * size / 1e6 / (reg_ms * 1e-3), "lines_per_s": float(d_counts.sum().item()) / (reg_ms * 1e-3),
-                                "bound": "serial dependence per image (no HBM / MFMA roofline applies): DESIGN.md section 4",
-                                "variant": "w8::k_region (the library's choice for one batch of this size: one persistent workgroup per CU; help across workgroups off)" if (depth > 1 or not waves) else "w%d::k_region" % waves,
-                                "cycles_per_image": {"mean": float(cyc.mean()), "max": float(cyc.max()), "max_over_mean": float(cyc.max() / cyc.mean()), "bad_records": bad_cyc},
-                                # the same statistics for the last step of the TIMED region (its own variant; with several steps in flight a
-                                # workgroup shares its CU with workgroups of other steps, so these cycles include that contention)
-                                "timed_region": {"variant": "w%d::k_region, help %s, %d steps in flight" % (waves if waves else 8, "off" if (depth > 1 and not a.help_waves) else "on", depth),
-                                                 "cycles_per_image": {"mean": float(timed_cyc.mean()), "max": float(timed_cyc.max()), "max_over_mean": float(timed_cyc.max() / timed_cyc.mean())}},
-                                # full evaluations of the last step that wavefronts of finished workgroups did for other images
-                                "help_across_workgroups": {"evaluations": int(sum(x["help_evals"] for x in stats)),
-                                                           "images_helped": int(sum(1 for x in stats if x["help_exports"] > 0))}},
-            "roofline_pipeline": {"bound": "hbm", "algorithmic_bytes_per_step": alg_img * n, "achieved": alg_img * n_total / step_s / 1e9,
-                                  "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": alg_img * n_total / step_s / 1e9 / (HBM_PEAK_GBS * world),
-                                  "note": "SURVEY 8d algorithmic bytes of the whole path (K1+K2+K3+K5; %.1f MB per image) over the step time" % (alg_img / 1e6)},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            if use_dist:                                       # the gathered results of the last step of EVERY slot in flight: every line arrived, nothing overflowed
+                per, _ = lsd.gather_layout(n_total, world)
+                for j, rj in sorted(res_slot.items()):
+                    counts_all, slabs = rj
+                    assert int(counts_all[:, :per].sum().item()) == int(total_lines) == int(counts_all[:, per].sum().item()), "lsd_gather_lines lost lines (slot %d)" % j
+                    assert not bool(counts_all[:, per + 1].any().item()), "lsd_gather_lines: a slab overflowed or an image was given up (slot %d)" % j
+            grad_ms = kt["gradient"] / un_steps
+            un_step_s = un_dt / un_steps
+            grad_bytes = GRAD_BYTES_PER_PX * w * h * n
+            achieved = grad_bytes / (grad_ms * 1e-3) / 1e9 if grad_ms > 0 else 0.0
+            traffic, traffic_all, traffic_src = None, {}, None
+            tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+            if os.path.exists(tpath) and n == 512 and size == 2048:
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get("k_gradient_bytes_per_launch")
+                    traffic_all = {k: v["hbm_bytes_per_launch"] for k, v in tj.get("kernels", {}).items()}
+                    same = tj.get("source_sha") == source_sha()
+                    traffic_src = "profiles/traffic_latest.json (%s, kernel sources %s): separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, not this run" % (
+                        tj.get("build", "build not recorded"), "identical to this run's (sha %s)" % source_sha() if same else "DIFFERENT from this run's: sha %s vs %s" % (tj.get("source_sha"), source_sha()))
+                except Exception:
+                    traffic = None
+            # per-image cycles of the region stage (s_memtime, read after the timed region): the batch time is its heaviest images
+            stats = [ctx.fetch(i, lsd.DBG_STATS, (w, h)) for i in range(n)]
+            ties = ctx.last_sensitivity(n)                      # decisions within the noise of the reference's libm, per image (lsd_last_sensitivity)
+            cyc_raw = np.array([x["cycles_total"] for x in stats], np.int64)
+            # (a record that is not a positive clock count is left out of the statistics and listed.  The count is a difference of the shader clock,
+            #  s_memtime, which is a counter of the XCD: a workgroup that was preempted -- more hardware queues in use than the device has, e.g. this
+            #  process beside another -- and resumed elsewhere read another counter; the kernel falls back to the constant 100 MHz clock then, so
+            #  that none should show up here any more)
+            bad_cyc = [(int(i), int(v)) for i, v in enumerate(cyc_raw) if v <= 0]
+            cyc = cyc_raw[cyc_raw > 0].astype(np.float64) if (cyc_raw > 0).any() else np.ones(1)
+            nb_mean = float(np.mean([ctx.fetch(i, lsd.DBG_NB, (w, h)) for i in range(0, n, max(1, n // 32))]))
+            # SURVEY 8d algorithmic bytes of the whole path per image: K1 W*H + 8wh, K2 25wh, K3 8wh + 12 nb, K5 W*H (K4: latency-bound, none)
+            alg_img = 2.0 * size * size + (8 + 25 + 8) * w * h + 12.0 * nb_mean
+            reg_ms = kt["region"] / un_steps
+            out.update({
+                # the timed region keeps `steps_in_flight` steps in flight (one context, stream and set of output buffers each);
+                # `one_step_at_a_time` is the same step run alone, measured right after it -- the source of every per-kernel figure below
+                "one_step_at_a_time": {"steps": un_steps, "ms_per_step": un_step_s * 1e3, "value": mpix / un_step_s, "unit": "Mpix/s",
+                                       "note": "a batch alone on the GPU, the library's defaults (8 waves per image as persistent workgroups, help across workgroups off); kernel_ms, roofline and dominant_kernel are from these steps "
+                                               "(HIP events of a launch inside an overlapped region also time its wait for a CU)" if depth > 1 else "identical to the timed region"},
+                "one_step_at_a_time_with_cost_history": ({"ms_per_step": hist_dt / un_steps * 1e3, "value": mpix / (hist_dt / un_steps), "unit": "Mpix/s",
+                                                         "note": "lsd_set_cost_history(1): the same batch again, its images started in the order of their cost in the previous "
+                                                                 "step (a caller re-extracting one site's maps); rank 0's clock, not part of `value`"} if hist_dt else None),
+                # images of rank 0's batch with at least one decision inside the libm's noise (lsd_last_sensitivity): on the others any libm within
+                # one ulp of correct rounding gives the reference's result; and the number of such decisions over the batch
+                "libm_sensitive_images": int((ties > 0).sum()), "libm_near_ties": int(ties.sum()),
+                # N > 1 only: the same --batch images split over the ranks (the strong split), timed like the weak job right after it
+                "strong_split": ({"scaling": "strong", "images_total": a.batch, "ms_per_step": strong_dt / a.steps * 1e3,
+                                  "value": a.batch * size * size / 1e6 / (strong_dt / a.steps), "unit": "Mpix/s", "steps": a.steps,
+                                  "steps_in_flight": depth,
+                                  "note": "rank 0's %d images in contiguous shards over the %d ranks, RCCL gather of the line lists in every step; same contexts and "
+                                          "depth as the weak job, max over ranks; compare with the N = 1 line's value" % (a.batch, world)} if strong_dt else None),
+                "kernel_ms": {k: v / un_steps for k, v in kt.items()},
+                # the same kernels inside the timed region, event to event (mean over the slots' last steps): what the front end of a step
+                # takes while the region stages of the other steps in flight hold the CUs
+                "kernel_ms_in_timed_region": ({k: float(np.mean([t[k] for t in tr_front])) for k in ("gauss", "gradient", "sort", "region", "lines")} if tr_front else None),
+                # informational: every kernel's HBM traffic (PMC, profiles/traffic_latest.json) over its live launch time
+                "kernel_hbm_GBs": {k: traffic_all["k_" + k] / (kt[k] / un_steps * 1e-3) / 1e9
+                                   for k in ("gauss", "gradient", "sort", "region", "lines") if ("k_" + k) in traffic_all and kt[k] > 0},
+                # the kernel north_star prices: the gradient pass, algorithmic bytes over its HIP-event launch time of THIS run
+                "roofline": {"kernel": "k_gradient", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": grad_bytes, "avg_launch_ms": grad_ms,
+                             "note": "k_gradient is the pass north_star prices, not the dominant kernel: see dominant_kernel / roofline_pipeline"},
+                # ... and the whole truth next to it: the step is the region stage, a serial-latency / instruction-issue bound kernel
+                "dominant_kernel": {"name": "k_region", "ms": reg_ms, "share_of_step": reg_ms / (un_step_s * 1e3),
+                                    "Mpix_per_s": n * size * size / 1e6 / (reg_ms * 1e-3), "lines_per_s": float(d_counts.sum().item()) / (reg_ms * 1e-3),
+                                    "bound": "serial dependence per image (no HBM / MFMA roofline applies): DESIGN.md section 4",
+                                    "variant": "w8::k_region (the library's choice for one batch of this size: one persistent workgroup per CU; help across workgroups off)" if (depth > 1 or not waves) else "w%d::k_region" % waves,
+                                    "cycles_per_image": {"mean": float(cyc.mean()), "max": float(cyc.max()), "max_over_mean": float(cyc.max() / cyc.mean()), "bad_records": bad_cyc},
+                                    # the same statistics for the last step of the TIMED region (its own variant; with several steps in flight a
+                                    # workgroup shares its CU with workgroups of other steps, so these cycles include that contention)
+                                    "timed_region": {"variant": "w%d::k_region, help %s, %d steps in flight" % (waves if waves else 8, "off" if (depth > 1 and not a.help_waves) else "on", depth),
+                                                     "cycles_per_image": {"mean": float(timed_cyc.mean()), "max": float(timed_cyc.max()), "max_over_mean": float(timed_cyc.max() / timed_cyc.mean())}},
+                                    # full evaluations of the last step that wavefronts of finished workgroups did for other images
+                                    "help_across_workgroups": {"evaluations": int(sum(x["help_evals"] for x in stats)),
+                                                               "images_helped": int(sum(1 for x in stats if x["help_exports"] > 0))}},
+                "roofline_pipeline": {"bound": "hbm", "algorithmic_bytes_per_step": alg_img * n, "achieved": alg_img * n_total / step_s / 1e9,
+                                      "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": alg_img * n_total / step_s / 1e9 / (HBM_PEAK_GBS * world),
+                                      "note": "SURVEY 8d algorithmic bytes of the whole path (K1+K2+K3+K5; %.1f MB per image) over the step time" % (alg_img / 1e6)},
+            })
+        if a.full and world == 1 and not a.no_cpu_baseline:
             extras(out, a, ctx, lsd, ldist, maps, d_maps, d_lines, d_counts, d_ims, stream, dev, size, n_total, ctxs, outs, tstreams, waves)
             out["cpu_baseline"] = cb = cpu_baseline(size, first)
             # same-box ratios: the GPU against the single-thread port on THIS host's cores (cpu_baseline.kind = "port": a port of the

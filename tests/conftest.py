@@ -48,6 +48,17 @@ def tile2048(aisle1):
     return np.ascontiguousarray(np.tile(aisle1, (4, 2))[:2048, :2048])
 
 
+def libm_tie_image(name):
+    """One image of tests/golden/libm_ties/ (written by tests/golden/make_libm_ties.py): a u8 map of cells 0, 1 and 255, stored as the
+    bit planes of its 1 and 255 cells, one file per image (each file stays small enough to commit)."""
+    z = np.load(os.path.join(GOLDEN, "libm_ties", name + ".npz"))
+    rows, cols = (int(v) for v in z["shape"])
+    img = np.zeros(rows * cols, np.uint8)
+    img[np.unpackbits(z["eq1"], count=rows * cols).astype(bool)] = 1
+    img[np.unpackbits(z["eq255"], count=rows * cols).astype(bool)] = 255
+    return img.reshape(rows, cols)
+
+
 @pytest.fixture(scope="session")
 def lsdmod():
     """The product package (directory name has a hyphen, so import it through importlib)."""

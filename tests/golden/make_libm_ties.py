@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/libm_ties.npz: the images of the random parity campaigns (tools/campaign.py, 160 000 images + 3 900 large ones,
+"""Writes tests/golden/libm_ties/<name>.npz: the images of the random parity campaigns (tools/campaign.py, 160 000 images + 3 900 large ones,
 profiles/r04u_campaign_*.log, profiles/r05h_campaign_*.log, profiles/r06r_campaign_*.log, profiles/r06t_campaign_*.log) on which the HIP path and the glibc-built oracle disagree by one accept / reject decision.  On every
 one of them glibc misrounds a sin / cos / atan2 by one ulp on a structural tie (a rectangle edge exactly on a pixel row); the HIP
 path evaluates those functions correctly rounded and equals the restatement rebuilt on correctly rounded functions
@@ -39,7 +39,11 @@ for i, big in [(i, False) for i in SMALL] + [(i, True) for i in BIG] + [(i, True
     out[name] = img
     table[name] = (kw, len(a["lines"]), len(b["lines"]), int((a["dbg"]["used"] != b["dbg"]["used"]).sum()),
                    int((a["lineIm"] != b["lineIm"]).sum()))
-np.savez_compressed(os.path.join(ROOT, "tests", "golden", "libm_ties.npz"), **out)
+os.makedirs(os.path.join(ROOT, "tests", "golden", "libm_ties"), exist_ok=True)
+for name, img in out.items():                             # one file per image, its 1 and 255 cells as bit planes (tests/conftest.py: libm_tie_image)
+    assert np.isin(img, (0, 1, 255)).all(), name
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "libm_ties", name + ".npz"), shape=np.array(img.shape, np.int64),
+                        eq1=np.packbits(img == 1), eq255=np.packbits(img == 255))
 json.dump({k: dict(params=v[0], lines_glibc=v[1], lines_cr=v[2], used_diff=v[3], lineim_diff=v[4]) for k, v in table.items()},
           open(os.path.join(ROOT, "tests", "golden", "libm_ties.json"), "w"), indent=1)
 for k, v in table.items():

@@ -40,7 +40,8 @@ def test_gpus_n_without_a_launcher_builds_the_drivers_command_line():
     """`python3 bench.py --gpus 2` started like `--gpus 1` (no torch.distributed.run around it, no WORLD_SIZE): bench.py starts the
     ranks itself as a child job before anything touches the GPU; --dry-launch prints the command it would run."""
     import json, os, subprocess, sys
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    # (without the caller's own queue and IPC settings: the environment checked below is the one bench.py sets by itself)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY")}
     p = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
                         "--scaling", "strong", "--dry-launch"], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -100,3 +101,37 @@ def test_gpus_n_on_a_node_with_fewer_gpus_says_so_and_starts_nothing():
     p = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 2 and "--gpus 2 but this node shows" in p.stderr, (p.returncode, p.stderr[-500:])
+
+
+def test_dump_outputs_writes_the_callers_arrays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs on host tensors standing in for one slot's device buffers: every stored line record with its image index
+    (float64, all finite: a vertical line's infinite slope and intercept are written as a class), the counts as the library reported
+    them, and the lineIm rasters of a seeded sample of images (float32), under 64 MB."""
+    import importlib, os
+    import torch
+    lsd = importlib.import_module("linesegmentdetector-slam_amd")
+    n, max_lines, size = 6, 1024, 2048
+    g = np.random.default_rng(5)
+    counts = np.array([3, 0, -1, 1030, 17, 1024], np.int32)                   # a given-up image and an overflowed list among them
+    rec = np.zeros((n, max_lines), lsd.LINE_DTYPE)
+    for f in bench.LINE_FIELDS:
+        rec[f] = g.integers(0, 4, (n, max_lines)) if f == "orient" else g.random((n, max_lines))
+    rec["k"][0, :3] = [np.inf, -np.inf, np.nan]                                  # vertical lines, as the library stores them
+    rec["b"][0, :3] = [-np.inf, np.inf, np.nan]
+    ims = (g.random((n, size, size)) < 0.001).astype(np.uint8) * 255
+    slot = (torch.from_numpy(rec.view(np.int64).reshape(n, max_lines, 10).copy()), torch.from_numpy(counts), torch.from_numpy(ims))
+    bench.dump_outputs(str(tmp_path), lsd, slot, n, max_lines)
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    assert np.array_equal(np.load(tmp_path / "counts.npy"), counts.astype(np.float64))
+    rows = np.clip(counts, 0, max_lines)
+    lines = np.load(tmp_path / "lines.npy")
+    assert lines.dtype == np.float64 and lines.shape == (rows.sum(), 13) and np.isfinite(lines).all()
+    img, got = bench.dumped_line_records(lines, lsd)
+    assert np.array_equal(img, np.repeat(np.arange(n), rows))
+    for f in bench.LINE_FIELDS:
+        assert np.array_equal(got[f], np.concatenate([rec[f][i, :rows[i]] for i in range(n)]), equal_nan=True), f
+    sel = np.load(tmp_path / "line_im_index.npy")
+    got = np.load(tmp_path / "line_im.npy")
+    assert got.dtype == np.float32 and len(sel) == 3 and np.array_equal(got, ims[sel.astype(int)].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "again"), lsd, slot, n, max_lines)         # the sample is fixed: the same images every run
+    assert np.array_equal(np.load(tmp_path / "again" / "line_im_index.npy"), sel)

@@ -22,7 +22,7 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import tile2048
+from conftest import libm_tie_image, tile2048
 
 pytestmark = pytest.mark.gpu
 
@@ -587,7 +587,7 @@ def test_bench_strong_scaling_split(maps, lsdmod, ctx):
     sys.path.insert(0, root)
     import bench
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--scaling", "strong", "--batch", "6", "--size", "1024",
-                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -598,6 +598,33 @@ def test_bench_strong_scaling_split(maps, lsdmod, ctx):
     assert j["dominant_kernel"]["cycles_per_image"]["max_over_mean"] >= 1.0 and len(j["dominant_kernel"]["cycles_per_image"]["bad_records"]) <= 1, j["dominant_kernel"]["cycles_per_image"]
     ldist = importlib.import_module("linesegmentdetector-slam_amd.dist")
     assert [ldist.shard_range(6, 4, r) for r in range(4)] == [(0, 2), (2, 3), (3, 5), (5, 6)]    # what each of 4 ranks would take
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_computed(maps, lsdmod, ctx, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line only, and --dump-outputs holds the last timed step's counts, line
+    records and a seeded sample of lineIm rasters: the same as run_batch gives on the same images."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "6", "--size", "1024", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "Mpix/s" and j["higher_is_better"] is True
+    assert "one_step_at_a_time" not in j and "cpu_baseline" not in j and "map1" not in j
+    lines, offs, ims = ctx.run_batch(bench.make_batch(maps, 6, 1024))
+    counts = np.load(tmp_path / "counts.npy")
+    got = np.load(tmp_path / "lines.npy")
+    assert counts.dtype == got.dtype == np.float64 and np.isfinite(got).all()
+    assert np.array_equal(counts, np.diff(offs)) and j["lines_per_step"] == len(got) == len(lines)
+    img, rec = bench.dumped_line_records(got, lsdmod)
+    assert np.array_equal(img, np.repeat(np.arange(6), np.diff(offs)))
+    assert_lines_close(rec, lines)
+    assert np.array_equal(rec["orient"], lines["orient"])
+    sel = np.load(tmp_path / "line_im_index.npy").astype(int)
+    got_ims = np.load(tmp_path / "line_im.npy")
+    assert got_ims.dtype == np.float32 and len(sel) == 6 and np.array_equal(got_ims, ims[sel].astype(np.float32))
 
 
 def test_cpp_adapter_runs(maps, tmp_path):
@@ -980,7 +1007,7 @@ def test_rccl_gather_runs_on_the_gpu(maps, lsdmod, ctx):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--batch", "6", "--size", "1024",
-           "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -1414,7 +1441,7 @@ def test_libm_tie_images_equal_the_correctly_rounded_restatement(name, lsdmod, c
     """ALL disagreements with the glibc-built oracle the random campaigns found (33 of 160 000 images, 2 of 3 900 large ones:
     tests/golden/make_libm_ties.py): on every one the HIP path is bit-identical to the same restatement built on correctly rounded
     sin / cos / atan2 / exp / log10 / pow -- usedMap, lineIm, line records, every seed's decision and NFA value."""
-    img = np.load(os.path.join(os.path.dirname(__file__), "golden", "libm_ties.npz"))[name]
+    img = libm_tie_image(name)
     kw = LIBM_TIES[name]["params"]
     ref = oracle.lsd(img.copy(), debug=True, _lib=oracle.lib_cr(), **kw)
     d = ref["dbg"]

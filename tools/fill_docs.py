@@ -24,7 +24,7 @@ if prev:
     except Exception as e:
         drv = "n/a (%r)" % e
 rows = [
-    ("source", "`%s` (`python3 bench.py`, kernel sources sha %s)" % (os.path.relpath(src, ROOT), j.get("source_sha"))),
+    ("source", "`%s` (`python3 bench.py --full`, kernel sources sha %s)" % (os.path.relpath(src, ROOT), j.get("source_sha"))),
     ("timed region", "%d steps in flight, %d-wave region stage, help %s, %d timed steps after %d warm-up steps" % (
         j["config"]["steps_in_flight"], j["config"]["region_waves_per_image"], "on" if j["config"].get("help_across_workgroups") else "off", j["steps"], j["warmup"])),
     ("**`value`**", "**%.1f Gpix/s, %.1f ms per step, %.2f M lines/s** (%d lines per step)" % (j["value"] / 1e3, j["ms_per_step"], j["lines_per_s"] / 1e6, j["lines_per_step"])),
