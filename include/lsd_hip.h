@@ -247,6 +247,76 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx *ctx, const lsd_polar *d_scans
                                           lsd_line *d_lines_out, int *d_n_lines, lsd_position *d_pts_out, int pts_cap, int *d_n_pts,
                                           double *d_lidar_pos, int *d_im_size, void *stream);
 
+/* --- FeatureAssociation: pose fusion, UKF update and log replay ----------------------------------- */
+/* Replaces myfa::FeatureAssociation (LSD/myFA.cpp:13-184) with myfa::ukf (:404-536), and the frame loop of the replay driver
+ * (LSD/main_on_windows.cpp:80-186).  Per frame: the pair list of :28-58 (scan lines of len >= 40 against map lines within 35 % of
+ * their length, in that loop order), four scored candidates per pair (lsd_scan_to_map_match), those with score < 3 kept in
+ * single-thread order and sorted stably by score, then one of three branches:
+ *   LSD_FA_RESET  nothing kept: x = (-1, -1, 0, ...), P = diag(100, 100, 100, 1, 1, 1, .1, .1, .1)                 (:62-83)
+ *   LSD_FA_FIRST  |lastPose.x + 1| < 1e-4: x = the input x with x[0..2] = the best candidate's pose, P unchanged        (:86-95)
+ *   LSD_FA_UKF    weighted mean of the kept poses (w = 1/score^2), then the 9-state unscented update                (:140-176)
+ * The arithmetic is the reference's in its statement order, without FMA; the Eigen calls are restated as Eigen's own algorithms
+ * (unblocked LLT, the 3x3 cofactor inverse, ascending sums) -- bitwise agreement with an Eigen build is NOT verified.
+ * Quirks kept: the sigma points take ROWS of L (:446), a kept score of 0 makes the state NaN, a P that is not positive definite is
+ * factored up to its first failing column, angles are averaged without wrapping. */
+typedef struct lsd_fa_state {
+    double x[9];     /* kalman_x */
+    double P[81];    /* kalman_P, column-major as Eigen stores it (kalman_P.data()) */
+} lsd_fa_state;
+enum { LSD_FA_RESET = 0, LSD_FA_FIRST = 1, LSD_FA_UKF = 2 };
+typedef struct lsd_fa_report {
+    lsd_position estimate;   /* poseEstimate: the fused pose (UKF), the best candidate (FIRST), (-1, -1, 0) (RESET) */
+    double score;            /* its score (1/sqrt(sum w / n), the candidate's, INFINITY) */
+    lsd_position scan_pose;  /* the ScanPose the frame used */
+    int n_pairs;             /* pairs scored (4 candidates each) */
+    int n_kept;              /* candidates with score < 3 */
+    int branch;              /* LSD_FA_* */
+    int llt;                 /* UKF branch: -1 if LLT(P) succeeded, else the first column it stopped at; -2 on the other branches */
+} lsd_fa_report;
+/* The driver's starting state (LSD/main_on_windows.cpp:80-93): x = (-1, -1, 0, ...), P = diag(100, 100, 100, 1, 1, 1, .1, .1, .1). */
+void lsd_fa_initial_state(lsd_fa_state *out);
+/* One frame from host buffers: the drop-in for myfa::FeatureAssociation(&FAInput).  The FAInput fields are the arguments:
+ * map_cache (rows x cols), map lines, scan lines, scanImPoint, lidarPose (rounded on the device as trans2FA does, :228-229),
+ * lastPose, ScanPose and the state in; the state out (FAOutput.kalman_x / kalman_P) and the report.  in and out may alias.
+ * Blocking. */
+int lsd_feature_association(lsd_ctx *ctx, const double *map_cache, int cols, int rows, const lsd_line *map_lines, int n_map,
+                            const lsd_line *scan_lines, int n_scan, const lsd_position *scan_im_points, int n_points,
+                            lsd_position lidar_pose, lsd_position last_pose, lsd_position scan_pose, const lsd_fa_state *in,
+                            lsd_fa_state *out, lsd_fa_report *report);
+/* The replay loop for n_seq independent sequences against ONE map, on the device, asynchronous on `stream` (no host
+ * synchronisation between frames; 3 launches per frame index).  Frame t of sequence s uses slot s * frames_pitch + t of the
+ * lsd_enqueue_feature_scan_batch_device outputs (d_lines at slot * LSD_RDP_MAX_LINES, d_pts at slot * pts_cap; at most 360
+ * lines and pts_cap points of a scan are used), for t < n_frames[s] (a HOST array: the sequences are ragged).  d_odom holds
+ * n_seq x (frames_pitch + 1) odometry rows: the reference's Odom vector of the sequence (Odom[0].x = 0, frame t uses rows t and
+ * t + 1).  Per frame: ScanPose from the odometry and the mean of the past angle offsets (:125-140), lastPose = the previous state's
+ * x[0..2] (the initial state's at t = 0), FeatureAssociation, then the offset bookkeeping of :170-180.  d_states / d_reports:
+ * n_seq x frames_pitch records (slots past a sequence's end are not written).  The context's workspace grows before the first
+ * launch when needed (one synchronisation).
+ * d_init: each sequence starts at the driver's FIRST frame (cnt_frame = 1): the past angle offsets start empty, so an initial state
+ * must be a reset one (x[0] = -1, e.g. lsd_fa_initial_state) -- resuming a sequence midway from a state with x[0] != -1 would take the
+ * mean of no offsets (0/0) as the reference would, and its ScanPose, hence the whole trajectory, becomes NaN.  Replay a sequence in
+ * one call (or from a reset state) instead.
+ * Pairs, candidates and the loop's bookkeeping live in the CONTEXT's workspace: like lsd_enqueue_batch_device, one context serves
+ * one stream at a time -- another FeatureAssociation call on the same context (any stream) must not start before this one has
+ * finished (synchronise the stream, or use one context per stream). */
+int lsd_enqueue_localize_device(lsd_ctx *ctx, const double *d_map_cache, int cols, int rows, const lsd_line *d_map_lines, int n_map,
+                                int n_seq, int frames_pitch, const int *n_frames, const lsd_line *d_lines, const int *d_n_lines,
+                                const lsd_position *d_pts, int pts_cap, const int *d_n_pts, const double *d_lidar_pos,
+                                const lsd_position *d_odom, double map_resol, const lsd_fa_state *d_init, lsd_fa_state *d_states,
+                                lsd_fa_report *d_reports, void *stream);
+/* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
+ * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
+ * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:
+ * n_frames records.  LSD_ERR_CAPACITY if a scan
+ * marks more than 8192 pixels or has more than 360 lines (the records are then computed from the stored part). */
+int lsd_localize(lsd_ctx *ctx, const double *map_cache, int cols, int rows, const lsd_line *map_lines, int n_map, const lsd_polar *scans,
+                 const int *lens, int n_frames, int stride, const lsd_position *odom, lsd_map_param map_param, const lsd_fa_state *init,
+                 lsd_fa_state *states, lsd_fa_report *reports);
+/* Test hook: the fusion kernel alone on a caller-given candidate list (n x {x, y, ang, score}, in single-thread order; n may
+ * be 0) with lastPose, ScanPose and the state in. */
+int lsd_debug_fa_fuse(lsd_ctx *ctx, const lsd_match_score *cands, int n, lsd_position last_pose, lsd_position scan_pose,
+                      const lsd_fa_state *in, lsd_fa_state *out, lsd_fa_report *report);
+
 /* --- wire format (SURVEY 8f "next" #3) ---------------------------------------------------------- */
 /* Replaces the cell loop of the ROS map callback (LSD/main_on_linux.cpp:108-124): nav_msgs/OccupancyGrid cells
  * (int8: -1 unknown, 0 free, 1..100 occupied) become the loader's map values (0 unknown, 255 free, 1 occupied), the
@@ -289,7 +359,8 @@ int lsd_set_cost_history(lsd_ctx *ctx, int on);
  * wavefront on one image; this lowers the budget (2 .. 0xFFFF0 grows) so that tests reach the path.  Results do not change. */
 int lsd_debug_set_stamp_budget(lsd_ctx *ctx, unsigned grows);
 /* Test / developer hook: a schedule setting of the region stage by name ("SOFT", "CLAIM", "FEED", "BIG", "EARLY", "WB", "GATE", "SHARE",
- * "UP", "DOWN", "REQUEUE", "XPOLL", "LINGER", "HELP", "POOL"; csrc/lsd_ctx.hip: kTunings), clamped to its range.  None changes a
+ * "UP", "DOWN", "REQUEUE", "XPOLL", "LINGER", "HELP", "POOL"; csrc/lsd_ctx.hip: kTunings), clamped to its range, or "FA_LDS": the number
+ * of kept candidates up to which FeatureAssociation sorts in LDS (0..1024, default 1024; beyond it, in global memory).  None changes a
  * result.  From the ENVIRONMENT the shipped library takes two settings only, when a context is created: LSD_REGION_HELP (as
  * lsd_set_region_help) and LSD_REGION_POOL (calls with at most that many images, 0..16, default 4, get helper-only workgroups). */
 int lsd_debug_set_tuning(lsd_ctx *ctx, const char *name, int value);

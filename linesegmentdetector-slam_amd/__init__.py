@@ -58,6 +58,13 @@ class lsd_position(C.Structure):  # == structPosition, LSD/baseFunc.h:46-50
 POS_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8")])
 SCORE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "f8")])   # lsd_match_score
 
+# FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
+FA_STATE_DTYPE = np.dtype([("x", "f8", (9,)), ("P", "f8", (81,))])
+FA_REPORT_DTYPE = np.dtype([("estimate", POS_DTYPE), ("score", "f8"), ("scan_pose", POS_DTYPE), ("n_pairs", "i4"), ("n_kept", "i4"),
+                            ("branch", "i4"), ("llt", "i4")])
+assert FA_STATE_DTYPE.itemsize == 720 and FA_REPORT_DTYPE.itemsize == 72
+FA_RESET, FA_FIRST, FA_UKF = range(3)
+
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -150,6 +157,16 @@ def load_library(path=None):
         L.lsd_last_region_cycles.restype = i; L.lsd_last_region_cycles.argtypes = [vp, i, vp]
     if hasattr(L, "lsd_last_sensitivity") or not os.environ.get("LSD_HIP_LIB"):
         L.lsd_last_sensitivity.restype = i; L.lsd_last_sensitivity.argtypes = [vp, i, vp]
+    if hasattr(L, "lsd_feature_association") or not os.environ.get("LSD_HIP_LIB"):
+        L.lsd_fa_initial_state.restype = None; L.lsd_fa_initial_state.argtypes = [vp]
+        L.lsd_feature_association.restype = i
+        L.lsd_feature_association.argtypes = [vp, vp, i, i, vp, i, vp, i, vp, i, lsd_position, lsd_position, lsd_position, vp, vp, vp]
+        L.lsd_enqueue_localize_device.restype = i
+        L.lsd_enqueue_localize_device.argtypes = [vp, vp, i, i, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, dbl, vp, vp, vp, vp]
+        L.lsd_localize.restype = i
+        L.lsd_localize.argtypes = [vp, vp, i, i, vp, i, vp, vp, i, i, vp, lsd_map_param, vp, vp, vp]
+        L.lsd_debug_fa_fuse.restype = i
+        L.lsd_debug_fa_fuse.argtypes = [vp, vp, i, lsd_position, lsd_position, vp, vp, vp]
     L.lsd_debug_calibrate.restype = i; L.lsd_debug_calibrate.argtypes = [vp, sz]
     L.lsd_debug_eval_math.restype = i; L.lsd_debug_eval_math.argtypes = [vp, i, vp, vp, vp, vp, sz]
     if path is None:
@@ -164,6 +181,7 @@ EXPORTED_SYMBOLS = ["lsd_create", "lsd_destroy", "lsd_strerror", "lsd_last_error
                     "lsd_enqueue_map_cache_device", "lsd_occupancy_to_map", "lsd_enqueue_occupancy_to_map_device",
                     "lsd_scan_to_map_match", "lsd_enqueue_scan_to_map_match_device",
                     "lsd_feature_scan_batch", "lsd_enqueue_feature_scan_batch_device",
+                    "lsd_fa_initial_state", "lsd_feature_association", "lsd_enqueue_localize_device", "lsd_localize", "lsd_debug_fa_fuse",
                     "lsd_shard_range", "lsd_gather_layout", "lsd_comm_from_rccl", "lsd_gather_lines", "lsd_gather_unpack"]
 
 
@@ -360,6 +378,65 @@ class Context:
         if st == LSD_ERR_CAPACITY:
             raise LsdError(st, self.L.lsd_strerror(st).decode(), partial=out)
         return out
+
+    # -- FeatureAssociation ------------------------------------------------------------------------
+    @staticmethod
+    def fa_initial_state():
+        """lsd_fa_initial_state: the replay driver's starting state (LSD/main_on_windows.cpp:80-93) as an FA_STATE_DTYPE record."""
+        st = np.zeros(1, FA_STATE_DTYPE)
+        load_library().lsd_fa_initial_state(st.ctypes.data)
+        return st[0]
+
+    def feature_association(self, map_cache, map_lines, scan_lines, scan_im_points, lidar_pose, last_pose, scan_pose, state):
+        """lsd_feature_association: one frame of myfa::FeatureAssociation.  state: FA_STATE_DTYPE record (or (x [9], P [9, 9]) with P
+        indexed P[i, j]).  Returns (state out, report) as FA_STATE_DTYPE / FA_REPORT_DTYPE records."""
+        mc = np.ascontiguousarray(map_cache, np.float64)
+        rows, cols = mc.shape
+        ml, sl = np.ascontiguousarray(map_lines, LINE_DTYPE), np.ascontiguousarray(scan_lines, LINE_DTYPE)
+        pts = np.ascontiguousarray(scan_im_points, np.float64).reshape(-1, 3)
+        st_in = fa_state(state)
+        st_out = np.zeros(1, FA_STATE_DTYPE); rep = np.zeros(1, FA_REPORT_DTYPE)
+        self._chk(self.L.lsd_feature_association(self.h, mc.ctypes.data, cols, rows, ml.ctypes.data, len(ml), sl.ctypes.data, len(sl),
+                                                 pts.ctypes.data, len(pts), _pos(lidar_pose), _pos(last_pose), _pos(scan_pose),
+                                                 st_in.ctypes.data, st_out.ctypes.data, rep.ctypes.data))
+        return st_out[0], rep[0]
+
+    def debug_fa_fuse(self, cands, last_pose, scan_pose, state):
+        """lsd_debug_fa_fuse: the fusion kernel on a candidate list float64 [n, 4] = (x, y, ang, score) in single-thread order."""
+        cd = np.ascontiguousarray(np.asarray(cands, np.float64).reshape(-1, 4))
+        st_in = fa_state(state)
+        st_out = np.zeros(1, FA_STATE_DTYPE); rep = np.zeros(1, FA_REPORT_DTYPE)
+        self._chk(self.L.lsd_debug_fa_fuse(self.h, cd.ctypes.data, len(cd), _pos(last_pose), _pos(scan_pose), st_in.ctypes.data,
+                                           st_out.ctypes.data, rep.ctypes.data))
+        return st_out[0], rep[0]
+
+    def localize(self, map_cache, map_lines, scans, lens, odom, map_param, init=None):
+        """lsd_localize: replays one log.  scans float64 [n, stride, 2] (finite readings first, lens[t] of them), odom float64
+        [n + 1, 3] (the reference's Odom vector, load_odom), map_param = (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY).
+        Returns (states FA_STATE_DTYPE [n], reports FA_REPORT_DTYPE [n])."""
+        mc = np.ascontiguousarray(map_cache, np.float64)
+        rows, cols = mc.shape
+        ml = np.ascontiguousarray(map_lines, LINE_DTYPE)
+        sc = np.ascontiguousarray(scans, np.float64)
+        n, stride = sc.shape[0], sc.shape[1]
+        ln = np.ascontiguousarray(lens, np.int32)
+        od = np.ascontiguousarray(odom, np.float64).reshape(-1, 3)
+        if len(od) != n + 1:
+            raise LsdError(LSD_ERR_INVALID, "odom must have one row more than there are frames")
+        mp = lsd_map_param(int(map_param[0]), int(map_param[1]), float(map_param[2]), float(map_param[3]), float(map_param[4]))
+        ini = None if init is None else fa_state(init)
+        states = np.zeros(n, FA_STATE_DTYPE); reps = np.zeros(n, FA_REPORT_DTYPE)
+        self._chk(self.L.lsd_localize(self.h, mc.ctypes.data, cols, rows, ml.ctypes.data, len(ml), sc.ctypes.data, ln.ctypes.data, n, stride,
+                                      od.ctypes.data, mp, None if ini is None else ini.ctypes.data, states.ctypes.data, reps.ctypes.data))
+        return states, reps
+
+    def enqueue_localize_device(self, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts,
+                                pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, d_states, d_reports, stream=None):
+        """lsd_enqueue_localize_device on device pointers; n_frames: host int sequence [n_seq]."""
+        nf = np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_device(self.h, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch,
+                                                            nf.ctypes.data, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom,
+                                                            float(map_resol), d_init, d_states, d_reports, stream))
 
     def occupancy_to_map(self, grid_i8):
         """lsd_occupancy_to_map on an int8 [rows, cols] OccupancyGrid; returns the uint8 map."""
@@ -580,6 +657,65 @@ def ScanToMapMatch(mapCache, mapLinesInfo, scanLinesInfo, scanImPoint, lidarPose
                                                       z_occ_max_dis, maxEstiDist).ravel()
     keep = sc[sc["score"] < 3]
     return keep[np.argsort(keep["score"], kind="stable")]
+
+
+def _pos(p):
+    return lsd_position(float(p[0]), float(p[1]), float(p[2]) if len(p) > 2 else 0.0)
+
+
+def fa_state(state):
+    """An FA_STATE_DTYPE array of one record from a record, or from (kalman_x [9], kalman_P [9, 9] indexed P[i, j])."""
+    if isinstance(state, np.void) or (isinstance(state, np.ndarray) and state.dtype == FA_STATE_DTYPE):
+        return np.ascontiguousarray(np.asarray(state, FA_STATE_DTYPE).reshape(1))
+    x, P = state
+    st = np.zeros(1, FA_STATE_DTYPE)
+    st["x"][0] = np.asarray(x, np.float64).reshape(9)
+    st["P"][0] = np.asarray(P, np.float64).reshape(9, 9).ravel(order="F")      # column-major, as Eigen stores it
+    return st
+
+
+def load_odom(path_or_rows):
+    """The replay driver's Odom vector (LSD/main_on_windows.cpp:51-61) from Odom.txt (or its rows float64 [n, 3]): the feof loop
+    appends one more row after the last line (the file ends in a newline; fscanf then leaves the row as it was -- taken here to
+    repeat the last row, an assumption: the reference leaves it uninitialised), and Odom[0].x = 0.  A log of n lidar frames
+    has n rows, so the vector has n + 1 and the last frame sees a zero odometry step."""
+    rows = np.loadtxt(path_or_rows).reshape(-1, 3) if isinstance(path_or_rows, str) else np.asarray(path_or_rows, np.float64).reshape(-1, 3)
+    od = np.concatenate([rows, rows[-1:]], 0)
+    od[0, 0] = 0.0
+    return od
+
+
+def lidar_frames(lidar):
+    """The driver's read loop (LSD/main_on_windows.cpp:104-123) on float64 [n, 360, 2] (range, angle) frames: readings with an
+    infinite range dropped.  Returns (scans [n, 360, 2] with the finite readings first, lens int32 [n])."""
+    lid = np.asarray(lidar, np.float64)
+    scans = np.zeros_like(lid)
+    lens = np.zeros(len(lid), np.int32)
+    for f in range(len(lid)):
+        keep = lid[f][lid[f, :, 0] != np.inf]
+        scans[f, :len(keep)] = keep
+        lens[f] = len(keep)
+    return scans, lens
+
+
+def FeatureAssociation(mapCache, mapLinesInfo, scanLinesInfo, scanImPoint, lidarPose, lastPose, kalman_x, kalman_P, ScanPose, ctx=None):
+    """myfa::FeatureAssociation (LSD/myFA.cpp:13) on the FAInput fields: returns (kalman_x [9], kalman_P [9, 9], report)."""
+    st, rep = (ctx or default_context()).feature_association(mapCache, mapLinesInfo, scanLinesInfo, scanImPoint, lidarPose, lastPose, ScanPose,
+                                                             (kalman_x, kalman_P))
+    return st["x"].copy(), st["P"].reshape(9, 9, order="F").copy(), rep
+
+
+def replay_log(map_u8, map_param, lidar, odom, ctx=None):
+    """The replay driver (LSD/main_on_windows.cpp:24-186) on the device: mapCache and the map lines of map_u8 (a copy: the LSD call
+    rewrites it), then FeatureScan and FeatureAssociation for every lidar frame.  lidar float64 [n, 360, 2] as in Lidar.txt, odom the
+    Odom vector (load_odom, n + 1 rows).  Returns (states FA_STATE_DTYPE [n], reports FA_REPORT_DTYPE [n]); the trajectory is
+    states["x"][:, :3]."""
+    cx = ctx or default_context()
+    m = np.ascontiguousarray(map_u8, np.uint8).copy()
+    mapCache = cx.map_cache(m, float(map_param[2]), z_occ_max_dis)
+    LSD = myLineSegmentDetector(m, m.shape[1], m.shape[0], lsd_sca, lsd_sig, lsd_angThre, lsd_denThre, pseBin, ctx=cx)
+    scans, lens = lidar_frames(lidar)
+    return cx.localize(mapCache, LSD.linesInfo, scans, lens, odom, map_param)
 
 
 def mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=None):

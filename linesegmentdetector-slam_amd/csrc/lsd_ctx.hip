@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -90,6 +91,13 @@ struct lsd_ctx {
     size_t oc_cap = 0;
     uint8_t* mt_buf = nullptr;                          // staging of the host scan-to-map matching entry point
     size_t mt_cap = 0;
+    // device FeatureAssociation (k_fa.hip): its per-sequence workspace, and the staging of its host entry points
+    uint8_t* fa_buf = nullptr;
+    size_t fa_cap = 0;
+    uint8_t* fh_buf = nullptr;
+    size_t fh_cap = 0;
+    std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
+    int fa_lds_bound = kFaLdsMax;                       // kept candidates sorted in LDS up to this many (kTunings "FA_LDS")
     // lsd_gather_lines: this rank's padded counts + offsets, and its slab of packed line records
     int32_t* ga_cnt = nullptr;
     lsd_line* ga_slab = nullptr;
@@ -378,6 +386,7 @@ static const Tuning kTunings[] = {
     {"LINGER", 1, 1 << 30, &lsd_ctx::tun_linger, false},   // looks (~27 us each) a helper takes for an image that asks before it gives its CU back
     {"GROUPS", -1, 1 << 20, &lsd_ctx::tun_groups, false},  // 8-wave region stage as persistent workgroups: -1 (default) as many as CUs when the batch has more images, 0 never, n that many
     {"STOP", 0, 1 << 30, &lsd_ctx::tun_stop, false},       // developer build of the kernel: the seed loop ends after this many seeds (probe experiment)
+    {"FA_LDS", 0, kFaLdsMax, &lsd_ctx::fa_lds_bound, false},   // FeatureAssociation: kept candidates up to which the sort runs in LDS (tests reach the global path)
 };
 
 extern "C" {
@@ -464,7 +473,7 @@ void lsd_destroy(lsd_ctx* c) {
     (void)hipDeviceSynchronize();
     void* ptrs[] = {c->gauss, c->mag, c->deg, c->sc, c->recs, c->recs_scaled, c->pw, c->epochmap, c->ord, c->spill, c->gcopy, c->stamps, c->seedidx, c->seedpos, c->tepoch, c->slist, c->pend, c->order, c->xq, c->sets, c->wmeta, c->rnum,
                     c->maxbits, c->nb, c->nseed, c->stats, c->seeds, c->h_in, c->h_lineim, c->h_lines, c->h_counts,
-                    c->d_taps, c->d_lgamma, c->d_ptab, c->d_centres, c->mc_claim, c->mc_fa, c->mc_fb, c->mc_ctl, c->mc_in, c->mc_out, c->oc_in, c->oc_out, c->mt_buf, c->ga_cnt, c->ga_slab};
+                    c->d_taps, c->d_lgamma, c->d_ptab, c->d_centres, c->mc_claim, c->mc_fa, c->mc_fb, c->mc_ctl, c->mc_in, c->mc_out, c->oc_in, c->oc_out, c->mt_buf, c->fa_buf, c->fh_buf, c->ga_cnt, c->ga_slab};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -1118,6 +1127,216 @@ int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, 
     HIPCHK(c, hipEventRecord(c->ga_ev, s));
     c->ga_ev_valid = true;
     c->last_stream = s;
+    return LSD_OK;
+}
+
+// --- device FeatureAssociation (k_fa.hip) ------------------------------------------------------------------------------
+// Carves the per-sequence workspace of n_seq sequences with pair_cap pairs each out of c->fa_buf (grown with one synchronisation).
+static int fa_workspace(lsd_ctx* c, int n_seq, int pair_cap, FaArgs& a) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t ns = (size_t)n_seq, pc = (size_t)pair_cap;
+    const size_t b_pairs = up(ns * pc * 2 * 4), b_cnt = up(ns * 4), b_cand = up(ns * pc * 16 * 8), b_scr = up(ns * pc * 8 * 4),
+                 b_ctl = up(ns * kFaCtl * 8), b_aux = up(ns * kFaAux * 8);
+    const size_t total = b_pairs + 3 * b_cnt + b_cand + b_scr + b_ctl + b_aux;
+    if (total > c->fa_cap) {
+        c->fa_cap = 0;
+        HIPCHK(c, hipDeviceSynchronize());
+        HIPCHK(c, re_alloc(&c->fa_buf, total));
+        c->fa_cap = total;
+    }
+    uint8_t* b = c->fa_buf;
+    a.pairs = reinterpret_cast<int*>(b); b += b_pairs;
+    a.n_pairs = reinterpret_cast<int*>(b); b += b_cnt;
+    a.n_cand = reinterpret_cast<int*>(b); b += b_cnt;
+    a.n_frames = reinterpret_cast<int*>(b); b += b_cnt;
+    a.cand = reinterpret_cast<double*>(b); b += b_cand;
+    a.scratch = reinterpret_cast<int*>(b); b += b_scr;
+    a.ctl = reinterpret_cast<double*>(b); b += b_ctl;
+    a.aux = reinterpret_cast<double*>(b);
+    a.pair_cap = pair_cap;
+    a.lds_bound = c->fa_lds_bound;
+    return LSD_OK;
+}
+
+// Staging of the host entry points: `count` regions of the given sizes in c->fh_buf.
+static int fa_staging(lsd_ctx* c, std::initializer_list<size_t> sizes, std::vector<uint8_t*>& out) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t total = 0;
+    for (size_t v : sizes) total += up(v > 0 ? v : 1);
+    if (total > c->fh_cap) {
+        c->fh_cap = 0;
+        HIPCHK(c, hipDeviceSynchronize());
+        HIPCHK(c, re_alloc(&c->fh_buf, total));
+        c->fh_cap = total;
+    }
+    uint8_t* b = c->fh_buf;
+    out.clear();
+    for (size_t v : sizes) { out.push_back(b); b += up(v > 0 ? v : 1); }
+    return LSD_OK;
+}
+
+void lsd_fa_initial_state(lsd_fa_state* o) {                    // LSD/main_on_windows.cpp:84-93
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->x[0] = -1; o->x[1] = -1;
+    const double d[9] = {100, 100, 100, 1, 1, 1, 0.1, 0.1, 0.1};
+    for (int i = 0; i < 9; i++) o->P[i * 10] = d[i];
+}
+
+int lsd_feature_association(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map,
+                            const lsd_line* scan_lines, int n_scan, const lsd_position* pts, int n_points, lsd_position lidar,
+                            lsd_position last, lsd_position sp, const lsd_fa_state* in, lsd_fa_state* out, lsd_fa_report* report) {
+    if (!c || !map_cache || cols <= 0 || rows <= 0 || n_map < 0 || n_scan < 0 || n_points < 0 || (n_map > 0 && !map_lines) ||
+        (n_scan > 0 && !scan_lines) || (n_points > 0 && !pts) || !in || !out || !report)
+        return LSD_ERR_INVALID;
+    if ((long long)n_map * n_scan > (1 << 26)) return LSD_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b_mc = (size_t)cols * rows * 8;
+    std::vector<uint8_t*> st;
+    int r = fa_staging(c, {b_mc, (size_t)n_map * sizeof(lsd_line), (size_t)n_scan * sizeof(lsd_line), (size_t)n_points * sizeof(lsd_position),
+                           sizeof(lsd_fa_state) * 2, sizeof(lsd_fa_report), 8 * 8}, st);
+    if (r != LSD_OK) return r;
+    FaArgs a{};
+    const int pair_cap = std::max(1, n_map * n_scan);
+    if ((r = fa_workspace(c, 1, pair_cap, a)) != LSD_OK) return r;
+    lsd_fa_state* d_st = reinterpret_cast<lsd_fa_state*>(st[4]);
+    double* d_sc = reinterpret_cast<double*>(st[6]);              // lidarPose (2), then lastPose + ScanPose (6)
+    const double sc[8] = {lidar.x, lidar.y, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(st[0], map_cache, b_mc, hipMemcpyHostToDevice, s));
+    if (n_map) HIPCHK(c, hipMemcpyAsync(st[1], map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    if (n_scan) HIPCHK(c, hipMemcpyAsync(st[2], scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    if (n_points) HIPCHK(c, hipMemcpyAsync(st[3], pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_sc, sc, sizeof(sc), hipMemcpyHostToDevice, s));
+    a.map_cache = reinterpret_cast<const double*>(st[0]); a.cols = cols; a.rows = rows;
+    a.map_lines = reinterpret_cast<const lsd_line*>(st[1]); a.n_map = n_map;
+    a.scan_lines = reinterpret_cast<const lsd_line*>(st[2]); a.n_lines = nullptr; a.n_scan_given = n_scan; a.line_pitch = std::max(n_scan, 1);
+    a.pts = reinterpret_cast<const double*>(st[3]); a.n_pts = nullptr; a.n_pts_given = n_points; a.pts_pitch = std::max(n_points, 1);
+    a.lidar_pos = d_sc; a.given = d_sc + 2;
+    a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0;
+    a.odom = nullptr; a.map_resol = 1;
+    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = reinterpret_cast<lsd_fa_report*>(st[5]);
+    launch_fa_frame(a, 1, true, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(report, st[5], sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_debug_fa_fuse(lsd_ctx* c, const lsd_match_score* cands, int n, lsd_position last, lsd_position sp, const lsd_fa_state* in,
+                      lsd_fa_state* out, lsd_fa_report* report) {
+    if (!c || n < 0 || (n > 0 && !cands) || !in || !out || !report) return LSD_ERR_INVALID;
+    if (n > (1 << 26)) return LSD_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint8_t*> st;
+    int r = fa_staging(c, {sizeof(lsd_fa_state) * 2, sizeof(lsd_fa_report)}, st);
+    if (r != LSD_OK) return r;
+    FaArgs a{};
+    if ((r = fa_workspace(c, 1, std::max(1, (n + 3) / 4), a)) != LSD_OK) return r;
+    hipStream_t s = c->stream;
+    lsd_fa_state* d_st = reinterpret_cast<lsd_fa_state*>(st[0]);
+    const double ctl[kFaCtl] = {0, 0, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
+    const int cnt[2] = {0, n};
+    if (n) HIPCHK(c, hipMemcpyAsync(a.cand, cands, (size_t)n * sizeof(lsd_match_score), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(a.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(a.n_pairs, &cnt[0], 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(a.n_cand, &cnt[1], 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
+    a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0; a.odom = nullptr;
+    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = reinterpret_cast<lsd_fa_report*>(st[1]);
+    launch_fa_frame(a, 1, false, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(report, st[1], sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LSD_OK;
+}
+
+int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
+                                int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
+                                const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
+                                const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
+                                lsd_fa_report* d_reports, void* stream) {
+    if (!c || !d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || n_seq <= 0 || frames_pitch <= 0 ||
+        !n_frames || !d_lines || !d_n_lines || pts_cap < 0 || (pts_cap > 0 && !d_pts) || !d_n_pts || !d_lidar_pos || !d_odom ||
+        !(map_resol > 0) || !d_init || !d_states || !d_reports)
+        return LSD_ERR_INVALID;
+    int max_frames = 0;
+    for (int i = 0; i < n_seq; i++) {
+        if (n_frames[i] < 0 || n_frames[i] > frames_pitch) return LSD_ERR_INVALID;
+        max_frames = std::max(max_frames, n_frames[i]);
+    }
+    if ((long long)n_map * LSD_RDP_MAX_LINES > (1 << 26)) return LSD_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    FaArgs a{};
+    const int r = fa_workspace(c, n_seq, std::max(1, n_map * LSD_RDP_MAX_LINES), a);
+    if (r != LSD_OK) return r;
+    hipStream_t s = (hipStream_t)stream;
+    c->fa_nf.assign(n_frames, n_frames + n_seq);
+    HIPCHK(c, hipMemcpyAsync(const_cast<int*>(a.n_frames), c->fa_nf.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
+    a.map_cache = d_map_cache; a.cols = cols; a.rows = rows; a.map_lines = d_map_lines; a.n_map = n_map;
+    a.scan_lines = d_lines; a.n_lines = d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
+    a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = d_n_pts; a.pts_pitch = pts_cap;
+    a.lidar_pos = d_lidar_pos; a.frames_pitch = frames_pitch; a.odom = d_odom; a.given = nullptr; a.map_resol = map_resol;
+    a.init = d_init; a.state_in = nullptr; a.states = d_states; a.reports = d_reports;
+    for (int t = 0; t < max_frames; t++) {
+        a.t = t;
+        launch_fa_frame(a, n_seq, true, s);
+    }
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,
+                 const int* lens, int n_frames, int stride, const lsd_position* odom, lsd_map_param mp, const lsd_fa_state* init,
+                 lsd_fa_state* states, lsd_fa_report* reports) {
+    if (!c || !map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !map_lines) || !scans || !lens || n_frames <= 0 ||
+        stride <= 0 || !odom || !states || !reports || !(mp.mapResol > 0))
+        return LSD_ERR_INVALID;
+    for (int i = 0; i < n_frames; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int pts_cap = 8192;
+    const size_t nf = (size_t)n_frames, b_mc = (size_t)cols * rows * 8;
+    std::vector<uint8_t*> st;
+    int r = fa_staging(c, {b_mc, (size_t)n_map * sizeof(lsd_line), nf * stride * sizeof(lsd_polar), nf * 4, (nf + 1) * sizeof(lsd_position),
+                           sizeof(lsd_fa_state), nf * LSD_RDP_MAX_LINES * sizeof(lsd_line), nf * 4, nf * pts_cap * sizeof(lsd_position), nf * 4,
+                           nf * 16, nf * 8, nf * sizeof(lsd_fa_state), nf * sizeof(lsd_fa_report)}, st);
+    if (r != LSD_OK) return r;
+    hipStream_t s = c->stream;
+    lsd_fa_state h_init;
+    if (init) h_init = *init;
+    else lsd_fa_initial_state(&h_init);
+    HIPCHK(c, hipMemcpyAsync(st[0], map_cache, b_mc, hipMemcpyHostToDevice, s));
+    if (n_map) HIPCHK(c, hipMemcpyAsync(st[1], map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(st[2], scans, nf * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(st[3], lens, nf * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(st[4], odom, (nf + 1) * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(st[5], &h_init, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
+    r = lsd_enqueue_feature_scan_batch_device(c, reinterpret_cast<const lsd_polar*>(st[2]), reinterpret_cast<const int*>(st[3]), n_frames, stride,
+                                              mp, 3, 0.08, 0.5, reinterpret_cast<lsd_line*>(st[6]), reinterpret_cast<int*>(st[7]),
+                                              reinterpret_cast<lsd_position*>(st[8]), pts_cap, reinterpret_cast<int*>(st[9]),
+                                              reinterpret_cast<double*>(st[10]), reinterpret_cast<int*>(st[11]), s);   // rdp defaults, baseFunc.h:70-72
+    if (r != LSD_OK) return r;
+    r = lsd_enqueue_localize_device(c, reinterpret_cast<const double*>(st[0]), cols, rows, reinterpret_cast<const lsd_line*>(st[1]), n_map, 1,
+                                    n_frames, &n_frames, reinterpret_cast<const lsd_line*>(st[6]), reinterpret_cast<const int*>(st[7]),
+                                    reinterpret_cast<const lsd_position*>(st[8]), pts_cap, reinterpret_cast<const int*>(st[9]),
+                                    reinterpret_cast<const double*>(st[10]), reinterpret_cast<const lsd_position*>(st[4]), mp.mapResol,
+                                    reinterpret_cast<const lsd_fa_state*>(st[5]), reinterpret_cast<lsd_fa_state*>(st[12]),
+                                    reinterpret_cast<lsd_fa_report*>(st[13]), s);
+    if (r != LSD_OK) return r;
+    std::vector<int> nl(nf), np(nf);
+    HIPCHK(c, hipMemcpyAsync(states, st[12], nf * sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(reports, st[13], nf * sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(nl.data(), st[7], nf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(np.data(), st[9], nf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (size_t i = 0; i < nf; i++)
+        if (nl[i] > LSD_RDP_MAX_LINES || np[i] > pts_cap) return LSD_ERR_CAPACITY;
     return LSD_OK;
 }
 

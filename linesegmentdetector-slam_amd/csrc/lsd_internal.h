@@ -148,6 +148,28 @@ void launch_rdp(const double* scans, const int* lens, int n, int stride, int ori
 int rdp_max_len();
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
+// Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
+// of the per-frame arrays; the workspace arrays are per sequence (pairs: pair_cap x 2 ints, cand: 4 pair_cap x 4 doubles, scratch:
+// 8 pair_cap ints, ctl: kFaCtl doubles {lidarPose x, y, lastPose x, y, ang, ScanPose x, y, ang}, aux: kFaAux doubles {sum of
+// angRotate, its length, is_offset}).
+constexpr int kFaCtl = 8, kFaAux = 4, kFaLdsMax = 1024;
+struct FaArgs {
+    const double* map_cache; int cols, rows;
+    const lsd_line* map_lines; int n_map;
+    const lsd_line* scan_lines; const int* n_lines; int n_scan_given; int line_pitch;   // n_lines null: n_scan_given lines
+    const double* pts; const int* n_pts; int n_pts_given; int pts_pitch;                // n_pts null: n_pts_given points
+    const double* lidar_pos;                                                            // 2 per slot
+    const int* n_frames; int frames_pitch, t;                                           // n_frames null: every sequence has frame t
+    const lsd_position* odom;                                                           // (frames_pitch + 1) rows per sequence, or null
+    const double* given;                                                                // null, or 6 per sequence: lastPose, ScanPose
+    double map_resol;
+    const lsd_fa_state* init; const lsd_fa_state* state_in;                             // state_in (not null): the fuse kernel's input
+    lsd_fa_state* states; lsd_fa_report* reports;
+    int* pairs; int* n_pairs; int* n_cand; int pair_cap;
+    double* cand; int* scratch; double* ctl; double* aux;
+    int lds_bound;
+};
+void launch_fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t s);   // prepare = false: the fuse kernel alone (ctl, cand, counts given)
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and
