@@ -294,8 +294,8 @@ int lsd_feature_association(lsd_ctx *ctx, const double *map_cache, int cols, int
  * launch when needed (one synchronisation).
  * d_init: each sequence starts at the driver's FIRST frame (cnt_frame = 1): the past angle offsets start empty, so an initial state
  * must be a reset one (x[0] = -1, e.g. lsd_fa_initial_state) -- resuming a sequence midway from a state with x[0] != -1 would take the
- * mean of no offsets (0/0) as the reference would, and its ScanPose, hence the whole trajectory, becomes NaN.  Replay a sequence in
- * one call (or from a reset state) instead.
+ * mean of no offsets (0/0) as the reference would, and its ScanPose, hence the whole trajectory, becomes NaN.  To continue a sequence
+ * across calls (a live robot, a checkpoint), use lsd_enqueue_localize_resume_device, which carries the loop's variables.
  * Pairs, candidates and the loop's bookkeeping live in the CONTEXT's workspace: like lsd_enqueue_batch_device, one context serves
  * one stream at a time -- another FeatureAssociation call on the same context (any stream) must not start before this one has
  * finished (synchronise the stream, or use one context per stream). */
@@ -304,6 +304,37 @@ int lsd_enqueue_localize_device(lsd_ctx *ctx, const double *d_map_cache, int col
                                 const lsd_position *d_pts, int pts_cap, const int *d_n_pts, const double *d_lidar_pos,
                                 const lsd_position *d_odom, double map_resol, const lsd_fa_state *d_init, lsd_fa_state *d_states,
                                 lsd_fa_report *d_reports, void *stream);
+/* The replay driver's loop variables after some number of frames (LSD/main_on_windows.cpp:80-180), per sequence: what
+ * lsd_enqueue_localize_resume_device reads before a sequence's first frame of a call and writes after its last.  Plain bytes: a caller
+ * may copy it, keep it on the host, write it to disk and resume later. */
+typedef struct lsd_fa_carry {
+    lsd_fa_state state;   /* kalman_x / kalman_P after the last frame; lastPose = state.x[0..2] */
+    lsd_position odom;    /* Odom[cnt_frame]: the odometry row the last frame used as its new row (initially Odom[0]) */
+    double ang_sum;       /* the sum of angRotate, accumulated from 0 in push order (the reference's theta loop re-sums it so) */
+    double ang_count;     /* angRotate.size() */
+    int32_t frames;       /* cnt_frame: frames consumed so far (0: the next frame is the driver's first) */
+    int32_t is_offset;    /* isOffset (0 / 1) */
+} lsd_fa_carry;           /* 768 bytes */
+/* A carry before the driver's first frame: state (NULL: lsd_fa_initial_state), odom0 = Odom[0] (the driver sets Odom[0].x = 0),
+ * empty angle offsets, frames = 0, is_offset = 0. */
+void lsd_fa_carry_init(lsd_fa_carry *out, const lsd_fa_state *state, lsd_position odom0);
+/* The replay loop of lsd_enqueue_localize_device, resumable: each sequence continues from its carry d_carry[s] (device, n_seq records,
+ * read and updated in place).  Frame t (t < n_frames[s], a HOST array) of sequence s uses slot s * frames_pitch + t of the FeatureScan
+ * outputs and of d_states / d_reports, as there.  d_odom holds n_seq x frames_pitch rows: row t is the NEW odometry row of frame t,
+ * Odom[cnt_frame]; Odom[cnt_frame - 1] is the carry's odom at t = 0, else row t - 1.  The carry supplies lastPose and the previous
+ * state, the running sum and count of angRotate and isOffset, and cnt_frame (so the cnt_frame == 1 test of :176 is the sequence's
+ * global first frame, not the call's).  After the call d_carry[s] holds the driver's variables after that sequence's last frame; a
+ * sequence with n_frames[s] == 0 keeps its carry bit for bit and none of its state or report slots is written.  Splitting a sequence
+ * into calls at any frame gives the same states and reports, bit for bit, as one call from lsd_fa_carry_init.
+ * Like lsd_enqueue_localize_device: pairs and candidates live in the CONTEXT's workspace, so one context serves one stream at a time
+ * (synchronise before another FeatureAssociation call on the same context, or use one context per stream); the workspace grows
+ * before the first launch when needed (one synchronisation).  LSD_ERR_INVALID for a null carry, n_frames[s] outside 0..frames_pitch
+ * and the argument errors of lsd_enqueue_localize_device. */
+int lsd_enqueue_localize_resume_device(lsd_ctx *ctx, const double *d_map_cache, int cols, int rows, const lsd_line *d_map_lines,
+                                       int n_map, int n_seq, int frames_pitch, const int *n_frames, const lsd_line *d_lines,
+                                       const int *d_n_lines, const lsd_position *d_pts, int pts_cap, const int *d_n_pts,
+                                       const double *d_lidar_pos, const lsd_position *d_odom, double map_resol, lsd_fa_carry *d_carry,
+                                       lsd_fa_state *d_states, lsd_fa_report *d_reports, void *stream);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:

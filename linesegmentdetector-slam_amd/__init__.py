@@ -64,6 +64,10 @@ FA_REPORT_DTYPE = np.dtype([("estimate", POS_DTYPE), ("score", "f8"), ("scan_pos
                             ("branch", "i4"), ("llt", "i4")])
 assert FA_STATE_DTYPE.itemsize == 720 and FA_REPORT_DTYPE.itemsize == 72
 FA_RESET, FA_FIRST, FA_UKF = range(3)
+# lsd_fa_carry: the replay loop's variables between calls of lsd_enqueue_localize_resume_device (plain bytes: copy, keep, save, restore)
+FA_CARRY_DTYPE = np.dtype([("state", FA_STATE_DTYPE), ("odom", POS_DTYPE), ("ang_sum", "f8"), ("ang_count", "f8"), ("frames", "i4"),
+                           ("is_offset", "i4")])
+assert FA_CARRY_DTYPE.itemsize == 768
 
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
@@ -167,6 +171,10 @@ def load_library(path=None):
         L.lsd_localize.argtypes = [vp, vp, i, i, vp, i, vp, vp, i, i, vp, lsd_map_param, vp, vp, vp]
         L.lsd_debug_fa_fuse.restype = i
         L.lsd_debug_fa_fuse.argtypes = [vp, vp, i, lsd_position, lsd_position, vp, vp, vp]
+    if hasattr(L, "lsd_enqueue_localize_resume_device") or not os.environ.get("LSD_HIP_LIB"):
+        L.lsd_fa_carry_init.restype = None; L.lsd_fa_carry_init.argtypes = [vp, vp, lsd_position]
+        L.lsd_enqueue_localize_resume_device.restype = i
+        L.lsd_enqueue_localize_resume_device.argtypes = [vp, vp, i, i, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, dbl, vp, vp, vp, vp]
     L.lsd_debug_calibrate.restype = i; L.lsd_debug_calibrate.argtypes = [vp, sz]
     L.lsd_debug_eval_math.restype = i; L.lsd_debug_eval_math.argtypes = [vp, i, vp, vp, vp, vp, sz]
     if path is None:
@@ -182,6 +190,7 @@ EXPORTED_SYMBOLS = ["lsd_create", "lsd_destroy", "lsd_strerror", "lsd_last_error
                     "lsd_scan_to_map_match", "lsd_enqueue_scan_to_map_match_device",
                     "lsd_feature_scan_batch", "lsd_enqueue_feature_scan_batch_device",
                     "lsd_fa_initial_state", "lsd_feature_association", "lsd_enqueue_localize_device", "lsd_localize", "lsd_debug_fa_fuse",
+                    "lsd_fa_carry_init", "lsd_enqueue_localize_resume_device",
                     "lsd_shard_range", "lsd_gather_layout", "lsd_comm_from_rccl", "lsd_gather_lines", "lsd_gather_unpack"]
 
 
@@ -437,6 +446,24 @@ class Context:
         return self._chk(self.L.lsd_enqueue_localize_device(self.h, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch,
                                                             nf.ctypes.data, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom,
                                                             float(map_resol), d_init, d_states, d_reports, stream))
+
+    @staticmethod
+    def fa_carry_init(state=None, odom0=(0.0, 0.0, 0.0)):
+        """lsd_fa_carry_init: the loop's variables before the driver's first frame as an FA_CARRY_DTYPE record: state (None: the
+        initial state), Odom[0] = odom0 (the driver's Odom[0].x is 0), no angle offsets, frames = 0."""
+        c = np.zeros(1, FA_CARRY_DTYPE)
+        st = None if state is None else fa_state(state)
+        load_library().lsd_fa_carry_init(c.ctypes.data, None if st is None else st.ctypes.data, _pos(odom0))
+        return c[0]
+
+    def enqueue_localize_resume_device(self, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
+                                       d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_carry, d_states, d_reports, stream=None):
+        """lsd_enqueue_localize_resume_device on device pointers; n_frames: host int sequence [n_seq]; d_odom: n_seq x frames_pitch NEW
+        odometry rows; d_carry: n_seq FA_CARRY_DTYPE records, read and updated in place."""
+        nf = np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_resume_device(self.h, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch,
+                                                                   nf.ctypes.data, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos,
+                                                                   d_odom, float(map_resol), d_carry, d_states, d_reports, stream))
 
     def occupancy_to_map(self, grid_i8):
         """lsd_occupancy_to_map on an int8 [rows, cols] OccupancyGrid; returns the uint8 map."""
@@ -716,6 +743,134 @@ def replay_log(map_u8, map_param, lidar, odom, ctx=None):
     LSD = myLineSegmentDetector(m, m.shape[1], m.shape[0], lsd_sca, lsd_sig, lsd_angThre, lsd_denThre, pseBin, ctx=cx)
     scans, lens = lidar_frames(lidar)
     return cx.localize(mapCache, LSD.linesInfo, scans, lens, odom, map_param)
+
+
+def lidar_frames_batch(lidar):
+    """lidar_frames on float64 [..., 360, 2] frames at once (the same rule and the same output, vectorised)."""
+    lid = np.asarray(lidar, np.float64)
+    keep = lid[..., 0] != np.inf
+    order = np.argsort(~keep, axis=-1, kind="stable")                        # the finite readings first, in their order
+    scans = np.take_along_axis(lid, order[..., None], axis=-2)
+    lens = keep.sum(-1).astype(np.int32)
+    scans[np.arange(lid.shape[-2]) >= lens[..., None]] = 0.0
+    return scans, lens
+
+
+class Localizer:
+    """The laser side of the ROS node (laserCallback, LSD/main_on_linux.cpp:48-90) for n_robots robots against one map, with the replay
+    driver's frame loop (LSD/main_on_windows.cpp:80-180) carried from call to call: each step() advances every robot by its frames of the
+    tick (FeatureScan, FeatureAssociation, the UKF and the angle bookkeeping on the device, one stream), and the result is the same, bit for
+    bit, as one lsd_localize call over each robot's whole log.  The map (its cache and lines), the robots' carries (FA_CARRY_DTYPE) and the
+    FeatureScan staging live on the device (torch).  Like the context it uses, a Localizer serves one thread at a time."""
+
+    def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
+        import torch
+        self.ctx = ctx or default_context()
+        self.map_param = tuple(float(v) for v in map_param)
+        self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
+        self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._cap = 0
+        self.set_map(map_cache, map_lines)
+        self.reset(range(self.n_robots), odom0)
+
+    @classmethod
+    def from_occupancy_grid(cls, data, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None):
+        """A Localizer on the map mapCallback makes of an OccupancyGrid (map_param from the map metadata, mapParamCallback :92-99)."""
+        _, mapCache, LSD = mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=ctx)
+        return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx)
+
+    def set_map(self, map_cache, map_lines, map_param=None):
+        """A new map (mapCallback); the robots keep their carries."""
+        import torch
+        mc = map_cache if isinstance(map_cache, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map_cache, np.float64))
+        self._mc = mc.to(device="cuda", dtype=torch.float64).contiguous()
+        self._rows, self._cols = self._mc.shape
+        ml = np.ascontiguousarray(map_lines, LINE_DTYPE)
+        self._n_map = len(ml)
+        self._ml = torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()).cuda() if len(ml) else torch.zeros(80, dtype=torch.uint8, device="cuda")
+        if map_param is not None:
+            self.map_param = tuple(float(v) for v in map_param)
+
+    def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
+        """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot)."""
+        import torch
+        idx = [int(r) for r in robots]
+        if not idx:
+            return
+        o = np.broadcast_to(np.asarray(odom0, np.float64).reshape(-1, 3), (len(idx), 3))
+        rec = np.stack([Context.fa_carry_init(state, o[i]) for i in range(len(idx))])
+        self._carry.view(self.n_robots, -1)[torch.tensor(idx, device="cuda")] = torch.from_numpy(rec.view(np.uint8).reshape(len(idx), -1)).cuda()
+
+    @property
+    def carries(self):
+        """The robots' carries, FA_CARRY_DTYPE [n_robots] on the host (a checkpoint)."""
+        return self._carry.cpu().numpy().view(FA_CARRY_DTYPE).copy()
+
+    @carries.setter
+    def carries(self, rec):
+        import torch
+        rec = np.ascontiguousarray(rec, FA_CARRY_DTYPE).reshape(-1)
+        if len(rec) != self.n_robots:
+            raise LsdError(LSD_ERR_INVALID, "one carry per robot")
+        self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
+
+    # per frame slot: the tick's inputs (one upload) scans 360 x 2 doubles, the odometry row, the length; its outputs (one read-back) the
+    # state, the report, FeatureScan's line and pixel counts
+    _IN_B, _OUT_B = 5760 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
+
+    def _staging(self, n):
+        import torch
+        if n <= self._cap:
+            return
+        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
+        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B, torch.uint8)
+        self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
+        self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
+        self._cap = n
+
+    def step(self, lidar, odom, n_frames=None):
+        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does),
+        odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  n_frames: frames per robot this tick
+        (default k each; a robot with 0 is left untouched).  Returns (states FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots
+        past a robot's n_frames are zero.  Raises LsdError(LSD_ERR_CAPACITY) with (states, reports) in `partial` if a scan marks more than
+        pts_cap pixels or has more than 360 lines (the records are then computed from the stored part), as lsd_localize does."""
+        import torch
+        lid = np.asarray(lidar, np.float64)
+        S, k = lid.shape[0], lid.shape[1]
+        if S != self.n_robots or lid.shape[2:] != (360, 2) or k < 1:
+            raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
+        od = np.ascontiguousarray(odom, np.float64).reshape(S, k, 3)
+        nf = np.full(S, k, np.int32) if n_frames is None else np.ascontiguousarray(n_frames, np.int32).reshape(S)
+        if (nf < 0).any() or (nf > k).any():
+            raise LsdError(LSD_ERR_INVALID, "n_frames outside 0..k")
+        scans, lens = lidar_frames_batch(lid)
+        lens[np.arange(k)[None, :] >= nf[:, None]] = 0                       # slots past a robot's frames: nothing to scan
+        n = S * k
+        self._staging(n)
+        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
+        host_in = np.concatenate([scans.reshape(-1).view(np.uint8), od.reshape(-1).view(np.uint8), lens.reshape(-1).view(np.uint8)])
+        self._in[:n * self._IN_B].copy_(torch.from_numpy(host_in))
+        self._out[:b_st + b_rp].zero_()
+        d_sc, d_out = self._in.data_ptr(), self._out.data_ptr()
+        d_od, d_ln = d_sc + n * 5760, d_sc + n * 5784
+        d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
+        d_np = d_nl + 4 * n
+        cx, stream = self.ctx, torch.cuda.current_stream().cuda_stream
+        mp = self.map_param
+        mpar = lsd_map_param(int(mp[0]), int(mp[1]), mp[2], mp[3], mp[4])
+        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, mpar, rdp_leastPoint, rdp_threLine, rdp_leastDist,
+                                                           self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np,
+                                                           self._lp.data_ptr(), self._sz.data_ptr(), stream))
+        cx.enqueue_localize_resume_device(self._mc.data_ptr(), self._cols, self._rows, self._ml.data_ptr(), self._n_map, S, k, nf,
+                                          self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od,
+                                          mp[2], self._carry.data_ptr(), d_st, d_rp, stream)
+        out = self._out[:n * self._OUT_B].cpu().numpy()                      # the tick's one synchronisation
+        states = out[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
+        reports = out[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
+        counts = out[b_st + b_rp:].view(np.int32).reshape(2, n)
+        if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
+            raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
+        return states, reports
 
 
 def mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=None):

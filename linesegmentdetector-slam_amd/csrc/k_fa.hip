@@ -7,7 +7,7 @@
 //   k_fa_match    one lane per candidate, a grid-stride loop over a small grid; reads the pair count from the device (match_dev.h)
 //   k_fa_fuse     one workgroup per sequence: ordered compaction of score < 3, stable sort on (score, candidate index), the
 //                 weighted mean on one lane, the UKF with one lane per matrix entry and sequential sums, state + report + the
-//                 frame loop's angle bookkeeping
+//                 frame loop's angle bookkeeping (and, in the resumable loop, the carry after a sequence's last frame)
 // Arithmetic order (the build has -ffp-contract=off): plain ascending sums from 0 for every dot product; LLT as Eigen's unblocked
 // algorithm (size < 32); Xdiv * diag(Wc) rounded entry by entry before the product with Xdiv^T; the 3x3 inverse as Eigen's
 // compute_inverse_size3 (cyclic cofactors, det = (c00 m00 + c10 m10) + c20 m20, inv(j, i) = cof(i, j) / det as a product with
@@ -39,9 +39,37 @@ __device__ __forceinline__ int fa_block_scan(bool flag, int* s_w, int& total) {
 
 __device__ __forceinline__ double fa_atand(double v) { return atan_g(v) * 180.0 / kPi; }    // baseFunc.cpp:14-16
 
-// previous state of sequence s at frame t: the initial state at t = 0
+// previous state of sequence s at frame t: the initial state (the carry's) at t = 0
 __device__ __forceinline__ const lsd_fa_state* fa_prev(const FaArgs& a, int s) {
-    return a.t == 0 ? a.init + s : a.states + (size_t)s * a.frames_pitch + a.t - 1;
+    if (a.t == 0) return a.carry ? &a.carry[s].state : a.init + s;
+    return a.states + (size_t)s * a.frames_pitch + a.t - 1;
+}
+
+// Odom[cnt_frame - 1] and Odom[cnt_frame] of frame t
+__device__ __forceinline__ void fa_odom(const FaArgs& a, int s, lsd_position& o0, lsd_position& o1) {
+    if (a.carry) {
+        const lsd_position* r = a.odom + (size_t)s * a.frames_pitch;
+        o1 = r[a.t];
+        o0 = a.t == 0 ? a.carry[s].odom : r[a.t - 1];
+    } else {
+        const lsd_position* r = a.odom + (size_t)s * (a.frames_pitch + 1);
+        o0 = r[a.t];
+        o1 = r[a.t + 1];
+    }
+}
+
+// the loop's bookkeeping before frame t: the sum and length of angRotate, isOffset, and cnt_frame - 1 (empty before the first frame)
+struct FaBook { double sum, cnt; bool offset; int frame; };
+__device__ __forceinline__ FaBook fa_book(const FaArgs& a, int s) {
+    if (a.t > 0) {
+        const double* aux = a.aux + (size_t)s * kFaAux;
+        return {aux[0], aux[1], aux[2] != 0, (int)aux[3]};
+    }
+    if (a.carry) {
+        const lsd_fa_carry& c = a.carry[s];
+        return {c.ang_sum, c.ang_count, c.is_offset != 0, c.frames};
+    }
+    return {0.0, 0.0, false, 0};
 }
 
 __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
@@ -65,10 +93,10 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
             ctl[2] = prev->x[0]; ctl[3] = prev->x[1]; ctl[4] = prev->x[2];      // lastPose = the last state's x[0..2] (:169-171)
             double spx = 0, spy = 0, spa = 0;
             if (!(fabs(prev->x[0] + 1) < 0.0001)) {                // :125-140
-                const double* aux = a.aux + (size_t)s * kFaAux;
-                const double sum = a.t == 0 ? 0.0 : aux[0], cnt = a.t == 0 ? 0.0 : aux[1];
-                const double theta = sum / cnt;                    // the mean of angRotate (0/0 if it is empty)
-                const lsd_position o1 = a.odom[(size_t)s * (a.frames_pitch + 1) + a.t + 1], o0 = a.odom[(size_t)s * (a.frames_pitch + 1) + a.t];
+                const FaBook bk = fa_book(a, s);
+                const double theta = bk.sum / bk.cnt;              // the mean of angRotate (0/0 if it is empty)
+                lsd_position o0, o1;
+                fa_odom(a, s, o0, o1);
                 const double tx = (o1.x - o0.x) / a.map_resol, ty = (o1.y - o0.y) / a.map_resol, ta = fa_atand(o1.ang - o0.ang);
                 double sd, cd;
                 sincos_g(deg2rad_ref(theta), sd, cd);
@@ -338,17 +366,34 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_fuse(FaArgs a) {
     }
     // 5. the frame loop's angle bookkeeping (main_on_windows.cpp:172-180)
     if (!a.odom) return;
-    __syncthreads();                                               // out->x[2] was written by lane 2
+    __syncthreads();                                               // out->x[2] was written by lane 2; every read of `in` is done
+    const bool last = a.carry && a.t == a.n_frames[s] - 1;         // the resumable loop: write the loop's variables back to the carry
+    lsd_fa_carry* cy = last ? a.carry + s : nullptr;               // (at t = 0, `in` IS the carry's state: written only past the barrier)
     if (tid == 0) {
         double* aux = a.aux + (size_t)s * kFaAux;
-        double sum = a.t == 0 ? 0.0 : aux[0], cnt = a.t == 0 ? 0.0 : aux[1];
-        bool offset = a.t == 0 ? false : aux[2] != 0;
-        double angDiff = out->x[2] - fa_atand(a.odom[(size_t)s * (a.frames_pitch + 1) + a.t + 1].ang);
-        if (fabs(angDiff) > 90 && a.t == 0) offset = true;        // cnt_frame == 1
+        const FaBook bk = fa_book(a, s);
+        lsd_position o0, o1;
+        fa_odom(a, s, o0, o1);
+        bool offset = bk.offset;
+        double angDiff = out->x[2] - fa_atand(o1.ang);
+        if (fabs(angDiff) > 90 && bk.frame == 0) offset = true;   // cnt_frame == 1
         if (offset && angDiff < 0) angDiff += 360;
-        aux[0] = sum + angDiff;                                    // angRotate.push_back, summed from 0 in push order by the next frame
-        aux[1] = cnt + 1;
+        const double sum = bk.sum + angDiff, cnt = bk.cnt + 1;     // angRotate.push_back, summed from 0 in push order by the next frame
+        aux[0] = sum;
+        aux[1] = cnt;
         aux[2] = offset ? 1.0 : 0.0;
+        aux[3] = (double)(bk.frame + 1);
+        if (cy) {
+            cy->odom = o1;
+            cy->ang_sum = sum;
+            cy->ang_count = cnt;
+            cy->frames = bk.frame + 1;
+            cy->is_offset = offset ? 1 : 0;
+        }
+    }
+    if (cy) {
+        if (tid < 9) cy->state.x[tid] = out->x[tid];
+        if (tid < 81) cy->state.P[tid] = out->P[tid];
     }
 }
 

@@ -6,6 +6,7 @@
 // the thresholds (myLSD.cpp:148-149, :207-209) and two small lookup tables (log-gamma of integers,
 // logs of p = aliPro/2^k) that the kernels index instead of evaluating libm on the device.
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1255,14 +1256,27 @@ int lsd_debug_fa_fuse(lsd_ctx* c, const lsd_match_score* cands, int n, lsd_posit
     return LSD_OK;
 }
 
-int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
-                                int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
-                                const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
-                                const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
-                                lsd_fa_report* d_reports, void* stream) {
+static_assert(sizeof(lsd_fa_carry) == 768 && offsetof(lsd_fa_carry, odom) == 720 && offsetof(lsd_fa_carry, ang_sum) == 744 &&
+              offsetof(lsd_fa_carry, ang_count) == 752 && offsetof(lsd_fa_carry, frames) == 760 && offsetof(lsd_fa_carry, is_offset) == 764,
+              "lsd_fa_carry is plain bytes with the layout the Python mirror (FA_CARRY_DTYPE) assumes");
+
+void lsd_fa_carry_init(lsd_fa_carry* o, const lsd_fa_state* state, lsd_position odom0) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    if (state) o->state = *state;
+    else lsd_fa_initial_state(&o->state);
+    o->odom = odom0;
+}
+
+// The replay loop of both device entry points: d_init (lsd_enqueue_localize_device, odometry n_seq x (frames_pitch + 1)) or d_carry
+// (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.
+static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map, int n_seq,
+                           int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
+                           int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
+                           const lsd_fa_state* d_init, lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!c || !d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || n_seq <= 0 || frames_pitch <= 0 ||
         !n_frames || !d_lines || !d_n_lines || pts_cap < 0 || (pts_cap > 0 && !d_pts) || !d_n_pts || !d_lidar_pos || !d_odom ||
-        !(map_resol > 0) || !d_init || !d_states || !d_reports)
+        !(map_resol > 0) || !(d_init || d_carry) || !d_states || !d_reports)
         return LSD_ERR_INVALID;
     int max_frames = 0;
     for (int i = 0; i < n_seq; i++) {
@@ -1281,7 +1295,7 @@ int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols,
     a.scan_lines = d_lines; a.n_lines = d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
     a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = d_n_pts; a.pts_pitch = pts_cap;
     a.lidar_pos = d_lidar_pos; a.frames_pitch = frames_pitch; a.odom = d_odom; a.given = nullptr; a.map_resol = map_resol;
-    a.init = d_init; a.state_in = nullptr; a.states = d_states; a.reports = d_reports;
+    a.init = d_init; a.carry = d_carry; a.state_in = nullptr; a.states = d_states; a.reports = d_reports;
     for (int t = 0; t < max_frames; t++) {
         a.t = t;
         launch_fa_frame(a, n_seq, true, s);
@@ -1289,6 +1303,26 @@ int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols,
     HIPCHK(c, hipGetLastError());
     c->last_stream = s;
     return LSD_OK;
+}
+
+int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
+                                int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
+                                const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
+                                const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
+                                lsd_fa_report* d_reports, void* stream) {
+    if (!d_init) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+                           d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
+}
+
+int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
+                                       int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
+                                       const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
+                                       const lsd_position* d_odom, double map_resol, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
+                                       lsd_fa_report* d_reports, void* stream) {
+    if (!d_carry) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+                           d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
 }
 
 int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,

@@ -151,7 +151,10 @@ void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
 // of the per-frame arrays; the workspace arrays are per sequence (pairs: pair_cap x 2 ints, cand: 4 pair_cap x 4 doubles, scratch:
 // 8 pair_cap ints, ctl: kFaCtl doubles {lidarPose x, y, lastPose x, y, ang, ScanPose x, y, ang}, aux: kFaAux doubles {sum of
-// angRotate, its length, is_offset}).
+// angRotate, its length, is_offset, frames consumed}).
+// carry (not null): the resumable loop (lsd_enqueue_localize_resume_device).  The previous state, the bookkeeping and Odom[cnt_frame - 1]
+// of frame 0 come from carry[s]; odom then holds frames_pitch NEW rows per sequence (frame t: Odom[cnt_frame] = row t), and the fuse
+// kernel of a sequence's last frame writes the loop's variables back to carry[s].
 constexpr int kFaCtl = 8, kFaAux = 4, kFaLdsMax = 1024;
 struct FaArgs {
     const double* map_cache; int cols, rows;
@@ -161,6 +164,7 @@ struct FaArgs {
     const double* lidar_pos;                                                            // 2 per slot
     const int* n_frames; int frames_pitch, t;                                           // n_frames null: every sequence has frame t
     const lsd_position* odom;                                                           // (frames_pitch + 1) rows per sequence, or null
+    lsd_fa_carry* carry;                                                                // null, or n_seq carries (odom: frames_pitch rows)
     const double* given;                                                                // null, or 6 per sequence: lastPose, ScanPose
     double map_resol;
     const lsd_fa_state* init; const lsd_fa_state* state_in;                             // state_in (not null): the fuse kernel's input
