@@ -247,6 +247,28 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx *ctx, const lsd_polar *d_scans
                                           lsd_line *d_lines_out, int *d_n_lines, lsd_position *d_pts_out, int pts_cap, int *d_n_pts,
                                           double *d_lidar_pos, int *d_im_size, void *stream);
 
+/* --- Scan ingestion: the drivers' read loop on the device ------------------------------------------ */
+/* Replaces the loop in front of FeatureScan that drops the readings with an infinite range and packs the rest to the front of
+ * lidarPointPolar[] (the file driver, LSD/main_on_windows.cpp:104-123; laserCallback, LSD/main_on_linux.cpp:53-66), for a BATCH of
+ * raw scans resident on the device: one launch (k_ingest.hip), asynchronous on `stream`, no workspace, no synchronisation.  It writes
+ * exactly what lsd_enqueue_feature_scan_batch_device reads: d_scans (n_scans x stride readings: the kept ones first, in beam order,
+ * then EVERY slot from d_lens[i] to stride as +0.0 / +0.0) and d_lens (n_scans ints).  1 <= n_beams <= stride <= 1024.
+ *   d_raw    n_scans x n_beams (range, angle) pairs, the file driver's layout (Lidar.txt).  A reading is kept iff `range != INFINITY`
+ *            as the reference evaluates it (:115): -inf and NaN are KEPT, only +inf is dropped.
+ *   d_take   optional (NULL: every scan is taken), one int per scan: where it is 0 the scan has d_lens[i] = 0 and an all-zero row.
+ * d_raw and d_scans must not overlap (in-place is not supported) and must be 16-byte aligned (every hipMalloc'ed or torch base is).
+ * LSD_ERR_INVALID on a null or non-positive argument, n_beams > stride or a misaligned pointer; LSD_ERR_UNSUPPORTED on stride > 1024. */
+int lsd_enqueue_scan_ingest_device(lsd_ctx *ctx, const lsd_polar *d_raw, int n_scans, int n_beams, const int *d_take,
+                                   lsd_polar *d_scans, int *d_lens, int stride, void *stream);
+/* The same from sensor_msgs/LaserScan fields: d_ranges (n_scans x n_beams floats) and d_angle_min_inc (n_scans x 2 floats:
+ * angle_min, angle_increment of each message).  Kept iff `ranges[i] != INFINITY` in float (:57); range = (double)ranges[i];
+ * angle = (double)(angle_min + i * angle_increment) as the callback writes it on float fields (:60): the product and the sum are each
+ * rounded to SINGLE precision, never fused.
+ * NOT reproduced: laserCallback stores a finite reading at lidarPointPolar[i], not [len_lp], and then hands the first len_lp entries to
+ * FeatureScan, so with any infinite range it reads stale entries of earlier messages.  The file driver packs, and so do both entries. */
+int lsd_enqueue_laserscan_ingest_device(lsd_ctx *ctx, const float *d_ranges, const float *d_angle_min_inc, int n_scans, int n_beams,
+                                        const int *d_take, lsd_polar *d_scans, int *d_lens, int stride, void *stream);
+
 /* --- FeatureAssociation: pose fusion, UKF update and log replay ----------------------------------- */
 /* Replaces myfa::FeatureAssociation (LSD/myFA.cpp:13-184) with myfa::ukf (:404-536), and the frame loop of the replay driver
  * (LSD/main_on_windows.cpp:80-186).  Per frame: the pair list of :28-58 (scan lines of len >= 40 against map lines within 35 % of

@@ -175,6 +175,11 @@ def load_library(path=None):
         L.lsd_fa_carry_init.restype = None; L.lsd_fa_carry_init.argtypes = [vp, vp, lsd_position]
         L.lsd_enqueue_localize_resume_device.restype = i
         L.lsd_enqueue_localize_resume_device.argtypes = [vp, vp, i, i, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, dbl, vp, vp, vp, vp]
+    if hasattr(L, "lsd_enqueue_scan_ingest_device") or not os.environ.get("LSD_HIP_LIB"):
+        L.lsd_enqueue_scan_ingest_device.restype = i
+        L.lsd_enqueue_scan_ingest_device.argtypes = [vp, vp, i, i, vp, vp, vp, i, vp]
+        L.lsd_enqueue_laserscan_ingest_device.restype = i
+        L.lsd_enqueue_laserscan_ingest_device.argtypes = [vp, vp, vp, i, i, vp, vp, vp, i, vp]
     L.lsd_debug_calibrate.restype = i; L.lsd_debug_calibrate.argtypes = [vp, sz]
     L.lsd_debug_eval_math.restype = i; L.lsd_debug_eval_math.argtypes = [vp, i, vp, vp, vp, vp, sz]
     if path is None:
@@ -191,6 +196,7 @@ EXPORTED_SYMBOLS = ["lsd_create", "lsd_destroy", "lsd_strerror", "lsd_last_error
                     "lsd_feature_scan_batch", "lsd_enqueue_feature_scan_batch_device",
                     "lsd_fa_initial_state", "lsd_feature_association", "lsd_enqueue_localize_device", "lsd_localize", "lsd_debug_fa_fuse",
                     "lsd_fa_carry_init", "lsd_enqueue_localize_resume_device",
+                    "lsd_enqueue_scan_ingest_device", "lsd_enqueue_laserscan_ingest_device",
                     "lsd_shard_range", "lsd_gather_layout", "lsd_comm_from_rccl", "lsd_gather_lines", "lsd_gather_unpack"]
 
 
@@ -387,6 +393,18 @@ class Context:
         if st == LSD_ERR_CAPACITY:
             raise LsdError(st, self.L.lsd_strerror(st).decode(), partial=out)
         return out
+
+    def enqueue_scan_ingest_device(self, d_raw, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream=None):
+        """lsd_enqueue_scan_ingest_device on device pointers: n_scans x n_beams raw (range, angle) pairs -> d_scans [n_scans, stride, 2]
+        (the readings whose range is not +inf first, the rest +0.0) and d_lens; d_take: None, or one int per scan (0: lens 0, row zeroed)."""
+        return self._chk(self.L.lsd_enqueue_scan_ingest_device(self.h, d_raw, int(n_scans), int(n_beams), d_take, d_scans, d_lens, int(stride),
+                                                               stream))
+
+    def enqueue_laserscan_ingest_device(self, d_ranges, d_angle_min_inc, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream=None):
+        """lsd_enqueue_laserscan_ingest_device on device pointers: float32 ranges [n_scans, n_beams] and (angle_min, angle_increment)
+        float32 [n_scans, 2] of sensor_msgs/LaserScan messages; the outputs as enqueue_scan_ingest_device."""
+        return self._chk(self.L.lsd_enqueue_laserscan_ingest_device(self.h, d_ranges, d_angle_min_inc, int(n_scans), int(n_beams), d_take,
+                                                                    d_scans, d_lens, int(stride), stream))
 
     # -- FeatureAssociation ------------------------------------------------------------------------
     @staticmethod
@@ -814,8 +832,9 @@ class Localizer:
             raise LsdError(LSD_ERR_INVALID, "one carry per robot")
         self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
 
-    # per frame slot: the tick's inputs (one upload) scans 360 x 2 doubles, the odometry row, the length; its outputs (one read-back) the
-    # state, the report, FeatureScan's line and pixel counts
+    # per frame slot: the tick's inputs (one upload) the RAW scan (360 x 2 doubles, or less: the LaserScan floats), the odometry row, the
+    # take flag; the scan as FeatureScan reads it (k_ingest's output) and its length; its outputs (one read-back) the state, the report,
+    # FeatureScan's line and pixel counts
     _IN_B, _OUT_B = 5760 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
 
     def _staging(self, n):
@@ -824,38 +843,32 @@ class Localizer:
             return
         z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
         self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B, torch.uint8)
+        self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
         self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
         self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
         self._cap = n
 
-    def step(self, lidar, odom, n_frames=None):
-        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does),
-        odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  n_frames: frames per robot this tick
-        (default k each; a robot with 0 is left untouched).  Returns (states FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots
-        past a robot's n_frames are zero.  Raises LsdError(LSD_ERR_CAPACITY) with (states, reports) in `partial` if a scan marks more than
-        pts_cap pixels or has more than 360 lines (the records are then computed from the stored part), as lsd_localize does."""
-        import torch
-        lid = np.asarray(lidar, np.float64)
-        S, k = lid.shape[0], lid.shape[1]
-        if S != self.n_robots or lid.shape[2:] != (360, 2) or k < 1:
-            raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
-        od = np.ascontiguousarray(odom, np.float64).reshape(S, k, 3)
+    def _n_frames(self, n_frames, S, k):
         nf = np.full(S, k, np.int32) if n_frames is None else np.ascontiguousarray(n_frames, np.int32).reshape(S)
         if (nf < 0).any() or (nf > k).any():
             raise LsdError(LSD_ERR_INVALID, "n_frames outside 0..k")
-        scans, lens = lidar_frames_batch(lid)
-        lens[np.arange(k)[None, :] >= nf[:, None]] = 0                       # slots past a robot's frames: nothing to scan
+        return nf
+
+    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
+        """The tick on the current torch stream, every input on the device: ingest, FeatureScan, the resume entry.  Returns the byte
+        sizes of the states and the reports in self._out."""
+        import torch
         n = S * k
-        self._staging(n)
         b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
-        host_in = np.concatenate([scans.reshape(-1).view(np.uint8), od.reshape(-1).view(np.uint8), lens.reshape(-1).view(np.uint8)])
-        self._in[:n * self._IN_B].copy_(torch.from_numpy(host_in))
         self._out[:b_st + b_rp].zero_()
-        d_sc, d_out = self._in.data_ptr(), self._out.data_ptr()
-        d_od, d_ln = d_sc + n * 5760, d_sc + n * 5784
+        d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
         d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
         d_np = d_nl + 4 * n
         cx, stream = self.ctx, torch.cuda.current_stream().cuda_stream
+        if d_raw is not None:
+            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
+        else:
+            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
         mp = self.map_param
         mpar = lsd_map_param(int(mp[0]), int(mp[1]), mp[2], mp[3], mp[4])
         cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, mpar, rdp_leastPoint, rdp_threLine, rdp_leastDist,
@@ -864,6 +877,104 @@ class Localizer:
         cx.enqueue_localize_resume_device(self._mc.data_ptr(), self._cols, self._rows, self._ml.data_ptr(), self._n_map, S, k, nf,
                                           self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od,
                                           mp[2], self._carry.data_ptr(), d_st, d_rp, stream)
+        return b_st, b_rp
+
+    def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
+        """step() for a caller whose scans are on the device, without an upload, a read-back or a synchronisation: everything is enqueued
+        on the current torch stream.  Either lidar, a CUDA float64 tensor [S, k, 360, 2] of raw (range, angle) frames, or ranges, a CUDA
+        float32 tensor [S, k, B <= 360] with angle_min_inc CUDA float32 [S, k, 2] (sensor_msgs/LaserScan: ranges[], angle_min,
+        angle_increment; the angle of beam i is angle_min + i * angle_increment in single precision, as laserCallback computes it).
+        Readings whose range is +inf are dropped on the device (-inf and NaN are kept, as the reference's `!= INFINITY` keeps them).
+        odom: CUDA float64 [S, k, 3]; n_frames: as in step(), a HOST int array (when given, its take flags are one small asynchronous
+        upload).  Returns CUDA tensors (states uint8 [S, k, 720], reports uint8 [S, k, 72], counts int32 [2, S * k]): views of the
+        Localizer's own staging, valid until the next step*() call and, after the caller's synchronisation, readable as FA_STATE_DTYPE /
+        FA_REPORT_DTYPE records (`.cpu().numpy().view(FA_STATE_DTYPE)`); counts are FeatureScan's line and pixel counts per slot, for the
+        caller's own capacity check (more than 360 resp. pts_cap: the records are computed from the stored part).  Once the staging and the
+        context's workspace have their size (the first call, or a larger S * k) nothing here waits for the device."""
+        import torch
+        if (lidar is None) == (ranges is None):
+            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
+        src = lidar if ranges is None else ranges
+        want = torch.float64 if ranges is None else torch.float32
+        tensors = [("lidar" if ranges is None else "ranges", src, want), ("odom", odom, torch.float64)]
+        if ranges is not None:
+            tensors.append(("angle_min_inc", angle_min_inc, torch.float32))
+        for name, t, dt in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+                raise LsdError(LSD_ERR_INVALID, "%s must be a CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
+        S = self.n_robots
+        k = src.shape[1] if src.dim() >= 2 else 0
+        if ranges is None:
+            if tuple(src.shape) != (S, k, 360, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
+            n_beams = 360
+        else:
+            n_beams = src.shape[2] if src.dim() == 3 else 0
+            if tuple(src.shape) != (S, k, n_beams) or k < 1 or not 1 <= n_beams <= 360:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            if tuple(angle_min_inc.shape) != (S, k, 2):
+                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
+        if tuple(odom.shape) != (S, k, 3):
+            raise LsdError(LSD_ERR_INVALID, "odom must be [n_robots, k, 3]")
+        nf = self._n_frames(n_frames, S, k)
+        self._staging(S * k)
+        take = None
+        if n_frames is not None:
+            # pinned, so the copy does not wait for the stream; torch's host allocator keeps the block until the copy has run
+            take = torch.from_numpy((np.arange(k)[None, :] < nf[:, None]).astype(np.int32)).pin_memory().to("cuda", non_blocking=True)
+        src, od = src.contiguous(), odom.contiguous()
+        ami = None if ranges is None else angle_min_inc.contiguous()
+        self._held = (src, od, ami, take)                                    # the launches read them: alive until the next tick
+        b_st, b_rp = self._enqueue(S, k, nf, src.data_ptr() if ranges is None else None, None if ranges is None else src.data_ptr(),
+                                   None if ami is None else ami.data_ptr(), n_beams, None if take is None else take.data_ptr(), od.data_ptr())
+        n = S * k
+        return (self._out[:b_st].view(S, k, -1), self._out[b_st:b_st + b_rp].view(S, k, -1),
+                self._out[b_st + b_rp:n * self._OUT_B].view(torch.int32).view(2, n))
+
+    def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
+        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does,
+        on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  Instead of
+        lidar: ranges float32 [S, k, B <= 360] and angle_min_inc float32 [S, k, 2], the fields of sensor_msgs/LaserScan messages (see
+        step_device).  n_frames: frames per robot this tick (default k each; a robot with 0 is left untouched).  Returns (states
+        FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots past a robot's n_frames are zero.  Raises LsdError(LSD_ERR_CAPACITY)
+        with (states, reports) in `partial` if a scan marks more than pts_cap pixels or has more than 360 lines (the records are then
+        computed from the stored part), as lsd_localize does.  One upload (the raw frames, the odometry, the take flags), the device
+        tick of step_device, one read-back."""
+        import torch
+        if (lidar is None) == (ranges is None):
+            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
+        if ranges is None:
+            src = np.asarray(lidar, np.float64)
+            S, k = src.shape[0], src.shape[1]
+            if S != self.n_robots or src.shape[2:] != (360, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
+            n_beams = 360
+        else:
+            src = np.asarray(ranges, np.float32)
+            if src.ndim != 3 or src.shape[0] != self.n_robots or src.shape[1] < 1 or not 1 <= src.shape[2] <= 360:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            S, k, n_beams = src.shape
+            ami = np.asarray(angle_min_inc, np.float32)
+            if ami.shape != (S, k, 2):
+                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
+        od = np.ascontiguousarray(odom, np.float64).reshape(S, k, 3)
+        nf = self._n_frames(n_frames, S, k)
+        take = (np.arange(k)[None, :] < nf[:, None]).astype(np.int32)        # slots past a robot's frames: nothing to scan
+        n = S * k
+        self._staging(n)
+        b = lambda a: a.reshape(-1).view(np.uint8)
+        if ranges is None:                                                   # the frames (16-byte pairs) first, as they always were
+            host_in = np.concatenate([b(src), b(od), b(take)])
+            d_src = self._in.data_ptr()
+            d_od, d_ami = d_src + n * 5760, None
+        else:                                                                # the doubles first, then the floats
+            host_in = np.concatenate([b(od), b(src), b(ami), b(take)])
+            d_od = self._in.data_ptr()
+            d_src = d_od + n * 24
+            d_ami = d_src + src.nbytes
+        d_take = self._in.data_ptr() + len(host_in) - 4 * n
+        self._in[:len(host_in)].copy_(torch.from_numpy(host_in))
+        b_st, b_rp = self._enqueue(S, k, nf, d_src if ranges is None else None, None if ranges is None else d_src, d_ami, n_beams, d_take, d_od)
         out = self._out[:n * self._OUT_B].cpu().numpy()                      # the tick's one synchronisation
         states = out[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
         reports = out[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)

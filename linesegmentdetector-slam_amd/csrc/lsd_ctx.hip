@@ -1045,6 +1045,35 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, 
     return LSD_OK;
 }
 
+// the two ingest entries: the checks they share, then one launch of k_ingest
+static int enqueue_ingest(lsd_ctx* c, const lsd_polar* d_raw, const float* d_ranges, const float* d_min_inc, int n_scans, int n_beams,
+                          const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
+    if (!c || n_scans <= 0 || n_beams <= 0 || stride <= 0 || !d_scans || !d_lens || n_beams > stride) return LSD_ERR_INVALID;
+    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_scans)) & 15) {        // the kernel moves a pair in one 16-byte access
+        c->err = "scan ingest: d_raw and d_scans must be 16-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    launch_ingest(d_raw, d_ranges, d_min_inc, n_scans, n_beams, d_take, d_scans, d_lens, stride, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_enqueue_scan_ingest_device(lsd_ctx* c, const lsd_polar* d_raw, int n_scans, int n_beams, const int* d_take, lsd_polar* d_scans,
+                                   int* d_lens, int stride, void* stream) {
+    if (!d_raw) return LSD_ERR_INVALID;
+    return enqueue_ingest(c, d_raw, nullptr, nullptr, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream);
+}
+
+int lsd_enqueue_laserscan_ingest_device(lsd_ctx* c, const float* d_ranges, const float* d_angle_min_inc, int n_scans, int n_beams,
+                                        const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
+    if (!d_ranges || !d_angle_min_inc) return LSD_ERR_INVALID;
+    return enqueue_ingest(c, nullptr, d_ranges, d_angle_min_inc, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream);
+}
+
 int lsd_feature_scan_batch(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp,
                            int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                            lsd_position* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size) {

@@ -146,6 +146,9 @@ void launch_rdp(const double* scans, const int* lens, int n, int stride, int ori
                 double mapOriY, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                 double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
 int rdp_max_len();
+// the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
+void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
+                   int* lens, int stride, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t

@@ -3,9 +3,16 @@
 tests/golden/, to set beside tools/localize_probe.py's one-call replay.
 
 S robots (S = 1, 19, 256 by default) step one frame per call for TICKS ticks, robot s on the log from frame (7 s) mod (99 - TICKS), as
-localize_probe.py staggers its sequences.  A tick is timed whole, from a warm Localizer: the host's infinite-range filter and the uploads,
-FeatureScan of the S scans, the three FeatureAssociation launches, and the read-back of the tick's states and reports (one
-synchronisation).  One JSON line per S.  Usage: tools/stream_probe.py [--robots 1,19,256] [--ticks 60] [--warm 3]"""
+localize_probe.py staggers its sequences.  A tick is timed whole, from a warm Localizer:
+  --input host       (default) Localizer.step from host arrays: the upload of the raw frames, the ingest launch (k_ingest: the
+                     infinite-range filter), FeatureScan of the S scans, the three FeatureAssociation launches, and the read-back of the
+                     tick's states and reports (one synchronisation);
+  --input device     Localizer.step_device from (range, angle) pairs already on the device, then the caller's synchronisation: no upload,
+                     no read-back (the frames of a tick are gathered on the device before the clock starts);
+  --input laserscan  the same from float32 ranges and (angle_min, angle_increment) per message.
+us_host_filter_median is the host's infinite-range filter (lidar_frames_batch) on the tick's frames, measured beside the tick: the cost
+Localizer.step contained before the filter moved onto the device.  One JSON line per S.
+Usage: tools/stream_probe.py [--robots 1,19,256] [--ticks 60] [--warm 3] [--input host|device|laserscan]"""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -21,6 +28,7 @@ def main():
     ap.add_argument("--robots", default="1,19,256")
     ap.add_argument("--ticks", type=int, default=60)
     ap.add_argument("--warm", type=int, default=3)
+    ap.add_argument("--input", choices=("host", "device", "laserscan"), default="host")
     args = ap.parse_args()
     m, mp, lid, odom = fr.load_log("data")
     ctx = lsd.Context(0)
@@ -32,23 +40,39 @@ def main():
         od0 = odom[starts].copy(); od0[:, 0] = 0.0                       # the driver's Odom[0].x = 0
         loc = lsd.Localizer(mc, ml, mp, S, odom0=od0, ctx=ctx)
         frame = lambda t: (lid[starts + t][:, None], odom[starts + t + 1][:, None])
+        if args.input != "host":
+            d_lid, d_od, d_starts = torch.from_numpy(lid).cuda(), torch.from_numpy(odom).cuda(), torch.from_numpy(starts).cuda()
+            d_rg = d_lid[..., 0].float().contiguous()
+            d_ami = torch.tensor([-3.12414, 0.0174533], dtype=torch.float32, device="cuda").expand(S, 1, 2).contiguous()
+
+        def tick(t, a):
+            if args.input == "host":
+                return loc.step(*a)[1]["n_kept"], None
+            od = d_od[d_starts + t + 1][:, None]
+            src = dict(lidar=d_lid[d_starts + t][:, None]) if args.input == "device" else dict(ranges=d_rg[d_starts + t][:, None], angle_min_inc=d_ami)
+            torch.cuda.synchronize()                                     # the tick's inputs are on the device
+            t0 = time.perf_counter()
+            out = loc.step_device(odom=od, **src)
+            torch.cuda.synchronize()                                     # the caller's own
+            dt = time.perf_counter() - t0
+            return out[1].cpu().numpy().reshape(-1).view(lsd.FA_REPORT_DTYPE)["n_kept"], dt
         for t in range(args.warm):                                       # warm: staging and workspace sized, code loaded
-            loc.step(*frame(t))
+            tick(t, frame(t))
         loc.reset(range(S), odom0=od0)
         torch.cuda.synchronize()
         ts, tf, kept = [], [], []
         for t in range(T):
             a = frame(t)
             t0 = time.perf_counter()
-            st, rp = loc.step(*a)
-            ts.append(time.perf_counter() - t0)
-            kept.append(rp["n_kept"])
+            k, dt = tick(t, a)
+            ts.append(time.perf_counter() - t0 if dt is None else dt)
+            kept.append(k)
             t0 = time.perf_counter()
-            lsd.lidar_frames_batch(a[0])                                 # the host's share: the infinite-range filter alone
+            lsd.lidar_frames_batch(a[0])                                 # the host's infinite-range filter alone (no longer part of the tick)
             tf.append(time.perf_counter() - t0)
         ts, tf = np.array(ts) * 1e6, np.array(tf) * 1e6
         kept = np.concatenate(kept)
-        print(json.dumps(dict(robots=S, ticks=T, map_lines=len(ml), us_per_tick_median=float(np.median(ts)), us_per_tick_min=float(ts.min()),
+        print(json.dumps(dict(robots=S, input=args.input, ticks=T, map_lines=len(ml), us_per_tick_median=float(np.median(ts)), us_per_tick_min=float(ts.min()),
                               us_per_tick_p90=float(np.percentile(ts, 90)),
                               us_host_filter_median=float(np.median(tf)), frames_per_s=S / float(np.median(ts)) * 1e6,
                               kept_mean=float(kept.mean()), kept_max=int(kept.max()))), flush=True)
