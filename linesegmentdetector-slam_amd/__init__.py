@@ -87,6 +87,65 @@ class LsdError(RuntimeError):
         self.partial = partial
 
 
+# ---- the C ABI (include/lsd_hip.h), listed once: name -> (restype, argtypes) --------------------------------------------------
+_vp, _i, _sz, _dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_double
+_pi, _ppar = C.POINTER(C.c_int), C.POINTER(lsd_params)
+_localize_args = [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp]
+_ABI = {
+    "lsd_create": (_i, [C.POINTER(_vp), _i]),
+    "lsd_destroy": (None, [_vp]),
+    "lsd_strerror": (C.c_char_p, [_i]),
+    "lsd_last_error": (C.c_char_p, [_vp]),
+    "lsd_default_params": (None, [_ppar]),
+    "lsd_abi_version": (_i, []),
+    "lsd_free": (None, [_vp]),
+    "lsd_run": (_i, [_vp, _vp, _i, _i, _sz, _ppar, _vp, _sz, C.POINTER(_vp), _pi]),
+    "lsd_run_batch": (_i, [_vp, _vp, _i, _i, _i, _ppar, _vp, C.POINTER(_vp), _pi]),
+    "lsd_enqueue_batch_device": (_i, [_vp, _vp, _i, _i, _i, _ppar, C.c_uint, _vp, _vp, _i, _vp, _vp]),
+    "lsd_reserve": (_i, [_vp, _i, _i, _i]),
+    "lsd_synchronize": (_i, [_vp]),
+    "lsd_scaled_size": (None, [_i, _i, _dbl, _pi, _pi]),
+    "lsd_set_stop_after": (_i, [_vp, _i]),
+    "lsd_set_trace": (_i, [_vp, _i]),
+    "lsd_set_region_waves": (_i, [_vp, _i]),
+    "lsd_set_region_help": (_i, [_vp, _i]),
+    "lsd_debug_set_stamp_budget": (_i, [_vp, C.c_uint]),
+    "lsd_set_cost_history": (_i, [_vp, _i]),
+    "lsd_debug_set_tuning": (_i, [_vp, C.c_char_p, _i]),
+    "lsd_set_host_max_lines": (_i, [_vp, _i]),
+    "lsd_debug_fetch": (_i, [_vp, _i, _i, _vp, _sz]),
+    "lsd_last_timings": (_i, [_vp, C.POINTER(C.c_float)]),
+    "lsd_map_cache": (_i, [_vp, _vp, _i, _i, _sz, _dbl, _dbl, _vp]),
+    "lsd_enqueue_map_cache_device": (_i, [_vp, _vp, _i, _i, _i, _dbl, _dbl, _vp, _vp]),
+    "lsd_occupancy_to_map": (_i, [_vp, _vp, _i, _i, _vp, _sz]),
+    "lsd_enqueue_occupancy_to_map_device": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "lsd_scan_to_map_match": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, lsd_position, lsd_position, _vp, _i, _dbl, _dbl, _vp]),
+    "lsd_enqueue_scan_to_map_match_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, lsd_position, lsd_position, _vp, _i, _dbl, _dbl, _vp, _vp]),
+    "lsd_feature_scan_batch": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lsd_enqueue_feature_scan_batch_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "lsd_shard_range": (None, [_i, _i, _i, _pi, _pi]),
+    "lsd_gather_layout": (_i, [_i, _i, _pi, C.POINTER(_sz)]),
+    "lsd_comm_from_rccl": (_i, [_vp, C.POINTER(lsd_comm)]),
+    "lsd_gather_lines": (_i, [_vp, C.POINTER(lsd_comm), _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "lsd_gather_unpack": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz]),
+    "lsd_shard_balanced": (_i, [_vp, _i, _i, _vp]),
+    "lsd_last_region_cycles": (_i, [_vp, _i, _vp]),
+    "lsd_last_sensitivity": (_i, [_vp, _i, _vp]),
+    "lsd_fa_initial_state": (None, [_vp]),
+    "lsd_feature_association": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, lsd_position, lsd_position, lsd_position, _vp, _vp, _vp]),
+    "lsd_enqueue_localize_device": (_i, _localize_args),
+    "lsd_localize": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, lsd_map_param, _vp, _vp, _vp]),
+    "lsd_debug_fa_fuse": (_i, [_vp, _vp, _i, lsd_position, lsd_position, _vp, _vp, _vp]),
+    "lsd_fa_carry_init": (None, [_vp, _vp, lsd_position]),
+    "lsd_enqueue_localize_resume_device": (_i, _localize_args),
+    "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "lsd_enqueue_laserscan_ingest_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "lsd_debug_calibrate": (_i, [_vp, _sz]),
+    "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
+}
+EXPORTED_SYMBOLS = list(_ABI)
+del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args
+
 _lib = None
 
 
@@ -106,98 +165,19 @@ def load_library(path=None):
         raise ImportError("liblsdhip.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "-- there is no CPU fallback" % p)
     L = C.CDLL(p)
-    vp, i, sz, dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-    L.lsd_create.restype = i; L.lsd_create.argtypes = [C.POINTER(vp), i]
-    L.lsd_destroy.restype = None; L.lsd_destroy.argtypes = [vp]
-    L.lsd_strerror.restype = C.c_char_p; L.lsd_strerror.argtypes = [i]
-    L.lsd_last_error.restype = C.c_char_p; L.lsd_last_error.argtypes = [vp]
-    L.lsd_default_params.restype = None; L.lsd_default_params.argtypes = [C.POINTER(lsd_params)]
-    L.lsd_abi_version.restype = i; L.lsd_abi_version.argtypes = []
-    L.lsd_free.restype = None; L.lsd_free.argtypes = [vp]
-    L.lsd_run.restype = i
-    L.lsd_run.argtypes = [vp, vp, i, i, sz, C.POINTER(lsd_params), vp, sz, C.POINTER(vp), C.POINTER(i)]
-    L.lsd_run_batch.restype = i
-    L.lsd_run_batch.argtypes = [vp, vp, i, i, i, C.POINTER(lsd_params), vp, C.POINTER(vp), C.POINTER(i)]
-    L.lsd_enqueue_batch_device.restype = i
-    L.lsd_enqueue_batch_device.argtypes = [vp, vp, i, i, i, C.POINTER(lsd_params), C.c_uint, vp, vp, i, vp, vp]
-    L.lsd_reserve.restype = i; L.lsd_reserve.argtypes = [vp, i, i, i]
-    L.lsd_synchronize.restype = i; L.lsd_synchronize.argtypes = [vp]
-    L.lsd_scaled_size.restype = None; L.lsd_scaled_size.argtypes = [i, i, dbl, C.POINTER(i), C.POINTER(i)]
-    L.lsd_set_stop_after.restype = i; L.lsd_set_stop_after.argtypes = [vp, i]
-    L.lsd_set_trace.restype = i; L.lsd_set_trace.argtypes = [vp, i]
-    L.lsd_set_region_waves.restype = i; L.lsd_set_region_waves.argtypes = [vp, i]
-    L.lsd_set_region_help.restype = i; L.lsd_set_region_help.argtypes = [vp, i]
-    L.lsd_debug_set_stamp_budget.restype = i; L.lsd_debug_set_stamp_budget.argtypes = [vp, C.c_uint]
-    if hasattr(L, "lsd_set_cost_history") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_set_cost_history.restype = i; L.lsd_set_cost_history.argtypes = [vp, i]
-    if hasattr(L, "lsd_debug_set_tuning") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_debug_set_tuning.restype = i; L.lsd_debug_set_tuning.argtypes = [vp, C.c_char_p, i]
-    L.lsd_set_host_max_lines.restype = i; L.lsd_set_host_max_lines.argtypes = [vp, i]
-    L.lsd_debug_fetch.restype = i; L.lsd_debug_fetch.argtypes = [vp, i, i, vp, sz]
-    L.lsd_last_timings.restype = i; L.lsd_last_timings.argtypes = [vp, C.POINTER(C.c_float)]
-    L.lsd_map_cache.restype = i; L.lsd_map_cache.argtypes = [vp, vp, i, i, sz, dbl, dbl, vp]
-    L.lsd_enqueue_map_cache_device.restype = i
-    L.lsd_enqueue_map_cache_device.argtypes = [vp, vp, i, i, i, dbl, dbl, vp, vp]
-    L.lsd_occupancy_to_map.restype = i; L.lsd_occupancy_to_map.argtypes = [vp, vp, i, i, vp, sz]
-    L.lsd_enqueue_occupancy_to_map_device.restype = i
-    L.lsd_enqueue_occupancy_to_map_device.argtypes = [vp, vp, sz, vp, vp]
-    L.lsd_scan_to_map_match.restype = i
-    L.lsd_scan_to_map_match.argtypes = [vp, vp, i, i, vp, i, vp, i, vp, i, lsd_position, lsd_position, vp, i, dbl, dbl, vp]
-    L.lsd_enqueue_scan_to_map_match_device.restype = i
-    L.lsd_enqueue_scan_to_map_match_device.argtypes = [vp, vp, i, i, vp, vp, vp, i, lsd_position, lsd_position, vp, i, dbl, dbl, vp, vp]
-    if hasattr(L, "lsd_feature_scan_batch") or not os.environ.get("LSD_HIP_LIB"):      # (a developer A/B build may predate this entry point)
-        L.lsd_feature_scan_batch.restype = i
-        L.lsd_feature_scan_batch.argtypes = [vp, vp, vp, i, i, lsd_map_param, i, dbl, dbl, vp, vp, vp, i, vp, vp, vp]
-        L.lsd_enqueue_feature_scan_batch_device.restype = i
-        L.lsd_enqueue_feature_scan_batch_device.argtypes = [vp, vp, vp, i, i, lsd_map_param, i, dbl, dbl, vp, vp, vp, i, vp, vp, vp, vp]
-    if hasattr(L, "lsd_gather_lines") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_shard_range.restype = None; L.lsd_shard_range.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
-        L.lsd_gather_layout.restype = i; L.lsd_gather_layout.argtypes = [i, i, C.POINTER(i), C.POINTER(sz)]
-        L.lsd_comm_from_rccl.restype = i; L.lsd_comm_from_rccl.argtypes = [vp, C.POINTER(lsd_comm)]
-        L.lsd_gather_lines.restype = i; L.lsd_gather_lines.argtypes = [vp, C.POINTER(lsd_comm), vp, vp, i, i, i, i, vp, vp, vp]
-        L.lsd_gather_unpack.restype = i; L.lsd_gather_unpack.argtypes = [vp, vp, i, i, i, vp, vp, sz]
-    if hasattr(L, "lsd_shard_balanced") or not os.environ.get("LSD_HIP_LIB"):      # (an A/B build with the gather entry points may predate these two)
-        L.lsd_shard_balanced.restype = i; L.lsd_shard_balanced.argtypes = [vp, i, i, vp]
-        L.lsd_last_region_cycles.restype = i; L.lsd_last_region_cycles.argtypes = [vp, i, vp]
-    if hasattr(L, "lsd_last_sensitivity") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_last_sensitivity.restype = i; L.lsd_last_sensitivity.argtypes = [vp, i, vp]
-    if hasattr(L, "lsd_feature_association") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_fa_initial_state.restype = None; L.lsd_fa_initial_state.argtypes = [vp]
-        L.lsd_feature_association.restype = i
-        L.lsd_feature_association.argtypes = [vp, vp, i, i, vp, i, vp, i, vp, i, lsd_position, lsd_position, lsd_position, vp, vp, vp]
-        L.lsd_enqueue_localize_device.restype = i
-        L.lsd_enqueue_localize_device.argtypes = [vp, vp, i, i, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, dbl, vp, vp, vp, vp]
-        L.lsd_localize.restype = i
-        L.lsd_localize.argtypes = [vp, vp, i, i, vp, i, vp, vp, i, i, vp, lsd_map_param, vp, vp, vp]
-        L.lsd_debug_fa_fuse.restype = i
-        L.lsd_debug_fa_fuse.argtypes = [vp, vp, i, lsd_position, lsd_position, vp, vp, vp]
-    if hasattr(L, "lsd_enqueue_localize_resume_device") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_fa_carry_init.restype = None; L.lsd_fa_carry_init.argtypes = [vp, vp, lsd_position]
-        L.lsd_enqueue_localize_resume_device.restype = i
-        L.lsd_enqueue_localize_resume_device.argtypes = [vp, vp, i, i, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, dbl, vp, vp, vp, vp]
-    if hasattr(L, "lsd_enqueue_scan_ingest_device") or not os.environ.get("LSD_HIP_LIB"):
-        L.lsd_enqueue_scan_ingest_device.restype = i
-        L.lsd_enqueue_scan_ingest_device.argtypes = [vp, vp, i, i, vp, vp, vp, i, vp]
-        L.lsd_enqueue_laserscan_ingest_device.restype = i
-        L.lsd_enqueue_laserscan_ingest_device.argtypes = [vp, vp, vp, i, i, vp, vp, vp, i, vp]
-    L.lsd_debug_calibrate.restype = i; L.lsd_debug_calibrate.argtypes = [vp, sz]
-    L.lsd_debug_eval_math.restype = i; L.lsd_debug_eval_math.argtypes = [vp, i, vp, vp, vp, vp, sz]
+    # The shipped library exports every symbol (an AttributeError here otherwise); a developer A/B build (LSD_HIP_LIB) may predate any of
+    # them and then fails at the call instead.
+    for name, (restype, argtypes) in _ABI.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            if not os.environ.get("LSD_HIP_LIB"):
+                raise
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = ["lsd_create", "lsd_destroy", "lsd_strerror", "lsd_last_error", "lsd_default_params",
-                    "lsd_abi_version", "lsd_free", "lsd_run", "lsd_run_batch", "lsd_enqueue_batch_device",
-                    "lsd_reserve", "lsd_synchronize", "lsd_scaled_size", "lsd_set_stop_after", "lsd_set_trace", "lsd_set_region_waves", "lsd_set_region_help", "lsd_debug_set_stamp_budget", "lsd_debug_set_tuning", "lsd_set_cost_history", "lsd_shard_balanced", "lsd_last_region_cycles", "lsd_last_sensitivity", "lsd_set_host_max_lines",
-                    "lsd_debug_fetch", "lsd_last_timings", "lsd_debug_eval_math", "lsd_debug_calibrate", "lsd_map_cache",
-                    "lsd_enqueue_map_cache_device", "lsd_occupancy_to_map", "lsd_enqueue_occupancy_to_map_device",
-                    "lsd_scan_to_map_match", "lsd_enqueue_scan_to_map_match_device",
-                    "lsd_feature_scan_batch", "lsd_enqueue_feature_scan_batch_device",
-                    "lsd_fa_initial_state", "lsd_feature_association", "lsd_enqueue_localize_device", "lsd_localize", "lsd_debug_fa_fuse",
-                    "lsd_fa_carry_init", "lsd_enqueue_localize_resume_device",
-                    "lsd_enqueue_scan_ingest_device", "lsd_enqueue_laserscan_ingest_device",
-                    "lsd_shard_range", "lsd_gather_layout", "lsd_comm_from_rccl", "lsd_gather_lines", "lsd_gather_unpack"]
 
 
 def shard_range(n_items, world, rank):
@@ -283,6 +263,16 @@ class Context:
             raise LsdError(st, self.L.lsd_strerror(st).decode() + " / " + self.L.lsd_last_error(self.h).decode())
         return st
 
+    def _take_lines(self, lines_p, n):
+        """The n records of the buffer the C side has handed over (run / run_batch) as a LINE_DTYPE array; the buffer is freed, before
+        any raise."""
+        lines = np.zeros(n if lines_p else 0, LINE_DTYPE)
+        if len(lines):
+            C.memmove(lines.ctypes.data, lines_p, 80 * len(lines))
+            lines["_pad"] = 0
+        self.L.lsd_free(lines_p)
+        return lines
+
     # -- host-buffer entry points -----------------------------------------------------------------
     def run(self, map_u8, params=None, want_lineim=True):
         """lsd_run on a C-contiguous uint8 image; the image is rewritten in place like the reference does."""
@@ -293,11 +283,7 @@ class Context:
         lines_p, n = C.c_void_p(), C.c_int()
         st = self.L.lsd_run(self.h, map_u8.ctypes.data, cols, rows, map_u8.strides[0], C.byref(p),
                             line_im.ctypes.data if want_lineim else None, cols, C.byref(lines_p), C.byref(n))
-        lines = np.zeros(n.value if lines_p else 0, LINE_DTYPE)
-        if len(lines):
-            C.memmove(lines.ctypes.data, lines_p, 80 * len(lines))
-            lines["_pad"] = 0
-        self.L.lsd_free(lines_p)                                   # (before any raise: the C side has handed the buffer over)
+        lines = self._take_lines(lines_p, n.value)
         self._chk(st)
         return lines, line_im
 
@@ -312,11 +298,7 @@ class Context:
         st = self.L.lsd_run_batch(self.h, maps_u8.ctypes.data, n, cols, rows, C.byref(p),
                                   line_ims.ctypes.data if want_lineim else None, C.byref(lines_p), offs)
         offsets = np.frombuffer(offs, np.int32).copy()
-        lines = np.zeros(int(offsets[-1]) if lines_p else 0, LINE_DTYPE)
-        if len(lines):
-            C.memmove(lines.ctypes.data, lines_p, 80 * len(lines))
-            lines["_pad"] = 0
-        self.L.lsd_free(lines_p)                                   # (before any raise: the C side has handed the buffer over)
+        lines = self._take_lines(lines_p, int(offsets[-1]))
         self._chk(st)
         return lines, offsets, line_ims
 
@@ -356,9 +338,8 @@ class Context:
         pts = np.ascontiguousarray(scan_im_points).view(np.float64).reshape(-1, 3)
         pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         out = np.zeros((len(pr), 4), SCORE_DTYPE)
-        mk = lambda p: lsd_position(float(p[0]), float(p[1]), float(p[2]) if len(p) > 2 else 0.0)
         self._chk(self.L.lsd_scan_to_map_match(self.h, mc.ctypes.data, cols, rows, ml.ctypes.data, len(ml), sl.ctypes.data, len(sl),
-                                               pts.ctypes.data, len(pts), mk(lidar_pose), mk(last_pose), pr.ctypes.data, len(pr),
+                                               pts.ctypes.data, len(pts), _pos(lidar_pose), _pos(last_pose), pr.ctypes.data, len(pr),
                                                float(z_occ), float(max_esti_dist), out.ctypes.data))
         return out
 
@@ -371,7 +352,7 @@ class Context:
         ln = np.ascontiguousarray(lens, np.int32)
         lines = np.zeros((n, 360), LINE_DTYPE); pts = np.zeros((n, pts_cap, 3), np.float64)
         nl = np.zeros(n, np.int32); npt = np.zeros(n, np.int32); lp = np.zeros((n, 2), np.float64); sz = np.zeros((n, 2), np.int32)
-        mp = lsd_map_param(int(map_param[0]), int(map_param[1]), float(map_param[2]), float(map_param[3]), float(map_param[4]))
+        mp = _map_param(map_param)
         # (more than 360 line records in a scan -- the reference would overrun its array there -- raises LsdError(LSD_ERR_CAPACITY), with
         #  the stored records, which the C side says are valid, in the exception's `partial`)
         st = self.L.lsd_feature_scan_batch(self.h, sc.ctypes.data, ln.ctypes.data, n, stride, mp, int(region_point_limit), float(thre_line),
@@ -450,7 +431,7 @@ class Context:
         od = np.ascontiguousarray(odom, np.float64).reshape(-1, 3)
         if len(od) != n + 1:
             raise LsdError(LSD_ERR_INVALID, "odom must have one row more than there are frames")
-        mp = lsd_map_param(int(map_param[0]), int(map_param[1]), float(map_param[2]), float(map_param[3]), float(map_param[4]))
+        mp = _map_param(map_param)
         ini = None if init is None else fa_state(init)
         states = np.zeros(n, FA_STATE_DTYPE); reps = np.zeros(n, FA_REPORT_DTYPE)
         self._chk(self.L.lsd_localize(self.h, mc.ctypes.data, cols, rows, ml.ctypes.data, len(ml), sc.ctypes.data, ln.ctypes.data, n, stride,
@@ -708,6 +689,10 @@ def _pos(p):
     return lsd_position(float(p[0]), float(p[1]), float(p[2]) if len(p) > 2 else 0.0)
 
 
+def _map_param(mp):
+    return lsd_map_param(int(mp[0]), int(mp[1]), float(mp[2]), float(mp[3]), float(mp[4]))
+
+
 def fa_state(state):
     """An FA_STATE_DTYPE array of one record from a record, or from (kalman_x [9], kalman_P [9, 9] indexed P[i, j])."""
     if isinstance(state, np.void) or (isinstance(state, np.ndarray) and state.dtype == FA_STATE_DTYPE):
@@ -870,8 +855,7 @@ class Localizer:
         else:
             cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
         mp = self.map_param
-        mpar = lsd_map_param(int(mp[0]), int(mp[1]), mp[2], mp[3], mp[4])
-        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, mpar, rdp_leastPoint, rdp_threLine, rdp_leastDist,
+        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, _map_param(mp), rdp_leastPoint, rdp_threLine, rdp_leastDist,
                                                            self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np,
                                                            self._lp.data_ptr(), self._sz.data_ptr(), stream))
         cx.enqueue_localize_resume_device(self._mc.data_ptr(), self._cols, self._rows, self._ml.data_ptr(), self._n_map, S, k, nf,

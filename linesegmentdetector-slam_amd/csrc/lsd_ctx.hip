@@ -12,14 +12,38 @@
 #include <string.h>
 
 #include <algorithm>
-#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "lsd_devbuf.h"
 #include "lsd_internal.h"
 
 using namespace lsdhip;
+
+// The main workspace: everything ensure_workspace sizes from the batch geometry, with the capacities it was sized for.  A failed
+// (re)allocation forgets all of it at once (`ws = Workspace{}`).
+struct Workspace {
+    size_t cap_gpx = 0;                          // Gaussian elements per image (rows padded to Geom::gp)
+    size_t cap_n = 0, cap_npx = 0, cap_ws = 0;   // images, scaled pixels per image, wave slots
+    int cap_max_lines = 0;
+    DevBuf<double> gauss, mag, deg, recs, recs_scaled;
+    DevBuf<double2> sc;
+    DevBuf<uint32_t> order;
+    DevBuf<uint32_t> sets;               // n x 256: certified sets of the region stage (k_region.hip)
+    DevBuf<uint32_t> pw, epochmap, ord, spill, gcopy, stamps, seedidx, seedpos, tepoch;
+    uint32_t run_id = 0;   // curMap stamps are unique per run: (run_id << 20) + grow number (a wave that uses up its 2^20 clears its stamps)
+    DevBuf<uint32_t> slist;
+    DevBuf<double> pend;
+    DevBuf<float4> wmeta;
+    DevBuf<int> rnum;
+    DevBuf<uint32_t> xq;
+    DevBuf<unsigned long long> maxbits;  // [0, cap_n) the maxima, then cap_n int32: the gradient pass's near-tie counts -- one memset clears both
+    DevBuf<int32_t> nb, nseed;
+    DevBuf<long long> stats;
+    DevBuf<SeedRec> seeds;               // allocated only while tracing is on
+    int32_t* ties() const { return reinterpret_cast<int32_t*>(maxbits.get() + cap_n); }
+};
 
 struct lsd_ctx {
     int device = 0;
@@ -32,38 +56,18 @@ struct lsd_ctx {
     int tun_share = 0;                                             // ... and for at least this share (%) of the time since the launch began (LSD_REGION_SHARE)
     int pool_max_images = 4;                                       // calls with at most this many images get a pool of helper workgroups (LSD_REGION_POOL)
     int tun_early = 0, tun_wb = 10, tun_up = 32, tun_down = 96, tun_requeue = 1, tun_xpoll = 20000, tun_linger = 1000000, tun_stop = 0;
-    uint32_t* xq = nullptr;
     int region_waves_mode = 0;         // 0: choose per batch; 4 / 8: force that region-stage variant (lsd_set_region_waves)
     bool prefer4 = false;              // the 8-wave workspace did not fit this device's memory once: batches run on 4 waves per image
     hipStream_t stream = nullptr;      // the context's own stream
     hipStream_t last_stream = nullptr; // stream of the last enqueue
     std::string err;
-    // workspace capacity
-    size_t cap_gpx = 0;                                      // Gaussian elements per image (rows padded to Geom::gp)
-    size_t cap_n = 0, cap_npx = 0, cap_wh = 0, cap_ws = 0;   // images, scaled pixels per image, input pixels per image, wave slots
-    int cap_max_lines = 0;
-    bool cap_trace = false;
-    // workspace
-    double *gauss = nullptr, *mag = nullptr, *deg = nullptr, *recs = nullptr, *recs_scaled = nullptr;
-    double2* sc = nullptr;
-    uint32_t* order = nullptr;
-    uint32_t *sets = nullptr;            // n x 256: certified sets of the region stage (k_region.hip)
-    uint32_t *pw = nullptr, *epochmap = nullptr, *ord = nullptr, *spill = nullptr, *gcopy = nullptr, *stamps = nullptr, *seedidx = nullptr, *seedpos = nullptr, *tepoch = nullptr;
-    uint32_t run_id = 0;   // curMap stamps are unique per run: (run_id << 20) + grow number (a wave that uses up its 2^20 clears its stamps)
-    uint32_t* slist = nullptr;
-    double* pend = nullptr;
-    float4* wmeta = nullptr;
-    int* rnum = nullptr;
+    Workspace ws;
     int mcap = 16384;
     int gcap = 8192;
-    unsigned long long* maxbits = nullptr;
-    int32_t *nb = nullptr, *nseed = nullptr;
-    long long* stats = nullptr;
-    void* seeds = nullptr;
     // host-API staging (device side), and the pinned host buffers every host <-> device copy goes through
-    uint8_t *h_in = nullptr, *h_lineim = nullptr;
-    lsd_line *h_lines = nullptr, *h_flat = nullptr;
-    int32_t *h_counts = nullptr, *h_offs = nullptr;
+    DevBuf<uint8_t> h_in, h_lineim;
+    DevBuf<lsd_line> h_lines, h_flat;
+    DevBuf<int32_t> h_counts, h_offs;
     uint8_t* pin[2] = {nullptr, nullptr};
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
     bool pin_used[2] = {false, false};  // a DMA through the buffer has been queued: its event must be waited for before the buffer is written again
@@ -72,43 +76,35 @@ struct lsd_ctx {
     int hcap_max_lines = 0;
     bool hcap_lineim = false;
     // tables
-    double *d_taps = nullptr, *d_lgamma = nullptr, *d_ptab = nullptr;
-    int* d_centres = nullptr;
-    int lg_count = 0;                   // entries of d_lgamma
+    DevBuf<double> d_taps, d_lgamma, d_ptab;
+    DevBuf<int> d_centres;
     bool cost_history = false;          // lsd_set_cost_history: the region stage takes the images in the order of their cost in the last launch
     int hist_n = 0;                     // images of the launch whose counter records are in `stats` (0: none)
     lsd_params tab_params{};
     bool tab_valid = false;
     int tapR = 0;
     // createMapCache workspace
-    unsigned long long* mc_claim = nullptr;
-    uint32_t *mc_fa = nullptr, *mc_fb = nullptr;
-    int* mc_ctl = nullptr;                              // spread flood: frontier sizes + per-chunk counts
-    size_t mc_ctl_n = 0;
-    uint8_t* mc_in = nullptr;
-    double* mc_out = nullptr;
-    size_t mc_cap = 0, mc_hcap = 0;
-    uint8_t *oc_in = nullptr, *oc_out = nullptr;        // occupancy-grid staging of the host entry point
-    size_t oc_cap = 0;
-    uint8_t* mt_buf = nullptr;                          // staging of the host scan-to-map matching entry point
-    size_t mt_cap = 0;
-    // device FeatureAssociation (k_fa.hip): its per-sequence workspace, and the staging of its host entry points
-    uint8_t* fa_buf = nullptr;
-    size_t fa_cap = 0;
-    uint8_t* fh_buf = nullptr;
-    size_t fh_cap = 0;
+    DevBuf<unsigned long long> mc_claim;
+    DevBuf<uint32_t> mc_fa, mc_fb;
+    DevBuf<int> mc_ctl;                                 // spread flood: frontier sizes + per-chunk counts
+    DevBuf<uint8_t> mc_in;
+    DevBuf<double> mc_out;
+    DevBuf<uint8_t> oc_in, oc_out;                      // occupancy-grid staging of the host entry point
+    // staging of the host entry points of scan-to-map matching, FeatureScan and FeatureAssociation (one arena: each of them ends in a
+    // stream synchronisation, so no two are live at once), and the per-sequence workspace of the device FeatureAssociation (k_fa.hip)
+    DevBuf<uint8_t> stage;
+    DevBuf<uint8_t> fa_buf;
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
     int fa_lds_bound = kFaLdsMax;                       // kept candidates sorted in LDS up to this many (kTunings "FA_LDS")
     // lsd_gather_lines: this rank's padded counts + offsets, and its slab of packed line records
-    int32_t* ga_cnt = nullptr;
-    lsd_line* ga_slab = nullptr;
-    size_t ga_cnt_cap = 0, ga_slab_cap = 0;
+    DevBuf<int32_t> ga_cnt;
+    DevBuf<lsd_line> ga_slab;
     hipEvent_t ga_ev = nullptr;         // recorded behind the collectives of the last lsd_gather_lines (they read ga_cnt / ga_slab)
     bool ga_ev_valid = false;
     // options
     int stop_after = 0;
     int tun_groups = -1;                // the 8-wave region stage as persistent workgroups (k_region.hip: k_region): -1 = as many as CUs when the batch has more images than that, 0 = never
-    int* pcount = nullptr;              // ... and the launch's image counter
+    DevBuf<int> pcount;                 // ... and the launch's image counter
     bool trace = false;
     int host_max_lines = 8192;
     // last run
@@ -212,21 +208,21 @@ static int ensure_tables(lsd_ctx* c, const lsd_params* p, const Geom& g, hipStre
     // log-gamma of every pixel count a rectangle of this geometry can have (all + 1 <= w*h + 1, myLSD.cpp:1030): host libm values, as
     // the reference computes them; the device only looks them up
     const int lg_need = (int)std::min<long long>(std::max<long long>((long long)g.npx + 2, kLgTable), kLgTableMax);
-    if (c->lg_count < lg_need) {
+    if ((int)c->d_lgamma.capacity() < lg_need) {
         HIPCHK(c, hipStreamSynchronize(s));
         if (c->done_valid) HIPCHK(c, hipEventSynchronize(c->ev_done));
         std::lock_guard<std::mutex> lk(g_lg_mu);
         const double* tab = log_gamma_table(lg_need);
-        if (c->d_lgamma) { HIPCHK(c, hipFree(c->d_lgamma)); c->d_lgamma = nullptr; c->lg_count = 0; }
-        HIPCHK(c, hipMalloc(&c->d_lgamma, sizeof(double) * lg_need));
-        HIPCHK(c, hipMemcpy(c->d_lgamma, tab, sizeof(double) * lg_need, hipMemcpyHostToDevice));
-        c->lg_count = lg_need;
+        HIPCHK(c, c->d_lgamma.resize(lg_need));
+        const hipError_t e = hipMemcpy(c->d_lgamma.get(), tab, sizeof(double) * lg_need, hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)c->d_lgamma.resize(0);           // (its capacity says how much of the table is on the device)
+        HIPCHK(c, e);
     }
     if (c->tab_valid && memcmp(&c->tab_params, p, sizeof(lsd_params)) == 0) return LSD_OK;
-    if (!c->d_ptab) {
-        HIPCHK(c, hipMalloc(&c->d_ptab, sizeof(double) * kPTable * 3));
-        HIPCHK(c, hipMalloc(&c->d_taps, sizeof(double) * 3 * (2 * kMaxTapRadius + 1)));
-        HIPCHK(c, hipMalloc(&c->d_centres, sizeof(int) * kCentreCount));
+    if (!c->d_ptab.get()) {
+        HIPCHK(c, c->d_ptab.resize(kPTable * 3));
+        HIPCHK(c, c->d_taps.resize(3 * (2 * kMaxTapRadius + 1)));
+        HIPCHK(c, c->d_centres.resize(kCentreCount));
     }
     std::vector<double> taps;
     gauss_taps(p->sca, p->sig, g.tapR, taps);
@@ -242,20 +238,13 @@ static int ensure_tables(lsd_ctx* c, const lsd_params* p, const Geom& g, hipStre
     // kernels of an earlier enqueue (on whatever stream, which may be gone by now) may still read the tables: wait for the event
     // that enqueue recorded, never for its stream
     if (c->done_valid) HIPCHK(c, hipEventSynchronize(c->ev_done));
-    HIPCHK(c, hipMemcpy(c->d_taps, taps.data(), sizeof(double) * taps.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_ptab, pt, sizeof(pt), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_centres, centres.data(), sizeof(int) * kCentreCount, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_taps.get(), taps.data(), sizeof(double) * taps.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_ptab.get(), pt, sizeof(pt), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_centres.get(), centres.data(), sizeof(int) * kCentreCount, hipMemcpyHostToDevice));
     c->tab_params = *p;
     c->tab_valid = true;
     c->tapR = g.tapR;
     return LSD_OK;
-}
-
-template <class T>
-static hipError_t re_alloc(T** p, size_t count) {
-    if (*p) { hipError_t e = hipFree(*p); *p = nullptr; if (e != hipSuccess) return e; }
-    if (count == 0) return hipSuccess;
-    return hipMalloc((void**)p, count * sizeof(T));
 }
 
 // wavefronts per image of the region-stage build a batch of n images runs on (see launch below)
@@ -300,44 +289,44 @@ static int pool_reserve_for(const lsd_ctx* c, int n) {
 static size_t tm_words(size_t npx) { return npx / 16 + 4 * 8200; }
 
 static int ensure_workspace_impl(lsd_ctx* c, size_t n, size_t npx, size_t gpx, int max_lines, bool trace) {
+    Workspace& w = c->ws;
     const size_t need_ws = (n + (size_t)pool_reserve_for(c, (int)n)) * (size_t)waves_for(c, (int)n);   // per-wave arrays: wave slots of the images and of the helper pool
-    const bool grow_main = n > c->cap_n || npx > c->cap_npx || gpx > c->cap_gpx || need_ws > c->cap_ws;
+    const bool grow_main = n > w.cap_n || npx > w.cap_npx || gpx > w.cap_gpx || need_ws > w.cap_ws;
     if (grow_main) {
-        const size_t nn = n > c->cap_n ? n : c->cap_n, pp = npx > c->cap_npx ? npx : c->cap_npx;
-        const size_t gg = gpx > c->cap_gpx ? gpx : c->cap_gpx;
-        const size_t ws = need_ws > c->cap_ws ? need_ws : c->cap_ws;
+        const size_t nn = n > w.cap_n ? n : w.cap_n, pp = npx > w.cap_npx ? npx : w.cap_npx;
+        const size_t gg = gpx > w.cap_gpx ? gpx : w.cap_gpx;
+        const size_t ws = need_ws > w.cap_ws ? need_ws : w.cap_ws;
         HIPCHK(c, hipDeviceSynchronize());
         const size_t tot = nn * pp;
-        HIPCHK(c, re_alloc(&c->gauss, nn * gg)); HIPCHK(c, re_alloc(&c->mag, tot)); HIPCHK(c, re_alloc(&c->deg, tot));
-        HIPCHK(c, re_alloc(&c->sc, tot));
-        HIPCHK(c, re_alloc(&c->pw, tot)); HIPCHK(c, re_alloc(&c->epochmap, tot)); HIPCHK(c, re_alloc(&c->ord, tot));
-        HIPCHK(c, re_alloc(&c->spill, ws * pp)); HIPCHK(c, re_alloc(&c->gcopy, ws * pp)); HIPCHK(c, re_alloc(&c->wmeta, ws * (size_t)c->mcap));
-        HIPCHK(c, re_alloc(&c->stamps, ws * tm_words(pp))); HIPCHK(c, re_alloc(&c->seedidx, tot)); HIPCHK(c, re_alloc(&c->seedpos, tot)); HIPCHK(c, re_alloc(&c->tepoch, nn * (pp / 16 + 4096)));
-        HIPCHK(c, hipMemset(c->stamps, 0, ws * tm_words(pp) * sizeof(uint32_t)));
-        HIPCHK(c, hipMemset(c->epochmap, 0, tot * sizeof(uint32_t)));
-        c->run_id = 0;
+        HIPCHK(c, w.gauss.resize(nn * gg)); HIPCHK(c, w.mag.resize(tot)); HIPCHK(c, w.deg.resize(tot));
+        HIPCHK(c, w.sc.resize(tot));
+        HIPCHK(c, w.pw.resize(tot)); HIPCHK(c, w.epochmap.resize(tot)); HIPCHK(c, w.ord.resize(tot));
+        HIPCHK(c, w.spill.resize(ws * pp)); HIPCHK(c, w.gcopy.resize(ws * pp)); HIPCHK(c, w.wmeta.resize(ws * (size_t)c->mcap));
+        HIPCHK(c, w.stamps.resize(ws * tm_words(pp))); HIPCHK(c, w.seedidx.resize(tot)); HIPCHK(c, w.seedpos.resize(tot)); HIPCHK(c, w.tepoch.resize(nn * (pp / 16 + 4096)));
+        HIPCHK(c, hipMemset(w.stamps.get(), 0, ws * tm_words(pp) * sizeof(uint32_t)));
+        HIPCHK(c, hipMemset(w.epochmap.get(), 0, tot * sizeof(uint32_t)));
+        w.run_id = 0;
         const size_t gs = ws * (size_t)region_slots();                          // result slots: NS per wave slot
-        HIPCHK(c, re_alloc(&c->slist, gs * (size_t)c->gcap));
-        HIPCHK(c, re_alloc(&c->pend, gs * 24));
-        HIPCHK(c, re_alloc(&c->order, nn));
-        HIPCHK(c, re_alloc(&c->sets, nn * 256));
-        HIPCHK(c, re_alloc(&c->xq, nn * (size_t)(kXStride + 1) + kXHdr));
-        HIPCHK(c, re_alloc(&c->maxbits, nn + (nn + 1) / 2)); HIPCHK(c, re_alloc(&c->nb, nn)); HIPCHK(c, re_alloc(&c->nseed, nn));   // (maxbits: [0, nn) the maxima, then nn int32: the gradient pass's near-tie counts -- one memset clears both)
-        HIPCHK(c, re_alloc(&c->stats, nn * kStatWords)); HIPCHK(c, re_alloc(&c->rnum, nn * (size_t)region_ring() * 2));
-        if (c->seeds) { HIPCHK(c, hipFree(c->seeds)); c->seeds = nullptr; c->cap_trace = false; }
-        if (nn != c->cap_n) { c->cap_max_lines = 0; }
-        c->cap_n = nn; c->cap_npx = pp; c->cap_gpx = gg; c->cap_ws = ws;
+        HIPCHK(c, w.slist.resize(gs * (size_t)c->gcap));
+        HIPCHK(c, w.pend.resize(gs * 24));
+        HIPCHK(c, w.order.resize(nn));
+        HIPCHK(c, w.sets.resize(nn * 256));
+        HIPCHK(c, w.xq.resize(nn * (size_t)(kXStride + 1) + kXHdr));
+        HIPCHK(c, w.maxbits.resize(nn + (nn + 1) / 2)); HIPCHK(c, w.nb.resize(nn)); HIPCHK(c, w.nseed.resize(nn));   // (maxbits: [0, nn) the maxima, then nn int32: the gradient pass's near-tie counts -- one memset clears both)
+        HIPCHK(c, w.stats.resize(nn * kStatWords)); HIPCHK(c, w.rnum.resize(nn * (size_t)region_ring() * 2));
+        HIPCHK(c, w.seeds.resize(0));
+        if (nn != w.cap_n) { w.cap_max_lines = 0; }
+        w.cap_n = nn; w.cap_npx = pp; w.cap_gpx = gg; w.cap_ws = ws;
     }
-    if (max_lines > c->cap_max_lines) {
+    if (max_lines > w.cap_max_lines) {
         HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->recs, c->cap_n * (size_t)max_lines * 12));
-        HIPCHK(c, re_alloc(&c->recs_scaled, c->cap_n * (size_t)max_lines * 4));
-        c->cap_max_lines = max_lines;
+        HIPCHK(c, w.recs.resize(w.cap_n * (size_t)max_lines * 12));
+        HIPCHK(c, w.recs_scaled.resize(w.cap_n * (size_t)max_lines * 4));
+        w.cap_max_lines = max_lines;
     }
-    if (trace && !c->cap_trace) {
+    if (trace && !w.seeds.get()) {
         HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, hipMalloc(&c->seeds, c->cap_n * c->cap_npx * sizeof(SeedRec)));
-        c->cap_trace = true;
+        HIPCHK(c, w.seeds.resize(w.cap_n * w.cap_npx));
     }
     return LSD_OK;
 }
@@ -347,14 +336,8 @@ static int ensure_workspace_impl(lsd_ctx* c, size_t n, size_t npx, size_t gpx, i
 static int ensure_workspace(lsd_ctx* c, size_t n, size_t npx, size_t gpx, int max_lines, bool trace) {
     int st = ensure_workspace_impl(c, n, npx, gpx, max_lines, trace);
     if (st != LSD_OK) {
-        (void)hipGetLastError();                                      // the failed hipMalloc is sticky otherwise
-        void** ptrs[] = {(void**)&c->gauss, (void**)&c->mag, (void**)&c->deg, (void**)&c->sc, (void**)&c->pw, (void**)&c->epochmap,
-                         (void**)&c->ord, (void**)&c->spill, (void**)&c->gcopy, (void**)&c->wmeta, (void**)&c->stamps,
-                         (void**)&c->seedidx, (void**)&c->seedpos, (void**)&c->tepoch, (void**)&c->slist, (void**)&c->pend, (void**)&c->order, (void**)&c->xq, (void**)&c->sets,
-                         (void**)&c->maxbits, (void**)&c->nb, (void**)&c->nseed, (void**)&c->stats, (void**)&c->rnum, (void**)&c->seeds,
-                         (void**)&c->recs, (void**)&c->recs_scaled};
-        for (void** pp : ptrs) if (*pp) { (void)hipFree(*pp); *pp = nullptr; }
-        c->cap_n = c->cap_npx = c->cap_gpx = c->cap_ws = 0; c->cap_max_lines = 0; c->cap_trace = false;
+        (void)hipGetLastError();                                      // the failed allocation is sticky otherwise
+        c->ws = Workspace{};
         if (st == LSD_ERR_NOMEM && c->region_waves_mode == 0 && !c->prefer4 && waves_for(c, (int)n) == 8) {
             // the 8-wave variant's workspace does not fit: once more with 4 wavefronts per image (half the per-wave arrays)
             c->prefer4 = true;
@@ -472,20 +455,13 @@ void lsd_destroy(lsd_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void* ptrs[] = {c->gauss, c->mag, c->deg, c->sc, c->recs, c->recs_scaled, c->pw, c->epochmap, c->ord, c->spill, c->gcopy, c->stamps, c->seedidx, c->seedpos, c->tepoch, c->slist, c->pend, c->order, c->xq, c->sets, c->wmeta, c->rnum,
-                    c->maxbits, c->nb, c->nseed, c->stats, c->seeds, c->h_in, c->h_lineim, c->h_lines, c->h_counts,
-                    c->d_taps, c->d_lgamma, c->d_ptab, c->d_centres, c->mc_claim, c->mc_fa, c->mc_fb, c->mc_ctl, c->mc_in, c->mc_out, c->oc_in, c->oc_out, c->mt_buf, c->fa_buf, c->fh_buf, c->ga_cnt, c->ga_slab};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     if (c->ga_ev) (void)hipEventDestroy(c->ga_ev);
-    if (c->pcount) (void)hipFree(c->pcount);
     for (int k = 0; k < 2; k++) { if (c->pin[k]) (void)hipHostFree(c->pin[k]); if (c->pin_ev[k]) (void)hipEventDestroy(c->pin_ev[k]); }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->h_flat) (void)hipFree(c->h_flat);
-    if (c->h_offs) (void)hipFree(c->h_offs);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                     // (every device buffer is a DevBuf member: freed here)
 }
 
 const char* lsd_last_error(const lsd_ctx* c) { return c ? c->err.c_str() : ""; }
@@ -543,7 +519,7 @@ int lsd_reserve(lsd_ctx* c, int n, int cols, int rows) {
     int st = make_geom(&p, cols, rows, &g);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
-    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, (size_t)g.gp * g.h, c->cap_max_lines, c->trace);
+    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, (size_t)g.gp * g.h, c->ws.cap_max_lines, c->trace);
     if (st != LSD_OK) return st;
     // ... and the tables: the log-gamma table is sized by the geometry (w*h + 2 host-libm values: ~40 ms of host work and a blocking
     // copy for a 2048^2 map), taps / centres / log p for the default parameters.  Done here, the first enqueue after a reserve neither
@@ -568,14 +544,15 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     // the workspace is shared by every enqueue of this context: work queued on another stream must be over first
     if (c->done_valid && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
 
+    Workspace& w = c->ws;
     Buffers b{};
     b.in = d_maps;
     b.in_rw = (flags & LSD_FLAG_WRITEBACK_MAP) ? d_maps : nullptr;
-    b.gauss = c->gauss; b.mag = c->mag; b.deg = c->deg; b.sc = c->sc; b.pw = c->pw; b.epochmap = c->epochmap; b.sets = c->sets; b.maxbits = c->maxbits; b.nb = c->nb; b.ties = reinterpret_cast<int32_t*>(c->maxbits + c->cap_n);
-    b.ord = c->ord; b.spill = c->spill; b.gcopy = c->gcopy; b.wmeta = c->wmeta; b.mcap = c->mcap; b.stamps = c->stamps; b.seedidx = c->seedidx; b.seedpos = c->seedpos; b.tepoch = c->tepoch;
+    b.gauss = w.gauss.get(); b.mag = w.mag.get(); b.deg = w.deg.get(); b.sc = w.sc.get(); b.pw = w.pw.get(); b.epochmap = w.epochmap.get(); b.sets = w.sets.get(); b.maxbits = w.maxbits.get(); b.nb = w.nb.get(); b.ties = w.ties();
+    b.ord = w.ord.get(); b.spill = w.spill.get(); b.gcopy = w.gcopy.get(); b.wmeta = w.wmeta.get(); b.mcap = c->mcap; b.stamps = w.stamps.get(); b.seedidx = w.seedidx.get(); b.seedpos = w.seedpos.get(); b.tepoch = w.tepoch.get();
     b.tm_stride = 4 * ((g.w + 7) >> 3) * ((g.h + 7) >> 3);
-    b.order = c->order; b.slist = c->slist; b.gcap = c->gcap; b.id_budget = c->id_budget; b.pend = c->pend; b.rnum = c->rnum;
-    b.recs = c->recs; b.recs_scaled = c->recs_scaled; b.counts = d_counts; b.lines = d_lines; b.line_im = d_line_ims;
+    b.order = w.order.get(); b.slist = w.slist.get(); b.gcap = c->gcap; b.id_budget = c->id_budget; b.pend = w.pend.get(); b.rnum = w.rnum.get();
+    b.recs = w.recs.get(); b.recs_scaled = w.recs_scaled.get(); b.counts = d_counts; b.lines = d_lines; b.line_im = d_line_ims;
     b.max_lines = max_lines;
     {   // the region stage's schedule (k_region.hip): look-ahead of the seed hand-out and of the full evaluations (seeds ahead of the
         // cursor; it adapts between the two values), idle lane groups per refill, results a wave may have waiting for the cursor
@@ -592,20 +569,20 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
         b.tun_help = c->tun_help >= 0 ? c->tun_help : 0;
         b.tun_early = c->tun_early; b.tun_wb = c->tun_wb; b.tun_gate = c->tun_gate; b.tun_share = c->tun_share; b.tun_up = c->tun_up; b.tun_down = c->tun_down; b.tun_requeue = c->tun_requeue;
         b.tun_xpoll = c->tun_xpoll; b.tun_linger = c->tun_linger; b.tun_stop = c->tun_stop;
-        b.xq = (b.tun_help > 0 && !c->trace) ? c->xq : nullptr;
+        b.xq = (b.tun_help > 0 && !c->trace) ? w.xq.get() : nullptr;
         b.npool = b.xq ? pool_for(c, n) : 0;
     }
-    b.taps = c->d_taps; b.centres = c->d_centres; b.lgamma = c->d_lgamma; b.lg_count = c->lg_count; b.ptab = c->d_ptab;
-    b.seeds = c->trace ? c->seeds : nullptr; b.nseed = c->nseed; b.stats = c->stats;
+    b.taps = c->d_taps.get(); b.centres = c->d_centres.get(); b.lgamma = c->d_lgamma.get(); b.lg_count = (int)c->d_lgamma.capacity(); b.ptab = c->d_ptab.get();
+    b.seeds = c->trace ? w.seeds.get() : nullptr; b.nseed = w.nseed.get(); b.stats = w.stats.get();
 
     // Every dispatch of a batch in flight has to get onto a hardware pipe that the launches of other batches may be holding (a region launch
     // waits for workgroup slots for tens of milliseconds), so a batch costs as few dispatches as it can: ONE fill in front of the kernels (the
     // gradient maxima and, behind them, the gradient pass's near-tie counts); the region stage clears its own counter records and tile epochs
     // image by image; the line counts and list lengths are written by the kernels that own them unless the pipeline is cut short.
-    HIPCHK(c, hipMemsetAsync(c->maxbits, 0, sizeof(unsigned long long) * c->cap_n + sizeof(int32_t) * (size_t)n, s));
+    HIPCHK(c, hipMemsetAsync(w.maxbits.get(), 0, sizeof(unsigned long long) * w.cap_n + sizeof(int32_t) * (size_t)n, s));
     const bool full_region = c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION;
     if (!full_region) HIPCHK(c, hipMemsetAsync(d_counts, 0, sizeof(int32_t) * n, s));            // (else k_region writes every image's count)
-    if (c->stop_after != 0 && c->stop_after < LSD_STAGE_SORT) HIPCHK(c, hipMemsetAsync(c->nb, 0, sizeof(int32_t) * (size_t)n, s));   // (else k_sort writes every image's length)
+    if (c->stop_after != 0 && c->stop_after < LSD_STAGE_SORT) HIPCHK(c, hipMemsetAsync(w.nb.get(), 0, sizeof(int32_t) * (size_t)n, s));   // (else k_sort writes every image's length)
 
     HIPCHK(c, hipEventRecord(c->ev[0], s));
     // Mat::zeros, myLSD.cpp:215: the Gaussian's tiles clear lineIm on the way where the raster is made of whole 16-byte words; else a
@@ -617,31 +594,31 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     HIPCHK(c, hipEventRecord(c->ev[1], s));
     if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_GRAD) launch_gradient(g, b, n, s);
     HIPCHK(c, hipEventRecord(c->ev[2], s));
-    if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_SORT) { launch_sort(g, b, n, s); launch_order(b, n, g.npx, (c->cost_history && c->hist_n == n && !c->trace) ? c->stats : nullptr, s); }
+    if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_SORT) { launch_sort(g, b, n, s); launch_order(b, n, g.npx, (c->cost_history && c->hist_n == n && !c->trace) ? w.stats.get() : nullptr, s); }
     HIPCHK(c, hipEventRecord(c->ev[3], s));
     hipStream_t sr = s;
     if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION) {
         // stamps of earlier runs must never look current: every run gets its own 2^20-wide id range
-        if (++c->run_id >= 1023u) {
-            HIPCHK(c, hipMemsetAsync(c->stamps, 0, c->cap_ws * tm_words(c->cap_npx) * sizeof(uint32_t), sr));
-            HIPCHK(c, hipMemsetAsync(c->epochmap, 0, c->cap_n * c->cap_npx * sizeof(uint32_t), sr));   // (the set labels carry the run number too)
-            c->run_id = 1;
+        if (++w.run_id >= 1023u) {
+            HIPCHK(c, hipMemsetAsync(w.stamps.get(), 0, w.cap_ws * tm_words(w.cap_npx) * sizeof(uint32_t), sr));
+            HIPCHK(c, hipMemsetAsync(w.epochmap.get(), 0, w.cap_n * w.cap_npx * sizeof(uint32_t), sr));   // (the set labels carry the run number too)
+            w.run_id = 1;
         }
         // (the counter records and the tile epochs are cleared by the region stage itself, image by image: region_image)
-        if (b.xq) HIPCHK(c, hipMemsetAsync(c->xq, 0, sizeof(uint32_t) * ((size_t)n * (kXStride + 1) + kXHdr), sr));
+        if (b.xq) HIPCHK(c, hipMemsetAsync(b.xq, 0, sizeof(uint32_t) * ((size_t)n * (kXStride + 1) + kXHdr), sr));
         // 8 wavefronts per image take a whole CU each: worth it up to four images per CU (waves_for); the per-wave workspace
         // (stamps / spill / gcopy: 12 B per scaled pixel and wave) was sized for it by ensure_workspace
         const bool wide = waves_for(c, n) == 8;
         int grid = n;
         const int groups = c->tun_groups >= 0 ? c->tun_groups : c->num_cus;
         if (wide && groups > 0 && groups < n && !b.xq && !c->trace) {           // persistent workgroups (k_region.hip: k_region): fewer workgroups than images
-            if (!c->pcount) HIPCHK(c, hipMalloc(&c->pcount, 64));
-            HIPCHK(c, hipMemsetAsync(c->pcount, 0, sizeof(int), sr));
-            b.pcount = c->pcount; b.nimg = n; b.npool = 0;
+            if (!c->pcount.get()) HIPCHK(c, c->pcount.resize(16));
+            HIPCHK(c, hipMemsetAsync(c->pcount.get(), 0, sizeof(int), sr));
+            b.pcount = c->pcount.get(); b.nimg = n; b.npool = 0;
             grid = groups;
         }
-        if (wide) launch_region_w8(g, b, grid, c->run_id << 20, sr);
-        else launch_region_w4(g, b, grid, c->run_id << 20, sr);
+        if (wide) launch_region_w8(g, b, grid, w.run_id << 20, sr);
+        else launch_region_w4(g, b, grid, w.run_id << 20, sr);
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     if (c->stop_after == 0) launch_lines(g, b, n, s);
@@ -717,10 +694,10 @@ static int ensure_host_staging(lsd_ctx* c, size_t n, size_t wh, int max_lines, b
         const bool li = lineim || c->hcap_lineim;
         c->hcap_n = 0; c->hcap_wh = 0; c->hcap_max_lines = 0; c->hcap_lineim = false;   // (stay 0 if an allocation below fails)
         HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->h_in, nn * ww));
-        HIPCHK(c, re_alloc(&c->h_lineim, li ? nn * ww : 0));
-        HIPCHK(c, re_alloc(&c->h_lines, nn * (size_t)ml)); HIPCHK(c, re_alloc(&c->h_flat, nn * (size_t)ml));
-        HIPCHK(c, re_alloc(&c->h_counts, nn)); HIPCHK(c, re_alloc(&c->h_offs, nn + 3));
+        HIPCHK(c, c->h_in.resize(nn * ww));
+        HIPCHK(c, c->h_lineim.resize(li ? nn * ww : 0));
+        HIPCHK(c, c->h_lines.resize(nn * (size_t)ml)); HIPCHK(c, c->h_flat.resize(nn * (size_t)ml));
+        HIPCHK(c, c->h_counts.resize(nn)); HIPCHK(c, c->h_offs.resize(nn + 3));
         c->hcap_n = nn; c->hcap_wh = ww; c->hcap_max_lines = ml; c->hcap_lineim = li;
     }
     return LSD_OK;
@@ -740,26 +717,26 @@ int lsd_run_batch(lsd_ctx* c, uint8_t* maps, int n, int cols, int rows, const ls
     st = ensure_host_staging(c, (size_t)n, wh, ml, line_ims != nullptr);
     if (st != LSD_OK) return st;
     hipStream_t s = c->stream;
-    st = h2d_staged(c, c->h_in, maps, (size_t)n * wh, s);
+    st = h2d_staged(c, c->h_in.get(), maps, (size_t)n * wh, s);
     if (st != LSD_OK) return st;
-    st = lsd_enqueue_batch_device(c, c->h_in, n, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, line_ims ? c->h_lineim : nullptr,
-                                  c->h_lines, ml, c->h_counts, s);
+    st = lsd_enqueue_batch_device(c, c->h_in.get(), n, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, line_ims ? c->h_lineim.get() : nullptr,
+                                  c->h_lines.get(), ml, c->h_counts.get(), s);
     if (st != LSD_OK) return st;
-    launch_compact_lines(c->h_lines, c->h_counts, ml, n, c->h_flat, c->h_offs, s);
+    launch_compact_lines(c->h_lines.get(), c->h_counts.get(), ml, n, c->h_flat.get(), c->h_offs.get(), s);
     // the observable in-place remap is final after K1 (event 1 of the enqueue): it travels back on the second stream while
     // the gradient / sort / region / line kernels run
     HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev[1], 0));
-    st = d2h_staged(c, maps, c->h_in, (size_t)n * wh, c->copy_stream);
+    st = d2h_staged(c, maps, c->h_in.get(), (size_t)n * wh, c->copy_stream);
     if (st != LSD_OK) return st;
     std::vector<int32_t> offs((size_t)n + 3);                                                  // offsets[n + 1], the overflow count, 1 + first image given up
-    st = d2h_staged(c, offs.data(), c->h_offs, sizeof(int32_t) * (size_t)(n + 3), s);          // (waits for the pipeline)
+    st = d2h_staged(c, offs.data(), c->h_offs.get(), sizeof(int32_t) * (size_t)(n + 3), s);          // (waits for the pipeline)
     if (st != LSD_OK) return st;
     memcpy(offsets_out, offs.data(), sizeof(int32_t) * (size_t)(n + 1));
     const int total = offsets_out[n];
     lsd_line* out = (lsd_line*)calloc(total > 0 ? total : 1, sizeof(lsd_line));
     if (!out) return LSD_ERR_NOMEM;
-    st = total > 0 ? d2h_staged(c, out, c->h_flat, sizeof(lsd_line) * (size_t)total, s) : LSD_OK;
-    if (st == LSD_OK && line_ims) st = d2h_staged(c, line_ims, c->h_lineim, (size_t)n * wh, s);
+    st = total > 0 ? d2h_staged(c, out, c->h_flat.get(), sizeof(lsd_line) * (size_t)total, s) : LSD_OK;
+    if (st == LSD_OK && line_ims) st = d2h_staged(c, line_ims, c->h_lineim.get(), (size_t)n * wh, s);
     if (st != LSD_OK) { free(out); return st; }
     *lines_out = out;
     if (offs[(size_t)n + 2] > 0) {
@@ -806,7 +783,7 @@ int lsd_last_region_cycles(lsd_ctx* c, int n, long long* cycles_out) {
     if (!c || !cycles_out || n <= 0 || n > c->last_n || n > c->hist_n) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->last_stream));
-    HIPCHK(c, hipMemcpy2D(cycles_out, sizeof(long long), c->stats + kStatTotalWord, sizeof(long long) * kStatWords, sizeof(long long), (size_t)n,
+    HIPCHK(c, hipMemcpy2D(cycles_out, sizeof(long long), c->ws.stats.get() + kStatTotalWord, sizeof(long long) * kStatWords, sizeof(long long), (size_t)n,
                           hipMemcpyDeviceToHost));
     return LSD_OK;
 }
@@ -817,9 +794,9 @@ int lsd_last_sensitivity(lsd_ctx* c, int n, int* near_ties) {
     HIPCHK(c, hipStreamSynchronize(c->last_stream));
     std::vector<long long> reg((size_t)n);
     std::vector<int32_t> grad((size_t)n);
-    HIPCHK(c, hipMemcpy2D(reg.data(), sizeof(long long), c->stats + kStatTiesWord, sizeof(long long) * kStatWords, sizeof(long long), (size_t)n,
+    HIPCHK(c, hipMemcpy2D(reg.data(), sizeof(long long), c->ws.stats.get() + kStatTiesWord, sizeof(long long) * kStatWords, sizeof(long long), (size_t)n,
                           hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(grad.data(), reinterpret_cast<int32_t*>(c->maxbits + c->cap_n), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(grad.data(), c->ws.ties(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
         const long long v = reg[(size_t)i] + grad[(size_t)i];
         near_ties[i] = v > 0x7fffffffll ? 0x7fffffff : (int)v;
@@ -831,6 +808,7 @@ int lsd_debug_fetch(lsd_ctx* c, int image, int what, void* out, size_t bytes) {
     if (!c || !out || image < 0 || image >= c->last_n) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->last_stream));
+    const Workspace& w = c->ws;
     const size_t npx = (size_t)c->geom.npx, off = (size_t)image * npx;
     const void* src = nullptr;
     size_t need = 0;
@@ -838,43 +816,41 @@ int lsd_debug_fetch(lsd_ctx* c, int image, int what, void* out, size_t bytes) {
     switch (what) {
         case LSD_DBG_GAUSS:                                           // (rows are padded to gp doubles on the device)
             if (bytes < npx * 8) return LSD_ERR_INVALID;
-            HIPCHK(c, hipMemcpy2D(out, (size_t)c->geom.w * 8, c->gauss + (size_t)image * c->geom.gp * c->geom.h, (size_t)c->geom.gp * 8,
+            HIPCHK(c, hipMemcpy2D(out, (size_t)c->geom.w * 8, w.gauss.get() + (size_t)image * c->geom.gp * c->geom.h, (size_t)c->geom.gp * 8,
                                   (size_t)c->geom.w * 8, (size_t)c->geom.h, hipMemcpyDeviceToHost));
             return LSD_OK;
-        case LSD_DBG_MAG: src = c->mag + off; need = npx * 8; break;
-        case LSD_DBG_DEG: src = c->deg + off; need = npx * 8; break;
-        case LSD_DBG_STATE: src = c->pw + off; need = npx * 4; break;
+        case LSD_DBG_MAG: src = w.mag.get() + off; need = npx * 8; break;
+        case LSD_DBG_DEG: src = w.deg.get() + off; need = npx * 8; break;
+        case LSD_DBG_STATE: src = w.pw.get() + off; need = npx * 4; break;
         case LSD_DBG_ORDER:
         case LSD_DBG_ORDER_VAL:
-            HIPCHK(c, hipMemcpy(&nbv, c->nb + image, 4, hipMemcpyDeviceToHost));
-            if (what == LSD_DBG_ORDER) { src = c->ord + off; need = (size_t)nbv * 4; }
+            HIPCHK(c, hipMemcpy(&nbv, w.nb.get() + image, 4, hipMemcpyDeviceToHost));
+            if (what == LSD_DBG_ORDER) { src = w.ord.get() + off; need = (size_t)nbv * 4; }
             else {                                                    // the bin values are recomputed on demand (k_sort.hip: k_ordv)
                 if (bytes < (size_t)nbv * 2) return LSD_ERR_INVALID;
-                uint16_t* tmp = nullptr;
-                HIPCHK(c, hipMalloc(&tmp, (size_t)(nbv > 0 ? nbv : 1) * 2));
-                launch_ordv(c->mag + off, c->maxbits + image, c->ord + off, tmp, nbv, c->geom.pseBin, c->last_stream);
-                hipError_t e = hipStreamSynchronize(c->last_stream);
-                if (e == hipSuccess && nbv > 0) e = hipMemcpy(out, tmp, (size_t)nbv * 2, hipMemcpyDeviceToHost);
-                (void)hipFree(tmp);
-                HIPCHK(c, e);
+                DevBuf<uint16_t> tmp;
+                HIPCHK(c, tmp.resize((size_t)(nbv > 0 ? nbv : 1)));
+                launch_ordv(w.mag.get() + off, w.maxbits.get() + image, w.ord.get() + off, tmp.get(), nbv, c->geom.pseBin, c->last_stream);
+                HIPCHK(c, hipStreamSynchronize(c->last_stream));
+                if (nbv > 0) HIPCHK(c, hipMemcpy(out, tmp.get(), (size_t)nbv * 2, hipMemcpyDeviceToHost));
                 return LSD_OK;
             }
             break;
-        case LSD_DBG_NB: src = c->nb + image; need = 4; break;
-        case LSD_DBG_MAXGRAD: src = c->maxbits + image; need = 8; break;
+        case LSD_DBG_NB: src = w.nb.get() + image; need = 4; break;
+        case LSD_DBG_MAXGRAD: src = w.maxbits.get() + image; need = 8; break;
         case LSD_DBG_RECS:
             HIPCHK(c, hipMemcpy(&cnt, c->last_counts + image, 4, hipMemcpyDeviceToHost));
             if (cnt > c->last_max_lines) cnt = c->last_max_lines;
-            src = c->recs + (size_t)image * c->last_max_lines * 12; need = (size_t)cnt * 12 * 8;
+            src = w.recs.get() + (size_t)image * c->last_max_lines * 12; need = (size_t)cnt * 12 * 8;
             break;
-        case LSD_DBG_NSEED: src = c->nseed + image; need = 4; break;
+        case LSD_DBG_NSEED: src = w.nseed.get() + image; need = 4; break;
         case LSD_DBG_SEEDS:
-            if (!c->seeds) return LSD_ERR_INVALID;
-            HIPCHK(c, hipMemcpy(&nseed, c->nseed + image, 4, hipMemcpyDeviceToHost));
-            src = (const SeedRec*)c->seeds + off; need = (size_t)nseed * sizeof(SeedRec);
+            if (!w.seeds.get()) return LSD_ERR_INVALID;
+            HIPCHK(c, hipMemcpy(&nseed, w.nseed.get() + image, 4, hipMemcpyDeviceToHost));
+            src = w.seeds.get() + off; need = (size_t)nseed * sizeof(SeedRec);
             break;
         case LSD_DBG_STATS:                                           // (a larger `bytes` reads the records of the following images too)
-            src = c->stats + (size_t)image * kStatWords; need = 8 * kStatWords;
+            src = w.stats.get() + (size_t)image * kStatWords; need = 8 * kStatWords;
             if (bytes > need) { const size_t all = (size_t)(c->last_n - image) * need; need = bytes < all ? bytes / need * need : all; }
             break;
         default: return LSD_ERR_INVALID;
@@ -895,27 +871,17 @@ int lsd_enqueue_map_cache_device(lsd_ctx* c, const uint8_t* d_maps, int n, int c
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
     const size_t need = (size_t)n * cols * rows;
-    if (need > c->mc_cap) {
-        c->mc_cap = 0;                                   // (stays 0 if an allocation below fails)
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->mc_claim, need)); HIPCHK(c, re_alloc(&c->mc_fa, need * 2)); HIPCHK(c, re_alloc(&c->mc_fb, need * 2));
-        c->mc_cap = need;
-    }
-    if ((size_t)n > c->mc_ctl_n) {                                                     // frontier sizes + up to 64 chunk counts per map
-        c->mc_ctl_n = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->mc_ctl, (size_t)n * (2 + 64)));
-        c->mc_ctl_n = (size_t)n;
-    }
+    HIPCHK(c, c->mc_claim.reserve(need)); HIPCHK(c, c->mc_fa.reserve(need * 2)); HIPCHK(c, c->mc_fb.reserve(need * 2));
+    HIPCHK(c, c->mc_ctl.reserve((size_t)n * (2 + 64)));                                // frontier sizes + up to 64 chunk counts per map
     const int cell_radius = cvt_x86(floor(z_occ_max_dis / res));           // myLSD.cpp:13
     // few maps: spread each over G workgroups (kernel per level phase); many maps: one workgroup per map, one launch
     int G = (2 * c->num_cus) / n;
     if (G > 64) G = 64;
     if (G >= 4)                                                    // measured crossover: 128 maps 33 vs 42 ms, 256 maps 67 vs 56 ms
-        launch_mapcache_spread(d_maps, d_out, c->mc_claim, c->mc_fa, c->mc_fb, c->mc_ctl, c->mc_ctl + 2 * (size_t)n, n, G, cols, rows, res,
+        launch_mapcache_spread(d_maps, d_out, c->mc_claim.get(), c->mc_fa.get(), c->mc_fb.get(), c->mc_ctl.get(), c->mc_ctl.get() + 2 * (size_t)n, n, G, cols, rows, res,
                                z_occ_max_dis, cell_radius, s);
     else
-        launch_mapcache(d_maps, d_out, c->mc_claim, c->mc_fa, c->mc_fb, n, cols, rows, res, z_occ_max_dis, cell_radius, s);
+        launch_mapcache(d_maps, d_out, c->mc_claim.get(), c->mc_fa.get(), c->mc_fb.get(), n, cols, rows, res, z_occ_max_dis, cell_radius, s);
     HIPCHK(c, hipGetLastError());
     c->last_stream = s;
     return LSD_OK;
@@ -926,18 +892,13 @@ int lsd_map_cache(lsd_ctx* c, const uint8_t* map, int cols, int rows, size_t str
     if (!c || !map || !out || cols <= 0 || rows <= 0 || stride < (size_t)cols) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t wh = (size_t)cols * rows;
-    if (wh > c->mc_hcap) {
-        c->mc_hcap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->mc_in, wh)); HIPCHK(c, re_alloc(&c->mc_out, wh));
-        c->mc_hcap = wh;
-    }
+    HIPCHK(c, c->mc_in.reserve(wh)); HIPCHK(c, c->mc_out.reserve(wh));
     int st;
-    if (stride == (size_t)cols) { st = h2d_staged(c, c->mc_in, map, wh, c->stream); if (st != LSD_OK) return st; }
-    else HIPCHK(c, hipMemcpy2DAsync(c->mc_in, cols, map, stride, cols, rows, hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_map_cache_device(c, c->mc_in, 1, cols, rows, res, z_occ_max_dis, c->mc_out, c->stream);
+    if (stride == (size_t)cols) { st = h2d_staged(c, c->mc_in.get(), map, wh, c->stream); if (st != LSD_OK) return st; }
+    else HIPCHK(c, hipMemcpy2DAsync(c->mc_in.get(), cols, map, stride, cols, rows, hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_map_cache_device(c, c->mc_in.get(), 1, cols, rows, res, z_occ_max_dis, c->mc_out.get(), c->stream);
     if (st != LSD_OK) return st;
-    return d2h_staged(c, out, c->mc_out, wh * sizeof(double), c->stream);
+    return d2h_staged(c, out, c->mc_out.get(), wh * sizeof(double), c->stream);
 }
 
 int lsd_enqueue_occupancy_to_map_device(lsd_ctx* c, const int8_t* d_grid, size_t n_cells, uint8_t* d_map, void* stream) {
@@ -955,16 +916,11 @@ int lsd_occupancy_to_map(lsd_ctx* c, const int8_t* grid, int cols, int rows, uin
     if (!c || !grid || !map_out || cols <= 0 || rows <= 0 || map_stride < (size_t)cols) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t wh = (size_t)cols * rows;
-    if (wh > c->oc_cap) {
-        c->oc_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->oc_in, wh)); HIPCHK(c, re_alloc(&c->oc_out, wh));
-        c->oc_cap = wh;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->oc_in, grid, wh, hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_occupancy_to_map_device(c, reinterpret_cast<const int8_t*>(c->oc_in), wh, c->oc_out, c->stream);
+    HIPCHK(c, c->oc_in.reserve(wh)); HIPCHK(c, c->oc_out.reserve(wh));
+    HIPCHK(c, hipMemcpyAsync(c->oc_in.get(), grid, wh, hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_occupancy_to_map_device(c, reinterpret_cast<const int8_t*>(c->oc_in.get()), wh, c->oc_out.get(), c->stream);
     if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpy2DAsync(map_out, map_stride, c->oc_out, cols, cols, rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(map_out, map_stride, c->oc_out.get(), cols, cols, rows, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }
@@ -996,33 +952,19 @@ int lsd_scan_to_map_match(lsd_ctx* c, const double* map_cache, int cols, int row
     for (int p = 0; p < n_pairs; p++)
         if (pairs[2 * p] < 0 || pairs[2 * p] >= n_map || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_scan) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_mc = (size_t)cols * rows * sizeof(double), b_ml = (size_t)n_map * sizeof(lsd_line), b_sl = (size_t)n_scan * sizeof(lsd_line);
-    const size_t b_pt = (size_t)(n_points > 0 ? n_points : 1) * sizeof(lsd_position), b_pr = (size_t)n_pairs * 2 * sizeof(int);
-    const size_t b_out = (size_t)n_pairs * 4 * sizeof(lsd_match_score);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t total = up(b_mc) + up(b_ml) + up(b_sl) + up(b_pt) + up(b_pr) + up(b_out);
-    if (total > c->mt_cap) {
-        c->mt_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->mt_buf, total));
-        c->mt_cap = total;
-    }
-    uint8_t* base = c->mt_buf;
-    double* d_mc = reinterpret_cast<double*>(base); base += up(b_mc);
-    lsd_line* d_ml = reinterpret_cast<lsd_line*>(base); base += up(b_ml);
-    lsd_line* d_sl = reinterpret_cast<lsd_line*>(base); base += up(b_sl);
-    lsd_position* d_pt = reinterpret_cast<lsd_position*>(base); base += up(b_pt);
-    int* d_pr = reinterpret_cast<int*>(base); base += up(b_pr);
-    lsd_match_score* d_out = reinterpret_cast<lsd_match_score*>(base);
-    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, b_mc, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, b_ml, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sl, scan_lines, b_sl, hipMemcpyHostToDevice, c->stream));
+    const size_t n_mc = (size_t)cols * rows, n_pr = (size_t)n_pairs * 2, n_out = (size_t)n_pairs * 4;
+    double* d_mc; lsd_line *d_ml, *d_sl; lsd_position* d_pt; int* d_pr; lsd_match_score* d_out;
+    auto regions = [&](Carver& k) { k(d_mc, n_mc); k(d_ml, n_map); k(d_sl, n_scan); k(d_pt, n_points); k(d_pr, n_pr); k(d_out, n_out); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sl, scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, c->stream));
     if (n_points > 0) HIPCHK(c, hipMemcpyAsync(d_pt, pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_pr, pairs, b_pr, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_pr, pairs, n_pr * sizeof(int), hipMemcpyHostToDevice, c->stream));
     const int st = lsd_enqueue_scan_to_map_match_device(c, d_mc, cols, rows, d_ml, d_sl, d_pt, n_points, lidar, last, d_pr, n_pairs,
                                                         z_occ_max_dis, max_esti_dist, d_out, c->stream);
     if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, d_out, n_out * sizeof(lsd_match_score), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }
@@ -1082,36 +1024,24 @@ int lsd_feature_scan_batch(lsd_ctx* c, const lsd_polar* scans, const int* lens, 
         return LSD_ERR_INVALID;
     for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_sc = (size_t)n_scans * stride * sizeof(lsd_polar), b_len = (size_t)n_scans * sizeof(int);
-    const size_t b_li = (size_t)n_scans * LSD_RDP_MAX_LINES * sizeof(lsd_line), b_pt = (size_t)n_scans * (pts_cap > 0 ? pts_cap : 1) * sizeof(lsd_position);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t total = up(b_sc) + up(b_len) + up(b_li) + up(b_pt) + 4 * up((size_t)n_scans * 16);
-    if (total > c->mt_cap) {                           // (shares the staging buffer of the matching entry point)
-        c->mt_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->mt_buf, total));
-        c->mt_cap = total;
-    }
-    uint8_t* base = c->mt_buf;
-    lsd_polar* d_sc = reinterpret_cast<lsd_polar*>(base); base += up(b_sc);
-    int* d_len = reinterpret_cast<int*>(base); base += up(b_len);
-    lsd_line* d_li = reinterpret_cast<lsd_line*>(base); base += up(b_li);
-    lsd_position* d_pt = reinterpret_cast<lsd_position*>(base); base += up(b_pt);
-    int* d_nl = reinterpret_cast<int*>(base); base += up((size_t)n_scans * 16);
-    int* d_np = reinterpret_cast<int*>(base); base += up((size_t)n_scans * 16);
-    double* d_lp = reinterpret_cast<double*>(base); base += up((size_t)n_scans * 16);
-    int* d_sz = reinterpret_cast<int*>(base);
+    const size_t ns = (size_t)n_scans, b_sc = ns * stride * sizeof(lsd_polar), b_len = ns * sizeof(int), b_li = ns * LSD_RDP_MAX_LINES * sizeof(lsd_line);
+    lsd_polar* d_sc; int *d_len, *d_nl, *d_np, *d_sz; lsd_line* d_li; lsd_position* d_pt; double* d_lp;
+    auto regions = [&](Carver& k) {
+        k(d_sc, ns * stride); k(d_len, ns); k(d_li, ns * LSD_RDP_MAX_LINES); k(d_pt, ns * pts_cap);
+        k(d_nl, ns); k(d_np, ns); k(d_lp, ns * 2); k(d_sz, ns * 2);
+    };
+    HIPCHK(c, carve(c->stage, regions));
     HIPCHK(c, hipMemcpyAsync(d_sc, scans, b_sc, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_len, lens, b_len, hipMemcpyHostToDevice, c->stream));
     const int st = lsd_enqueue_feature_scan_batch_device(c, d_sc, d_len, n_scans, stride, mp, region_point_limit, thre_line, line_dist_thre_m,
                                                          d_li, d_nl, d_pt, pts_cap, d_np, d_lp, d_sz, c->stream);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipMemcpyAsync(lines_out, d_li, b_li, hipMemcpyDeviceToHost, c->stream));
-    if (pts_cap > 0) HIPCHK(c, hipMemcpyAsync(pts_out, d_pt, (size_t)n_scans * pts_cap * sizeof(lsd_position), hipMemcpyDeviceToHost, c->stream));
+    if (pts_cap > 0) HIPCHK(c, hipMemcpyAsync(pts_out, d_pt, ns * pts_cap * sizeof(lsd_position), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(n_lines, d_nl, b_len, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(n_pts, d_np, b_len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(lidar_pos, d_lp, (size_t)n_scans * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(im_size, d_sz, (size_t)n_scans * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(lidar_pos, d_lp, ns * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(im_size, d_sz, ns * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n_scans; i++)
         if (n_lines[i] > LSD_RDP_MAX_LINES) return LSD_ERR_CAPACITY;      // more chords than the 360 records per scan hold (the first 360 are valid)
@@ -1130,26 +1060,16 @@ int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, 
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t need_cnt = (size_t)(per + 2) + (size_t)(n_local > 0 ? n_local : 1);
-    if (need_cnt > c->ga_cnt_cap) {
-        c->ga_cnt_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->ga_cnt, need_cnt));
-        c->ga_cnt_cap = need_cnt;
-    }
-    if ((size_t)cap_rows > c->ga_slab_cap) {
-        c->ga_slab_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->ga_slab, (size_t)cap_rows));
-        c->ga_slab_cap = (size_t)cap_rows;
-    }
+    HIPCHK(c, c->ga_cnt.reserve(need_cnt));
+    HIPCHK(c, c->ga_slab.reserve((size_t)cap_rows));
     // the staging buffers belong to the context: an earlier hand-off's collectives (on whatever stream) must have read them
     if (c->ga_ev_valid) HIPCHK(c, hipStreamWaitEvent(s, c->ga_ev, 0));
     // rows past this rank's lines are zero (nothing stale travels)
-    HIPCHK(c, hipMemsetAsync(c->ga_slab, 0, sizeof(lsd_line) * (size_t)cap_rows, s));
-    launch_pack_lines(d_lines, d_counts, n_local, max_lines, per, cap_rows, c->ga_cnt, c->ga_cnt + (per + 2), c->ga_slab, s);
+    HIPCHK(c, hipMemsetAsync(c->ga_slab.get(), 0, sizeof(lsd_line) * (size_t)cap_rows, s));
+    launch_pack_lines(d_lines, d_counts, n_local, max_lines, per, cap_rows, c->ga_cnt.get(), c->ga_cnt.get() + (per + 2), c->ga_slab.get(), s);
     HIPCHK(c, hipGetLastError());
-    if (comm->all_gather(comm->user, c->ga_cnt, d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
-        comm->all_gather(comm->user, c->ga_slab, d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0) {
+    if (comm->all_gather(comm->user, c->ga_cnt.get(), d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
+        comm->all_gather(comm->user, c->ga_slab.get(), d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0) {
         c->err = "lsd_gather_lines: the communicator's all_gather failed";
         return LSD_ERR_HIP;
     }
@@ -1161,47 +1081,17 @@ int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, 
 }
 
 // --- device FeatureAssociation (k_fa.hip) ------------------------------------------------------------------------------
-// Carves the per-sequence workspace of n_seq sequences with pair_cap pairs each out of c->fa_buf (grown with one synchronisation).
+// Carves the per-sequence workspace of n_seq sequences with pair_cap pairs each out of c->fa_buf (grown with one synchronisation; while
+// it is large enough this is pointer arithmetic only: Localizer.step_device never waits for the device).
 static int fa_workspace(lsd_ctx* c, int n_seq, int pair_cap, FaArgs& a) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t ns = (size_t)n_seq, pc = (size_t)pair_cap;
-    const size_t b_pairs = up(ns * pc * 2 * 4), b_cnt = up(ns * 4), b_cand = up(ns * pc * 16 * 8), b_scr = up(ns * pc * 8 * 4),
-                 b_ctl = up(ns * kFaCtl * 8), b_aux = up(ns * kFaAux * 8);
-    const size_t total = b_pairs + 3 * b_cnt + b_cand + b_scr + b_ctl + b_aux;
-    if (total > c->fa_cap) {
-        c->fa_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->fa_buf, total));
-        c->fa_cap = total;
-    }
-    uint8_t* b = c->fa_buf;
-    a.pairs = reinterpret_cast<int*>(b); b += b_pairs;
-    a.n_pairs = reinterpret_cast<int*>(b); b += b_cnt;
-    a.n_cand = reinterpret_cast<int*>(b); b += b_cnt;
-    a.n_frames = reinterpret_cast<int*>(b); b += b_cnt;
-    a.cand = reinterpret_cast<double*>(b); b += b_cand;
-    a.scratch = reinterpret_cast<int*>(b); b += b_scr;
-    a.ctl = reinterpret_cast<double*>(b); b += b_ctl;
-    a.aux = reinterpret_cast<double*>(b);
+    auto regions = [&](Carver& k) {
+        k(a.pairs, ns * pc * 2); k(a.n_pairs, ns); k(a.n_cand, ns); k(a.n_frames, ns);
+        k(a.cand, ns * pc * 16); k(a.scratch, ns * pc * 8); k(a.ctl, ns * kFaCtl); k(a.aux, ns * kFaAux);
+    };
+    HIPCHK(c, carve(c->fa_buf, regions));
     a.pair_cap = pair_cap;
     a.lds_bound = c->fa_lds_bound;
-    return LSD_OK;
-}
-
-// Staging of the host entry points: `count` regions of the given sizes in c->fh_buf.
-static int fa_staging(lsd_ctx* c, std::initializer_list<size_t> sizes, std::vector<uint8_t*>& out) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t total = 0;
-    for (size_t v : sizes) total += up(v > 0 ? v : 1);
-    if (total > c->fh_cap) {
-        c->fh_cap = 0;
-        HIPCHK(c, hipDeviceSynchronize());
-        HIPCHK(c, re_alloc(&c->fh_buf, total));
-        c->fh_cap = total;
-    }
-    uint8_t* b = c->fh_buf;
-    out.clear();
-    for (size_t v : sizes) { out.push_back(b); b += up(v > 0 ? v : 1); }
     return LSD_OK;
 }
 
@@ -1221,36 +1111,35 @@ int lsd_feature_association(lsd_ctx* c, const double* map_cache, int cols, int r
         return LSD_ERR_INVALID;
     if ((long long)n_map * n_scan > (1 << 26)) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t b_mc = (size_t)cols * rows * 8;
-    std::vector<uint8_t*> st;
-    int r = fa_staging(c, {b_mc, (size_t)n_map * sizeof(lsd_line), (size_t)n_scan * sizeof(lsd_line), (size_t)n_points * sizeof(lsd_position),
-                           sizeof(lsd_fa_state) * 2, sizeof(lsd_fa_report), 8 * 8}, st);
-    if (r != LSD_OK) return r;
+    const size_t n_mc = (size_t)cols * rows;
+    double *d_mc, *d_sc;                                          // d_sc: lidarPose (2), then lastPose + ScanPose (6)
+    lsd_line *d_ml, *d_sl; lsd_position* d_pts; lsd_fa_state* d_st; lsd_fa_report* d_rep;
+    auto regions = [&](Carver& k) { k(d_mc, n_mc); k(d_ml, n_map); k(d_sl, n_scan); k(d_pts, n_points); k(d_st, 2); k(d_rep, 1); k(d_sc, 8); };
+    HIPCHK(c, carve(c->stage, regions));
     FaArgs a{};
     const int pair_cap = std::max(1, n_map * n_scan);
-    if ((r = fa_workspace(c, 1, pair_cap, a)) != LSD_OK) return r;
-    lsd_fa_state* d_st = reinterpret_cast<lsd_fa_state*>(st[4]);
-    double* d_sc = reinterpret_cast<double*>(st[6]);              // lidarPose (2), then lastPose + ScanPose (6)
+    const int r = fa_workspace(c, 1, pair_cap, a);
+    if (r != LSD_OK) return r;
     const double sc[8] = {lidar.x, lidar.y, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(st[0], map_cache, b_mc, hipMemcpyHostToDevice, s));
-    if (n_map) HIPCHK(c, hipMemcpyAsync(st[1], map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    if (n_scan) HIPCHK(c, hipMemcpyAsync(st[2], scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    if (n_points) HIPCHK(c, hipMemcpyAsync(st[3], pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_map) HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    if (n_scan) HIPCHK(c, hipMemcpyAsync(d_sl, scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    if (n_points) HIPCHK(c, hipMemcpyAsync(d_pts, pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_sc, sc, sizeof(sc), hipMemcpyHostToDevice, s));
-    a.map_cache = reinterpret_cast<const double*>(st[0]); a.cols = cols; a.rows = rows;
-    a.map_lines = reinterpret_cast<const lsd_line*>(st[1]); a.n_map = n_map;
-    a.scan_lines = reinterpret_cast<const lsd_line*>(st[2]); a.n_lines = nullptr; a.n_scan_given = n_scan; a.line_pitch = std::max(n_scan, 1);
-    a.pts = reinterpret_cast<const double*>(st[3]); a.n_pts = nullptr; a.n_pts_given = n_points; a.pts_pitch = std::max(n_points, 1);
+    a.map_cache = d_mc; a.cols = cols; a.rows = rows;
+    a.map_lines = d_ml; a.n_map = n_map;
+    a.scan_lines = d_sl; a.n_lines = nullptr; a.n_scan_given = n_scan; a.line_pitch = std::max(n_scan, 1);
+    a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = nullptr; a.n_pts_given = n_points; a.pts_pitch = std::max(n_points, 1);
     a.lidar_pos = d_sc; a.given = d_sc + 2;
     a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0;
     a.odom = nullptr; a.map_resol = 1;
-    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = reinterpret_cast<lsd_fa_report*>(st[5]);
+    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = d_rep;
     launch_fa_frame(a, 1, true, s);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(report, st[5], sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(report, d_rep, sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     c->last_stream = s;
     return LSD_OK;
@@ -1261,13 +1150,13 @@ int lsd_debug_fa_fuse(lsd_ctx* c, const lsd_match_score* cands, int n, lsd_posit
     if (!c || n < 0 || (n > 0 && !cands) || !in || !out || !report) return LSD_ERR_INVALID;
     if (n > (1 << 26)) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<uint8_t*> st;
-    int r = fa_staging(c, {sizeof(lsd_fa_state) * 2, sizeof(lsd_fa_report)}, st);
-    if (r != LSD_OK) return r;
+    lsd_fa_state* d_st; lsd_fa_report* d_rep;
+    auto regions = [&](Carver& k) { k(d_st, 2); k(d_rep, 1); };
+    HIPCHK(c, carve(c->stage, regions));
     FaArgs a{};
-    if ((r = fa_workspace(c, 1, std::max(1, (n + 3) / 4), a)) != LSD_OK) return r;
+    const int r = fa_workspace(c, 1, std::max(1, (n + 3) / 4), a);
+    if (r != LSD_OK) return r;
     hipStream_t s = c->stream;
-    lsd_fa_state* d_st = reinterpret_cast<lsd_fa_state*>(st[0]);
     const double ctl[kFaCtl] = {0, 0, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
     const int cnt[2] = {0, n};
     if (n) HIPCHK(c, hipMemcpyAsync(a.cand, cands, (size_t)n * sizeof(lsd_match_score), hipMemcpyHostToDevice, s));
@@ -1276,11 +1165,11 @@ int lsd_debug_fa_fuse(lsd_ctx* c, const lsd_match_score* cands, int n, lsd_posit
     HIPCHK(c, hipMemcpyAsync(a.n_cand, &cnt[1], 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
     a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0; a.odom = nullptr;
-    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = reinterpret_cast<lsd_fa_report*>(st[1]);
+    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = d_rep;
     launch_fa_frame(a, 1, false, s);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(report, st[1], sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(report, d_rep, sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return LSD_OK;
 }
@@ -1364,39 +1253,36 @@ int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const 
     if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
     const int pts_cap = 8192;
-    const size_t nf = (size_t)n_frames, b_mc = (size_t)cols * rows * 8;
-    std::vector<uint8_t*> st;
-    int r = fa_staging(c, {b_mc, (size_t)n_map * sizeof(lsd_line), nf * stride * sizeof(lsd_polar), nf * 4, (nf + 1) * sizeof(lsd_position),
-                           sizeof(lsd_fa_state), nf * LSD_RDP_MAX_LINES * sizeof(lsd_line), nf * 4, nf * pts_cap * sizeof(lsd_position), nf * 4,
-                           nf * 16, nf * 8, nf * sizeof(lsd_fa_state), nf * sizeof(lsd_fa_report)}, st);
-    if (r != LSD_OK) return r;
+    const size_t nf = (size_t)n_frames, n_mc = (size_t)cols * rows;
+    double *d_mc, *d_lp; lsd_line *d_ml, *d_lines; lsd_polar* d_scans; int *d_lens, *d_nl, *d_np, *d_sz; lsd_position *d_odom, *d_pts;
+    lsd_fa_state *d_init, *d_states; lsd_fa_report* d_reports;
+    auto regions = [&](Carver& k) {
+        k(d_mc, n_mc); k(d_ml, n_map); k(d_scans, nf * stride); k(d_lens, nf); k(d_odom, nf + 1); k(d_init, 1);
+        k(d_lines, nf * LSD_RDP_MAX_LINES); k(d_nl, nf); k(d_pts, nf * pts_cap); k(d_np, nf); k(d_lp, nf * 2); k(d_sz, nf * 2);
+        k(d_states, nf); k(d_reports, nf);
+    };
+    HIPCHK(c, carve(c->stage, regions));
     hipStream_t s = c->stream;
     lsd_fa_state h_init;
     if (init) h_init = *init;
     else lsd_fa_initial_state(&h_init);
-    HIPCHK(c, hipMemcpyAsync(st[0], map_cache, b_mc, hipMemcpyHostToDevice, s));
-    if (n_map) HIPCHK(c, hipMemcpyAsync(st[1], map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(st[2], scans, nf * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(st[3], lens, nf * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(st[4], odom, (nf + 1) * sizeof(lsd_position), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(st[5], &h_init, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
-    r = lsd_enqueue_feature_scan_batch_device(c, reinterpret_cast<const lsd_polar*>(st[2]), reinterpret_cast<const int*>(st[3]), n_frames, stride,
-                                              mp, 3, 0.08, 0.5, reinterpret_cast<lsd_line*>(st[6]), reinterpret_cast<int*>(st[7]),
-                                              reinterpret_cast<lsd_position*>(st[8]), pts_cap, reinterpret_cast<int*>(st[9]),
-                                              reinterpret_cast<double*>(st[10]), reinterpret_cast<int*>(st[11]), s);   // rdp defaults, baseFunc.h:70-72
+    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, s));
+    if (n_map) HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_scans, scans, nf * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_lens, lens, nf * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_odom, odom, (nf + 1) * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_init, &h_init, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
+    int r = lsd_enqueue_feature_scan_batch_device(c, d_scans, d_lens, n_frames, stride, mp, 3, 0.08, 0.5, d_lines, d_nl, d_pts, pts_cap, d_np,
+                                                  d_lp, d_sz, s);   // rdp defaults, baseFunc.h:70-72
     if (r != LSD_OK) return r;
-    r = lsd_enqueue_localize_device(c, reinterpret_cast<const double*>(st[0]), cols, rows, reinterpret_cast<const lsd_line*>(st[1]), n_map, 1,
-                                    n_frames, &n_frames, reinterpret_cast<const lsd_line*>(st[6]), reinterpret_cast<const int*>(st[7]),
-                                    reinterpret_cast<const lsd_position*>(st[8]), pts_cap, reinterpret_cast<const int*>(st[9]),
-                                    reinterpret_cast<const double*>(st[10]), reinterpret_cast<const lsd_position*>(st[4]), mp.mapResol,
-                                    reinterpret_cast<const lsd_fa_state*>(st[5]), reinterpret_cast<lsd_fa_state*>(st[12]),
-                                    reinterpret_cast<lsd_fa_report*>(st[13]), s);
+    r = lsd_enqueue_localize_device(c, d_mc, cols, rows, d_ml, n_map, 1, n_frames, &n_frames, d_lines, d_nl, d_pts, pts_cap, d_np, d_lp, d_odom,
+                                    mp.mapResol, d_init, d_states, d_reports, s);
     if (r != LSD_OK) return r;
     std::vector<int> nl(nf), np(nf);
-    HIPCHK(c, hipMemcpyAsync(states, st[12], nf * sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(reports, st[13], nf * sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(nl.data(), st[7], nf * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(np.data(), st[9], nf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(states, d_states, nf * sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(reports, d_reports, nf * sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(nl.data(), d_nl, nf * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(np.data(), d_np, nf * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     for (size_t i = 0; i < nf; i++)
         if (nl[i] > LSD_RDP_MAX_LINES || np[i] > pts_cap) return LSD_ERR_CAPACITY;
@@ -1406,26 +1292,24 @@ int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const 
 int lsd_debug_calibrate(lsd_ctx* c, size_t bytes) {
     if (!c || bytes < 8) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    double* buf = nullptr;
-    HIPCHK(c, hipMalloc(&buf, bytes));
-    launch_calib(buf, bytes / 8, c->stream);
+    DevBuf<double> buf;
+    HIPCHK(c, buf.resize(bytes / 8));
+    launch_calib(buf.get(), bytes / 8, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(buf);
     return LSD_OK;
 }
 
 int lsd_debug_eval_math(lsd_ctx* c, int fn, const double* a, const double* b, double* out0, double* out1, size_t n) {
     if (!c || !a || !out0 || !out1 || n == 0 || fn < 0 || fn > 6 || ((fn == 1 || fn == 6) && !b)) return LSD_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    double *da = nullptr, *db = nullptr, *d0 = nullptr, *d1 = nullptr;
-    HIPCHK(c, hipMalloc(&da, n * 8)); HIPCHK(c, hipMalloc(&db, n * 8)); HIPCHK(c, hipMalloc(&d0, n * 8)); HIPCHK(c, hipMalloc(&d1, n * 8));
-    HIPCHK(c, hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
-    if (b) HIPCHK(c, hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice));
-    launch_dbgmath(fn, da, db, d0, d1, n, c->stream);
+    DevBuf<double> da, db, d0, d1;
+    HIPCHK(c, da.resize(n)); HIPCHK(c, db.resize(n)); HIPCHK(c, d0.resize(n)); HIPCHK(c, d1.resize(n));
+    HIPCHK(c, hipMemcpy(da.get(), a, n * 8, hipMemcpyHostToDevice));
+    if (b) HIPCHK(c, hipMemcpy(db.get(), b, n * 8, hipMemcpyHostToDevice));
+    launch_dbgmath(fn, da.get(), db.get(), d0.get(), d1.get(), n, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out0, d0, n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out1, d1, n * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(d0); (void)hipFree(d1);
+    HIPCHK(c, hipMemcpy(out0, d0.get(), n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out1, d1.get(), n * 8, hipMemcpyDeviceToHost));
     return LSD_OK;
 }
 
