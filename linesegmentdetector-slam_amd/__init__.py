@@ -572,11 +572,11 @@ class Context:
                           "wait_noseed", "requeued_ahead", "cycles_eval_at_cursor", "depth_end", "nfa_min_abs_enc", "nfa_min_gap_enc", "help_exports", "help_evals", "near_ties",
                           "wd_commit", "wd_next", "wd_nseeds", "wd_state", "wd_nbig", "wd_lock", "wd_pend", "wd_wave"),
                          [int(x) for x in v]))
-            d["set_answers"], d["sets_founded"] = int(v[41]), int(v[42])   # evaluations answered by a certified uniform set / sets founded (k_region.hip)
+            d["set_answers"], d["sets_founded"] = int(v[41]), int(v[42])   # evaluations answered by a certified uniform set / sets founded (region/eval.h)
             d["cycles_nfa_count"], d["nfa_tail_iters"] = int(v[43]), int(v[44])   # developer build: cycles of the NFA's pixel count, iterations of its tail sum
             d["nfa_bracket_misses"] = int(v[40])   # stopping tests of the NFA's tail left to the correctly rounded pow / log10 (an image the watchdog gave up keeps its record here instead)
             # how close RectangleImprover's comparisons came to a tie, as margins (distance of the operands over what an ulp of exp / log10 /
-            # pow can move them; k_region.hip: improve()): smallest for a logNFA compared with 0, smallest for two compared NFA values (inf: none seen)
+            # pow can move them; region/nfa.h: improve()): smallest for a logNFA compared with 0, smallest for two compared NFA values (inf: none seen)
             for k in ("nfa_min_abs", "nfa_min_gap"):
                 enc = d.pop(k + "_enc")
                 d[k] = float("inf") if enc == 0 else float(np.array([0x7ff0000000000000 - enc], np.uint64).view(np.float64)[0])

@@ -30,7 +30,7 @@ struct Workspace {
     DevBuf<double> gauss, mag, deg, recs, recs_scaled;
     DevBuf<double2> sc;
     DevBuf<uint32_t> order;
-    DevBuf<uint32_t> sets;               // n x 256: certified sets of the region stage (k_region.hip)
+    DevBuf<uint32_t> sets;               // n x 256: certified sets of the region stage (region/eval.h: certify_set)
     DevBuf<uint32_t> pw, epochmap, ord, spill, gcopy, stamps, seedidx, seedpos, tepoch;
     uint32_t run_id = 0;   // curMap stamps are unique per run: (run_id << 20) + grow number (a wave that uses up its 2^20 clears its stamps)
     DevBuf<uint32_t> slist;

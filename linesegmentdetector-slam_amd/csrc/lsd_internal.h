@@ -12,8 +12,8 @@ constexpr int kMaxTapRadius = 40;               // hSize = 2*h+1 <= 81 taps per 
 constexpr int kLgTable = 16384;                 // host-tabulated log-gamma entries every context starts with; it grows to w*h + 2 (the largest
 constexpr int kLgTableMax = 1 << 23;            //    pixel count a rectangle can have, + 1), up to this many
 constexpr int kStatWords = 48;                  // counters per image of the region stage (lsd_debug_fetch LSD_DBG_STATS)
-constexpr int kStatTiesWord = 39;               // ... and this one its decisions within the libm's noise (k_region.hip: ST_TIES; lsd_last_sensitivity)
-constexpr int kStatTotalWord = 8;               // ... of which this one holds the shader clocks the stage spent on the image (k_region.hip: ST_TOTAL)
+constexpr int kStatTiesWord = 39;               // ... and this one its decisions within the libm's noise (region/stats.h: ST_TIES; lsd_last_sensitivity)
+constexpr int kStatTotalWord = 8;               // ... of which this one holds the shader clocks the stage spent on the image (region/stats.h: ST_TOTAL)
 constexpr int kPTable = 16;                     // host-tabulated log(p), log10(p), log(1-p) for p = aliPro/2^k
 // Help across workgroups in the region stage (k_region.hip): a control block of 32-bit words per launch, cleared before it.
 //   per image (kXStride words): [0] accept epoch [1] commit cursor [2] image finished [3] helper wavefronts attached
@@ -58,7 +58,7 @@ struct Buffers {
     double* deg;           // n x npx
     double2* sc;           // n x npx : (sin, cos)(deg), written where usedMap == 0 after the gradient pass
     uint32_t* pw;          // n x npx : packed pixel word (see above)
-    uint32_t* epochmap;    // n x npx : accept epoch of pixels with code 3; for growable pixels the label of their certified set, tagged with the run number (k_region.hip; cleared with the stamps when the run numbers wrap)
+    uint32_t* epochmap;    // n x npx : accept epoch of pixels with code 3; for growable pixels the label of their certified set, tagged with the run number (region/config.h: label_make; cleared with the stamps when the run numbers wrap)
     uint32_t* sets;        // n x 256 : sizes of the certified sets of the launch by label, 0 = none / ended (cleared by the region stage itself)
     uint32_t* tepoch;      // n x ceil(w/8) x ceil(h/8) : per tile, epoch + 1 of the latest accepted line with a pixel in it (cleared per run)
     unsigned long long* maxbits;  // n : bit pattern of max gradient (non-negative double)
@@ -77,7 +77,7 @@ struct Buffers {
     uint32_t* seedpos;     // n x npx : their pixels (y*w+x), same order
     uint32_t* slist;       // n x NW x NS x gcap : lists of the speculative results in flight (examined pixels, pixels to mark)
     int gcap;
-    uint32_t id_budget;    // curMap stamp ids per wave and run (k_region.hip: grow())
+    uint32_t id_budget;    // curMap stamp ids per wave and run (region/grow.h: grow())
     int tun_soft, tun_claim, tun_feed, tun_big;   // schedule of the region stage (k_region.hip; lsd_ctx.hip has the defaults)
     uint32_t* xq;          // n x kXStride + kXHdr + n : control block of the help across workgroups (see above), null: no help
     int tun_help;          // helper wavefronts an image may have attached

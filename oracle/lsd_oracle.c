@@ -433,7 +433,7 @@ static double note_nfa(orc_state *st, double v, double best, int first)
 {
     if (st->dbg && fabs(v) <= DBL_MAX) {
         /* margins: distance over the most two libms (each within an ulp of the correctly rounded exp / log10 / pow) can move the
-         * operands apart -- noise(v) = 2^-51 |v + logNT| + 2^-52 (1 + max(|v|, logNT)), see k_region.hip: improve() */
+         * operands apart -- noise(v) = 2^-51 |v + logNT| + 2^-52 (1 + max(|v|, logNT)), see region/nfa.h: improve() */
         const double nv = 0x1p-51 * fabs(v + st->logNT) + 0x1p-52 * (1.0 + fmax(fabs(v), st->logNT));
         const double a = fabs(v) / nv;
         if (!st->nfa_host_only && a < st->dbg->nfa_min_abs) st->dbg->nfa_min_abs = a;   /* (-logNT - n log10 p: host numbers on the HIP path too) */

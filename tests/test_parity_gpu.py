@@ -236,8 +236,8 @@ def test_seed_trace_matches_oracle(maps, lsdmod, ctx, oracle):
 
 
 def test_fast_sincos_error_bound(lsdmod, ctx):
-    """RegionGrower's classifier works on fp32 ESTIMATES (k_region.hip): the unit vector of a pixel's packed angle -- fp32 with
-    the two lowest mantissa bits dropped, hardware sin/cos -- must lie within 3e-6 of the exact one (kEpsU = 6e-6 in k_region.hip = this + the 1.9e-6 of a batch's fp32 partial sums, bounded below); every margin
+    """RegionGrower's classifier works on fp32 ESTIMATES (region/grow.h): the unit vector of a pixel's packed angle -- fp32 with
+    the two lowest mantissa bits dropped, hardware sin/cos -- must lie within 3e-6 of the exact one (kEpsU = 6e-6 in region/grow.h = this + the 1.9e-6 of a batch's fp32 partial sums, bounded below); every margin
     of the classifier is built on that bound (a candidate closer to the tolerance than the margins goes to the exact test)."""
     rng = np.random.default_rng(11)
     a = np.concatenate([rng.uniform(-np.pi, np.pi, 4_000_000), np.linspace(-np.pi, np.pi, 200_001),
@@ -245,7 +245,7 @@ def test_fast_sincos_error_bound(lsdmod, ctx):
                         rng.uniform(-1e-3, 1e-3, 100_000)])
     s, c = ctx.eval_math(3, a)
     err = np.hypot(s - np.sin(a), c - np.cos(a))
-    assert err.max() <= 3.0e-6, err.max()                                      # the first part of kEpsU = 6e-6 (k_region.hip)
+    assert err.max() <= 3.0e-6, err.max()                                      # the first part of kEpsU = 6e-6 (region/grow.h)
     # the second part: 64 such unit vectors summed in fp32 (a batch's partial sums) against the fp64 sum of the same terms
     rng2 = np.random.default_rng(7)
     worst = 0.0
@@ -885,7 +885,7 @@ def test_default_variant_for_long_batches(maps, lsdmod, ctx, oracle):
 
 def test_certified_uniform_sets_answer_like_full_evaluations(maps, lsdmod, ctx, oracle):
     """The heaviest bench images are one sparse structure of pixels with the SAME level-line angle, grown again from each of its
-    hundreds of seeds and given up by Refiner every time (k_region.hip, "Certified uniform sets").  The region stage founds a set from
+    hundreds of seeds and given up by Refiner every time (region/eval.h, "Certified uniform sets").  The region stage founds a set from
     the first such evaluation and answers the structure's other seeds without growing anything.  Every seed's record -- first region,
     final region, outcome, logNFA -- must be the oracle's, with the trace on (every record through the cursor one by one) and off, and
     most of the structure's seeds must have been answered by the set."""
@@ -944,7 +944,7 @@ def test_nfa_values_equal_the_correctly_rounded_restatement(maps, lsdmod, ctx, o
 
 def test_device_libm_is_inside_the_nfa_bracket(lsdmod, ctx):
     """The stopping test of the binomial tail (myLSD.cpp:1052-1053) is decided from the device math library's pow and log10 wherever
-    a bracket of 2^-44 relative (kOcmlBracket in k_region.hip) around them decides it: the library's values must lie within a
+    a bracket of 2^-44 relative (kOcmlBracket in region/nfa.h) around them decides it: the library's values must lie within a
     sixteenth of that bracket of the correctly rounded ones, over the arguments the NFA produces (a ratio in (0, 1) to a pixel count;
     tails between 1e-300 and 1e3)."""
     rng = np.random.default_rng(7)
@@ -964,7 +964,7 @@ def test_nfa_decisions_are_far_from_ties(maps, lsdmod, ctx):
     """RectangleImprover's decisions (logNFA > 0, candidate > best so far) are those of correctly rounded arithmetic (above); glibc's
     exp / log10 / pow are not correctly rounded (test_crmath.py: log10 off by one ulp in one call out of seven), so a decision of the
     reference could differ where two compared values sit within what those last places can move them.  The region stage records every
-    comparison's MARGIN -- the distance of its operands over that noise (k_region.hip: improve()); below 1 a flip is possible.  What
+    comparison's MARGIN -- the distance of its operands over that noise (region/nfa.h: improve()); below 1 a flip is possible.  What
     comes closest are STRUCTURAL near-ties: the binomial tail B(1/p + 1, 1/p, p) equals p^(1/p - 1) = B(1/p - 1, 1/p - 1, p) exactly, and
     the two evaluations (the sum through the Lanczos / Windschitl log-gamma, the closed form) differ by the log-gamma formulas' own
     error, ~3e-13 absolute -- the same on every libm.  On every fixture and on the whole 512-image bench batch every margin is >= 10."""

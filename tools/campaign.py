@@ -20,7 +20,7 @@ BIG = bool(os.environ.get("CAMPAIGN_BIG"))                    # larger maps (spi
 # The floor the campaign ENFORCES on RectangleImprover's comparisons (logNFA > 0, candidate > best so far).  The HIP path evaluates
 # the NFA's exp / log10 / pow correctly rounded; glibc's are within one ulp of that (its log10 differs in one call out of seven:
 # tests/test_crmath.py).  The region stage records every comparison's MARGIN: the distance of its operands over the most those last
-# places can move them apart (k_region.hip: improve()).  Below 1 a decision could differ between the two libms; the campaign fails
+# places can move them apart (region/nfa.h: improve()).  Below 1 a decision could differ between the two libms; the campaign fails
 # below kMarginFloor.  (What comes closest are structural near-ties: B(1/p + 1, 1/p, p) = p^(1/p - 1) exactly, evaluated once through
 # the log-gamma formulas and once in closed form, ~3e-13 apart = a margin of ~25; and tails of almost 1, where logNFA = -logNT + 1e-14.)
 kMarginFloor = 2.0
