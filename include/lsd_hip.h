@@ -37,7 +37,8 @@ enum {
     LSD_ERR_INTERNAL = 7        /* the region stage's watchdog gave an image up (a defect detector; lsd_last_error() names the image) */
 };
 
-/* The five LSD knobs of myLineSegmentDetector (LSD/myLSD.h:132); defaults LSD/baseFunc.h:64-68. */
+/* The five LSD knobs of myLineSegmentDetector (LSD/myLSD.h:132); defaults LSD/baseFunc.h:64-68.
+ * LSD_ERR_UNSUPPORTED, before anything is enqueued, if the tap radius exceeds 40 or K1's window (csrc/k1_lds.h) exceeds the device's LDS per workgroup: at sig = 0.6, sca >= 0.12 runs on 160 KiB. */
 typedef struct lsd_params {
     double sca;      /* 0.3  */
     double sig;      /* 0.6  */

@@ -8,18 +8,13 @@
 // Bit-exactness: same taps (computed on the host with the host libm), same accumulation order
 // (newVal += pix * ker[i], i ascending), fp64, no FMA contraction (-ffp-contract=off).
 #include "lsd_internal.h"
+#include "k1_lds.h"
 #include <algorithm>
 
 namespace lsdhip {
 
-// Output tile: 32 wide, 24 high.  The height sets the LDS a workgroup needs (the x-pass sums of the window's rows: 38 KB at 24, 49 KB
-// at 32, 27 KB at 16) against the rows of the window that neighbouring tiles compute twice; the kernel is bound by the latency of its
-// staging, so workgroups per CU count: 32 -> 24 rows (four workgroups per CU instead of three) 2.58 -> 2.35 ms on the bench batch, 16
-// rows (five) 2.83 (profiles/r06g_k1_tile_heights.log; same bits).
-#ifndef LSD_K1_TH
-#define LSD_K1_TH 24
-#endif
-constexpr int TW = 32, TH = LSD_K1_TH, NT = 256;
+// Output tile (k1_lds.h says why 32 x 24).
+constexpr int TW = kK1TileW, TH = kK1TileH, NT = 256;
 
 __device__ __forceinline__ int reflect_idx(int j, int lim) {  // myLSD.cpp:436-443
     const int dou = 2 * lim;
@@ -284,20 +279,21 @@ __global__ __launch_bounds__(256) void k_remap_inplace(uint8_t* __restrict__ img
 }
 
 // clr: lineIm to be cleared on the way (null: none; the caller has checked that every image's raster is a whole number of 16-byte words)
+static auto gauss_kernel(const Geom& g) { return 2 * g.tapR + 1 == 17 ? k_gauss<17> : k_gauss<0>; }
+
+// Before the first enqueue of a call: a window above 64 KiB needs the kernel's dynamic-LDS limit raised (make_geom has checked the size
+// against the device's limit).  An error here leaves nothing queued.
+hipError_t prepare_gauss(const Geom& g) {
+    const K1Lds L = k1_lds(g.sca, g.tapR);
+    if (L.bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(gauss_kernel(g)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes);
+}
+
 void launch_gauss(const Geom& g, const Buffers& b, int n, uint8_t* clr, hipStream_t s) {
-    const int span = (int)floor((TW - 1) / g.sca) + 2;            // bound on centre(X0+31) - centre(X0) + 1
-    const int IWmax = span + 2 * g.tapR + 1;
-    int IWp = ((IWmax + 3) & ~3) + 8;                             // + the alignment slack of the word-wise staging and of the x-pass's 5-word reads
-    if (((IWp >> 2) & 1) == 0) IWp += 4;                          // odd pitch in 32-bit words: consecutive rows start in different LDS banks
-    const int IHmax = (int)floor((TH - 1) / g.sca) + 2 + 2 * g.tapR + 1;   // (as IWmax, for the tile's height)
-    const int hSize = 2 * g.tapR + 1;
-    const size_t lds = (size_t)IHmax * TW * sizeof(double) + 3 * hSize * sizeof(double) + (size_t)IHmax * IWp;
-    auto kern = hSize == 17 ? k_gauss<17> : k_gauss<0>;
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const K1Lds L = k1_lds(g.sca, g.tapR);
     const unsigned gx = (g.w + TW - 1) / TW, gy = (g.h + TH - 1) / TH, tiles = gx * gy * (unsigned)n;
-    hipLaunchKernelGGL(kern, dim3(((tiles + 7u) >> 3) * 8u), dim3(NT), lds, s, b.in, b.gauss, b.taps, b.centres, g.W, g.H, g.w, g.h, g.gp,
-                       g.tapR, IWp, IHmax, gx, gy, tiles, clr);
+    hipLaunchKernelGGL(gauss_kernel(g), dim3(((tiles + 7u) >> 3) * 8u), dim3(NT), L.bytes, s, b.in, b.gauss, b.taps, b.centres, g.W, g.H, g.w, g.h, g.gp,
+                       g.tapR, L.IWp, L.IHmax, gx, gy, tiles, clr);
 }
 
 void launch_remap_writeback(const Geom& g, const Buffers& b, int n, hipStream_t s) {

@@ -18,6 +18,7 @@
 
 #include "lsd_devbuf.h"
 #include "lsd_internal.h"
+#include "k1_lds.h"
 
 using namespace lsdhip;
 
@@ -48,6 +49,7 @@ struct Workspace {
 struct lsd_ctx {
     int device = 0;
     int num_cus = 256;                 // compute units of the device
+    size_t max_lds = 0;                // LDS a workgroup may have (hipDeviceAttributeMaxSharedMemoryPerBlock): bounds K1's window (make_geom)
     uint32_t id_budget = 0xFFFF0u;     // curMap stamp ids a wave may use per run before it clears its stamps (lsd_debug_set_stamp_budget)
     int tun_soft = 0, tun_claim = 0, tun_feed = 3, tun_big = 0;   // region-stage schedule (0: default), see k_region.hip
     int tun_help = -1;                                             // helper wavefronts per image (-1: default, 0: none)
@@ -177,7 +179,8 @@ static const double* log_gamma_table(int count) {
     return tab.data();
 }
 
-static int make_geom(const lsd_params* p, int cols, int rows, Geom* g) {
+// c: the context whose device has to launch K1 on this geometry (its LDS limit, and lsd_last_error for that refusal)
+static int make_geom(lsd_ctx* c, const lsd_params* p, int cols, int rows, Geom* g) {
     if (!p || cols <= 0 || rows <= 0) return LSD_ERR_INVALID;
     if (!(p->sca > 0) || !(p->sig > 0) || !(p->angThre > 0) || p->pseBin < 1) return LSD_ERR_INVALID;
     if (p->pseBin > 1024) return LSD_ERR_UNSUPPORTED;
@@ -194,6 +197,16 @@ static int make_geom(const lsd_params* p, int cols, int rows, Geom* g) {
     g->sca = p->sca;
     g->tapR = tap_radius(p->sca, p->sig);
     if (g->tapR < 0 || g->tapR > kMaxTapRadius) return LSD_ERR_UNSUPPORTED;
+    // K1 stages a tile's whole source window in LDS (k1_lds.h): ~(23 / sca + 2 tapR) rows of (31 / sca + 2 tapR) bytes and 32 doubles.
+    // A window beyond what a workgroup of this device may have could not be launched: refused here, before anything is enqueued.
+    const size_t k1_bytes = k1_lds(p->sca, g->tapR).bytes;
+    if (k1_bytes > c->max_lds) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "sca = %g, sig = %g: the Gaussian's window needs %zu bytes of LDS per workgroup, the device has %zu",
+                 p->sca, p->sig, k1_bytes, c->max_lds);
+        c->err = msg;
+        return LSD_ERR_UNSUPPORTED;
+    }
     g->pseBin = p->pseBin;
     g->degThre = p->angThre / 180.0 * kPi;                          // :148
     g->gradThre = 2.0 / sin(g->degThre);                            // :149
@@ -415,6 +428,11 @@ int lsd_create(lsd_ctx** out, int device) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->num_cus = cus;
     }
+    {   // make_geom holds K1's window against this: without it no parameter set could be accepted or refused honestly
+        int lds = 0;
+        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || lds <= 0) { delete c; return LSD_ERR_HIP; }
+        c->max_lds = (size_t)lds;
+    }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return LSD_ERR_HIP; }
     for (auto& e : c->ev)
         if (hipEventCreate(&e) != hipSuccess) { delete c; return LSD_ERR_HIP; }
@@ -516,7 +534,7 @@ int lsd_reserve(lsd_ctx* c, int n, int cols, int rows) {
     if (!c || n <= 0) return LSD_ERR_INVALID;
     lsd_params p; lsd_default_params(&p);
     Geom g;
-    int st = make_geom(&p, cols, rows, &g);
+    int st = make_geom(c, &p, cols, rows, &g);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
     st = ensure_workspace(c, (size_t)n, (size_t)g.npx, (size_t)g.gp * g.h, c->ws.cap_max_lines, c->trace);
@@ -533,7 +551,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
                              void* stream) {
     if (!c || !d_maps || n <= 0 || !d_lines || !d_counts || max_lines <= 0) return LSD_ERR_INVALID;
     Geom g;
-    int st = make_geom(p, cols, rows, &g);
+    int st = make_geom(c, p, cols, rows, &g);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
@@ -541,6 +559,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     if (st != LSD_OK) return st;
     st = ensure_tables(c, p, g, s);
     if (st != LSD_OK) return st;
+    HIPCHK(c, prepare_gauss(g));
     // the workspace is shared by every enqueue of this context: work queued on another stream must be over first
     if (c->done_valid && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
 
@@ -708,7 +727,7 @@ int lsd_run_batch(lsd_ctx* c, uint8_t* maps, int n, int cols, int rows, const ls
     if (!c || !maps || n <= 0 || !lines_out || !offsets_out) return LSD_ERR_INVALID;
     *lines_out = nullptr;
     Geom g;
-    int st = make_geom(p, cols, rows, &g);
+    int st = make_geom(c, p, cols, rows, &g);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t wh = (size_t)cols * rows;

@@ -118,6 +118,7 @@ struct SeedRec {  // mirrors oracle's orc_seed
 };
 
 // launchers (each enqueues on `s`)
+hipError_t prepare_gauss(const Geom& g);   // raises K1's dynamic-LDS limit where its window needs it; called before a call enqueues anything
 void launch_gauss(const Geom& g, const Buffers& b, int n, uint8_t* clr, hipStream_t s);   // clr: lineIm to be cleared on the way, or null
 void launch_remap_writeback(const Geom& g, const Buffers& b, int n, hipStream_t s);
 void launch_gradient(const Geom& g, const Buffers& b, int n, hipStream_t s);

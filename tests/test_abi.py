@@ -333,3 +333,43 @@ def test_region_kernel_keeps_its_registers_and_stays_out_of_scratch(tmp_path):
     # (592 B: the stages are capped at 168 registers of which the calling convention leaves 104 free of a save; grow() needs ~146 at once
     #  and so saves 43 callee-saved registers per call whether or not it calls anything -- DESIGN.md section 5, "K4's HBM traffic")
     assert int(re.search(r"; ScratchSize: (\d+)", kern).group(1)) <= 620
+
+
+def _tap_radius(sca, sig):
+    """myLSD.cpp:390-393, as lsd_ctx.hip's tap_radius restates it."""
+    import math
+    if sca < 1:
+        sig = sig / sca
+    return int(math.ceil(sig * math.sqrt(2 * 3 * math.log(10))))
+
+
+def test_k1_lds_formula_is_pinned(tmp_path):
+    """The LDS a workgroup of K1 needs (csrc/k1_lds.h: what launch_gauss asks for and what make_geom holds against the device's limit),
+    compiled with the host compiler.  The byte counts are those of a 32 x 24 tile: a change of the tile, of the pitch's slack or of the
+    window's bound changes them, and with them the smallest scale the library accepts (160 KiB of LDS: sca = 0.12 fits, 0.1 does not)."""
+    so = str(tmp_path / "libk1lds_host.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-o", so, os.path.join(ROOT, "tests", "k1_lds_host.cpp"), "-lm"],
+                   check=True)
+    L = C.CDLL(so)
+    L.k1_lds_bytes.restype = C.c_long
+    L.k1_lds_bytes.argtypes = [C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    assert (L.k1_tile_w(), L.k1_tile_h()) == (32, 24)
+
+    def lds(sca, sig):
+        iwp, ih = C.c_int(), C.c_int()
+        b = L.k1_lds_bytes(sca, _tap_radius(sca, sig), C.byref(iwp), C.byref(ih))
+        r = _tap_radius(sca, sig)
+        assert iwp.value % 4 == 0 and (iwp.value // 4) % 2 == 1                  # whole words, odd pitch
+        assert b == ih.value * 32 * 8 + 3 * (2 * r + 1) * 8 + ih.value * iwp.value
+        return r, b
+
+    table = {0.3: (8, 37268), 0.2: (12, 64784), 0.15: (15, 95232), 0.12: (19, 131784), 0.1: (23, 176340)}
+    for sca, want in table.items():
+        assert lds(sca, 0.6) == want, sca
+    assert lds(0.3, 3.2) == (40, 73812)                                           # the largest tap radius the library takes
+    assert table[0.2][1] <= 64 * 1024 < table[0.15][1]                            # no attribute / attribute path of launch_gauss
+    assert table[0.12][1] <= 160 * 1024 < table[0.1][1]                           # accepted / refused on a CU with 160 KiB
+    for sig in (0.6, 1.0, 2.1):                                                   # monotone in 1/sca at fixed sig
+        inv = np.linspace(0.5, 12.0, 2301)
+        b = np.array([lds(1.0 / v, sig)[1] for v in inv])
+        assert np.all(np.diff(b) >= 0), sig

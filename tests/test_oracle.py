@@ -201,6 +201,12 @@ def test_oracle_asan_clean(maps, oracle):
         "for k in ('map1', 'aisle1'):\n"
         "    r = oracle.lsd(z[k].copy(), debug=True, _lib=L)\n"
         "    oracle.map_cache(z[k].copy(), 0.05, _lib=L)\n"
+        # the widest reflection windows (tap radius 23 / 40) and the upsampled indexing (w > W) of the thing everything is compared against
+        "for sca in (0.1, 1.0, 2.0):\n"
+        "    oracle.lsd(z['map1'].copy(), sca=sca, debug=True, _lib=L)\n"
+        "tiny = np.random.default_rng(11).choice(np.array([0, 1, 255], np.uint8), size=(10, 10))\n"
+        "d = oracle.lsd(tiny, sig=3.2, debug=True, _lib=L)['dbg']\n"
+        "assert (d['w'], d['h']) == (3, 3) and np.isfinite(d['gauss']).all()\n"
         "print('OK')\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), so,
          os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "maps.npz"))
@@ -211,6 +217,23 @@ def test_oracle_asan_clean(maps, oracle):
     env = dict(os.environ, LD_PRELOAD=asan[-1], ASAN_OPTIONS="detect_leaks=0")
     p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "OK" in p.stdout, p.stderr[-2000:]
+
+
+def test_unit_scale_returns_the_rectangles_as_the_seed_loop_left_them(maps, oracle):
+    """myLSD.cpp:252-258 (lsd_oracle.c: `if (sca != 1)`): at sca == 1 the end points that come back are those of the rectangle the seed
+    loop produced; at any other scale (v - 1) / sca + 1 holds to the bit.  (At sca == 1 that expression is the identity in fp64 for
+    v >= 0.5, which every end point is: the first half pins "unscaled", it cannot tell which side of the comparison ran.)"""
+    for name in ("map1", "mapValue"):
+        r = oracle.lsd(maps[name].copy(), sca=1.0, debug=True)
+        recs, lines = r["dbg"]["recs"], r["lines"]                     # recs: structRec as the seed loop left it (x1 y1 x2 y2 first)
+        assert len(lines) == len(recs) > 10
+        for k, f in enumerate(("x1", "y1", "x2", "y2")):
+            assert np.array_equal(lines[f], recs[:, k]), (name, f)
+        r = oracle.lsd(maps[name].copy(), sca=0.5, debug=True)
+        recs, lines = r["dbg"]["recs"], r["lines"]
+        assert len(lines) == len(recs) > 10
+        for k, f in enumerate(("x1", "y1", "x2", "y2")):
+            assert np.array_equal(lines[f], (recs[:, k] - 1.0) / 0.5 + 1), (name, f)
 
 
 def test_occupancy_to_map_exhaustive(oracle):

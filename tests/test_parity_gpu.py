@@ -373,6 +373,149 @@ def test_synthetic_ragged_sizes(seed, rows, cols, lsdmod, ctx, oracle):
     full_check(lsdmod, ctx, oracle, synth(seed, rows, cols))
 
 
+def synth_tiny(seed, rows, cols):
+    """An image too small for synth()'s wall margins: free, occupied and unknown cells at random (a third each, roughly)."""
+    rng = np.random.default_rng(seed)
+    return rng.choice(np.array([0, 1, 255], np.uint8), size=(rows, cols), p=[0.4, 0.3, 0.3])
+
+
+# ---- the front end at every scale ----------------------------------------------------------------------------------------------
+# Each case names the branch of K1 (k_gauss.hip) or of the region stage's tail it is there for; LDS bytes are those of csrc/k1_lds.h
+# (tests/test_abi.py::test_k1_lds_formula_is_pinned).  image: a fixture's name, (name, rows, cols) for its top-left part, or
+# ("synth" | "tiny", seed, rows, cols).
+def _sweep_image(spec, maps):
+    if isinstance(spec, str):
+        return maps[spec]
+    if spec[0] == "synth":
+        return synth(*spec[1:])
+    if spec[0] == "tiny":
+        return synth_tiny(*spec[1:])
+    return np.ascontiguousarray(maps[spec[0]][:spec[1], :spec[2]])
+
+
+def _sweep_cases():
+    aisle2_cut = ("aisle2", 600, 1600)
+    cases = []
+
+    def add(why, images, params):
+        for im in images:
+            for kw in params:
+                name = im if isinstance(im, str) else "%s%dx%d" % (im[0], im[-2], im[-1])
+                pid = "-".join("%s%.4g" % (k, v) for k, v in kw.items())
+                cases.append(pytest.param(im, kw, id="%s-%s-%s" % (why, name, pid)))
+
+    sca = lambda *v: [dict(sca=s) for s in v]
+    # widths that are multiples of 4, tap counts other than 17: the generic kernel's aligned-word staging of interior tiles
+    add("generic_plain_staging", ["map1", aisle2_cut], sca(0.25, 0.5, 0.8))
+    # 1377 columns: every tile of the generic kernel reflects / assembles its words byte by byte; gX % 3 tap phases at other strides
+    add("generic_reflecting_staging", ["mapValue"], sca(0.25, 1.0 / 3, 0.5, 0.7, 0.8))
+    # 17 taps at other scales: the unrolled kernel with another span, pitch and 5-word read offset than at sca = 0.3
+    add("k17_other_geometry", ["map1", "mapValue"], [dict(sca=0.5, sig=1.0), dict(sca=1.0, sig=2.1)])
+    # sca == 1: one source pixel per output pixel, and the rectangles come back unscaled (myLSD.cpp:252-258).  The cases fail if that
+    # side of the tail computes anything else; they cannot tell it from (v - 1) / 1 + 1, which is v to the bit for end points >= 0.5
+    add("unit_scale_no_rescale", ["map1", "mapValue", "aisle1"], sca(1.0))
+    # sca > 1: repeated window centres, w > W, every border tile reflects; 303 lines on mapValue at 2.0
+    add("upsampling", ["map1", "mapValue"], sca(1.5, 2.0))
+    # LDS of 64 784 B (just under 64 KiB: no attribute), 95 232 B and 131 784 B (hipFuncSetAttribute path)
+    add("large_lds_window", ["mapValue", "aisle1"], sca(0.2, 0.15, 0.12))
+    # tap radius 40 = kMaxTapRadius: 81 taps, 73 812 B
+    add("max_tap_radius", ["mapValue", "aisle1"], [dict(sca=0.3, sig=3.2)])
+    # the window is wider than twice the image: reflect_idx wraps more than once, in both axes
+    add("multiple_reflection", [("tiny", 11, 10, 10), ("tiny", 12, 9, 40)], [dict(sca=0.3, sig=3.2)])
+    # ragged tiles (sizes that are multiples of nothing) at a second and a third scale
+    add("ragged_tiles", [("synth", 2, 333, 517), ("synth", 3, 101, 999)], sca(0.5, 1.0))
+    return cases
+
+
+@pytest.fixture
+def own_ctx(lsdmod):
+    """A context per test: a workspace keeps the largest image count and the largest scaled size it has seen, and an upsampled map in
+    the module's shared context would be multiplied by the 512 images of the bench-batch tests."""
+    c = lsdmod.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("image,kw", _sweep_cases())
+def test_front_end_at_other_scales(image, kw, maps, lsdmod, own_ctx, oracle):
+    """The whole pipeline against the oracle at scales other than 0.3, with full_check's own assertions and tolerances."""
+    full = dict(sca=0.3, sig=0.6, angThre=22.5, denThre=0.7, pseBin=1024)
+    full.update(kw)
+    full_check(lsdmod, own_ctx, oracle, _sweep_image(image, maps), lsdmod.make_params(**full), kw=full)
+
+
+def _device_batch_against_oracle(lsdmod, ctx, oracle, batch, kw, max_lines=1024):
+    """One resident batch through the device entry point on torch's buffers and stream, every image against the oracle."""
+    import torch
+    n, rows, cols = batch.shape
+    d_maps = torch.from_numpy(batch.copy()).cuda()
+    d_lines = torch.zeros((n, max_lines, 10), dtype=torch.int64, device="cuda")
+    d_counts = torch.zeros(n, dtype=torch.int32, device="cuda")
+    d_ims = torch.full((n, rows, cols), 7, dtype=torch.uint8, device="cuda")
+    ctx.enqueue_device(d_maps.data_ptr(), n, cols, rows, d_lines.data_ptr(), max_lines, d_counts.data_ptr(),
+                       d_line_ims=d_ims.data_ptr(), params=lsdmod.make_params(**kw), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_maps.cpu().numpy(), batch)                        # read-only without the write-back flag
+    counts = d_counts.cpu().numpy()
+    raw = d_lines.cpu().numpy()
+    for i in range(n):
+        ref = oracle.lsd(batch[i].copy(), debug=True, **kw)
+        d = ref["dbg"]
+        assert counts[i] == len(ref["lines"]) <= max_lines, (i, kw)
+        assert np.array_equal(ctx.fetch(i, lsdmod.DBG_GAUSS, (d["w"], d["h"])), d["gauss"]), (i, kw)
+        assert np.array_equal((ctx.fetch(i, lsdmod.DBG_STATE, (d["w"], d["h"])) & 3).astype(np.uint8), d["used"]), (i, kw)
+        got = raw[i, :counts[i]].copy().view(np.uint8).reshape(-1, 80).view(lsdmod.LINE_DTYPE).reshape(-1)
+        assert_lines_close(got, ref["lines"])
+        assert np.array_equal(d_ims[i].cpu().numpy(), ref["lineIm"]), (i, kw)
+
+
+def test_one_context_across_scales_keeps_nothing_of_the_previous_geometry(maps, lsdmod, oracle):
+    """Three different images as a resident batch at sca = 0.5, the same three at sca = 1.0 on the same context directly afterwards,
+    then at the default parameters: the taps and window centres are replaced when the parameters change (ensure_tables), the workspace
+    is resized, and every run equals the oracle's."""
+    src = maps["map1"]
+    batch = np.stack([src, np.roll(src, 37, 1), src[::-1].copy()]).copy()
+    c = lsdmod.Context(0)                                                      # a context of its own: its first geometry is sca = 0.5
+    try:
+        for kw in (dict(sca=0.5), dict(sca=1.0), {}):
+            full = dict(sca=0.3, sig=0.6, angThre=22.5, denThre=0.7, pseBin=1024)
+            full.update(kw)
+            _device_batch_against_oracle(lsdmod, c, oracle, batch, full)
+    finally:
+        c.close()
+
+
+def test_window_beyond_the_lds_is_refused_before_anything_runs(maps, lsdmod, ctx):
+    """sca = 0.1, sig = 0.6: K1's window would need 176 340 B of LDS, more than a workgroup can have.  Refused by make_geom with
+    LSD_ERR_UNSUPPORTED through the host and the device entry point -- nothing is enqueued, no launch is attempted: the map and the
+    output buffers are untouched, and the context goes on.  (sca = 0.12, 131 784 B, is accepted: test_front_end_at_other_scales.)"""
+    import torch
+    img = maps["map1"].copy()
+    rows, cols = img.shape
+    P = lsdmod.make_params(sca=0.1, sig=0.6)
+    with pytest.raises(lsdmod.LsdError) as e:
+        ctx.run(img, P)
+    assert e.value.status == lsdmod.LSD_ERR_UNSUPPORTED
+    msg = ctx.L.lsd_last_error(ctx.h)
+    msg = msg.decode() if isinstance(msg, bytes) else msg
+    assert "176340" in msg and "LDS" in msg
+    assert np.array_equal(img, maps["map1"])
+    d_map = torch.from_numpy(maps["map1"].copy()).cuda()
+    d_lines = torch.full((1, 64, 10), 0x5a5a5a5a5a5a5a5a, dtype=torch.int64, device="cuda")
+    d_counts = torch.full((1,), -77, dtype=torch.int32, device="cuda")
+    d_im = torch.full((rows, cols), 0xa5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    with pytest.raises(lsdmod.LsdError) as e:
+        ctx.enqueue_device(d_map.data_ptr(), 1, cols, rows, d_lines.data_ptr(), 64, d_counts.data_ptr(), d_line_ims=d_im.data_ptr(),
+                           params=P, flags=lsdmod.LSD_FLAG_WRITEBACK_MAP, stream=torch.cuda.current_stream().cuda_stream)
+    assert e.value.status == lsdmod.LSD_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert np.array_equal(d_map.cpu().numpy(), maps["map1"])
+    assert bool((d_lines == 0x5a5a5a5a5a5a5a5a).all()) and int(d_counts[0]) == -77 and bool((d_im == 0xa5).all())
+    lines, _ = ctx.run(maps["map1"].copy())
+    assert len(lines) == 7
+
+
 def test_blank_and_minimum_images(lsdmod, ctx, oracle):
     lines, im = ctx.run(np.zeros((64, 80), np.uint8))
     assert len(lines) == 0 and not im.any()
@@ -723,7 +866,8 @@ def test_error_codes(maps, lsdmod, ctx):
     assert call(img.ctypes.data, 3, 3, 3, P) == lsdmod.LSD_ERR_INVALID                        # scaled size below 2x2
     assert call(img.ctypes.data, 70000, 4, 70000, P) == lsdmod.LSD_ERR_UNSUPPORTED            # coordinates are packed in 16 bits
     for field, val, want in (("pseBin", 2048, lsdmod.LSD_ERR_UNSUPPORTED), ("pseBin", 0, lsdmod.LSD_ERR_INVALID),
-                             ("sca", 0.0, lsdmod.LSD_ERR_INVALID), ("sig", -1.0, lsdmod.LSD_ERR_INVALID)):
+                             ("sca", 0.0, lsdmod.LSD_ERR_INVALID), ("sig", -1.0, lsdmod.LSD_ERR_INVALID),
+                             ("sca", 0.1, lsdmod.LSD_ERR_UNSUPPORTED)):        # K1's window (176 340 B at sig = 0.6) is beyond the LDS
         Q = lsdmod.make_params()
         setattr(Q, field, val)
         assert call(img.ctypes.data, cols, rows, cols, Q) == want, field
