@@ -242,7 +242,8 @@ typedef struct lsd_map_param { int oriMapCol, oriMapRow; double mapResol, mapOri
 int lsd_feature_scan_batch(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, lsd_map_param map_param,
                            int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line *lines_out, int *n_lines,
                            lsd_position *pts_out, int pts_cap, int *n_pts, double *lidar_pos, int *im_size);
-/* The same with every array resident on the device, asynchronous on `stream`. */
+/* The same with every array resident on the device, asynchronous on `stream`.  The running time grows with the pixel extent of a
+ * scan (the raster loops take one step per pixel of a line's extent, in one lane): the caller bounds the ranges. */
 int lsd_enqueue_feature_scan_batch_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
                                           lsd_map_param map_param, int region_point_limit, double thre_line, double line_dist_thre_m,
                                           lsd_line *d_lines_out, int *d_n_lines, lsd_position *d_pts_out, int pts_cap, int *d_n_pts,
