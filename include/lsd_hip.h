@@ -359,6 +359,23 @@ int lsd_enqueue_localize_resume_device(lsd_ctx *ctx, const double *d_map_cache, 
                                        const int *d_n_lines, const lsd_position *d_pts, int pts_cap, const int *d_n_pts,
                                        const double *d_lidar_pos, const lsd_position *d_odom, double map_resol, lsd_fa_carry *d_carry,
                                        lsd_fa_state *d_states, lsd_fa_report *d_reports, void *stream);
+/* The two loops above against a map that is still being made when the call is enqueued (lsd_enqueue_map_update_device on an earlier
+ * stream position): the map's line count is read ON THE DEVICE, by the one kernel that uses it (the pair list of :28-58), as
+ * min(max(*d_n_map, 0), map_lines_cap) -- the detector's count conventions: an overflowed count leaves the first map_lines_cap records
+ * valid, -1 (an image given up) none.  d_map_lines holds map_lines_cap records.  Everything the host sizes -- the context's workspace,
+ * the limit map_lines_cap * 360 <= 1 << 26 (LSD_ERR_UNSUPPORTED) -- is sized from map_lines_cap as the entries above size it from
+ * n_map; every other argument and rule is theirs.  LSD_ERR_INVALID also for a null d_n_map or map_lines_cap <= 0.  With *d_n_map ==
+ * n_map <= map_lines_cap the states and reports are those of the entries above, bit for bit. */
+int lsd_enqueue_localize_live_map_device(lsd_ctx *ctx, const double *d_map_cache, int cols, int rows, const lsd_line *d_map_lines,
+                                         int map_lines_cap, const int32_t *d_n_map, int n_seq, int frames_pitch, const int *n_frames,
+                                         const lsd_line *d_lines, const int *d_n_lines, const lsd_position *d_pts, int pts_cap,
+                                         const int *d_n_pts, const double *d_lidar_pos, const lsd_position *d_odom, double map_resol,
+                                         const lsd_fa_state *d_init, lsd_fa_state *d_states, lsd_fa_report *d_reports, void *stream);
+int lsd_enqueue_localize_resume_live_map_device(lsd_ctx *ctx, const double *d_map_cache, int cols, int rows, const lsd_line *d_map_lines,
+                                                int map_lines_cap, const int32_t *d_n_map, int n_seq, int frames_pitch, const int *n_frames,
+                                                const lsd_line *d_lines, const int *d_n_lines, const lsd_position *d_pts, int pts_cap,
+                                                const int *d_n_pts, const double *d_lidar_pos, const lsd_position *d_odom, double map_resol,
+                                                lsd_fa_carry *d_carry, lsd_fa_state *d_states, lsd_fa_report *d_reports, void *stream);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:
@@ -380,6 +397,29 @@ int lsd_occupancy_to_map(lsd_ctx *ctx, const int8_t *grid, int cols, int rows, u
 /* The same for n_cells device-resident cells (any number of equally sized grids back to back), asynchronous on
  * `stream`; both pointers 16-byte aligned.  Lets a map that arrives on the device never touch the host. */
 int lsd_enqueue_occupancy_to_map_device(lsd_ctx *ctx, const int8_t *d_grid, size_t n_cells, uint8_t *d_map, void *stream);
+
+/* --- the map callback as one enqueue ------------------------------------------------------------ */
+/* Replaces the body of mapCallback (LSD/main_on_linux.cpp:97-134) for a grid that is already on the device, asynchronous on `stream`,
+ * in the callback's order:
+ *   1. the cells of d_grid (rows x cols int8, packed) -> d_map (rows x cols uint8), as lsd_enqueue_occupancy_to_map_device (:108-124);
+ *   2. createMapCache(d_map, res, z_occ_max_dis) -> d_map_cache (rows x cols doubles), read BEFORE the detector rewrites the map (:130;
+ *      the callback passes z_occ_max_dis = 2, :126-127);
+ *   3. myLineSegmentDetector on d_map with LSD_FLAG_WRITEBACK_MAP (:132): d_map ends as the callback's mapValue does, d_lines (max_lines
+ *      records) and *d_count are structLSD.linesInfo / len_linesInfo, d_line_im (rows x cols uint8, or NULL) is structLSD.lineIm.
+ * *d_count follows lsd_enqueue_batch_device: above max_lines the map overflowed (its first max_lines records are valid), -1 the region
+ * stage gave the map up.  Argument errors -- a null pointer other than d_line_im, a non-positive size, d_grid or d_map not 16-byte
+ * aligned (LSD_ERR_INVALID), cols * rows >= 2^31 or parameters the detector refuses (LSD_ERR_UNSUPPORTED) -- are found before anything
+ * is enqueued.  Like every enqueue that uses the context's workspace, an update on another stream than the context's last detector run
+ * is ordered behind that run by an event (never a host wait); apart from that one context serves one stream at a time, so a caller
+ * that localises on one stream while maps are made on another gives the map side a context of its own (Localizer does). */
+int lsd_enqueue_map_update_device(lsd_ctx *ctx, const int8_t *d_grid, int cols, int rows, double res, double z_occ_max_dis,
+                                  const lsd_params *p, uint8_t *d_map, double *d_map_cache, lsd_line *d_lines, int max_lines,
+                                  int32_t *d_count, uint8_t *d_line_im, void *stream);
+/* Sizes what lsd_enqueue_map_update_device allocates for a cols x rows grid: lsd_reserve(ctx, 1, cols, rows) with the detector's record
+ * arrays for up to the host line capacity (lsd_set_host_max_lines, default 8192) per map, createMapCache's scratch, and the lookup
+ * tables of the default parameters.  After it an update of that size or smaller, with the default parameters and max_lines up to that
+ * capacity, makes no allocation, no blocking copy and no host wait. */
+int lsd_reserve_map_update(lsd_ctx *ctx, int cols, int rows);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

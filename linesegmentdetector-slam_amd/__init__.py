@@ -91,6 +91,7 @@ class LsdError(RuntimeError):
 _vp, _i, _sz, _dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_double
 _pi, _ppar = C.POINTER(C.c_int), C.POINTER(lsd_params)
 _localize_args = [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp]
+_live_map_args = _localize_args[:6] + [_vp] + _localize_args[6:]      # int n_map -> int map_lines_cap, const int32_t *d_n_map
 _ABI = {
     "lsd_create": (_i, [C.POINTER(_vp), _i]),
     "lsd_destroy": (None, [_vp]),
@@ -138,13 +139,17 @@ _ABI = {
     "lsd_debug_fa_fuse": (_i, [_vp, _vp, _i, lsd_position, lsd_position, _vp, _vp, _vp]),
     "lsd_fa_carry_init": (None, [_vp, _vp, lsd_position]),
     "lsd_enqueue_localize_resume_device": (_i, _localize_args),
+    "lsd_enqueue_localize_live_map_device": (_i, _live_map_args),
+    "lsd_enqueue_localize_resume_live_map_device": (_i, _live_map_args),
+    "lsd_enqueue_map_update_device": (_i, [_vp, _vp, _i, _i, _dbl, _dbl, _ppar, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "lsd_enqueue_laserscan_ingest_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
 }
 EXPORTED_SYMBOLS = list(_ABI)
-del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args
+del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args, _live_map_args
 
 _lib = None
 
@@ -464,6 +469,39 @@ class Context:
                                                                    nf.ctypes.data, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos,
                                                                    d_odom, float(map_resol), d_carry, d_states, d_reports, stream))
 
+    def enqueue_localize_live_map_device(self, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch, n_frames,
+                                         d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, d_states,
+                                         d_reports, stream=None):
+        """lsd_enqueue_localize_live_map_device: enqueue_localize_device with the map's line count read on the device (d_n_map: one
+        int32, held to 0..map_lines_cap; d_map_lines: map_lines_cap records)."""
+        nf = np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_live_map_device(self.h, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map,
+                                                                     n_seq, frames_pitch, nf.ctypes.data, d_lines, d_n_lines, d_pts, pts_cap,
+                                                                     d_n_pts, d_lidar_pos, d_odom, float(map_resol), d_init, d_states,
+                                                                     d_reports, stream))
+
+    def enqueue_localize_resume_live_map_device(self, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch,
+                                                n_frames, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol,
+                                                d_carry, d_states, d_reports, stream=None):
+        """lsd_enqueue_localize_resume_live_map_device: enqueue_localize_resume_device with the map's line count read on the device."""
+        nf = np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_resume_live_map_device(self.h, d_map_cache, cols, rows, d_map_lines, map_lines_cap,
+                                                                            d_n_map, n_seq, frames_pitch, nf.ctypes.data, d_lines, d_n_lines,
+                                                                            d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, float(map_resol),
+                                                                            d_carry, d_states, d_reports, stream))
+
+    def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
+                                  d_line_im=None, params=None, stream=None):
+        """lsd_enqueue_map_update_device: the map callback (cells -> map -> mapCache -> LSD with the map rewritten) as one enqueue on
+        raw device addresses; asynchronous."""
+        p = params or make_params()
+        return self._chk(self.L.lsd_enqueue_map_update_device(self.h, d_grid, cols, rows, float(res), float(z_occ_max_dis), C.byref(p), d_map,
+                                                              d_map_cache, d_lines, max_lines, d_count, d_line_im, stream))
+
+    def reserve_map_update(self, cols, rows):
+        """lsd_reserve_map_update: after it enqueue_map_update_device of a cols x rows grid (or a smaller one) never allocates or waits."""
+        self._chk(self.L.lsd_reserve_map_update(self.h, cols, rows))
+
     def occupancy_to_map(self, grid_i8):
         """lsd_occupancy_to_map on an int8 [rows, cols] OccupancyGrid; returns the uint8 map."""
         assert grid_i8.dtype == np.int8 and grid_i8.ndim == 2 and grid_i8.flags.c_contiguous
@@ -759,12 +797,55 @@ def lidar_frames_batch(lidar):
     return scans, lens
 
 
+def _cuda_stream(stream):
+    """The torch stream an enqueue goes on: `stream`, or the current one."""
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream()
+    if not isinstance(stream, torch.cuda.Stream):
+        raise LsdError(LSD_ERR_INVALID, "stream must be a torch.cuda.Stream (or None: the current stream)")
+    return stream
+
+
+def _occupancy_grid(d_grid, cols, rows, device):
+    """d_grid as the map update reads it: a contiguous CUDA int8 tensor of rows * cols cells (flat, or [rows, cols]) on `device`."""
+    import torch
+    if not isinstance(d_grid, torch.Tensor) or not d_grid.is_cuda or d_grid.dtype != torch.int8:
+        raise LsdError(LSD_ERR_INVALID, "d_grid must be a CUDA int8 tensor")
+    if d_grid.device.index != int(device):
+        raise LsdError(LSD_ERR_INVALID, "d_grid is on cuda:%d, the context on device %d" % (d_grid.device.index, int(device)))
+    if cols <= 0 or rows <= 0 or tuple(d_grid.shape) not in ((rows * cols,), (rows, cols)):
+        raise LsdError(LSD_ERR_INVALID, "d_grid must hold oriMapRow x oriMapCol cells, flat or [rows, cols]")
+    return d_grid.contiguous()
+
+
+class _MapSlot:
+    """One of a Localizer's two maps on the device: the map bytes, the cache, the line records and their count, the geometry the ticks
+    pass with them, and the two events of the hand-over."""
+
+    def __init__(self):
+        self.cells = self.cap_lines = 0          # what the tensors hold (grow-only)
+        self.map = self.mc = self.lines = self.count = None
+        self.cols = self.rows = 0
+        self.lines_cap = 0                       # the records the map's update could write: what the ticks hold the count to
+        self.n_host = None                       # set_map: the count as the host knows it; None: only the device does (set_map_device)
+        self.map_param = None
+        self.grid = None                         # the update's input, alive until the slot is filled again
+        self.ready = None                        # recorded behind the update that filled the slot
+        self.waited = set()                      # streams that have been put behind `ready`
+        self.last_stream = None                  # the stream of the last tick that read the slot (None: no tick since it was filled)
+        self.idle = None                         # recorded behind that tick when the ticks moved on to the other slot
+
+
 class Localizer:
     """The laser side of the ROS node (laserCallback, LSD/main_on_linux.cpp:48-90) for n_robots robots against one map, with the replay
     driver's frame loop (LSD/main_on_windows.cpp:80-180) carried from call to call: each step() advances every robot by its frames of the
     tick (FeatureScan, FeatureAssociation, the UKF and the angle bookkeeping on the device, one stream), and the result is the same, bit for
     bit, as one lsd_localize call over each robot's whole log.  The map (its cache and lines), the robots' carries (FA_CARRY_DTYPE) and the
-    FeatureScan staging live on the device (torch).  Like the context it uses, a Localizer serves one thread at a time."""
+    FeatureScan staging live on the device (torch).  The map side (mapCallback, :97-134) is set_map from host arrays or set_map_device
+    from a grid on the device: the Localizer holds two map slots, a new map is made in the one the ticks are not reading -- on a side
+    stream if the caller wants -- and handed over through events, so ticks keep running on the old map meanwhile.  Like the context it
+    uses, a Localizer serves one thread at a time, and its ticks one stream at a time."""
 
     def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
         import torch
@@ -773,6 +854,9 @@ class Localizer:
         self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
         self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self._cap = 0
+        self._slots, self._cur = (_MapSlot(), _MapSlot()), 1       # the ticks read slot _cur; a new map is made in the other one
+        self._lines_cap = 512
+        self._map_ctx = None
         self.set_map(map_cache, map_lines)
         self.reset(range(self.n_robots), odom0)
 
@@ -782,17 +866,131 @@ class Localizer:
         _, mapCache, LSD = mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=ctx)
         return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx)
 
+    def _fit(self, slot, cells, n_lines, keep=False):
+        """The slot's tensors for at least `cells` cells and n_lines records.  Growing them waits -- on the host -- for the ticks that
+        still read the slot and for the update that filled it; keep: what it holds moves over."""
+        import torch
+        if slot.cells >= cells and slot.cap_lines >= n_lines:
+            return
+        for ev in (slot.idle, slot.ready):
+            if ev is not None:
+                ev.synchronize()
+        if slot.last_stream is not None:
+            slot.last_stream.synchronize()
+        cells, n_lines = max(cells, slot.cells), max(n_lines, slot.cap_lines)
+        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
+        new = (z(cells, torch.uint8), z(cells, torch.float64), z(n_lines * 80, torch.uint8), z(1, torch.int32))
+        if keep and slot.cells:
+            for dst, src in zip(new, (slot.map, slot.mc, slot.lines, slot.count)):
+                dst[:src.numel()].copy_(src)
+        # the blocks may have served other work of this stream, and an update may write them from another one: that work is over first
+        torch.cuda.current_stream().synchronize()
+        slot.map, slot.mc, slot.lines, slot.count = new
+        slot.cells, slot.cap_lines = cells, n_lines
+
+    def _target(self, stream, cells, n_lines):
+        """The slot the ticks are not reading, large enough, with `stream` behind its last readers and its last update."""
+        slot = self._slots[1 - self._cur]
+        self._fit(slot, cells, n_lines)
+        for ev in (slot.idle, slot.ready):
+            if ev is not None:
+                stream.wait_event(ev)
+        return slot
+
+    def _hand_over(self, slot, stream, cols, rows, lines_cap, n_host, map_param, grid=None):
+        """`slot` has been filled on `stream`: the ticks from now on read it, once their stream is behind the update."""
+        import torch
+        slot.ready = torch.cuda.Event()
+        slot.ready.record(stream)
+        slot.waited = {stream.cuda_stream}
+        slot.cols, slot.rows, slot.lines_cap, slot.n_host, slot.map_param, slot.grid = cols, rows, lines_cap, n_host, map_param, grid
+        slot.idle = None
+        old = self._slots[self._cur]
+        if old is not slot and old.last_stream is not None:          # behind the last tick that read the map the ticks now leave
+            old.idle = torch.cuda.Event()
+            old.idle.record(old.last_stream)
+            old.last_stream = None
+        self._cur = self._slots.index(slot)
+        self.map_param = map_param
+
+    def _map_context(self):
+        # The map side has a context of its own (DESIGN.md 8.1.2): the detector's workspace and createMapCache's scratch belong to a
+        # context, which serves one stream at a time, and the ticks' context is busy on theirs while an update runs on a side stream.
+        if self._map_ctx is None:
+            self._map_ctx = Context(self.ctx.device)
+        return self._map_ctx
+
     def set_map(self, map_cache, map_lines, map_param=None):
-        """A new map (mapCallback); the robots keep their carries."""
+        """A new map (mapCallback) from host arrays or tensors; the robots keep their carries.  It is copied, on the current torch
+        stream, into the map slot the ticks are not reading, and the ticks after the call read that slot: the hand-over of
+        set_map_device, with the line count known to the host."""
         import torch
         mc = map_cache if isinstance(map_cache, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map_cache, np.float64))
-        self._mc = mc.to(device="cuda", dtype=torch.float64).contiguous()
-        self._rows, self._cols = self._mc.shape
+        rows, cols = mc.shape
         ml = np.ascontiguousarray(map_lines, LINE_DTYPE)
-        self._n_map = len(ml)
-        self._ml = torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()).cuda() if len(ml) else torch.zeros(80, dtype=torch.uint8, device="cuda")
-        if map_param is not None:
-            self.map_param = tuple(float(v) for v in map_param)
+        stream = torch.cuda.current_stream()
+        slot = self._target(stream, rows * cols, max(len(ml), 1))
+        slot.mc[:rows * cols].copy_(mc.reshape(-1))
+        if len(ml):
+            slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
+        slot.count.fill_(len(ml))
+        mp = self.map_param if map_param is None else tuple(float(v) for v in map_param)
+        self._hand_over(slot, stream, cols, rows, max(len(ml), 1), len(ml), mp)
+
+    def reserve_map(self, cols, rows, lines_cap=512):
+        """Sizes everything a set_map_device of a cols x rows grid (or a smaller one) and the ticks after it need: both map slots
+        (lines_cap records each: from now on a device-made map keeps its first lines_cap lines and the ticks' workspace is sized for
+        lines_cap x 360 pairs per robot), the map side's context (lsd_reserve_map_update) and the ticks' workspace.  A set-up call: it
+        waits for the device.  After it neither set_map_device nor the ticks wait for the device or allocate."""
+        import torch
+        cols, rows, lines_cap = int(cols), int(rows), int(lines_cap)
+        if cols <= 0 or rows <= 0 or lines_cap <= 0:
+            raise LsdError(LSD_ERR_INVALID, "cols, rows and lines_cap must be positive")
+        if lines_cap * 360 > 1 << 26:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
+        torch.cuda.synchronize()
+        for i, slot in enumerate(self._slots):
+            self._fit(slot, rows * cols, lines_cap, keep=i == self._cur)
+        self._lines_cap = lines_cap
+        self._map_context().reserve_map_update(cols, rows)
+        # a tick of no frames: nothing is launched, the workspace of n_robots sequences against lines_cap map lines is carved
+        S, cur = self.n_robots, self._slots[self._cur]
+        self._staging(S)
+        d_out = self._out.data_ptr()
+        self.ctx.enqueue_localize_resume_live_map_device(cur.mc.data_ptr(), cur.cols, cur.rows, cur.lines.data_ptr(), lines_cap,
+                                                         cur.count.data_ptr(), S, 1, np.zeros(S, np.int32), self._lines.data_ptr(),
+                                                         self._lens.data_ptr(), self._pts.data_ptr(), self.pts_cap, self._lens.data_ptr(),
+                                                         self._lp.data_ptr(), self._in.data_ptr(), cur.map_param[2], self._carry.data_ptr(),
+                                                         d_out, d_out, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+
+    def set_map_device(self, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream=None):
+        """mapCallback for an OccupancyGrid that is already on the device, without a host round trip: d_grid is a CUDA int8 tensor of
+        oriMapRow * oriMapCol cells (flat, or [rows, cols]), ready on `stream` (a torch.cuda.Stream; default: the current one).  The
+        whole callback (lsd_enqueue_map_update_device: cells, mapCache with the callback's z_occ_max_dis = 2, the detector) is enqueued
+        on `stream` into the map slot the ticks are NOT reading, behind an event recorded after the last tick that read that slot, and
+        an event is recorded behind it.  Ticks enqueued before this call keep the old map; the first tick after it puts its own stream
+        behind that event and reads the new slot -- the line count on the device (map_counts), map_param from this call's arguments.
+        Nothing here waits for the device once reserve_map covers the geometry; a larger grid, or more lines than the slot holds, makes
+        the slot grow first, which waits on the host for the ticks that still read it and for its last update.  A map with more than
+        lines_cap lines (reserve_map; default 512) keeps its first lines_cap: step() then raises LSD_ERR_CAPACITY, a step_device
+        caller checks map_counts."""
+        cols, rows = int(oriMapCol), int(oriMapRow)
+        grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
+        stream = _cuda_stream(stream)
+        mctx = self._map_context()
+        slot = self._target(stream, rows * cols, self._lines_cap)
+        mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, float(mapResol), 2.0, slot.map.data_ptr(), slot.mc.data_ptr(),
+                                       slot.lines.data_ptr(), self._lines_cap, slot.count.data_ptr(), None, None, stream.cuda_stream)
+        self._hand_over(slot, stream, cols, rows, self._lines_cap, None, (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY)),
+                        grid)
+
+    @property
+    def map_counts(self):
+        """The line count of the map the next tick reads: a CUDA int32 tensor of one element, valid once the update that makes the map
+        has run (the caller's synchronisation).  Above lines_cap: the ticks use the first lines_cap lines; -1: the detector gave the map
+        up and the ticks see no map lines."""
+        return self._slots[self._cur].count
 
     def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
         """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot)."""
@@ -827,7 +1025,7 @@ class Localizer:
         if n <= self._cap:
             return
         z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
-        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B, torch.uint8)
+        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + 8, torch.uint8)     # (+ the map's line count of step())
         self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
         self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
         self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
@@ -858,9 +1056,17 @@ class Localizer:
         cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, _map_param(mp), rdp_leastPoint, rdp_threLine, rdp_leastDist,
                                                            self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np,
                                                            self._lp.data_ptr(), self._sz.data_ptr(), stream))
-        cx.enqueue_localize_resume_device(self._mc.data_ptr(), self._cols, self._rows, self._ml.data_ptr(), self._n_map, S, k, nf,
-                                          self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od,
-                                          mp[2], self._carry.data_ptr(), d_st, d_rp, stream)
+        m, ts = self._slots[self._cur], torch.cuda.current_stream()
+        if ts.cuda_stream not in m.waited:                                   # the first tick of this stream on a new map: behind its update
+            ts.wait_event(m.ready)
+            m.waited.add(ts.cuda_stream)
+        m.last_stream = ts
+        tail = (S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od, mp[2],
+                self._carry.data_ptr(), d_st, d_rp, stream)
+        if m.n_host is not None:
+            cx.enqueue_localize_resume_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.n_host, *tail)
+        else:                                                                # a map made on the device: so is its line count
+            cx.enqueue_localize_resume_live_map_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.lines_cap, m.count.data_ptr(), *tail)
         return b_st, b_rp
 
     def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
@@ -923,7 +1129,9 @@ class Localizer:
         FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots past a robot's n_frames are zero.  Raises LsdError(LSD_ERR_CAPACITY)
         with (states, reports) in `partial` if a scan marks more than pts_cap pixels or has more than 360 lines (the records are then
         computed from the stored part), as lsd_localize does.  One upload (the raw frames, the odometry, the take flags), the device
-        tick of step_device, one read-back."""
+        tick of step_device, one read-back.  Raises LsdError(LSD_ERR_CAPACITY) as well, with (states, reports) in `partial`, when the
+        map the tick used was made on the device (set_map_device) and has more lines than its slot holds (the records are computed
+        from the first lines_cap of them), and LsdError(LSD_ERR_INTERNAL) when that map's count is -1."""
         import torch
         if (lidar is None) == (ranges is None):
             raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
@@ -959,10 +1167,20 @@ class Localizer:
         d_take = self._in.data_ptr() + len(host_in) - 4 * n
         self._in[:len(host_in)].copy_(torch.from_numpy(host_in))
         b_st, b_rp = self._enqueue(S, k, nf, d_src if ranges is None else None, None if ranges is None else d_src, d_ami, n_beams, d_take, d_od)
-        out = self._out[:n * self._OUT_B].cpu().numpy()                      # the tick's one synchronisation
+        m = self._slots[self._cur]
+        live = m.n_host is None                                              # a device-made map: its line count rides in the read-back
+        if live:
+            self._out[n * self._OUT_B:n * self._OUT_B + 4].view(torch.int32).copy_(m.count)
+        out = self._out[:n * self._OUT_B + (4 if live else 0)].cpu().numpy()  # the tick's one synchronisation
         states = out[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
         reports = out[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
-        counts = out[b_st + b_rp:].view(np.int32).reshape(2, n)
+        counts = out[b_st + b_rp:n * self._OUT_B].view(np.int32).reshape(2, n)
+        n_map = int(out[n * self._OUT_B:].view(np.int32)[0]) if live else m.n_host
+        if n_map < 0:
+            raise LsdError(LSD_ERR_INTERNAL, "the detector gave the map up (count -1): the tick saw no map lines", partial=(states, reports))
+        if n_map > m.lines_cap:
+            raise LsdError(LSD_ERR_CAPACITY, "the map has %d lines, its slot holds %d (reserve_map): the tick used the first %d"
+                           % (n_map, m.lines_cap, m.lines_cap), partial=(states, reports))
         if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
             raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
         return states, reports
@@ -978,6 +1196,27 @@ def mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=None):
     mapCache = cx.map_cache(mapValue, mapResol, 2.0)
     LSD = myLineSegmentDetector(mapValue, oriMapCol, oriMapRow, lsd_sca, lsd_sig, lsd_angThre, lsd_denThre, pseBin, ctx=cx)
     return mapValue, mapCache, LSD
+
+
+def mapCallback_device(d_grid, oriMapCol, oriMapRow, mapResol, ctx=None, stream=None, max_lines=8192):
+    """mapCallback for an OccupancyGrid that is already on the device (a CUDA int8 tensor of oriMapRow * oriMapCol cells, flat or
+    [rows, cols]), as one enqueue (lsd_enqueue_map_update_device) on `stream` (a torch.cuda.Stream; default: the current one), without
+    a synchronisation.  Returns CUDA tensors (map uint8 [rows, cols]: mapValue as the LSD call leaves it; map_cache float64 [rows,
+    cols]; lines uint8 [max_lines, 80]: LINE_DTYPE records, the first min(count, max_lines) valid; count int32 [1]: len_linesInfo, above
+    max_lines on overflow, -1 if the detector gave the map up; line_im uint8 [rows, cols]), readable after the caller's synchronisation."""
+    import torch
+    cx = ctx or default_context()
+    cols, rows = int(oriMapCol), int(oriMapRow)
+    grid = _occupancy_grid(d_grid, cols, rows, cx.device)
+    stream = _cuda_stream(stream)
+    with torch.cuda.stream(stream):                                          # (the outputs belong to the stream that writes them)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=grid.device)
+        m, mc, li = e((rows, cols), torch.uint8), e((rows, cols), torch.float64), e((rows, cols), torch.uint8)
+        lines, count = e((int(max_lines), 80), torch.uint8), e((1,), torch.int32)
+    cx.enqueue_map_update_device(grid.data_ptr(), cols, rows, float(mapResol), 2.0, m.data_ptr(), mc.data_ptr(), lines.data_ptr(), int(max_lines),
+                                 count.data_ptr(), li.data_ptr(), None, stream.cuda_stream)
+    grid.record_stream(stream)
+    return m, mc, lines, count, li
 
 
 def runLSD(MapGray, oriMapCol=None, oriMapRow=None, sca=lsd_sca, sig=lsd_sig, angThre=lsd_angThre,

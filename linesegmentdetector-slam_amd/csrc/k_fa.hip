@@ -110,7 +110,10 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
     // the pair list of :28-58 in its loop order
     const int n_scan = min(a.n_lines ? a.n_lines[slot] : a.n_scan_given, a.line_pitch);
     const lsd_line* sl = a.scan_lines + slot * a.line_pitch;
-    const long long total = (long long)max(n_scan, 0) * a.n_map;
+    // the map's line count: the host's, or the device's (a map update still in flight when the tick was enqueued) held to its capacity --
+    // an overflowed detector count leaves the first n_map records valid, a given-up image (-1) none
+    const int n_map = a.d_n_map ? min(max(*a.d_n_map, 0), a.n_map) : a.n_map;
+    const long long total = (long long)max(n_scan, 0) * n_map;
     int* pairs = a.pairs + (size_t)s * a.pair_cap * 2;
     int base = 0;
     for (long long b = 0; b < total; b += kFaThreads) {
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
         bool take = false;
         int cs = 0, cm = 0;
         if (q < total) {
-            cs = (int)(q / a.n_map); cm = (int)(q % a.n_map);
+            cs = (int)(q / n_map); cm = (int)(q % n_map);
             const double ls = sl[cs].len, lm = a.map_lines[cm].len, ld = ls * 0.35;   // ignoreScanLength, scanToMapDiff (baseFunc.h:80-82)
             take = !(ls < 40) && !(lm < ls - ld || lm > ls + ld);
         }

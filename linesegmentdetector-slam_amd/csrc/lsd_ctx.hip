@@ -118,6 +118,7 @@ struct lsd_ctx {
     bool ev_valid = false;
     hipEvent_t ev_done = nullptr;      // end of the last enqueue: a later enqueue on ANOTHER stream waits for it (shared workspace)
     bool done_valid = false;
+    hipStream_t done_stream = nullptr; // the stream ev_done was recorded on (last_stream moves with every entry point, this one with the detector only)
 };
 
 constexpr size_t kPinBytes = 32u << 20;   // two pinned staging buffers of this size per context
@@ -643,7 +644,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     if (c->stop_after == 0) launch_lines(g, b, n, s);
     HIPCHK(c, hipEventRecord(c->ev[5], s));
     HIPCHK(c, hipEventRecord(c->ev_done, s));
-    c->done_valid = true;
+    c->done_valid = true; c->done_stream = s;
     HIPCHK(c, hipGetLastError());
     c->ev_valid = true;
     c->hist_n = (c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION) ? n : 0;     // (the counter records of this launch: the next one's cost history)
@@ -883,15 +884,22 @@ int lsd_debug_fetch(lsd_ctx* c, int image, int what, void* out, size_t bytes) {
     return LSD_OK;
 }
 
+// createMapCache's scratch for n maps of `cells` cells (lsd_enqueue_map_cache_device): grow-only, nothing happens while it suffices
+static int reserve_map_cache(lsd_ctx* c, size_t n, size_t cells) {
+    const size_t need = n * cells;
+    HIPCHK(c, c->mc_claim.reserve(need)); HIPCHK(c, c->mc_fa.reserve(need * 2)); HIPCHK(c, c->mc_fb.reserve(need * 2));
+    HIPCHK(c, c->mc_ctl.reserve(n * (2 + 64)));                                        // frontier sizes + up to 64 chunk counts per map
+    return LSD_OK;
+}
+
 int lsd_enqueue_map_cache_device(lsd_ctx* c, const uint8_t* d_maps, int n, int cols, int rows, double res,
                                  double z_occ_max_dis, double* d_out, void* stream) {
     if (!c || !d_maps || !d_out || n <= 0 || cols <= 0 || rows <= 0 || !(res > 0) || !(z_occ_max_dis >= 0)) return LSD_ERR_INVALID;
     if ((long long)cols * rows >= (1ll << 31)) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
-    const size_t need = (size_t)n * cols * rows;
-    HIPCHK(c, c->mc_claim.reserve(need)); HIPCHK(c, c->mc_fa.reserve(need * 2)); HIPCHK(c, c->mc_fb.reserve(need * 2));
-    HIPCHK(c, c->mc_ctl.reserve((size_t)n * (2 + 64)));                                // frontier sizes + up to 64 chunk counts per map
+    const int rs = reserve_map_cache(c, (size_t)n, (size_t)cols * rows);
+    if (rs != LSD_OK) return rs;
     const int cell_radius = cvt_x86(floor(z_occ_max_dis / res));           // myLSD.cpp:13
     // few maps: spread each over G workgroups (kernel per level phase); many maps: one workgroup per map, one launch
     int G = (2 * c->num_cus) / n;
@@ -942,6 +950,50 @@ int lsd_occupancy_to_map(lsd_ctx* c, const int8_t* grid, int cols, int rows, uin
     HIPCHK(c, hipMemcpy2DAsync(map_out, map_stride, c->oc_out.get(), cols, cols, rows, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
+}
+
+int lsd_reserve_map_update(lsd_ctx* c, int cols, int rows) {
+    if (!c || cols <= 0 || rows <= 0) return LSD_ERR_INVALID;
+    if ((long long)cols * rows >= (1ll << 31)) return LSD_ERR_UNSUPPORTED;
+    int st = lsd_reserve(c, 1, cols, rows);                         // the detector's workspace and the tables of the default parameters
+    if (st != LSD_OK) return st;
+    // ... its record arrays for as many lines per map as the host entry points take (lsd_set_host_max_lines: 128 B each), which
+    // lsd_reserve leaves to the first enqueue because it is not told a capacity
+    Geom g;
+    lsd_params p; lsd_default_params(&p);
+    st = make_geom(c, &p, cols, rows, &g);
+    if (st != LSD_OK) return st;
+    st = ensure_workspace(c, 1, (size_t)g.npx, (size_t)g.gp * g.h, std::max(c->ws.cap_max_lines, c->host_max_lines), c->trace);
+    if (st != LSD_OK) return st;
+    return reserve_map_cache(c, 1, (size_t)cols * rows);
+}
+
+int lsd_enqueue_map_update_device(lsd_ctx* c, const int8_t* d_grid, int cols, int rows, double res, double z_occ_max_dis, const lsd_params* p,
+                                  uint8_t* d_map, double* d_map_cache, lsd_line* d_lines, int max_lines, int32_t* d_count, uint8_t* d_line_im,
+                                  void* stream) {
+    // every refusal of the three entries below, taken here: nothing is enqueued unless all of them accept
+    if (!c || !d_grid || !d_map || !d_map_cache || !d_lines || !d_count || max_lines <= 0 || cols <= 0 || rows <= 0 || !(res > 0) ||
+        !(z_occ_max_dis >= 0))
+        return LSD_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_grid) | reinterpret_cast<uintptr_t>(d_map)) & 15u) {
+        c->err = "map update: d_grid and d_map must be 16-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if ((long long)cols * rows >= (1ll << 31)) return LSD_ERR_UNSUPPORTED;
+    Geom g;
+    int st = make_geom(c, p, cols, rows, &g);
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // The detector's workspace and createMapCache's scratch are the context's: an update on another stream than the last detector run's
+    // goes behind the event that run recorded (an update ends with the detector, so the event covers its flood as well).
+    if (c->done_valid && c->done_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
+    const size_t cells = (size_t)cols * rows;
+    st = lsd_enqueue_occupancy_to_map_device(c, d_grid, cells, d_map, s);                                  // main_on_linux.cpp:108-124
+    if (st != LSD_OK) return st;
+    st = lsd_enqueue_map_cache_device(c, d_map, 1, cols, rows, res, z_occ_max_dis, d_map_cache, s);        // :130, before the detector rewrites the map
+    if (st != LSD_OK) return st;
+    return lsd_enqueue_batch_device(c, d_map, 1, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, d_line_im, d_lines, max_lines, d_count, s);   // :132
 }
 
 int lsd_enqueue_scan_to_map_match_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
@@ -1206,9 +1258,10 @@ void lsd_fa_carry_init(lsd_fa_carry* o, const lsd_fa_state* state, lsd_position 
 }
 
 // The replay loop of both device entry points: d_init (lsd_enqueue_localize_device, odometry n_seq x (frames_pitch + 1)) or d_carry
-// (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.
-static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map, int n_seq,
-                           int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
+// (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.  d_n_map (the live-map entries):
+// the map's line count is read on the device and n_map is its capacity; everything the host sizes is sized from n_map either way.
+static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
+                           const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
                            int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                            const lsd_fa_state* d_init, lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!c || !d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || n_seq <= 0 || frames_pitch <= 0 ||
@@ -1228,7 +1281,7 @@ static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int 
     hipStream_t s = (hipStream_t)stream;
     c->fa_nf.assign(n_frames, n_frames + n_seq);
     HIPCHK(c, hipMemcpyAsync(const_cast<int*>(a.n_frames), c->fa_nf.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
-    a.map_cache = d_map_cache; a.cols = cols; a.rows = rows; a.map_lines = d_map_lines; a.n_map = n_map;
+    a.map_cache = d_map_cache; a.cols = cols; a.rows = rows; a.map_lines = d_map_lines; a.n_map = n_map; a.d_n_map = d_n_map;
     a.scan_lines = d_lines; a.n_lines = d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
     a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = d_n_pts; a.pts_pitch = pts_cap;
     a.lidar_pos = d_lidar_pos; a.frames_pitch = frames_pitch; a.odom = d_odom; a.given = nullptr; a.map_resol = map_resol;
@@ -1248,7 +1301,7 @@ int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols,
                                 const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
                                 lsd_fa_report* d_reports, void* stream) {
     if (!d_init) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
                            d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
 }
 
@@ -1258,8 +1311,28 @@ int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, in
                                        const lsd_position* d_odom, double map_resol, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
                                        lsd_fa_report* d_reports, void* stream) {
     if (!d_carry) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
                            d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
+}
+
+int lsd_enqueue_localize_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
+                                         int map_lines_cap, const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames,
+                                         const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts, int pts_cap,
+                                         const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
+                                         const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
+    if (!d_init || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
+                           d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
+}
+
+int lsd_enqueue_localize_resume_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
+                                                int map_lines_cap, const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames,
+                                                const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts, int pts_cap,
+                                                const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
+                                                lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
+    if (!d_carry || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
+                           d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
 }
 
 int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,

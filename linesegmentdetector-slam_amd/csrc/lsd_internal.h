@@ -162,7 +162,7 @@ void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local
 constexpr int kFaCtl = 8, kFaAux = 4, kFaLdsMax = 1024;
 struct FaArgs {
     const double* map_cache; int cols, rows;
-    const lsd_line* map_lines; int n_map;
+    const lsd_line* map_lines; int n_map; const int32_t* d_n_map;                       // d_n_map (not null): the count lives on the device, n_map is its capacity
     const lsd_line* scan_lines; const int* n_lines; int n_scan_given; int line_pitch;   // n_lines null: n_scan_given lines
     const double* pts; const int* n_pts; int n_pts_given; int pts_pitch;                // n_pts null: n_pts_given points
     const double* lidar_pos;                                                            // 2 per slot

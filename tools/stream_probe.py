@@ -12,7 +12,18 @@ localize_probe.py staggers its sequences.  A tick is timed whole, from a warm Lo
   --input laserscan  the same from float32 ranges and (angle_min, angle_increment) per message.
 us_host_filter_median is the host's infinite-range filter (lidar_frames_batch) on the tick's frames, measured beside the tick: the cost
 Localizer.step contained before the filter moved onto the device.  One JSON line per S.
-Usage: tools/stream_probe.py [--robots 1,19,256] [--ticks 60] [--warm 3] [--input host|device|laserscan]"""
+
+--map-update: the map side instead, on the f3key map and log.  For every S, from "the OccupancyGrid is on the device" to "the first tick
+on the new map has finished" (the caller's synchronisation), --reps times per run, --runs runs of each path alternating in one session:
+  path host    what the map callback cost before the device-side update: the grid's download, mapCallback (three blocking host calls),
+               Localizer.set_map (the fp64 cache and the lines uploaded again), step_device;
+  path device  Localizer.set_map_device on a side stream, step_device on the current one: no host round trip, no synchronisation.
+Each run also steps --ticks ticks with ONE update a third of the way in, an event recorded behind every tick, and reports the longest and
+the median gap between two consecutive ticks' completions (us_gap_max / us_gap_median; the device clock).  One JSON line per S, path and
+run, then one summary line per S and path: the median of the runs' medians and, as spread, their range.  The probe reports; it asserts
+nothing.
+Usage: tools/stream_probe.py [--robots 1,19,256] [--ticks 60] [--warm 3] [--input host|device|laserscan]
+       tools/stream_probe.py --map-update [--robots 1,19,256] [--ticks 30] [--reps 5] [--runs 3]"""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -23,13 +34,77 @@ import fa_restatement as fr
 lsd = importlib.import_module("linesegmentdetector-slam_amd")
 
 
+def map_update(args):
+    m, mp, lid, odom = fr.load_log("f3key")
+    rows, cols = m.shape
+    p = [float(v) for v in mp]
+    grid = np.where(m == 0, -1, np.where(m == 255, 0, 100)).astype(np.int8)            # unknown / free / occupied cells
+    d_grid, d_lid, d_od = torch.from_numpy(grid).cuda(), torch.from_numpy(lid).cuda(), torch.from_numpy(odom).cuda()
+    ctx, side, T = lsd.Context(0), torch.cuda.Stream(), args.ticks
+    for S in (int(v) for v in args.robots.split(",")):
+        starts = np.array([(7 * s) % (len(lid) - T - args.reps) for s in range(S)])
+        od0 = odom[starts].copy(); od0[:, 0] = 0.0
+        loc = lsd.Localizer.from_occupancy_grid(grid.reshape(-1), cols, rows, p[2], p[3], p[4], S, odom0=od0, ctx=ctx)
+        loc.reserve_map(cols, rows)
+        d_starts = torch.from_numpy(starts).cuda()
+        ins = [(d_lid[d_starts + t][:, None].contiguous(), d_od[d_starts + t + 1][:, None].contiguous()) for t in range(T + args.reps)]
+
+        def host_update():
+            g = d_grid.cpu().numpy()                                     # the grid is on the device: the host path starts with its download
+            _, mc, LSD = lsd.mapCallback(g.reshape(-1), cols, rows, p[2], ctx=ctx)
+            loc.set_map(mc, LSD.linesInfo, p)
+            return LSD.len_linesInfo
+
+        def device_update():
+            loc.set_map_device(d_grid, cols, rows, p[2], p[3], p[4], stream=side)
+
+        for update in (host_update, device_update):                      # warm: code loaded, both slots and every workspace sized
+            update(); loc.step_device(*ins[0]); torch.cuda.synchronize()
+        n_lines = host_update()
+        meds = {"host": [], "device": []}
+        for run in range(args.runs):
+            for path, update in (("host", host_update), ("device", device_update)):
+                loc.reset(range(S), odom0=od0)
+                torch.cuda.synchronize()
+                ts = []
+                for r in range(args.reps):
+                    t0 = time.perf_counter()
+                    update()
+                    loc.step_device(*ins[r])
+                    torch.cuda.synchronize()                             # the caller's own: the first tick on the new map has finished
+                    ts.append(time.perf_counter() - t0)
+                evs = []
+                for t in range(T):
+                    if t == T // 3:
+                        update()
+                    loc.step_device(*ins[args.reps + t])
+                    evs.append(torch.cuda.Event(enable_timing=True)); evs[-1].record()
+                torch.cuda.synchronize()
+                gaps = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(T - 1)]) * 1e3
+                ts = np.array(ts) * 1e6
+                meds[path].append(float(np.median(ts)))
+                print(json.dumps(dict(mode="map-update", robots=S, path=path, run=run + 1, map="f3key", map_lines=n_lines, reps=args.reps,
+                                      us_update_to_tick_median=float(np.median(ts)), us_update_to_tick_min=float(ts.min()),
+                                      us_update_to_tick_max=float(ts.max()), ticks=T, us_gap_max=float(gaps.max()), gap_at=int(gaps.argmax()) + 1,
+                                      update_before_tick=T // 3, us_gap_median=float(np.median(gaps)))), flush=True)
+        for path, v in meds.items():
+            print(json.dumps(dict(mode="map-update", robots=S, path=path, summary=True, runs=args.runs, us_update_to_tick=float(np.median(v)),
+                                  spread=float(max(v) - min(v)))), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", default="1,19,256")
     ap.add_argument("--ticks", type=int, default=60)
     ap.add_argument("--warm", type=int, default=3)
     ap.add_argument("--input", choices=("host", "device", "laserscan"), default="host")
+    ap.add_argument("--map-update", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--runs", type=int, default=3)
     args = ap.parse_args()
+    if args.map_update:
+        return map_update(args)
     m, mp, lid, odom = fr.load_log("data")
     ctx = lsd.Context(0)
     mc = ctx.map_cache(m.copy(), float(mp[2]), lsd.z_occ_max_dis)
