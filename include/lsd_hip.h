@@ -376,6 +376,45 @@ int lsd_enqueue_localize_resume_live_map_device(lsd_ctx *ctx, const double *d_ma
                                                 const lsd_line *d_lines, const int *d_n_lines, const lsd_position *d_pts, int pts_cap,
                                                 const int *d_n_pts, const double *d_lidar_pos, const lsd_position *d_odom, double map_resol,
                                                 lsd_fa_carry *d_carry, lsd_fa_state *d_states, lsd_fa_report *d_reports, void *stream);
+/* A fleet on several maps in one call.  lsd_map_ref describes one device-resident map: what the entries above take as d_map_cache,
+ * cols, rows, d_map_lines, n_map (and d_n_map: NULL, or the live-map convention above with n_map as the capacity) and, from
+ * lsd_map_param, the three values FeatureScan and the loop read.  The table maps[n_maps] is a HOST array (as n_frames is): every field
+ * is checked on the host, and the entry copies it to the device from context-owned storage without waiting for the stream.  d_map_of is
+ * a DEVICE array of one int32 per sequence: the map id of sequence s, read when the kernels run, so re-assigning a robot is a device
+ * write.  An id outside 0..n_maps-1 (use -1) means the sequence sits the call out: its carry, its state and report slots keep their
+ * bytes, it counts no pairs and no candidates, FeatureScan writes counts 0 for its scans and nothing else, and no other sequence is
+ * affected.
+ *   lsd_enqueue_feature_scan_maps_device      lsd_enqueue_feature_scan_batch_device with mapResol / mapOriX / mapOriY of scan i taken
+ *                                             from map d_map_of[i / scans_per_seq] (the Localizer's slot layout: slot = s * k + t)
+ *   lsd_enqueue_localize_maps_device          lsd_enqueue_localize_device, sequence s against map d_map_of[s]
+ *   lsd_enqueue_localize_resume_maps_device   lsd_enqueue_localize_resume_device, likewise
+ * Every sequence gets, bit for bit, what it gets alone on its map through those entries.  The per-sequence workspace and the pair limit
+ * (LSD_ERR_UNSUPPORTED) are taken from the largest n_map of the table.  Refused before anything is enqueued: LSD_ERR_INVALID for
+ * n_maps <= 0, a null table, a null d_map_of, scans_per_seq <= 0, a map with cols or rows <= 0, n_map < 0, a null cache, null lines at
+ * n_map > 0 or mapResol not > 0 (and the argument errors of the entries above); LSD_ERR_UNSUPPORTED for n_maps > LSD_MAX_MAPS. */
+#define LSD_MAX_MAPS 64
+typedef struct lsd_map_ref {
+    const double   *d_map_cache;   /* rows x cols */
+    const lsd_line *d_map_lines;   /* n_map records (capacity when d_n_map is set) */
+    const int32_t  *d_n_map;       /* NULL: n_map is the count; else the count is read on the device and held to 0..n_map */
+    int cols, rows, n_map;
+    double mapResol, mapOriX, mapOriY;
+} lsd_map_ref;
+int lsd_enqueue_feature_scan_maps_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                         const lsd_map_ref *maps, int n_maps, const int32_t *d_map_of, int scans_per_seq,
+                                         int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line *d_lines_out,
+                                         int *d_n_lines, lsd_position *d_pts_out, int pts_cap, int *d_n_pts, double *d_lidar_pos,
+                                         int *d_im_size, void *stream);
+int lsd_enqueue_localize_maps_device(lsd_ctx *ctx, const lsd_map_ref *maps, int n_maps, const int32_t *d_map_of, int n_seq,
+                                     int frames_pitch, const int *n_frames, const lsd_line *d_lines, const int *d_n_lines,
+                                     const lsd_position *d_pts, int pts_cap, const int *d_n_pts, const double *d_lidar_pos,
+                                     const lsd_position *d_odom, const lsd_fa_state *d_init, lsd_fa_state *d_states,
+                                     lsd_fa_report *d_reports, void *stream);
+int lsd_enqueue_localize_resume_maps_device(lsd_ctx *ctx, const lsd_map_ref *maps, int n_maps, const int32_t *d_map_of, int n_seq,
+                                            int frames_pitch, const int *n_frames, const lsd_line *d_lines, const int *d_n_lines,
+                                            const lsd_position *d_pts, int pts_cap, const int *d_n_pts, const double *d_lidar_pos,
+                                            const lsd_position *d_odom, lsd_fa_carry *d_carry, lsd_fa_state *d_states,
+                                            lsd_fa_report *d_reports, void *stream);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:

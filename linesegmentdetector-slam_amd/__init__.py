@@ -51,6 +51,20 @@ class lsd_map_param(C.Structure):      # structMapParam, LSD/baseFunc.h:25-31
     _fields_ = [("oriMapCol", C.c_int), ("oriMapRow", C.c_int), ("mapResol", C.c_double), ("mapOriX", C.c_double), ("mapOriY", C.c_double)]
 
 
+LSD_MAX_MAPS = 64
+
+
+class lsd_map_ref(C.Structure):        # one device-resident map of the fleet entries (include/lsd_hip.h)
+    _fields_ = [("d_map_cache", C.c_void_p), ("d_map_lines", C.c_void_p), ("d_n_map", C.c_void_p), ("cols", C.c_int), ("rows", C.c_int),
+                ("n_map", C.c_int), ("mapResol", C.c_double), ("mapOriX", C.c_double), ("mapOriY", C.c_double)]
+
+
+# numpy view of lsd_map_ref: a table is an array of these (the pointers as integers, 0 = NULL)
+MAP_REF_DTYPE = np.dtype([("d_map_cache", "u8"), ("d_map_lines", "u8"), ("d_n_map", "u8"), ("cols", "i4"), ("rows", "i4"), ("n_map", "i4"),
+                          ("_pad", "i4"), ("mapResol", "f8"), ("mapOriX", "f8"), ("mapOriY", "f8")])
+assert MAP_REF_DTYPE.itemsize == 64 == C.sizeof(lsd_map_ref)
+
+
 class lsd_position(C.Structure):  # == structPosition, LSD/baseFunc.h:46-50
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("ang", C.c_double)]
 
@@ -91,6 +105,7 @@ class LsdError(RuntimeError):
 _vp, _i, _sz, _dbl = C.c_void_p, C.c_int, C.c_size_t, C.c_double
 _pi, _ppar = C.POINTER(C.c_int), C.POINTER(lsd_params)
 _localize_args = [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp]
+_maps_args = [_vp, _vp, _i, _vp] + _localize_args[6:16] + _localize_args[17:]   # the map and map_resol -> maps, n_maps, d_map_of
 _live_map_args = _localize_args[:6] + [_vp] + _localize_args[6:]      # int n_map -> int map_lines_cap, const int32_t *d_n_map
 _ABI = {
     "lsd_create": (_i, [C.POINTER(_vp), _i]),
@@ -141,6 +156,9 @@ _ABI = {
     "lsd_enqueue_localize_resume_device": (_i, _localize_args),
     "lsd_enqueue_localize_live_map_device": (_i, _live_map_args),
     "lsd_enqueue_localize_resume_live_map_device": (_i, _live_map_args),
+    "lsd_enqueue_feature_scan_maps_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_localize_maps_device": (_i, _maps_args),
+    "lsd_enqueue_localize_resume_maps_device": (_i, _maps_args),
     "lsd_enqueue_map_update_device": (_i, [_vp, _vp, _i, _i, _dbl, _dbl, _ppar, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -149,7 +167,7 @@ _ABI = {
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
 }
 EXPORTED_SYMBOLS = list(_ABI)
-del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args, _live_map_args
+del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args, _live_map_args, _maps_args
 
 _lib = None
 
@@ -490,6 +508,36 @@ class Context:
                                                                             d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, float(map_resol),
                                                                             d_carry, d_states, d_reports, stream))
 
+    def enqueue_feature_scan_maps_device(self, d_scans, d_lens, n_scans, stride, maps, d_map_of, scans_per_seq, d_lines_out, d_n_lines,
+                                         d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size, region_point_limit=rdp_leastPoint,
+                                         thre_line=rdp_threLine, line_dist_thre_m=rdp_leastDist, stream=None):
+        """lsd_enqueue_feature_scan_maps_device on device pointers: FeatureScan of n_scans scans, scan i with mapResol / mapOriX / mapOriY
+        of map d_map_of[i // scans_per_seq].  maps: a HOST table (map_table); d_map_of: device int32, one id per sequence, an id outside
+        the table: the sequence's scans get counts 0 and nothing else."""
+        tab = map_table(maps)
+        return self._chk(self.L.lsd_enqueue_feature_scan_maps_device(self.h, d_scans, d_lens, int(n_scans), int(stride), tab.ctypes.data,
+                                                                     len(tab), d_map_of, int(scans_per_seq), int(region_point_limit),
+                                                                     float(thre_line), float(line_dist_thre_m), d_lines_out, d_n_lines,
+                                                                     d_pts_out, int(pts_cap), d_n_pts, d_lidar_pos, d_im_size, stream))
+
+    def enqueue_localize_maps_device(self, maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts,
+                                     d_lidar_pos, d_odom, d_init, d_states, d_reports, stream=None):
+        """lsd_enqueue_localize_maps_device: enqueue_localize_device with sequence s against map d_map_of[s] of the HOST table `maps`
+        (map_table); an id outside the table: the sequence sits the call out."""
+        tab, nf = map_table(maps), np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_maps_device(self.h, tab.ctypes.data, len(tab), d_map_of, int(n_seq), int(frames_pitch),
+                                                                 nf.ctypes.data, d_lines, d_n_lines, d_pts, int(pts_cap), d_n_pts, d_lidar_pos,
+                                                                 d_odom, d_init, d_states, d_reports, stream))
+
+    def enqueue_localize_resume_maps_device(self, maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap, d_n_pts,
+                                            d_lidar_pos, d_odom, d_carry, d_states, d_reports, stream=None):
+        """lsd_enqueue_localize_resume_maps_device: enqueue_localize_resume_device with sequence s against map d_map_of[s]."""
+        tab, nf = map_table(maps), np.ascontiguousarray(n_frames, np.int32)
+        return self._chk(self.L.lsd_enqueue_localize_resume_maps_device(self.h, tab.ctypes.data, len(tab), d_map_of, int(n_seq),
+                                                                        int(frames_pitch), nf.ctypes.data, d_lines, d_n_lines, d_pts,
+                                                                        int(pts_cap), d_n_pts, d_lidar_pos, d_odom, d_carry, d_states,
+                                                                        d_reports, stream))
+
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
         """lsd_enqueue_map_update_device: the map callback (cells -> map -> mapCache -> LSD with the map rewritten) as one enqueue on
@@ -731,6 +779,23 @@ def _map_param(mp):
     return lsd_map_param(int(mp[0]), int(mp[1]), float(mp[2]), float(mp[3]), float(mp[4]))
 
 
+def map_ref(d_map_cache, cols, rows, d_map_lines, n_map, map_param, d_n_map=0):
+    """One MAP_REF_DTYPE record: device addresses (integers) of the cache, the line records and -- or 0 -- the device-side line count,
+    the geometry, and mapResol / mapOriX / mapOriY from map_param = (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY)."""
+    r = np.zeros(1, MAP_REF_DTYPE)[0]
+    r["d_map_cache"], r["d_map_lines"], r["d_n_map"] = int(d_map_cache or 0), int(d_map_lines or 0), int(d_n_map or 0)
+    r["cols"], r["rows"], r["n_map"] = int(cols), int(rows), int(n_map)
+    r["mapResol"], r["mapOriX"], r["mapOriY"] = float(map_param[2]), float(map_param[3]), float(map_param[4])
+    return r
+
+
+def map_table(maps):
+    """The host table the fleet entries take: a contiguous MAP_REF_DTYPE array from an array or a sequence of map_ref records."""
+    if isinstance(maps, np.ndarray) and maps.dtype == MAP_REF_DTYPE:
+        return np.ascontiguousarray(maps).reshape(-1)
+    return np.array(list(maps), MAP_REF_DTYPE).reshape(-1)
+
+
 def fa_state(state):
     """An FA_STATE_DTYPE array of one record from a record, or from (kalman_x [9], kalman_P [9, 9] indexed P[i, j])."""
     if isinstance(state, np.void) or (isinstance(state, np.ndarray) and state.dtype == FA_STATE_DTYPE):
@@ -837,7 +902,123 @@ class _MapSlot:
         self.idle = None                         # recorded behind that tick when the ticks moved on to the other slot
 
 
-class Localizer:
+class _Ticks:
+    """What Localizer and FleetLocalizer share: the robots' carries on the device, the FeatureScan staging and the device tick's front
+    (step_device: the checks of its inputs, the take flags, the views of the output staging).  A subclass supplies _enqueue, the tick's
+    launches against its map or maps."""
+
+    def __init__(self, ctx, n_robots, pts_cap):
+        import torch
+        self.ctx = ctx or default_context()
+        self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
+        self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._cap = 0
+        self._held = None
+
+    def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
+        """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot)."""
+        import torch
+        idx = [int(r) for r in robots]
+        if not idx:
+            return
+        o = np.broadcast_to(np.asarray(odom0, np.float64).reshape(-1, 3), (len(idx), 3))
+        rec = np.stack([Context.fa_carry_init(state, o[i]) for i in range(len(idx))])
+        self._carry.view(self.n_robots, -1)[torch.tensor(idx, device="cuda")] = torch.from_numpy(rec.view(np.uint8).reshape(len(idx), -1)).cuda()
+
+    @property
+    def carries(self):
+        """The robots' carries, FA_CARRY_DTYPE [n_robots] on the host (a checkpoint)."""
+        return self._carry.cpu().numpy().view(FA_CARRY_DTYPE).copy()
+
+    @carries.setter
+    def carries(self, rec):
+        import torch
+        rec = np.ascontiguousarray(rec, FA_CARRY_DTYPE).reshape(-1)
+        if len(rec) != self.n_robots:
+            raise LsdError(LSD_ERR_INVALID, "one carry per robot")
+        self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
+
+    # per frame slot: the tick's inputs (one upload) the RAW scan (360 x 2 doubles, or less: the LaserScan floats), the odometry row, the
+    # take flag; the scan as FeatureScan reads it (k_ingest's output) and its length; its outputs (one read-back) the state, the report,
+    # FeatureScan's line and pixel counts
+    _IN_B, _OUT_B = 5760 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
+
+    def _staging(self, n):
+        import torch
+        if n <= self._cap:
+            return
+        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
+        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + 8, torch.uint8)     # (+ the map's line count of step())
+        self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
+        self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
+        self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
+        self._cap = n
+
+    def _n_frames(self, n_frames, S, k):
+        nf = np.full(S, k, np.int32) if n_frames is None else np.ascontiguousarray(n_frames, np.int32).reshape(S)
+        if (nf < 0).any() or (nf > k).any():
+            raise LsdError(LSD_ERR_INVALID, "n_frames outside 0..k")
+        return nf
+
+    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
+        """The tick on the current torch stream, every input on the device; returns the byte sizes of the states and the reports in
+        self._out."""
+        raise NotImplementedError
+
+    def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
+        """step() for a caller whose scans are on the device, without an upload, a read-back or a synchronisation: everything is enqueued
+        on the current torch stream.  Either lidar, a CUDA float64 tensor [S, k, 360, 2] of raw (range, angle) frames, or ranges, a CUDA
+        float32 tensor [S, k, B <= 360] with angle_min_inc CUDA float32 [S, k, 2] (sensor_msgs/LaserScan: ranges[], angle_min,
+        angle_increment; the angle of beam i is angle_min + i * angle_increment in single precision, as laserCallback computes it).
+        Readings whose range is +inf are dropped on the device (-inf and NaN are kept, as the reference's `!= INFINITY` keeps them).
+        odom: CUDA float64 [S, k, 3]; n_frames: as in step(), a HOST int array (when given, its take flags are one small asynchronous
+        upload).  Returns CUDA tensors (states uint8 [S, k, 720], reports uint8 [S, k, 72], counts int32 [2, S * k]): views of the
+        Localizer's own staging, valid until the next step*() call and, after the caller's synchronisation, readable as FA_STATE_DTYPE /
+        FA_REPORT_DTYPE records (`.cpu().numpy().view(FA_STATE_DTYPE)`); counts are FeatureScan's line and pixel counts per slot, for the
+        caller's own capacity check (more than 360 resp. pts_cap: the records are computed from the stored part).  Once the staging and the
+        context's workspace have their size (the first call, or a larger S * k) nothing here waits for the device."""
+        import torch
+        if (lidar is None) == (ranges is None):
+            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
+        src = lidar if ranges is None else ranges
+        want = torch.float64 if ranges is None else torch.float32
+        tensors = [("lidar" if ranges is None else "ranges", src, want), ("odom", odom, torch.float64)]
+        if ranges is not None:
+            tensors.append(("angle_min_inc", angle_min_inc, torch.float32))
+        for name, t, dt in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
+                raise LsdError(LSD_ERR_INVALID, "%s must be a CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
+        S = self.n_robots
+        k = src.shape[1] if src.dim() >= 2 else 0
+        if ranges is None:
+            if tuple(src.shape) != (S, k, 360, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
+            n_beams = 360
+        else:
+            n_beams = src.shape[2] if src.dim() == 3 else 0
+            if tuple(src.shape) != (S, k, n_beams) or k < 1 or not 1 <= n_beams <= 360:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            if tuple(angle_min_inc.shape) != (S, k, 2):
+                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
+        if tuple(odom.shape) != (S, k, 3):
+            raise LsdError(LSD_ERR_INVALID, "odom must be [n_robots, k, 3]")
+        nf = self._n_frames(n_frames, S, k)
+        self._staging(S * k)
+        take = None
+        if n_frames is not None:
+            # pinned, so the copy does not wait for the stream; torch's host allocator keeps the block until the copy has run
+            take = torch.from_numpy((np.arange(k)[None, :] < nf[:, None]).astype(np.int32)).pin_memory().to("cuda", non_blocking=True)
+        src, od = src.contiguous(), odom.contiguous()
+        ami = None if ranges is None else angle_min_inc.contiguous()
+        self._held = (src, od, ami, take)                                    # the launches read them: alive until the next tick
+        b_st, b_rp = self._enqueue(S, k, nf, src.data_ptr() if ranges is None else None, None if ranges is None else src.data_ptr(),
+                                   None if ami is None else ami.data_ptr(), n_beams, None if take is None else take.data_ptr(), od.data_ptr())
+        n = S * k
+        return (self._out[:b_st].view(S, k, -1), self._out[b_st:b_st + b_rp].view(S, k, -1),
+                self._out[b_st + b_rp:n * self._OUT_B].view(torch.int32).view(2, n))
+
+
+class Localizer(_Ticks):
     """The laser side of the ROS node (laserCallback, LSD/main_on_linux.cpp:48-90) for n_robots robots against one map, with the replay
     driver's frame loop (LSD/main_on_windows.cpp:80-180) carried from call to call: each step() advances every robot by its frames of the
     tick (FeatureScan, FeatureAssociation, the UKF and the angle bookkeeping on the device, one stream), and the result is the same, bit for
@@ -848,12 +1029,8 @@ class Localizer:
     uses, a Localizer serves one thread at a time, and its ticks one stream at a time."""
 
     def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
-        import torch
-        self.ctx = ctx or default_context()
+        super().__init__(ctx, n_robots, pts_cap)
         self.map_param = tuple(float(v) for v in map_param)
-        self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
-        self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        self._cap = 0
         self._slots, self._cur = (_MapSlot(), _MapSlot()), 1       # the ticks read slot _cur; a new map is made in the other one
         self._lines_cap = 512
         self._map_ctx = None
@@ -992,51 +1169,6 @@ class Localizer:
         up and the ticks see no map lines."""
         return self._slots[self._cur].count
 
-    def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
-        """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot)."""
-        import torch
-        idx = [int(r) for r in robots]
-        if not idx:
-            return
-        o = np.broadcast_to(np.asarray(odom0, np.float64).reshape(-1, 3), (len(idx), 3))
-        rec = np.stack([Context.fa_carry_init(state, o[i]) for i in range(len(idx))])
-        self._carry.view(self.n_robots, -1)[torch.tensor(idx, device="cuda")] = torch.from_numpy(rec.view(np.uint8).reshape(len(idx), -1)).cuda()
-
-    @property
-    def carries(self):
-        """The robots' carries, FA_CARRY_DTYPE [n_robots] on the host (a checkpoint)."""
-        return self._carry.cpu().numpy().view(FA_CARRY_DTYPE).copy()
-
-    @carries.setter
-    def carries(self, rec):
-        import torch
-        rec = np.ascontiguousarray(rec, FA_CARRY_DTYPE).reshape(-1)
-        if len(rec) != self.n_robots:
-            raise LsdError(LSD_ERR_INVALID, "one carry per robot")
-        self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
-
-    # per frame slot: the tick's inputs (one upload) the RAW scan (360 x 2 doubles, or less: the LaserScan floats), the odometry row, the
-    # take flag; the scan as FeatureScan reads it (k_ingest's output) and its length; its outputs (one read-back) the state, the report,
-    # FeatureScan's line and pixel counts
-    _IN_B, _OUT_B = 5760 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
-
-    def _staging(self, n):
-        import torch
-        if n <= self._cap:
-            return
-        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
-        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + 8, torch.uint8)     # (+ the map's line count of step())
-        self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
-        self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
-        self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
-        self._cap = n
-
-    def _n_frames(self, n_frames, S, k):
-        nf = np.full(S, k, np.int32) if n_frames is None else np.ascontiguousarray(n_frames, np.int32).reshape(S)
-        if (nf < 0).any() or (nf > k).any():
-            raise LsdError(LSD_ERR_INVALID, "n_frames outside 0..k")
-        return nf
-
     def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
         """The tick on the current torch stream, every input on the device: ingest, FeatureScan, the resume entry.  Returns the byte
         sizes of the states and the reports in self._out."""
@@ -1068,58 +1200,6 @@ class Localizer:
         else:                                                                # a map made on the device: so is its line count
             cx.enqueue_localize_resume_live_map_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.lines_cap, m.count.data_ptr(), *tail)
         return b_st, b_rp
-
-    def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
-        """step() for a caller whose scans are on the device, without an upload, a read-back or a synchronisation: everything is enqueued
-        on the current torch stream.  Either lidar, a CUDA float64 tensor [S, k, 360, 2] of raw (range, angle) frames, or ranges, a CUDA
-        float32 tensor [S, k, B <= 360] with angle_min_inc CUDA float32 [S, k, 2] (sensor_msgs/LaserScan: ranges[], angle_min,
-        angle_increment; the angle of beam i is angle_min + i * angle_increment in single precision, as laserCallback computes it).
-        Readings whose range is +inf are dropped on the device (-inf and NaN are kept, as the reference's `!= INFINITY` keeps them).
-        odom: CUDA float64 [S, k, 3]; n_frames: as in step(), a HOST int array (when given, its take flags are one small asynchronous
-        upload).  Returns CUDA tensors (states uint8 [S, k, 720], reports uint8 [S, k, 72], counts int32 [2, S * k]): views of the
-        Localizer's own staging, valid until the next step*() call and, after the caller's synchronisation, readable as FA_STATE_DTYPE /
-        FA_REPORT_DTYPE records (`.cpu().numpy().view(FA_STATE_DTYPE)`); counts are FeatureScan's line and pixel counts per slot, for the
-        caller's own capacity check (more than 360 resp. pts_cap: the records are computed from the stored part).  Once the staging and the
-        context's workspace have their size (the first call, or a larger S * k) nothing here waits for the device."""
-        import torch
-        if (lidar is None) == (ranges is None):
-            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
-        src = lidar if ranges is None else ranges
-        want = torch.float64 if ranges is None else torch.float32
-        tensors = [("lidar" if ranges is None else "ranges", src, want), ("odom", odom, torch.float64)]
-        if ranges is not None:
-            tensors.append(("angle_min_inc", angle_min_inc, torch.float32))
-        for name, t, dt in tensors:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt:
-                raise LsdError(LSD_ERR_INVALID, "%s must be a CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
-        S = self.n_robots
-        k = src.shape[1] if src.dim() >= 2 else 0
-        if ranges is None:
-            if tuple(src.shape) != (S, k, 360, 2) or k < 1:
-                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
-            n_beams = 360
-        else:
-            n_beams = src.shape[2] if src.dim() == 3 else 0
-            if tuple(src.shape) != (S, k, n_beams) or k < 1 or not 1 <= n_beams <= 360:
-                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
-            if tuple(angle_min_inc.shape) != (S, k, 2):
-                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
-        if tuple(odom.shape) != (S, k, 3):
-            raise LsdError(LSD_ERR_INVALID, "odom must be [n_robots, k, 3]")
-        nf = self._n_frames(n_frames, S, k)
-        self._staging(S * k)
-        take = None
-        if n_frames is not None:
-            # pinned, so the copy does not wait for the stream; torch's host allocator keeps the block until the copy has run
-            take = torch.from_numpy((np.arange(k)[None, :] < nf[:, None]).astype(np.int32)).pin_memory().to("cuda", non_blocking=True)
-        src, od = src.contiguous(), odom.contiguous()
-        ami = None if ranges is None else angle_min_inc.contiguous()
-        self._held = (src, od, ami, take)                                    # the launches read them: alive until the next tick
-        b_st, b_rp = self._enqueue(S, k, nf, src.data_ptr() if ranges is None else None, None if ranges is None else src.data_ptr(),
-                                   None if ami is None else ami.data_ptr(), n_beams, None if take is None else take.data_ptr(), od.data_ptr())
-        n = S * k
-        return (self._out[:b_st].view(S, k, -1), self._out[b_st:b_st + b_rp].view(S, k, -1),
-                self._out[b_st + b_rp:n * self._OUT_B].view(torch.int32).view(2, n))
 
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does,
@@ -1181,6 +1261,143 @@ class Localizer:
         if n_map > m.lines_cap:
             raise LsdError(LSD_ERR_CAPACITY, "the map has %d lines, its slot holds %d (reserve_map): the tick used the first %d"
                            % (n_map, m.lines_cap, m.lines_cap), partial=(states, reports))
+        if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
+            raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
+        return states, reports
+
+
+def fleet_map_ids(map_ids, n_maps, count=None):
+    """Map ids as the fleet entries read them: int32 [count], each a map of the table (0..n_maps-1) or -1 (the robot sits out)."""
+    ids = np.ascontiguousarray(map_ids, np.int32).reshape(-1)
+    if count is not None and len(ids) != count:
+        raise LsdError(LSD_ERR_INVALID, "one map id per robot")
+    if ((ids < -1) | (ids >= n_maps)).any():
+        raise LsdError(LSD_ERR_INVALID, "a map id is 0..%d, or -1 for a robot that sits out" % (n_maps - 1))
+    return ids
+
+
+class FleetLocalizer(_Ticks):
+    """Localizer for a fleet on several maps: every robot is ticked against the map its id names, all of them in ONE tick (one ingest,
+    one FeatureScan launch and one set of FeatureAssociation launches per frame index: lsd_enqueue_feature_scan_maps_device with
+    scans_per_seq = k, lsd_enqueue_localize_resume_maps_device), and each gets, bit for bit, what a Localizer on its map alone gives
+    it.  maps: a list of (map_cache, map_lines, map_param) host arrays, one per map id (at most LSD_MAX_MAPS), each uploaded once;
+    map_of: one id per robot -- this sets n_robots --, or -1 for a robot that sits out (parked, between floors): its carry stays as it
+    is and its slots of a tick's results stay zero.  The ids live on the device: assign() rewrites them on the current stream.  step,
+    step_device, reset and carries are as Localizer's (step_device, reset and carries are the same code).  The map side is host arrays only -- set_map(i, ...) --: the two-slot device
+    hand-over of one map (Localizer.set_map_device) has no per-map form here yet, although the C entries would take such a map (a table
+    record whose d_n_map points at the count lsd_enqueue_map_update_device writes)."""
+
+    def __init__(self, maps, map_of, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
+        import torch
+        maps = list(maps)
+        if not maps:
+            raise LsdError(LSD_ERR_INVALID, "at least one map")
+        if len(maps) > LSD_MAX_MAPS:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "more than LSD_MAX_MAPS = %d maps" % LSD_MAX_MAPS)
+        ids = fleet_map_ids(map_of, len(maps))
+        if not len(ids):
+            raise LsdError(LSD_ERR_INVALID, "at least one robot")
+        super().__init__(ctx, len(ids), pts_cap)
+        self._table = np.zeros(len(maps), MAP_REF_DTYPE)
+        self._tensors = [None] * len(maps)                                   # per map: the cache and the line records on the device
+        for i, m in enumerate(maps):
+            self.set_map(i, *m)
+        self._map_of = torch.from_numpy(ids).cuda()
+        self.reset(range(self.n_robots), odom0)
+
+    @property
+    def n_maps(self):
+        return len(self._table)
+
+    @property
+    def map_of(self):
+        """The robots' map ids, int32 [n_robots] on the host (a read-back)."""
+        return self._map_of.cpu().numpy()
+
+    def set_map(self, i, map_cache, map_lines, map_param):
+        """Replaces map i from host arrays: uploaded on the current torch stream -- the ticks' --, read by the ticks after the call.  The
+        robots on it keep their carries."""
+        import torch
+        i = int(i)
+        if not 0 <= i < len(self._table):
+            raise LsdError(LSD_ERR_INVALID, "map %d of %d" % (i, len(self._table)))
+        mc = np.ascontiguousarray(map_cache, np.float64)
+        ml = np.ascontiguousarray(map_lines, LINE_DTYPE).reshape(-1)
+        mp = tuple(float(v) for v in map_param)
+        if mc.ndim != 2 or not mc.size or len(mp) != 5 or not mp[2] > 0:
+            raise LsdError(LSD_ERR_INVALID, "map_cache is [rows, cols], map_param (oriMapCol, oriMapRow, mapResol > 0, mapOriX, mapOriY)")
+        if len(ml) * 360 > 1 << 26:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "map lines x 360 pairs per robot exceed 1 << 26")
+        d_mc = torch.from_numpy(mc).cuda()
+        d_ml = torch.from_numpy(ml.view(np.uint8).reshape(-1).copy() if len(ml) else np.zeros(80, np.uint8)).cuda()
+        self._tensors[i] = (d_mc, d_ml)
+        self._table[i] = map_ref(d_mc.data_ptr(), mc.shape[1], mc.shape[0], d_ml.data_ptr(), len(ml), mp)
+
+    def assign(self, robots, map_ids):
+        """Moves the given robots to the given maps (one id each, or one for all; -1: the robot sits out from now on): the ids are
+        rewritten on the device, on the current torch stream, without waiting for it.  The carries are NOT touched, and a carry is in
+        the pixel frame of the map it was made on: after a move to another map follow with reset(robots, odom0, state)."""
+        import torch
+        idx = np.ascontiguousarray([int(r) for r in robots], np.int64)
+        if not len(idx):
+            return
+        if ((idx < 0) | (idx >= self.n_robots)).any():
+            raise LsdError(LSD_ERR_INVALID, "a robot is 0..%d" % (self.n_robots - 1))
+        ids = np.asarray(map_ids, np.int32).reshape(-1)
+        ids = fleet_map_ids(np.repeat(ids, len(idx)) if len(ids) == 1 else ids, len(self._table), len(idx))
+        # pinned, so the copies do not wait for the stream (as the take flags of step_device)
+        up = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
+        self._map_of.index_copy_(0, up(idx), up(ids))
+
+    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
+        """Localizer's tick through the fleet entries: ingest, FeatureScan with each robot's map geometry, the resume loop with each
+        robot's map."""
+        import torch
+        n = S * k
+        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
+        self._out[:b_st + b_rp].zero_()
+        d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
+        d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
+        d_np = d_nl + 4 * n
+        cx, stream = self.ctx, torch.cuda.current_stream().cuda_stream
+        if d_raw is not None:
+            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
+        else:
+            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
+        d_of = self._map_of.data_ptr()
+        cx.enqueue_feature_scan_maps_device(d_sc, d_ln, n, 360, self._table, d_of, k, self._lines.data_ptr(), d_nl, self._pts.data_ptr(),
+                                            self.pts_cap, d_np, self._lp.data_ptr(), self._sz.data_ptr(), stream=stream)
+        cx.enqueue_localize_resume_maps_device(self._table, d_of, S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap,
+                                               d_np, self._lp.data_ptr(), d_od, self._carry.data_ptr(), d_st, d_rp, stream)
+        return b_st, b_rp
+
+    def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
+        """Localizer.step for the fleet: the same arguments, results and capacity error (LsdError(LSD_ERR_CAPACITY) with (states,
+        reports) in `partial` if a scan marks more than pts_cap pixels or has more than 360 lines).  The slots of a robot that sits out
+        are zero, like those past a robot's n_frames.  The host side differs from Localizer.step in one respect: the inputs are not
+        packed into one staging upload but uploaded as they are (the frames, the odometry, with ranges= the two float arrays; the take
+        flags by step_device), then the device tick of step_device and one read-back of the Localizer's output staging, whose layout
+        (states, reports, FeatureScan's counts) is the same."""
+        import torch
+        if (lidar is None) == (ranges is None):
+            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+        src = np.asarray(lidar, np.float64) if ranges is None else np.asarray(ranges, np.float32)
+        od = np.asarray(odom, np.float64)
+        if src.ndim >= 2 and od.size == src.shape[0] * src.shape[1] * 3:
+            od = od.reshape(src.shape[0], src.shape[1], 3)
+        if ranges is None:
+            out = self.step_device(up(src, np.float64), up(od, np.float64), n_frames)
+        else:
+            out = self.step_device(None, up(od, np.float64), n_frames, ranges=up(src, np.float32),
+                                   angle_min_inc=up(angle_min_inc, np.float32))
+        S, k = out[0].shape[:2]
+        n = S * k
+        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
+        host = self._out[:n * self._OUT_B].cpu().numpy()                       # the tick's one synchronisation
+        states = host[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
+        reports = host[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
+        counts = host[b_st + b_rp:].view(np.int32).reshape(2, n)
         if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
             raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
         return states, reports

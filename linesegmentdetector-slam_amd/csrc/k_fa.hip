@@ -72,11 +72,34 @@ __device__ __forceinline__ FaBook fa_book(const FaArgs& a, int s) {
     return {0.0, 0.0, false, 0};
 }
 
+// The map of sequence s: the single map of the arguments (kMaps false: the entries that take one map), or record map_of[s] of the table
+// (the fleet entries).  `live` false: the id is outside the table and the sequence sits the call out.  The sequence is the workgroup's
+// (blockIdx.y), so the id and the record are uniform: plain loads through a const __restrict__ pointer, which the compiler keeps scalar.
+// n_map is the count the pair list uses: the host's, or the device's (a map update still in flight when the tick was enqueued) held to
+// its capacity -- an overflowed detector count leaves the first n_map records valid, a given-up image (-1) none.
+struct FaMap { const double* cache; const lsd_line* lines; int cols, rows, n_map; double resol; bool live; };
+template <bool kMaps>
+__device__ __forceinline__ FaMap fa_map(const FaArgs& a, int s) {
+    if constexpr (!kMaps) {
+        return {a.map_cache, a.map_lines, a.cols, a.rows, a.d_n_map ? min(max(*a.d_n_map, 0), a.n_map) : a.n_map, a.map_resol, true};
+    } else {
+        const int32_t* __restrict__ of = a.map_of;
+        const int id = of[s];
+        if ((unsigned)id >= (unsigned)a.n_maps) return {nullptr, nullptr, 0, 0, 0, 1.0, false};
+        const lsd_map_ref* __restrict__ m = a.maps + id;
+        const int32_t* dn = m->d_n_map;
+        const int cap = m->n_map;
+        return {m->d_map_cache, m->d_map_lines, m->cols, m->rows, dn ? min(max(*dn, 0), cap) : cap, m->mapResol, true};
+    }
+}
+
+template <bool kMaps>
 __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
     const int s = blockIdx.y, tid = threadIdx.x;
     __shared__ int s_w[kFaThreads / 64];
-    const bool live = !a.n_frames || a.t < a.n_frames[s];
-    if (!live) {                                                   // past the end of this sequence: k_fa_match scores nothing
+    const FaMap mp = fa_map<kMaps>(a, s);
+    const bool live = (!a.n_frames || a.t < a.n_frames[s]) && mp.live;
+    if (!live) {                                                   // past the end of this sequence, or sitting out: k_fa_match scores nothing
         if (tid == 0) { a.n_pairs[s] = 0; a.n_cand[s] = 0; }
         return;
     }
@@ -97,7 +120,7 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
                 const double theta = bk.sum / bk.cnt;              // the mean of angRotate (0/0 if it is empty)
                 lsd_position o0, o1;
                 fa_odom(a, s, o0, o1);
-                const double tx = (o1.x - o0.x) / a.map_resol, ty = (o1.y - o0.y) / a.map_resol, ta = fa_atand(o1.ang - o0.ang);
+                const double tx = (o1.x - o0.x) / mp.resol, ty = (o1.y - o0.y) / mp.resol, ta = fa_atand(o1.ang - o0.ang);
                 double sd, cd;
                 sincos_g(deg2rad_ref(theta), sd, cd);
                 spx = tx * cd - ty * sd;
@@ -110,9 +133,7 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
     // the pair list of :28-58 in its loop order
     const int n_scan = min(a.n_lines ? a.n_lines[slot] : a.n_scan_given, a.line_pitch);
     const lsd_line* sl = a.scan_lines + slot * a.line_pitch;
-    // the map's line count: the host's, or the device's (a map update still in flight when the tick was enqueued) held to its capacity --
-    // an overflowed detector count leaves the first n_map records valid, a given-up image (-1) none
-    const int n_map = a.d_n_map ? min(max(*a.d_n_map, 0), a.n_map) : a.n_map;
+    const int n_map = mp.n_map;
     const long long total = (long long)max(n_scan, 0) * n_map;
     int* pairs = a.pairs + (size_t)s * a.pair_cap * 2;
     int base = 0;
@@ -122,7 +143,7 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
         int cs = 0, cm = 0;
         if (q < total) {
             cs = (int)(q / n_map); cm = (int)(q % n_map);
-            const double ls = sl[cs].len, lm = a.map_lines[cm].len, ld = ls * 0.35;   // ignoreScanLength, scanToMapDiff (baseFunc.h:80-82)
+            const double ls = sl[cs].len, lm = mp.lines[cm].len, ld = ls * 0.35;   // ignoreScanLength, scanToMapDiff (baseFunc.h:80-82)
             take = !(ls < 40) && !(lm < ls - ld || lm > ls + ld);
         }
         int cnt;
@@ -133,23 +154,30 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_prepare(FaArgs a) {
     if (tid == 0) { a.n_pairs[s] = base; a.n_cand[s] = 4 * base; }
 }
 
+template <bool kMaps>
 __global__ __launch_bounds__(64) void k_fa_match(FaArgs a) {
     const int s = blockIdx.y;
     const int n_cand = a.n_cand[s];                                // the count is the device's: a grid-stride loop over a small grid
+    const FaMap mp = fa_map<kMaps>(a, s);
+    if (!mp.live) return;                                          // (sitting out: k_fa_prepare left n_cand 0 as well)
     const size_t slot = (size_t)s * a.frames_pitch + a.t;
     const double* ctl = a.ctl + (size_t)s * kFaCtl;
     const int n_points = min(a.n_pts ? a.n_pts[slot] : a.n_pts_given, a.pts_pitch);
     for (int b = blockIdx.x * 64; b < n_cand; b += gridDim.x * 64) {     // uniform per workgroup (one wavefront)
         const int cidx = b + threadIdx.x;
-        match_candidate(cidx < n_cand, cidx, a.map_cache, a.cols, a.rows, a.map_lines, a.scan_lines + slot * a.line_pitch,
+        match_candidate(cidx < n_cand, cidx, mp.cache, mp.cols, mp.rows, mp.lines, a.scan_lines + slot * a.line_pitch,
                         a.pts + slot * a.pts_pitch * 3, n_points, ctl[0], ctl[1], ctl[2], ctl[3], a.pairs + (size_t)s * a.pair_cap * 2,
                         1.0 /* z_occ_max_dis, baseFunc.h:60 */, 60.0 /* maxEstiDist, :86 */, a.cand + (size_t)s * a.pair_cap * 16);
     }
 }
 
+template <bool kMaps>
 __global__ __launch_bounds__(kFaThreads) void k_fa_fuse(FaArgs a) {
     const int s = blockIdx.y, tid = threadIdx.x;
     if (a.n_frames && a.t >= a.n_frames[s]) return;
+    if constexpr (kMaps) {                                         // sitting out: the carry, the state and the report keep their bytes
+        if ((unsigned)a.map_of[s] >= (unsigned)a.n_maps) return;
+    }
     const size_t slot = (size_t)s * a.frames_pitch + a.t;
     const lsd_fa_state* in = fa_prev(a, s);
     if (a.state_in) in = a.state_in + s;
@@ -400,16 +428,23 @@ __global__ __launch_bounds__(kFaThreads) void k_fa_fuse(FaArgs a) {
     }
 }
 
-void launch_fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t st) {
+template <bool kMaps>
+static void fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t st) {
     if (prepare) {
-        hipLaunchKernelGGL(k_fa_prepare, dim3(1, n_seq), dim3(kFaThreads), 0, st, a);
+        hipLaunchKernelGGL(k_fa_prepare<kMaps>, dim3(1, n_seq), dim3(kFaThreads), 0, st, a);
         // 50-120 pairs (200-480 candidates) per frame on the reference's logs: 8 wavefronts per sequence cover them in one pass; more
         // loop.  (The capacity, n_map x 360 pairs, would be ~900 workgroups per sequence and frame, nearly all of them empty.)
         const long long cap_blocks = ((long long)a.pair_cap * 4 + 63) / 64;
         const int blocks = (int)(cap_blocks < kFaMatchBlocks ? cap_blocks : kFaMatchBlocks);
-        hipLaunchKernelGGL(k_fa_match, dim3(blocks > 0 ? blocks : 1, n_seq), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_fa_match<kMaps>, dim3(blocks > 0 ? blocks : 1, n_seq), dim3(64), 0, st, a);
     }
-    hipLaunchKernelGGL(k_fa_fuse, dim3(1, n_seq), dim3(kFaThreads), 0, st, a);
+    hipLaunchKernelGGL(k_fa_fuse<kMaps>, dim3(1, n_seq), dim3(kFaThreads), 0, st, a);
+}
+
+// the single-map entries launch the kMaps = false instantiation: the same registers and no scratch gained; FaArgs is 24 bytes larger
+void launch_fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t st) {
+    if (a.maps) fa_frame<true>(a, n_seq, prepare, st);
+    else fa_frame<false>(a, n_seq, prepare, st);
 }
 
 }  // namespace lsdhip

@@ -35,17 +35,17 @@ __device__ __forceinline__ double rdp_thre_delta(double val) {                  
     return 1.1;
 }
 
-__global__ __launch_bounds__(64) void k_rdp(const double* __restrict__ scans /* n x stride x {range, angle} */, const int* __restrict__ lens,
-                                            int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX, double mapOriY,
-                                            int region_point_limit, double thre_line, double line_dist_thre_m,
-                                            lsd_line* __restrict__ lines_out, int* __restrict__ n_lines, double* __restrict__ pts_out, int pts_cap,
-                                            int* __restrict__ n_pts, double* __restrict__ lidar_pos, int* __restrict__ im_size) {
+// One scan (blockIdx.x) with the map's resolution and origin given: the body of both kernels below.
+__device__ __forceinline__ void rdp_scan(const double* __restrict__ scans /* n x stride x {range, angle} */, const int* __restrict__ lens,
+                                         int stride, double mapResol, double mapOriX, double mapOriY,
+                                         int region_point_limit, double thre_line, double line_dist_thre_m,
+                                         lsd_line* __restrict__ lines_out, int* __restrict__ n_lines, double* __restrict__ pts_out, int pts_cap,
+                                         int* __restrict__ n_pts, double* __restrict__ lidar_pos, int* __restrict__ im_size) {
     __shared__ double px[kRdpMaxLen], py[kRdpMaxLen];
     __shared__ unsigned char brk[kRdpMaxLen], split[kRdpMaxLen];
     __shared__ short cs[kRdpMaxLen], ce[kRdpMaxLen];           // clusters: first and last reading
     __shared__ short stk[2 * kRdpMaxLen];                       // spans still to look at (RDP), later: the chords (a, b) in order
     __shared__ int s_cells, s_nch;
-    (void)oriMapCol; (void)oriMapRow;                          // (carried by structMapParam, unused by FeatureScan)
     const size_t scan = blockIdx.x;
     const int lane = threadIdx.x;
     const int len_lp = min(lens[scan], min(stride, kRdpMaxLen));
@@ -231,11 +231,46 @@ __global__ __launch_bounds__(64) void k_rdp(const double* __restrict__ scans /* 
     if (lane == 0) { n_lines[scan] = nl; n_pts[scan] = np; }
 }
 
+__global__ __launch_bounds__(64) void k_rdp(const double* __restrict__ scans, const int* __restrict__ lens,
+                                            int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX, double mapOriY,
+                                            int region_point_limit, double thre_line, double line_dist_thre_m,
+                                            lsd_line* __restrict__ lines_out, int* __restrict__ n_lines, double* __restrict__ pts_out, int pts_cap,
+                                            int* __restrict__ n_pts, double* __restrict__ lidar_pos, int* __restrict__ im_size) {
+    (void)oriMapCol; (void)oriMapRow;                          // (carried by structMapParam, unused by FeatureScan)
+    rdp_scan(scans, lens, stride, mapResol, mapOriX, mapOriY, region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines, pts_out,
+             pts_cap, n_pts, lidar_pos, im_size);
+}
+
+// The fleet's FeatureScan: scan i belongs to sequence i / scans_per_seq, whose map id is map_of[sequence]; the three values come from
+// that record of the table (uniform per workgroup: scalar loads).  An id outside the table: the sequence sits out, its scans get
+// counts 0 and nothing else is written.
+__global__ __launch_bounds__(64) void k_rdp_maps(const double* __restrict__ scans, const int* __restrict__ lens, int stride,
+                                                 const lsd_map_ref* __restrict__ maps, int n_maps, const int32_t* __restrict__ map_of,
+                                                 int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m,
+                                                 lsd_line* __restrict__ lines_out, int* __restrict__ n_lines, double* __restrict__ pts_out,
+                                                 int pts_cap, int* __restrict__ n_pts, double* __restrict__ lidar_pos,
+                                                 int* __restrict__ im_size) {
+    const int id = map_of[blockIdx.x / (unsigned)scans_per_seq];
+    if ((unsigned)id >= (unsigned)n_maps) {
+        if (threadIdx.x == 0) { n_lines[blockIdx.x] = 0; n_pts[blockIdx.x] = 0; }
+        return;
+    }
+    const lsd_map_ref* __restrict__ m = maps + id;
+    rdp_scan(scans, lens, stride, m->mapResol, m->mapOriX, m->mapOriY, region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines,
+             pts_out, pts_cap, n_pts, lidar_pos, im_size);
+}
+
 void launch_rdp(const double* scans, const int* lens, int n, int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX,
                 double mapOriY, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                 double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
     hipLaunchKernelGGL(k_rdp, dim3(n), dim3(64), 0, s, scans, lens, stride, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY,
                        region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
+}
+void launch_rdp_maps(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
+                     int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
+                     double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
+    hipLaunchKernelGGL(k_rdp_maps, dim3(n), dim3(64), 0, s, scans, lens, stride, maps, n_maps, map_of, scans_per_seq, region_point_limit,
+                       thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
 }
 int rdp_max_len() { return kRdpMaxLen; }
 int rdp_max_lines() { return kRdpMaxLines; }

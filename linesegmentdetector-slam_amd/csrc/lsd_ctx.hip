@@ -97,6 +97,10 @@ struct lsd_ctx {
     DevBuf<uint8_t> stage;
     DevBuf<uint8_t> fa_buf;
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
+    // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first
+    // LSD_MAX_MAPS of each belong to FeatureScan's entry, the rest to the two loops, so neither call disturbs the other's
+    std::vector<lsd_map_ref> map_tab_host = std::vector<lsd_map_ref>(2 * LSD_MAX_MAPS);
+    DevBuf<lsd_map_ref> map_tab;
     int fa_lds_bound = kFaLdsMax;                       // kept candidates sorted in LDS up to this many (kTunings "FA_LDS")
     // lsd_gather_lines: this rank's padded counts + offsets, and its slab of packed line records
     DevBuf<int32_t> ga_cnt;
@@ -1058,6 +1062,64 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, 
     return LSD_OK;
 }
 
+static_assert(sizeof(lsd_map_ref) == 64 && offsetof(lsd_map_ref, d_map_cache) == 0 && offsetof(lsd_map_ref, d_map_lines) == 8 &&
+              offsetof(lsd_map_ref, d_n_map) == 16 && offsetof(lsd_map_ref, cols) == 24 && offsetof(lsd_map_ref, rows) == 28 &&
+              offsetof(lsd_map_ref, n_map) == 32 && offsetof(lsd_map_ref, mapResol) == 40 && offsetof(lsd_map_ref, mapOriX) == 48 &&
+              offsetof(lsd_map_ref, mapOriY) == 56,
+              "lsd_map_ref has the layout the Python mirror (MAP_REF_DTYPE) assumes");
+
+// The fleet entries' table, checked field by field on the host (nothing the kernels follow is left to the device); *max_n_map: the
+// largest n_map, what the loops size their workspace from.
+static int map_table_check(const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int* max_n_map) {
+    if (!maps || n_maps <= 0 || !d_map_of) return LSD_ERR_INVALID;
+    if (n_maps > LSD_MAX_MAPS) return LSD_ERR_UNSUPPORTED;
+    int mx = 0;
+    for (int i = 0; i < n_maps; i++) {
+        const lsd_map_ref& m = maps[i];
+        if (!m.d_map_cache || m.cols <= 0 || m.rows <= 0 || m.n_map < 0 || (m.n_map > 0 && !m.d_map_lines) || !(m.mapResol > 0))
+            return LSD_ERR_INVALID;
+        mx = std::max(mx, m.n_map);
+    }
+    if (max_n_map) *max_n_map = mx;
+    return LSD_OK;
+}
+
+// The checked table to the device, asynchronously on `s`, the way n_frames travels: a host copy the context owns is the upload's source,
+// so the caller's array is free when the entry returns.  half 0: FeatureScan's records, 1: the loops'.
+static int map_table_upload(lsd_ctx* c, int half, const lsd_map_ref* maps, int n_maps, hipStream_t s, const lsd_map_ref** d_tab) {
+    HIPCHK(c, c->map_tab.reserve(2 * LSD_MAX_MAPS));             // (the first fleet call of a context: one synchronisation)
+    lsd_map_ref* h = c->map_tab_host.data() + (size_t)half * LSD_MAX_MAPS;
+    lsd_map_ref* d = c->map_tab.get() + (size_t)half * LSD_MAX_MAPS;
+    std::copy(maps, maps + n_maps, h);
+    HIPCHK(c, hipMemcpyAsync(d, h, sizeof(lsd_map_ref) * (size_t)n_maps, hipMemcpyHostToDevice, s));
+    *d_tab = d;
+    return LSD_OK;
+}
+
+int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride,
+                                         const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int scans_per_seq,
+                                         int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* d_lines_out,
+                                         int* d_n_lines, lsd_position* d_pts_out, int pts_cap, int* d_n_pts, double* d_lidar_pos,
+                                         int* d_im_size, void* stream) {
+    if (!c || !d_scans || !d_lens || n_scans <= 0 || stride <= 0 || !d_lines_out || !d_n_lines || !d_n_pts || !d_lidar_pos || !d_im_size ||
+        pts_cap < 0 || (pts_cap > 0 && !d_pts_out) || scans_per_seq <= 0)
+        return LSD_ERR_INVALID;
+    const int r = map_table_check(maps, n_maps, d_map_of, nullptr);
+    if (r != LSD_OK) return r;
+    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const lsd_map_ref* d_tab;
+    const int u = map_table_upload(c, 0, maps, n_maps, s, &d_tab);
+    if (u != LSD_OK) return u;
+    launch_rdp_maps(reinterpret_cast<const double*>(d_scans), d_lens, n_scans, stride, d_tab, n_maps, d_map_of, scans_per_seq,
+                    region_point_limit, thre_line, line_dist_thre_m, d_lines_out, d_n_lines, reinterpret_cast<double*>(d_pts_out), pts_cap,
+                    d_n_pts, d_lidar_pos, d_im_size, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
 // the two ingest entries: the checks they share, then one launch of k_ingest
 static int enqueue_ingest(lsd_ctx* c, const lsd_polar* d_raw, const float* d_ranges, const float* d_min_inc, int n_scans, int n_beams,
                           const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
@@ -1260,18 +1322,25 @@ void lsd_fa_carry_init(lsd_fa_carry* o, const lsd_fa_state* state, lsd_position 
 // The replay loop of both device entry points: d_init (lsd_enqueue_localize_device, odometry n_seq x (frames_pitch + 1)) or d_carry
 // (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.  d_n_map (the live-map entries):
 // the map's line count is read on the device and n_map is its capacity; everything the host sizes is sized from n_map either way.
+// fleet (the *_maps entries): the single-map arguments are unused, sequence s runs against maps[d_map_of[s]] and n_map is the table's
+// largest.
 static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
-                           const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
+                           const int32_t* d_n_map, bool fleet, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
                            int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                            const lsd_fa_state* d_init, lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
-    if (!c || !d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || n_seq <= 0 || frames_pitch <= 0 ||
-        !n_frames || !d_lines || !d_n_lines || pts_cap < 0 || (pts_cap > 0 && !d_pts) || !d_n_pts || !d_lidar_pos || !d_odom ||
-        !(map_resol > 0) || !(d_init || d_carry) || !d_states || !d_reports)
+    if (!c || n_seq <= 0 || frames_pitch <= 0 || !n_frames || !d_lines || !d_n_lines || pts_cap < 0 || (pts_cap > 0 && !d_pts) || !d_n_pts ||
+        !d_lidar_pos || !d_odom || !(d_init || d_carry) || !d_states || !d_reports)
+        return LSD_ERR_INVALID;
+    if (!fleet && (!d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || !(map_resol > 0)))
         return LSD_ERR_INVALID;
     int max_frames = 0;
     for (int i = 0; i < n_seq; i++) {
         if (n_frames[i] < 0 || n_frames[i] > frames_pitch) return LSD_ERR_INVALID;
         max_frames = std::max(max_frames, n_frames[i]);
+    }
+    if (fleet) {
+        const int r = map_table_check(maps, n_maps, d_map_of, &n_map);
+        if (r != LSD_OK) return r;
     }
     if ((long long)n_map * LSD_RDP_MAX_LINES > (1 << 26)) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1281,6 +1350,11 @@ static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int 
     hipStream_t s = (hipStream_t)stream;
     c->fa_nf.assign(n_frames, n_frames + n_seq);
     HIPCHK(c, hipMemcpyAsync(const_cast<int*>(a.n_frames), c->fa_nf.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
+    if (fleet) {
+        const int u = map_table_upload(c, 1, maps, n_maps, s, &a.maps);
+        if (u != LSD_OK) return u;
+        a.map_of = d_map_of; a.n_maps = n_maps;
+    }
     a.map_cache = d_map_cache; a.cols = cols; a.rows = rows; a.map_lines = d_map_lines; a.n_map = n_map; a.d_n_map = d_n_map;
     a.scan_lines = d_lines; a.n_lines = d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
     a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = d_n_pts; a.pts_pitch = pts_cap;
@@ -1301,7 +1375,7 @@ int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols,
                                 const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
                                 lsd_fa_report* d_reports, void* stream) {
     if (!d_init) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
                            d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
 }
 
@@ -1311,7 +1385,7 @@ int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, in
                                        const lsd_position* d_odom, double map_resol, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
                                        lsd_fa_report* d_reports, void* stream) {
     if (!d_carry) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
                            d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
 }
 
@@ -1321,7 +1395,7 @@ int lsd_enqueue_localize_live_map_device(lsd_ctx* c, const double* d_map_cache, 
                                          const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                                          const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!d_init || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
                            d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
 }
 
@@ -1331,8 +1405,27 @@ int lsd_enqueue_localize_resume_live_map_device(lsd_ctx* c, const double* d_map_
                                                 const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                                                 lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!d_carry || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
+    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
                            d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
+}
+
+int lsd_enqueue_localize_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq, int frames_pitch,
+                                     const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
+                                     int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom,
+                                     const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
+    if (!d_init) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, nullptr, 0, 0, nullptr, 0, nullptr, true, maps, n_maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines,
+                           d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, 1.0, d_init, nullptr, d_states, d_reports, stream);
+}
+
+int lsd_enqueue_localize_resume_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq,
+                                            int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
+                                            const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
+                                            const lsd_position* d_odom, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
+                                            lsd_fa_report* d_reports, void* stream) {
+    if (!d_carry) return LSD_ERR_INVALID;
+    return fa_enqueue_loop(c, nullptr, 0, 0, nullptr, 0, nullptr, true, maps, n_maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines,
+                           d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, 1.0, nullptr, d_carry, d_states, d_reports, stream);
 }
 
 int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,

@@ -146,6 +146,11 @@ void launch_compact_lines(const lsd_line* lines, const int32_t* counts, int max_
 void launch_rdp(const double* scans, const int* lens, int n, int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX,
                 double mapOriY, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                 double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
+// the same with mapResol / mapOriX / mapOriY of scan i read from maps[map_of[i / scans_per_seq]] (a device table of n_maps records); a
+// scan whose id is outside 0..n_maps-1 gets counts 0 and nothing else
+void launch_rdp_maps(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
+                     int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
+                     double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
 int rdp_max_len();
 // the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
 void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
@@ -159,6 +164,8 @@ void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local
 // carry (not null): the resumable loop (lsd_enqueue_localize_resume_device).  The previous state, the bookkeeping and Odom[cnt_frame - 1]
 // of frame 0 come from carry[s]; odom then holds frames_pitch NEW rows per sequence (frame t: Odom[cnt_frame] = row t), and the fuse
 // kernel of a sequence's last frame writes the loop's variables back to carry[s].
+// maps (not null): the fleet entries (lsd_enqueue_localize*_maps_device).  Sequence s runs against maps[map_of[s]], a device table of
+// n_maps records, in place of the single-map fields; an id outside 0..n_maps-1 makes the sequence sit the call out (fa_map, k_fa.hip).
 constexpr int kFaCtl = 8, kFaAux = 4, kFaLdsMax = 1024;
 struct FaArgs {
     const double* map_cache; int cols, rows;
@@ -171,6 +178,7 @@ struct FaArgs {
     lsd_fa_carry* carry;                                                                // null, or n_seq carries (odom: frames_pitch rows)
     const double* given;                                                                // null, or 6 per sequence: lastPose, ScanPose
     double map_resol;
+    const lsd_map_ref* maps; const int32_t* map_of; int n_maps;                         // maps null: the single map above
     const lsd_fa_state* init; const lsd_fa_state* state_in;                             // state_in (not null): the fuse kernel's input
     lsd_fa_state* states; lsd_fa_report* reports;
     int* pairs; int* n_pairs; int* n_cand; int pair_cap;

@@ -22,8 +22,17 @@ Each run also steps --ticks ticks with ONE update a third of the way in, an even
 the median gap between two consecutive ticks' completions (us_gap_max / us_gap_median; the device clock).  One JSON line per S, path and
 run, then one summary line per S and path: the median of the runs' medians and, as spread, their range.  The probe reports; it asserts
 nothing.
+
+--maps M[,M...]: a fleet on M maps (the maps of the three logs data, f3key, f4key, cycled), the S robots dealt to the maps in M equal
+blocks (the first S mod M blocks one robot larger), every robot on its map's log.  A tick -- step_device from pairs on the device, then
+the caller's synchronisation -- is timed on two paths, --runs runs of --ticks ticks each, alternating in one session:
+  path fleet       ONE FleetLocalizer tick for all S robots (lsd_enqueue_feature_scan_maps_device, lsd_enqueue_localize_resume_maps_device);
+  path localizers  M Localizers, one per map with its block of robots, ticked one after the other on the same stream: the single-map
+                   entries, what such a fleet cost before.  At M = 1 this is Localizer itself: the pair shows what the table costs.
+One JSON line per S, M, path and run, then a summary line per S, M and path (the median of the runs' medians, their range as spread).
 Usage: tools/stream_probe.py [--robots 1,19,256] [--ticks 60] [--warm 3] [--input host|device|laserscan]
-       tools/stream_probe.py --map-update [--robots 1,19,256] [--ticks 30] [--reps 5] [--runs 3]"""
+       tools/stream_probe.py --map-update [--robots 1,19,256] [--ticks 30] [--reps 5] [--runs 3]
+       tools/stream_probe.py --maps 1,3,8 [--robots 24,256] [--ticks 30] [--runs 3]"""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -93,6 +102,72 @@ def map_update(args):
     ctx.close()
 
 
+def fleet(args):
+    ctx, T = lsd.Context(0), args.ticks
+    logs = []
+    for name in fr.LOGS:
+        m, mp, lid, odom = fr.load_log(name)
+        mc = ctx.map_cache(m.copy(), float(mp[2]), lsd.z_occ_max_dis)
+        ml = lsd.myLineSegmentDetector(m.copy(), m.shape[1], m.shape[0], 0.3, 0.6, 22.5, 0.7, 1024, ctx=ctx).linesInfo
+        logs.append(dict(name=name, map=(mc, ml, mp), lid=lid, odom=odom, d_lid=torch.from_numpy(lid).cuda(), d_od=torch.from_numpy(odom).cuda()))
+    for S in (int(v) for v in args.robots.split(",")):
+        for M in (int(v) for v in args.maps.split(",")):
+            sizes = [S // M + (1 if i < S % M else 0) for i in range(M)]
+            if min(sizes) < 1:
+                continue
+            groups, map_of = [], []
+            for i, n in enumerate(sizes):
+                lg = logs[i % len(logs)]
+                starts = np.array([(7 * s) % (len(lg["lid"]) - T - args.warm) for s in range(n)])
+                od0 = lg["odom"][starts].copy(); od0[:, 0] = 0.0
+                d_starts = torch.from_numpy(starts).cuda()
+                ins = [(lg["d_lid"][d_starts + t][:, None].contiguous(), lg["d_od"][d_starts + t + 1][:, None].contiguous())
+                       for t in range(T + args.warm)]
+                groups.append(dict(log=lg, od0=od0, ins=ins, loc=lsd.Localizer(*lg["map"], n, odom0=od0, ctx=ctx)))
+                map_of += [i] * n
+            od0 = np.concatenate([g["od0"] for g in groups])
+            fl = lsd.FleetLocalizer([g["log"]["map"] for g in groups], map_of, odom0=od0, ctx=ctx)
+            all_ins = [(torch.cat([g["ins"][t][0] for g in groups]), torch.cat([g["ins"][t][1] for g in groups])) for t in range(T + args.warm)]
+
+            def tick_fleet(t):
+                return [fl.step_device(*all_ins[t])]
+
+            def tick_localizers(t):
+                return [g["loc"].step_device(*g["ins"][t]) for g in groups]
+
+            def restart():
+                fl.reset(range(S), odom0=od0)
+                for g in groups:
+                    g["loc"].reset(range(g["loc"].n_robots), odom0=g["od0"])
+            paths = (("fleet", tick_fleet), ("localizers", tick_localizers))
+            for _, tick in paths:                                        # warm: staging, workspace and table sized, code loaded
+                for t in range(args.warm):
+                    tick(t)
+            torch.cuda.synchronize()
+            meds = {name: [] for name, _ in paths}
+            for run in range(args.runs):
+                for name, tick in paths:
+                    restart()
+                    torch.cuda.synchronize()
+                    ts, kept = [], []
+                    for t in range(T):
+                        t0 = time.perf_counter()
+                        outs = tick(args.warm + t)
+                        torch.cuda.synchronize()                         # the caller's own
+                        ts.append(time.perf_counter() - t0)
+                        kept.append(np.concatenate([o[1].cpu().numpy().reshape(-1).view(lsd.FA_REPORT_DTYPE)["n_kept"] for o in outs]))
+                    ts, kept = np.array(ts) * 1e6, np.concatenate(kept)
+                    meds[name].append(float(np.median(ts)))
+                    print(json.dumps(dict(mode="fleet", robots=S, maps=M, path=name, run=run + 1, ticks=T, us_per_tick_median=float(np.median(ts)),
+                                          us_per_tick_min=float(ts.min()), us_per_tick_p90=float(np.percentile(ts, 90)),
+                                          map_lines=[len(g["log"]["map"][1]) for g in groups], kept_mean=float(kept.mean()),
+                                          kept_max=int(kept.max()))), flush=True)
+            for name, v in meds.items():
+                print(json.dumps(dict(mode="fleet", robots=S, maps=M, path=name, summary=True, runs=args.runs, us_per_tick=float(np.median(v)),
+                                      spread=float(max(v) - min(v)))), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", default="1,19,256")
@@ -102,9 +177,12 @@ def main():
     ap.add_argument("--map-update", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--maps", default=None)
     args = ap.parse_args()
     if args.map_update:
         return map_update(args)
+    if args.maps:
+        return fleet(args)
     m, mp, lid, odom = fr.load_log("data")
     ctx = lsd.Context(0)
     mc = ctx.map_cache(m.copy(), float(mp[2]), lsd.z_occ_max_dis)
