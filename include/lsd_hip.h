@@ -415,6 +415,25 @@ int lsd_enqueue_localize_resume_maps_device(lsd_ctx *ctx, const lsd_map_ref *map
                                             const lsd_position *d_pts, int pts_cap, const int *d_n_pts, const double *d_lidar_pos,
                                             const lsd_position *d_odom, lsd_fa_carry *d_carry, lsd_fa_state *d_states,
                                             lsd_fa_report *d_reports, void *stream);
+/* Carries from one map frame to another.  A carry's state holds the pose, its velocity and its acceleration in PIXELS of the map it was
+ * made on (FeatureScan and the loop turn metres into pixels with mapResol / mapOriX / mapOriY), so a map that comes back with another
+ * origin or resolution -- a SLAM map that grew -- leaves lastPose off by the shift; the reference's node carries no state between scans
+ * and never met this.  lsd_enqueue_fa_carry_rebase_device moves d_carry[0..n_seq) (device) from frame `from` to frame `to`, in place,
+ * asynchronous on `stream`, in one launch, without workspace: it allocates nothing and waits for nothing.
+ * Sequence s moves iff d_key is NULL or d_key[s] == key, read ON THE DEVICE when the kernel runs: with d_key = d_map_of it means "the
+ * robots on map `key`" and stays right behind an earlier re-assignment on the stream.  Every other carry keeps its bytes.
+ * Arithmetic, fp64 without FMA, in this order:  s = from.mapResol / to.mapResol;  tx = (from.mapOriX - to.mapOriX) / to.mapResol, ty
+ * likewise;  x[0] = x[0] * s + tx, x[1] = x[1] * s + ty;  x[3], x[4], x[6], x[7] *= s;  x[2], x[5], x[8] (degrees) untouched;
+ * P[i][j] = (P[i][j] * d_i) * d_j with d_k = s for k % 3 != 2, else 1;  odom (metres), ang_sum, ang_count, frames, is_offset untouched.
+ * With equal resolutions s is exactly 1: P and the rates keep their bits, only x[0] and x[1] shift.  The pose in metres, x * mapResol +
+ * mapOri, is preserved up to rounding; nothing about orientation is (the reference reads only origin.position).
+ * Left alone, bit for bit: a carry without a pose, |x[0] + 1| < 1e-4 -- the reference's own "no pose yet / just reset" test
+ * (myFA.cpp:99), which the exact lastPose.x == -1 of :330 would otherwise stop recognising.  A NaN state stays NaN by the arithmetic.
+ * from == to in all three fields launches nothing and returns LSD_OK.  Refused before anything is enqueued, LSD_ERR_INVALID: a null
+ * carry, n_seq <= 0, a resolution that is not finite and > 0, a non-finite origin. */
+typedef struct lsd_map_frame { double mapResol, mapOriX, mapOriY; } lsd_map_frame;
+int lsd_enqueue_fa_carry_rebase_device(lsd_ctx *ctx, lsd_fa_carry *d_carry, int n_seq, const int32_t *d_key, int32_t key,
+                                       lsd_map_frame from, lsd_map_frame to, void *stream);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:

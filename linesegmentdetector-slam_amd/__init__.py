@@ -65,6 +65,10 @@ MAP_REF_DTYPE = np.dtype([("d_map_cache", "u8"), ("d_map_lines", "u8"), ("d_n_ma
 assert MAP_REF_DTYPE.itemsize == 64 == C.sizeof(lsd_map_ref)
 
 
+class lsd_map_frame(C.Structure):      # what turns metres into a map's pixels: the frame a carry's state is in (include/lsd_hip.h)
+    _fields_ = [("mapResol", C.c_double), ("mapOriX", C.c_double), ("mapOriY", C.c_double)]
+
+
 class lsd_position(C.Structure):  # == structPosition, LSD/baseFunc.h:46-50
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("ang", C.c_double)]
 
@@ -159,6 +163,7 @@ _ABI = {
     "lsd_enqueue_feature_scan_maps_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "lsd_enqueue_localize_maps_device": (_i, _maps_args),
     "lsd_enqueue_localize_resume_maps_device": (_i, _maps_args),
+    "lsd_enqueue_fa_carry_rebase_device": (_i, [_vp, _vp, _i, _vp, C.c_int32, lsd_map_frame, lsd_map_frame, _vp]),
     "lsd_enqueue_map_update_device": (_i, [_vp, _vp, _i, _i, _dbl, _dbl, _ppar, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -538,6 +543,16 @@ class Context:
                                                                         int(pts_cap), d_n_pts, d_lidar_pos, d_odom, d_carry, d_states,
                                                                         d_reports, stream))
 
+    def enqueue_fa_carry_rebase_device(self, d_carry, n_seq, d_key, key, frame_from, frame_to, stream=None):
+        """lsd_enqueue_fa_carry_rebase_device: the n_seq carries at d_carry (FA_CARRY_DTYPE records on the device) from the map frame
+        frame_from to frame_to (map_frame: (mapResol, mapOriX, mapOriY), or a map_param), in place, asynchronous on `stream`.  d_key: None
+        (every sequence), or device int32 [n_seq]: sequence s moves iff d_key[s] == key, read when the kernel runs.  The arguments the
+        C entry refuses are refused here first, before the library is called."""
+        f, t = map_frame(frame_from), map_frame(frame_to)
+        if not d_carry or int(n_seq) <= 0:
+            raise LsdError(LSD_ERR_INVALID, "a null carry, or n_seq <= 0")
+        return self._chk(self.L.lsd_enqueue_fa_carry_rebase_device(self.h, d_carry, int(n_seq), d_key, int(key), f, t, stream))
+
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
         """lsd_enqueue_map_update_device: the map callback (cells -> map -> mapCache -> LSD with the map rewritten) as one enqueue on
@@ -779,6 +794,22 @@ def _map_param(mp):
     return lsd_map_param(int(mp[0]), int(mp[1]), float(mp[2]), float(mp[3]), float(mp[4]))
 
 
+def map_frame(frame):
+    """An lsd_map_frame from (mapResol, mapOriX, mapOriY), from a map_param (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) or from an
+    lsd_map_frame; LsdError(LSD_ERR_INVALID) for a resolution that is not finite and > 0 or an origin that is not finite."""
+    if isinstance(frame, lsd_map_frame):
+        v = (frame.mapResol, frame.mapOriX, frame.mapOriY)
+    else:
+        v = tuple(float(x) for x in frame)
+        if len(v) == 5:
+            v = v[2:]
+    if len(v) != 3:
+        raise LsdError(LSD_ERR_INVALID, "a map frame is (mapResol, mapOriX, mapOriY)")
+    if not (np.isfinite(v[0]) and v[0] > 0 and np.isfinite(v[1]) and np.isfinite(v[2])):
+        raise LsdError(LSD_ERR_INVALID, "a map frame needs a finite mapResol > 0 and a finite origin, not %r" % (v,))
+    return lsd_map_frame(*v)
+
+
 def map_ref(d_map_cache, cols, rows, d_map_lines, n_map, map_param, d_n_map=0):
     """One MAP_REF_DTYPE record: device addresses (integers) of the cache, the line records and -- or 0 -- the device-side line count,
     the geometry, and mapResol / mapOriX / mapOriY from map_param = (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY)."""
@@ -902,6 +933,86 @@ class _MapSlot:
         self.idle = None                         # recorded behind that tick when the ticks moved on to the other slot
 
 
+class _MapPair:
+    """The two slots of one map and the hand-over between them, as Localizer and -- per map id -- FleetLocalizer use it: the ticks read
+    slot `cur`; a new map is made in the other one, on any stream, behind the events of that slot's last readers and last update, and
+    handed over through `ready`; nothing waits on the host unless a slot has to grow."""
+
+    def __init__(self):
+        self.slots, self.cur = (_MapSlot(), _MapSlot()), 1
+
+    @property
+    def current(self):
+        return self.slots[self.cur]
+
+    @staticmethod
+    def fit(slot, cells, n_lines, keep=False):
+        """The slot's tensors for at least `cells` cells and n_lines records.  Growing them waits -- on the host -- for the ticks that
+        still read the slot and for the update that filled it; keep: what it holds moves over."""
+        import torch
+        if slot.cells >= cells and slot.cap_lines >= n_lines:
+            return
+        for ev in (slot.idle, slot.ready):
+            if ev is not None:
+                ev.synchronize()
+        if slot.last_stream is not None:
+            slot.last_stream.synchronize()
+        cells, n_lines = max(cells, slot.cells), max(n_lines, slot.cap_lines)
+        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
+        new = (z(cells, torch.uint8), z(cells, torch.float64), z(n_lines * 80, torch.uint8), z(1, torch.int32))
+        if keep and slot.cells:
+            for dst, src in zip(new, (slot.map, slot.mc, slot.lines, slot.count)):
+                dst[:src.numel()].copy_(src)
+        # the blocks may have served other work of this stream, and an update may write them from another one: that work is over first
+        torch.cuda.current_stream().synchronize()
+        slot.map, slot.mc, slot.lines, slot.count = new
+        slot.cells, slot.cap_lines = cells, n_lines
+
+    def target(self, stream, cells, n_lines):
+        """The slot the ticks are not reading, large enough, with `stream` behind its last readers and its last update."""
+        slot = self.slots[1 - self.cur]
+        self.fit(slot, cells, n_lines)
+        for ev in (slot.idle, slot.ready):
+            if ev is not None:
+                stream.wait_event(ev)
+        return slot
+
+    def hand_over(self, slot, stream, cols, rows, lines_cap, n_host, map_param, grid=None):
+        """`slot` has been filled on `stream`: the ticks from now on read it, once their stream is behind the update."""
+        import torch
+        slot.ready = torch.cuda.Event()
+        slot.ready.record(stream)
+        slot.waited = {stream.cuda_stream}
+        slot.cols, slot.rows, slot.lines_cap, slot.n_host, slot.map_param, slot.grid = cols, rows, lines_cap, n_host, map_param, grid
+        slot.idle = None
+        old = self.slots[self.cur]
+        if old is not slot and old.last_stream is not None:          # behind the last tick that read the map the ticks now leave
+            old.idle = torch.cuda.Event()
+            old.idle.record(old.last_stream)
+            old.last_stream = None
+        self.cur = self.slots.index(slot)
+
+    def read_by(self, ts):
+        """The slot a tick on torch stream `ts` reads: the first tick of a stream on a new map goes behind its update."""
+        m = self.slots[self.cur]
+        if ts.cuda_stream not in m.waited:
+            ts.wait_event(m.ready)
+            m.waited.add(ts.cuda_stream)
+        m.last_stream = ts
+        return m
+
+
+def _frame_of(map_param):
+    """(mapResol, mapOriX, mapOriY) of a map_param: the frame carries made on that map are in."""
+    return tuple(float(v) for v in map_param[2:5])
+
+
+def _compose_rebase(pending, frame_from, frame_to):
+    """A re-base still pending followed by another: the earliest `from`, the latest `to` (None: they cancel)."""
+    f = pending[0] if pending else frame_from
+    return None if f == frame_to else (f, frame_to)
+
+
 class _Ticks:
     """What Localizer and FleetLocalizer share: the robots' carries on the device, the FeatureScan staging and the device tick's front
     (step_device: the checks of its inputs, the take flags, the views of the output staging).  A subclass supplies _enqueue, the tick's
@@ -914,20 +1025,32 @@ class _Ticks:
         self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self._cap = 0
         self._held = None
+        self._tail_b = 8                                                     # bytes behind the outputs: the map line counts of step()
+        # every hand-over re-bases, as set_map*(..., rebase=True) does for one: the setting of a site whose maps grow.  It is also how
+        # Localizer.set_map_device, whose parameter list is fixed, is told to re-base.
+        self.rebase_on_hand_over = False
+
+    def _flush_rebase(self):
+        """Enqueues, on the current torch stream, every re-base that a set_map*(..., rebase=True) left pending for the next tick."""
 
     def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
-        """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot)."""
+        """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot).  A
+        re-base that is pending (set_map*(..., rebase=True) without a tick since) is enqueued first, on the current stream: a `state`
+        given here is in the frame of the map the next tick reads."""
         import torch
         idx = [int(r) for r in robots]
         if not idx:
             return
+        self._flush_rebase()
         o = np.broadcast_to(np.asarray(odom0, np.float64).reshape(-1, 3), (len(idx), 3))
         rec = np.stack([Context.fa_carry_init(state, o[i]) for i in range(len(idx))])
         self._carry.view(self.n_robots, -1)[torch.tensor(idx, device="cuda")] = torch.from_numpy(rec.view(np.uint8).reshape(len(idx), -1)).cuda()
 
     @property
     def carries(self):
-        """The robots' carries, FA_CARRY_DTYPE [n_robots] on the host (a checkpoint)."""
+        """The robots' carries, FA_CARRY_DTYPE [n_robots] on the host (a checkpoint), in the frame of the map the next tick reads (a
+        pending re-base is enqueued first)."""
+        self._flush_rebase()
         return self._carry.cpu().numpy().view(FA_CARRY_DTYPE).copy()
 
     @carries.setter
@@ -936,6 +1059,7 @@ class _Ticks:
         rec = np.ascontiguousarray(rec, FA_CARRY_DTYPE).reshape(-1)
         if len(rec) != self.n_robots:
             raise LsdError(LSD_ERR_INVALID, "one carry per robot")
+        self._flush_rebase()
         self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
 
     # per frame slot: the tick's inputs (one upload) the RAW scan (360 x 2 doubles, or less: the LaserScan floats), the odometry row, the
@@ -948,7 +1072,7 @@ class _Ticks:
         if n <= self._cap:
             return
         z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
-        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + 8, torch.uint8)     # (+ the map's line count of step())
+        self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + self._tail_b, torch.uint8)     # (+ the map line counts of step())
         self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
         self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
         self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
@@ -1031,7 +1155,8 @@ class Localizer(_Ticks):
     def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
         super().__init__(ctx, n_robots, pts_cap)
         self.map_param = tuple(float(v) for v in map_param)
-        self._slots, self._cur = (_MapSlot(), _MapSlot()), 1       # the ticks read slot _cur; a new map is made in the other one
+        self._pair = _MapPair()                                    # the ticks read its current slot; a new map is made in the other one
+        self._rebase = None                                        # (from, to): the carries' move to a new map's frame, due at the next tick
         self._lines_cap = 512
         self._map_ctx = None
         self.set_map(map_cache, map_lines)
@@ -1043,51 +1168,19 @@ class Localizer(_Ticks):
         _, mapCache, LSD = mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=ctx)
         return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx)
 
-    def _fit(self, slot, cells, n_lines, keep=False):
-        """The slot's tensors for at least `cells` cells and n_lines records.  Growing them waits -- on the host -- for the ticks that
-        still read the slot and for the update that filled it; keep: what it holds moves over."""
-        import torch
-        if slot.cells >= cells and slot.cap_lines >= n_lines:
-            return
-        for ev in (slot.idle, slot.ready):
-            if ev is not None:
-                ev.synchronize()
-        if slot.last_stream is not None:
-            slot.last_stream.synchronize()
-        cells, n_lines = max(cells, slot.cells), max(n_lines, slot.cap_lines)
-        z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
-        new = (z(cells, torch.uint8), z(cells, torch.float64), z(n_lines * 80, torch.uint8), z(1, torch.int32))
-        if keep and slot.cells:
-            for dst, src in zip(new, (slot.map, slot.mc, slot.lines, slot.count)):
-                dst[:src.numel()].copy_(src)
-        # the blocks may have served other work of this stream, and an update may write them from another one: that work is over first
-        torch.cuda.current_stream().synchronize()
-        slot.map, slot.mc, slot.lines, slot.count = new
-        slot.cells, slot.cap_lines = cells, n_lines
+    def _flush_rebase(self):
+        if self._rebase is not None:
+            import torch
+            f, t = self._rebase
+            self._rebase = None
+            self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, None, 0, f, t, torch.cuda.current_stream().cuda_stream)
 
-    def _target(self, stream, cells, n_lines):
-        """The slot the ticks are not reading, large enough, with `stream` behind its last readers and its last update."""
-        slot = self._slots[1 - self._cur]
-        self._fit(slot, cells, n_lines)
-        for ev in (slot.idle, slot.ready):
-            if ev is not None:
-                stream.wait_event(ev)
-        return slot
-
-    def _hand_over(self, slot, stream, cols, rows, lines_cap, n_host, map_param, grid=None):
-        """`slot` has been filled on `stream`: the ticks from now on read it, once their stream is behind the update."""
-        import torch
-        slot.ready = torch.cuda.Event()
-        slot.ready.record(stream)
-        slot.waited = {stream.cuda_stream}
-        slot.cols, slot.rows, slot.lines_cap, slot.n_host, slot.map_param, slot.grid = cols, rows, lines_cap, n_host, map_param, grid
-        slot.idle = None
-        old = self._slots[self._cur]
-        if old is not slot and old.last_stream is not None:          # behind the last tick that read the map the ticks now leave
-            old.idle = torch.cuda.Event()
-            old.idle.record(old.last_stream)
-            old.last_stream = None
-        self._cur = self._slots.index(slot)
+    def _hand_over(self, slot, stream, cols, rows, lines_cap, n_host, map_param, grid, rebase):
+        """The pair's hand-over, with the Localizer's map_param and -- rebase -- the carries' move to the new map's frame left pending
+        for the next tick."""
+        if rebase or self.rebase_on_hand_over:
+            self._rebase = _compose_rebase(self._rebase, _frame_of(self.map_param), _frame_of(map_param))
+        self._pair.hand_over(slot, stream, cols, rows, lines_cap, n_host, map_param, grid)
         self.map_param = map_param
 
     def _map_context(self):
@@ -1097,22 +1190,24 @@ class Localizer(_Ticks):
             self._map_ctx = Context(self.ctx.device)
         return self._map_ctx
 
-    def set_map(self, map_cache, map_lines, map_param=None):
+    def set_map(self, map_cache, map_lines, map_param=None, rebase=False):
         """A new map (mapCallback) from host arrays or tensors; the robots keep their carries.  It is copied, on the current torch
         stream, into the map slot the ticks are not reading, and the ticks after the call read that slot: the hand-over of
-        set_map_device, with the line count known to the host."""
+        set_map_device, with the line count known to the host.  rebase: as set_map_device's."""
         import torch
         mc = map_cache if isinstance(map_cache, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map_cache, np.float64))
         rows, cols = mc.shape
         ml = np.ascontiguousarray(map_lines, LINE_DTYPE)
+        mp = self.map_param if map_param is None else tuple(float(v) for v in map_param)
+        if rebase or self.rebase_on_hand_over:
+            map_frame(mp)                                                    # a frame the re-base would refuse: before anything is enqueued
         stream = torch.cuda.current_stream()
-        slot = self._target(stream, rows * cols, max(len(ml), 1))
+        slot = self._pair.target(stream, rows * cols, max(len(ml), 1))
         slot.mc[:rows * cols].copy_(mc.reshape(-1))
         if len(ml):
             slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
         slot.count.fill_(len(ml))
-        mp = self.map_param if map_param is None else tuple(float(v) for v in map_param)
-        self._hand_over(slot, stream, cols, rows, max(len(ml), 1), len(ml), mp)
+        self._hand_over(slot, stream, cols, rows, max(len(ml), 1), len(ml), mp, None, rebase)
 
     def reserve_map(self, cols, rows, lines_cap=512):
         """Sizes everything a set_map_device of a cols x rows grid (or a smaller one) and the ticks after it need: both map slots
@@ -1126,12 +1221,12 @@ class Localizer(_Ticks):
         if lines_cap * 360 > 1 << 26:
             raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
         torch.cuda.synchronize()
-        for i, slot in enumerate(self._slots):
-            self._fit(slot, rows * cols, lines_cap, keep=i == self._cur)
+        for i, slot in enumerate(self._pair.slots):
+            self._pair.fit(slot, rows * cols, lines_cap, keep=i == self._pair.cur)
         self._lines_cap = lines_cap
         self._map_context().reserve_map_update(cols, rows)
         # a tick of no frames: nothing is launched, the workspace of n_robots sequences against lines_cap map lines is carved
-        S, cur = self.n_robots, self._slots[self._cur]
+        S, cur = self.n_robots, self._pair.current
         self._staging(S)
         d_out = self._out.data_ptr()
         self.ctx.enqueue_localize_resume_live_map_device(cur.mc.data_ptr(), cur.cols, cur.rows, cur.lines.data_ptr(), lines_cap,
@@ -1151,23 +1246,36 @@ class Localizer(_Ticks):
         Nothing here waits for the device once reserve_map covers the geometry; a larger grid, or more lines than the slot holds, makes
         the slot grow first, which waits on the host for the ticks that still read it and for its last update.  A map with more than
         lines_cap lines (reserve_map; default 512) keeps its first lines_cap: step() then raises LSD_ERR_CAPACITY, a step_device
-        caller checks map_counts."""
+        caller checks map_counts.
+        The re-base: the carries are in pixels of the map they were made on, so a map that comes back with another origin or resolution
+        (a SLAM map that grew) leaves every lastPose off by the shift -- beyond maxEstiDist the track is lost.  This method's parameter
+        list is fixed, so it has no keyword for it: set the attribute rebase_on_hand_over = True (set_map, and FleetLocalizer's set_map
+        and set_map_device, also take rebase=True for one call).  With it, and a map_param that differs from the one the ticks were
+        using in mapResol, mapOriX or mapOriY, every robot's carry is moved to the new
+        frame (lsd_enqueue_fa_carry_rebase_device: the pose in metres is kept up to rounding; a robot without a pose is left alone) by
+        the first tick after this call, on that tick's stream, in front of its launches: ticks enqueued earlier read the old map with
+        old-frame carries, this tick and later ones the new map with new-frame carries, and nothing waits on the host.  Two hand-overs
+        without a tick between them compose (the earliest `from`, the latest `to`); reset, carries and a carries assignment enqueue a
+        pending re-base first.  The default, rebase_on_hand_over = False, leaves the carries alone as before.  Only the origin's
+        position and the resolution are followed: a map frame that rotates is not."""
         cols, rows = int(oriMapCol), int(oriMapRow)
         grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
         stream = _cuda_stream(stream)
+        if self.rebase_on_hand_over:
+            map_frame((mapResol, mapOriX, mapOriY))                          # a frame the re-base would refuse: before anything is enqueued
         mctx = self._map_context()
-        slot = self._target(stream, rows * cols, self._lines_cap)
+        slot = self._pair.target(stream, rows * cols, self._lines_cap)
         mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, float(mapResol), 2.0, slot.map.data_ptr(), slot.mc.data_ptr(),
                                        slot.lines.data_ptr(), self._lines_cap, slot.count.data_ptr(), None, None, stream.cuda_stream)
         self._hand_over(slot, stream, cols, rows, self._lines_cap, None, (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY)),
-                        grid)
+                        grid, False)
 
     @property
     def map_counts(self):
         """The line count of the map the next tick reads: a CUDA int32 tensor of one element, valid once the update that makes the map
         has run (the caller's synchronisation).  Above lines_cap: the ticks use the first lines_cap lines; -1: the detector gave the map
         up and the ticks see no map lines."""
-        return self._slots[self._cur].count
+        return self._pair.current.count
 
     def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
         """The tick on the current torch stream, every input on the device: ingest, FeatureScan, the resume entry.  Returns the byte
@@ -1188,11 +1296,8 @@ class Localizer(_Ticks):
         cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, _map_param(mp), rdp_leastPoint, rdp_threLine, rdp_leastDist,
                                                            self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np,
                                                            self._lp.data_ptr(), self._sz.data_ptr(), stream))
-        m, ts = self._slots[self._cur], torch.cuda.current_stream()
-        if ts.cuda_stream not in m.waited:                                   # the first tick of this stream on a new map: behind its update
-            ts.wait_event(m.ready)
-            m.waited.add(ts.cuda_stream)
-        m.last_stream = ts
+        m = self._pair.read_by(torch.cuda.current_stream())                  # the first tick of this stream on a new map: behind its update
+        self._flush_rebase()                                                 # and, in front of its launches, the carries into that map's frame
         tail = (S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od, mp[2],
                 self._carry.data_ptr(), d_st, d_rp, stream)
         if m.n_host is not None:
@@ -1247,7 +1352,7 @@ class Localizer(_Ticks):
         d_take = self._in.data_ptr() + len(host_in) - 4 * n
         self._in[:len(host_in)].copy_(torch.from_numpy(host_in))
         b_st, b_rp = self._enqueue(S, k, nf, d_src if ranges is None else None, None if ranges is None else d_src, d_ami, n_beams, d_take, d_od)
-        m = self._slots[self._cur]
+        m = self._pair.current
         live = m.n_host is None                                              # a device-made map: its line count rides in the read-back
         if live:
             self._out[n * self._OUT_B:n * self._OUT_B + 4].view(torch.int32).copy_(m.count)
@@ -1280,12 +1385,16 @@ class FleetLocalizer(_Ticks):
     """Localizer for a fleet on several maps: every robot is ticked against the map its id names, all of them in ONE tick (one ingest,
     one FeatureScan launch and one set of FeatureAssociation launches per frame index: lsd_enqueue_feature_scan_maps_device with
     scans_per_seq = k, lsd_enqueue_localize_resume_maps_device), and each gets, bit for bit, what a Localizer on its map alone gives
-    it.  maps: a list of (map_cache, map_lines, map_param) host arrays, one per map id (at most LSD_MAX_MAPS), each uploaded once;
-    map_of: one id per robot -- this sets n_robots --, or -1 for a robot that sits out (parked, between floors): its carry stays as it
-    is and its slots of a tick's results stay zero.  The ids live on the device: assign() rewrites them on the current stream.  step,
-    step_device, reset and carries are as Localizer's (step_device, reset and carries are the same code).  The map side is host arrays only -- set_map(i, ...) --: the two-slot device
-    hand-over of one map (Localizer.set_map_device) has no per-map form here yet, although the C entries would take such a map (a table
-    record whose d_n_map points at the count lsd_enqueue_map_update_device writes)."""
+    it.  maps: a list of (map_cache, map_lines, map_param) host arrays, one per map id (at most LSD_MAX_MAPS); map_of: one id per robot
+    -- this sets n_robots --, or -1 for a robot that sits out (parked, between floors): its carry stays as it is and its slots of a
+    tick's results stay zero.  The ids live on the device: assign() rewrites them on the current stream.  step, step_device, reset and
+    carries are as Localizer's (step_device, reset and carries are the same code).  The map side is Localizer's, per map id: every map
+    has two slots, set_map(i, ...) from host arrays or set_map_device(i, ...) from a grid on the device makes the new map in the slot
+    the ticks are not reading -- on a side stream if the caller wants -- and hands it over through events, so the ticks keep running
+    on the old map meanwhile; reserve_map(i, ...) sizes what that needs.  One map-side context serves all maps: updates of different
+    maps on different streams serialise on the device (lsd_enqueue_map_update_device orders itself behind the context's previous run
+    with an event), never on the host.  Like the context it uses, a FleetLocalizer serves one thread at a time, and its ticks one
+    stream at a time."""
 
     def __init__(self, maps, map_of, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
         import torch
@@ -1298,8 +1407,13 @@ class FleetLocalizer(_Ticks):
         if not len(ids):
             raise LsdError(LSD_ERR_INVALID, "at least one robot")
         super().__init__(ctx, len(ids), pts_cap)
+        self._tail_b = 4 * len(maps)
         self._table = np.zeros(len(maps), MAP_REF_DTYPE)
-        self._tensors = [None] * len(maps)                                   # per map: the cache and the line records on the device
+        self._pairs = [_MapPair() for _ in maps]                             # per map id: the slot the ticks read, and the other one
+        self._caps = [512] * len(maps)                                       # per map id: the line records a device-made map keeps (reserve_map)
+        self._rebases = {}                                                   # map id -> (from, to): due at the next tick, for the robots then on it
+        self._map_ctx, self._map_geom = None, (0, 0)
+        self._mask = None
         for i, m in enumerate(maps):
             self.set_map(i, *m)
         self._map_of = torch.from_numpy(ids).cuda()
@@ -1314,13 +1428,45 @@ class FleetLocalizer(_Ticks):
         """The robots' map ids, int32 [n_robots] on the host (a read-back)."""
         return self._map_of.cpu().numpy()
 
-    def set_map(self, i, map_cache, map_lines, map_param):
-        """Replaces map i from host arrays: uploaded on the current torch stream -- the ticks' --, read by the ticks after the call.  The
-        robots on it keep their carries."""
-        import torch
+    def _map_id(self, i):
         i = int(i)
         if not 0 <= i < len(self._table):
             raise LsdError(LSD_ERR_INVALID, "map %d of %d" % (i, len(self._table)))
+        return i
+
+    def _map_context(self):
+        # one context for the map side of every map (Localizer._map_context: the ticks' context is busy on their stream)
+        if self._map_ctx is None:
+            self._map_ctx = Context(self.ctx.device)
+        return self._map_ctx
+
+    def _flush_rebase(self):
+        if self._rebases:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+            pending, self._rebases = self._rebases, {}
+            for i, (f, t) in pending.items():                                # "the robots on map i", read when the kernel runs
+                self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, self._map_of.data_ptr(), i, f, t, stream)
+
+    def _hand_over(self, i, slot, stream, cols, rows, lines_cap, n_host, map_param, grid, rebase):
+        """Map i's hand-over: the pair's, table record i, and -- rebase -- the move of the carries of the robots on map i left pending
+        for the next tick."""
+        pair = self._pairs[i]
+        if (rebase or self.rebase_on_hand_over) and pair.current.map_param is not None:
+            r = _compose_rebase(self._rebases.get(i), _frame_of(pair.current.map_param), _frame_of(map_param))
+            self._rebases.pop(i, None)
+            if r is not None:
+                self._rebases[i] = r
+        pair.hand_over(slot, stream, cols, rows, lines_cap, n_host, map_param, grid)
+        self._table[i] = map_ref(slot.mc.data_ptr(), cols, rows, slot.lines.data_ptr(), lines_cap if n_host is None else n_host, map_param,
+                                 slot.count.data_ptr() if n_host is None else 0)
+
+    def set_map(self, i, map_cache, map_lines, map_param, rebase=False):
+        """Replaces map i from host arrays.  It is copied, on the current torch stream, into the slot of map i that the ticks are not
+        reading, and the ticks after the call read that slot: the hand-over of set_map_device with the line count known to the host, so
+        a host-made and a device-made map can alternate on one id.  The robots on it keep their carries; rebase: as set_map_device's."""
+        import torch
+        i = self._map_id(i)
         mc = np.ascontiguousarray(map_cache, np.float64)
         ml = np.ascontiguousarray(map_lines, LINE_DTYPE).reshape(-1)
         mp = tuple(float(v) for v in map_param)
@@ -1328,15 +1474,91 @@ class FleetLocalizer(_Ticks):
             raise LsdError(LSD_ERR_INVALID, "map_cache is [rows, cols], map_param (oriMapCol, oriMapRow, mapResol > 0, mapOriX, mapOriY)")
         if len(ml) * 360 > 1 << 26:
             raise LsdError(LSD_ERR_UNSUPPORTED, "map lines x 360 pairs per robot exceed 1 << 26")
-        d_mc = torch.from_numpy(mc).cuda()
-        d_ml = torch.from_numpy(ml.view(np.uint8).reshape(-1).copy() if len(ml) else np.zeros(80, np.uint8)).cuda()
-        self._tensors[i] = (d_mc, d_ml)
-        self._table[i] = map_ref(d_mc.data_ptr(), mc.shape[1], mc.shape[0], d_ml.data_ptr(), len(ml), mp)
+        if rebase or self.rebase_on_hand_over:
+            map_frame(mp)
+        rows, cols = mc.shape
+        stream = torch.cuda.current_stream()
+        slot = self._pairs[i].target(stream, rows * cols, max(len(ml), 1))
+        slot.mc[:rows * cols].copy_(torch.from_numpy(mc.reshape(-1)))
+        if len(ml):
+            slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
+        slot.count.fill_(len(ml))
+        self._hand_over(i, slot, stream, cols, rows, max(len(ml), 1), len(ml), mp, None, rebase)
+
+    def reserve_map(self, i, cols, rows, lines_cap=512):
+        """Sizes everything a set_map_device(i, ...) of a cols x rows grid (or a smaller one) and the ticks after it need: both slots of
+        map i (lines_cap records each: from now on a device-made map i keeps its first lines_cap lines), the one map-side context
+        (lsd_reserve_map_update for the largest geometry reserved so far) and the ticks' workspace (for the largest lines_cap and line
+        count of the table).  A set-up call: it waits for the device.  After it neither set_map_device(i, ...) nor the ticks wait for
+        the device or allocate."""
+        import torch
+        i, cols, rows, lines_cap = self._map_id(i), int(cols), int(rows), int(lines_cap)
+        if cols <= 0 or rows <= 0 or lines_cap <= 0:
+            raise LsdError(LSD_ERR_INVALID, "cols, rows and lines_cap must be positive")
+        if lines_cap * 360 > 1 << 26:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
+        torch.cuda.synchronize()
+        pair = self._pairs[i]
+        for j, slot in enumerate(pair.slots):
+            pair.fit(slot, rows * cols, lines_cap, keep=j == pair.cur)
+        cur = pair.current                                                   # (its tensors may have moved)
+        self._table[i]["d_map_cache"], self._table[i]["d_map_lines"] = cur.mc.data_ptr(), cur.lines.data_ptr()
+        if cur.n_host is None:
+            self._table[i]["d_n_map"] = cur.count.data_ptr()
+        self._caps[i] = lines_cap
+        self._map_geom = (max(self._map_geom[0], cols), max(self._map_geom[1], rows))
+        self._map_context().reserve_map_update(*self._map_geom)
+        # a tick of no frames: nothing is launched, the workspace of n_robots sequences against the largest line capacity is carved
+        S = self.n_robots
+        self._staging(S)
+        tab = self._table.copy()
+        tab[i]["n_map"] = max(max(self._caps), int(tab["n_map"].max()))      # (no frame: no record of it is read)
+        d_out = self._out.data_ptr()
+        self.ctx.enqueue_localize_resume_maps_device(tab, self._map_of.data_ptr(), S, 1, np.zeros(S, np.int32), self._lines.data_ptr(),
+                                                     self._lens.data_ptr(), self._pts.data_ptr(), self.pts_cap, self._lens.data_ptr(),
+                                                     self._lp.data_ptr(), self._in.data_ptr(), self._carry.data_ptr(), d_out, d_out,
+                                                     torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+
+    def set_map_device(self, i, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream=None, rebase=False):
+        """Localizer.set_map_device for map i: the whole map callback (lsd_enqueue_map_update_device) is enqueued on `stream` (a
+        torch.cuda.Stream; default: the current one) into the slot of map i that the ticks are NOT reading, behind an event recorded
+        after the last tick that read that slot, and table record i is rewritten: the slot's cache and lines, its count on the device,
+        lines_cap (reserve_map; default 512) as the capacity, the new geometry.  Ticks enqueued before the call keep the old map; the
+        first tick after it puts its own stream behind the update.  The robots on other maps are not affected.  Nothing here waits for
+        the device once reserve_map(i, ...) covers the geometry.  A map with more than lines_cap lines keeps its first lines_cap:
+        step() then raises LSD_ERR_CAPACITY and names the map, a step_device caller checks map_counts.
+        rebase=True: when the new map_param differs from the one the ticks were using for map i in mapResol, mapOriX or mapOriY, the
+        carries of the robots that are on map i when the next tick runs are moved to the new frame by that tick, in front of its
+        launches (Localizer.set_map_device; lsd_enqueue_fa_carry_rebase_device with d_key = the robots' map ids, key = i)."""
+        i = self._map_id(i)
+        cols, rows = int(oriMapCol), int(oriMapRow)
+        grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
+        stream = _cuda_stream(stream)
+        mp = (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY))
+        if not mp[2] > 0:
+            raise LsdError(LSD_ERR_INVALID, "mapResol must be > 0")
+        if rebase or self.rebase_on_hand_over:
+            map_frame(mp)
+        mctx, cap = self._map_context(), self._caps[i]
+        slot = self._pairs[i].target(stream, rows * cols, cap)
+        mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, mp[2], 2.0, slot.map.data_ptr(), slot.mc.data_ptr(), slot.lines.data_ptr(), cap,
+                                       slot.count.data_ptr(), None, None, stream.cuda_stream)
+        self._hand_over(i, slot, stream, cols, rows, cap, None, mp, grid, rebase)
+
+    @property
+    def map_counts(self):
+        """Per map id, the line count of the map the next tick reads: a list of CUDA int32 tensors of one element, with
+        Localizer.map_counts' conventions (valid once the update that makes the map has run; above the map's lines_cap: the ticks use
+        the first lines_cap lines; -1: the detector gave the map up and the ticks see no map lines)."""
+        return [pair.current.count for pair in self._pairs]
 
     def assign(self, robots, map_ids):
         """Moves the given robots to the given maps (one id each, or one for all; -1: the robot sits out from now on): the ids are
-        rewritten on the device, on the current torch stream, without waiting for it.  The carries are NOT touched, and a carry is in
-        the pixel frame of the map it was made on: after a move to another map follow with reset(robots, odom0, state)."""
+        rewritten on the device, on the current torch stream, without waiting for it (a pending re-base is enqueued first: it is for
+        the robots that were on its map).  The carries are NOT touched, and a carry is in the pixel frame of the map it was made on:
+        after a move follow with rebase(robots, from_map, to_map) if the two maps share a world frame, else with reset(robots, odom0,
+        state)."""
         import torch
         idx = np.ascontiguousarray([int(r) for r in robots], np.int64)
         if not len(idx):
@@ -1345,13 +1567,39 @@ class FleetLocalizer(_Ticks):
             raise LsdError(LSD_ERR_INVALID, "a robot is 0..%d" % (self.n_robots - 1))
         ids = np.asarray(map_ids, np.int32).reshape(-1)
         ids = fleet_map_ids(np.repeat(ids, len(idx)) if len(ids) == 1 else ids, len(self._table), len(idx))
+        self._flush_rebase()
         # pinned, so the copies do not wait for the stream (as the take flags of step_device)
         up = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
         self._map_of.index_copy_(0, up(idx), up(ids))
 
+    def rebase(self, robots, from_map, to_map):
+        """Moves the given robots' carries from the pixel frame of map from_map to that of map to_map (the map_param the next tick
+        uses for each), on the current torch stream, without waiting for it: lsd_enqueue_fa_carry_rebase_device with a small device
+        mask as the key.  The use: after assign() has moved robots between maps of ONE site that share a world frame -- two halls, an
+        annex, the same floor at two resolutions -- they keep tracking where a reset would start them over; the pose in metres is kept
+        up to rounding, a robot without a pose is left alone.  Maps in unrelated world frames (or frames that are rotated against each
+        other: only the origin's position and the resolution are followed) still need reset."""
+        import torch
+        idx = np.ascontiguousarray([int(r) for r in robots], np.int64)
+        a, b = self._map_id(from_map), self._map_id(to_map)
+        if ((idx < 0) | (idx >= self.n_robots)).any():
+            raise LsdError(LSD_ERR_INVALID, "a robot is 0..%d" % (self.n_robots - 1))
+        f, t = map_frame(self._pairs[a].current.map_param), map_frame(self._pairs[b].current.map_param)
+        if not len(idx):
+            return
+        self._flush_rebase()
+        mask = np.zeros(self.n_robots, np.int32)
+        mask[idx] = 1
+        if self._mask is None:
+            self._mask = torch.zeros(self.n_robots, dtype=torch.int32, device="cuda")
+        self._mask.copy_(torch.from_numpy(mask).pin_memory(), non_blocking=True)
+        self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, self._mask.data_ptr(), 1, f, t,
+                                                torch.cuda.current_stream().cuda_stream)
+
     def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
         """Localizer's tick through the fleet entries: ingest, FeatureScan with each robot's map geometry, the resume loop with each
-        robot's map."""
+        robot's map -- behind the update of every map whose current slot this stream has not read yet, and behind the pending
+        re-bases."""
         import torch
         n = S * k
         b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
@@ -1359,7 +1607,8 @@ class FleetLocalizer(_Ticks):
         d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
         d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
         d_np = d_nl + 4 * n
-        cx, stream = self.ctx, torch.cuda.current_stream().cuda_stream
+        cx, ts = self.ctx, torch.cuda.current_stream()
+        stream = ts.cuda_stream
         if d_raw is not None:
             cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
         else:
@@ -1367,17 +1616,23 @@ class FleetLocalizer(_Ticks):
         d_of = self._map_of.data_ptr()
         cx.enqueue_feature_scan_maps_device(d_sc, d_ln, n, 360, self._table, d_of, k, self._lines.data_ptr(), d_nl, self._pts.data_ptr(),
                                             self.pts_cap, d_np, self._lp.data_ptr(), self._sz.data_ptr(), stream=stream)
+        for pair in self._pairs:
+            pair.read_by(ts)
+        self._flush_rebase()
         cx.enqueue_localize_resume_maps_device(self._table, d_of, S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap,
                                                d_np, self._lp.data_ptr(), d_od, self._carry.data_ptr(), d_st, d_rp, stream)
         return b_st, b_rp
 
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
-        """Localizer.step for the fleet: the same arguments, results and capacity error (LsdError(LSD_ERR_CAPACITY) with (states,
-        reports) in `partial` if a scan marks more than pts_cap pixels or has more than 360 lines).  The slots of a robot that sits out
-        are zero, like those past a robot's n_frames.  The host side differs from Localizer.step in one respect: the inputs are not
-        packed into one staging upload but uploaded as they are (the frames, the odometry, with ranges= the two float arrays; the take
-        flags by step_device), then the device tick of step_device and one read-back of the Localizer's output staging, whose layout
-        (states, reports, FeatureScan's counts) is the same."""
+        """Localizer.step for the fleet: the same arguments, results and errors, with (states, reports) in `partial`:
+        LsdError(LSD_ERR_CAPACITY) if a scan marks more than pts_cap pixels or has more than 360 lines, or if a map the tick used was
+        made on the device and has more lines than its slots hold (the records of its robots are computed from the first lines_cap of
+        them), LsdError(LSD_ERR_INTERNAL) if such a map's count is -1 (its robots saw no map lines); the message names the map id, and
+        the robots on other maps are not affected.  The slots of a robot that sits out are zero, like those past a robot's n_frames.
+        The host side differs from Localizer.step in one respect: the inputs are not packed into one staging upload but uploaded as
+        they are (the frames, the odometry, with ranges= the two float arrays; the take flags by step_device), then the device tick of
+        step_device and one read-back of the output staging, whose layout (states, reports, FeatureScan's counts, then the line counts
+        of the device-made maps) is the same."""
         import torch
         if (lidar is None) == (ranges is None):
             raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
@@ -1394,10 +1649,22 @@ class FleetLocalizer(_Ticks):
         S, k = out[0].shape[:2]
         n = S * k
         b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
-        host = self._out[:n * self._OUT_B].cpu().numpy()                       # the tick's one synchronisation
+        live = [(i, pair.current) for i, pair in enumerate(self._pairs) if pair.current.n_host is None]
+        for j, (i, m) in enumerate(live):                                      # the device-made maps: their line counts ride in the read-back
+            self._out[n * self._OUT_B + 4 * j:n * self._OUT_B + 4 * j + 4].view(torch.int32).copy_(m.count)
+        host = self._out[:n * self._OUT_B + 4 * len(live)].cpu().numpy()      # the tick's one synchronisation
         states = host[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
         reports = host[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
-        counts = host[b_st + b_rp:].view(np.int32).reshape(2, n)
+        counts = host[b_st + b_rp:n * self._OUT_B].view(np.int32).reshape(2, n)
+        n_map = host[n * self._OUT_B:].view(np.int32)
+        for j, (i, m) in enumerate(live):
+            if n_map[j] < 0:
+                raise LsdError(LSD_ERR_INTERNAL, "map %d: the detector gave the map up (count -1): the tick saw no map lines" % i,
+                               partial=(states, reports))
+        for j, (i, m) in enumerate(live):
+            if n_map[j] > m.lines_cap:
+                raise LsdError(LSD_ERR_CAPACITY, "map %d has %d lines, its slots hold %d (reserve_map): the tick used the first %d"
+                               % (i, n_map[j], m.lines_cap, m.lines_cap), partial=(states, reports))
         if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
             raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
         return states, reports

@@ -447,4 +447,35 @@ void launch_fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t st) {
     else fa_frame<false>(a, n_seq, prepare, st);
 }
 
+// Carries from one map frame to another, in place (lsd_enqueue_fa_carry_rebase_device): one lane per (sequence,
+// entry), entries 0..8 = state.x, 9..89 = state.P; sc = from.mapResol / to.mapResol, tx / ty = the origin's move in pixels of `to`.
+// A sequence moves iff key_of is null or key_of[s] == key, read here, when the kernel runs.  The carry's "no pose" test (x[0] read by
+// every lane of the sequence) must see the value from before lane 0's write: the barrier between the read and the writes orders them
+// (a workgroup holds kFaRebaseSeqs whole sequences, so every lane that reads a sequence's x[0] shares the barrier with its writer).
+constexpr int kFaRebaseEntries = 90, kFaRebaseSeqs = 2;
+__global__ __launch_bounds__(kFaRebaseEntries * kFaRebaseSeqs) void k_fa_rebase(lsd_fa_carry* carry, int n_seq, const int32_t* key_of, int32_t key,
+                                                                                 double sc, double tx, double ty) {
+    const int s = blockIdx.x * kFaRebaseSeqs + (int)threadIdx.x / kFaRebaseEntries, e = (int)threadIdx.x % kFaRebaseEntries;
+    bool move = s < n_seq && (!key_of || key_of[s] == key);
+    double x0 = 0;
+    if (move) x0 = carry[s].state.x[0];
+    __syncthreads();
+    if (!move || fabs(x0 + 1) < 0.0001) return;                    // no pose yet / just reset (myFA.cpp:99): the sentinel keeps its bytes
+    lsd_fa_state* st = &carry[s].state;
+    if (e < 9) {
+        if (e % 3 == 2) return;                                    // degrees
+        const double v = st->x[e] * sc;
+        st->x[e] = e == 0 ? v + tx : e == 1 ? v + ty : v;
+    } else {
+        const int q = e - 9, i = q % 9, j = q / 9;                 // column-major; the scaling is symmetric in (i, j) up to its order
+        const double di = i % 3 != 2 ? sc : 1.0, dj = j % 3 != 2 ? sc : 1.0;
+        st->P[q] = (st->P[q] * di) * dj;
+    }
+}
+
+void launch_fa_rebase(lsd_fa_carry* carry, int n_seq, const int32_t* key_of, int32_t key, double sc, double tx, double ty, hipStream_t st) {
+    hipLaunchKernelGGL(k_fa_rebase, dim3((n_seq + kFaRebaseSeqs - 1) / kFaRebaseSeqs), dim3(kFaRebaseEntries * kFaRebaseSeqs), 0, st, carry,
+                       n_seq, key_of, key, sc, tx, ty);
+}
+
 }  // namespace lsdhip

@@ -1319,6 +1319,22 @@ void lsd_fa_carry_init(lsd_fa_carry* o, const lsd_fa_state* state, lsd_position 
     o->odom = odom0;
 }
 
+int lsd_enqueue_fa_carry_rebase_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, const int32_t* d_key, int32_t key, lsd_map_frame from,
+                                       lsd_map_frame to, void* stream) {
+    if (!c) return LSD_ERR_INVALID;
+    auto bad = [](const lsd_map_frame& f) {
+        return !(std::isfinite(f.mapResol) && f.mapResol > 0) || !std::isfinite(f.mapOriX) || !std::isfinite(f.mapOriY);
+    };
+    if (!d_carry || n_seq <= 0 || bad(from) || bad(to)) return LSD_ERR_INVALID;
+    if (from.mapResol == to.mapResol && from.mapOriX == to.mapOriX && from.mapOriY == to.mapOriY) return LSD_OK;   // the same frame: no launch
+    HIPCHK(c, hipSetDevice(c->device));
+    const double sc = from.mapResol / to.mapResol;
+    const double tx = (from.mapOriX - to.mapOriX) / to.mapResol, ty = (from.mapOriY - to.mapOriY) / to.mapResol;
+    launch_fa_rebase(d_carry, n_seq, d_key, key, sc, tx, ty, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LSD_OK;
+}
+
 // The replay loop of both device entry points: d_init (lsd_enqueue_localize_device, odometry n_seq x (frames_pitch + 1)) or d_carry
 // (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.  d_n_map (the live-map entries):
 // the map's line count is read on the device and n_map is its capacity; everything the host sizes is sized from n_map either way.
