@@ -488,6 +488,12 @@ enum { LSD_STAGE_ALL = 0, LSD_STAGE_GAUSS = 1, LSD_STAGE_GRAD = 2, LSD_STAGE_SOR
 int lsd_set_stop_after(lsd_ctx *ctx, int stage);
 /* Enables the per-seed trace buffer (LSD_DBG_SEEDS); costs one record store per grown seed. */
 int lsd_set_trace(lsd_ctx *ctx, int on);
+/* The fused front end (default 1): for the reference's 17 Gaussian taps (sca 0.3, sig 0.6) the Gaussian and the gradient pass run as
+ * one kernel and GaussImage never exists in device memory; 0 runs them as two kernels with the image in between, as every other tap
+ * count, lsd_set_stop_after(LSD_STAGE_GAUSS) and lsd_set_trace do anyway.  Results are identical.  On the fused path lsd_last_timings
+ * reports the kernel under "gauss" and "gradient" as exactly 0, the per-image Gaussian workspace (8 B per scaled pixel) is not
+ * allocated, and LSD_DBG_GAUSS is recomputed on demand (lsd_debug_fetch). */
+int lsd_set_fused_front(lsd_ctx *ctx, int on);
 /* Region stage variant: 4 wavefronts per image (three images per CU: the throughput build) or 8 (one image per CU, ~1.5x lower
  * latency per image, images taken heaviest first).  0 (default) picks 8 while the batch has at most four images per CU (the step is
  * bounded by its heaviest image until then) and 4 beyond.  Results do not depend on the choice.  Set it before lsd_reserve: the
@@ -535,6 +541,10 @@ int lsd_debug_set_tuning(lsd_ctx *ctx, const char *name, int value);
  *                                   cycles_select*, cycles_commit*, filter_skips*
  *                                   (summed over the wavefronts that share an image; * = counted by the developer build only,
  *                                   `make stats` -> liblsdhip_stats.so, and 0 in the product build)
+ * After a call that took the fused front end (lsd_set_fused_front) there is no GaussImage to copy: GAUSS runs the Gaussian kernel alone
+ * on the requested image of the last call's INPUT, so for lsd_enqueue_batch_device the caller's d_maps must still be alive and
+ * unchanged when GAUSS is fetched (a map the call itself rewrote, LSD_FLAG_WRITEBACK_MAP, is read as rewritten; the host entry points
+ * keep their own copy).
  * Returns LSD_ERR_INVALID if `bytes` is smaller than the item. */
 enum { LSD_DBG_GAUSS = 1, LSD_DBG_MAG, LSD_DBG_DEG, LSD_DBG_STATE, LSD_DBG_ORDER, LSD_DBG_ORDER_VAL,
        LSD_DBG_NB, LSD_DBG_MAXGRAD, LSD_DBG_RECS, LSD_DBG_SEEDS, LSD_DBG_NSEED, LSD_DBG_STATS };

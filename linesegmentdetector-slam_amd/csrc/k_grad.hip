@@ -6,17 +6,12 @@
 // usedMap code, the only thing RegionGrower reads per neighbour), i.e. 8 + 20 B per pixel actually
 // move, plus one 16-byte (sin, cos) pair for the ~7 % of pixels that stay growable.
 #include "lsd_internal.h"
-#include "devmath.h"
+#include "grad_px.h"
 
 namespace lsdhip {
 
 constexpr int GX = 64;     // columns per wavefront (one lane per column)
 constexpr int GR = 8;      // rows walked by a wavefront
-
-// fp32 angle with the two lowest mantissa bits replaced by the usedMap code (lsd_internal.h)
-__device__ __forceinline__ uint32_t pack_pw(double d, uint32_t code) {
-    return (__float_as_uint(__double2float_rn(d)) & ~3u) | code;
-}
 
 // One 64-lane workgroup owns a 64-column x 8-row strip.  Each lane walks its column downwards keeping the row
 // above in registers; the left neighbour comes from the adjacent lane (lane 0 loads it), so every gauss value is
@@ -67,17 +62,12 @@ __global__ __launch_bounds__(GX) void k_gradient(const double* __restrict__ gaus
         for (int i = lane; i < cnt; i += GX) {
             const uint32_t e = l_px[i];
             const double2 gr = l_g[i];
-            double d;                                          // :169 (first stage inline, second stage out of line: devmath.h)
-            if (!crm::atan2_fast(gr.x, -gr.y, d)) d = atan2_g(gr.x, -gr.y);
-            if (fabs(fabs(d - kPi) - 0.000001) <= 1e-14) atomicAdd(&ties[img], 1);   // within an ulp of atan2 of the rule's threshold: a decision another libm could take differently (lsd_last_sensitivity)
-            if (fabs(d - kPi) < 0.000001) d = 0;               // :170-171
+            const double d = grad_angle(gr.x, gr.y, &ties[img]);   // :169-171
             l_g[i] = make_double2(d, 0.0);
             if (e & 1u) {                                      // sin/cos(deg) for RegionGrower (:545-546)
                 const int lt = (int)(e >> 1);
                 const size_t p = base + (size_t)(y0 + lt / GX) * w + ((int)bx * GX + lt % GX);
-                double sv, cv;
-                if (!crm::sincos_fast(d, sv, cv)) sincos_g(d, sv, cv);
-                sc[p] = make_double2(sv, cv);
+                sc[p] = grad_sincos(d);
             }
         }
         #pragma unroll
@@ -119,20 +109,10 @@ __global__ __launch_bounds__(GX) void k_gradient(const double* __restrict__ gaus
             if (lane != 0) B = t;
         }
         const double C = up, D = upl;
-        double m = 0, d = 0, gradX = 0, gradY = 0;
-        uint32_t u = 0;
-        bool heavy = false;
-        if (colok && x >= 1 && y >= 1) {                       // Q3: row 0 / col 0 stay mag=0, deg=0, used=0
-            gradX = (B + D - A - C) / 2.0;                     // myLSD.cpp:161
-            gradY = (C + D - A - B) / 2.0;                     // :162
-            m = sqrt(gradX * gradX + gradY * gradY);           // :163 (pow(.,2) == x*x, Q12)
-            if (m < gradThre) u = 1;                           // :165-166
-            if (gradX == 0.0 && gradY == 0.0) {
-                // atan2(+-0, -(+-0)) (:169) followed by the "pi -> 0" rule (:170-171): IEEE special cases
-                if (signbit(-gradY)) d = signbit(gradX) ? -kPi : 0.0;
-                else d = gradX;
-            } else heavy = true;
-        }
+        const GradPx px = grad_pixel(A, B, C, D, colok && x >= 1 && y >= 1, gradThre);   // (grad_px.h)
+        const double m = px.m, d = px.d, gradX = px.gradX, gradY = px.gradY;
+        const uint32_t u = px.u;
+        const bool heavy = px.heavy;
         if (colok) {
             const size_t p = base + (size_t)y * w + x;
             mag[p] = m;

@@ -112,12 +112,18 @@ struct lsd_ctx {
     int tun_groups = -1;                // the 8-wave region stage as persistent workgroups (k_region.hip: k_region): -1 = as many as CUs when the batch has more images than that, 0 = never
     DevBuf<int> pcount;                 // ... and the launch's image counter
     bool trace = false;
+    bool fused_front = true;            // lsd_set_fused_front: K1 + K2 as one kernel where it applies (use_front)
     int host_max_lines = 8192;
     // last run
     Geom geom{};
     int last_n = 0;
     int last_max_lines = 0;
     int32_t* last_counts = nullptr;
+    // the last call took the fused front end: no Gaussian image exists, LSD_DBG_GAUSS recomputes the requested one from the call's input
+    // (last_in; last_remapped: that input has been rewritten in place since, LSD_FLAG_WRITEBACK_MAP) into dbg_gauss
+    bool last_fused = false, last_remapped = false;
+    const uint8_t* last_in = nullptr;
+    DevBuf<double> dbg_gauss;
     hipEvent_t ev[7]{};
     bool ev_valid = false;
     hipEvent_t ev_done = nullptr;      // end of the last enqueue: a later enqueue on ANOTHER stream waits for it (shared workspace)
@@ -301,6 +307,14 @@ static int pool_reserve_for(const lsd_ctx* c, int n) {
     const int now = c->tun_help < 0 ? 24 : c->tun_help;
     return pool_for(c, n, now > 24 ? now : 24);
 }
+
+// Does a call with this geometry take the fused front end (k_front.hip)?  The reference's 17 taps, a pipeline that runs at least as far
+// as the gradient pass, no seed trace, and its LDS fits; everything else runs K1 and K2 as two kernels.
+static bool use_front(const lsd_ctx* c, const Geom& g) {
+    return c->fused_front && !c->trace && (c->stop_after == 0 || c->stop_after >= LSD_STAGE_GRAD) && front_fits(g, c->max_lds);
+}
+// ... and the Gaussian elements per image its workspace needs: none on the fused path (1.55 GB per context at 512 maps of 2048^2)
+static size_t gauss_elems(const lsd_ctx* c, const Geom& g) { return use_front(c, g) ? 0 : (size_t)g.gp * g.h; }
 
 // Words per wave of the member-mask array (4 per 8x8 tile) for any image of up to npx scaled pixels: tiles <= npx / 64 + (w + h) / 8 + 1,
 // and w, h <= 32766 (make_geom).
@@ -535,6 +549,12 @@ int lsd_set_trace(lsd_ctx* c, int on) {
     return LSD_OK;
 }
 
+int lsd_set_fused_front(lsd_ctx* c, int on) {
+    if (!c) return LSD_ERR_INVALID;
+    c->fused_front = on != 0;
+    return LSD_OK;
+}
+
 int lsd_reserve(lsd_ctx* c, int n, int cols, int rows) {
     if (!c || n <= 0) return LSD_ERR_INVALID;
     lsd_params p; lsd_default_params(&p);
@@ -542,7 +562,7 @@ int lsd_reserve(lsd_ctx* c, int n, int cols, int rows) {
     int st = make_geom(c, &p, cols, rows, &g);
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
-    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, (size_t)g.gp * g.h, c->ws.cap_max_lines, c->trace);
+    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, gauss_elems(c, g), c->ws.cap_max_lines, c->trace);
     if (st != LSD_OK) return st;
     // ... and the tables: the log-gamma table is sized by the geometry (w*h + 2 host-libm values: ~40 ms of host work and a blocking
     // copy for a 2048^2 map), taps / centres / log p for the default parameters.  Done here, the first enqueue after a reserve neither
@@ -560,11 +580,12 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     if (st != LSD_OK) return st;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
-    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, (size_t)g.gp * g.h, max_lines, c->trace);
+    st = ensure_workspace(c, (size_t)n, (size_t)g.npx, gauss_elems(c, g), max_lines, c->trace);
     if (st != LSD_OK) return st;
     st = ensure_tables(c, p, g, s);
     if (st != LSD_OK) return st;
-    HIPCHK(c, prepare_gauss(g));
+    const bool fused = use_front(c, g);
+    if (!fused) HIPCHK(c, prepare_gauss(g));
     // the workspace is shared by every enqueue of this context: work queued on another stream must be over first
     if (c->done_valid && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
 
@@ -613,10 +634,13 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     // kernel of its own does (inside the event window either way: part of "gauss")
     const bool fused_clear = d_line_ims && (((size_t)cols * rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_line_ims) & 15) == 0;
     if (d_line_ims && !fused_clear) launch_clear(d_line_ims, (size_t)n * cols * rows, c->num_cus, s);
-    launch_gauss(g, b, n, fused_clear ? d_line_ims : nullptr, s);
+    // K1 and K2 as one kernel where that applies (use_front): its time is reported under "gauss" and "gradient" reads exactly 0
+    // (lsd_last_timings) -- two events back to back would give microseconds
+    if (fused) launch_front(g, b, n, fused_clear ? d_line_ims : nullptr, s);
+    else launch_gauss(g, b, n, fused_clear ? d_line_ims : nullptr, false, s);
     if (b.in_rw) launch_remap_writeback(g, b, n, s);
     HIPCHK(c, hipEventRecord(c->ev[1], s));
-    if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_GRAD) launch_gradient(g, b, n, s);
+    if (!fused && (c->stop_after == 0 || c->stop_after >= LSD_STAGE_GRAD)) launch_gradient(g, b, n, s);
     HIPCHK(c, hipEventRecord(c->ev[2], s));
     if (c->stop_after == 0 || c->stop_after >= LSD_STAGE_SORT) { launch_sort(g, b, n, s); launch_order(b, n, g.npx, (c->cost_history && c->hist_n == n && !c->trace) ? w.stats.get() : nullptr, s); }
     HIPCHK(c, hipEventRecord(c->ev[3], s));
@@ -653,6 +677,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     c->ev_valid = true;
     c->hist_n = (c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION) ? n : 0;     // (the counter records of this launch: the next one's cost history)
     c->geom = g; c->last_n = n; c->last_max_lines = max_lines; c->last_counts = d_counts; c->last_stream = s;
+    c->last_fused = fused; c->last_in = d_maps; c->last_remapped = b.in_rw != nullptr;
     return LSD_OK;
 }
 
@@ -669,6 +694,7 @@ int lsd_last_timings(lsd_ctx* c, float ms[6]) {
     HIPCHK(c, hipEventSynchronize(c->ev[5]));
     for (int i = 0; i < 5; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     HIPCHK(c, hipEventElapsedTime(&ms[5], c->ev[0], c->ev[5]));
+    if (c->last_fused) ms[1] = 0.0f;                                 // (the fused front end: all of it is under "gauss")
     return LSD_OK;
 }
 
@@ -840,6 +866,21 @@ int lsd_debug_fetch(lsd_ctx* c, int image, int what, void* out, size_t bytes) {
     switch (what) {
         case LSD_DBG_GAUSS:                                           // (rows are padded to gp doubles on the device)
             if (bytes < npx * 8) return LSD_ERR_INVALID;
+            if (c->last_fused) {
+                // no Gaussian image exists after the fused front end: K1 alone computes the requested one from the call's input (still
+                // alive: lsd_hip.h), without the remap where the call has rewritten that input in place since (not idempotent: 1 -> 255 -> 0)
+                const Geom& g = c->geom;
+                HIPCHK(c, c->dbg_gauss.reserve((size_t)g.gp * g.h));
+                HIPCHK(c, prepare_gauss(g));
+                Buffers b{};
+                b.in = c->last_in + (size_t)image * g.W * g.H; b.gauss = c->dbg_gauss.get();
+                b.taps = c->d_taps.get(); b.centres = c->d_centres.get();
+                launch_gauss(g, b, 1, nullptr, c->last_remapped, c->last_stream);
+                HIPCHK(c, hipGetLastError());
+                HIPCHK(c, hipStreamSynchronize(c->last_stream));
+                HIPCHK(c, hipMemcpy2D(out, (size_t)g.w * 8, c->dbg_gauss.get(), (size_t)g.gp * 8, (size_t)g.w * 8, (size_t)g.h, hipMemcpyDeviceToHost));
+                return LSD_OK;
+            }
             HIPCHK(c, hipMemcpy2D(out, (size_t)c->geom.w * 8, w.gauss.get() + (size_t)image * c->geom.gp * c->geom.h, (size_t)c->geom.gp * 8,
                                   (size_t)c->geom.w * 8, (size_t)c->geom.h, hipMemcpyDeviceToHost));
             return LSD_OK;
@@ -967,7 +1008,7 @@ int lsd_reserve_map_update(lsd_ctx* c, int cols, int rows) {
     lsd_params p; lsd_default_params(&p);
     st = make_geom(c, &p, cols, rows, &g);
     if (st != LSD_OK) return st;
-    st = ensure_workspace(c, 1, (size_t)g.npx, (size_t)g.gp * g.h, std::max(c->ws.cap_max_lines, c->host_max_lines), c->trace);
+    st = ensure_workspace(c, 1, (size_t)g.npx, gauss_elems(c, g), std::max(c->ws.cap_max_lines, c->host_max_lines), c->trace);
     if (st != LSD_OK) return st;
     return reserve_map_cache(c, 1, (size_t)cols * rows);
 }

@@ -53,7 +53,7 @@ __host__ __device__ inline uint32_t pw_used(uint32_t w) { return (w & 3u) == 3u 
 struct Buffers {
     const uint8_t* in;     // n x H x W (pitch W)
     uint8_t* in_rw;        // same pointer when write-back of the remap is requested, else null
-    double* gauss;         // n x h x gp (row pitch gp: see Geom)
+    double* gauss;         // n x h x gp (row pitch gp: see Geom); null on the fused front end's path
     double* mag;           // n x npx
     double* deg;           // n x npx
     double2* sc;           // n x npx : (sin, cos)(deg), written where usedMap == 0 after the gradient pass
@@ -119,7 +119,10 @@ struct SeedRec {  // mirrors oracle's orc_seed
 
 // launchers (each enqueues on `s`)
 hipError_t prepare_gauss(const Geom& g);   // raises K1's dynamic-LDS limit where its window needs it; called before a call enqueues anything
-void launch_gauss(const Geom& g, const Buffers& b, int n, uint8_t* clr, hipStream_t s);   // clr: lineIm to be cleared on the way, or null
+void launch_gauss(const Geom& g, const Buffers& b, int n, uint8_t* clr, bool remapped, hipStream_t s);   // clr: lineIm to be cleared on the way, or null; remapped: b.in holds remapped values already
+// the fused front end (k_front.hip): K1 + K2 in one kernel for the reference's 17 taps, without the Gaussian image (b.gauss is not used)
+bool front_fits(const Geom& g, size_t max_lds);   // 17 taps and its LDS (k_front_lds.h) within the device's and the default launch limit
+void launch_front(const Geom& g, const Buffers& b, int n, uint8_t* clr, hipStream_t s);
 void launch_remap_writeback(const Geom& g, const Buffers& b, int n, hipStream_t s);
 void launch_gradient(const Geom& g, const Buffers& b, int n, hipStream_t s);
 void launch_sort(const Geom& g, const Buffers& b, int n, hipStream_t s);
