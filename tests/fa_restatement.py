@@ -24,8 +24,23 @@ INF = float("inf")
 
 _crm = None
 LOGS = ("data", "f3key", "f4key")                      # the replay logs under tests/golden/ (make_localize_logs.py)
+# Three more recorded logs per key (data<N> of data_f3key / data_f4key), chosen from tests/golden/localize_survey.json: the longest,
+# the one with the most resets after its first fix, the one with the largest n_kept.  A list of its own: the resume, fleet and
+# re-base suites run over LOGS only.
+MORE_LOGS = ("f3key_9", "f3key_2", "f3key_3", "f4key_3", "f4key_2", "f4key_4")
 LOG_MAPS = {"data": "mapValue", "f3key": "f3key", "f4key": "f4key"}
+LOG_MAPS.update({n: n.split("_")[0] for n in MORE_LOGS})
 LOG_FRAMES = {"data": 99, "f3key": 279, "f4key": 273}
+
+
+def log_lidar(z):
+    """The lidar frames float64 [frames in the file, 360, 2] of a packed log: stored whole ("lidar"), or as the ranges and the one
+    angle column that every frame of the log shares ("lidar_range" [n, 360], "lidar_angle" [360])."""
+    import numpy as np
+    if "lidar" in z.files:
+        return z["lidar"]
+    r = z["lidar_range"]
+    return np.stack([r, np.broadcast_to(z["lidar_angle"], r.shape)], 2).astype(np.float64)
 
 
 def load_log(name):
@@ -33,9 +48,16 @@ def load_log(name):
     import numpy as np
     g = os.path.join(ROOT, "tests", "golden")
     z = np.load(os.path.join(g, "localize_%s.npz" % name))
-    lid = np.load(os.path.join(g, "lidar.npz"))["lidar"] if name == "data" else z["lidar"]
+    lid = np.load(os.path.join(g, "lidar.npz"))["lidar"] if name == "data" else log_lidar(z)
     n = int(z["n_frames"])
     return np.load(os.path.join(g, "maps.npz"))[LOG_MAPS[name]], z["map_param"], lid[:n], z["odom"]
+
+
+def load_way_points(name):
+    """(realPos.txt float64 [k, 2] in metres, recored_Odom.txt int [k]: the 1-based frame count at which the robot stood on each)."""
+    import numpy as np
+    z = np.load(os.path.join(ROOT, "tests", "golden", "localize_%s.npz" % name))
+    return z["real_pos"], z["recorded"]
 
 
 def crm():

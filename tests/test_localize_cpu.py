@@ -98,7 +98,7 @@ def test_log_fixtures(name):
     assert odom[0, 0] == 0 and np.array_equal(odom[-1], odom[-2]) and np.array_equal(odom[1:n], z["odom_raw"][1:])
     assert m.shape == (int(mp[1]), int(mp[0])) and mp[2] == 0.025
     if name != "data":
-        assert z["lidar"].shape[0] == n + 1                # one lidar frame more than the driver replays (:183)
+        assert fr.log_lidar(z).shape[0] == n + 1               # one lidar frame more than the driver replays (:183)
 
 
 def replay(oracle, lsdmod, name, _lib):
