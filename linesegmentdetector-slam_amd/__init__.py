@@ -1019,24 +1019,126 @@ def _compose_rebase(pending, frame_from, frame_to):
 
 
 class _Ticks:
-    """What Localizer and FleetLocalizer share: the robots' carries on the device, the FeatureScan staging and the device tick's front
-    (step_device: the checks of its inputs, the take flags, the views of the output staging).  A subclass supplies _enqueue, the tick's
-    launches against its map or maps."""
+    """Localizer and FleetLocalizer but for their argument adapters: the robots' carries on the device, the map side -- one _MapPair per
+    map (one for Localizer), the hand-over, the pending re-bases, the one map-side context --, the FeatureScan staging, and the tick
+    (step, step_device).  A subclass supplies three hooks of the map side (_rebase_key, _map_changed, _carve), the tick's two launches
+    against its map or maps (_feature_scan, _loop) and the texts of step()'s two map errors."""
 
-    def __init__(self, ctx, n_robots, pts_cap):
+    _GAVE_UP = "the detector gave the map up (count -1): the tick saw no map lines"
+    _OVER = "the map has %(n)d lines, its slot holds %(cap)d (reserve_map): the tick used the first %(cap)d"
+
+    def __init__(self, ctx, n_robots, pts_cap, n_maps=1):
         import torch
         self.ctx = ctx or default_context()
         self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
         self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._pairs = [_MapPair() for _ in range(n_maps)]                    # per map: the slot the ticks read, and the other one
+        self._caps = [512] * n_maps                                          # per map: the line records a device-made map keeps (reserve_map)
+        self._rebases = {}                                                   # map -> (from, to): due at the next tick
+        self._map_ctx, self._map_geom = None, (0, 0)                         # the map side's context, the largest geometry reserved for it
         self._cap = 0
         self._held = None
-        self._tail_b = 8                                                     # bytes behind the outputs: the map line counts of step()
+        self._tail_b = 4 * len(self._pairs)                                  # bytes behind the outputs: the map line counts of step()
         # every hand-over re-bases, as set_map*(..., rebase=True) does for one: the setting of a site whose maps grow.  It is also how
         # Localizer.set_map_device, whose parameter list is fixed, is told to re-base.
         self.rebase_on_hand_over = False
 
+    # ---- the three hooks of the map side ----
+    def _rebase_key(self, i):
+        """(d_key, key) of lsd_enqueue_fa_carry_rebase_device: the robots whose carries a pending re-base of map i moves."""
+        raise NotImplementedError
+
+    def _map_changed(self, i):
+        """Map i has been handed over, or its current slot's tensors have moved: whatever else names them follows."""
+
+    def _carve(self, i):
+        """A tick of no frames on the current torch stream: nothing is launched, the workspace of n_robots sequences against the line
+        capacity reserve_map has just set for map i is carved."""
+        raise NotImplementedError
+
+    # ---- the map side, per map index ----
+    def _map_context(self):
+        # The map side has a context of its own (DESIGN.md 8.1.2), one for every map: the detector's workspace and createMapCache's
+        # scratch belong to a context, which serves one stream at a time, and the ticks' context is busy on theirs while an update runs
+        # on a side stream.
+        if self._map_ctx is None:
+            self._map_ctx = Context(self.ctx.device)
+        return self._map_ctx
+
     def _flush_rebase(self):
         """Enqueues, on the current torch stream, every re-base that a set_map*(..., rebase=True) left pending for the next tick."""
+        if self._rebases:
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+            pending, self._rebases = self._rebases, {}
+            for i, (f, t) in pending.items():                                # (a key is read when the kernel runs)
+                self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, *self._rebase_key(i), f, t, stream)
+
+    def _hand_over(self, i, slot, stream, cols, rows, lines_cap, n_host, map_param, grid, rebase):
+        """Map i's hand-over: the pair's, what _map_changed adds, and -- rebase -- the carries' move to the new map's frame left pending
+        for the next tick."""
+        pair = self._pairs[i]
+        if (rebase or self.rebase_on_hand_over) and pair.current.map_param is not None:
+            r = _compose_rebase(self._rebases.get(i), _frame_of(pair.current.map_param), _frame_of(map_param))
+            self._rebases.pop(i, None)
+            if r is not None:
+                self._rebases[i] = r
+        pair.hand_over(slot, stream, cols, rows, lines_cap, n_host, map_param, grid)
+        self._map_changed(i)
+
+    def _set_map(self, i, map_cache, map_lines, map_param, rebase):
+        import torch
+        mc = map_cache if isinstance(map_cache, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map_cache, np.float64))
+        ml = np.ascontiguousarray(map_lines, LINE_DTYPE).reshape(-1)
+        mp = tuple(float(v) for v in map_param)
+        if mc.dim() != 2 or not mc.numel() or len(mp) != 5 or not mp[2] > 0:
+            raise LsdError(LSD_ERR_INVALID, "map_cache is [rows, cols], map_param (oriMapCol, oriMapRow, mapResol > 0, mapOriX, mapOriY)")
+        if len(ml) * 360 > 1 << 26:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "map lines x 360 pairs per robot exceed 1 << 26")
+        if rebase or self.rebase_on_hand_over:
+            map_frame(mp)                                                    # a frame the re-base would refuse: before anything is enqueued
+        rows, cols = mc.shape
+        stream = torch.cuda.current_stream()
+        slot = self._pairs[i].target(stream, rows * cols, max(len(ml), 1))
+        slot.mc[:rows * cols].copy_(mc.reshape(-1))
+        if len(ml):
+            slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
+        slot.count.fill_(len(ml))
+        self._hand_over(i, slot, stream, cols, rows, max(len(ml), 1), len(ml), mp, None, rebase)
+
+    def _reserve_map(self, i, cols, rows, lines_cap):
+        import torch
+        cols, rows, lines_cap = int(cols), int(rows), int(lines_cap)
+        if cols <= 0 or rows <= 0 or lines_cap <= 0:
+            raise LsdError(LSD_ERR_INVALID, "cols, rows and lines_cap must be positive")
+        if lines_cap * 360 > 1 << 26:
+            raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
+        torch.cuda.synchronize()
+        pair = self._pairs[i]
+        for j, slot in enumerate(pair.slots):
+            pair.fit(slot, rows * cols, lines_cap, keep=j == pair.cur)
+        self._map_changed(i)                                                 # (the current slot's tensors may have moved)
+        self._caps[i] = lines_cap
+        self._map_geom = (max(self._map_geom[0], cols), max(self._map_geom[1], rows))
+        self._map_context().reserve_map_update(*self._map_geom)
+        self._staging(self.n_robots)
+        self._carve(i)
+        torch.cuda.synchronize()
+
+    def _set_map_device(self, i, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream, rebase):
+        cols, rows = int(oriMapCol), int(oriMapRow)
+        grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
+        stream = _cuda_stream(stream)
+        mp = (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY))
+        if not mp[2] > 0:
+            raise LsdError(LSD_ERR_INVALID, "mapResol must be > 0")
+        if rebase or self.rebase_on_hand_over:
+            map_frame(mp)                                                    # a frame the re-base would refuse: before anything is enqueued
+        mctx, cap = self._map_context(), self._caps[i]
+        slot = self._pairs[i].target(stream, rows * cols, cap)
+        mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, mp[2], 2.0, slot.map.data_ptr(), slot.mc.data_ptr(), slot.lines.data_ptr(), cap,
+                                       slot.count.data_ptr(), None, None, stream.cuda_stream)
+        self._hand_over(i, slot, stream, cols, rows, cap, None, mp, grid, rebase)
 
     def reset(self, robots, odom0=(0.0, 0.0, 0.0), state=None):
         """Restarts the given robots at the driver's first frame: lsd_fa_carry_init(state, odom0) (odom0 [3], or one row per robot).  A
@@ -1089,10 +1191,106 @@ class _Ticks:
             raise LsdError(LSD_ERR_INVALID, "n_frames outside 0..k")
         return nf
 
-    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
-        """The tick on the current torch stream, every input on the device; returns the byte sizes of the states and the reports in
-        self._out."""
+    def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
+        """FeatureScan of the tick's n = S * k scans into the staging (self._lines, self._pts, self._lp, self._sz) and the two count rows."""
         raise NotImplementedError
+
+    def _loop(self, S, k, nf, d_n_lines, d_n_pts, d_od, d_states, d_reports, stream):
+        """The resume loop on what _feature_scan left, against the current slot of the map or of every map."""
+        raise NotImplementedError
+
+    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
+        """The tick on the current torch stream, every input on the device: ingest, FeatureScan, then -- behind the update of every map
+        whose current slot this stream has not read yet, and behind the pending re-bases -- the resume loop.  Returns the byte sizes of
+        the states and the reports in self._out."""
+        import torch
+        n = S * k
+        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
+        self._out[:b_st + b_rp].zero_()
+        d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
+        d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
+        d_np = d_nl + 4 * n
+        cx, ts = self.ctx, torch.cuda.current_stream()
+        stream = ts.cuda_stream
+        if d_raw is not None:
+            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
+        else:
+            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
+        self._feature_scan(n, k, d_sc, d_ln, d_nl, d_np, stream)
+        for pair in self._pairs:
+            pair.read_by(ts)                                                 # the first tick of this stream on a new map: behind its update
+        self._flush_rebase()                                                 # and, in front of the loop, the carries into that map's frame
+        self._loop(S, k, nf, d_nl, d_np, d_od, d_st, d_rp, stream)
+        return b_st, b_rp
+
+    def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
+        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does,
+        on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  Instead of
+        lidar: ranges float32 [S, k, B <= 360] and angle_min_inc float32 [S, k, 2], the fields of sensor_msgs/LaserScan messages (see
+        step_device).  n_frames: frames per robot this tick (default k each; a robot with 0 is left untouched).  Returns (states
+        FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots past a robot's n_frames are zero, and so are those of a robot that
+        sits out (FleetLocalizer).  Raises LsdError(LSD_ERR_CAPACITY) with (states, reports) in `partial` if a scan marks more than
+        pts_cap pixels or has more than 360 lines (the records are then computed from the stored part), as lsd_localize does.  One upload
+        (the raw frames, the odometry, the take flags), the device tick of step_device, one read-back.  Raises
+        LsdError(LSD_ERR_CAPACITY) as well, with (states, reports) in `partial`, when a map the tick used was made on the device
+        (set_map_device) and has more lines than its slots hold (the records of its robots are computed from the first lines_cap of
+        them), and LsdError(LSD_ERR_INTERNAL) when such a map's count is -1 (its robots saw no map lines); FleetLocalizer's message
+        names the map id, and the robots on other maps are not affected."""
+        import torch
+        if (lidar is None) == (ranges is None):
+            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
+        if ranges is None:
+            src = np.asarray(lidar, np.float64)
+            S, k = src.shape[0], src.shape[1]
+            if S != self.n_robots or src.shape[2:] != (360, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
+            n_beams = 360
+        else:
+            src = np.asarray(ranges, np.float32)
+            if src.ndim != 3 or src.shape[0] != self.n_robots or src.shape[1] < 1 or not 1 <= src.shape[2] <= 360:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            S, k, n_beams = src.shape
+            ami = np.asarray(angle_min_inc, np.float32)
+            if ami.shape != (S, k, 2):
+                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
+        od = np.ascontiguousarray(odom, np.float64).reshape(S, k, 3)
+        nf = self._n_frames(n_frames, S, k)
+        take = (np.arange(k)[None, :] < nf[:, None]).astype(np.int32)        # slots past a robot's frames: nothing to scan
+        n = S * k
+        self._staging(n)
+        b = lambda a: a.reshape(-1).view(np.uint8)
+        if ranges is None:                                                   # the frames (16-byte pairs) first
+            host_in = np.concatenate([b(src), b(od), b(take)])
+            d_src = self._in.data_ptr()
+            d_od, d_ami = d_src + n * 5760, None
+        else:                                                                # the doubles first, then the floats
+            host_in = np.concatenate([b(od), b(src), b(ami), b(take)])
+            d_od = self._in.data_ptr()
+            d_src = d_od + n * 24
+            d_ami = d_src + src.nbytes
+        d_take = self._in.data_ptr() + len(host_in) - 4 * n
+        self._in[:len(host_in)].copy_(torch.from_numpy(host_in))
+        b_st, b_rp = self._enqueue(S, k, nf, d_src if ranges is None else None, None if ranges is None else d_src, d_ami, n_beams, d_take, d_od)
+        # the device-made maps: their line counts ride in the read-back
+        live = [(i, pair.current) for i, pair in enumerate(self._pairs) if pair.current.n_host is None]
+        end = n * self._OUT_B
+        for j, (i, m) in enumerate(live):
+            self._out[end + 4 * j:end + 4 * j + 4].view(torch.int32).copy_(m.count)
+        out = self._out[:end + 4 * len(live)].cpu().numpy()                  # the tick's one synchronisation
+        states = out[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
+        reports = out[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
+        counts = out[b_st + b_rp:end].view(np.int32).reshape(2, n)
+        if live:
+            n_map = out[end:].view(np.int32)
+            for j, (i, m) in enumerate(live):
+                if n_map[j] < 0:
+                    raise LsdError(LSD_ERR_INTERNAL, self._GAVE_UP % dict(i=i), partial=(states, reports))
+            for j, (i, m) in enumerate(live):
+                if n_map[j] > m.lines_cap:
+                    raise LsdError(LSD_ERR_CAPACITY, self._OVER % dict(i=i, n=n_map[j], cap=m.lines_cap), partial=(states, reports))
+        if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
+            raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
+        return states, reports
 
     def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """step() for a caller whose scans are on the device, without an upload, a read-back or a synchronisation: everything is enqueued
@@ -1155,16 +1353,12 @@ class Localizer(_Ticks):
     FeatureScan staging live on the device (torch).  The map side (mapCallback, :97-134) is set_map from host arrays or set_map_device
     from a grid on the device: the Localizer holds two map slots, a new map is made in the one the ticks are not reading -- on a side
     stream if the caller wants -- and handed over through events, so ticks keep running on the old map meanwhile.  Like the context it
-    uses, a Localizer serves one thread at a time, and its ticks one stream at a time."""
+    uses, a Localizer serves one thread at a time, and its ticks one stream at a time.  The code is _Ticks': the methods here pass map
+    index 0 to it, and the ticks go through the single-map entries."""
 
     def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
         super().__init__(ctx, n_robots, pts_cap)
-        self.map_param = tuple(float(v) for v in map_param)
-        self._pair = _MapPair()                                    # the ticks read its current slot; a new map is made in the other one
-        self._rebase = None                                        # (from, to): the carries' move to a new map's frame, due at the next tick
-        self._lines_cap = 512
-        self._map_ctx = None
-        self.set_map(map_cache, map_lines)
+        self._set_map(0, map_cache, map_lines, map_param, False)
         self.reset(range(self.n_robots), odom0)
 
     @classmethod
@@ -1173,73 +1367,37 @@ class Localizer(_Ticks):
         _, mapCache, LSD = mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=ctx)
         return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx)
 
-    def _flush_rebase(self):
-        if self._rebase is not None:
-            import torch
-            f, t = self._rebase
-            self._rebase = None
-            self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, None, 0, f, t, torch.cuda.current_stream().cuda_stream)
+    @property
+    def map_param(self):
+        """(oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) of the map the next tick reads: set_map's default."""
+        return self._pairs[0].current.map_param
 
-    def _hand_over(self, slot, stream, cols, rows, lines_cap, n_host, map_param, grid, rebase):
-        """The pair's hand-over, with the Localizer's map_param and -- rebase -- the carries' move to the new map's frame left pending
-        for the next tick."""
-        if rebase or self.rebase_on_hand_over:
-            self._rebase = _compose_rebase(self._rebase, _frame_of(self.map_param), _frame_of(map_param))
-        self._pair.hand_over(slot, stream, cols, rows, lines_cap, n_host, map_param, grid)
-        self.map_param = map_param
+    def _rebase_key(self, i):
+        return None, 0                                                       # every robot
 
-    def _map_context(self):
-        # The map side has a context of its own (DESIGN.md 8.1.2): the detector's workspace and createMapCache's scratch belong to a
-        # context, which serves one stream at a time, and the ticks' context is busy on theirs while an update runs on a side stream.
-        if self._map_ctx is None:
-            self._map_ctx = Context(self.ctx.device)
-        return self._map_ctx
-
-    def set_map(self, map_cache, map_lines, map_param=None, rebase=False):
-        """A new map (mapCallback) from host arrays or tensors; the robots keep their carries.  It is copied, on the current torch
-        stream, into the map slot the ticks are not reading, and the ticks after the call read that slot: the hand-over of
-        set_map_device, with the line count known to the host.  rebase: as set_map_device's."""
+    def _carve(self, i):
         import torch
-        mc = map_cache if isinstance(map_cache, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(map_cache, np.float64))
-        rows, cols = mc.shape
-        ml = np.ascontiguousarray(map_lines, LINE_DTYPE)
-        mp = self.map_param if map_param is None else tuple(float(v) for v in map_param)
-        if rebase or self.rebase_on_hand_over:
-            map_frame(mp)                                                    # a frame the re-base would refuse: before anything is enqueued
-        stream = torch.cuda.current_stream()
-        slot = self._pair.target(stream, rows * cols, max(len(ml), 1))
-        slot.mc[:rows * cols].copy_(mc.reshape(-1))
-        if len(ml):
-            slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
-        slot.count.fill_(len(ml))
-        self._hand_over(slot, stream, cols, rows, max(len(ml), 1), len(ml), mp, None, rebase)
-
-    def reserve_map(self, cols, rows, lines_cap=512):
-        """Sizes everything a set_map_device of a cols x rows grid (or a smaller one) and the ticks after it need: both map slots
-        (lines_cap records each: from now on a device-made map keeps its first lines_cap lines and the ticks' workspace is sized for
-        lines_cap x 360 pairs per robot), the map side's context (lsd_reserve_map_update) and the ticks' workspace.  A set-up call: it
-        waits for the device.  After it neither set_map_device nor the ticks wait for the device or allocate."""
-        import torch
-        cols, rows, lines_cap = int(cols), int(rows), int(lines_cap)
-        if cols <= 0 or rows <= 0 or lines_cap <= 0:
-            raise LsdError(LSD_ERR_INVALID, "cols, rows and lines_cap must be positive")
-        if lines_cap * 360 > 1 << 26:
-            raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
-        torch.cuda.synchronize()
-        for i, slot in enumerate(self._pair.slots):
-            self._pair.fit(slot, rows * cols, lines_cap, keep=i == self._pair.cur)
-        self._lines_cap = lines_cap
-        self._map_context().reserve_map_update(cols, rows)
-        # a tick of no frames: nothing is launched, the workspace of n_robots sequences against lines_cap map lines is carved
-        S, cur = self.n_robots, self._pair.current
-        self._staging(S)
-        d_out = self._out.data_ptr()
-        self.ctx.enqueue_localize_resume_live_map_device(cur.mc.data_ptr(), cur.cols, cur.rows, cur.lines.data_ptr(), lines_cap,
+        S, cur, d_out = self.n_robots, self._pairs[0].current, self._out.data_ptr()
+        self.ctx.enqueue_localize_resume_live_map_device(cur.mc.data_ptr(), cur.cols, cur.rows, cur.lines.data_ptr(), self._caps[0],
                                                          cur.count.data_ptr(), S, 1, np.zeros(S, np.int32), self._lines.data_ptr(),
                                                          self._lens.data_ptr(), self._pts.data_ptr(), self.pts_cap, self._lens.data_ptr(),
                                                          self._lp.data_ptr(), self._in.data_ptr(), cur.map_param[2], self._carry.data_ptr(),
                                                          d_out, d_out, torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
+
+    def set_map(self, map_cache, map_lines, map_param=None, rebase=False):
+        """A new map (mapCallback) from host arrays or tensors (map_param: default, the one in use); the robots keep their carries.  It
+        is copied, on the current torch stream, into the map slot the ticks are not reading, and the ticks after the call read that
+        slot: the hand-over of set_map_device, with the line count known to the host, so a host-made and a device-made map can
+        alternate.  rebase: as set_map_device's."""
+        self._set_map(0, map_cache, map_lines, self.map_param if map_param is None else map_param, rebase)
+
+    def reserve_map(self, cols, rows, lines_cap=512):
+        """Sizes everything a set_map_device of a cols x rows grid (or a smaller one) and the ticks after it need: both map slots
+        (lines_cap records each: from now on a device-made map keeps its first lines_cap lines and the ticks' workspace is sized for
+        lines_cap x 360 pairs per robot), the map side's context (lsd_reserve_map_update for the largest geometry reserved so far) and
+        the ticks' workspace.  A set-up call: it waits for the device.  After it neither set_map_device nor the ticks wait for the
+        device or allocate."""
+        self._reserve_map(0, cols, rows, lines_cap)
 
     def set_map_device(self, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream=None):
         """mapCallback for an OccupancyGrid that is already on the device, without a host round trip: d_grid is a CUDA int8 tensor of
@@ -1256,124 +1414,36 @@ class Localizer(_Ticks):
         (a SLAM map that grew) leaves every lastPose off by the shift -- beyond maxEstiDist the track is lost.  This method's parameter
         list is fixed, so it has no keyword for it: set the attribute rebase_on_hand_over = True (set_map, and FleetLocalizer's set_map
         and set_map_device, also take rebase=True for one call).  With it, and a map_param that differs from the one the ticks were
-        using in mapResol, mapOriX or mapOriY, every robot's carry is moved to the new
-        frame (lsd_enqueue_fa_carry_rebase_device: the pose in metres is kept up to rounding; a robot without a pose is left alone) by
-        the first tick after this call, on that tick's stream, in front of its launches: ticks enqueued earlier read the old map with
-        old-frame carries, this tick and later ones the new map with new-frame carries, and nothing waits on the host.  Two hand-overs
-        without a tick between them compose (the earliest `from`, the latest `to`); reset, carries and a carries assignment enqueue a
-        pending re-base first.  The default, rebase_on_hand_over = False, leaves the carries alone as before.  Only the origin's
-        position and the resolution are followed: a map frame that rotates is not."""
-        cols, rows = int(oriMapCol), int(oriMapRow)
-        grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
-        stream = _cuda_stream(stream)
-        if self.rebase_on_hand_over:
-            map_frame((mapResol, mapOriX, mapOriY))                          # a frame the re-base would refuse: before anything is enqueued
-        mctx = self._map_context()
-        slot = self._pair.target(stream, rows * cols, self._lines_cap)
-        mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, float(mapResol), 2.0, slot.map.data_ptr(), slot.mc.data_ptr(),
-                                       slot.lines.data_ptr(), self._lines_cap, slot.count.data_ptr(), None, None, stream.cuda_stream)
-        self._hand_over(slot, stream, cols, rows, self._lines_cap, None, (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY)),
-                        grid, False)
+        using in mapResol, mapOriX or mapOriY, every robot's carry is moved to the new frame (lsd_enqueue_fa_carry_rebase_device: the
+        pose in metres is kept up to rounding; a robot without a pose is left alone) by the first tick after this call, on that tick's
+        stream, in front of its launches: ticks enqueued earlier read the old map with old-frame carries, this tick and later ones the
+        new map with new-frame carries, and nothing waits on the host.  Two hand-overs without a tick between them compose (the
+        earliest `from`, the latest `to`); reset, carries and a carries assignment enqueue a pending re-base first.  The default,
+        rebase_on_hand_over = False, leaves the carries alone.  Only the origin's position and the resolution are followed: a map
+        frame that rotates is not."""
+        self._set_map_device(0, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream, False)
 
     @property
     def map_counts(self):
         """The line count of the map the next tick reads: a CUDA int32 tensor of one element, valid once the update that makes the map
         has run (the caller's synchronisation).  Above lines_cap: the ticks use the first lines_cap lines; -1: the detector gave the map
         up and the ticks see no map lines."""
-        return self._pair.current.count
+        return self._pairs[0].current.count
 
-    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
-        """The tick on the current torch stream, every input on the device: ingest, FeatureScan, the resume entry.  Returns the byte
-        sizes of the states and the reports in self._out."""
-        import torch
-        n = S * k
-        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
-        self._out[:b_st + b_rp].zero_()
-        d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
-        d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
-        d_np = d_nl + 4 * n
-        cx, stream = self.ctx, torch.cuda.current_stream().cuda_stream
-        if d_raw is not None:
-            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
-        else:
-            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
-        mp = self.map_param
-        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_sc, d_ln, n, 360, _map_param(mp), rdp_leastPoint, rdp_threLine, rdp_leastDist,
-                                                           self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np,
-                                                           self._lp.data_ptr(), self._sz.data_ptr(), stream))
-        m = self._pair.read_by(torch.cuda.current_stream())                  # the first tick of this stream on a new map: behind its update
-        self._flush_rebase()                                                 # and, in front of its launches, the carries into that map's frame
-        tail = (S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap, d_np, self._lp.data_ptr(), d_od, mp[2],
-                self._carry.data_ptr(), d_st, d_rp, stream)
+    def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
+        cx, m = self.ctx, self._pairs[0].current
+        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_scans, d_lens, n, 360, _map_param(m.map_param), rdp_leastPoint, rdp_threLine,
+                                                           rdp_leastDist, self._lines.data_ptr(), d_n_lines, self._pts.data_ptr(), self.pts_cap,
+                                                           d_n_pts, self._lp.data_ptr(), self._sz.data_ptr(), stream))
+
+    def _loop(self, S, k, nf, d_n_lines, d_n_pts, d_od, d_states, d_reports, stream):
+        m = self._pairs[0].current
+        tail = (S, k, nf, self._lines.data_ptr(), d_n_lines, self._pts.data_ptr(), self.pts_cap, d_n_pts, self._lp.data_ptr(), d_od, m.map_param[2],
+                self._carry.data_ptr(), d_states, d_reports, stream)
         if m.n_host is not None:
-            cx.enqueue_localize_resume_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.n_host, *tail)
+            self.ctx.enqueue_localize_resume_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.n_host, *tail)
         else:                                                                # a map made on the device: so is its line count
-            cx.enqueue_localize_resume_live_map_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.lines_cap, m.count.data_ptr(), *tail)
-        return b_st, b_rp
-
-    def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
-        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does,
-        on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  Instead of
-        lidar: ranges float32 [S, k, B <= 360] and angle_min_inc float32 [S, k, 2], the fields of sensor_msgs/LaserScan messages (see
-        step_device).  n_frames: frames per robot this tick (default k each; a robot with 0 is left untouched).  Returns (states
-        FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots past a robot's n_frames are zero.  Raises LsdError(LSD_ERR_CAPACITY)
-        with (states, reports) in `partial` if a scan marks more than pts_cap pixels or has more than 360 lines (the records are then
-        computed from the stored part), as lsd_localize does.  One upload (the raw frames, the odometry, the take flags), the device
-        tick of step_device, one read-back.  Raises LsdError(LSD_ERR_CAPACITY) as well, with (states, reports) in `partial`, when the
-        map the tick used was made on the device (set_map_device) and has more lines than its slot holds (the records are computed
-        from the first lines_cap of them), and LsdError(LSD_ERR_INTERNAL) when that map's count is -1."""
-        import torch
-        if (lidar is None) == (ranges is None):
-            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
-        if ranges is None:
-            src = np.asarray(lidar, np.float64)
-            S, k = src.shape[0], src.shape[1]
-            if S != self.n_robots or src.shape[2:] != (360, 2) or k < 1:
-                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
-            n_beams = 360
-        else:
-            src = np.asarray(ranges, np.float32)
-            if src.ndim != 3 or src.shape[0] != self.n_robots or src.shape[1] < 1 or not 1 <= src.shape[2] <= 360:
-                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
-            S, k, n_beams = src.shape
-            ami = np.asarray(angle_min_inc, np.float32)
-            if ami.shape != (S, k, 2):
-                raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
-        od = np.ascontiguousarray(odom, np.float64).reshape(S, k, 3)
-        nf = self._n_frames(n_frames, S, k)
-        take = (np.arange(k)[None, :] < nf[:, None]).astype(np.int32)        # slots past a robot's frames: nothing to scan
-        n = S * k
-        self._staging(n)
-        b = lambda a: a.reshape(-1).view(np.uint8)
-        if ranges is None:                                                   # the frames (16-byte pairs) first, as they always were
-            host_in = np.concatenate([b(src), b(od), b(take)])
-            d_src = self._in.data_ptr()
-            d_od, d_ami = d_src + n * 5760, None
-        else:                                                                # the doubles first, then the floats
-            host_in = np.concatenate([b(od), b(src), b(ami), b(take)])
-            d_od = self._in.data_ptr()
-            d_src = d_od + n * 24
-            d_ami = d_src + src.nbytes
-        d_take = self._in.data_ptr() + len(host_in) - 4 * n
-        self._in[:len(host_in)].copy_(torch.from_numpy(host_in))
-        b_st, b_rp = self._enqueue(S, k, nf, d_src if ranges is None else None, None if ranges is None else d_src, d_ami, n_beams, d_take, d_od)
-        m = self._pair.current
-        live = m.n_host is None                                              # a device-made map: its line count rides in the read-back
-        if live:
-            self._out[n * self._OUT_B:n * self._OUT_B + 4].view(torch.int32).copy_(m.count)
-        out = self._out[:n * self._OUT_B + (4 if live else 0)].cpu().numpy()  # the tick's one synchronisation
-        states = out[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
-        reports = out[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
-        counts = out[b_st + b_rp:n * self._OUT_B].view(np.int32).reshape(2, n)
-        n_map = int(out[n * self._OUT_B:].view(np.int32)[0]) if live else m.n_host
-        if n_map < 0:
-            raise LsdError(LSD_ERR_INTERNAL, "the detector gave the map up (count -1): the tick saw no map lines", partial=(states, reports))
-        if n_map > m.lines_cap:
-            raise LsdError(LSD_ERR_CAPACITY, "the map has %d lines, its slot holds %d (reserve_map): the tick used the first %d"
-                           % (n_map, m.lines_cap, m.lines_cap), partial=(states, reports))
-        if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
-            raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
-        return states, reports
+            self.ctx.enqueue_localize_resume_live_map_device(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.lines_cap, m.count.data_ptr(), *tail)
 
 
 def fleet_map_ids(map_ids, n_maps, count=None):
@@ -1393,13 +1463,15 @@ class FleetLocalizer(_Ticks):
     it.  maps: a list of (map_cache, map_lines, map_param) host arrays, one per map id (at most LSD_MAX_MAPS); map_of: one id per robot
     -- this sets n_robots --, or -1 for a robot that sits out (parked, between floors): its carry stays as it is and its slots of a
     tick's results stay zero.  The ids live on the device: assign() rewrites them on the current stream.  step, step_device, reset and
-    carries are as Localizer's (step_device, reset and carries are the same code).  The map side is Localizer's, per map id: every map
-    has two slots, set_map(i, ...) from host arrays or set_map_device(i, ...) from a grid on the device makes the new map in the slot
-    the ticks are not reading -- on a side stream if the caller wants -- and hands it over through events, so the ticks keep running
-    on the old map meanwhile; reserve_map(i, ...) sizes what that needs.  One map-side context serves all maps: updates of different
-    maps on different streams serialise on the device (lsd_enqueue_map_update_device orders itself behind the context's previous run
-    with an event), never on the host.  Like the context it uses, a FleetLocalizer serves one thread at a time, and its ticks one
-    stream at a time."""
+    carries are Localizer's (the same code, _Ticks').  So is the map side, per map id: every map has two slots, set_map(i, ...) from
+    host arrays or set_map_device(i, ...) from a grid on the device makes the new map in the slot the ticks are not reading -- on a side
+    stream if the caller wants -- and hands it over through events, so the ticks keep running on the old map meanwhile;
+    reserve_map(i, ...) sizes what that needs.  One map-side context serves all maps: updates of different maps on different streams
+    serialise on the device (lsd_enqueue_map_update_device orders itself behind the context's previous run with an event), never on
+    the host.  Like the context it uses, a FleetLocalizer serves one thread at a time, and its ticks one stream at a time."""
+
+    _GAVE_UP = "map %(i)d: the detector gave the map up (count -1): the tick saw no map lines"
+    _OVER = "map %(i)d has %(n)d lines, its slots hold %(cap)d (reserve_map): the tick used the first %(cap)d"
 
     def __init__(self, maps, map_of, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
         import torch
@@ -1411,13 +1483,8 @@ class FleetLocalizer(_Ticks):
         ids = fleet_map_ids(map_of, len(maps))
         if not len(ids):
             raise LsdError(LSD_ERR_INVALID, "at least one robot")
-        super().__init__(ctx, len(ids), pts_cap)
-        self._tail_b = 4 * len(maps)
-        self._table = np.zeros(len(maps), MAP_REF_DTYPE)
-        self._pairs = [_MapPair() for _ in maps]                             # per map id: the slot the ticks read, and the other one
-        self._caps = [512] * len(maps)                                       # per map id: the line records a device-made map keeps (reserve_map)
-        self._rebases = {}                                                   # map id -> (from, to): due at the next tick, for the robots then on it
-        self._map_ctx, self._map_geom = None, (0, 0)
+        super().__init__(ctx, len(ids), pts_cap, len(maps))
+        self._table = np.zeros(len(maps), MAP_REF_DTYPE)                     # what the *_maps entries take: record i names map i's current slot
         self._mask = None
         for i, m in enumerate(maps):
             self.set_map(i, *m)
@@ -1439,91 +1506,32 @@ class FleetLocalizer(_Ticks):
             raise LsdError(LSD_ERR_INVALID, "map %d of %d" % (i, len(self._table)))
         return i
 
-    def _map_context(self):
-        # one context for the map side of every map (Localizer._map_context: the ticks' context is busy on their stream)
-        if self._map_ctx is None:
-            self._map_ctx = Context(self.ctx.device)
-        return self._map_ctx
+    def _rebase_key(self, i):
+        return self._map_of.data_ptr(), i                                    # the robots on map i
 
-    def _flush_rebase(self):
-        if self._rebases:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-            pending, self._rebases = self._rebases, {}
-            for i, (f, t) in pending.items():                                # "the robots on map i", read when the kernel runs
-                self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, self._map_of.data_ptr(), i, f, t, stream)
+    def _map_changed(self, i):
+        m = self._pairs[i].current                                           # a device-made map: its count on the device, lines_cap as the capacity
+        self._table[i] = map_ref(m.mc.data_ptr(), m.cols, m.rows, m.lines.data_ptr(), m.lines_cap if m.n_host is None else m.n_host, m.map_param,
+                                 m.count.data_ptr() if m.n_host is None else 0)
 
-    def _hand_over(self, i, slot, stream, cols, rows, lines_cap, n_host, map_param, grid, rebase):
-        """Map i's hand-over: the pair's, table record i, and -- rebase -- the move of the carries of the robots on map i left pending
-        for the next tick."""
-        pair = self._pairs[i]
-        if (rebase or self.rebase_on_hand_over) and pair.current.map_param is not None:
-            r = _compose_rebase(self._rebases.get(i), _frame_of(pair.current.map_param), _frame_of(map_param))
-            self._rebases.pop(i, None)
-            if r is not None:
-                self._rebases[i] = r
-        pair.hand_over(slot, stream, cols, rows, lines_cap, n_host, map_param, grid)
-        self._table[i] = map_ref(slot.mc.data_ptr(), cols, rows, slot.lines.data_ptr(), lines_cap if n_host is None else n_host, map_param,
-                                 slot.count.data_ptr() if n_host is None else 0)
-
-    def set_map(self, i, map_cache, map_lines, map_param, rebase=False):
-        """Replaces map i from host arrays.  It is copied, on the current torch stream, into the slot of map i that the ticks are not
-        reading, and the ticks after the call read that slot: the hand-over of set_map_device with the line count known to the host, so
-        a host-made and a device-made map can alternate on one id.  The robots on it keep their carries; rebase: as set_map_device's."""
+    def _carve(self, i):
         import torch
-        i = self._map_id(i)
-        mc = np.ascontiguousarray(map_cache, np.float64)
-        ml = np.ascontiguousarray(map_lines, LINE_DTYPE).reshape(-1)
-        mp = tuple(float(v) for v in map_param)
-        if mc.ndim != 2 or not mc.size or len(mp) != 5 or not mp[2] > 0:
-            raise LsdError(LSD_ERR_INVALID, "map_cache is [rows, cols], map_param (oriMapCol, oriMapRow, mapResol > 0, mapOriX, mapOriY)")
-        if len(ml) * 360 > 1 << 26:
-            raise LsdError(LSD_ERR_UNSUPPORTED, "map lines x 360 pairs per robot exceed 1 << 26")
-        if rebase or self.rebase_on_hand_over:
-            map_frame(mp)
-        rows, cols = mc.shape
-        stream = torch.cuda.current_stream()
-        slot = self._pairs[i].target(stream, rows * cols, max(len(ml), 1))
-        slot.mc[:rows * cols].copy_(torch.from_numpy(mc.reshape(-1)))
-        if len(ml):
-            slot.lines[:80 * len(ml)].copy_(torch.from_numpy(ml.view(np.uint8).reshape(-1).copy()))
-        slot.count.fill_(len(ml))
-        self._hand_over(i, slot, stream, cols, rows, max(len(ml), 1), len(ml), mp, None, rebase)
-
-    def reserve_map(self, i, cols, rows, lines_cap=512):
-        """Sizes everything a set_map_device(i, ...) of a cols x rows grid (or a smaller one) and the ticks after it need: both slots of
-        map i (lines_cap records each: from now on a device-made map i keeps its first lines_cap lines), the one map-side context
-        (lsd_reserve_map_update for the largest geometry reserved so far) and the ticks' workspace (for the largest lines_cap and line
-        count of the table).  A set-up call: it waits for the device.  After it neither set_map_device(i, ...) nor the ticks wait for
-        the device or allocate."""
-        import torch
-        i, cols, rows, lines_cap = self._map_id(i), int(cols), int(rows), int(lines_cap)
-        if cols <= 0 or rows <= 0 or lines_cap <= 0:
-            raise LsdError(LSD_ERR_INVALID, "cols, rows and lines_cap must be positive")
-        if lines_cap * 360 > 1 << 26:
-            raise LsdError(LSD_ERR_UNSUPPORTED, "lines_cap x 360 pairs per robot exceed 1 << 26")
-        torch.cuda.synchronize()
-        pair = self._pairs[i]
-        for j, slot in enumerate(pair.slots):
-            pair.fit(slot, rows * cols, lines_cap, keep=j == pair.cur)
-        cur = pair.current                                                   # (its tensors may have moved)
-        self._table[i]["d_map_cache"], self._table[i]["d_map_lines"] = cur.mc.data_ptr(), cur.lines.data_ptr()
-        if cur.n_host is None:
-            self._table[i]["d_n_map"] = cur.count.data_ptr()
-        self._caps[i] = lines_cap
-        self._map_geom = (max(self._map_geom[0], cols), max(self._map_geom[1], rows))
-        self._map_context().reserve_map_update(*self._map_geom)
-        # a tick of no frames: nothing is launched, the workspace of n_robots sequences against the largest line capacity is carved
-        S = self.n_robots
-        self._staging(S)
+        S, d_out = self.n_robots, self._out.data_ptr()
         tab = self._table.copy()
-        tab[i]["n_map"] = max(max(self._caps), int(tab["n_map"].max()))      # (no frame: no record of it is read)
-        d_out = self._out.data_ptr()
+        tab[i]["n_map"] = max(max(self._caps), int(tab["n_map"].max()))      # the table's largest capacity (no frame: no record of it is read)
         self.ctx.enqueue_localize_resume_maps_device(tab, self._map_of.data_ptr(), S, 1, np.zeros(S, np.int32), self._lines.data_ptr(),
                                                      self._lens.data_ptr(), self._pts.data_ptr(), self.pts_cap, self._lens.data_ptr(),
                                                      self._lp.data_ptr(), self._in.data_ptr(), self._carry.data_ptr(), d_out, d_out,
                                                      torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
+
+    def set_map(self, i, map_cache, map_lines, map_param, rebase=False):
+        """Localizer.set_map for map i; the robots on it keep their carries, the robots on other maps are not affected."""
+        self._set_map(self._map_id(i), map_cache, map_lines, map_param, rebase)
+
+    def reserve_map(self, i, cols, rows, lines_cap=512):
+        """Localizer.reserve_map for map i: both slots of map i, the one map-side context, and the ticks' workspace for the largest
+        lines_cap and line count of the table."""
+        self._reserve_map(self._map_id(i), cols, rows, lines_cap)
 
     def set_map_device(self, i, d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream=None, rebase=False):
         """Localizer.set_map_device for map i: the whole map callback (lsd_enqueue_map_update_device) is enqueued on `stream` (a
@@ -1536,20 +1544,7 @@ class FleetLocalizer(_Ticks):
         rebase=True: when the new map_param differs from the one the ticks were using for map i in mapResol, mapOriX or mapOriY, the
         carries of the robots that are on map i when the next tick runs are moved to the new frame by that tick, in front of its
         launches (Localizer.set_map_device; lsd_enqueue_fa_carry_rebase_device with d_key = the robots' map ids, key = i)."""
-        i = self._map_id(i)
-        cols, rows = int(oriMapCol), int(oriMapRow)
-        grid = _occupancy_grid(d_grid, cols, rows, self.ctx.device)
-        stream = _cuda_stream(stream)
-        mp = (float(cols), float(rows), float(mapResol), float(mapOriX), float(mapOriY))
-        if not mp[2] > 0:
-            raise LsdError(LSD_ERR_INVALID, "mapResol must be > 0")
-        if rebase or self.rebase_on_hand_over:
-            map_frame(mp)
-        mctx, cap = self._map_context(), self._caps[i]
-        slot = self._pairs[i].target(stream, rows * cols, cap)
-        mctx.enqueue_map_update_device(grid.data_ptr(), cols, rows, mp[2], 2.0, slot.map.data_ptr(), slot.mc.data_ptr(), slot.lines.data_ptr(), cap,
-                                       slot.count.data_ptr(), None, None, stream.cuda_stream)
-        self._hand_over(i, slot, stream, cols, rows, cap, None, mp, grid, rebase)
+        self._set_map_device(self._map_id(i), d_grid, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, stream, rebase)
 
     @property
     def map_counts(self):
@@ -1601,78 +1596,14 @@ class FleetLocalizer(_Ticks):
         self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, self._mask.data_ptr(), 1, f, t,
                                                 torch.cuda.current_stream().cuda_stream)
 
-    def _enqueue(self, S, k, nf, d_raw, d_ranges, d_ami, n_beams, d_take, d_od):
-        """Localizer's tick through the fleet entries: ingest, FeatureScan with each robot's map geometry, the resume loop with each
-        robot's map -- behind the update of every map whose current slot this stream has not read yet, and behind the pending
-        re-bases."""
-        import torch
-        n = S * k
-        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
-        self._out[:b_st + b_rp].zero_()
-        d_sc, d_ln, d_out = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
-        d_st, d_rp, d_nl = d_out, d_out + b_st, d_out + b_st + b_rp
-        d_np = d_nl + 4 * n
-        cx, ts = self.ctx, torch.cuda.current_stream()
-        stream = ts.cuda_stream
-        if d_raw is not None:
-            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
-        else:
-            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
-        d_of = self._map_of.data_ptr()
-        cx.enqueue_feature_scan_maps_device(d_sc, d_ln, n, 360, self._table, d_of, k, self._lines.data_ptr(), d_nl, self._pts.data_ptr(),
-                                            self.pts_cap, d_np, self._lp.data_ptr(), self._sz.data_ptr(), stream=stream)
-        for pair in self._pairs:
-            pair.read_by(ts)
-        self._flush_rebase()
-        cx.enqueue_localize_resume_maps_device(self._table, d_of, S, k, nf, self._lines.data_ptr(), d_nl, self._pts.data_ptr(), self.pts_cap,
-                                               d_np, self._lp.data_ptr(), d_od, self._carry.data_ptr(), d_st, d_rp, stream)
-        return b_st, b_rp
+    def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
+        self.ctx.enqueue_feature_scan_maps_device(d_scans, d_lens, n, 360, self._table, self._map_of.data_ptr(), k, self._lines.data_ptr(), d_n_lines,
+                                                  self._pts.data_ptr(), self.pts_cap, d_n_pts, self._lp.data_ptr(), self._sz.data_ptr(), stream=stream)
 
-    def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
-        """Localizer.step for the fleet: the same arguments, results and errors, with (states, reports) in `partial`:
-        LsdError(LSD_ERR_CAPACITY) if a scan marks more than pts_cap pixels or has more than 360 lines, or if a map the tick used was
-        made on the device and has more lines than its slots hold (the records of its robots are computed from the first lines_cap of
-        them), LsdError(LSD_ERR_INTERNAL) if such a map's count is -1 (its robots saw no map lines); the message names the map id, and
-        the robots on other maps are not affected.  The slots of a robot that sits out are zero, like those past a robot's n_frames.
-        The host side differs from Localizer.step in one respect: the inputs are not packed into one staging upload but uploaded as
-        they are (the frames, the odometry, with ranges= the two float arrays; the take flags by step_device), then the device tick of
-        step_device and one read-back of the output staging, whose layout (states, reports, FeatureScan's counts, then the line counts
-        of the device-made maps) is the same."""
-        import torch
-        if (lidar is None) == (ranges is None):
-            raise LsdError(LSD_ERR_INVALID, "give either lidar or ranges")
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
-        src = np.asarray(lidar, np.float64) if ranges is None else np.asarray(ranges, np.float32)
-        od = np.asarray(odom, np.float64)
-        if src.ndim >= 2 and od.size == src.shape[0] * src.shape[1] * 3:
-            od = od.reshape(src.shape[0], src.shape[1], 3)
-        if ranges is None:
-            out = self.step_device(up(src, np.float64), up(od, np.float64), n_frames)
-        else:
-            out = self.step_device(None, up(od, np.float64), n_frames, ranges=up(src, np.float32),
-                                   angle_min_inc=up(angle_min_inc, np.float32))
-        S, k = out[0].shape[:2]
-        n = S * k
-        b_st, b_rp = n * FA_STATE_DTYPE.itemsize, n * FA_REPORT_DTYPE.itemsize
-        live = [(i, pair.current) for i, pair in enumerate(self._pairs) if pair.current.n_host is None]
-        for j, (i, m) in enumerate(live):                                      # the device-made maps: their line counts ride in the read-back
-            self._out[n * self._OUT_B + 4 * j:n * self._OUT_B + 4 * j + 4].view(torch.int32).copy_(m.count)
-        host = self._out[:n * self._OUT_B + 4 * len(live)].cpu().numpy()      # the tick's one synchronisation
-        states = host[:b_st].view(FA_STATE_DTYPE).reshape(S, k)
-        reports = host[b_st:b_st + b_rp].view(FA_REPORT_DTYPE).reshape(S, k)
-        counts = host[b_st + b_rp:n * self._OUT_B].view(np.int32).reshape(2, n)
-        n_map = host[n * self._OUT_B:].view(np.int32)
-        for j, (i, m) in enumerate(live):
-            if n_map[j] < 0:
-                raise LsdError(LSD_ERR_INTERNAL, "map %d: the detector gave the map up (count -1): the tick saw no map lines" % i,
-                               partial=(states, reports))
-        for j, (i, m) in enumerate(live):
-            if n_map[j] > m.lines_cap:
-                raise LsdError(LSD_ERR_CAPACITY, "map %d has %d lines, its slots hold %d (reserve_map): the tick used the first %d"
-                               % (i, n_map[j], m.lines_cap, m.lines_cap), partial=(states, reports))
-        if (counts[0] > 360).any() or (counts[1] > self.pts_cap).any():
-            raise LsdError(LSD_ERR_CAPACITY, load_library().lsd_strerror(LSD_ERR_CAPACITY).decode(), partial=(states, reports))
-        return states, reports
+    def _loop(self, S, k, nf, d_n_lines, d_n_pts, d_od, d_states, d_reports, stream):
+        self.ctx.enqueue_localize_resume_maps_device(self._table, self._map_of.data_ptr(), S, k, nf, self._lines.data_ptr(), d_n_lines,
+                                                     self._pts.data_ptr(), self.pts_cap, d_n_pts, self._lp.data_ptr(), d_od, self._carry.data_ptr(),
+                                                     d_states, d_reports, stream)
 
 
 def mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=None):

@@ -1085,12 +1085,20 @@ int lsd_scan_to_map_match(lsd_ctx* c, const double* map_cache, int cols, int row
     return LSD_OK;
 }
 
+// the two FeatureScan enqueue entries: the argument check they share
+static bool feature_scan_args_bad(const lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const lsd_line* d_lines_out,
+                                  const int* d_n_lines, const lsd_position* d_pts_out, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
+                                  const int* d_im_size) {
+    return !c || !d_scans || !d_lens || n_scans <= 0 || stride <= 0 || !d_lines_out || !d_n_lines || !d_n_pts || !d_lidar_pos || !d_im_size ||
+           pts_cap < 0 || (pts_cap > 0 && !d_pts_out);
+}
+
 int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride,
                                           lsd_map_param mp, int region_point_limit, double thre_line, double line_dist_thre_m,
                                           lsd_line* d_lines_out, int* d_n_lines, lsd_position* d_pts_out, int pts_cap, int* d_n_pts,
                                           double* d_lidar_pos, int* d_im_size, void* stream) {
-    if (!c || !d_scans || !d_lens || n_scans <= 0 || stride <= 0 || !d_lines_out || !d_n_lines || !d_n_pts || !d_lidar_pos || !d_im_size ||
-        pts_cap < 0 || (pts_cap > 0 && !d_pts_out) || !(mp.mapResol > 0))
+    if (feature_scan_args_bad(c, d_scans, d_lens, n_scans, stride, d_lines_out, d_n_lines, d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size) ||
+        !(mp.mapResol > 0))
         return LSD_ERR_INVALID;
     if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1142,8 +1150,8 @@ int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, c
                                          int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* d_lines_out,
                                          int* d_n_lines, lsd_position* d_pts_out, int pts_cap, int* d_n_pts, double* d_lidar_pos,
                                          int* d_im_size, void* stream) {
-    if (!c || !d_scans || !d_lens || n_scans <= 0 || stride <= 0 || !d_lines_out || !d_n_lines || !d_n_pts || !d_lidar_pos || !d_im_size ||
-        pts_cap < 0 || (pts_cap > 0 && !d_pts_out) || scans_per_seq <= 0)
+    if (feature_scan_args_bad(c, d_scans, d_lens, n_scans, stride, d_lines_out, d_n_lines, d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size) ||
+        scans_per_seq <= 0)
         return LSD_ERR_INVALID;
     const int r = map_table_check(maps, n_maps, d_map_of, nullptr);
     if (r != LSD_OK) return r;
@@ -1376,27 +1384,39 @@ int lsd_enqueue_fa_carry_rebase_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_
     return LSD_OK;
 }
 
-// The replay loop of both device entry points: d_init (lsd_enqueue_localize_device, odometry n_seq x (frames_pitch + 1)) or d_carry
-// (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch) -- exactly one of them is given.  d_n_map (the live-map entries):
-// the map's line count is read on the device and n_map is its capacity; everything the host sizes is sized from n_map either way.
-// fleet (the *_maps entries): the single-map arguments are unused, sequence s runs against maps[d_map_of[s]] and n_map is the table's
-// largest.
-static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
-                           const int32_t* d_n_map, bool fleet, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
-                           int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
-                           const lsd_fa_state* d_init, lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
-    if (!c || n_seq <= 0 || frames_pitch <= 0 || !n_frames || !d_lines || !d_n_lines || pts_cap < 0 || (pts_cap > 0 && !d_pts) || !d_n_pts ||
-        !d_lidar_pos || !d_odom || !(d_init || d_carry) || !d_states || !d_reports)
+// What the replay loop runs against.  One map: its fields; with d_n_map (the live-map entries) the map's line count is read on the device
+// and n_map is its capacity.  Or the table (the *_maps entries; a non-null `maps` is what selects it): sequence s runs against
+// maps[d_map_of[s]] and the single-map fields are unused.  Everything the host sizes is sized from n_map, resp. the table's largest.
+struct FaLoopMap {
+    const double* d_map_cache; int cols, rows; const lsd_line* d_map_lines; int n_map; const int32_t* d_n_map; double map_resol;
+    const lsd_map_ref* maps; int n_maps; const int32_t* d_map_of;
+};
+
+// The frames of the loop: FeatureScan's outputs, the odometry, where each sequence starts from -- d_init (lsd_enqueue_localize_device,
+// odometry n_seq x (frames_pitch + 1)) or d_carry (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch), exactly one of
+// them -- and the outputs.
+struct FaLoopFrames {
+    int n_seq, frames_pitch; const int* n_frames;
+    const lsd_line* d_lines; const int* d_n_lines; const lsd_position* d_pts; int pts_cap; const int* d_n_pts; const double* d_lidar_pos;
+    const lsd_position* d_odom; const lsd_fa_state* d_init; lsd_fa_carry* d_carry; lsd_fa_state* d_states; lsd_fa_report* d_reports;
+};
+
+// The replay loop of every device entry point.
+static int fa_enqueue_loop(lsd_ctx* c, const FaLoopMap& m, const FaLoopFrames& f, void* stream) {
+    const int n_seq = f.n_seq;
+    if (!c || n_seq <= 0 || f.frames_pitch <= 0 || !f.n_frames || !f.d_lines || !f.d_n_lines || f.pts_cap < 0 || (f.pts_cap > 0 && !f.d_pts) ||
+        !f.d_n_pts || !f.d_lidar_pos || !f.d_odom || !(f.d_init || f.d_carry) || !f.d_states || !f.d_reports)
         return LSD_ERR_INVALID;
-    if (!fleet && (!d_map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !d_map_lines) || !(map_resol > 0)))
+    if (!m.maps && (!m.d_map_cache || m.cols <= 0 || m.rows <= 0 || m.n_map < 0 || (m.n_map > 0 && !m.d_map_lines) || !(m.map_resol > 0)))
         return LSD_ERR_INVALID;
     int max_frames = 0;
     for (int i = 0; i < n_seq; i++) {
-        if (n_frames[i] < 0 || n_frames[i] > frames_pitch) return LSD_ERR_INVALID;
-        max_frames = std::max(max_frames, n_frames[i]);
+        if (f.n_frames[i] < 0 || f.n_frames[i] > f.frames_pitch) return LSD_ERR_INVALID;
+        max_frames = std::max(max_frames, f.n_frames[i]);
     }
-    if (fleet) {
-        const int r = map_table_check(maps, n_maps, d_map_of, &n_map);
+    int n_map = m.n_map;
+    if (m.maps) {
+        const int r = map_table_check(m.maps, m.n_maps, m.d_map_of, &n_map);
         if (r != LSD_OK) return r;
     }
     if ((long long)n_map * LSD_RDP_MAX_LINES > (1 << 26)) return LSD_ERR_UNSUPPORTED;
@@ -1405,18 +1425,19 @@ static int fa_enqueue_loop(lsd_ctx* c, const double* d_map_cache, int cols, int 
     const int r = fa_workspace(c, n_seq, std::max(1, n_map * LSD_RDP_MAX_LINES), a);
     if (r != LSD_OK) return r;
     hipStream_t s = (hipStream_t)stream;
-    c->fa_nf.assign(n_frames, n_frames + n_seq);
+    c->fa_nf.assign(f.n_frames, f.n_frames + n_seq);
     HIPCHK(c, hipMemcpyAsync(const_cast<int*>(a.n_frames), c->fa_nf.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
-    if (fleet) {
-        const int u = map_table_upload(c, 1, maps, n_maps, s, &a.maps);
+    if (m.maps) {
+        const int u = map_table_upload(c, 1, m.maps, m.n_maps, s, &a.maps);
         if (u != LSD_OK) return u;
-        a.map_of = d_map_of; a.n_maps = n_maps;
+        a.map_of = m.d_map_of; a.n_maps = m.n_maps;
     }
-    a.map_cache = d_map_cache; a.cols = cols; a.rows = rows; a.map_lines = d_map_lines; a.n_map = n_map; a.d_n_map = d_n_map;
-    a.scan_lines = d_lines; a.n_lines = d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
-    a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = d_n_pts; a.pts_pitch = pts_cap;
-    a.lidar_pos = d_lidar_pos; a.frames_pitch = frames_pitch; a.odom = d_odom; a.given = nullptr; a.map_resol = map_resol;
-    a.init = d_init; a.carry = d_carry; a.state_in = nullptr; a.states = d_states; a.reports = d_reports;
+    a.map_cache = m.d_map_cache; a.cols = m.cols; a.rows = m.rows; a.map_lines = m.d_map_lines; a.n_map = n_map; a.d_n_map = m.d_n_map;
+    a.scan_lines = f.d_lines; a.n_lines = f.d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
+    a.pts = reinterpret_cast<const double*>(f.d_pts); a.n_pts = f.d_n_pts; a.pts_pitch = f.pts_cap;
+    a.lidar_pos = f.d_lidar_pos; a.frames_pitch = f.frames_pitch; a.odom = f.d_odom; a.given = nullptr;
+    a.map_resol = m.maps ? 1.0 : m.map_resol;                    // (the table carries each map's own)
+    a.init = f.d_init; a.carry = f.d_carry; a.state_in = nullptr; a.states = f.d_states; a.reports = f.d_reports;
     for (int t = 0; t < max_frames; t++) {
         a.t = t;
         launch_fa_frame(a, n_seq, true, s);
@@ -1432,8 +1453,12 @@ int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols,
                                 const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
                                 lsd_fa_report* d_reports, void* stream) {
     if (!d_init) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
-                           d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
+    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = n_map,
+                           .map_resol = map_resol};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
@@ -1442,8 +1467,12 @@ int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, in
                                        const lsd_position* d_odom, double map_resol, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
                                        lsd_fa_report* d_reports, void* stream) {
     if (!d_carry) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, n_map, nullptr, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines, d_pts, pts_cap,
-                           d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
+    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = n_map,
+                           .map_resol = map_resol};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_enqueue_localize_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
@@ -1452,8 +1481,12 @@ int lsd_enqueue_localize_live_map_device(lsd_ctx* c, const double* d_map_cache, 
                                          const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                                          const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!d_init || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
-                           d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, d_init, nullptr, d_states, d_reports, stream);
+    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = map_lines_cap,
+                           .d_n_map = d_n_map, .map_resol = map_resol};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_enqueue_localize_resume_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
@@ -1462,8 +1495,12 @@ int lsd_enqueue_localize_resume_live_map_device(lsd_ctx* c, const double* d_map_
                                                 const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
                                                 lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!d_carry || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, d_map_cache, cols, rows, d_map_lines, map_lines_cap, d_n_map, false, nullptr, 0, nullptr, n_seq, frames_pitch, n_frames, d_lines, d_n_lines,
-                           d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, map_resol, nullptr, d_carry, d_states, d_reports, stream);
+    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = map_lines_cap,
+                           .d_n_map = d_n_map, .map_resol = map_resol};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_enqueue_localize_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq, int frames_pitch,
@@ -1471,8 +1508,11 @@ int lsd_enqueue_localize_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_
                                      int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom,
                                      const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
     if (!d_init) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, nullptr, 0, 0, nullptr, 0, nullptr, true, maps, n_maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines,
-                           d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, 1.0, d_init, nullptr, d_states, d_reports, stream);
+    const FaLoopMap map = {.maps = maps, .n_maps = n_maps, .d_map_of = d_map_of};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_enqueue_localize_resume_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq,
@@ -1481,8 +1521,11 @@ int lsd_enqueue_localize_resume_maps_device(lsd_ctx* c, const lsd_map_ref* maps,
                                             const lsd_position* d_odom, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
                                             lsd_fa_report* d_reports, void* stream) {
     if (!d_carry) return LSD_ERR_INVALID;
-    return fa_enqueue_loop(c, nullptr, 0, 0, nullptr, 0, nullptr, true, maps, n_maps, d_map_of, n_seq, frames_pitch, n_frames, d_lines,
-                           d_n_lines, d_pts, pts_cap, d_n_pts, d_lidar_pos, d_odom, 1.0, nullptr, d_carry, d_states, d_reports, stream);
+    const FaLoopMap map = {.maps = maps, .n_maps = n_maps, .d_map_of = d_map_of};
+    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
+                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
+                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
+    return fa_enqueue_loop(c, map, frames, stream);
 }
 
 int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,
