@@ -233,12 +233,24 @@ int lsd_enqueue_scan_to_map_match_device(lsd_ctx *ctx, const double *d_map_cache
  *                            their number, of which the first pts_cap are stored
  *   lidar_pos[2 i .. ]       structLidarPointRec lidarPos (x, y), :33-36;  im_size[2 i ..] = (cols, rows) of FS.lineIm, :31
  * FS.lineIm itself is im_size zeros with 255 at the listed pixels.  region_point_limit / thre_line / line_dist_thre_m are
- * rdp_leastPoint / rdp_threLine / rdp_leastDist (LSD/baseFunc.h:70-72: 3, 0.08, 0.5).  lens[i] <= 1024.
+ * rdp_leastPoint / rdp_threLine / rdp_leastDist (LSD/baseFunc.h:70-72: 3, 0.08, 0.5).  lens[i] <= stride <= the context's scan
+ * capacity (lsd_set_scan_capacity: 1024 unless raised); a larger stride is LSD_ERR_UNSUPPORTED.
  * lsd_polar is structLidarPointPolar (LSD/myRDP.h:34-38) without its `split` work flag; lsd_map_param is structMapParam
  * (LSD/baseFunc.h:25-31). */
 typedef struct lsd_polar { double range, angle; } lsd_polar;
 typedef struct lsd_map_param { int oriMapCol, oriMapRow; double mapResol, mapOriX, mapOriY; } lsd_map_param;
 #define LSD_RDP_MAX_LINES 360
+/* The scan capacity of a context: the most readings per scan (the largest `stride`) that FeatureScan, the two ingest entries and
+ * lsd_localize take.  1024 by default -- the reference's lidar has 360 --; a context for a lidar with more readings per revolution
+ * (1081, 1141, 3200 ...) raises it, up to LSD_SCAN_MAX_LEN.  Strides above 1024 run on a kernel of their own whose LDS grows with
+ * the launch's stride, not with the capacity (26 bytes per reading: 104 KiB at 4096), with the same results bit for bit; strides up
+ * to 1024 run as before whatever the capacity.  The line records stay LSD_RDP_MAX_LINES per scan: a long scan with more chords
+ * reports the full count, stores the first 360, and the host entry points return LSD_ERR_CAPACITY.
+ * lsd_set_scan_capacity: LSD_ERR_INVALID below 1024, LSD_ERR_UNSUPPORTED above LSD_SCAN_MAX_LEN or where a scan of `readings`
+ * would need more LDS than the device gives a workgroup (lsd_last_error says how much).  Nothing is enqueued or allocated. */
+#define LSD_SCAN_MAX_LEN 4096
+int lsd_set_scan_capacity(lsd_ctx *ctx, int readings);
+int lsd_scan_capacity(const lsd_ctx *ctx);
 int lsd_feature_scan_batch(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, lsd_map_param map_param,
                            int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line *lines_out, int *n_lines,
                            lsd_position *pts_out, int pts_cap, int *n_pts, double *lidar_pos, int *im_size);
@@ -254,12 +266,14 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx *ctx, const lsd_polar *d_scans
  * lidarPointPolar[] (the file driver, LSD/main_on_windows.cpp:104-123; laserCallback, LSD/main_on_linux.cpp:53-66), for a BATCH of
  * raw scans resident on the device: one launch (k_ingest.hip), asynchronous on `stream`, no workspace, no synchronisation.  It writes
  * exactly what lsd_enqueue_feature_scan_batch_device reads: d_scans (n_scans x stride readings: the kept ones first, in beam order,
- * then EVERY slot from d_lens[i] to stride as +0.0 / +0.0) and d_lens (n_scans ints).  1 <= n_beams <= stride <= 1024.
+ * then EVERY slot from d_lens[i] to stride as +0.0 / +0.0) and d_lens (n_scans ints).  1 <= n_beams <= stride <= the context's scan
+ * capacity (lsd_set_scan_capacity; 1024 by default).
  *   d_raw    n_scans x n_beams (range, angle) pairs, the file driver's layout (Lidar.txt).  A reading is kept iff `range != INFINITY`
  *            as the reference evaluates it (:115): -inf and NaN are KEPT, only +inf is dropped.
  *   d_take   optional (NULL: every scan is taken), one int per scan: where it is 0 the scan has d_lens[i] = 0 and an all-zero row.
  * d_raw and d_scans must not overlap (in-place is not supported) and must be 16-byte aligned (every hipMalloc'ed or torch base is).
- * LSD_ERR_INVALID on a null or non-positive argument, n_beams > stride or a misaligned pointer; LSD_ERR_UNSUPPORTED on stride > 1024. */
+ * LSD_ERR_INVALID on a null or non-positive argument, n_beams > stride or a misaligned pointer; LSD_ERR_UNSUPPORTED on a stride above
+ * the scan capacity. */
 int lsd_enqueue_scan_ingest_device(lsd_ctx *ctx, const lsd_polar *d_raw, int n_scans, int n_beams, const int *d_take,
                                    lsd_polar *d_scans, int *d_lens, int stride, void *stream);
 /* The same from sensor_msgs/LaserScan fields: d_ranges (n_scans x n_beams floats) and d_angle_min_inc (n_scans x 2 floats:

@@ -52,6 +52,7 @@ class lsd_map_param(C.Structure):      # structMapParam, LSD/baseFunc.h:25-31
 
 
 LSD_MAX_MAPS = 64
+LSD_SCAN_MAX_LEN = 4096                                               # lsd_set_scan_capacity's upper limit (readings per scan)
 
 
 class lsd_map_ref(C.Structure):        # one device-resident map of the fleet entries (include/lsd_hip.h)
@@ -144,6 +145,8 @@ _ABI = {
     "lsd_enqueue_scan_to_map_match_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, lsd_position, lsd_position, _vp, _i, _dbl, _dbl, _vp, _vp]),
     "lsd_feature_scan_batch": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lsd_enqueue_feature_scan_batch_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "lsd_set_scan_capacity": (_i, [_vp, _i]),
+    "lsd_scan_capacity": (_i, [_vp]),
     "lsd_shard_range": (None, [_i, _i, _i, _pi, _pi]),
     "lsd_gather_layout": (_i, [_i, _i, _pi, C.POINTER(_sz)]),
     "lsd_comm_from_rccl": (_i, [_vp, C.POINTER(lsd_comm)]),
@@ -372,9 +375,20 @@ class Context:
                                                float(z_occ), float(max_esti_dist), out.ctypes.data))
         return out
 
+    def set_scan_capacity(self, readings):
+        """lsd_set_scan_capacity: the most readings per scan (the largest stride) FeatureScan, the ingest entries and localize take, 1024
+        (the default) .. LSD_SCAN_MAX_LEN = 4096.  Strides above 1024 run on the long FeatureScan kernel, with the same results."""
+        self._chk(self.L.lsd_set_scan_capacity(self.h, int(readings)))
+
+    @property
+    def scan_capacity(self):
+        """lsd_scan_capacity: the context's scan capacity in readings."""
+        return int(self.L.lsd_scan_capacity(self.h))
+
     def feature_scan_batch(self, scans, lens, map_param, region_point_limit=rdp_leastPoint, thre_line=rdp_threLine,
                            line_dist_thre_m=rdp_leastDist, pts_cap=4096):
-        """lsd_feature_scan_batch: scans float64 [n, stride, 2] = (range, angle), lens int32 [n] finite readings per scan,
+        """lsd_feature_scan_batch: scans float64 [n, stride, 2] = (range, angle), lens int32 [n] finite readings per scan (stride up to
+        the context's scan_capacity: 1024 unless set_scan_capacity raised it),
         map_param = (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY).  Returns a list of dicts like FeatureScan() below."""
         sc = np.ascontiguousarray(scans, np.float64)
         n, stride = sc.shape[0], sc.shape[1]
@@ -855,8 +869,8 @@ def load_odom(path_or_rows):
 
 
 def lidar_frames(lidar):
-    """The driver's read loop (LSD/main_on_windows.cpp:104-123) on float64 [n, 360, 2] (range, angle) frames: readings with an
-    infinite range dropped.  Returns (scans [n, 360, 2] with the finite readings first, lens int32 [n])."""
+    """The driver's read loop (LSD/main_on_windows.cpp:104-123) on float64 [n, B, 2] (range, angle) frames (the reference's B: 360):
+    readings with an infinite range dropped.  Returns (scans [n, B, 2] with the finite readings first, lens int32 [n])."""
     lid = np.asarray(lidar, np.float64)
     scans = np.zeros_like(lid)
     lens = np.zeros(len(lid), np.int32)
@@ -888,7 +902,7 @@ def replay_log(map_u8, map_param, lidar, odom, ctx=None):
 
 
 def lidar_frames_batch(lidar):
-    """lidar_frames on float64 [..., 360, 2] frames at once (the same rule and the same output, vectorised)."""
+    """lidar_frames on float64 [..., B, 2] frames at once (the same rule and the same output, vectorised)."""
     lid = np.asarray(lidar, np.float64)
     keep = lid[..., 0] != np.inf
     order = np.argsort(~keep, axis=-1, kind="stable")                        # the finite readings first, in their order
@@ -1018,19 +1032,34 @@ def _compose_rebase(pending, frame_from, frame_to):
     return None if f == frame_to else (f, frame_to)
 
 
+def _check_n_beams(n_beams):
+    """n_beams of Localizer / FleetLocalizer: readings per scan, 1 .. LSD_SCAN_MAX_LEN."""
+    n = int(n_beams)
+    if n < 1:
+        raise LsdError(LSD_ERR_INVALID, "n_beams must be at least 1")
+    if n > LSD_SCAN_MAX_LEN:
+        raise LsdError(LSD_ERR_UNSUPPORTED, "n_beams above LSD_SCAN_MAX_LEN = %d" % LSD_SCAN_MAX_LEN)
+    return n
+
+
 class _Ticks:
     """Localizer and FleetLocalizer but for their argument adapters: the robots' carries on the device, the map side -- one _MapPair per
     map (one for Localizer), the hand-over, the pending re-bases, the one map-side context --, the FeatureScan staging, and the tick
-    (step, step_device).  A subclass supplies three hooks of the map side (_rebase_key, _map_changed, _carve), the tick's two launches
+    (step, step_device).  n_beams: the readings per scan the ticks take (the staging, the ingest and FeatureScan strides; 360, the
+    reference's lidar, unless the constructor says otherwise; above 1024 the context's scan capacity is raised to it).  A subclass supplies three hooks of the map side (_rebase_key, _map_changed, _carve), the tick's two launches
     against its map or maps (_feature_scan, _loop) and the texts of step()'s two map errors."""
 
     _GAVE_UP = "the detector gave the map up (count -1): the tick saw no map lines"
     _OVER = "the map has %(n)d lines, its slot holds %(cap)d (reserve_map): the tick used the first %(cap)d"
 
-    def __init__(self, ctx, n_robots, pts_cap, n_maps=1):
+    def __init__(self, ctx, n_robots, pts_cap, n_maps=1, n_beams=360):
         import torch
         self.ctx = ctx or default_context()
         self.n_robots, self.pts_cap = int(n_robots), int(pts_cap)
+        self.n_beams = _check_n_beams(n_beams)
+        self._IN_B = self._in_b(self.n_beams)
+        if self.n_beams > max(1024, self.ctx.scan_capacity):                 # a long lidar: the context takes its scans from now on
+            self.ctx.set_scan_capacity(self.n_beams)
         self._carry = torch.zeros(self.n_robots * FA_CARRY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         self._pairs = [_MapPair() for _ in range(n_maps)]                    # per map: the slot the ticks read, and the other one
         self._caps = [512] * n_maps                                          # per map: the line records a device-made map keeps (reserve_map)
@@ -1169,10 +1198,14 @@ class _Ticks:
         self._flush_rebase()
         self._carry.copy_(torch.from_numpy(rec.view(np.uint8).copy()))
 
-    # per frame slot: the tick's inputs (one upload) the RAW scan (360 x 2 doubles, or less: the LaserScan floats), the odometry row, the
-    # take flag; the scan as FeatureScan reads it (k_ingest's output) and its length; its outputs (one read-back) the state, the report,
-    # FeatureScan's line and pixel counts
-    _IN_B, _OUT_B = 5760 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
+    # per frame slot: the tick's inputs (one upload) the RAW scan (n_beams x 2 doubles, or less: the LaserScan floats), the odometry row,
+    # the take flag; the scan as FeatureScan reads it (k_ingest's output) and its length; its outputs (one read-back) the state, the
+    # report, FeatureScan's line and pixel counts.  _IN_B is per instance (__init__); the class's is the reference lidar's, 360 readings.
+    @staticmethod
+    def _in_b(n_beams):
+        return 16 * n_beams + 24 + 4
+
+    _IN_B, _OUT_B = 16 * 360 + 24 + 4, FA_STATE_DTYPE.itemsize + FA_REPORT_DTYPE.itemsize + 8
 
     def _staging(self, n):
         import torch
@@ -1180,7 +1213,7 @@ class _Ticks:
             return
         z = lambda count, dt: torch.zeros(count, dtype=dt, device="cuda")
         self._in, self._out = z(n * self._IN_B, torch.uint8), z(n * self._OUT_B + self._tail_b, torch.uint8)     # (+ the map line counts of step())
-        self._scans, self._lens = z(n * 360 * 2, torch.float64), z(n, torch.int32)
+        self._scans, self._lens = z(n * self.n_beams * 2, torch.float64), z(n, torch.int32)
         self._lines, self._pts = z(n * 360 * 80, torch.uint8), z(n * self.pts_cap * 3, torch.float64)
         self._lp, self._sz = z(n * 2, torch.float64), z(n * 2, torch.int32)
         self._cap = n
@@ -1213,9 +1246,9 @@ class _Ticks:
         cx, ts = self.ctx, torch.cuda.current_stream()
         stream = ts.cuda_stream
         if d_raw is not None:
-            cx.enqueue_scan_ingest_device(d_raw, n, 360, d_take, d_sc, d_ln, 360, stream)
+            cx.enqueue_scan_ingest_device(d_raw, n, self.n_beams, d_take, d_sc, d_ln, self.n_beams, stream)
         else:
-            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, 360, stream)
+            cx.enqueue_laserscan_ingest_device(d_ranges, d_ami, n, n_beams, d_take, d_sc, d_ln, self.n_beams, stream)
         self._feature_scan(n, k, d_sc, d_ln, d_nl, d_np, stream)
         for pair in self._pairs:
             pair.read_by(ts)                                                 # the first tick of this stream on a new map: behind its update
@@ -1224,10 +1257,12 @@ class _Ticks:
         return b_st, b_rp
 
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
-        """lidar float64 [S, k, 360, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames does,
-        on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots.  Instead of
-        lidar: ranges float32 [S, k, B <= 360] and angle_min_inc float32 [S, k, 2], the fields of sensor_msgs/LaserScan messages (see
-        step_device).  n_frames: frames per robot this tick (default k each; a robot with 0 is left untouched).  Returns (states
+        """lidar float64 [S, k, n_beams, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames
+        does, on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots; n_beams
+        is the constructor's (default 360, the reference's lidar).  Instead of lidar: ranges float32 [S, k, B <= n_beams] and
+        angle_min_inc float32 [S, k, 2], the fields of sensor_msgs/LaserScan messages (see step_device).  A robot whose lidar has fewer
+        readings than n_beams pads each scan at the tail with +inf ranges, which the ingest drops: its scan is then exactly the shorter
+        one (in the LaserScan layout the kept beams' angles, angle_min + i * angle_increment, do not depend on B).  n_frames: frames per robot this tick (default k each; a robot with 0 is left untouched).  Returns (states
         FA_STATE_DTYPE [S, k], reports FA_REPORT_DTYPE [S, k]); slots past a robot's n_frames are zero, and so are those of a robot that
         sits out (FleetLocalizer).  Raises LsdError(LSD_ERR_CAPACITY) with (states, reports) in `partial` if a scan marks more than
         pts_cap pixels or has more than 360 lines (the records are then computed from the stored part), as lsd_localize does.  One upload
@@ -1242,13 +1277,13 @@ class _Ticks:
         if ranges is None:
             src = np.asarray(lidar, np.float64)
             S, k = src.shape[0], src.shape[1]
-            if S != self.n_robots or src.shape[2:] != (360, 2) or k < 1:
-                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
-            n_beams = 360
+            if S != self.n_robots or src.shape[2:] != (self.n_beams, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, %d, 2]" % self.n_beams)
+            n_beams = self.n_beams
         else:
             src = np.asarray(ranges, np.float32)
-            if src.ndim != 3 or src.shape[0] != self.n_robots or src.shape[1] < 1 or not 1 <= src.shape[2] <= 360:
-                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            if src.ndim != 3 or src.shape[0] != self.n_robots or src.shape[1] < 1 or not 1 <= src.shape[2] <= self.n_beams:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= %d]" % self.n_beams)
             S, k, n_beams = src.shape
             ami = np.asarray(angle_min_inc, np.float32)
             if ami.shape != (S, k, 2):
@@ -1262,7 +1297,7 @@ class _Ticks:
         if ranges is None:                                                   # the frames (16-byte pairs) first
             host_in = np.concatenate([b(src), b(od), b(take)])
             d_src = self._in.data_ptr()
-            d_od, d_ami = d_src + n * 5760, None
+            d_od, d_ami = d_src + n * 16 * self.n_beams, None
         else:                                                                # the doubles first, then the floats
             host_in = np.concatenate([b(od), b(src), b(ami), b(take)])
             d_od = self._in.data_ptr()
@@ -1294,8 +1329,8 @@ class _Ticks:
 
     def step_device(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """step() for a caller whose scans are on the device, without an upload, a read-back or a synchronisation: everything is enqueued
-        on the current torch stream.  Either lidar, a CUDA float64 tensor [S, k, 360, 2] of raw (range, angle) frames, or ranges, a CUDA
-        float32 tensor [S, k, B <= 360] with angle_min_inc CUDA float32 [S, k, 2] (sensor_msgs/LaserScan: ranges[], angle_min,
+        on the current torch stream.  Either lidar, a CUDA float64 tensor [S, k, n_beams, 2] of raw (range, angle) frames, or ranges, a CUDA
+        float32 tensor [S, k, B <= n_beams] (n_beams: the constructor's, default 360; a shorter lidar pads its tail with +inf, see step) with angle_min_inc CUDA float32 [S, k, 2] (sensor_msgs/LaserScan: ranges[], angle_min,
         angle_increment; the angle of beam i is angle_min + i * angle_increment in single precision, as laserCallback computes it).
         Readings whose range is +inf are dropped on the device (-inf and NaN are kept, as the reference's `!= INFINITY` keeps them).
         odom: CUDA float64 [S, k, 3]; n_frames: as in step(), a HOST int array (when given, its take flags are one small asynchronous
@@ -1318,13 +1353,13 @@ class _Ticks:
         S = self.n_robots
         k = src.shape[1] if src.dim() >= 2 else 0
         if ranges is None:
-            if tuple(src.shape) != (S, k, 360, 2) or k < 1:
-                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, 360, 2]")
-            n_beams = 360
+            if tuple(src.shape) != (S, k, self.n_beams, 2) or k < 1:
+                raise LsdError(LSD_ERR_INVALID, "lidar must be [n_robots, k >= 1, %d, 2]" % self.n_beams)
+            n_beams = self.n_beams
         else:
             n_beams = src.shape[2] if src.dim() == 3 else 0
-            if tuple(src.shape) != (S, k, n_beams) or k < 1 or not 1 <= n_beams <= 360:
-                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= 360]")
+            if tuple(src.shape) != (S, k, n_beams) or k < 1 or not 1 <= n_beams <= self.n_beams:
+                raise LsdError(LSD_ERR_INVALID, "ranges must be [n_robots, k >= 1, 1 <= B <= %d]" % self.n_beams)
             if tuple(angle_min_inc.shape) != (S, k, 2):
                 raise LsdError(LSD_ERR_INVALID, "angle_min_inc must be [n_robots, k, 2]")
         if tuple(odom.shape) != (S, k, 3):
@@ -1354,18 +1389,23 @@ class Localizer(_Ticks):
     from a grid on the device: the Localizer holds two map slots, a new map is made in the one the ticks are not reading -- on a side
     stream if the caller wants -- and handed over through events, so ticks keep running on the old map meanwhile.  Like the context it
     uses, a Localizer serves one thread at a time, and its ticks one stream at a time.  The code is _Ticks': the methods here pass map
-    index 0 to it, and the ticks go through the single-map entries."""
+    index 0 to it, and the ticks go through the single-map entries.
+    n_beams (default 360, the reference's lidar; 1 .. LSD_SCAN_MAX_LEN = 4096): the readings per scan of the robots' lidar -- 1081 for a
+    UTM-30LX or an LMS1xx, 1141 for an LMS5xx, up to 3200 for an RPLidar S.  Above 1024 the context's scan capacity is raised to it
+    (Context.set_scan_capacity) and FeatureScan runs on its long kernel; the line records stay at 360 per scan."""
 
-    def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
-        super().__init__(ctx, n_robots, pts_cap)
+    def __init__(self, map_cache, map_lines, map_param, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192, n_beams=360):
+        super().__init__(ctx, n_robots, pts_cap, n_beams=n_beams)
         self._set_map(0, map_cache, map_lines, map_param, False)
         self.reset(range(self.n_robots), odom0)
 
     @classmethod
-    def from_occupancy_grid(cls, data, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None):
+    def from_occupancy_grid(cls, data, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY, n_robots=1, odom0=(0.0, 0.0, 0.0), ctx=None,
+                            n_beams=360):
         """A Localizer on the map mapCallback makes of an OccupancyGrid (map_param from the map metadata, mapParamCallback :92-99)."""
+        _check_n_beams(n_beams)                                              # (before the map is made)
         _, mapCache, LSD = mapCallback(data, oriMapCol, oriMapRow, mapResol, ctx=ctx)
-        return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx)
+        return cls(mapCache, LSD.linesInfo, (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY), n_robots, odom0, ctx, n_beams=n_beams)
 
     @property
     def map_param(self):
@@ -1432,7 +1472,7 @@ class Localizer(_Ticks):
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current
-        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_scans, d_lens, n, 360, _map_param(m.map_param), rdp_leastPoint, rdp_threLine,
+        cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_scans, d_lens, n, self.n_beams, _map_param(m.map_param), rdp_leastPoint, rdp_threLine,
                                                            rdp_leastDist, self._lines.data_ptr(), d_n_lines, self._pts.data_ptr(), self.pts_cap,
                                                            d_n_pts, self._lp.data_ptr(), self._sz.data_ptr(), stream))
 
@@ -1468,12 +1508,15 @@ class FleetLocalizer(_Ticks):
     stream if the caller wants -- and hands it over through events, so the ticks keep running on the old map meanwhile;
     reserve_map(i, ...) sizes what that needs.  One map-side context serves all maps: updates of different maps on different streams
     serialise on the device (lsd_enqueue_map_update_device orders itself behind the context's previous run with an event), never on
-    the host.  Like the context it uses, a FleetLocalizer serves one thread at a time, and its ticks one stream at a time."""
+    the host.  Like the context it uses, a FleetLocalizer serves one thread at a time, and its ticks one stream at a time.
+    n_beams: as Localizer's, one value for the fleet.  A fleet with mixed lidars uses the largest; a robot with fewer readings pads each
+    scan at the tail with +inf ranges, which the ingest drops, so its scan is exactly the shorter one (in the LaserScan layout the kept
+    beams' angles, angle_min + i * angle_increment, do not depend on the padded length)."""
 
     _GAVE_UP = "map %(i)d: the detector gave the map up (count -1): the tick saw no map lines"
     _OVER = "map %(i)d has %(n)d lines, its slots hold %(cap)d (reserve_map): the tick used the first %(cap)d"
 
-    def __init__(self, maps, map_of, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192):
+    def __init__(self, maps, map_of, odom0=(0.0, 0.0, 0.0), ctx=None, pts_cap=8192, n_beams=360):
         import torch
         maps = list(maps)
         if not maps:
@@ -1483,7 +1526,7 @@ class FleetLocalizer(_Ticks):
         ids = fleet_map_ids(map_of, len(maps))
         if not len(ids):
             raise LsdError(LSD_ERR_INVALID, "at least one robot")
-        super().__init__(ctx, len(ids), pts_cap, len(maps))
+        super().__init__(ctx, len(ids), pts_cap, len(maps), n_beams=n_beams)
         self._table = np.zeros(len(maps), MAP_REF_DTYPE)                     # what the *_maps entries take: record i names map i's current slot
         self._mask = None
         for i, m in enumerate(maps):
@@ -1597,7 +1640,7 @@ class FleetLocalizer(_Ticks):
                                                 torch.cuda.current_stream().cuda_stream)
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
-        self.ctx.enqueue_feature_scan_maps_device(d_scans, d_lens, n, 360, self._table, self._map_of.data_ptr(), k, self._lines.data_ptr(), d_n_lines,
+        self.ctx.enqueue_feature_scan_maps_device(d_scans, d_lens, n, self.n_beams, self._table, self._map_of.data_ptr(), k, self._lines.data_ptr(), d_n_lines,
                                                   self._pts.data_ptr(), self.pts_cap, d_n_pts, self._lp.data_ptr(), self._sz.data_ptr(), stream=stream)
 
     def _loop(self, S, k, nf, d_n_lines, d_n_pts, d_od, d_states, d_reports, stream):

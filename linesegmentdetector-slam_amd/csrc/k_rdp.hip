@@ -263,12 +263,22 @@ __global__ __launch_bounds__(64) void k_rdp_maps(const double* __restrict__ scan
 void launch_rdp(const double* scans, const int* lens, int n, int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX,
                 double mapOriY, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                 double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
+    if (stride > kRdpMaxLen) {                         // a long scan (lsd_set_scan_capacity): k_rdp_long.hip
+        launch_rdp_long(scans, lens, n, stride, mapResol, mapOriX, mapOriY, region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines,
+                        pts_out, pts_cap, n_pts, lidar_pos, im_size, s);
+        return;
+    }
     hipLaunchKernelGGL(k_rdp, dim3(n), dim3(64), 0, s, scans, lens, stride, oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY,
                        region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
 }
 void launch_rdp_maps(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
                      int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                      double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
+    if (stride > kRdpMaxLen) {
+        launch_rdp_maps_long(scans, lens, n, stride, maps, n_maps, map_of, scans_per_seq, region_point_limit, thre_line, line_dist_thre_m,
+                             lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size, s);
+        return;
+    }
     hipLaunchKernelGGL(k_rdp_maps, dim3(n), dim3(64), 0, s, scans, lens, stride, maps, n_maps, map_of, scans_per_seq, region_point_limit,
                        thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
 }

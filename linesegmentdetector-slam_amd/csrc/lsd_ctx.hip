@@ -19,6 +19,7 @@
 #include "lsd_devbuf.h"
 #include "lsd_internal.h"
 #include "k1_lds.h"
+#include "k_rdp_lds.h"
 
 using namespace lsdhip;
 
@@ -113,6 +114,8 @@ struct lsd_ctx {
     DevBuf<int> pcount;                 // ... and the launch's image counter
     bool trace = false;
     bool fused_front = true;            // lsd_set_fused_front: K1 + K2 as one kernel where it applies (use_front)
+    int scan_cap = kRdpShortMaxLen;     // lsd_set_scan_capacity: readings per scan (the stride) FeatureScan and the ingest entries take
+    bool rdp_long_ready = false;        // the long FeatureScan kernels' dynamic-LDS limit covers scan_cap (prepare_rdp_long)
     int host_max_lines = 8192;
     // last run
     Geom geom{};
@@ -554,6 +557,25 @@ int lsd_set_fused_front(lsd_ctx* c, int on) {
     c->fused_front = on != 0;
     return LSD_OK;
 }
+
+// The scan capacity: the largest stride the FeatureScan and ingest entries take.  1024 (k_rdp's static arrays) unless the caller asks
+// for more; above it the launches go to k_rdp_long, whose LDS grows with the stride (k_rdp_lds.h): a capacity whose scans would not fit
+// this device's LDS is refused here, before anything is enqueued -- make_geom's rule for K1's window.
+int lsd_set_scan_capacity(lsd_ctx* c, int readings) {
+    if (!c || readings < kRdpShortMaxLen) return LSD_ERR_INVALID;
+    if (readings > LSD_SCAN_MAX_LEN) return LSD_ERR_UNSUPPORTED;
+    if (readings > kRdpShortMaxLen && rdp_long_lds(readings) > c->max_lds) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "scan capacity %d: FeatureScan's work arrays need %zu bytes of LDS, the device gives a workgroup %zu", readings,
+                 rdp_long_lds(readings), c->max_lds);
+        c->err = buf;
+        return LSD_ERR_UNSUPPORTED;
+    }
+    if (readings != c->scan_cap) { c->scan_cap = readings; c->rdp_long_ready = false; }
+    return LSD_OK;
+}
+
+int lsd_scan_capacity(const lsd_ctx* c) { return c ? c->scan_cap : LSD_ERR_INVALID; }
 
 int lsd_reserve(lsd_ctx* c, int n, int cols, int rows) {
     if (!c || n <= 0) return LSD_ERR_INVALID;
@@ -1085,6 +1107,16 @@ int lsd_scan_to_map_match(lsd_ctx* c, const double* map_cache, int cols, int row
     return LSD_OK;
 }
 
+// Before a FeatureScan launch: a stride above 1024 goes to the long kernels (k_rdp_long.hip), whose dynamic LDS at this context's capacity
+// may be above the 64 KiB a kernel gets without asking.  Their limit is raised once per context (and again after the capacity changes),
+// to the capacity's need: every stride the entries let through fits.
+static hipError_t rdp_long_prepare(lsd_ctx* c, int stride) {
+    if (stride <= rdp_max_len() || c->rdp_long_ready) return hipSuccess;
+    const hipError_t e = prepare_rdp_long(rdp_long_lds(c->scan_cap));
+    if (e == hipSuccess) c->rdp_long_ready = true;
+    return e;
+}
+
 // the two FeatureScan enqueue entries: the argument check they share
 static bool feature_scan_args_bad(const lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const lsd_line* d_lines_out,
                                   const int* d_n_lines, const lsd_position* d_pts_out, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
@@ -1100,9 +1132,10 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, 
     if (feature_scan_args_bad(c, d_scans, d_lens, n_scans, stride, d_lines_out, d_n_lines, d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size) ||
         !(mp.mapResol > 0))
         return LSD_ERR_INVALID;
-    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
+    HIPCHK(c, rdp_long_prepare(c, stride));
     launch_rdp(reinterpret_cast<const double*>(d_scans), d_lens, n_scans, stride, mp.oriMapCol, mp.oriMapRow, mp.mapResol, mp.mapOriX, mp.mapOriY,
                region_point_limit, thre_line, line_dist_thre_m, d_lines_out, d_n_lines, reinterpret_cast<double*>(d_pts_out), pts_cap, d_n_pts,
                d_lidar_pos, d_im_size, s);
@@ -1111,6 +1144,7 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, 
     return LSD_OK;
 }
 
+static_assert(LSD_SCAN_MAX_LEN == kRdpLongMaxLen, "the header's limit is the long kernel's");
 static_assert(sizeof(lsd_map_ref) == 64 && offsetof(lsd_map_ref, d_map_cache) == 0 && offsetof(lsd_map_ref, d_map_lines) == 8 &&
               offsetof(lsd_map_ref, d_n_map) == 16 && offsetof(lsd_map_ref, cols) == 24 && offsetof(lsd_map_ref, rows) == 28 &&
               offsetof(lsd_map_ref, n_map) == 32 && offsetof(lsd_map_ref, mapResol) == 40 && offsetof(lsd_map_ref, mapOriX) == 48 &&
@@ -1155,9 +1189,10 @@ int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, c
         return LSD_ERR_INVALID;
     const int r = map_table_check(maps, n_maps, d_map_of, nullptr);
     if (r != LSD_OK) return r;
-    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, rdp_long_prepare(c, stride));
     const lsd_map_ref* d_tab;
     const int u = map_table_upload(c, 0, maps, n_maps, s, &d_tab);
     if (u != LSD_OK) return u;
@@ -1173,7 +1208,7 @@ int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, c
 static int enqueue_ingest(lsd_ctx* c, const lsd_polar* d_raw, const float* d_ranges, const float* d_min_inc, int n_scans, int n_beams,
                           const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
     if (!c || n_scans <= 0 || n_beams <= 0 || stride <= 0 || !d_scans || !d_lens || n_beams > stride) return LSD_ERR_INVALID;
-    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_scans)) & 15) {        // the kernel moves a pair in one 16-byte access
         c->err = "scan ingest: d_raw and d_scans must be 16-byte aligned";
         return LSD_ERR_INVALID;
@@ -1535,7 +1570,7 @@ int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const 
         stride <= 0 || !odom || !states || !reports || !(mp.mapResol > 0))
         return LSD_ERR_INVALID;
     for (int i = 0; i < n_frames; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    if (stride > rdp_max_len()) return LSD_ERR_UNSUPPORTED;
+    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
     HIPCHK(c, hipSetDevice(c->device));
     const int pts_cap = 8192;
     const size_t nf = (size_t)n_frames, n_mc = (size_t)cols * rows;

@@ -155,6 +155,15 @@ void launch_rdp_maps(const double* scans, const int* lens, int n, int stride, co
                      int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
                      double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
 int rdp_max_len();
+// k_rdp_long.hip: the same two for strides above rdp_max_len(), which launch_rdp / launch_rdp_maps send there; dynamic LDS of
+// rdp_long_lds(stride) bytes (k_rdp_lds.h), for which prepare_rdp_long raises the kernels' limit where it is above 64 KiB
+void launch_rdp_long(const double* scans, const int* lens, int n, int stride, double mapResol, double mapOriX, double mapOriY,
+                     int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines, double* pts_out,
+                     int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
+void launch_rdp_maps_long(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
+                          int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out,
+                          int* n_lines, double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
+hipError_t prepare_rdp_long(size_t bytes);
 // the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
 void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
                    int* lens, int stride, hipStream_t s);
