@@ -275,7 +275,10 @@ void launch_mapcache_spread(const uint8_t* maps, double* out, unsigned long long
     const dim3 grid(G, n), blk(MNT);
     hipLaunchKernelGGL(k_mc_init_count, grid, blk, 0, s, a);
     hipLaunchKernelGGL(k_mc_init_emit, grid, blk, 0, s, a);
-    const int levels = (int)(1.5 * (cell_radius > 0 ? cell_radius : 0)) + 3;          // covers the bulk; the rest below
+    // covers the bulk; the rest below.  The plan grows with 1 / res without bound (three launches per level), so it stops at W + H:
+    // k_mc_finish completes whatever is left, and no result depends on where the plan ends
+    const double plan = 1.5 * (cell_radius > 0 ? cell_radius : 0) + 3;
+    const int levels = plan < (double)W + H ? (int)plan : W + H;
     for (int level = 1; level <= levels; level++) {
         hipLaunchKernelGGL(k_mc_level<0>, grid, blk, 0, s, a, (unsigned long long)level);
         hipLaunchKernelGGL(k_mc_level<1>, grid, blk, 0, s, a, (unsigned long long)level);

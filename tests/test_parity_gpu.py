@@ -1557,10 +1557,12 @@ def test_stamp_ids_running_out_changes_nothing(maps, lsdmod, ctx, oracle):
 
 
 def test_map_cache_many_small_maps_one_workgroup_each(lsdmod, ctx, oracle):
-    """More than 64 maps take the one-workgroup-per-map kernel (fewer take the kernel-per-level one): same answers."""
+    """The entry spreads each map over G = min(64, 2 * num_cus // n) workgroups (a kernel per level phase) while G >= 4, and runs one
+    workgroup per map beyond that: more than num_cus // 2 maps (129 on 256 CUs) take the one-workgroup kernel, five maps the spread
+    one: same answers."""
     import torch
     rng = np.random.default_rng(5)
-    n, rows, cols = 70, 96, 160
+    n, rows, cols = torch.cuda.get_device_properties(0).multi_processor_count // 2 + 1, 96, 160
     batch = np.zeros((n, rows, cols), np.uint8)
     batch[rng.random(batch.shape) < 0.01] = 1
     batch[rng.random(batch.shape) < 0.2] = 255
@@ -1569,7 +1571,7 @@ def test_map_cache_many_small_maps_one_workgroup_each(lsdmod, ctx, oracle):
     ctx.enqueue_map_cache_device(d.data_ptr(), n, cols, rows, 0.05, 1.0, out.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     got = out.cpu().numpy()
-    for i in (0, 1, 35, 69):
+    for i in sorted({0, 1, 35, 69, n - 1} & set(range(n))):
         assert np.array_equal(got[i], oracle.map_cache(batch[i].copy(), 0.05))
     few = torch.zeros((5, rows, cols), dtype=torch.float64, device="cuda")
     ctx.enqueue_map_cache_device(d.data_ptr(), 5, cols, rows, 0.05, 1.0, few.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
