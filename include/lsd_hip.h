@@ -95,7 +95,10 @@ int lsd_set_host_max_lines(lsd_ctx *ctx, int max_lines);
  *   d_line_ims n x rows x cols uint8 or NULL
  *   d_lines    n x max_lines lsd_line (image i's lines start at d_lines + i*max_lines)
  *   d_counts   n int32 line counts.  A count > max_lines means that image overflowed (its first max_lines lines are valid; the
- *              host entry points report LSD_ERR_CAPACITY).  A count of -1 means the region stage's watchdog gave the image up
+ *              host entry points report LSD_ERR_CAPACITY).  Nothing is written behind the first min(count, max_lines) records of an
+ *              image, and the lineIm of an overflowing image holds the raster of its first max_lines lines only: the lines that
+ *              were dropped leave no pixel (the reference has no capacity and marks them all).
+ *              A count of -1 means the region stage's watchdog gave the image up
  *              (no wavefront of its workgroup found anything to do for seconds: a defect of the commit protocol, never seen
  *              on a released build): the image has no valid lines, its lineIm is blank, the other images are unaffected;
  *              the host entry points report LSD_ERR_INTERNAL and treat the image as having no lines.
@@ -568,6 +571,12 @@ int lsd_debug_fetch(lsd_ctx *ctx, int image, int what, void *out, size_t bytes);
  * doubles: fn 0 = sin/cos(a) -> out0,out1; fn 1 = atan2(a, b) -> out0; fn 2 = atan(a) -> out0;
  * fn 3 = the region stage's fp32 ESTIMATE of sin/cos of the packed angle of a (its error bound is a test). */
 int lsd_debug_eval_math(lsd_ctx *ctx, int fn, const double *a, const double *b, double *out0, double *out1, size_t n);
+
+/* Test hook: K5 alone (csrc/k_lines.hip) on n caller-given rectangles recs[n][4] = x1 y1 x2 y2, already in the map's cells, as one
+ * image of cols x rows: lines_out[n] receives the records (bytes K5 does not write stay 0xFF) and line_im, rows x cols or NULL,
+ * the raster.  End points no map produces -- a sample exactly half-way between two cells, x1 == x2 and y1 == y2 -- reach K5 only
+ * through here.  Keep |coordinates| small: the walk visits every integer between the end points. */
+int lsd_debug_lines(lsd_ctx *ctx, const double *recs, int n, int cols, int rows, lsd_line *lines_out, uint8_t *line_im);
 
 /* Profiling hook: streams `bytes` once with 8-B-per-lane stores (k_calib_write8) and once with 8-B-per-lane loads
  * (k_calib_read8) so that rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE can be calibrated for the front end's access shape. */

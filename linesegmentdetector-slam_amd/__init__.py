@@ -27,6 +27,7 @@ STAGE_ALL, STAGE_GAUSS, STAGE_GRAD, STAGE_SORT, STAGE_REGION = range(5)
 # LSD defaults, LSD/baseFunc.h:64-68
 lsd_sca, lsd_sig, lsd_angThre, lsd_denThre, pseBin = 0.3, 0.6, 22.5, 0.7, 1024
 z_occ_max_dis = 1.0   # LSD/baseFunc.h:60
+HOST_MAX_LINES_DEFAULT = 8192   # a fresh context's line capacity per image of run / run_batch (lsd_set_host_max_lines in lsd_hip.h)
 rdp_leastPoint, rdp_threLine, rdp_leastDist = 3, 0.08, 0.5   # RDP defaults, LSD/baseFunc.h:70-72
 
 
@@ -174,6 +175,7 @@ _ABI = {
     "lsd_enqueue_laserscan_ingest_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
+    "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = list(_ABI)
 del _vp, _i, _sz, _dbl, _pi, _ppar, _localize_args, _live_map_args, _maps_args
@@ -290,24 +292,26 @@ class Context:
         except Exception:
             pass
 
-    def _chk(self, st, allow=()):
+    def _chk(self, st, allow=(), partial=None):
         if st != LSD_OK and st not in allow:
-            raise LsdError(st, self.L.lsd_strerror(st).decode() + " / " + self.L.lsd_last_error(self.h).decode())
+            raise LsdError(st, self.L.lsd_strerror(st).decode() + " / " + self.L.lsd_last_error(self.h).decode(),
+                           partial=partial if st == LSD_ERR_CAPACITY else None)
         return st
 
     def _take_lines(self, lines_p, n):
         """The n records of the buffer the C side has handed over (run / run_batch) as a LINE_DTYPE array; the buffer is freed, before
-        any raise."""
+        any raise.  The bytes are the device's, the tail padding of structLinesInfo (_pad, which K5 writes as 0) included."""
         lines = np.zeros(n if lines_p else 0, LINE_DTYPE)
         if len(lines):
             C.memmove(lines.ctypes.data, lines_p, 80 * len(lines))
-            lines["_pad"] = 0
         self.L.lsd_free(lines_p)
         return lines
 
     # -- host-buffer entry points -----------------------------------------------------------------
     def run(self, map_u8, params=None, want_lineim=True):
-        """lsd_run on a C-contiguous uint8 image; the image is rewritten in place like the reference does."""
+        """lsd_run on a C-contiguous uint8 image; the image is rewritten in place like the reference does.  An image with more lines
+        than the host capacity (set_host_max_lines) raises LsdError(LSD_ERR_CAPACITY) whose `partial` is what the call would have
+        returned: the first records and their raster."""
         assert map_u8.dtype == np.uint8 and map_u8.ndim == 2
         rows, cols = map_u8.shape
         p = params or make_params()
@@ -316,11 +320,13 @@ class Context:
         st = self.L.lsd_run(self.h, map_u8.ctypes.data, cols, rows, map_u8.strides[0], C.byref(p),
                             line_im.ctypes.data if want_lineim else None, cols, C.byref(lines_p), C.byref(n))
         lines = self._take_lines(lines_p, n.value)
-        self._chk(st)
+        self._chk(st, partial=(lines, line_im))
         return lines, line_im
 
     def run_batch(self, maps_u8, params=None, want_lineim=True):
-        """lsd_run_batch on an [n, rows, cols] uint8 array (rewritten in place)."""
+        """lsd_run_batch on an [n, rows, cols] uint8 array (rewritten in place) -> (lines, offsets int32 [n + 1], line_ims).  On
+        LSD_ERR_CAPACITY (an image with more lines than the host capacity: its first records are kept) the raised LsdError's
+        `partial` holds that triple."""
         assert maps_u8.dtype == np.uint8 and maps_u8.ndim == 3 and maps_u8.flags.c_contiguous
         n, rows, cols = maps_u8.shape
         p = params or make_params()
@@ -331,7 +337,7 @@ class Context:
                                   line_ims.ctypes.data if want_lineim else None, C.byref(lines_p), offs)
         offsets = np.frombuffer(offs, np.int32).copy()
         lines = self._take_lines(lines_p, int(offsets[-1]))
-        self._chk(st)
+        self._chk(st, partial=(lines, offsets, line_ims))
         return lines, offsets, line_ims
 
     # -- device-resident batch --------------------------------------------------------------------
@@ -634,7 +640,7 @@ class Context:
         self._chk(self.L.lsd_set_fused_front(self.h, 1 if on else 0))
 
     def set_host_max_lines(self, max_lines):
-        """Line capacity per image of run / run_batch (default 8192); more lines -> LsdError(LSD_ERR_CAPACITY)."""
+        """Line capacity per image of run / run_batch (default HOST_MAX_LINES_DEFAULT); more lines -> LsdError(LSD_ERR_CAPACITY)."""
         self._chk(self.L.lsd_set_host_max_lines(self.h, max_lines))
 
     def set_cost_history(self, on):
@@ -715,6 +721,15 @@ class Context:
         self._chk(self.L.lsd_debug_eval_math(self.h, fn, a.ctypes.data, None if b is None else b.ctypes.data,
                                              o0.ctypes.data, o1.ctypes.data, a.size))
         return o0, o1
+
+    def debug_lines(self, recs, rows, cols, want_lineim=True):
+        """lsd_debug_lines: K5 alone on rectangles float64 [n, 4] = (x1, y1, x2, y2) in the cells of a rows x cols map -> (records
+        LINE_DTYPE [n], lineIm or None) (test hook)."""
+        r = np.ascontiguousarray(recs, np.float64).reshape(-1, 4)
+        lines = np.zeros(len(r), LINE_DTYPE)
+        im = np.zeros((rows, cols), np.uint8) if want_lineim else None
+        self._chk(self.L.lsd_debug_lines(self.h, r.ctypes.data, len(r), cols, rows, lines.ctypes.data, im.ctypes.data if want_lineim else None))
+        return lines, im
 
     def fetch_recs(self, image, count):
         a = np.zeros(max(count * 12, 1), np.float64)

@@ -146,4 +146,8 @@ void launch_lines(const Geom& g, const Buffers& b, int n, hipStream_t s) {
                        g.W, g.H);
 }
 
+void launch_lines_of(const double* recs_scaled, const int32_t* count, lsd_line* lines, uint8_t* line_im, int n, int W, int H, hipStream_t s) {
+    hipLaunchKernelGGL(k_lines, dim3(1), dim3(256), 0, s, recs_scaled, count, lines, line_im, n, W, H);
+}
+
 }  // namespace lsdhip

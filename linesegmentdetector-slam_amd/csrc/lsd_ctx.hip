@@ -1633,4 +1633,22 @@ int lsd_debug_eval_math(lsd_ctx* c, int fn, const double* a, const double* b, do
     return LSD_OK;
 }
 
+int lsd_debug_lines(lsd_ctx* c, const double* recs, int n, int cols, int rows, lsd_line* lines_out, uint8_t* line_im) {
+    if (!c || !recs || !lines_out || n <= 0 || cols <= 0 || rows <= 0) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> dr; DevBuf<int32_t> dn; DevBuf<lsd_line> dl; DevBuf<uint8_t> di;
+    const size_t px = (size_t)cols * rows;
+    HIPCHK(c, dr.resize((size_t)n * 4)); HIPCHK(c, dn.resize(1)); HIPCHK(c, dl.resize(n));
+    if (line_im) HIPCHK(c, di.resize(px));
+    HIPCHK(c, hipMemcpy(dr.get(), recs, (size_t)n * 4 * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dn.get(), &n, 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(dl.get(), 0xFF, (size_t)n * sizeof(lsd_line), c->stream));   // what K5 leaves unwritten shows
+    if (line_im) launch_clear(di.get(), px, c->num_cus, c->stream);
+    launch_lines_of(dr.get(), dn.get(), dl.get(), line_im ? di.get() : nullptr, n, cols, rows, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(lines_out, dl.get(), (size_t)n * sizeof(lsd_line), hipMemcpyDeviceToHost));
+    if (line_im) HIPCHK(c, hipMemcpy(line_im, di.get(), px, hipMemcpyDeviceToHost));
+    return LSD_OK;
+}
+
 }  // extern "C"

@@ -10,8 +10,13 @@ UsedMap indexing"):
   * logNFA of every seed that reaches RectangleImprover: BIT-EXACT against the restatement built on correctly rounded exp / log10 /
     pow (the device evaluates them correctly rounded: crmath.h), <= 4 ulp of max(|logNFA|, logNT) against the glibc build (glibc's
     log10 is off by one ulp in one call out of seven);
-  * line endpoints x1,y1,x2,y2 and len: 1e-6 px absolute; dx,dy: 1e-9; k,b: 1e-6 relative
-    (transcendentals on the rectangle path differ by ulps between OCML and glibc).
+  * line records against the CORRECTLY ROUNDED build of the oracle (oracle.lib_cr(): sin / cos / atan2 / exp / log10 / pow correctly
+    rounded, as the device evaluates them): BIT-EXACT, every byte of every record -- k, b, dx, dy, x1, y1, x2, y2, len, orient and the
+    tail padding (assert_lines_identical; the fixtures, two bench images, the libm-tie images here, the generated cases of
+    tests/test_line_cases_gpu.py);
+  * line records against the GLIBC build of the oracle (assert_lines_close): x1,y1,x2,y2 and len within 1e-6 px absolute, dx,dy
+    within 1e-9, k,b within 1e-6 relative, orient equal (glibc's sin / cos / atan2 are within an ulp of correct rounding, and the
+    rectangle's end points are built from them).
 """
 import importlib
 import json
@@ -60,6 +65,14 @@ def assert_lines_close(got, ref):
         assert np.array_equal(a[~fin], b[~fin], equal_nan=True)
         assert np.all(np.abs(a[fin] - b[fin]) <= REL_TOL * np.maximum(1.0, np.abs(b[fin]))), f
     assert np.array_equal(got["orient"], ref["orient"])
+
+
+def assert_lines_identical(got, ref):
+    """Every byte of every record, the padding word included (ref: the correctly rounded build of the oracle, _pad == 0)."""
+    assert len(got) == len(ref)
+    for f in ref.dtype.names:
+        assert np.ascontiguousarray(got[f]).tobytes() == np.ascontiguousarray(ref[f]).tobytes(), f
+    assert got.tobytes() == ref.tobytes()
 
 
 def full_check(lsdmod, ctx, oracle, img, params=None, kw=None):
@@ -1073,8 +1086,10 @@ def test_nfa_values_equal_the_correctly_rounded_restatement(maps, lsdmod, ctx, o
     ctx.set_trace(True)
     try:
         for im in imgs:
-            d = oracle.lsd(im.copy(), debug=True, _lib=oracle.lib_cr())["dbg"]
-            ctx.run(im.copy(), want_lineim=False)
+            ref = oracle.lsd(im.copy(), debug=True, _lib=oracle.lib_cr())
+            d = ref["dbg"]
+            lines, _ = ctx.run(im.copy(), want_lineim=False)
+            assert_lines_identical(lines, ref["lines"])               # ... and so is every line record
             seeds = ctx.fetch(0, lsdmod.DBG_SEEDS, (d["w"], d["h"]))
             st = ctx.fetch(0, lsdmod.DBG_STATS, (d["w"], d["h"]))
             assert len(seeds) == len(d["seeds"])
@@ -1600,6 +1615,7 @@ def test_libm_tie_images_equal_the_correctly_rounded_restatement(name, lsdmod, c
     used = (ctx.fetch(0, lsdmod.DBG_STATE, (d["w"], d["h"])) & 3).astype(np.uint8)
     assert np.array_equal(used, d["used"]) and np.array_equal(im, ref["lineIm"])
     assert_lines_close(lines, ref["lines"])
+    assert_lines_identical(lines, ref["lines"])
     assert len(seeds) == len(d["seeds"])
     for f in ("order_idx", "num", "outcome", "final_num"):
         assert np.array_equal(seeds[f], d["seeds"][f]), f
