@@ -496,6 +496,40 @@ int lsd_enqueue_map_update_device(lsd_ctx *ctx, const int8_t *d_grid, int cols, 
  * capacity, makes no allocation, no blocking copy and no host wait. */
 int lsd_reserve_map_update(lsd_ctx *ctx, int cols, int rows);
 
+/* --- mapping with known poses: localised scans into an OccupancyGrid ------------------------------ */
+/* No reference counterpart: the reference's maps come from an outside SLAM (Karto) that re-publishes the grid.  These entries turn the
+ * scans and poses a fleet has on the device every tick into that grid.  Known poses only: no scan matching against the growing grid, no
+ * loop closure.  The map state is two caller-owned device planes of rows x cols uint32, d_pass and d_hit (Karto's counting model), in the
+ * frame map_param names; the entries ADD to them (clear them with hipMemsetAsync).  Counters wrap at 2^32.
+ * lsd_enqueue_grid_integrate_device: n_scans scans as the ingest entries write them (d_scans at a pitch of `stride` readings, d_lens),
+ * scan i at the pose (x, y in map pixels, ang in degrees: the rotation of the scan frame onto the map) held in the first three doubles of
+ * the record at d_poses + i * pose_pitch_bytes -- packed lsd_position (24), an array of lsd_fa_state (720) or of lsd_fa_carry (768) as
+ * it is.  One launch, asynchronous on `stream`, no workspace, no synchronisation.  The rule, fp64 without FMA:
+ *   scan skipped whole   a pose component not finite; |x + 1| < 1e-4 (the reference's "no pose" test, LSD/myFA.cpp:99); |x| or |y| > 2^20
+ *   beam i < len skipped range NaN, <= 0 or +inf; angle not finite; angle + ang / 180 * pi not finite
+ *   rr = min(range, range_max); the beam HITS iff range <= range_max;  th = angle + ang / 180.0 * pi;  (s, c) = sin, cos(th), correctly
+ *   rounded;  x0 = (int)round(x), y0 = (int)round(y), x1 = (int)round(x + rr * c / mapResol), y1 = (int)round(y + rr * s / mapResol)
+ *   the ray: dx = x1 - x0, dy = y1 - y0, n = max(|dx|, |dy|), m = min(|dx|, |dy|), the major axis x iff |dx| >= |dy|; for k = 0 .. n the
+ *   cell with major = start + k * sgn, minor = start + sgn_minor * ((2 k m + n) / (2 n)) in integers; n = 0: the start cell alone
+ *   every cell of the ray inside [0, cols) x [0, rows) gets pass += 1; a beam that hits and whose cell k = n is inside gives it hit += 1
+ * Refused before anything is enqueued, LSD_ERR_INVALID: a null pointer, n_scans < 0, stride <= 0 or above the context's scan capacity,
+ * cols or rows outside 1..65535, mapResol or range_max not > 0, range_max / mapResol >= 32767 (keeps 2 k m + n within 32 bits), a pitch
+ * below 24 or not a multiple of 8, d_scans not 16-byte or d_poses not 8-byte aligned.  n_scans == 0 launches nothing. */
+int lsd_enqueue_grid_integrate_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                      const void *d_poses, size_t pose_pitch_bytes, lsd_map_param map_param, double range_max,
+                                      uint32_t *d_pass, uint32_t *d_hit, void *stream);
+/* The planes as the int8 row-major grid lsd_enqueue_map_update_device and lsd_enqueue_occupancy_to_map_device take, integers only:
+ *   d_grid[i] = -1 if d_pass[i] < min_pass, else 100 if (uint64) d_hit[i] * occ_den >= (uint64) d_pass[i] * occ_num, else 0.
+ * Karto's min_pass_through and occupancy_threshold are min_pass = 2, occ_num / occ_den = 1 / 10.  LSD_ERR_INVALID for a null pointer,
+ * n_cells == 0, occ_den == 0 or occ_num > occ_den.  One launch, asynchronous on `stream`. */
+int lsd_enqueue_grid_publish_device(lsd_ctx *ctx, const uint32_t *d_pass, const uint32_t *d_hit, size_t n_cells, uint32_t min_pass,
+                                    uint32_t occ_num, uint32_t occ_den, int8_t *d_grid, void *stream);
+/* Host convenience: scans, lens, poses (n_scans packed lsd_position) and the two planes (rows x cols of map_param, IN-OUT) travel to the
+ * context's staging, lsd_enqueue_grid_integrate_device runs, the planes come back.  Blocking.  lens[i] outside 0..stride:
+ * LSD_ERR_INVALID. */
+int lsd_grid_integrate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
+                       lsd_map_param map_param, double range_max, uint32_t *pass, uint32_t *hit);
+
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */
 void lsd_scaled_size(int cols, int rows, double sca, int *w, int *h);

@@ -173,6 +173,9 @@ _ABI = {
     "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "lsd_enqueue_laserscan_ingest_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "lsd_enqueue_grid_integrate_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, _vp, _vp]),
+    "lsd_enqueue_grid_publish_device": (_i, [_vp, _vp, _vp, _sz, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "lsd_grid_integrate": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -597,6 +600,39 @@ class Context:
     def enqueue_occupancy_to_map_device(self, d_grid, n_cells, d_map, stream=None):
         return self._chk(self.L.lsd_enqueue_occupancy_to_map_device(self.h, d_grid, n_cells, d_map, stream))
 
+    # -- mapping with known poses -------------------------------------------------------------------
+    def enqueue_grid_integrate_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, map_param, range_max, d_pass, d_hit,
+                                      stream=None):
+        """lsd_enqueue_grid_integrate_device on device addresses: n_scans ingested scans (d_scans at a pitch of `stride` readings, d_lens),
+        scan i at the pose in the first three doubles of the record at d_poses + i * pose_pitch bytes (24: packed poses, 720: lsd_fa_state,
+        768: lsd_fa_carry), counted into the uint32 planes d_pass / d_hit of map_param's grid; asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_integrate_device(self.h, d_scans, d_lens, int(n_scans), int(stride), d_poses, int(pose_pitch),
+                                                                  _map_param(map_param), float(range_max), d_pass, d_hit, stream))
+
+    def enqueue_grid_publish_device(self, d_pass, d_hit, n_cells, d_grid, min_pass=2, occ_num=1, occ_den=10, stream=None):
+        """lsd_enqueue_grid_publish_device on device addresses: d_grid[i] = -1 where d_pass[i] < min_pass, else 100 where
+        d_hit[i] * occ_den >= d_pass[i] * occ_num, else 0; asynchronous."""
+        n_cells, min_pass, occ_num, occ_den = _u32s(n_cells, min_pass, occ_num, occ_den, limit=(1 << 64, 1 << 32, 1 << 32, 1 << 32))
+        return self._chk(self.L.lsd_enqueue_grid_publish_device(self.h, d_pass, d_hit, n_cells, min_pass, occ_num, occ_den, d_grid, stream))
+
+    def grid_integrate(self, scans, lens, poses, map_param, range_max, pass_counts=None, hit_counts=None):
+        """lsd_grid_integrate from host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3] (x, y in map pixels, ang
+        in degrees), the planes uint32 [rows, cols] (None: zeros).  Returns (pass, hit): new arrays, the given counts plus this call's."""
+        sc = np.ascontiguousarray(scans, np.float64)
+        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        mp = _map_param(map_param)
+        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or mp.oriMapCol <= 0 or mp.oriMapRow <= 0:
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], a grid of at least one cell")
+        shape = (mp.oriMapRow, mp.oriMapCol)
+        planes = []
+        for a in (pass_counts, hit_counts):
+            a = np.zeros(shape, np.uint32) if a is None else np.array(a, np.uint32).reshape(shape)
+            planes.append(np.ascontiguousarray(a))
+        self._chk(self.L.lsd_grid_integrate(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, mp,
+                                            float(range_max), planes[0].ctypes.data, planes[1].ctypes.data))
+        return planes[0], planes[1]
+
     def reserve(self, n, cols, rows):
         self._chk(self.L.lsd_reserve(self.h, n, cols, rows))
 
@@ -828,6 +864,14 @@ def _map_param(mp):
     return lsd_map_param(int(mp[0]), int(mp[1]), float(mp[2]), float(mp[3]), float(mp[4]))
 
 
+def _u32s(*values, limit):
+    """Counts as the C ABI's unsigned arguments take them: integers in 0 .. limit - 1 (ctypes would wrap anything else silently)."""
+    out = tuple(int(v) for v in values)
+    if any(not 0 <= v < m for v, m in zip(out, limit)):
+        raise LsdError(LSD_ERR_INVALID, "a count outside its unsigned range: %r" % (out,))
+    return out
+
+
 def map_frame(frame):
     """An lsd_map_frame from (mapResol, mapOriX, mapOriY), from a map_param (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) or from an
     lsd_map_frame; LsdError(LSD_ERR_INVALID) for a resolution that is not finite and > 0 or an origin that is not finite."""
@@ -947,6 +991,101 @@ def _occupancy_grid(d_grid, cols, rows, device):
     if cols <= 0 or rows <= 0 or tuple(d_grid.shape) not in ((rows * cols,), (rows, cols)):
         raise LsdError(LSD_ERR_INVALID, "d_grid must hold oriMapRow x oriMapCol cells, flat or [rows, cols]")
     return d_grid.contiguous()
+
+
+class GridMapper:
+    """Mapping with known poses: localised scans integrated into an occupancy grid on the device (k_gridmap.hip; include/lsd_hip.h,
+    "mapping with known poses").  The reference has no counterpart -- its maps come from an outside SLAM --, and this is
+    no SLAM either: no scan matching against the growing grid, no loop closure.  The mapper owns two planes of rows x cols counters
+    (torch tensors: uint32 values in int32 storage): `pass`, the beams that crossed a cell, and `hit`, those that ended in it.  A scan at
+    pose (x, y in pixels of THIS grid, ang in degrees) adds one ray per beam, cut at range_max (metres; a cut beam passes and does not
+    hit); publish_device() turns the planes into the int8 OccupancyGrid (-1 below min_pass passes, 100 where hit / pass >= occ[0] /
+    occ[1], else 0; the defaults are Karto's) that Localizer.set_map_device takes.  Poses from a Localizer are in pixels of the map it
+    localises on: give the mapper that map's mapResol, mapOriX and mapOriY (cols and rows may differ; cells outside are skipped).
+    Everything but counts() and integrate() is enqueued without waiting for the device."""
+
+    def __init__(self, cols, rows, mapResol, mapOriX, mapOriY, range_max, min_pass=2, occ=(1, 10), ctx=None):
+        import torch
+        self.ctx = ctx or default_context()
+        self.cols, self.rows = int(cols), int(rows)
+        self.mapResol, self.mapOriX, self.mapOriY, self.range_max = float(mapResol), float(mapOriX), float(mapOriY), float(range_max)
+        if not (0 < self.cols <= 65535 and 0 < self.rows <= 65535):
+            raise LsdError(LSD_ERR_INVALID, "cols and rows must be 1..65535")
+        if not (self.mapResol > 0 and self.range_max > 0 and self.range_max / self.mapResol < 32767):
+            raise LsdError(LSD_ERR_INVALID, "mapResol > 0, range_max > 0 and range_max / mapResol < 32767")
+        self.min_pass, self.occ_num, self.occ_den = _u32s(min_pass, occ[0], occ[1], limit=(1 << 32,) * 3)
+        if self.occ_den == 0 or self.occ_num > self.occ_den:
+            raise LsdError(LSD_ERR_INVALID, "occ = (num, den) with den > 0 and num <= den")
+        self._planes = torch.zeros((2, self.rows * self.cols), dtype=torch.int32, device="cuda:%d" % int(self.ctx.device))
+
+    @property
+    def map_param(self):
+        """(oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) of the grid: what set_map_device takes with a published grid."""
+        return (self.cols, self.rows, self.mapResol, self.mapOriX, self.mapOriY)
+
+    @property
+    def d_pass(self):
+        return self._planes[0].data_ptr()
+
+    @property
+    def d_hit(self):
+        return self._planes[1].data_ptr()
+
+    def clear(self, stream=None):
+        """Both planes to zero, on `stream` (a torch.cuda.Stream; default: the current one)."""
+        import torch
+        with torch.cuda.stream(_cuda_stream(stream)):
+            self._planes.zero_()
+
+    def _enqueue(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, stream):
+        ctx.enqueue_grid_integrate_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, self.d_pass,
+                                          self.d_hit, stream)
+
+    def integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, stream=None):
+        """Adds scans that are on the device: d_scans a CUDA float64 tensor [n, stride, 2] as the ingest entries write it, d_lens CUDA
+        int32 [n], d_poses a CUDA tensor holding n records at pose_pitch bytes, each starting with (x, y, ang) as doubles -- float64
+        [n, 3] (pitch 24), or the bytes of lsd_fa_state (720) or lsd_fa_carry (768) records.  On `stream` (default: the current one)."""
+        import torch
+        for name, t, dt in (("d_scans", d_scans, torch.float64), ("d_lens", d_lens, torch.int32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise LsdError(LSD_ERR_INVALID, "%s must be a contiguous CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
+        if not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous():
+            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor")
+        n, pitch = d_lens.numel(), int(pose_pitch)
+        if d_scans.dim() != 3 or d_scans.shape[0] != n or d_scans.shape[2] != 2 or d_scans.shape[1] < 1:
+            raise LsdError(LSD_ERR_INVALID, "d_scans must be [n, stride >= 1, 2] with one length per scan")
+        if pitch < 24 or (n and d_poses.numel() * d_poses.element_size() < (n - 1) * pitch + 24):
+            raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
+        self._enqueue(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
+                      _cuda_stream(stream).cuda_stream)
+        self._held = (d_scans, d_lens, d_poses)                              # the launch reads them: alive until the next one
+
+    def integrate(self, scans, lens, poses):
+        """integrate_device for host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]; one upload, then the
+        launch on the current stream."""
+        import torch
+        sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
+        dev = self._planes.device
+        self.integrate_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev))
+
+    def publish_device(self, stream=None):
+        """The planes as an OccupancyGrid: a new CUDA int8 tensor [rows, cols], written on `stream` (default: the current one) -- what
+        Localizer.set_map_device(grid, *mapper.map_param) takes, on the same stream, without the host in between."""
+        import torch
+        ts = _cuda_stream(stream)
+        with torch.cuda.stream(ts):
+            grid = torch.empty((self.rows, self.cols), dtype=torch.int8, device=self._planes.device)
+        self.ctx.enqueue_grid_publish_device(self.d_pass, self.d_hit, self.rows * self.cols, grid.data_ptr(), self.min_pass, self.occ_num,
+                                             self.occ_den, ts.cuda_stream)
+        return grid
+
+    def counts(self):
+        """(pass, hit) as numpy uint32 [rows, cols]: a read-back, which waits for the device."""
+        both = self._planes.cpu().numpy().view(np.uint32).reshape(2, self.rows, self.cols)
+        return both[0].copy(), both[1].copy()
 
 
 class _MapSlot:
@@ -1082,6 +1221,7 @@ class _Ticks:
         self._map_ctx, self._map_geom = None, (0, 0)                         # the map side's context, the largest geometry reserved for it
         self._cap = 0
         self._held = None
+        self._last_tick = None                                               # (S, k, stream, robots) of the last tick enqueued
         self._tail_b = 4 * len(self._pairs)                                  # bytes behind the outputs: the map line counts of step()
         # every hand-over re-bases, as set_map*(..., rebase=True) does for one: the setting of a site whose maps grow.  It is also how
         # Localizer.set_map_device, whose parameter list is fixed, is told to re-base.
@@ -1269,7 +1409,34 @@ class _Ticks:
             pair.read_by(ts)                                                 # the first tick of this stream on a new map: behind its update
         self._flush_rebase()                                                 # and, in front of the loop, the carries into that map's frame
         self._loop(S, k, nf, d_nl, d_np, d_od, d_st, d_rp, stream)
+        self._last_tick = (S, k, ts, self._tick_robots())                    # what integrate_last_tick reads
         return b_st, b_rp
+
+    def _tick_robots(self):
+        """The host's record of which robots the tick being enqueued belongs to, for integrate_last_tick (Localizer: all of them)."""
+        return None
+
+    def _integrate_last_tick(self, mapper, robots):
+        """integrate_last_tick for the robots `robots` (ascending indices): one launch per run of neighbouring robots, on the tick's
+        stream, reading the tick's staging -- slot s * k + t holds frame t of robot s: its packed scan and length (k_ingest's output)
+        and, in the read-back block, the state the frame produced, whose first three doubles are the pose (pitch 720)."""
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        S, k, ts, _ = self._last_tick
+        d_sc, d_ln, d_st = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
+        b_state, b_scan = FA_STATE_DTYPE.itemsize, 16 * self.n_beams
+        robots = [int(r) for r in robots]
+        a = 0
+        while a < len(robots):
+            b = a
+            while b + 1 < len(robots) and robots[b + 1] == robots[b] + 1:
+                b += 1
+            first, count = robots[a] * k, (robots[b] - robots[a] + 1) * k
+            mapper._enqueue(self.ctx, d_sc + first * b_scan, d_ln + first * 4, count, self.n_beams, d_st + first * b_state, b_state,
+                            ts.cuda_stream)
+            a = b + 1
 
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """lidar float64 [S, k, n_beams, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames
@@ -1485,6 +1652,15 @@ class Localizer(_Ticks):
         up and the ticks see no map lines."""
         return self._pairs[0].current.count
 
+    def integrate_last_tick(self, mapper):
+        """Mapping with known poses: enqueues, on the stream of the last step / step_device and behind it, the integration into `mapper`
+        (a GridMapper) of every frame of that tick, each at the state it produced -- the packed scans and the states are read from the
+        tick's own staging, nothing is read back and nothing waits.  A frame whose state has no pose (a reset: x = -1) falls out by the
+        mapper's "no pose" rule, a slot past a robot's n_frames holds an empty scan.  Call it before the next tick, which reuses the
+        staging.  The poses are in pixels of the map the tick localised on: the mapper's mapResol / mapOriX / mapOriY are that map's.
+        With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
+        self._integrate_last_tick(mapper, range(self.n_robots))
+
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current
         cx._chk(cx.L.lsd_enqueue_feature_scan_batch_device(cx.h, d_scans, d_lens, n, self.n_beams, _map_param(m.map_param), rdp_leastPoint, rdp_threLine,
@@ -1547,6 +1723,7 @@ class FleetLocalizer(_Ticks):
         for i, m in enumerate(maps):
             self.set_map(i, *m)
         self._map_of = torch.from_numpy(ids).cuda()
+        self._map_of_host = ids.copy()                                       # the ids as enqueued so far (integrate_last_tick's filter)
         self.reset(range(self.n_robots), odom0)
 
     @property
@@ -1629,6 +1806,7 @@ class FleetLocalizer(_Ticks):
         # pinned, so the copies do not wait for the stream (as the take flags of step_device)
         up = lambda a: torch.from_numpy(a).pin_memory().to("cuda", non_blocking=True)
         self._map_of.index_copy_(0, up(idx), up(ids))
+        self._map_of_host[idx] = ids
 
     def rebase(self, robots, from_map, to_map):
         """Moves the given robots' carries from the pixel frame of map from_map to that of map to_map (the map_param the next tick
@@ -1653,6 +1831,18 @@ class FleetLocalizer(_Ticks):
         self._mask.copy_(torch.from_numpy(mask).pin_memory(), non_blocking=True)
         self.ctx.enqueue_fa_carry_rebase_device(self._carry.data_ptr(), self.n_robots, self._mask.data_ptr(), 1, f, t,
                                                 torch.cuda.current_stream().cuda_stream)
+
+    def _tick_robots(self):
+        return self._map_of_host.copy()
+
+    def integrate_last_tick(self, mapper, map_id):
+        """Localizer.integrate_last_tick for the robots that were on map `map_id` when the last tick was enqueued (the ids as
+        assign() had left them by then; robots on other maps and robots that sat out are not touched): one launch per run of
+        neighbouring robots.  The mapper's frame is that map's."""
+        i = self._map_id(map_id)
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        self._integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i))
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         self.ctx.enqueue_feature_scan_maps_device(d_scans, d_lens, n, self.n_beams, self._table, self._map_of.data_ptr(), k, self._lines.data_ptr(), d_n_lines,

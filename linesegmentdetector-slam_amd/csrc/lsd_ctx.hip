@@ -1063,6 +1063,71 @@ int lsd_enqueue_map_update_device(lsd_ctx* c, const int8_t* d_grid, int cols, in
     return lsd_enqueue_batch_device(c, d_map, 1, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, d_line_im, d_lines, max_lines, d_count, s);   // :132
 }
 
+// --- mapping with known poses (k_gridmap.hip) ---
+// the pose is the first three doubles of each record the entry's pitch may step over
+static_assert(sizeof(lsd_position) == 24 && offsetof(lsd_position, x) == 0 && offsetof(lsd_position, y) == 8 && offsetof(lsd_position, ang) == 16 &&
+              sizeof(lsd_fa_state) == 720 && offsetof(lsd_fa_state, x) == 0 && offsetof(lsd_fa_carry, state) == 0 && sizeof(lsd_fa_carry) == 768,
+              "lsd_enqueue_grid_integrate_device reads a pose from the head of lsd_position, lsd_fa_state and lsd_fa_carry records");
+
+// what both integrate entries refuse about the sizes, the frame and the range (c not null)
+static bool grid_frame_bad(const lsd_ctx* c, int n_scans, int stride, const lsd_map_param& mp, double range_max) {
+    if (n_scans < 0 || stride <= 0 || stride > c->scan_cap) return true;
+    if (mp.oriMapCol <= 0 || mp.oriMapRow <= 0 || mp.oriMapCol > 65535 || mp.oriMapRow > 65535) return true;
+    return !(mp.mapResol > 0) || !(range_max > 0) || !(range_max / mp.mapResol < 32767);     // (a NaN fails every test)
+}
+
+int lsd_enqueue_grid_integrate_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                      size_t pose_pitch, lsd_map_param mp, double range_max, uint32_t* d_pass, uint32_t* d_hit, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_poses || !d_pass || !d_hit || grid_frame_bad(c, n_scans, stride, mp, range_max)) return LSD_ERR_INVALID;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) || (reinterpret_cast<uintptr_t>(d_poses) & 7)) {
+        c->err = "grid integrate: pose pitch >= 24 and a multiple of 8, d_scans 16-byte and d_poses 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_integrate(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_pass, d_hit, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_enqueue_grid_publish_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, size_t n_cells, uint32_t min_pass,
+                                    uint32_t occ_num, uint32_t occ_den, int8_t* d_grid, void* stream) {
+    if (!c || !d_pass || !d_hit || !d_grid || n_cells == 0 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
+    if (n_cells > (size_t)65535 * 65535) return LSD_ERR_INVALID;      // (more cells than the largest grid the integration takes)
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_publish(d_pass, d_hit, n_cells, min_pass, occ_num, occ_den, d_grid, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_grid_integrate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                       double range_max, uint32_t* pass, uint32_t* hit) {
+    if (!c || !scans || !lens || !poses || !pass || !hit || grid_frame_bad(c, n_scans, stride, mp, range_max)) return LSD_ERR_INVALID;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint32_t *d_pa, *d_hi;
+    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_pa, cells); k(d_hi, cells); };
+    HIPCHK(c, carve(c->stage, regions));
+    if (ns) {
+        HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(d_pa, pass, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_hi, hit, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_grid_integrate_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_pa, d_hi, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(pass, d_pa, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hit, d_hi, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
 int lsd_enqueue_scan_to_map_match_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
                                          const lsd_line* d_scan_lines, const lsd_position* d_pts, int n_points,
                                          lsd_position lidar, lsd_position last, const int* d_pairs, int n_pairs,

@@ -169,6 +169,12 @@ hipError_t prepare_rdp_long(size_t bytes);
 // the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
 void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
                    int* lens, int stride, hipStream_t s);
+// mapping with known poses (k_gridmap.hip): n_scans scans as launch_rdp reads them, each at the pose in the first three doubles of the
+// record at poses + i * pose_pitch, counted into the two planes of a cols x rows grid; and a pair of planes published as an int8 grid
+void launch_grid_integrate(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols,
+                           int rows, double resol, double range_max, uint32_t* pass, uint32_t* hit, hipStream_t s);
+void launch_grid_publish(const uint32_t* pass, const uint32_t* hit, size_t n_cells, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,
+                         int8_t* grid, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
