@@ -498,8 +498,8 @@ int lsd_reserve_map_update(lsd_ctx *ctx, int cols, int rows);
 
 /* --- mapping with known poses: localised scans into an OccupancyGrid ------------------------------ */
 /* No reference counterpart: the reference's maps come from an outside SLAM (Karto) that re-publishes the grid.  These entries turn the
- * scans and poses a fleet has on the device every tick into that grid.  Known poses only: no scan matching against the growing grid, no
- * loop closure.  The map state is two caller-owned device planes of rows x cols uint32, d_pass and d_hit (Karto's counting model), in the
+ * scans and poses a fleet has on the device every tick into that grid.  These entries take a pose as it is; the section after this one corrects
+ * it against the growing grid first (correlative scan-to-grid matching).  No loop closure.  The map state is two caller-owned device planes of rows x cols uint32, d_pass and d_hit (Karto's counting model), in the
  * frame map_param names; the entries ADD to them (clear them with hipMemsetAsync).  Counters wrap at 2^32.
  * lsd_enqueue_grid_integrate_device: n_scans scans as the ingest entries write them (d_scans at a pitch of `stride` readings, d_lens),
  * scan i at the pose (x, y in map pixels, ang in degrees: the rotation of the scan frame onto the map) held in the first three doubles of
@@ -529,6 +529,60 @@ int lsd_enqueue_grid_publish_device(lsd_ctx *ctx, const uint32_t *d_pass, const 
  * LSD_ERR_INVALID. */
 int lsd_grid_integrate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
                        lsd_map_param map_param, double range_max, uint32_t *pass, uint32_t *hit);
+
+/* --- correlative scan-to-grid matching: a pose corrected against the growing grid before it is integrated ------- */
+/* Scan matching against the growing grid now exists (csrc/k_gridmatch.hip): Olson's / Karto's correlative matcher in
+ * its plain, single-resolution form.  The planes are turned into a uint8 lookup plane (every occupied cell smeared by a small table), and
+ * each scan's rounded end cells are translated over a window of whole cells and whole angle steps around its pose and summed on that
+ * plane.  The result is made of integers and has no iteration order: tests/grid_match_cases.py restates both rules and the device gives
+ * the same bytes.  NOT built: a coarse-to-fine (multi-resolution) search, sub-cell refinement, a covariance of the response, loop
+ * closure, the fleet classes.
+ * lsd_enqueue_grid_likelihood_device: a cell is OCCUPIED iff the publish rule gives it 100 (d_pass >= min_pass and (uint64) d_hit *
+ * occ_den >= (uint64) d_pass * occ_num);  d_corr[y][x] = the maximum of smear.w[|v|][|u|] over all |u|, |v| <= smear.radius for which
+ * (x + u, y + v) is inside the grid and occupied, 0 if there is none (a maximum has no order: the table need not be monotone).  One
+ * launch, no workspace, asynchronous.  LSD_ERR_INVALID before anything is enqueued: a null pointer, cols or rows outside 1..65535, a
+ * radius outside 0..7, occ_den == 0 or occ_num > occ_den.
+ * lsd_grid_smear_default (host only, a convenience): w[|v|][|u|] = (uint8) floor(255 * exp(-(u^2 + v^2) / (2 sigma_cells^2)) + 0.5) for
+ * |u|, |v| <= radius with the host's libm, 0 elsewhere.  LSD_ERR_INVALID: out null, radius outside 0..7, sigma_cells not finite or <= 0. */
+typedef struct lsd_grid_smear { int radius; uint8_t w[8][8]; } lsd_grid_smear;   /* radius 0..7, w[|dv|][|du|] */
+int lsd_enqueue_grid_likelihood_device(lsd_ctx *ctx, const uint32_t *d_pass, const uint32_t *d_hit, int cols, int rows,
+                                       uint32_t min_pass, uint32_t occ_num, uint32_t occ_den, lsd_grid_smear smear, uint8_t *d_corr,
+                                       void *stream);
+int lsd_grid_smear_default(double sigma_cells, int radius, lsd_grid_smear *out);
+/* lsd_enqueue_grid_match_device: scans, lengths and poses as lsd_enqueue_grid_integrate_device reads them, d_corr a rows x cols plane of
+ * map_param's grid.  Everything is fp64 without FMA, with the integration's own helpers.  For scan n at pose (x, y, ang):
+ *   skipped scans and beams   the integration's tests (above); a skipped scan's record: its pose's 24 bytes, flags = 2, every other field 0
+ *   candidates  (a, j, i), a in -na..na, j in -wy..wy, i in -wx..wx;  theta_a = ang + (double) a * ang_step (a multiply, then an add)
+ *   a beam is SCORED at angle a iff it is not skipped, range <= range_max and th = angle + theta_a / 180 * pi is finite; its end cell is
+ *   ex = (int)round(x + range * cos(th) / mapResol), ey = (int)round(y + range * sin(th) / mapResol); nb(a) counts the scored beams
+ *   S(a, j, i) = the sum over the beams scored at a of d_corr[ey + j][ex + i], 0 where that cell is outside the grid (uint32: at most
+ *   255 * 4096 < 2^20)
+ *   the winner: the largest S, then the smallest i^2 + j^2, then the smallest |a|, then the smallest linear index
+ *   ((a + na) * (2 wy + 1) + (j + wy)) * (2 wx + 1) + (i + wx) -- on a featureless plane the prior pose wins
+ *   record: score = S of the winner, n_beams = nb of its angle, di, dj, da its offsets, score_prior = S(0, 0, 0), reserved = 0
+ *   ACCEPTED (flags bit 0) iff n_beams >= min_beams and (uint64) score * min_den >= (uint64) 255 * n_beams * min_num; then
+ *   (x, y, ang) = (x + di, y + dj, theta_da); else the input pose's bits are copied
+ * An array of records IS a d_poses argument of pitch 56 for lsd_enqueue_grid_integrate_device.  Two launches, asynchronous on `stream`;
+ * the n_scans * (2 na + 1) slots between them (16 bytes each) are context workspace, grown before the first launch when needed -- that
+ * case alone synchronises; there is no other allocation, copy or host wait.  LSD_ERR_INVALID before anything is enqueued: whatever
+ * lsd_enqueue_grid_integrate_device refuses on the arguments the two share; wx, wy or na outside 0..63; ang_step not finite or negative;
+ * ang_step == 0 with na > 0; min_den == 0 or min_num > min_den; d_corr or d_out null, d_out not 8-byte aligned.  n_scans == 0 launches
+ * nothing.
+ * (The record's type is lsd_grid_match_rec: in C a typedef and the host entry below cannot share the name lsd_grid_match; the struct
+ * tag can.) */
+typedef struct lsd_grid_search { int wx, wy, na; double ang_step; uint32_t min_beams, min_num, min_den; } lsd_grid_search;
+typedef struct lsd_grid_match {            /* 56 bytes; its head is a pose, so an array of these IS a d_poses argument (pitch 56) */
+    double x, y, ang; uint32_t score, n_beams; int32_t di, dj, da; uint32_t flags, score_prior, reserved;
+} lsd_grid_match_rec;
+#define LSD_GRID_MATCH_ACCEPTED 1u
+#define LSD_GRID_MATCH_SKIPPED 2u
+int lsd_enqueue_grid_match_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                  const void *d_poses, size_t pose_pitch_bytes, lsd_map_param map_param, double range_max,
+                                  const uint8_t *d_corr, lsd_grid_search search, lsd_grid_match_rec *d_out, void *stream);
+/* Host convenience: scans, lens, poses (n_scans packed lsd_position) and the plane (rows x cols of map_param) travel to the context's
+ * staging, lsd_enqueue_grid_match_device runs, the n_scans records come back.  Blocking.  lens[i] outside 0..stride: LSD_ERR_INVALID. */
+int lsd_grid_match(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
+                   lsd_map_param map_param, double range_max, const uint8_t *corr, lsd_grid_search search, lsd_grid_match_rec *out);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

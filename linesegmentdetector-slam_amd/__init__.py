@@ -76,6 +76,27 @@ class lsd_position(C.Structure):  # == structPosition, LSD/baseFunc.h:46-50
 
 
 POS_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8")])
+
+
+# correlative scan-to-grid matching (include/lsd_hip.h): the smear table, the search window and the record of one matched scan
+class lsd_grid_smear(C.Structure):     # radius 0..7, w[|dv|][|du|]
+    _fields_ = [("radius", C.c_int), ("w", (C.c_uint8 * 8) * 8)]
+
+
+class lsd_grid_search(C.Structure):
+    _fields_ = [("wx", C.c_int), ("wy", C.c_int), ("na", C.c_int), ("ang_step", C.c_double), ("min_beams", C.c_uint32),
+                ("min_num", C.c_uint32), ("min_den", C.c_uint32)]
+
+
+class lsd_grid_match(C.Structure):     # the C side's lsd_grid_match_rec (struct lsd_grid_match)
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("ang", C.c_double), ("score", C.c_uint32), ("n_beams", C.c_uint32), ("di", C.c_int32),
+                ("dj", C.c_int32), ("da", C.c_int32), ("flags", C.c_uint32), ("score_prior", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+GRID_MATCH_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "u4"), ("n_beams", "u4"), ("di", "i4"), ("dj", "i4"),
+                             ("da", "i4"), ("flags", "u4"), ("score_prior", "u4"), ("reserved", "u4")])
+assert GRID_MATCH_DTYPE.itemsize == 56 == C.sizeof(lsd_grid_match) and C.sizeof(lsd_grid_smear) == 68 and C.sizeof(lsd_grid_search) == 40
+GRID_MATCH_ACCEPTED, GRID_MATCH_SKIPPED = 1, 2
 SCORE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "f8")])   # lsd_match_score
 
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
@@ -176,6 +197,10 @@ _ABI = {
     "lsd_enqueue_grid_integrate_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, _vp, _vp]),
     "lsd_enqueue_grid_publish_device": (_i, [_vp, _vp, _vp, _sz, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "lsd_grid_integrate": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, _vp]),
+    "lsd_enqueue_grid_likelihood_device": (_i, [_vp, _vp, _vp, _i, _i, C.c_uint32, C.c_uint32, C.c_uint32, lsd_grid_smear, _vp, _vp]),
+    "lsd_grid_smear_default": (_i, [_dbl, _i, C.POINTER(lsd_grid_smear)]),
+    "lsd_enqueue_grid_match_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, lsd_grid_search, _vp, _vp]),
+    "lsd_grid_match": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, lsd_grid_search, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -633,6 +658,38 @@ class Context:
                                             float(range_max), planes[0].ctypes.data, planes[1].ctypes.data))
         return planes[0], planes[1]
 
+    # -- correlative scan-to-grid matching ----------------------------------------------------------
+    def enqueue_grid_likelihood_device(self, d_pass, d_hit, cols, rows, d_corr, min_pass=2, occ_num=1, occ_den=10, smear=None, stream=None):
+        """lsd_enqueue_grid_likelihood_device on device addresses: d_corr[y][x] (uint8, rows x cols) = the largest smear.w[|v|][|u|] over the
+        occupied cells (x + u, y + v) within smear.radius (occupied: what the publish rule gives 100), 0 if none; asynchronous.  smear: an
+        lsd_grid_smear or what grid_smear() takes (None: grid_smear_default(1.0, 3))."""
+        min_pass, occ_num, occ_den = _u32s(min_pass, occ_num, occ_den, limit=(1 << 32,) * 3)
+        return self._chk(self.L.lsd_enqueue_grid_likelihood_device(self.h, d_pass, d_hit, int(cols), int(rows), min_pass, occ_num, occ_den,
+                                                                   grid_smear(smear), d_corr, stream))
+
+    def enqueue_grid_match_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, map_param, range_max, d_corr, search, d_out,
+                                  stream=None):
+        """lsd_enqueue_grid_match_device on device addresses: scans, lengths and poses as enqueue_grid_integrate_device reads them, matched on
+        the plane d_corr over the window `search` (an lsd_grid_search or what grid_search() takes); d_out receives n_scans records of 56
+        bytes (GRID_MATCH_DTYPE), which are a d_poses argument of pitch 56 themselves; asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_match_device(self.h, d_scans, d_lens, int(n_scans), int(stride), d_poses, int(pose_pitch),
+                                                              _map_param(map_param), float(range_max), d_corr, grid_search(search), d_out, stream))
+
+    def grid_match(self, scans, lens, poses, map_param, range_max, corr, search):
+        """lsd_grid_match from host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3], corr uint8 [rows, cols].
+        Returns the n records as a numpy array of GRID_MATCH_DTYPE.  Blocking."""
+        sc = np.ascontiguousarray(scans, np.float64)
+        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        mp = _map_param(map_param)
+        co = np.ascontiguousarray(corr, np.uint8)
+        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], corr uint8 [rows, cols]")
+        out = np.zeros(len(ln), GRID_MATCH_DTYPE)
+        self._chk(self.L.lsd_grid_match(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, mp, float(range_max),
+                                        co.ctypes.data, grid_search(search), out.ctypes.data))
+        return out
+
     def reserve(self, n, cols, rows):
         self._chk(self.L.lsd_reserve(self.h, n, cols, rows))
 
@@ -872,6 +929,54 @@ def _u32s(*values, limit):
     return out
 
 
+def grid_smear_default(sigma_cells=1.0, radius=3):
+    """lsd_grid_smear_default: the table w[|v|][|u|] = floor(255 * exp(-(u^2 + v^2) / (2 sigma_cells^2)) + 0.5) within `radius`, 0 elsewhere."""
+    out = lsd_grid_smear()
+    st = load_library().lsd_grid_smear_default(float(sigma_cells), int(radius), C.byref(out))
+    if st != LSD_OK:
+        raise LsdError(st, "grid_smear_default: sigma_cells > 0 and finite, radius 0..7")
+    return out
+
+
+def grid_smear(smear=None):
+    """An lsd_grid_smear: `smear` itself, (radius, w) with w an 8 x 8 table of 0..255 indexed [|dv|][|du|], or None: the default table."""
+    if isinstance(smear, lsd_grid_smear):
+        return smear
+    if smear is None:
+        return grid_smear_default(1.0, 3)
+    radius, w = smear
+    w = np.asarray(w)
+    if w.shape != (8, 8) or (w < 0).any() or (w > 255).any():
+        raise LsdError(LSD_ERR_INVALID, "a smear table is 8 x 8 values of 0..255")
+    out = lsd_grid_smear()
+    out.radius = int(radius)
+    C.memmove(out.w, np.ascontiguousarray(w, np.uint8).ctypes.data, 64)
+    return out
+
+
+def grid_smear_table(smear):
+    """(radius, the 8 x 8 uint8 table) of an lsd_grid_smear."""
+    return int(smear.radius), np.frombuffer(bytes(smear.w), np.uint8).reshape(8, 8).copy()
+
+
+def grid_search(search=None, **kw):
+    """An lsd_grid_search: `search` itself, a dict or a tuple (wx, wy, na, ang_step, min_beams, min_num, min_den), or keywords.  The window
+    is +-wx, +-wy cells and +-na steps of ang_step degrees; a match is accepted with at least min_beams scored beams and a mean response
+    of at least 255 * min_num / min_den."""
+    if isinstance(search, lsd_grid_search):
+        return search
+    if isinstance(search, dict):
+        kw = dict(search, **kw)
+        search = None
+    if search is None:
+        a = dict(wx=3, wy=3, na=2, ang_step=0.5, min_beams=30, min_num=1, min_den=4)
+        a.update(kw)
+        search = tuple(a[k] for k in ("wx", "wy", "na", "ang_step", "min_beams", "min_num", "min_den"))
+    wx, wy, na, step, mb, mn, md = search
+    mb, mn, md = _u32s(mb, mn, md, limit=(1 << 32,) * 3)
+    return lsd_grid_search(int(wx), int(wy), int(na), float(step), mb, mn, md)
+
+
 def map_frame(frame):
     """An lsd_map_frame from (mapResol, mapOriX, mapOriY), from a map_param (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) or from an
     lsd_map_frame; LsdError(LSD_ERR_INVALID) for a resolution that is not finite and > 0 or an origin that is not finite."""
@@ -996,7 +1101,7 @@ def _occupancy_grid(d_grid, cols, rows, device):
 class GridMapper:
     """Mapping with known poses: localised scans integrated into an occupancy grid on the device (k_gridmap.hip; include/lsd_hip.h,
     "mapping with known poses").  The reference has no counterpart -- its maps come from an outside SLAM --, and this is
-    no SLAM either: no scan matching against the growing grid, no loop closure.  The mapper owns two planes of rows x cols counters
+    no full SLAM either: no loop closure; a pose is entered as it is unless the match_* methods below correct it first.  The mapper owns two planes of rows x cols counters
     (torch tensors: uint32 values in int32 storage): `pass`, the beams that crossed a cell, and `hit`, those that ended in it.  A scan at
     pose (x, y in pixels of THIS grid, ang in degrees) adds one ray per beam, cut at range_max (metres; a cut beam passes and does not
     hit); publish_device() turns the planes into the int8 OccupancyGrid (-1 below min_pass passes, 100 where hit / pass >= occ[0] /
@@ -1017,6 +1122,7 @@ class GridMapper:
         if self.occ_den == 0 or self.occ_num > self.occ_den:
             raise LsdError(LSD_ERR_INVALID, "occ = (num, den) with den > 0 and num <= den")
         self._planes = torch.zeros((2, self.rows * self.cols), dtype=torch.int32, device="cuda:%d" % int(self.ctx.device))
+        self._corr = torch.zeros((self.rows, self.cols), dtype=torch.uint8, device=self._planes.device)     # likelihood_device's plane
 
     @property
     def map_param(self):
@@ -1081,6 +1187,81 @@ class GridMapper:
         self.ctx.enqueue_grid_publish_device(self.d_pass, self.d_hit, self.rows * self.cols, grid.data_ptr(), self.min_pass, self.occ_num,
                                              self.occ_den, ts.cuda_stream)
         return grid
+
+    # -- correlative scan-to-grid matching (k_gridmatch.hip) --
+    @property
+    def d_corr(self):
+        return self._corr.data_ptr()
+
+    def likelihood_device(self, smear=None, stream=None):
+        """Refreshes the mapper's lookup plane from its counters, on `stream` (default: the current one): every occupied cell (what
+        publish_device gives 100) smeared by `smear` (default: grid_smear_default(1.0, 3)).  Returns the plane, a CUDA uint8 tensor
+        [rows, cols] the mapper owns."""
+        self.ctx.enqueue_grid_likelihood_device(self.d_pass, self.d_hit, self.cols, self.rows, self.d_corr, self.min_pass, self.occ_num,
+                                                self.occ_den, smear, _cuda_stream(stream).cuda_stream)
+        return self._corr
+
+    def _enqueue_match(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts):
+        """n records (a new CUDA uint8 tensor [n, 56]) of the scans at device addresses, matched on the mapper's plane on the stream ts."""
+        import torch
+        with torch.cuda.stream(ts):
+            rec = torch.empty((n, GRID_MATCH_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+        ctx.enqueue_grid_match_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, self.d_corr, search,
+                                      rec.data_ptr(), ts.cuda_stream)
+        return rec
+
+    def _checked(self, d_scans, d_lens, d_poses, pose_pitch):
+        import torch
+        for name, t, dt in (("d_scans", d_scans, torch.float64), ("d_lens", d_lens, torch.int32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise LsdError(LSD_ERR_INVALID, "%s must be a contiguous CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
+        if not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous():
+            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor")
+        n, pitch = d_lens.numel(), int(pose_pitch)
+        if d_scans.dim() != 3 or d_scans.shape[0] != n or d_scans.shape[2] != 2 or d_scans.shape[1] < 1:
+            raise LsdError(LSD_ERR_INVALID, "d_scans must be [n, stride >= 1, 2] with one length per scan")
+        if pitch < 24 or (n and d_poses.numel() * d_poses.element_size() < (n - 1) * pitch + 24):
+            raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
+        return n, pitch
+
+    def match_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None):
+        """Matches scans that are on the device (the arguments of integrate_device) on the plane likelihood_device wrote last, over the
+        window `search` (grid_search(); None: its defaults).  Returns the records: a CUDA uint8 tensor [n, 56] (GRID_MATCH_DTYPE), whose
+        heads are the corrected poses -- integrate_device(d_scans, d_lens, records, 56) enters the scans there.  On `stream`."""
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
+        rec = self._enqueue_match(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
+                                  _cuda_stream(stream))
+        self._held_match = (d_scans, d_lens, d_poses)
+        return rec
+
+    def match(self, scans, lens, poses, search=None):
+        """match_device for host arrays (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]); returns the records as a numpy
+        array of GRID_MATCH_DTYPE: a read-back, which waits for the device."""
+        import torch
+        sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
+        dev = self._planes.device
+        rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search)
+        return rec.cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy()
+
+    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts):
+        if refresh:
+            self.likelihood_device(smear, ts)
+        rec = self._enqueue_match(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts)
+        self._enqueue(ctx, d_scans, d_lens, n, stride, rec.data_ptr(), GRID_MATCH_DTYPE.itemsize, ts.cuda_stream)
+        self._held_rec = rec                                                 # the integration reads it: alive until the next one
+        return rec
+
+    def match_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, refresh=True, smear=None):
+        """In stream order: likelihood_device(smear) (refresh=False: the plane as it is), match_device, then integrate_device at the records
+        (pitch 56).  All scans of one call are matched against the plane as it was before the call.  Returns the records."""
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
+        rec = self._match_and_integrate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
+                                        refresh, smear, _cuda_stream(stream))
+        self._held_match = (d_scans, d_lens, d_poses)
+        return rec
 
     def counts(self):
         """(pass, hit) as numpy uint32 [rows, cols]: a read-back, which waits for the device."""
@@ -1660,6 +1841,19 @@ class Localizer(_Ticks):
         staging.  The poses are in pixels of the map the tick localised on: the mapper's mapResol / mapOriX / mapOriY are that map's.
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
+
+    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None):
+        """integrate_last_tick with the correlative match in front (GridMapper.match_and_integrate_device): on the last
+        tick's stream and behind the tick, the mapper's lookup plane is refreshed (refresh=False: kept as it is), every frame of the tick is
+        matched on it around the state it produced (pitch 720), and integrated at the record's pose.  Nothing is read back and nothing
+        waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 56] (GRID_MATCH_DTYPE; slot s * k + t is frame t of robot s)."""
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        S, k, ts, _ = self._last_tick
+        return mapper._match_and_integrate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
+                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts)
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current

@@ -97,6 +97,7 @@ struct lsd_ctx {
     // stream synchronisation, so no two are live at once), and the per-sequence workspace of the device FeatureAssociation (k_fa.hip)
     DevBuf<uint8_t> stage;
     DevBuf<uint8_t> fa_buf;
+    DevBuf<uint8_t> gm_slots;                           // lsd_enqueue_grid_match_device: the per-(scan, angle) slots between its two kernels
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
     // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first
     // LSD_MAX_MAPS of each belong to FeatureScan's entry, the rest to the two loops, so neither call disturbs the other's
@@ -1124,6 +1125,78 @@ int lsd_grid_integrate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int 
     if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
     HIPCHK(c, hipMemcpyAsync(pass, d_pa, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(hit, d_hi, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- correlative scan-to-grid matching (k_gridmatch.hip) ---
+int lsd_grid_smear_default(double sigma_cells, int radius, lsd_grid_smear* out) {
+    if (!out || radius < 0 || radius > 7 || !(sigma_cells > 0) || !std::isfinite(sigma_cells)) return LSD_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->radius = radius;
+    for (int v = 0; v <= radius; v++)
+        for (int u = 0; u <= radius; u++) out->w[v][u] = (uint8_t)floor(255 * exp(-(double)(u * u + v * v) / (2 * sigma_cells * sigma_cells)) + 0.5);
+    return LSD_OK;
+}
+
+int lsd_enqueue_grid_likelihood_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, int cols, int rows, uint32_t min_pass,
+                                       uint32_t occ_num, uint32_t occ_den, lsd_grid_smear smear, uint8_t* d_corr, void* stream) {
+    if (!c || !d_pass || !d_hit || !d_corr || cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535) return LSD_ERR_INVALID;
+    if (smear.radius < 0 || smear.radius > 7 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_likelihood(d_pass, d_hit, cols, rows, min_pass, occ_num, occ_den, smear, d_corr, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+// what both match entries refuse about the search
+static bool grid_search_bad(const lsd_grid_search& se) {
+    if (se.wx < 0 || se.wx > 63 || se.wy < 0 || se.wy > 63 || se.na < 0 || se.na > 63) return true;
+    if (!std::isfinite(se.ang_step) || se.ang_step < 0 || (se.ang_step == 0 && se.na > 0)) return true;
+    return se.min_den == 0 || se.min_num > se.min_den;
+}
+
+int lsd_enqueue_grid_match_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                  size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, lsd_grid_search se,
+                                  lsd_grid_match_rec* d_out, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_poses || !d_corr || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se))
+        return LSD_ERR_INVALID;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
+        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_out)) & 7)) {
+        c->err = "grid match: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses and d_out 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->gm_slots.reserve(grid_match_slot_bytes(n_scans, se.na)));   // (grown: one synchronisation; else nothing happens)
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_match(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr, se,
+                      c->gm_slots.get(), d_out, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_grid_match(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                   double range_max, const uint8_t* corr, lsd_grid_search se, lsd_grid_match_rec* out) {
+    if (!c || !scans || !lens || !poses || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se))
+        return LSD_ERR_INVALID;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t* d_co; lsd_grid_match_rec* d_out;
+    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_co, cells); k(d_out, ns); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }

@@ -175,6 +175,14 @@ void launch_grid_integrate(const lsd_polar* scans, const int* lens, int n_scans,
                            int rows, double resol, double range_max, uint32_t* pass, uint32_t* hit, hipStream_t s);
 void launch_grid_publish(const uint32_t* pass, const uint32_t* hit, size_t n_cells, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,
                          int8_t* grid, hipStream_t s);
+// correlative scan-to-grid matching (k_gridmatch.hip): the lookup plane of a pair of counter planes; and n_scans scans matched on it around
+// their poses, through `slots` (grid_match_slot_bytes(n_scans, na) bytes of workspace) into n_scans records
+void launch_grid_likelihood(const uint32_t* pass, const uint32_t* hit, int cols, int rows, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,
+                            const lsd_grid_smear& smear, uint8_t* corr, hipStream_t s);
+size_t grid_match_slot_bytes(int n_scans, int na);
+void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
+                       double resol, double range_max, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out,
+                       hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
