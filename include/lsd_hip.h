@@ -535,8 +535,8 @@ int lsd_grid_integrate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, in
  * its plain, single-resolution form.  The planes are turned into a uint8 lookup plane (every occupied cell smeared by a small table), and
  * each scan's rounded end cells are translated over a window of whole cells and whole angle steps around its pose and summed on that
  * plane.  The result is made of integers and has no iteration order: tests/grid_match_cases.py restates both rules and the device gives
- * the same bytes.  NOT built: a coarse-to-fine (multi-resolution) search, sub-cell refinement, a covariance of the response, loop
- * closure, the fleet classes.
+ * the same bytes.  The same match as a coarse-to-fine search: the section after this one.  NOT built: sub-cell refinement, a covariance
+ * of the response, loop closure, the fleet classes.
  * lsd_enqueue_grid_likelihood_device: a cell is OCCUPIED iff the publish rule gives it 100 (d_pass >= min_pass and (uint64) d_hit *
  * occ_den >= (uint64) d_pass * occ_num);  d_corr[y][x] = the maximum of smear.w[|v|][|u|] over all |u|, |v| <= smear.radius for which
  * (x + u, y + v) is inside the grid and occupied, 0 if there is none (a maximum has no order: the table need not be monotone).  One
@@ -583,6 +583,42 @@ int lsd_enqueue_grid_match_device(lsd_ctx *ctx, const lsd_polar *d_scans, const 
  * staging, lsd_enqueue_grid_match_device runs, the n_scans records come back.  Blocking.  lens[i] outside 0..stride: LSD_ERR_INVALID. */
 int lsd_grid_match(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
                    lsd_map_param map_param, double range_max, const uint8_t *corr, lsd_grid_search search, lsd_grid_match_rec *out);
+
+/* --- the same match, coarse to fine: a plane of block maxima prunes the window, the records stay the plain entry's byte for byte ---- */
+/* Olson's multi-resolution form in two levels (csrc/k_gridmatch_mr.hip; restated in tests/grid_match_mr_cases.py).  The
+ * angle axis is not coarsened.  For a block size b = `block` in 2..16:
+ *   the coarse plane: (rows + b - 1) x (cols + b - 1) bytes, coarse[y + b - 1][x + b - 1] = the maximum of d_corr[y + v][x + u] over
+ *   0 <= u, v < b with (x + u, y + v) inside the grid, 0 if there is none, for x = -(b - 1) .. cols - 1 and y likewise: a sliding maximum
+ *   anchored at the block's low corner, at full resolution (the block grid of a search is anchored at -wx, not at the plane)
+ *   blocks: nbx = ceil((2 wx + 1) / b), nby likewise; block (a, J, I) covers i = -wx + I b .. min(wx, -wx + I b + b - 1), j likewise
+ *   U(a, J, I) = the sum over the beams scored at a of coarse[ey - wy + J b + b - 1][ex - wx + I b + b - 1], 0 where that index is outside
+ *   the coarse plane: S <= U for every candidate of the block
+ *   the seed of angle a: the block with the largest U(a, ., .), among equals the smallest J nbx + I; L_a = the largest S among the seed's
+ *   candidates inside the window; L = the maximum of L_a over the angles
+ *   every block with U >= L is REFINED: its candidates inside the window are scored and enter the plain entry's key maximum.  The plain
+ *   winner's block has U >= S_win >= L, so it is among them: all 56 bytes of the record are lsd_enqueue_grid_match_device's
+ *   score_prior = S(0, 0, 0) and nb(a) are computed whatever is pruned
+ *   statistics (d_stats, may be NULL; 16 bytes per scan): blocks = (2 na + 1) nbx nby; refined = the blocks with U >= L; fine = the
+ *   candidates inside the window in refined blocks (the seeds' own evaluation is not counted); lower_bound = L; a skipped scan: all 0
+ * lsd_enqueue_grid_coarse_device: one launch, no workspace, asynchronous.  LSD_ERR_INVALID before anything is enqueued: a null pointer,
+ * cols or rows outside 1..65535, block outside 2..16.  lsd_grid_coarse_bytes: the plane's size, 0 for arguments the entry refuses.
+ * lsd_enqueue_grid_match_mr_device: d_coarse is what lsd_enqueue_grid_coarse_device made of d_corr with the same `block`.  Three launches
+ * (four with d_stats), asynchronous on `stream`; U (4 bytes per block and angle) and 40 bytes per (scan, angle) are context workspace,
+ * grown before the first launch when needed -- that case alone synchronises; there is no other allocation, copy or host wait.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: whatever lsd_enqueue_grid_match_device refuses, block outside 2..16,
+ * d_coarse null, d_stats not 4-byte aligned.  n_scans == 0 launches nothing. */
+typedef struct lsd_grid_match_mr_stats { uint32_t blocks, refined, fine, lower_bound; } lsd_grid_match_mr_stats;
+size_t lsd_grid_coarse_bytes(int cols, int rows, int block);
+int lsd_enqueue_grid_coarse_device(lsd_ctx *ctx, const uint8_t *d_corr, int cols, int rows, int block, uint8_t *d_coarse, void *stream);
+int lsd_enqueue_grid_match_mr_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                     const void *d_poses, size_t pose_pitch_bytes, lsd_map_param map_param, double range_max,
+                                     const uint8_t *d_corr, const uint8_t *d_coarse, int block, lsd_grid_search search,
+                                     lsd_grid_match_rec *d_out, lsd_grid_match_mr_stats *d_stats, void *stream);
+/* Host convenience: as lsd_grid_match; the coarse plane is built in the context's staging, `stats` (n_scans records) may be NULL.
+ * Blocking. */
+int lsd_grid_match_mr(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
+                      lsd_map_param map_param, double range_max, const uint8_t *corr, int block, lsd_grid_search search,
+                      lsd_grid_match_rec *out, lsd_grid_match_mr_stats *stats);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

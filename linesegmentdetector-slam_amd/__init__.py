@@ -97,6 +97,8 @@ GRID_MATCH_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", 
                              ("da", "i4"), ("flags", "u4"), ("score_prior", "u4"), ("reserved", "u4")])
 assert GRID_MATCH_DTYPE.itemsize == 56 == C.sizeof(lsd_grid_match) and C.sizeof(lsd_grid_smear) == 68 and C.sizeof(lsd_grid_search) == 40
 GRID_MATCH_ACCEPTED, GRID_MATCH_SKIPPED = 1, 2
+GRID_MATCH_MR_STATS_DTYPE = np.dtype([("blocks", "u4"), ("refined", "u4"), ("fine", "u4"), ("lower_bound", "u4")])   # lsd_grid_match_mr_stats
+assert GRID_MATCH_MR_STATS_DTYPE.itemsize == 16
 SCORE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "f8")])   # lsd_match_score
 
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
@@ -201,6 +203,10 @@ _ABI = {
     "lsd_grid_smear_default": (_i, [_dbl, _i, C.POINTER(lsd_grid_smear)]),
     "lsd_enqueue_grid_match_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, lsd_grid_search, _vp, _vp]),
     "lsd_grid_match": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, lsd_grid_search, _vp]),
+    "lsd_grid_coarse_bytes": (_sz, [_i, _i, _i]),
+    "lsd_enqueue_grid_coarse_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "lsd_enqueue_grid_match_mr_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, _vp, _i, lsd_grid_search, _vp, _vp, _vp]),
+    "lsd_grid_match_mr": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, _i, lsd_grid_search, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -690,6 +696,38 @@ class Context:
                                         co.ctypes.data, grid_search(search), out.ctypes.data))
         return out
 
+    # -- the same match, coarse to fine (k_gridmatch_mr.hip) -------------------------
+    def enqueue_grid_coarse_device(self, d_corr, cols, rows, block, d_coarse, stream=None):
+        """lsd_enqueue_grid_coarse_device on device addresses: d_coarse (uint8, (rows + block - 1) x (cols + block - 1)) = the maximum of
+        d_corr over the block x block cells from (x - block + 1, y - block + 1) up, cells outside the grid as 0; asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_coarse_device(self.h, d_corr, int(cols), int(rows), int(block), d_coarse, stream))
+
+    def enqueue_grid_match_mr_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, map_param, range_max, d_corr, d_coarse, block,
+                                     search, d_out, d_stats=None, stream=None):
+        """lsd_enqueue_grid_match_mr_device on device addresses: enqueue_grid_match_device's records, found by a coarse-to-fine search over
+        blocks of block x block translations; d_coarse is what enqueue_grid_coarse_device made of d_corr with the same block; d_stats (or
+        None) receives n_scans records of 16 bytes (GRID_MATCH_MR_STATS_DTYPE); asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_match_mr_device(self.h, d_scans, d_lens, int(n_scans), int(stride), d_poses, int(pose_pitch),
+                                                                 _map_param(map_param), float(range_max), d_corr, d_coarse, int(block),
+                                                                 grid_search(search), d_out, d_stats, stream))
+
+    def grid_match_mr(self, scans, lens, poses, map_param, range_max, corr, block, search, stats=False):
+        """lsd_grid_match_mr from host arrays (those of grid_match): the n records, and with stats=True (records, the n statistics records as
+        a numpy array of GRID_MATCH_MR_STATS_DTYPE).  Blocking."""
+        sc = np.ascontiguousarray(scans, np.float64)
+        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        mp = _map_param(map_param)
+        co = np.ascontiguousarray(corr, np.uint8)
+        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], corr uint8 [rows, cols]")
+        out = np.zeros(len(ln), GRID_MATCH_DTYPE)
+        st = np.zeros(len(ln), GRID_MATCH_MR_STATS_DTYPE)
+        self._chk(self.L.lsd_grid_match_mr(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, mp,
+                                           float(range_max), co.ctypes.data, int(block), grid_search(search), out.ctypes.data,
+                                           st.ctypes.data if stats else None))
+        return (out, st) if stats else out
+
     def reserve(self, n, cols, rows):
         self._chk(self.L.lsd_reserve(self.h, n, cols, rows))
 
@@ -1123,6 +1161,7 @@ class GridMapper:
             raise LsdError(LSD_ERR_INVALID, "occ = (num, den) with den > 0 and num <= den")
         self._planes = torch.zeros((2, self.rows * self.cols), dtype=torch.int32, device="cuda:%d" % int(self.ctx.device))
         self._corr = torch.zeros((self.rows, self.cols), dtype=torch.uint8, device=self._planes.device)     # likelihood_device's plane
+        self._coarse = {}                                                    # coarse_device's planes, by block size
 
     @property
     def map_param(self):
@@ -1193,22 +1232,54 @@ class GridMapper:
     def d_corr(self):
         return self._corr.data_ptr()
 
-    def likelihood_device(self, smear=None, stream=None):
+    def likelihood_device(self, smear=None, stream=None, block=0):
         """Refreshes the mapper's lookup plane from its counters, on `stream` (default: the current one): every occupied cell (what
         publish_device gives 100) smeared by `smear` (default: grid_smear_default(1.0, 3)).  Returns the plane, a CUDA uint8 tensor
-        [rows, cols] the mapper owns."""
+        [rows, cols] the mapper owns.  block = 2..16: coarse_device(block) behind it."""
         self.ctx.enqueue_grid_likelihood_device(self.d_pass, self.d_hit, self.cols, self.rows, self.d_corr, self.min_pass, self.occ_num,
                                                 self.occ_den, smear, _cuda_stream(stream).cuda_stream)
+        if block:
+            self.coarse_device(block, stream)
         return self._corr
 
-    def _enqueue_match(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts):
-        """n records (a new CUDA uint8 tensor [n, 56]) of the scans at device addresses, matched on the mapper's plane on the stream ts."""
+    def coarse_device(self, block, stream=None):
+        """Refreshes the plane of block maxima of the lookup plane as it is now (k_gridmatch_mr.hip), on `stream` (default:
+        the current one).  block: 2..16.  Returns the plane, a CUDA uint8 tensor [rows + block - 1, cols + block - 1] the mapper owns (one
+        per block size, allocated at its first use)."""
+        import torch
+        b = int(block)
+        if not 2 <= b <= 16:
+            raise LsdError(LSD_ERR_INVALID, "block must be 2..16")
+        ts = _cuda_stream(stream)
+        if b not in self._coarse:
+            with torch.cuda.stream(ts):
+                self._coarse[b] = torch.zeros((self.rows + b - 1, self.cols + b - 1), dtype=torch.uint8, device=self._planes.device)
+        self.ctx.enqueue_grid_coarse_device(self.d_corr, self.cols, self.rows, b, self._coarse[b].data_ptr(), ts.cuda_stream)
+        return self._coarse[b]
+
+    def _enqueue_match(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts, block=0, stats=False):
+        """n records (a new CUDA uint8 tensor [n, 56]) of the scans at device addresses, matched on the mapper's plane on the stream ts.
+        block: 0 the plain search, 2..16 the coarse-to-fine one on the coarse plane coarse_device(block) wrote last; with stats (records, a
+        new CUDA uint8 tensor [n, 16])."""
         import torch
         with torch.cuda.stream(ts):
             rec = torch.empty((n, GRID_MATCH_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
-        ctx.enqueue_grid_match_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, self.d_corr, search,
-                                      rec.data_ptr(), ts.cuda_stream)
-        return rec
+        if not block:
+            if stats:
+                raise LsdError(LSD_ERR_INVALID, "stats come with block = 2..16")
+            ctx.enqueue_grid_match_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, self.d_corr, search,
+                                          rec.data_ptr(), ts.cuda_stream)
+            return rec
+        b = int(block)
+        if b not in self._coarse:
+            self.coarse_device(b, ts)
+        st = None
+        if stats:
+            with torch.cuda.stream(ts):
+                st = torch.empty((n, GRID_MATCH_MR_STATS_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+        ctx.enqueue_grid_match_mr_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, self.d_corr,
+                                         self._coarse[b].data_ptr(), b, search, rec.data_ptr(), st.data_ptr() if stats else None, ts.cuda_stream)
+        return (rec, st) if stats else rec
 
     def _checked(self, d_scans, d_lens, d_poses, pose_pitch):
         import torch
@@ -1224,17 +1295,20 @@ class GridMapper:
             raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
         return n, pitch
 
-    def match_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None):
+    def match_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, block=0, stats=False):
         """Matches scans that are on the device (the arguments of integrate_device) on the plane likelihood_device wrote last, over the
         window `search` (grid_search(); None: its defaults).  Returns the records: a CUDA uint8 tensor [n, 56] (GRID_MATCH_DTYPE), whose
-        heads are the corrected poses -- integrate_device(d_scans, d_lens, records, 56) enters the scans there.  On `stream`."""
+        heads are the corrected poses -- integrate_device(d_scans, d_lens, records, 56) enters the scans there.  On `stream`.
+        block = 2..16: the same records by the coarse-to-fine search, on the coarse plane of the last coarse_device(block) /
+        likelihood_device(block=block) (made now if there is none yet); then stats=True returns (records, statistics: a CUDA uint8 tensor
+        [n, 16], GRID_MATCH_MR_STATS_DTYPE)."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
         rec = self._enqueue_match(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
-                                  _cuda_stream(stream))
+                                  _cuda_stream(stream), block, stats)
         self._held_match = (d_scans, d_lens, d_poses)
         return rec
 
-    def match(self, scans, lens, poses, search=None):
+    def match(self, scans, lens, poses, search=None, block=0):
         """match_device for host arrays (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]); returns the records as a numpy
         array of GRID_MATCH_DTYPE: a read-back, which waits for the device."""
         import torch
@@ -1243,23 +1317,27 @@ class GridMapper:
         if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
         dev = self._planes.device
-        rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search)
+        rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search, block=block)
         return rec.cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy()
 
-    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts):
+    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts, block=0, stats=False):
         if refresh:
-            self.likelihood_device(smear, ts)
-        rec = self._enqueue_match(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts)
+            self.likelihood_device(smear, ts, block)
+        got = self._enqueue_match(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts, block, stats)
+        rec = got[0] if stats else got
         self._enqueue(ctx, d_scans, d_lens, n, stride, rec.data_ptr(), GRID_MATCH_DTYPE.itemsize, ts.cuda_stream)
         self._held_rec = rec                                                 # the integration reads it: alive until the next one
-        return rec
+        return got
 
-    def match_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, refresh=True, smear=None):
+    def match_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, refresh=True, smear=None, block=0,
+                                   stats=False):
         """In stream order: likelihood_device(smear) (refresh=False: the plane as it is), match_device, then integrate_device at the records
-        (pitch 56).  All scans of one call are matched against the plane as it was before the call.  Returns the records."""
+        (pitch 56).  All scans of one call are matched against the plane as it was before the call.  Returns the records.  block = 2..16:
+        the coarse-to-fine search -- the coarse plane is refreshed whenever the lookup plane is --, and stats=True returns (records,
+        statistics) as match_device does."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
         rec = self._match_and_integrate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
-                                        refresh, smear, _cuda_stream(stream))
+                                        refresh, smear, _cuda_stream(stream), block, stats)
         self._held_match = (d_scans, d_lens, d_poses)
         return rec
 
@@ -1842,18 +1920,19 @@ class Localizer(_Ticks):
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
 
-    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None):
+    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0):
         """integrate_last_tick with the correlative match in front (GridMapper.match_and_integrate_device): on the last
         tick's stream and behind the tick, the mapper's lookup plane is refreshed (refresh=False: kept as it is), every frame of the tick is
         matched on it around the state it produced (pitch 720), and integrated at the record's pose.  Nothing is read back and nothing
-        waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 56] (GRID_MATCH_DTYPE; slot s * k + t is frame t of robot s)."""
+        waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 56] (GRID_MATCH_DTYPE; slot s * k + t is frame t of robot s).
+        block = 2..16: the same records by the coarse-to-fine search."""
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         if not isinstance(mapper, GridMapper):
             raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
         S, k, ts, _ = self._last_tick
         return mapper._match_and_integrate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
-                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts)
+                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts, block)
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current

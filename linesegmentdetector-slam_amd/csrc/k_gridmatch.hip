@@ -26,10 +26,10 @@
 //   k_grid_match        VGPRs 54   SGPRs 86   scratch 0 bytes   LDS 32840 bytes   4 waves / SIMD (the LDS: four workgroups per CU)
 //   k_grid_match_pick   VGPRs 14   SGPRs 36   scratch 0 bytes   LDS     0 bytes   8 waves / SIMD
 //
-// NOT in this file: a coarse-to-fine (multi-resolution) search, sub-cell refinement, a covariance of the response, loop closure, the
-// fleet classes.
+// The key, the slot and phase A live in gridmatch_dev.h, shared with the coarse-to-fine search of k_gridmatch_mr.hip, which ends in this
+// file's k_grid_match_pick.  NOT in either file: sub-cell refinement, a covariance of the response, loop closure, the fleet classes.
 #include "lsd_internal.h"
-#include "match_dev.h"
+#include "gridmatch_dev.h"
 
 namespace lsdhip {
 
@@ -72,35 +72,6 @@ __global__ __launch_bounds__(256) void k_grid_likelihood(const uint32_t* __restr
     corr[(size_t)y * cols + x] = (uint8_t)best;
 }
 
-constexpr int kGmLanes = 256, kGmMaxBeams = LSD_SCAN_MAX_LEN, kBeamBatch = 8;
-constexpr int kGmMaxWin = 63;                                        // wx, wy, na
-// the key's fields: i^2 + j^2 <= 2 * 63^2 = 7938 < 2^13, |a| <= 63 < 2^6, the linear index < 127^3 = 2048383 < 2^21 - 1, S < 2^20
-constexpr int kKeyLinBits = 21, kKeyAngBits = 6, kKeyDistBits = 13;
-constexpr int kKeyAngShift = kKeyLinBits, kKeyDistShift = kKeyLinBits + kKeyAngBits, kKeyScoreShift = kKeyDistShift + kKeyDistBits;
-static_assert(255ll * kGmMaxBeams < (1 << 20) && kKeyScoreShift + 20 <= 64, "the score fits its field");
-static_assert((2 * kGmMaxWin + 1) * (2 * kGmMaxWin + 1) * (2 * kGmMaxWin + 1) < (1 << kKeyLinBits) - 1, "a real key is never 0");
-
-struct GmSlot { unsigned long long key; uint32_t nb, s0; };          // per (scan, angle): the best key, the scored beams, S at (j, i) = (0, 0)
-static_assert(sizeof(GmSlot) == 16, "lsd_ctx.hip sizes the workspace by 16 bytes a slot");
-
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {      // every lane gets the maximum
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = shfl_xor_u64(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// the scan skipped whole: k_grid_integrate's test
-__device__ __forceinline__ bool gm_scan_skipped(double px, double py, double pang) {
-    return !(isfinite(px) && isfinite(py) && isfinite(pang)) || fabs(px + 1) < 1e-4 || fabs(px) > 1048576.0 || fabs(py) > 1048576.0;
-}
-
 __global__ __launch_bounds__(kGmLanes) void k_grid_match(const double2* __restrict__ scans, const int* __restrict__ lens, int stride,
                                                          const uint8_t* __restrict__ poses, size_t pose_pitch, int cols, int rows, double resol,
                                                          double range_max, const uint8_t* __restrict__ corr, int wx, int wy, int na,
@@ -117,40 +88,9 @@ __global__ __launch_bounds__(kGmLanes) void k_grid_match(const double2* __restri
     const int len = min(max(lens[scan], 0), stride);                 // (stride <= kGmMaxBeams: the entry refuses more)
     const double rot0 = deg2rad_ref(pang), rot = deg2rad_ref(pang + (double)a * ang_step);
     const double2* row = scans + (size_t)scan * stride;
-    // A. the end cells of this angle
-    int n_list = 0;
+    // A. the end cells of this angle (gridmatch_dev.h)
     uint32_t nb = 0;
-    for (int base = 0; base < len; base += kGmLanes) {
-        const int i = base + tid;
-        bool keep = false;
-        int ex = 0, ey = 0;
-        if (i < len) {
-            const double2 b = row[i];
-            const double th0 = b.y + rot0, th = b.y + rot;
-            if (b.x > 0 && b.x != (double)INFINITY && isfinite(b.y) && isfinite(th0) && b.x <= range_max && isfinite(th)) {
-                double s, c;
-                sincos_g(th, s, c);
-                ex = cvt_x86(round(px + b.x * c / resol));
-                ey = cvt_x86(round(py + b.x * s / resol));
-                nb++;
-                // |ex|, |ey| < 2^20 + 32768: the sums below cannot wrap
-                keep = ex + wx >= 0 && ex - wx < cols && ey + wy >= 0 && ey - wy < rows;
-            }
-        }
-        const unsigned long long m = __ballot(keep);
-        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (lane == 0) s_cnt[wave] = __builtin_popcountll(m);
-        __syncthreads();
-        int at = n_list, total = 0;
-        for (int w = 0; w < kGmLanes / 64; w++) {
-            const int cnt = s_cnt[w];
-            if (w < wave) at += cnt;
-            total += cnt;
-        }
-        if (keep) s_end[at + below] = make_int2(ex, ey);              // at + below < n_list + total <= base + 256 <= kGmMaxBeams
-        n_list += total;
-        __syncthreads();                                             // the next chunk rewrites s_cnt; B reads s_end
-    }
+    const int n_list = gm_end_cells(row, len, px, py, rot0, rot, resol, range_max, cols, rows, wx, wy, 0, 0, s_end, s_cnt, nb);
     // B. the translations
     const int nx = 2 * wx + 1, ny = 2 * wy + 1, n_tr = nx * ny;
     unsigned long long best = 0;
@@ -160,26 +100,9 @@ __global__ __launch_bounds__(kGmLanes) void k_grid_match(const double2* __restri
         if (t < n_tr) {
             const int jj = t / nx, ii = t - jj * nx;
             const int i = ii - wx, j = jj - wy;
-            uint32_t S = 0;
-            for (int k0 = 0; k0 < n_list; k0 += kBeamBatch) {
-                uint32_t v[kBeamBatch];
-#pragma unroll
-                for (int u = 0; u < kBeamBatch; u++) {
-                    v[u] = 0;
-                    if (k0 + u < n_list) {
-                        const int2 e = s_end[k0 + u];
-                        const int cx = e.x + i, cy = e.y + j;
-                        if (cx >= 0 && cx < cols && cy >= 0 && cy < rows) v[u] = corr[(size_t)cy * cols + cx];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < kBeamBatch; u++) S += v[u];
-            }
+            const uint32_t S = gm_score(s_end, n_list, corr, cols, rows, i, j);
             const uint32_t lin = (uint32_t)((ai * ny + jj) * nx + ii);
-            const unsigned long long key = ((unsigned long long)S << kKeyScoreShift) |
-                                           ((unsigned long long)(((1u << kKeyDistBits) - 1) - (uint32_t)(i * i + j * j)) << kKeyDistShift) |
-                                           ((unsigned long long)(((1u << kKeyAngBits) - 1) - aa) << kKeyAngShift) |
-                                           (unsigned long long)(((1u << kKeyLinBits) - 1) - lin);
+            const unsigned long long key = gm_key(S, i, j, aa, lin);
             best = key > best ? key : best;
             if (i == 0 && j == 0) s_s0 = S;
         }
@@ -257,6 +180,13 @@ void launch_grid_likelihood(const uint32_t* pass, const uint32_t* hit, int cols,
     hipLaunchKernelGGL(k_grid_likelihood, grid, dim3(256), 0, s, pass, hit, cols, rows, min_pass, occ_num, occ_den, smear, corr);
 }
 
+void launch_grid_match_pick(int n_scans, const void* poses, size_t pose_pitch, const lsd_grid_search& se, const void* slots, lsd_grid_match_rec* out,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(k_grid_match_pick, dim3(n_scans), dim3(64), 0, s, static_cast<const uint8_t*>(poses), pose_pitch, se.wx, se.wy, se.na,
+                       se.ang_step, se.min_beams, se.min_num, se.min_den, static_cast<const GmSlot*>(slots),
+                       reinterpret_cast<unsigned long long*>(out));
+}
+
 size_t grid_match_slot_bytes(int n_scans, int na) { return (size_t)n_scans * (2 * na + 1) * sizeof(GmSlot); }
 
 void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
@@ -265,9 +195,7 @@ void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int
     hipLaunchKernelGGL(k_grid_match, dim3(n_scans, 2 * se.na + 1), dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride,
                        static_cast<const uint8_t*>(poses), pose_pitch, cols, rows, resol, range_max, corr, se.wx, se.wy, se.na, se.ang_step,
                        static_cast<GmSlot*>(slots));
-    hipLaunchKernelGGL(k_grid_match_pick, dim3(n_scans), dim3(64), 0, s, static_cast<const uint8_t*>(poses), pose_pitch, se.wx, se.wy, se.na,
-                       se.ang_step, se.min_beams, se.min_num, se.min_den, static_cast<const GmSlot*>(slots),
-                       reinterpret_cast<unsigned long long*>(out));
+    launch_grid_match_pick(n_scans, poses, pose_pitch, se, slots, out, s);
 }
 
 }  // namespace lsdhip

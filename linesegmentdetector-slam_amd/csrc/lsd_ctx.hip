@@ -97,6 +97,7 @@ struct lsd_ctx {
     // stream synchronisation, so no two are live at once), and the per-sequence workspace of the device FeatureAssociation (k_fa.hip)
     DevBuf<uint8_t> stage;
     DevBuf<uint8_t> fa_buf;
+    DevBuf<uint8_t> gm_mr_ws;                           // lsd_enqueue_grid_match_mr_device: U, the coarse slots, the counts and the pick's slots
     DevBuf<uint8_t> gm_slots;                           // lsd_enqueue_grid_match_device: the per-(scan, angle) slots between its two kernels
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
     // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first
@@ -1197,6 +1198,79 @@ int lsd_grid_match(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_sc
     const int st = lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
     if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
     HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- the same match, coarse to fine (k_gridmatch_mr.hip) ---
+size_t lsd_grid_coarse_bytes(int cols, int rows, int block) {
+    if (cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535 || block < 2 || block > 16) return 0;
+    return (size_t)(cols + block - 1) * (rows + block - 1);
+}
+
+int lsd_enqueue_grid_coarse_device(lsd_ctx* c, const uint8_t* d_corr, int cols, int rows, int block, uint8_t* d_coarse, void* stream) {
+    if (!c || !d_corr || !d_coarse || lsd_grid_coarse_bytes(cols, rows, block) == 0) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_coarse(d_corr, cols, rows, block, d_coarse, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_enqueue_grid_match_mr_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                     size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, const uint8_t* d_coarse,
+                                     int block, lsd_grid_search se, lsd_grid_match_rec* d_out, lsd_grid_match_mr_stats* d_stats, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_poses || !d_corr || !d_coarse || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
+        grid_search_bad(se) || block < 2 || block > 16)
+        return LSD_ERR_INVALID;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
+        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_out)) & 7) || (reinterpret_cast<uintptr_t>(d_stats) & 3)) {
+        c->err = "grid match: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses and d_out 8-byte, d_stats 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t bytes[4];
+    grid_match_mr_ws(n_scans, se, block, bytes);
+    uint8_t* r[4];
+    auto regions = [&](Carver& k) { for (int i = 0; i < 4; i++) k(r[i], bytes[i]); };
+    HIPCHK(c, carve(c->gm_mr_ws, regions));                          // (grown: one synchronisation; else nothing but pointer arithmetic)
+    void* const ws[4] = {r[0], r[1], r[2], r[3]};
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_match_mr(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr, d_coarse,
+                         block, se, ws, d_out, d_stats, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_grid_match_mr(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                      double range_max, const uint8_t* corr, int block, lsd_grid_search se, lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats) {
+    if (!c || !scans || !lens || !poses || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se) || block < 2 ||
+        block > 16)
+        return LSD_ERR_INVALID;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t *d_co, *d_cs; lsd_grid_match_rec* d_out; lsd_grid_match_mr_stats* d_st;
+    auto regions = [&](Carver& k) {
+        k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_co, cells); k(d_cs, lsd_grid_coarse_bytes(mp.oriMapCol, mp.oriMapRow, block));
+        k(d_out, ns); k(d_st, ns);
+    };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    int st = lsd_enqueue_grid_coarse_device(c, d_co, mp.oriMapCol, mp.oriMapRow, block, d_cs, c->stream);
+    if (st == LSD_OK)
+        st = lsd_enqueue_grid_match_mr_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, d_cs, block, se, d_out,
+                                              stats ? d_st : nullptr, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_match_mr_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }

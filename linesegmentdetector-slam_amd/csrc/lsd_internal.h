@@ -183,6 +183,16 @@ size_t grid_match_slot_bytes(int n_scans, int na);
 void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
                        double resol, double range_max, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out,
                        hipStream_t s);
+void launch_grid_match_pick(int n_scans, const void* poses, size_t pose_pitch, const lsd_grid_search& se, const void* slots, lsd_grid_match_rec* out,
+                            hipStream_t s);
+// the same match as a coarse-to-fine search (k_gridmatch_mr.hip): the plane of block maxima ((rows + block - 1) x (cols + block - 1)
+// bytes), and the match through four regions of workspace -- U, the coarse slots, the counts, the slots of launch_grid_match_pick --
+// whose sizes grid_match_mr_ws gives; stats may be null
+void launch_grid_coarse(const uint8_t* corr, int cols, int rows, int block, uint8_t* coarse, hipStream_t s);
+void grid_match_mr_ws(int n_scans, const lsd_grid_search& se, int block, size_t bytes[4]);
+void launch_grid_match_mr(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
+                          double resol, double range_max, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se,
+                          void* const ws[4], lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
