@@ -535,8 +535,8 @@ int lsd_grid_integrate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, in
  * its plain, single-resolution form.  The planes are turned into a uint8 lookup plane (every occupied cell smeared by a small table), and
  * each scan's rounded end cells are translated over a window of whole cells and whole angle steps around its pose and summed on that
  * plane.  The result is made of integers and has no iteration order: tests/grid_match_cases.py restates both rules and the device gives
- * the same bytes.  The same match as a coarse-to-fine search: the section after this one.  NOT built: sub-cell refinement, a covariance
- * of the response, loop closure, the fleet classes.
+ * the same bytes.  The same match as a coarse-to-fine search: the section after this one; a sub-cell pose and a covariance of the
+ * response: the one after that.  NOT built: loop closure, the fleet classes.
  * lsd_enqueue_grid_likelihood_device: a cell is OCCUPIED iff the publish rule gives it 100 (d_pass >= min_pass and (uint64) d_hit *
  * occ_den >= (uint64) d_pass * occ_num);  d_corr[y][x] = the maximum of smear.w[|v|][|u|] over all |u|, |v| <= smear.radius for which
  * (x + u, y + v) is inside the grid and occupied, 0 if there is none (a maximum has no order: the table need not be monotone).  One
@@ -619,6 +619,65 @@ int lsd_enqueue_grid_match_mr_device(lsd_ctx *ctx, const lsd_polar *d_scans, con
 int lsd_grid_match_mr(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
                       lsd_map_param map_param, double range_max, const uint8_t *corr, int block, lsd_grid_search search,
                       lsd_grid_match_rec *out, lsd_grid_match_mr_stats *stats);
+
+/* --- the response around a match: a covariance and a sub-cell, sub-step pose from the scores next to the winner ---------------- */
+/* A stage behind either match entry (csrc/k_gridresponse.hip; restated in tests/grid_response_cases.py): it reads the
+ * records a match wrote and writes one response record per scan.  Integer sums until one fp64 division per output; fp64 without FMA.
+ * Inputs per scan: the scan and its length, its ORIGINAL pose (x, y, ang) -- the one the match was given, at d_poses + n *
+ * pose_pitch_bytes --, its lsd_grid_match_rec, the lookup plane, mapResol, range_max and the search's ang_step.
+ *   a scan GETS A RESPONSE iff its record has LSD_GRID_MATCH_ACCEPTED set, LSD_GRID_MATCH_SKIPPED clear and |di|, |dj|, |da| <= 63 (the
+ *   record is caller memory: the range test makes noise harmless).  Otherwise the response record is the match record's 24 pose bytes,
+ *   flags = LSD_GRID_RESPONSE_NONE, every other byte 0, and nothing is scored
+ *   candidates  (a', j', i'), a' in -ra..ra, j' in -ry..ry, i' in -rx..rx, centred on the winner;  theta = ang + (double)(da + a') *
+ *   ang_step (the match's own expression: at a' = 0 the end cells are the winner's).  The scored beams and their end cells (ex, ey) are
+ *   the match's, from the ORIGINAL pose (round(x + di + ..) is not round(x + ..) + di); an original pose the match's scan test skips
+ *   (noise again) scores no beam
+ *   R(a', j', i') = the sum over the beams scored at theta of d_corr[ey + dj + j'][ex + di + i'], 0 outside the grid.  The window may
+ *   leave the search's.  score_centre = R(0, 0, 0); it equals the record's score for an authentic record, else
+ *   LSD_GRID_RESPONSE_MISMATCH is set and the record's score is used as given
+ *   a candidate is USED iff (uint64) R * keep_den >= (uint64) score * keep_num; its weight w is then R, else 0.  n_used counts them.
+ *   m[10] (int64, each < 2^38: exact, no order) = sum w, sum w i', w j', w a', w i'^2, w i'j', w j'^2, w i'a', w j'a', w a'^2
+ *   covariance about the winner (Karto's), with W = m[0] > 0:  cov = { (double) m[4] / (double) W, m[5] / W, m[6] / W  (pixels^2),
+ *   (m[7] / W) * ang_step, (m[8] / W) * ang_step, (m[9] / W) * (ang_step * ang_step) };  W == 0: six zeros and LSD_GRID_RESPONSE_EMPTY
+ *   sub-cell offsets, per axis: m_ and p_ the R one step below and above the centre (the other two offsets 0), c = score_centre, num =
+ *   m_ - p_, den = 2 (m_ - 2 c + p_) in int64.  m_ > c, p_ > c or den >= 0: +0.0 and the axis's NOT_PEAK bit (a plateau, or a winner on
+ *   the rim of the search window with a higher neighbour outside).  Else num == 0: +0.0 (0 / den would be -0.0).  Else (double) num /
+ *   (double) den, within +-0.5.  ra == 0: the angle offset is +0.0 with no flag.  sub = { x, y, a } offsets
+ *   the refined pose: x = rec.x + sub[0], y = rec.y + sub[1], ang = rec.ang + sub[2] * ang_step
+ * The record's head is a pose: an array of them IS a d_poses argument of pitch 192 for lsd_enqueue_grid_integrate_device.
+ * d_volume may be NULL; otherwise it receives n_scans x (2 ra + 1)(2 ry + 1)(2 rx + 1) uint32 values of R, i' fastest, zeros for a scan
+ * without a response (lsd_grid_response_volume_bytes: its size; 0 for arguments the entry refuses).  With NULL the volume is context
+ * workspace, grown before the first launch when needed -- that case alone synchronises; there is no other allocation, copy or host wait.
+ * Two launches, asynchronous on `stream`.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: whatever
+ * lsd_enqueue_grid_match_device refuses on the arguments the two share; rx or ry outside 1..7, ra outside 0..7; keep_den == 0 or
+ * keep_num > keep_den; ang_step not finite or negative, ang_step == 0 with ra > 0; d_records or d_out null or not 8-byte aligned;
+ * d_volume not 4-byte aligned.  n_scans == 0 launches nothing.
+ * (The parameters' type is lsd_grid_response_par: the host entry below has the struct tag's name.) */
+typedef struct lsd_grid_response { int rx, ry, ra; uint32_t keep_num, keep_den; } lsd_grid_response_par;
+typedef struct lsd_grid_response_rec {     /* 192 bytes; its head is a pose, so an array of these IS a d_poses argument (pitch 192) */
+    double x, y, ang;
+    double cov[6];                         /* xx, xy, yy, xa, ya, aa */
+    double sub[3];                         /* x, y, a */
+    int64_t m[10];
+    uint32_t score_centre, n_used, flags, reserved;
+} lsd_grid_response_rec;
+#define LSD_GRID_RESPONSE_VALID 1u
+#define LSD_GRID_RESPONSE_NONE 2u
+#define LSD_GRID_RESPONSE_X_NOT_PEAK 4u
+#define LSD_GRID_RESPONSE_Y_NOT_PEAK 8u
+#define LSD_GRID_RESPONSE_A_NOT_PEAK 16u
+#define LSD_GRID_RESPONSE_EMPTY 32u
+#define LSD_GRID_RESPONSE_MISMATCH 64u
+size_t lsd_grid_response_volume_bytes(int n_scans, lsd_grid_response_par response);
+int lsd_enqueue_grid_response_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                     const void *d_poses, size_t pose_pitch_bytes, const lsd_grid_match_rec *d_records,
+                                     lsd_map_param map_param, double range_max, const uint8_t *d_corr, double ang_step,
+                                     lsd_grid_response_par response, lsd_grid_response_rec *d_out, uint32_t *d_volume, void *stream);
+/* Host convenience: as lsd_grid_match, with the n_scans match records; `volume` (lsd_grid_response_volume_bytes bytes) may be NULL.
+ * Blocking. */
+int lsd_grid_response(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
+                      const lsd_grid_match_rec *records, lsd_map_param map_param, double range_max, const uint8_t *corr,
+                      double ang_step, lsd_grid_response_par response, lsd_grid_response_rec *out, uint32_t *volume);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

@@ -99,6 +99,23 @@ assert GRID_MATCH_DTYPE.itemsize == 56 == C.sizeof(lsd_grid_match) and C.sizeof(
 GRID_MATCH_ACCEPTED, GRID_MATCH_SKIPPED = 1, 2
 GRID_MATCH_MR_STATS_DTYPE = np.dtype([("blocks", "u4"), ("refined", "u4"), ("fine", "u4"), ("lower_bound", "u4")])   # lsd_grid_match_mr_stats
 assert GRID_MATCH_MR_STATS_DTYPE.itemsize == 16
+
+
+# the response around a match (include/lsd_hip.h): its parameters (the C side's lsd_grid_response_par) and its record
+class lsd_grid_response(C.Structure):
+    _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("ra", C.c_int), ("keep_num", C.c_uint32), ("keep_den", C.c_uint32)]
+
+
+class lsd_grid_response_rec(C.Structure):
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("ang", C.c_double), ("cov", C.c_double * 6), ("sub", C.c_double * 3),
+                ("m", C.c_int64 * 10), ("score_centre", C.c_uint32), ("n_used", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+GRID_RESPONSE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("cov", "f8", (6,)), ("sub", "f8", (3,)), ("m", "i8", (10,)),
+                                ("score_centre", "u4"), ("n_used", "u4"), ("flags", "u4"), ("reserved", "u4")])
+assert GRID_RESPONSE_DTYPE.itemsize == 192 == C.sizeof(lsd_grid_response_rec) and C.sizeof(lsd_grid_response) == 20
+(GRID_RESPONSE_VALID, GRID_RESPONSE_NONE, GRID_RESPONSE_X_NOT_PEAK, GRID_RESPONSE_Y_NOT_PEAK, GRID_RESPONSE_A_NOT_PEAK, GRID_RESPONSE_EMPTY,
+ GRID_RESPONSE_MISMATCH) = 1, 2, 4, 8, 16, 32, 64
 SCORE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "f8")])   # lsd_match_score
 
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
@@ -207,6 +224,10 @@ _ABI = {
     "lsd_enqueue_grid_coarse_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "lsd_enqueue_grid_match_mr_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, _vp, _i, lsd_grid_search, _vp, _vp, _vp]),
     "lsd_grid_match_mr": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, _i, lsd_grid_search, _vp, _vp]),
+    "lsd_grid_response_volume_bytes": (_sz, [_i, lsd_grid_response]),
+    "lsd_enqueue_grid_response_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, lsd_map_param, _dbl, _vp, _dbl, lsd_grid_response, _vp, _vp,
+                                              _vp]),
+    "lsd_grid_response": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, lsd_map_param, _dbl, _vp, _dbl, lsd_grid_response, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -728,6 +749,38 @@ class Context:
                                            st.ctypes.data if stats else None))
         return (out, st) if stats else out
 
+    # -- the response around a match (k_gridresponse.hip) -----------------------------
+    def enqueue_grid_response_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, d_records, map_param, range_max, d_corr,
+                                     ang_step, response, d_out, d_volume=None, stream=None):
+        """lsd_enqueue_grid_response_device on device addresses: the scans, lengths and ORIGINAL poses a match entry was given, and the
+        n_scans records (56 bytes each) it wrote; ang_step is the search's; response: an lsd_grid_response or what grid_response() takes.
+        d_out receives n_scans records of 192 bytes (GRID_RESPONSE_DTYPE), which are a d_poses argument of pitch 192 themselves; d_volume
+        (or None) the n_scans x (2 ra + 1)(2 ry + 1)(2 rx + 1) uint32 scores; asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_response_device(self.h, d_scans, d_lens, int(n_scans), int(stride), d_poses, int(pose_pitch),
+                                                                 d_records, _map_param(map_param), float(range_max), d_corr, float(ang_step),
+                                                                 grid_response(response), d_out, d_volume, stream))
+
+    def grid_response(self, scans, lens, poses, records, map_param, range_max, corr, ang_step, response=None, volume=False):
+        """lsd_grid_response from host arrays (those of grid_match, and its records as a numpy array of GRID_MATCH_DTYPE): the n response
+        records as a numpy array of GRID_RESPONSE_DTYPE, and with volume=True (records, the scores: uint32 [n, 2 ra + 1, 2 ry + 1,
+        2 rx + 1]).  Blocking."""
+        sc = np.ascontiguousarray(scans, np.float64)
+        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        rec = np.ascontiguousarray(records)
+        mp = _map_param(map_param)
+        co = np.ascontiguousarray(corr, np.uint8)
+        if (sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol) or
+                rec.dtype != GRID_MATCH_DTYPE or rec.shape != (len(ln),)):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], records GRID_MATCH_DTYPE [n], corr uint8 [rows, cols]")
+        rp = grid_response(response)
+        out = np.zeros(len(ln), GRID_RESPONSE_DTYPE)
+        vol = np.zeros((len(ln), 2 * rp.ra + 1, 2 * rp.ry + 1, 2 * rp.rx + 1) if volume else (0,), np.uint32)
+        self._chk(self.L.lsd_grid_response(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, rec.ctypes.data,
+                                           mp, float(range_max), co.ctypes.data, float(ang_step), rp, out.ctypes.data,
+                                           vol.ctypes.data if volume else None))
+        return (out, vol) if volume else out
+
     def reserve(self, n, cols, rows):
         self._chk(self.L.lsd_reserve(self.h, n, cols, rows))
 
@@ -1015,6 +1068,24 @@ def grid_search(search=None, **kw):
     return lsd_grid_search(int(wx), int(wy), int(na), float(step), mb, mn, md)
 
 
+def grid_response(response=None, rx=3, ry=3, ra=1, keep=(1, 2)):
+    """An lsd_grid_response: `response` itself, a dict of rx / ry / ra / keep (or keep_num, keep_den), a tuple (rx, ry, ra, keep_num,
+    keep_den), or keywords.  The neighbourhood is +-rx, +-ry cells and +-ra angle steps around the winner; a candidate enters the
+    covariance iff its score is at least keep[0] / keep[1] of the winner's."""
+    if isinstance(response, lsd_grid_response):
+        return response
+    if isinstance(response, dict):
+        a = dict(response)
+        if "keep" in a:
+            a["keep_num"], a["keep_den"] = a.pop("keep")
+        response = (a.get("rx", rx), a.get("ry", ry), a.get("ra", ra), a.get("keep_num", keep[0]), a.get("keep_den", keep[1]))
+    if response is None or response is True:
+        response = (rx, ry, ra, keep[0], keep[1])
+    rx, ry, ra, kn, kd = response
+    kn, kd = _u32s(kn, kd, limit=(1 << 32,) * 2)
+    return lsd_grid_response(int(rx), int(ry), int(ra), kn, kd)
+
+
 def map_frame(frame):
     """An lsd_map_frame from (mapResol, mapOriX, mapOriY), from a map_param (oriMapCol, oriMapRow, mapResol, mapOriX, mapOriY) or from an
     lsd_map_frame; LsdError(LSD_ERR_INVALID) for a resolution that is not finite and > 0 or an origin that is not finite."""
@@ -1295,49 +1366,100 @@ class GridMapper:
             raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
         return n, pitch
 
-    def match_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, block=0, stats=False):
+    def _enqueue_response(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, d_records, search, response, ts, volume=False):
+        """n response records (a new CUDA uint8 tensor [n, 192]) of the scans at device addresses, from the match records at d_records and
+        the ORIGINAL poses at d_poses, on the mapper's plane on the stream ts; ang_step is `search`'s.  With volume (records, the scores: a
+        new CUDA int32 tensor [n, 2 ra + 1, 2 ry + 1, 2 rx + 1] holding uint32 values)."""
+        import torch
+        rp, se = grid_response(response), grid_search(search)
+        with torch.cuda.stream(ts):
+            out = torch.empty((n, GRID_RESPONSE_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+            vol = torch.empty((n, 2 * rp.ra + 1, 2 * rp.ry + 1, 2 * rp.rx + 1), dtype=torch.int32, device=self._planes.device) if volume else None
+        ctx.enqueue_grid_response_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, d_records, self.map_param, self.range_max, self.d_corr,
+                                         se.ang_step, rp, out.data_ptr(), vol.data_ptr() if volume else None, ts.cuda_stream)
+        return (out, vol) if volume else out
+
+    def response_device(self, d_scans, d_lens, d_poses, d_records, pose_pitch=24, search=None, response=None, stream=None, volume=False):
+        """The response around a match (k_gridresponse.hip): for the scans and the ORIGINAL poses match_device was given
+        and the records it returned (either search wrote them), the scores in the neighbourhood `response` (grid_response(); None: its
+        defaults) of each winner, on the plane likelihood_device wrote last; `search` is the match's (its ang_step is read).  Returns the
+        response records: a CUDA uint8 tensor [n, 192] (GRID_RESPONSE_DTYPE) whose heads are the refined poses --
+        integrate_device(d_scans, d_lens, responses, 192) enters the scans there --, with a covariance, the sub-cell offsets and the integer
+        moments behind them.  volume=True: (records, the scores).  On `stream`; nothing waits."""
+        import torch
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
+        if (not isinstance(d_records, torch.Tensor) or not d_records.is_cuda or not d_records.is_contiguous() or
+                d_records.numel() * d_records.element_size() < n * GRID_MATCH_DTYPE.itemsize):
+            raise LsdError(LSD_ERR_INVALID, "d_records must be a contiguous CUDA tensor of n records of 56 bytes")
+        got = self._enqueue_response(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
+                                     d_records.data_ptr(), search, response, _cuda_stream(stream), volume)
+        self._held_response = (d_scans, d_lens, d_poses, d_records)
+        return got
+
+    def match_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, block=0, stats=False, response=None):
         """Matches scans that are on the device (the arguments of integrate_device) on the plane likelihood_device wrote last, over the
         window `search` (grid_search(); None: its defaults).  Returns the records: a CUDA uint8 tensor [n, 56] (GRID_MATCH_DTYPE), whose
         heads are the corrected poses -- integrate_device(d_scans, d_lens, records, 56) enters the scans there.  On `stream`.
         block = 2..16: the same records by the coarse-to-fine search, on the coarse plane of the last coarse_device(block) /
         likelihood_device(block=block) (made now if there is none yet); then stats=True returns (records, statistics: a CUDA uint8 tensor
-        [n, 16], GRID_MATCH_MR_STATS_DTYPE)."""
+        [n, 16], GRID_MATCH_MR_STATS_DTYPE).  response (grid_response(); True: its defaults) given: response_device behind the match, and
+        its records are returned beside what is returned without it."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
-        rec = self._enqueue_match(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
-                                  _cuda_stream(stream), block, stats)
-        self._held_match = (d_scans, d_lens, d_poses)
-        return rec
+        ts = _cuda_stream(stream)
+        got = self._enqueue_match(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search, ts,
+                                  block, stats)
+        if response is not None:
+            rec = got[0] if stats else got
+            resp = self._enqueue_response(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
+                                          rec.data_ptr(), search, response, ts)
+            got = got + (resp,) if stats else (got, resp)
+        self._held_match = (d_scans, d_lens, d_poses, got)
+        return got
 
-    def match(self, scans, lens, poses, search=None, block=0):
+    def match(self, scans, lens, poses, search=None, block=0, response=None):
         """match_device for host arrays (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]); returns the records as a numpy
-        array of GRID_MATCH_DTYPE: a read-back, which waits for the device."""
+        array of GRID_MATCH_DTYPE: a read-back, which waits for the device.  response given: (records, the response records as a numpy
+        array of GRID_RESPONSE_DTYPE)."""
         import torch
         sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
         po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
         if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
         dev = self._planes.device
-        rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search, block=block)
-        return rec.cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy()
+        rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search, block=block,
+                                response=response)
+        if response is None:
+            return rec.cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy()
+        return (rec[0].cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy(), rec[1].cpu().numpy().reshape(-1).view(GRID_RESPONSE_DTYPE).copy())
 
-    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts, block=0, stats=False):
+    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts, block=0, stats=False,
+                             response=None, integrate_at="match"):
+        if integrate_at not in ("match", "response") or (integrate_at == "response" and response is None):
+            raise LsdError(LSD_ERR_INVALID, "integrate_at is 'match' or, with response given, 'response'")
         if refresh:
             self.likelihood_device(smear, ts, block)
         got = self._enqueue_match(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts, block, stats)
         rec = got[0] if stats else got
-        self._enqueue(ctx, d_scans, d_lens, n, stride, rec.data_ptr(), GRID_MATCH_DTYPE.itemsize, ts.cuda_stream)
-        self._held_rec = rec                                                 # the integration reads it: alive until the next one
+        at, pitch = rec, GRID_MATCH_DTYPE.itemsize
+        if response is not None:
+            resp = self._enqueue_response(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, rec.data_ptr(), search, response, ts)
+            got = got + (resp,) if stats else (got, resp)
+            if integrate_at == "response":
+                at, pitch = resp, GRID_RESPONSE_DTYPE.itemsize
+        self._enqueue(ctx, d_scans, d_lens, n, stride, at.data_ptr(), pitch, ts.cuda_stream)
+        self._held_rec = got                                                 # the integration reads it: alive until the next one
         return got
 
     def match_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, refresh=True, smear=None, block=0,
-                                   stats=False):
+                                   stats=False, response=None, integrate_at="match"):
         """In stream order: likelihood_device(smear) (refresh=False: the plane as it is), match_device, then integrate_device at the records
         (pitch 56).  All scans of one call are matched against the plane as it was before the call.  Returns the records.  block = 2..16:
         the coarse-to-fine search -- the coarse plane is refreshed whenever the lookup plane is --, and stats=True returns (records,
-        statistics) as match_device does."""
+        statistics) as match_device does.  response given: response_device behind the match, its records returned beside the others; then
+        integrate_at="response" integrates at the refined poses (pitch 192) instead of the records' ("match", the default)."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
         rec = self._match_and_integrate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
-                                        refresh, smear, _cuda_stream(stream), block, stats)
+                                        refresh, smear, _cuda_stream(stream), block, stats, response, integrate_at)
         self._held_match = (d_scans, d_lens, d_poses)
         return rec
 
@@ -1920,19 +2042,21 @@ class Localizer(_Ticks):
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
 
-    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0):
+    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match"):
         """integrate_last_tick with the correlative match in front (GridMapper.match_and_integrate_device): on the last
         tick's stream and behind the tick, the mapper's lookup plane is refreshed (refresh=False: kept as it is), every frame of the tick is
         matched on it around the state it produced (pitch 720), and integrated at the record's pose.  Nothing is read back and nothing
         waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 56] (GRID_MATCH_DTYPE; slot s * k + t is frame t of robot s).
-        block = 2..16: the same records by the coarse-to-fine search."""
+        block = 2..16: the same records by the coarse-to-fine search.  response (grid_response()) given: the response
+        stage behind the match, and (records, response records: a CUDA uint8 tensor [n_robots * k, 192],
+        GRID_RESPONSE_DTYPE) is returned; then integrate_at="response" integrates at the refined poses instead of the records'."""
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         if not isinstance(mapper, GridMapper):
             raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
         S, k, ts, _ = self._last_tick
         return mapper._match_and_integrate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
-                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts, block)
+                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts, block, False, response, integrate_at)
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current

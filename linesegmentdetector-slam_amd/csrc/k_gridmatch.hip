@@ -27,7 +27,8 @@
 //   k_grid_match_pick   VGPRs 14   SGPRs 36   scratch 0 bytes   LDS     0 bytes   8 waves / SIMD
 //
 // The key, the slot and phase A live in gridmatch_dev.h, shared with the coarse-to-fine search of k_gridmatch_mr.hip, which ends in this
-// file's k_grid_match_pick.  NOT in either file: sub-cell refinement, a covariance of the response, loop closure, the fleet classes.
+// file's k_grid_match_pick; k_gridresponse.hip reads the records for a sub-cell pose and a covariance of the response.  NOT in any of
+// them: loop closure, the fleet classes.
 #include "lsd_internal.h"
 #include "gridmatch_dev.h"
 

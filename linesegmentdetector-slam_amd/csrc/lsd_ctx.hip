@@ -98,6 +98,7 @@ struct lsd_ctx {
     DevBuf<uint8_t> stage;
     DevBuf<uint8_t> fa_buf;
     DevBuf<uint8_t> gm_mr_ws;                           // lsd_enqueue_grid_match_mr_device: U, the coarse slots, the counts and the pick's slots
+    DevBuf<uint32_t> gr_volume;                         // lsd_enqueue_grid_response_device: the volume of R where the caller gives none
     DevBuf<uint8_t> gm_slots;                           // lsd_enqueue_grid_match_device: the per-(scan, angle) slots between its two kernels
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
     // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first
@@ -1271,6 +1272,73 @@ int lsd_grid_match_mr(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n
     if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
     HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
     if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_match_mr_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- the response around a match (k_gridresponse.hip) ---
+// what both response entries refuse about the window, the keep ratio and the step
+static bool grid_response_bad(const lsd_grid_response_par& rp, double ang_step) {
+    if (rp.rx < 1 || rp.rx > 7 || rp.ry < 1 || rp.ry > 7 || rp.ra < 0 || rp.ra > 7) return true;
+    if (rp.keep_den == 0 || rp.keep_num > rp.keep_den) return true;
+    return !std::isfinite(ang_step) || ang_step < 0 || (ang_step == 0 && rp.ra > 0);
+}
+
+size_t lsd_grid_response_volume_bytes(int n_scans, lsd_grid_response_par rp) {
+    if (n_scans < 0 || rp.rx < 1 || rp.rx > 7 || rp.ry < 1 || rp.ry > 7 || rp.ra < 0 || rp.ra > 7) return 0;
+    return grid_response_volume_bytes(n_scans, rp);
+}
+
+int lsd_enqueue_grid_response_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                     size_t pose_pitch, const lsd_grid_match_rec* d_records, lsd_map_param mp, double range_max,
+                                     const uint8_t* d_corr, double ang_step, lsd_grid_response_par rp, lsd_grid_response_rec* d_out,
+                                     uint32_t* d_volume, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_poses || !d_records || !d_corr || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
+        grid_response_bad(rp, ang_step))
+        return LSD_ERR_INVALID;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
+        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_out)) & 7) ||
+        (reinterpret_cast<uintptr_t>(d_volume) & 3)) {
+        c->err = "grid response: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses, d_records and d_out 8-byte, d_volume 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!d_volume) {
+        HIPCHK(c, c->gr_volume.reserve(grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t)));   // (grown: one synchronisation; else nothing happens)
+        d_volume = c->gr_volume.get();
+    }
+    hipStream_t s = (hipStream_t)stream;
+    launch_grid_response(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, d_records, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr,
+                         ang_step, rp, d_volume, d_out, s);
+    HIPCHK(c, hipGetLastError());
+    c->last_stream = s;
+    return LSD_OK;
+}
+
+int lsd_grid_response(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses,
+                      const lsd_grid_match_rec* records, lsd_map_param mp, double range_max, const uint8_t* corr, double ang_step,
+                      lsd_grid_response_par rp, lsd_grid_response_rec* out, uint32_t* volume) {
+    if (!c || !scans || !lens || !poses || !records || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
+        grid_response_bad(rp, ang_step))
+        return LSD_ERR_INVALID;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow, n_vol = grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t);
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; lsd_grid_match_rec* d_rec; uint8_t* d_co; lsd_grid_response_rec* d_out; uint32_t* d_vol;
+    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_rec, ns); k(d_co, cells); k(d_out, ns); k(d_vol, n_vol); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_rec, records, ns * sizeof(lsd_grid_match_rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_grid_response_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), d_rec, mp, range_max, d_co, ang_step, rp,
+                                                    d_out, d_vol, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_response_rec), hipMemcpyDeviceToHost, c->stream));
+    if (volume) HIPCHK(c, hipMemcpyAsync(volume, d_vol, n_vol * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }

@@ -193,6 +193,12 @@ void grid_match_mr_ws(int n_scans, const lsd_grid_search& se, int block, size_t 
 void launch_grid_match_mr(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
                           double resol, double range_max, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se,
                           void* const ws[4], lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s);
+// the response around a match (k_gridresponse.hip): the records of either search -> the volume of R (grid_response_volume_bytes bytes,
+// the caller's or workspace) -> n_scans response records
+size_t grid_response_volume_bytes(int n_scans, const lsd_grid_response_par& rp);
+void launch_grid_response(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch,
+                          const lsd_grid_match_rec* records, int cols, int rows, double resol, double range_max, const uint8_t* corr, double ang_step,
+                          const lsd_grid_response_par& rp, uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
