@@ -670,11 +670,9 @@ class Context:
     def grid_integrate(self, scans, lens, poses, map_param, range_max, pass_counts=None, hit_counts=None):
         """lsd_grid_integrate from host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3] (x, y in map pixels, ang
         in degrees), the planes uint32 [rows, cols] (None: zeros).  Returns (pass, hit): new arrays, the given counts plus this call's."""
-        sc = np.ascontiguousarray(scans, np.float64)
-        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
         mp = _map_param(map_param)
-        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or mp.oriMapCol <= 0 or mp.oriMapRow <= 0:
+        if not ok or mp.oriMapCol <= 0 or mp.oriMapRow <= 0:
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], a grid of at least one cell")
         shape = (mp.oriMapRow, mp.oriMapCol)
         planes = []
@@ -705,12 +703,10 @@ class Context:
     def grid_match(self, scans, lens, poses, map_param, range_max, corr, search):
         """lsd_grid_match from host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3], corr uint8 [rows, cols].
         Returns the n records as a numpy array of GRID_MATCH_DTYPE.  Blocking."""
-        sc = np.ascontiguousarray(scans, np.float64)
-        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
         mp = _map_param(map_param)
         co = np.ascontiguousarray(corr, np.uint8)
-        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol):
+        if not ok or co.shape != (mp.oriMapRow, mp.oriMapCol):
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], corr uint8 [rows, cols]")
         out = np.zeros(len(ln), GRID_MATCH_DTYPE)
         self._chk(self.L.lsd_grid_match(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, mp, float(range_max),
@@ -735,12 +731,10 @@ class Context:
     def grid_match_mr(self, scans, lens, poses, map_param, range_max, corr, block, search, stats=False):
         """lsd_grid_match_mr from host arrays (those of grid_match): the n records, and with stats=True (records, the n statistics records as
         a numpy array of GRID_MATCH_MR_STATS_DTYPE).  Blocking."""
-        sc = np.ascontiguousarray(scans, np.float64)
-        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
         mp = _map_param(map_param)
         co = np.ascontiguousarray(corr, np.uint8)
-        if sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol):
+        if not ok or co.shape != (mp.oriMapRow, mp.oriMapCol):
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], corr uint8 [rows, cols]")
         out = np.zeros(len(ln), GRID_MATCH_DTYPE)
         st = np.zeros(len(ln), GRID_MATCH_MR_STATS_DTYPE)
@@ -764,14 +758,11 @@ class Context:
         """lsd_grid_response from host arrays (those of grid_match, and its records as a numpy array of GRID_MATCH_DTYPE): the n response
         records as a numpy array of GRID_RESPONSE_DTYPE, and with volume=True (records, the scores: uint32 [n, 2 ra + 1, 2 ry + 1,
         2 rx + 1]).  Blocking."""
-        sc = np.ascontiguousarray(scans, np.float64)
-        ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
         rec = np.ascontiguousarray(records)
         mp = _map_param(map_param)
         co = np.ascontiguousarray(corr, np.uint8)
-        if (sc.ndim != 3 or sc.shape[2] != 2 or sc.shape[0] != len(ln) or len(po) != len(ln) or co.shape != (mp.oriMapRow, mp.oriMapCol) or
-                rec.dtype != GRID_MATCH_DTYPE or rec.shape != (len(ln),)):
+        if not ok or co.shape != (mp.oriMapRow, mp.oriMapCol) or rec.dtype != GRID_MATCH_DTYPE or rec.shape != (len(ln),):
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], records GRID_MATCH_DTYPE [n], corr uint8 [rows, cols]")
         rp = grid_response(response)
         out = np.zeros(len(ln), GRID_RESPONSE_DTYPE)
@@ -1010,6 +1001,15 @@ def _pos(p):
 
 def _map_param(mp):
     return lsd_map_param(int(mp[0]), int(mp[1]), float(mp[2]), float(mp[3]), float(mp[4]))
+
+
+def _host_scans(scans, lens, poses):
+    """The host arrays every grid method takes, contiguous: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]; and whether
+    they have those shapes."""
+    sc = np.ascontiguousarray(scans, np.float64)
+    ln = np.ascontiguousarray(lens, np.int32).reshape(-1)
+    po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+    return sc, ln, po, sc.ndim == 3 and sc.shape[2] == 2 and sc.shape[0] == len(ln) and len(po) == len(ln)
 
 
 def _u32s(*values, limit):
@@ -1261,17 +1261,7 @@ class GridMapper:
         """Adds scans that are on the device: d_scans a CUDA float64 tensor [n, stride, 2] as the ingest entries write it, d_lens CUDA
         int32 [n], d_poses a CUDA tensor holding n records at pose_pitch bytes, each starting with (x, y, ang) as doubles -- float64
         [n, 3] (pitch 24), or the bytes of lsd_fa_state (720) or lsd_fa_carry (768) records.  On `stream` (default: the current one)."""
-        import torch
-        for name, t, dt in (("d_scans", d_scans, torch.float64), ("d_lens", d_lens, torch.int32)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise LsdError(LSD_ERR_INVALID, "%s must be a contiguous CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
-        if not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous():
-            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor")
-        n, pitch = d_lens.numel(), int(pose_pitch)
-        if d_scans.dim() != 3 or d_scans.shape[0] != n or d_scans.shape[2] != 2 or d_scans.shape[1] < 1:
-            raise LsdError(LSD_ERR_INVALID, "d_scans must be [n, stride >= 1, 2] with one length per scan")
-        if pitch < 24 or (n and d_poses.numel() * d_poses.element_size() < (n - 1) * pitch + 24):
-            raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
         self._enqueue(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
                       _cuda_stream(stream).cuda_stream)
         self._held = (d_scans, d_lens, d_poses)                              # the launch reads them: alive until the next one
@@ -1280,9 +1270,8 @@ class GridMapper:
         """integrate_device for host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]; one upload, then the
         launch on the current stream."""
         import torch
-        sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
+        if not ok or ((ln < 0) | (ln > sc.shape[1])).any():
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
         dev = self._planes.device
         self.integrate_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev))
@@ -1405,14 +1394,8 @@ class GridMapper:
         [n, 16], GRID_MATCH_MR_STATS_DTYPE).  response (grid_response(); True: its defaults) given: response_device behind the match, and
         its records are returned beside what is returned without it."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
-        ts = _cuda_stream(stream)
-        got = self._enqueue_match(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search, ts,
-                                  block, stats)
-        if response is not None:
-            rec = got[0] if stats else got
-            resp = self._enqueue_response(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
-                                          rec.data_ptr(), search, response, ts)
-            got = got + (resp,) if stats else (got, resp)
+        got = self._chain(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
+                          _cuda_stream(stream), block, stats, response)
         self._held_match = (d_scans, d_lens, d_poses, got)
         return got
 
@@ -1421,9 +1404,8 @@ class GridMapper:
         array of GRID_MATCH_DTYPE: a read-back, which waits for the device.  response given: (records, the response records as a numpy
         array of GRID_RESPONSE_DTYPE)."""
         import torch
-        sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
-        po = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
-        if sc.ndim != 3 or sc.shape[0] != len(ln) or len(po) != len(ln) or ((ln < 0) | (ln > sc.shape[1])).any():
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
+        if not ok or ((ln < 0) | (ln > sc.shape[1])).any():
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
         dev = self._planes.device
         rec = self.match_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, search, block=block,
@@ -1432,22 +1414,25 @@ class GridMapper:
             return rec.cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy()
         return (rec[0].cpu().numpy().reshape(-1).view(GRID_MATCH_DTYPE).copy(), rec[1].cpu().numpy().reshape(-1).view(GRID_RESPONSE_DTYPE).copy())
 
-    def _match_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, refresh, smear, ts, block=0, stats=False,
-                             response=None, integrate_at="match"):
-        if integrate_at not in ("match", "response") or (integrate_at == "response" and response is None):
+    def _chain(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts, block=0, stats=False, response=None, integrate=False,
+               refresh=False, smear=None, integrate_at="match"):
+        """What match_device, match_and_integrate_device and Localizer.refine_and_integrate_last_tick enqueue on the stream ts, in this
+        order: likelihood_device (refresh), the match (block: coarse to fine), the response (response given) and, with integrate, the
+        integration at the match records or at the response's.  Returns the records, with the statistics (stats) and then the response
+        records (response given) behind them in a tuple."""
+        if integrate and (integrate_at not in ("match", "response") or (integrate_at == "response" and response is None)):
             raise LsdError(LSD_ERR_INVALID, "integrate_at is 'match' or, with response given, 'response'")
         if refresh:
             self.likelihood_device(smear, ts, block)
         got = self._enqueue_match(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, search, ts, block, stats)
-        rec = got[0] if stats else got
-        at, pitch = rec, GRID_MATCH_DTYPE.itemsize
+        parts = list(got) if stats else [got]
         if response is not None:
-            resp = self._enqueue_response(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, rec.data_ptr(), search, response, ts)
-            got = got + (resp,) if stats else (got, resp)
-            if integrate_at == "response":
-                at, pitch = resp, GRID_RESPONSE_DTYPE.itemsize
-        self._enqueue(ctx, d_scans, d_lens, n, stride, at.data_ptr(), pitch, ts.cuda_stream)
-        self._held_rec = got                                                 # the integration reads it: alive until the next one
+            parts.append(self._enqueue_response(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, parts[0].data_ptr(), search, response, ts))
+        got = tuple(parts) if len(parts) > 1 else parts[0]
+        if integrate:
+            at = parts[-1] if integrate_at == "response" else parts[0]      # records of 192 or of 56 bytes, a pose at the head of each
+            self._enqueue(ctx, d_scans, d_lens, n, stride, at.data_ptr(), at.shape[1], ts.cuda_stream)
+            self._held_rec = got                                             # the integration reads it: alive until the next one
         return got
 
     def match_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, search=None, stream=None, refresh=True, smear=None, block=0,
@@ -1458,8 +1443,8 @@ class GridMapper:
         statistics) as match_device does.  response given: response_device behind the match, its records returned beside the others; then
         integrate_at="response" integrates at the refined poses (pitch 192) instead of the records' ("match", the default)."""
         n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
-        rec = self._match_and_integrate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
-                                        refresh, smear, _cuda_stream(stream), block, stats, response, integrate_at)
+        rec = self._chain(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, search,
+                          _cuda_stream(stream), block, stats, response, integrate=True, refresh=refresh, smear=smear, integrate_at=integrate_at)
         self._held_match = (d_scans, d_lens, d_poses)
         return rec
 
@@ -2055,8 +2040,9 @@ class Localizer(_Ticks):
         if not isinstance(mapper, GridMapper):
             raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
         S, k, ts, _ = self._last_tick
-        return mapper._match_and_integrate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
-                                           FA_STATE_DTYPE.itemsize, search, refresh, smear, ts, block, False, response, integrate_at)
+        return mapper._chain(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
+                             FA_STATE_DTYPE.itemsize, search, ts, block, response=response, integrate=True, refresh=refresh, smear=smear,
+                             integrate_at=integrate_at)
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current

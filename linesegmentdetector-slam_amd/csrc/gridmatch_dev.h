@@ -16,7 +16,7 @@ static_assert(255ll * kGmMaxBeams < (1 << 20) && kKeyScoreShift + 20 <= 64, "the
 static_assert((2 * kGmMaxWin + 1) * (2 * kGmMaxWin + 1) * (2 * kGmMaxWin + 1) < (1 << kKeyLinBits) - 1, "a real key is never 0");
 
 struct GmSlot { unsigned long long key; uint32_t nb, s0; };          // per (scan, angle): the best key, the scored beams, S at (j, i) = (0, 0)
-static_assert(sizeof(GmSlot) == 16, "lsd_ctx.hip sizes the workspace by 16 bytes a slot");
+static_assert(sizeof(GmSlot) == 16, "lsd_grid.hip sizes the workspace by 16 bytes a slot");
 
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int mask) {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask, 64);

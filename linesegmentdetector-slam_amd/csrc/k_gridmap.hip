@@ -112,10 +112,9 @@ __global__ __launch_bounds__(256) void k_grid_publish(const uint32_t* __restrict
     grid[i] = p < min_pass ? -1 : ((unsigned long long)h * occ_den >= (unsigned long long)p * occ_num ? 100 : 0);
 }
 
-void launch_grid_integrate(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols,
-                           int rows, double resol, double range_max, uint32_t* pass, uint32_t* hit, hipStream_t s) {
-    hipLaunchKernelGGL(k_grid_integrate, dim3(n_scans), dim3(kGridLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride,
-                       static_cast<const uint8_t*>(poses), pose_pitch, cols, rows, resol, range_max, pass, hit);
+void launch_grid_integrate(const GridScans& g, uint32_t* pass, uint32_t* hit, hipStream_t s) {
+    hipLaunchKernelGGL(k_grid_integrate, dim3(g.n_scans), dim3(kGridLanes), 0, s, reinterpret_cast<const double2*>(g.scans), g.lens, g.stride,
+                       static_cast<const uint8_t*>(g.poses), g.pose_pitch, g.cols, g.rows, g.resol, g.range_max, pass, hit);
 }
 
 void launch_grid_publish(const uint32_t* pass, const uint32_t* hit, size_t n_cells, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,

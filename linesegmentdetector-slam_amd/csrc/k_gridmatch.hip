@@ -190,13 +190,11 @@ void launch_grid_match_pick(int n_scans, const void* poses, size_t pose_pitch, c
 
 size_t grid_match_slot_bytes(int n_scans, int na) { return (size_t)n_scans * (2 * na + 1) * sizeof(GmSlot); }
 
-void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
-                       double resol, double range_max, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_grid_match, dim3(n_scans, 2 * se.na + 1), dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride,
-                       static_cast<const uint8_t*>(poses), pose_pitch, cols, rows, resol, range_max, corr, se.wx, se.wy, se.na, se.ang_step,
-                       static_cast<GmSlot*>(slots));
-    launch_grid_match_pick(n_scans, poses, pose_pitch, se, slots, out, s);
+void launch_grid_match(const GridScans& g, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_grid_match, dim3(g.n_scans, 2 * se.na + 1), dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(g.scans), g.lens,
+                       g.stride, static_cast<const uint8_t*>(g.poses), g.pose_pitch, g.cols, g.rows, g.resol, g.range_max, corr, se.wx, se.wy, se.na,
+                       se.ang_step, static_cast<GmSlot*>(slots));
+    launch_grid_match_pick(g.n_scans, g.poses, g.pose_pitch, se, slots, out, s);
 }
 
 }  // namespace lsdhip

@@ -287,22 +287,21 @@ void grid_match_mr_ws(int n_scans, const lsd_grid_search& se, int block, size_t 
     bytes[3] = sa * sizeof(GmSlot);
 }
 
-void launch_grid_match_mr(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
-                          double resol, double range_max, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se,
-                          void* const ws[4], lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s) {
-    const dim3 grid(n_scans, 2 * se.na + 1);
-    const double2* sc = reinterpret_cast<const double2*>(scans);
-    const uint8_t* po = static_cast<const uint8_t*>(poses);
+void launch_grid_match_mr(const GridScans& g, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se, void* const ws[4],
+                          lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s) {
+    const dim3 grid(g.n_scans, 2 * se.na + 1);
+    const double2* sc = reinterpret_cast<const double2*>(g.scans);
+    const uint8_t* po = static_cast<const uint8_t*>(g.poses);
     uint32_t* U = static_cast<uint32_t*>(ws[0]);
     MrSlot* ms = static_cast<MrSlot*>(ws[1]);
     MrCount* mc = static_cast<MrCount*>(ws[2]);
-    hipLaunchKernelGGL(k_grid_match_coarse, grid, dim3(kGmLanes), 0, s, sc, lens, stride, po, pose_pitch, cols, rows, resol, range_max, corr, coarse,
-                       block, se.wx, se.wy, se.na, se.ang_step, U, ms);
-    hipLaunchKernelGGL(k_grid_match_fine, grid, dim3(kGmLanes), 0, s, sc, lens, stride, po, pose_pitch, cols, rows, resol, range_max, corr, block,
-                       se.wx, se.wy, se.na, se.ang_step, U, ms, static_cast<GmSlot*>(ws[3]), mc);
-    launch_grid_match_pick(n_scans, poses, pose_pitch, se, ws[3], out, s);
+    hipLaunchKernelGGL(k_grid_match_coarse, grid, dim3(kGmLanes), 0, s, sc, g.lens, g.stride, po, g.pose_pitch, g.cols, g.rows, g.resol, g.range_max,
+                       corr, coarse, block, se.wx, se.wy, se.na, se.ang_step, U, ms);
+    hipLaunchKernelGGL(k_grid_match_fine, grid, dim3(kGmLanes), 0, s, sc, g.lens, g.stride, po, g.pose_pitch, g.cols, g.rows, g.resol, g.range_max,
+                       corr, block, se.wx, se.wy, se.na, se.ang_step, U, ms, static_cast<GmSlot*>(ws[3]), mc);
+    launch_grid_match_pick(g.n_scans, g.poses, g.pose_pitch, se, ws[3], out, s);
     if (stats)
-        hipLaunchKernelGGL(k_grid_match_mr_stats, dim3(n_scans), dim3(64), 0, s, po, pose_pitch, block, se.wx, se.wy, se.na, ms, mc,
+        hipLaunchKernelGGL(k_grid_match_mr_stats, dim3(g.n_scans), dim3(64), 0, s, po, g.pose_pitch, block, se.wx, se.wy, se.na, ms, mc,
                            reinterpret_cast<uint32_t*>(stats));
 }
 

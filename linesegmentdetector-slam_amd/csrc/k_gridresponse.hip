@@ -168,13 +168,12 @@ size_t grid_response_volume_bytes(int n_scans, const lsd_grid_response_par& rp) 
     return (size_t)n_scans * (2 * rp.ra + 1) * (2 * rp.ry + 1) * (2 * rp.rx + 1) * sizeof(uint32_t);
 }
 
-void launch_grid_response(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch,
-                          const lsd_grid_match_rec* records, int cols, int rows, double resol, double range_max, const uint8_t* corr, double ang_step,
-                          const lsd_grid_response_par& rp, uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_grid_response, dim3(n_scans, 2 * rp.ra + 1), dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride,
-                       static_cast<const uint8_t*>(poses), pose_pitch, records, cols, rows, resol, range_max, corr, ang_step, rp.rx, rp.ry, rp.ra,
-                       volume);
-    hipLaunchKernelGGL(k_grid_response_finish, dim3(n_scans), dim3(64), 0, s, reinterpret_cast<const unsigned long long*>(records), volume, ang_step,
+void launch_grid_response(const GridScans& g, const lsd_grid_match_rec* records, const uint8_t* corr, double ang_step, const lsd_grid_response_par& rp,
+                          uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_grid_response, dim3(g.n_scans, 2 * rp.ra + 1), dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(g.scans), g.lens,
+                       g.stride, static_cast<const uint8_t*>(g.poses), g.pose_pitch, records, g.cols, g.rows, g.resol, g.range_max, corr, ang_step,
+                       rp.rx, rp.ry, rp.ra, volume);
+    hipLaunchKernelGGL(k_grid_response_finish, dim3(g.n_scans), dim3(64), 0, s, reinterpret_cast<const unsigned long long*>(records), volume, ang_step,
                        rp.rx, rp.ry, rp.ra, rp.keep_num, rp.keep_den, reinterpret_cast<unsigned long long*>(out));
 }
 

@@ -16,137 +16,13 @@
 #include <string>
 #include <vector>
 
-#include "lsd_devbuf.h"
-#include "lsd_internal.h"
+#include "lsd_ctx.h"
 #include "k1_lds.h"
 #include "k_rdp_lds.h"
 
 using namespace lsdhip;
 
-// The main workspace: everything ensure_workspace sizes from the batch geometry, with the capacities it was sized for.  A failed
-// (re)allocation forgets all of it at once (`ws = Workspace{}`).
-struct Workspace {
-    size_t cap_gpx = 0;                          // Gaussian elements per image (rows padded to Geom::gp)
-    size_t cap_n = 0, cap_npx = 0, cap_ws = 0;   // images, scaled pixels per image, wave slots
-    int cap_max_lines = 0;
-    DevBuf<double> gauss, mag, deg, recs, recs_scaled;
-    DevBuf<double2> sc;
-    DevBuf<uint32_t> order;
-    DevBuf<uint32_t> sets;               // n x 256: certified sets of the region stage (region/eval.h: certify_set)
-    DevBuf<uint32_t> pw, epochmap, ord, spill, gcopy, stamps, seedidx, seedpos, tepoch;
-    uint32_t run_id = 0;   // curMap stamps are unique per run: (run_id << 20) + grow number (a wave that uses up its 2^20 clears its stamps)
-    DevBuf<uint32_t> slist;
-    DevBuf<double> pend;
-    DevBuf<float4> wmeta;
-    DevBuf<int> rnum;
-    DevBuf<uint32_t> xq;
-    DevBuf<unsigned long long> maxbits;  // [0, cap_n) the maxima, then cap_n int32: the gradient pass's near-tie counts -- one memset clears both
-    DevBuf<int32_t> nb, nseed;
-    DevBuf<long long> stats;
-    DevBuf<SeedRec> seeds;               // allocated only while tracing is on
-    int32_t* ties() const { return reinterpret_cast<int32_t*>(maxbits.get() + cap_n); }
-};
-
-struct lsd_ctx {
-    int device = 0;
-    int num_cus = 256;                 // compute units of the device
-    size_t max_lds = 0;                // LDS a workgroup may have (hipDeviceAttributeMaxSharedMemoryPerBlock): bounds K1's window (make_geom)
-    uint32_t id_budget = 0xFFFF0u;     // curMap stamp ids a wave may use per run before it clears its stamps (lsd_debug_set_stamp_budget)
-    int tun_soft = 0, tun_claim = 0, tun_feed = 3, tun_big = 0;   // region-stage schedule (0: default), see k_region.hip
-    int tun_help = -1;                                             // helper wavefronts per image (-1: default, 0: none)
-    // developer experiments (environment variables read once, when the context is created; DESIGN_NOTES.md says what each was for)
-    int tun_gate = 12000;                                          // an image asks for help once it has run for this long (x 1024 clocks: ~5 ms)
-    int tun_share = 0;                                             // ... and for at least this share (%) of the time since the launch began (LSD_REGION_SHARE)
-    int pool_max_images = 4;                                       // calls with at most this many images get a pool of helper workgroups (LSD_REGION_POOL)
-    int tun_early = 0, tun_wb = 10, tun_up = 32, tun_down = 96, tun_requeue = 1, tun_xpoll = 20000, tun_linger = 1000000, tun_stop = 0;
-    int region_waves_mode = 0;         // 0: choose per batch; 4 / 8: force that region-stage variant (lsd_set_region_waves)
-    bool prefer4 = false;              // the 8-wave workspace did not fit this device's memory once: batches run on 4 waves per image
-    hipStream_t stream = nullptr;      // the context's own stream
-    hipStream_t last_stream = nullptr; // stream of the last enqueue
-    std::string err;
-    Workspace ws;
-    int mcap = 16384;
-    int gcap = 8192;
-    // host-API staging (device side), and the pinned host buffers every host <-> device copy goes through
-    DevBuf<uint8_t> h_in, h_lineim;
-    DevBuf<lsd_line> h_lines, h_flat;
-    DevBuf<int32_t> h_counts, h_offs;
-    uint8_t* pin[2] = {nullptr, nullptr};
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    bool pin_used[2] = {false, false};  // a DMA through the buffer has been queued: its event must be waited for before the buffer is written again
-    hipStream_t copy_stream = nullptr;  // second stream: the remapped maps travel back while the rest of the pipeline runs
-    size_t hcap_n = 0, hcap_wh = 0;
-    int hcap_max_lines = 0;
-    bool hcap_lineim = false;
-    // tables
-    DevBuf<double> d_taps, d_lgamma, d_ptab;
-    DevBuf<int> d_centres;
-    bool cost_history = false;          // lsd_set_cost_history: the region stage takes the images in the order of their cost in the last launch
-    int hist_n = 0;                     // images of the launch whose counter records are in `stats` (0: none)
-    lsd_params tab_params{};
-    bool tab_valid = false;
-    int tapR = 0;
-    // createMapCache workspace
-    DevBuf<unsigned long long> mc_claim;
-    DevBuf<uint32_t> mc_fa, mc_fb;
-    DevBuf<int> mc_ctl;                                 // spread flood: frontier sizes + per-chunk counts
-    DevBuf<uint8_t> mc_in;
-    DevBuf<double> mc_out;
-    DevBuf<uint8_t> oc_in, oc_out;                      // occupancy-grid staging of the host entry point
-    // staging of the host entry points of scan-to-map matching, FeatureScan and FeatureAssociation (one arena: each of them ends in a
-    // stream synchronisation, so no two are live at once), and the per-sequence workspace of the device FeatureAssociation (k_fa.hip)
-    DevBuf<uint8_t> stage;
-    DevBuf<uint8_t> fa_buf;
-    DevBuf<uint8_t> gm_mr_ws;                           // lsd_enqueue_grid_match_mr_device: U, the coarse slots, the counts and the pick's slots
-    DevBuf<uint32_t> gr_volume;                         // lsd_enqueue_grid_response_device: the volume of R where the caller gives none
-    DevBuf<uint8_t> gm_slots;                           // lsd_enqueue_grid_match_device: the per-(scan, angle) slots between its two kernels
-    std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
-    // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first
-    // LSD_MAX_MAPS of each belong to FeatureScan's entry, the rest to the two loops, so neither call disturbs the other's
-    std::vector<lsd_map_ref> map_tab_host = std::vector<lsd_map_ref>(2 * LSD_MAX_MAPS);
-    DevBuf<lsd_map_ref> map_tab;
-    int fa_lds_bound = kFaLdsMax;                       // kept candidates sorted in LDS up to this many (kTunings "FA_LDS")
-    // lsd_gather_lines: this rank's padded counts + offsets, and its slab of packed line records
-    DevBuf<int32_t> ga_cnt;
-    DevBuf<lsd_line> ga_slab;
-    hipEvent_t ga_ev = nullptr;         // recorded behind the collectives of the last lsd_gather_lines (they read ga_cnt / ga_slab)
-    bool ga_ev_valid = false;
-    // options
-    int stop_after = 0;
-    int tun_groups = -1;                // the 8-wave region stage as persistent workgroups (k_region.hip: k_region): -1 = as many as CUs when the batch has more images than that, 0 = never
-    DevBuf<int> pcount;                 // ... and the launch's image counter
-    bool trace = false;
-    bool fused_front = true;            // lsd_set_fused_front: K1 + K2 as one kernel where it applies (use_front)
-    int scan_cap = kRdpShortMaxLen;     // lsd_set_scan_capacity: readings per scan (the stride) FeatureScan and the ingest entries take
-    bool rdp_long_ready = false;        // the long FeatureScan kernels' dynamic-LDS limit covers scan_cap (prepare_rdp_long)
-    int host_max_lines = 8192;
-    // last run
-    Geom geom{};
-    int last_n = 0;
-    int last_max_lines = 0;
-    int32_t* last_counts = nullptr;
-    // the last call took the fused front end: no Gaussian image exists, LSD_DBG_GAUSS recomputes the requested one from the call's input
-    // (last_in; last_remapped: that input has been rewritten in place since, LSD_FLAG_WRITEBACK_MAP) into dbg_gauss
-    bool last_fused = false, last_remapped = false;
-    const uint8_t* last_in = nullptr;
-    DevBuf<double> dbg_gauss;
-    hipEvent_t ev[7]{};
-    bool ev_valid = false;
-    hipEvent_t ev_done = nullptr;      // end of the last enqueue: a later enqueue on ANOTHER stream waits for it (shared workspace)
-    bool done_valid = false;
-    hipStream_t done_stream = nullptr; // the stream ev_done was recorded on (last_stream moves with every entry point, this one with the detector only)
-};
-
 constexpr size_t kPinBytes = 32u << 20;   // two pinned staging buffers of this size per context
-
-#define HIPCHK(ctx, call)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                       \
-            return e_ == hipErrorOutOfMemory ? LSD_ERR_NOMEM : LSD_ERR_HIP;                       \
-        }                                                                                         \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // host-computed scalars and tables
@@ -1066,283 +942,6 @@ int lsd_enqueue_map_update_device(lsd_ctx* c, const int8_t* d_grid, int cols, in
     return lsd_enqueue_batch_device(c, d_map, 1, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, d_line_im, d_lines, max_lines, d_count, s);   // :132
 }
 
-// --- mapping with known poses (k_gridmap.hip) ---
-// the pose is the first three doubles of each record the entry's pitch may step over
-static_assert(sizeof(lsd_position) == 24 && offsetof(lsd_position, x) == 0 && offsetof(lsd_position, y) == 8 && offsetof(lsd_position, ang) == 16 &&
-              sizeof(lsd_fa_state) == 720 && offsetof(lsd_fa_state, x) == 0 && offsetof(lsd_fa_carry, state) == 0 && sizeof(lsd_fa_carry) == 768,
-              "lsd_enqueue_grid_integrate_device reads a pose from the head of lsd_position, lsd_fa_state and lsd_fa_carry records");
-
-// what both integrate entries refuse about the sizes, the frame and the range (c not null)
-static bool grid_frame_bad(const lsd_ctx* c, int n_scans, int stride, const lsd_map_param& mp, double range_max) {
-    if (n_scans < 0 || stride <= 0 || stride > c->scan_cap) return true;
-    if (mp.oriMapCol <= 0 || mp.oriMapRow <= 0 || mp.oriMapCol > 65535 || mp.oriMapRow > 65535) return true;
-    return !(mp.mapResol > 0) || !(range_max > 0) || !(range_max / mp.mapResol < 32767);     // (a NaN fails every test)
-}
-
-int lsd_enqueue_grid_integrate_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
-                                      size_t pose_pitch, lsd_map_param mp, double range_max, uint32_t* d_pass, uint32_t* d_hit, void* stream) {
-    if (!c || !d_scans || !d_lens || !d_poses || !d_pass || !d_hit || grid_frame_bad(c, n_scans, stride, mp, range_max)) return LSD_ERR_INVALID;
-    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) || (reinterpret_cast<uintptr_t>(d_poses) & 7)) {
-        c->err = "grid integrate: pose pitch >= 24 and a multiple of 8, d_scans 16-byte and d_poses 8-byte aligned";
-        return LSD_ERR_INVALID;
-    }
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_integrate(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_pass, d_hit, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_enqueue_grid_publish_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, size_t n_cells, uint32_t min_pass,
-                                    uint32_t occ_num, uint32_t occ_den, int8_t* d_grid, void* stream) {
-    if (!c || !d_pass || !d_hit || !d_grid || n_cells == 0 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
-    if (n_cells > (size_t)65535 * 65535) return LSD_ERR_INVALID;      // (more cells than the largest grid the integration takes)
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_publish(d_pass, d_hit, n_cells, min_pass, occ_num, occ_den, d_grid, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_grid_integrate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
-                       double range_max, uint32_t* pass, uint32_t* hit) {
-    if (!c || !scans || !lens || !poses || !pass || !hit || grid_frame_bad(c, n_scans, stride, mp, range_max)) return LSD_ERR_INVALID;
-    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
-    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint32_t *d_pa, *d_hi;
-    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_pa, cells); k(d_hi, cells); };
-    HIPCHK(c, carve(c->stage, regions));
-    if (ns) {
-        HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(d_pa, pass, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_hi, hit, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_grid_integrate_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_pa, d_hi, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(pass, d_pa, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hit, d_hi, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
-}
-
-// --- correlative scan-to-grid matching (k_gridmatch.hip) ---
-int lsd_grid_smear_default(double sigma_cells, int radius, lsd_grid_smear* out) {
-    if (!out || radius < 0 || radius > 7 || !(sigma_cells > 0) || !std::isfinite(sigma_cells)) return LSD_ERR_INVALID;
-    memset(out, 0, sizeof *out);
-    out->radius = radius;
-    for (int v = 0; v <= radius; v++)
-        for (int u = 0; u <= radius; u++) out->w[v][u] = (uint8_t)floor(255 * exp(-(double)(u * u + v * v) / (2 * sigma_cells * sigma_cells)) + 0.5);
-    return LSD_OK;
-}
-
-int lsd_enqueue_grid_likelihood_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, int cols, int rows, uint32_t min_pass,
-                                       uint32_t occ_num, uint32_t occ_den, lsd_grid_smear smear, uint8_t* d_corr, void* stream) {
-    if (!c || !d_pass || !d_hit || !d_corr || cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535) return LSD_ERR_INVALID;
-    if (smear.radius < 0 || smear.radius > 7 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_likelihood(d_pass, d_hit, cols, rows, min_pass, occ_num, occ_den, smear, d_corr, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-// what both match entries refuse about the search
-static bool grid_search_bad(const lsd_grid_search& se) {
-    if (se.wx < 0 || se.wx > 63 || se.wy < 0 || se.wy > 63 || se.na < 0 || se.na > 63) return true;
-    if (!std::isfinite(se.ang_step) || se.ang_step < 0 || (se.ang_step == 0 && se.na > 0)) return true;
-    return se.min_den == 0 || se.min_num > se.min_den;
-}
-
-int lsd_enqueue_grid_match_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
-                                  size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, lsd_grid_search se,
-                                  lsd_grid_match_rec* d_out, void* stream) {
-    if (!c || !d_scans || !d_lens || !d_poses || !d_corr || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se))
-        return LSD_ERR_INVALID;
-    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
-        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_out)) & 7)) {
-        c->err = "grid match: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses and d_out 8-byte aligned";
-        return LSD_ERR_INVALID;
-    }
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->gm_slots.reserve(grid_match_slot_bytes(n_scans, se.na)));   // (grown: one synchronisation; else nothing happens)
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_match(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr, se,
-                      c->gm_slots.get(), d_out, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_grid_match(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
-                   double range_max, const uint8_t* corr, lsd_grid_search se, lsd_grid_match_rec* out) {
-    if (!c || !scans || !lens || !poses || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se))
-        return LSD_ERR_INVALID;
-    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
-    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t* d_co; lsd_grid_match_rec* d_out;
-    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_co, cells); k(d_out, ns); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
-}
-
-// --- the same match, coarse to fine (k_gridmatch_mr.hip) ---
-size_t lsd_grid_coarse_bytes(int cols, int rows, int block) {
-    if (cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535 || block < 2 || block > 16) return 0;
-    return (size_t)(cols + block - 1) * (rows + block - 1);
-}
-
-int lsd_enqueue_grid_coarse_device(lsd_ctx* c, const uint8_t* d_corr, int cols, int rows, int block, uint8_t* d_coarse, void* stream) {
-    if (!c || !d_corr || !d_coarse || lsd_grid_coarse_bytes(cols, rows, block) == 0) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_coarse(d_corr, cols, rows, block, d_coarse, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_enqueue_grid_match_mr_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
-                                     size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, const uint8_t* d_coarse,
-                                     int block, lsd_grid_search se, lsd_grid_match_rec* d_out, lsd_grid_match_mr_stats* d_stats, void* stream) {
-    if (!c || !d_scans || !d_lens || !d_poses || !d_corr || !d_coarse || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
-        grid_search_bad(se) || block < 2 || block > 16)
-        return LSD_ERR_INVALID;
-    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
-        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_out)) & 7) || (reinterpret_cast<uintptr_t>(d_stats) & 3)) {
-        c->err = "grid match: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses and d_out 8-byte, d_stats 4-byte aligned";
-        return LSD_ERR_INVALID;
-    }
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    size_t bytes[4];
-    grid_match_mr_ws(n_scans, se, block, bytes);
-    uint8_t* r[4];
-    auto regions = [&](Carver& k) { for (int i = 0; i < 4; i++) k(r[i], bytes[i]); };
-    HIPCHK(c, carve(c->gm_mr_ws, regions));                          // (grown: one synchronisation; else nothing but pointer arithmetic)
-    void* const ws[4] = {r[0], r[1], r[2], r[3]};
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_match_mr(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr, d_coarse,
-                         block, se, ws, d_out, d_stats, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_grid_match_mr(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
-                      double range_max, const uint8_t* corr, int block, lsd_grid_search se, lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats) {
-    if (!c || !scans || !lens || !poses || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_search_bad(se) || block < 2 ||
-        block > 16)
-        return LSD_ERR_INVALID;
-    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
-    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t *d_co, *d_cs; lsd_grid_match_rec* d_out; lsd_grid_match_mr_stats* d_st;
-    auto regions = [&](Carver& k) {
-        k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_co, cells); k(d_cs, lsd_grid_coarse_bytes(mp.oriMapCol, mp.oriMapRow, block));
-        k(d_out, ns); k(d_st, ns);
-    };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    int st = lsd_enqueue_grid_coarse_device(c, d_co, mp.oriMapCol, mp.oriMapRow, block, d_cs, c->stream);
-    if (st == LSD_OK)
-        st = lsd_enqueue_grid_match_mr_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, d_cs, block, se, d_out,
-                                              stats ? d_st : nullptr, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
-    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_match_mr_stats), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
-}
-
-// --- the response around a match (k_gridresponse.hip) ---
-// what both response entries refuse about the window, the keep ratio and the step
-static bool grid_response_bad(const lsd_grid_response_par& rp, double ang_step) {
-    if (rp.rx < 1 || rp.rx > 7 || rp.ry < 1 || rp.ry > 7 || rp.ra < 0 || rp.ra > 7) return true;
-    if (rp.keep_den == 0 || rp.keep_num > rp.keep_den) return true;
-    return !std::isfinite(ang_step) || ang_step < 0 || (ang_step == 0 && rp.ra > 0);
-}
-
-size_t lsd_grid_response_volume_bytes(int n_scans, lsd_grid_response_par rp) {
-    if (n_scans < 0 || rp.rx < 1 || rp.rx > 7 || rp.ry < 1 || rp.ry > 7 || rp.ra < 0 || rp.ra > 7) return 0;
-    return grid_response_volume_bytes(n_scans, rp);
-}
-
-int lsd_enqueue_grid_response_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
-                                     size_t pose_pitch, const lsd_grid_match_rec* d_records, lsd_map_param mp, double range_max,
-                                     const uint8_t* d_corr, double ang_step, lsd_grid_response_par rp, lsd_grid_response_rec* d_out,
-                                     uint32_t* d_volume, void* stream) {
-    if (!c || !d_scans || !d_lens || !d_poses || !d_records || !d_corr || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
-        grid_response_bad(rp, ang_step))
-        return LSD_ERR_INVALID;
-    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (reinterpret_cast<uintptr_t>(d_scans) & 15) ||
-        ((reinterpret_cast<uintptr_t>(d_poses) | reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_out)) & 7) ||
-        (reinterpret_cast<uintptr_t>(d_volume) & 3)) {
-        c->err = "grid response: pose pitch >= 24 and a multiple of 8, d_scans 16-byte, d_poses, d_records and d_out 8-byte, d_volume 4-byte aligned";
-        return LSD_ERR_INVALID;
-    }
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!d_volume) {
-        HIPCHK(c, c->gr_volume.reserve(grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t)));   // (grown: one synchronisation; else nothing happens)
-        d_volume = c->gr_volume.get();
-    }
-    hipStream_t s = (hipStream_t)stream;
-    launch_grid_response(d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, d_records, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_corr,
-                         ang_step, rp, d_volume, d_out, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_grid_response(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses,
-                      const lsd_grid_match_rec* records, lsd_map_param mp, double range_max, const uint8_t* corr, double ang_step,
-                      lsd_grid_response_par rp, lsd_grid_response_rec* out, uint32_t* volume) {
-    if (!c || !scans || !lens || !poses || !records || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) ||
-        grid_response_bad(rp, ang_step))
-        return LSD_ERR_INVALID;
-    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    if (n_scans == 0) return LSD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow, n_vol = grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t);
-    lsd_polar* d_sc; int* d_len; lsd_position* d_po; lsd_grid_match_rec* d_rec; uint8_t* d_co; lsd_grid_response_rec* d_out; uint32_t* d_vol;
-    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); k(d_rec, ns); k(d_co, cells); k(d_out, ns); k(d_vol, n_vol); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_rec, records, ns * sizeof(lsd_grid_match_rec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_grid_response_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), d_rec, mp, range_max, d_co, ang_step, rp,
-                                                    d_out, d_vol, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_response_rec), hipMemcpyDeviceToHost, c->stream));
-    if (volume) HIPCHK(c, hipMemcpyAsync(volume, d_vol, n_vol * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
-}
-
 int lsd_enqueue_scan_to_map_match_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
                                          const lsd_line* d_scan_lines, const lsd_position* d_pts, int n_points,
                                          lsd_position lidar, lsd_position last, const int* d_pairs, int n_pairs,
@@ -1542,38 +1141,6 @@ int lsd_feature_scan_batch(lsd_ctx* c, const lsd_polar* scans, const int* lens, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n_scans; i++)
         if (n_lines[i] > LSD_RDP_MAX_LINES) return LSD_ERR_CAPACITY;      // more chords than the 360 records per scan hold (the first 360 are valid)
-    return LSD_OK;
-}
-
-int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, const int32_t* d_counts, int n_local, int max_lines,
-                     int n_total, int cap_rows, int32_t* d_counts_all, lsd_line* d_slabs_all, void* stream) {
-    if (!c || !comm || !comm->all_gather || comm->world <= 0 || comm->rank < 0 || comm->rank >= comm->world || n_total <= 0 || n_local < 0 ||
-        max_lines <= 0 || cap_rows <= 0 || !d_counts_all || !d_slabs_all || (n_local > 0 && (!d_lines || !d_counts)))
-        return LSD_ERR_INVALID;
-    int lo, hi, per;
-    lsd_shard_range(n_total, comm->world, comm->rank, &lo, &hi);
-    if (hi - lo != n_local) return LSD_ERR_INVALID;                      // the caller's shard is not the one lsd_shard_range gives this rank
-    lsd_gather_layout(n_total, comm->world, &per, nullptr);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t need_cnt = (size_t)(per + 2) + (size_t)(n_local > 0 ? n_local : 1);
-    HIPCHK(c, c->ga_cnt.reserve(need_cnt));
-    HIPCHK(c, c->ga_slab.reserve((size_t)cap_rows));
-    // the staging buffers belong to the context: an earlier hand-off's collectives (on whatever stream) must have read them
-    if (c->ga_ev_valid) HIPCHK(c, hipStreamWaitEvent(s, c->ga_ev, 0));
-    // rows past this rank's lines are zero (nothing stale travels)
-    HIPCHK(c, hipMemsetAsync(c->ga_slab.get(), 0, sizeof(lsd_line) * (size_t)cap_rows, s));
-    launch_pack_lines(d_lines, d_counts, n_local, max_lines, per, cap_rows, c->ga_cnt.get(), c->ga_cnt.get() + (per + 2), c->ga_slab.get(), s);
-    HIPCHK(c, hipGetLastError());
-    if (comm->all_gather(comm->user, c->ga_cnt.get(), d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
-        comm->all_gather(comm->user, c->ga_slab.get(), d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0) {
-        c->err = "lsd_gather_lines: the communicator's all_gather failed";
-        return LSD_ERR_HIP;
-    }
-    if (!c->ga_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ga_ev, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ga_ev, s));
-    c->ga_ev_valid = true;
-    c->last_stream = s;
     return LSD_OK;
 }
 

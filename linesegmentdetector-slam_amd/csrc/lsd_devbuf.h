@@ -1,5 +1,5 @@
-// lsd_devbuf.h -- device memory of the host side (lsd_ctx.hip): the one owner of a hipMalloc allocation, and the one carver that lays
-// typed regions out in such a buffer.  hipMalloc and hipFree are called here and nowhere else.
+// lsd_devbuf.h -- device memory of the host side (lsd_ctx.h: the context owns it): the one owner of a hipMalloc allocation, and the one carver
+// that lays typed regions out in such a buffer.  hipMalloc and hipFree are called here and nowhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

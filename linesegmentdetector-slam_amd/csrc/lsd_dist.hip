@@ -23,7 +23,7 @@ constexpr ncclDataType_t ncclInt8 = 0;
 #include <string>
 #include <vector>
 
-#include "lsd_internal.h"
+#include "lsd_ctx.h"
 
 namespace lsdhip {
 
@@ -167,9 +167,40 @@ int lsd_gather_unpack(const int32_t* counts_all, const lsd_line* slabs_all, int 
     return (flags & 2) ? LSD_ERR_INTERNAL : (flags & 1) ? LSD_ERR_CAPACITY : LSD_OK;
 }
 
+int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, const int32_t* d_counts, int n_local, int max_lines,
+                     int n_total, int cap_rows, int32_t* d_counts_all, lsd_line* d_slabs_all, void* stream) {
+    if (!c || !comm || !comm->all_gather || comm->world <= 0 || comm->rank < 0 || comm->rank >= comm->world || n_total <= 0 || n_local < 0 ||
+        max_lines <= 0 || cap_rows <= 0 || !d_counts_all || !d_slabs_all || (n_local > 0 && (!d_lines || !d_counts)))
+        return LSD_ERR_INVALID;
+    int lo, hi, per;
+    lsd_shard_range(n_total, comm->world, comm->rank, &lo, &hi);
+    if (hi - lo != n_local) return LSD_ERR_INVALID;                      // the caller's shard is not the one lsd_shard_range gives this rank
+    lsd_gather_layout(n_total, comm->world, &per, nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need_cnt = (size_t)(per + 2) + (size_t)(n_local > 0 ? n_local : 1);
+    HIPCHK(c, c->ga_cnt.reserve(need_cnt));
+    HIPCHK(c, c->ga_slab.reserve((size_t)cap_rows));
+    // the staging buffers belong to the context: an earlier hand-off's collectives (on whatever stream) must have read them
+    if (c->ga_ev_valid) HIPCHK(c, hipStreamWaitEvent(s, c->ga_ev, 0));
+    // rows past this rank's lines are zero (nothing stale travels)
+    HIPCHK(c, hipMemsetAsync(c->ga_slab.get(), 0, sizeof(lsd_line) * (size_t)cap_rows, s));
+    launch_pack_lines(d_lines, d_counts, n_local, max_lines, per, cap_rows, c->ga_cnt.get(), c->ga_cnt.get() + (per + 2), c->ga_slab.get(), s);
+    HIPCHK(c, hipGetLastError());
+    if (comm->all_gather(comm->user, c->ga_cnt.get(), d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
+        comm->all_gather(comm->user, c->ga_slab.get(), d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0) {
+        c->err = "lsd_gather_lines: the communicator's all_gather failed";
+        return LSD_ERR_HIP;
+    }
+    if (!c->ga_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ga_ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ga_ev, s));
+    c->ga_ev_valid = true;
+    c->last_stream = s;
+    return LSD_OK;
+}
+
 }  // extern "C"
 
-// (lsd_gather_lines needs the context's workspace: it lives in lsd_ctx.hip next to the struct)
 namespace lsdhip {
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s) {

@@ -1,0 +1,282 @@
+// lsd_grid.hip -- the grid stack's part of the C ABI (include/lsd_hip.h): mapping with known poses (k_gridmap.hip), the correlative
+// scan-to-grid match, plain (k_gridmatch.hip) and coarse to fine (k_gridmatch_mr.hip), and the response around a match
+// (k_gridresponse.hip).  The four scan-taking device entries receive the scans of a frame the same way: one check (grid_scans_bad)
+// turns those arguments into the view the launchers take, and each entry adds only what is its own.  Their host conveniences share one
+// check and one staging path (host_scans_bad, stage_scans) in the same way.
+#include <math.h>
+#include <stddef.h>
+#include <string.h>
+
+#include "lsd_ctx.h"
+
+// the pose is the first three doubles of each record the entry's pitch may step over
+static_assert(sizeof(lsd_position) == 24 && offsetof(lsd_position, x) == 0 && offsetof(lsd_position, y) == 8 && offsetof(lsd_position, ang) == 16 &&
+              sizeof(lsd_fa_state) == 720 && offsetof(lsd_fa_state, x) == 0 && offsetof(lsd_fa_carry, state) == 0 && sizeof(lsd_fa_carry) == 768,
+              "lsd_enqueue_grid_integrate_device reads a pose from the head of lsd_position, lsd_fa_state and lsd_fa_carry records");
+
+static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// what every entry that takes scans refuses about the sizes, the frame and the range (c not null)
+static bool grid_frame_bad(const lsd_ctx* c, int n_scans, int stride, const lsd_map_param& mp, double range_max) {
+    if (n_scans < 0 || stride <= 0 || stride > c->scan_cap) return true;
+    if (mp.oriMapCol <= 0 || mp.oriMapRow <= 0 || mp.oriMapCol > 65535 || mp.oriMapRow > 65535) return true;
+    return !(mp.mapResol > 0) || !(range_max > 0) || !(range_max / mp.mapResol < 32767);     // (a NaN fails every test)
+}
+
+// The leading arguments of a scan-taking device entry: refused (true; with c->err naming `entry` where it is the pitch or an alignment),
+// or handed on as the view the launchers take.
+static bool grid_scans_bad(lsd_ctx* c, const char* entry, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                           size_t pose_pitch, const lsd_map_param& mp, double range_max, GridScans& g) {
+    if (!c || !d_scans || !d_lens || !d_poses || grid_frame_bad(c, n_scans, stride, mp, range_max)) return true;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || (addr(d_scans) & 15) || (addr(d_poses) & 7)) {
+        c->err = std::string(entry) + ": pose pitch >= 24 and a multiple of 8, d_scans 16-byte and d_poses 8-byte aligned";
+        return true;
+    }
+    g = GridScans{d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max};
+    return false;
+}
+
+// ... and those of a host entry, whose lengths can be read: each within 0..stride
+static bool host_scans_bad(const lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses,
+                           const lsd_map_param& mp, double range_max) {
+    if (!c || !scans || !lens || !poses || grid_frame_bad(c, n_scans, stride, mp, range_max)) return true;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return true;
+    return false;
+}
+
+// The staging of a host entry that has accepted its arguments: c->stage carved into the scans, the lengths, the poses and the regions
+// `more` names behind them, and the three uploads queued on c->stream.  d_sc, d_len, d_po: what the device entry is given then.
+template <class More>
+static int stage_scans(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_polar*& d_sc,
+                       int*& d_len, lsd_position*& d_po, More&& more) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_scans;
+    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); more(k); };
+    HIPCHK(c, carve(c->stage, regions));
+    if (ns) {
+        HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
+    }
+    return LSD_OK;
+}
+
+extern "C" {
+
+// --- mapping with known poses (k_gridmap.hip) ---
+int lsd_enqueue_grid_integrate_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                      size_t pose_pitch, lsd_map_param mp, double range_max, uint32_t* d_pass, uint32_t* d_hit, void* stream) {
+    GridScans g;
+    if (!d_pass || !d_hit || grid_scans_bad(c, "grid integrate", d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp, range_max, g))
+        return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) { launch_grid_integrate(g, d_pass, d_hit, s); return LSD_OK; });
+}
+
+int lsd_enqueue_grid_publish_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, size_t n_cells, uint32_t min_pass,
+                                    uint32_t occ_num, uint32_t occ_den, int8_t* d_grid, void* stream) {
+    if (!c || !d_pass || !d_hit || !d_grid || n_cells == 0 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
+    if (n_cells > (size_t)65535 * 65535) return LSD_ERR_INVALID;      // (more cells than the largest grid the integration takes)
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_grid_publish(d_pass, d_hit, n_cells, min_pass, occ_num, occ_den, d_grid, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_integrate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                       double range_max, uint32_t* pass, uint32_t* hit) {
+    if (!pass || !hit || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max)) return LSD_ERR_INVALID;
+    // (no scans: the planes still make the round trip)
+    const size_t cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint32_t *d_pa, *d_hi;
+    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) { k(d_pa, cells); k(d_hi, cells); });
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(d_pa, pass, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_hi, hit, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_grid_integrate_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_pa, d_hi, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(pass, d_pa, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hit, d_hi, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- correlative scan-to-grid matching (k_gridmatch.hip) ---
+int lsd_grid_smear_default(double sigma_cells, int radius, lsd_grid_smear* out) {
+    if (!out || radius < 0 || radius > 7 || !(sigma_cells > 0) || !std::isfinite(sigma_cells)) return LSD_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    out->radius = radius;
+    for (int v = 0; v <= radius; v++)
+        for (int u = 0; u <= radius; u++) out->w[v][u] = (uint8_t)floor(255 * exp(-(double)(u * u + v * v) / (2 * sigma_cells * sigma_cells)) + 0.5);
+    return LSD_OK;
+}
+
+int lsd_enqueue_grid_likelihood_device(lsd_ctx* c, const uint32_t* d_pass, const uint32_t* d_hit, int cols, int rows, uint32_t min_pass,
+                                       uint32_t occ_num, uint32_t occ_den, lsd_grid_smear smear, uint8_t* d_corr, void* stream) {
+    if (!c || !d_pass || !d_hit || !d_corr || cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535) return LSD_ERR_INVALID;
+    if (smear.radius < 0 || smear.radius > 7 || occ_den == 0 || occ_num > occ_den) return LSD_ERR_INVALID;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_grid_likelihood(d_pass, d_hit, cols, rows, min_pass, occ_num, occ_den, smear, d_corr, s);
+        return LSD_OK;
+    });
+}
+
+// what both match entries refuse about the search
+static bool grid_search_bad(const lsd_grid_search& se) {
+    if (se.wx < 0 || se.wx > 63 || se.wy < 0 || se.wy > 63 || se.na < 0 || se.na > 63) return true;
+    if (!std::isfinite(se.ang_step) || se.ang_step < 0 || (se.ang_step == 0 && se.na > 0)) return true;
+    return se.min_den == 0 || se.min_num > se.min_den;
+}
+
+int lsd_enqueue_grid_match_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                  size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, lsd_grid_search se,
+                                  lsd_grid_match_rec* d_out, void* stream) {
+    GridScans g;
+    if (!d_corr || !d_out || grid_search_bad(se) ||
+        grid_scans_bad(c, "grid match", d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp, range_max, g))
+        return LSD_ERR_INVALID;
+    if (addr(d_out) & 7) {
+        c->err = "grid match: d_out 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        HIPCHK(c, c->gm_slots.reserve(grid_match_slot_bytes(n_scans, se.na)));   // (grown: one synchronisation; else nothing happens)
+        launch_grid_match(g, d_corr, se, c->gm_slots.get(), d_out, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_match(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                   double range_max, const uint8_t* corr, lsd_grid_search se, lsd_grid_match_rec* out) {
+    if (!corr || !out || grid_search_bad(se) || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max)) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t* d_co; lsd_grid_match_rec* d_out;
+    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) { k(d_co, cells); k(d_out, ns); });
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- the same match, coarse to fine (k_gridmatch_mr.hip) ---
+size_t lsd_grid_coarse_bytes(int cols, int rows, int block) {
+    if (cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535 || block < 2 || block > 16) return 0;
+    return (size_t)(cols + block - 1) * (rows + block - 1);
+}
+
+int lsd_enqueue_grid_coarse_device(lsd_ctx* c, const uint8_t* d_corr, int cols, int rows, int block, uint8_t* d_coarse, void* stream) {
+    if (!c || !d_corr || !d_coarse || lsd_grid_coarse_bytes(cols, rows, block) == 0) return LSD_ERR_INVALID;
+    return enqueue_on(c, stream, [&](hipStream_t s) { launch_grid_coarse(d_corr, cols, rows, block, d_coarse, s); return LSD_OK; });
+}
+
+int lsd_enqueue_grid_match_mr_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                     size_t pose_pitch, lsd_map_param mp, double range_max, const uint8_t* d_corr, const uint8_t* d_coarse,
+                                     int block, lsd_grid_search se, lsd_grid_match_rec* d_out, lsd_grid_match_mr_stats* d_stats, void* stream) {
+    GridScans g;
+    if (!d_corr || !d_coarse || !d_out || grid_search_bad(se) || block < 2 || block > 16 ||
+        grid_scans_bad(c, "grid match", d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp, range_max, g))
+        return LSD_ERR_INVALID;
+    if ((addr(d_out) & 7) || (addr(d_stats) & 3)) {
+        c->err = "grid match: d_out 8-byte, d_stats 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        size_t bytes[4];
+        grid_match_mr_ws(n_scans, se, block, bytes);
+        uint8_t* r[4];
+        auto regions = [&](Carver& k) { for (int i = 0; i < 4; i++) k(r[i], bytes[i]); };
+        HIPCHK(c, carve(c->gm_mr_ws, regions));                      // (grown: one synchronisation; else nothing but pointer arithmetic)
+        void* const ws[4] = {r[0], r[1], r[2], r[3]};
+        launch_grid_match_mr(g, d_corr, d_coarse, block, se, ws, d_out, d_stats, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_match_mr(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                      double range_max, const uint8_t* corr, int block, lsd_grid_search se, lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats) {
+    if (!corr || !out || grid_search_bad(se) || block < 2 || block > 16 || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max))
+        return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t *d_co, *d_cs; lsd_grid_match_rec* d_out; lsd_grid_match_mr_stats* d_st;
+    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) {
+        k(d_co, cells); k(d_cs, lsd_grid_coarse_bytes(mp.oriMapCol, mp.oriMapRow, block)); k(d_out, ns); k(d_st, ns);
+    });
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_grid_coarse_device(c, d_co, mp.oriMapCol, mp.oriMapRow, block, d_cs, c->stream);
+    if (st == LSD_OK)
+        st = lsd_enqueue_grid_match_mr_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, d_cs, block, se, d_out,
+                                              stats ? d_st : nullptr, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_match_mr_stats), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- the response around a match (k_gridresponse.hip) ---
+size_t lsd_grid_response_volume_bytes(int n_scans, lsd_grid_response_par rp) {
+    if (n_scans < 0 || rp.rx < 1 || rp.rx > 7 || rp.ry < 1 || rp.ry > 7 || rp.ra < 0 || rp.ra > 7) return 0;
+    return grid_response_volume_bytes(n_scans, rp);
+}
+
+// what both response entries refuse about the window (one scan's volume has no size), the keep ratio and the step
+static bool grid_response_bad(const lsd_grid_response_par& rp, double ang_step) {
+    if (lsd_grid_response_volume_bytes(1, rp) == 0 || rp.keep_den == 0 || rp.keep_num > rp.keep_den) return true;
+    return !std::isfinite(ang_step) || ang_step < 0 || (ang_step == 0 && rp.ra > 0);
+}
+
+int lsd_enqueue_grid_response_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                     size_t pose_pitch, const lsd_grid_match_rec* d_records, lsd_map_param mp, double range_max,
+                                     const uint8_t* d_corr, double ang_step, lsd_grid_response_par rp, lsd_grid_response_rec* d_out,
+                                     uint32_t* d_volume, void* stream) {
+    GridScans g;
+    if (!d_records || !d_corr || !d_out || grid_response_bad(rp, ang_step) ||
+        grid_scans_bad(c, "grid response", d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp, range_max, g))
+        return LSD_ERR_INVALID;
+    if (((addr(d_records) | addr(d_out)) & 7) || (addr(d_volume) & 3)) {
+        c->err = "grid response: d_records and d_out 8-byte, d_volume 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        if (!d_volume) {
+            // (grown: one synchronisation; else nothing happens)
+            HIPCHK(c, c->gr_volume.reserve(grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t)));
+            d_volume = c->gr_volume.get();
+        }
+        launch_grid_response(g, d_records, d_corr, ang_step, rp, d_volume, d_out, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_response(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses,
+                      const lsd_grid_match_rec* records, lsd_map_param mp, double range_max, const uint8_t* corr, double ang_step,
+                      lsd_grid_response_par rp, lsd_grid_response_rec* out, uint32_t* volume) {
+    if (!records || !corr || !out || grid_response_bad(rp, ang_step) || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max))
+        return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow, n_vol = grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t);
+    lsd_polar* d_sc; int* d_len; lsd_position* d_po; lsd_grid_match_rec* d_rec; uint8_t* d_co; lsd_grid_response_rec* d_out; uint32_t* d_vol;
+    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po,
+                         [&](Carver& k) { k(d_rec, ns); k(d_co, cells); k(d_out, ns); k(d_vol, n_vol); });
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(d_rec, records, ns * sizeof(lsd_grid_match_rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_grid_response_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), d_rec, mp, range_max, d_co, ang_step, rp,
+                                          d_out, d_vol, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_response_rec), hipMemcpyDeviceToHost, c->stream));
+    if (volume) HIPCHK(c, hipMemcpyAsync(volume, d_vol, n_vol * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+}  // extern "C"

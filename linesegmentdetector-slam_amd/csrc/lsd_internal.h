@@ -1,4 +1,4 @@
-// lsd_internal.h -- shared between the host side (lsd_ctx.hip) and the gfx950 kernels.
+// lsd_internal.h -- shared between the host side (lsd_ctx.hip, lsd_grid.hip, lsd_dist.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -169,20 +169,21 @@ hipError_t prepare_rdp_long(size_t bytes);
 // the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
 void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
                    int* lens, int stride, hipStream_t s);
-// mapping with known poses (k_gridmap.hip): n_scans scans as launch_rdp reads them, each at the pose in the first three doubles of the
-// record at poses + i * pose_pitch, counted into the two planes of a cols x rows grid; and a pair of planes published as an int8 grid
-void launch_grid_integrate(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols,
-                           int rows, double resol, double range_max, uint32_t* pass, uint32_t* hit, hipStream_t s);
+// The grid stack (host side: lsd_grid.hip).  The scans of a frame as its four scan-taking launchers receive them: n_scans scans as
+// launch_rdp reads them, each at the pose in the first three doubles of the record at poses + i * pose_pitch, in a cols x rows grid of
+// resol metres a cell, beams cut at range_max
+struct GridScans { const lsd_polar* scans; const int* lens; int n_scans, stride; const void* poses; size_t pose_pitch;
+                   int cols, rows; double resol, range_max; };
+// mapping with known poses (k_gridmap.hip): the scans counted into the two planes of the grid; and a pair of planes published as an int8 grid
+void launch_grid_integrate(const GridScans& g, uint32_t* pass, uint32_t* hit, hipStream_t s);
 void launch_grid_publish(const uint32_t* pass, const uint32_t* hit, size_t n_cells, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,
                          int8_t* grid, hipStream_t s);
-// correlative scan-to-grid matching (k_gridmatch.hip): the lookup plane of a pair of counter planes; and n_scans scans matched on it around
+// correlative scan-to-grid matching (k_gridmatch.hip): the lookup plane of a pair of counter planes; and the scans matched on it around
 // their poses, through `slots` (grid_match_slot_bytes(n_scans, na) bytes of workspace) into n_scans records
 void launch_grid_likelihood(const uint32_t* pass, const uint32_t* hit, int cols, int rows, uint32_t min_pass, uint32_t occ_num, uint32_t occ_den,
                             const lsd_grid_smear& smear, uint8_t* corr, hipStream_t s);
 size_t grid_match_slot_bytes(int n_scans, int na);
-void launch_grid_match(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
-                       double resol, double range_max, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out,
-                       hipStream_t s);
+void launch_grid_match(const GridScans& g, const uint8_t* corr, const lsd_grid_search& se, void* slots, lsd_grid_match_rec* out, hipStream_t s);
 void launch_grid_match_pick(int n_scans, const void* poses, size_t pose_pitch, const lsd_grid_search& se, const void* slots, lsd_grid_match_rec* out,
                             hipStream_t s);
 // the same match as a coarse-to-fine search (k_gridmatch_mr.hip): the plane of block maxima ((rows + block - 1) x (cols + block - 1)
@@ -190,15 +191,13 @@ void launch_grid_match_pick(int n_scans, const void* poses, size_t pose_pitch, c
 // whose sizes grid_match_mr_ws gives; stats may be null
 void launch_grid_coarse(const uint8_t* corr, int cols, int rows, int block, uint8_t* coarse, hipStream_t s);
 void grid_match_mr_ws(int n_scans, const lsd_grid_search& se, int block, size_t bytes[4]);
-void launch_grid_match_mr(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch, int cols, int rows,
-                          double resol, double range_max, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se,
-                          void* const ws[4], lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s);
+void launch_grid_match_mr(const GridScans& g, const uint8_t* corr, const uint8_t* coarse, int block, const lsd_grid_search& se, void* const ws[4],
+                          lsd_grid_match_rec* out, lsd_grid_match_mr_stats* stats, hipStream_t s);
 // the response around a match (k_gridresponse.hip): the records of either search -> the volume of R (grid_response_volume_bytes bytes,
 // the caller's or workspace) -> n_scans response records
 size_t grid_response_volume_bytes(int n_scans, const lsd_grid_response_par& rp);
-void launch_grid_response(const lsd_polar* scans, const int* lens, int n_scans, int stride, const void* poses, size_t pose_pitch,
-                          const lsd_grid_match_rec* records, int cols, int rows, double resol, double range_max, const uint8_t* corr, double ang_step,
-                          const lsd_grid_response_par& rp, uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s);
+void launch_grid_response(const GridScans& g, const lsd_grid_match_rec* records, const uint8_t* corr, double ang_step, const lsd_grid_response_par& rp,
+                          uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t

@@ -114,5 +114,5 @@ def test_default_host_capacity_is_the_header_s(lsdmod):
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lsd_hip.h")).read()
     m = re.search(r"Line capacity per image of the host entry points above \(default (\d+);", src)
     assert m and int(m.group(1)) == lsdmod.HOST_MAX_LINES_DEFAULT
-    ctx_src = open(os.path.join(os.path.dirname(lsdmod.__file__), "csrc", "lsd_ctx.hip")).read()
+    ctx_src = open(os.path.join(os.path.dirname(lsdmod.__file__), "csrc", "lsd_ctx.h")).read()
     assert re.search(r"int host_max_lines = %d;" % lsdmod.HOST_MAX_LINES_DEFAULT, ctx_src)
