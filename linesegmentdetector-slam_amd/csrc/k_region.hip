@@ -13,7 +13,7 @@
 // SPECULATIVELY ahead of a commit cursor and commit in seed order:
 //   * seeds are handed out in chunks of 32; every seed has a record in an LDS ring (state byte, snapshot epoch, a result word);
 //   * a wavefront first CLASSIFIES the seeds of its chunk, eight at a time: its eight 8-lane groups each grow one seed's region
-//     out of a 16x16-pixel window in LDS.  Nine regions in ten stay below regThre pixels and end there (nothing to mark, :228);
+//     out of a window of 16 x kWinRows pixels in LDS.  Nine regions in ten stay below regThre pixels and end there (nothing to mark, :228);
 //   * the others wait for a FULL evaluation by whichever wave is free: grow() with all 64 lanes (8 frontier pixels x 8
 //     neighbours per batch out of an LDS tile cache of packed pixel words), rectangle, Refiner incl. its regrow, NFA
 //     (eval_seed()); results that mark nothing are published in the ring, results that mark usedMap are stashed (record +
@@ -706,7 +706,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
     // ---- The small-region grower: eight seeds side by side ----
     // Nine seeds in ten grow a region of fewer than regThre (12..16) pixels and are dropped at once (:228), and such a region
     // keeps 8 of the 64 lanes of grow() busy.  So the wave's eight 8-lane GROUPS each grow the region of one seed, one list
-    // entry x its 8 neighbours per step, out of a private 16x16-pixel window of packed pixel words around the seed (LDS,
+    // entry x its 8 neighbours per step, out of a private window of 16 x kWinRows packed pixel words around the seed (LDS,
     // loaded once per seed: a small region cannot leave it without being given up first).  The candidates of an entry are
     // decided in reference order against the estimated sum vector exactly as grow() decides a batch pixel by pixel; a test too
     // close to call, a neighbour outside the window or a region that reaches regThre pixels hands the seed over to a full
@@ -719,8 +719,8 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
     int ncap = 1;                                           // a group gives its seed up when the region reaches ncap pixels
     if (g.regThre > 1.0 && g.degThre < 1.5) ncap = g.regThre >= (double)SCAP ? SCAP : (int)ceil(g.regThre);
     const float cos_tol_s = (float)g_tol0[2];
-    uint32_t* const swin = G_ARENA(wave) + grp * 256;       // this group's window (the arena holds no full evaluation meanwhile)
-    uint32_t* const slst = G_ARENA(wave) + 8 * 256 + grp * SCAP;   // this group's list: ly << 4 | lx
+    uint32_t* const swin = G_ARENA(wave) + grp * kWinWords;      // this group's window (the arena holds no full evaluation meanwhile)
+    uint32_t* const slst = G_ARENA(wave) + 8 * kWinWords + grp * SCAP;   // this group's list: ly << 4 | lx
     int gk = -1;                                            // seed of this lane's group, -1: idle
     int gn = 0, gi = 0, gex = 0, gsnap = 0;
     float gC = 0.0f, gS = 0.0f;                             // estimated sum vector of the group's region
@@ -747,13 +747,13 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
     // The windows fetched at the last refill are in LDS: seeds used meanwhile (:222) are skipped, the others start with their own pixel (:515-520)
     auto window_arrived = [&]() {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t sw = swin[7 * 16 + 7];              // (row 7, column 7 of the window: the seed's own word)
+        const uint32_t sw = swin[kSeedRow * 16 + 7];       // (row kSeedRow, column 7 of the window: the seed's own word)
         const bool used = gld && (sw & 3u) != 0u;
         if (gld && !used) {
             float s0, c0;
             fast_sincos(__uint_as_float(sw & ~3u), s0, c0);
             gC = c0; gS = s0; gn = 1; gi = 0; gex = 1;
-            if (kq == 0) { swin[7 * 16 + 7] = sw | 1u; slst[0] = (7u << 4) | 7u; }
+            if (kq == 0) { swin[kSeedRow * 16 + 7] = sw | 1u; slst[0] = ((uint32_t)kSeedRow << 4) | 7u; }
         }
         if (used) {
             if (kq == 0) st_st(&rg.state[gk & (RW - 1)], R_SKIP);
@@ -884,18 +884,19 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
                     const int sxj = __builtin_amdgcn_readlane(ch_sx, j), syj = __builtin_amdgcn_readlane(ch_sy, j);
                     if (grp == gg) { gk = ch_k0 + j; gld = true; gsnap = snap; }
                     gldm |= 1ull << (8 * gg);
-                    // the window: 16 rows of 16 packed pixel words around the seed, as they are in pw[]; lane l fetches quarter l & 3 of row l >> 2
-                    const int wx = sxj - 7, wy = syj - 7;
-                    uint32_t* const win = G_ARENA(wave) + gg * 256;
+                    // the window: kWinRows rows of 16 packed pixel words around the seed, as they are in pw[]; lane l < 4 kWinRows fetches quarter l & 3 of row l >> 2
+                    const int wx = sxj - 7, wy = syj - kSeedRow;
+                    uint32_t* const win = G_ARENA(wave) + gg * kWinWords;
                     const int row = lane >> 2, q4 = (lane & 3) * 4;
-                    if (wx >= 0 && wx + 15 < w && wy >= 0 && wy + 15 < h) {
+                    if (wx >= 0 && wx + 15 < w && wy >= 0 && wy + kWinRows - 1 < h) {
                         // LDS-DMA: lane l's 16 bytes land at M0 + 16 l -- the window's layout
                         const uint32_t* src = c.pw + (size_t)(wy + row) * w + (wx + q4);
                         const uint32_t la = (uint32_t)uni((int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)win);
                         // (M0 is the compiler's to manage and it says so; nothing else in this kernel uses it)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
-                        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(la), "v"(src) : "memory", "m0");
+                        if (kWinRows == 16 || row < kWinRows)   // (the lanes of the rows a shorter window lacks stay out: the next window begins there)
+                            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(la), "v"(src) : "memory", "m0");
 #pragma clang diagnostic pop
                     } else {
                         const int y = wy + row, x0 = wx + q4;
@@ -907,7 +908,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
                             if ((unsigned)(x0 + 2) < (unsigned)w) v2 = rowp[x0 + 2];
                             if ((unsigned)(x0 + 3) < (unsigned)w) v3 = rowp[x0 + 3];
                         }
-                        *reinterpret_cast<uint4*>(&win[lane * 4]) = uint4{v0, v1, v2, v3};
+                        if (kWinRows == 16 || row < kWinRows) *reinterpret_cast<uint4*>(&win[lane * 4]) = uint4{v0, v1, v2, v3};
                     }
                 }
                 gld_age = 0;
@@ -924,7 +925,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
             const bool act = gk >= 0 && !gld;
             const uint32_t e = slst[act ? gi : 0];
             const int lx = (int)(e & 15u) + ox, ly = (int)(e >> 4) + oy;
-            const bool inwin = ((unsigned)lx < 16u) & ((unsigned)ly < 16u);
+            const bool inwin = ((unsigned)lx < 16u) & ((unsigned)ly < (unsigned)kWinRows);
             const int cell = ((ly & 15) << 4) | (lx & 15);
             const uint32_t word = swin[cell];
             // a neighbour outside the window: the region is not small enough for this grower
@@ -966,7 +967,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
             const bool fin = act & (done | bail);
             const unsigned long long finm = ballot64(fin & (kq == 0));
             if (finm) {
-                // box of the list's pixels, relative to the seed (window cell 7, 7): what a line accepted before the seed's turn must not touch
+                // box of the list's pixels, relative to the seed (window cell 7, kSeedRow): what a line accepted before the seed's turn must not touch
                 const uint32_t e0 = slst[kq < gn ? kq : 0], e1 = slst[kq + 8 < gn ? kq + 8 : 0];
                 const int bx0 = imin8(min((int)(e0 & 15u), (int)(e1 & 15u))), bx1 = imax8(max((int)(e0 & 15u), (int)(e1 & 15u)));
                 const int by0 = imin8(min((int)(e0 >> 4), (int)(e1 >> 4))), by1 = imax8(max((int)(e0 >> 4), (int)(e1 >> 4)));
@@ -975,7 +976,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
                     const int r = gk & (RW - 1);
                     if (light) {
                         rg.snap[r] = (uint16_t)gsnap;
-                        rg.aux[r] = (uint32_t)(bx0 - 7 + 32) | ((uint32_t)(by0 - 7 + 32) << 6) | ((uint32_t)(bx1 - 7 + 32) << 12) | ((uint32_t)(by1 - 7 + 32) << 18);
+                        rg.aux[r] = (uint32_t)(bx0 - 7 + 32) | ((uint32_t)(by0 - kSeedRow + 32) << 6) | ((uint32_t)(bx1 - 7 + 32) << 12) | ((uint32_t)(by1 - kSeedRow + 32) << 18);
                         if (trace) { rnum[r * 2] = gn; rnum[r * 2 + 1] = gn << 2; }
                     }
                     st_st(&rg.state[r], light ? R_LIGHT : R_BIG);

@@ -13,8 +13,22 @@ constexpr int kWaitSleep = 127;         // s_sleep of a wave that found nothing 
 #endif
 constexpr int NW = LSD_REGION_NW;        // wavefronts (concurrent speculative seeds) per image
 constexpr int NS = LSD_REGION_NS;        // result slots per wave: seeds a wave may have evaluated ahead of the cursor
+// Four workgroups per CU (LSD_REGION_WAVES_PER_SIMD >= 4 on the 4-wave build) leave each 40 KB of LDS: the build then takes the small sizes
+// below.  Every one of them only moves the point at which an existing, slower path with the same answer is taken (a small region handed to a
+// full evaluation, a list written through to `spill`, one more round of staging), so the committed sequence is the same at either size.
+#if LSD_REGION_WAVES_PER_SIMD >= 4
+#define LSD_REGION_DIET 1
+#else
+#define LSD_REGION_DIET 0
+#endif
 #ifndef LSD_REGION_LCAP
-#define LSD_REGION_LCAP 512
+#define LSD_REGION_LCAP (LSD_REGION_DIET ? 256 : 512)
+#endif
+#ifndef LSD_REGION_WINROWS
+#define LSD_REGION_WINROWS (LSD_REGION_DIET ? 12 : 16)
+#endif
+#ifndef LSD_REGION_STAGE
+#define LSD_REGION_STAGE (LSD_REGION_DIET ? 16 : 32)
 #endif
 #ifndef LSD_REGION_NT
 #define LSD_REGION_NT 16
@@ -27,6 +41,14 @@ constexpr int LCAP = LSD_REGION_LCAP;   // entries of the list ring (a power of 
 constexpr int LMASK = LCAP - 1;
 constexpr int NT = LSD_REGION_NT;       // tile-cache slots per wave (8x8-pixel tiles of packed pixel words; a power of two; 16 measured as good as 32)
 static_assert((NT & (NT - 1)) == 0 && NT >= 8 && LCAP >= 256 && (LCAP & (LCAP - 1)) == 0, "tile slots and list ring: powers of two");
+// The small-region grower's window: 16 columns x kWinRows rows of packed pixel words with the seed in column 7 of row kSeedRow (16 rows: 7 above the
+// seed and 8 below; 12 rows: 5 and 6).  A region whose examined pixels leave the window goes to a full evaluation.
+constexpr int kWinRows = LSD_REGION_WINROWS;
+constexpr int kSeedRow = (kWinRows - 1) / 2;
+constexpr int kWinWords = 16 * kWinRows;
+static_assert(kWinRows >= 8 && kWinRows <= 16 && (kWinRows & 3) == 0, "window rows: a multiple of four (lane l fetches a quarter of row l >> 2), at most 16 (list entries are ly << 4 | lx)");
+constexpr int kStage = LSD_REGION_STAGE;   // list elements the serial sums stage per round (lds.h: stage4 / acc32)
+static_assert(kStage == 16 || kStage == 32, "staging rounds of 16 or 32 elements");
 constexpr int RING = 128;    // remembered bounding boxes of recently accepted lines
 constexpr int kSetMax = 255;           // certified sets per image and launch (labels 1 .. kSetMax)
 constexpr int kSetMinPixels = 64;      // ... of at least this many pixels

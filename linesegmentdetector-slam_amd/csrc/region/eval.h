@@ -37,8 +37,8 @@ __device__ __noinline__ double refine_tol(int cw_, int sx, int sy, int num, doub
         if (m == 0ull) continue;
         ptNum += __builtin_popcountll(m);
         // (points outside the width contribute +0.0, which leaves a sum that started at +0.0 unchanged to the bit)
-        for (int half = 0; half < 2; half++) {
-            const int cnt = min(32, num - base - 32 * half);
+        for (int half = 0; half < kStageRounds; half++) {
+            const int cnt = min(kStage, num - base - kStage * half);
             if (cnt <= 0) break;
             stage4(wave, lane, half, flag ? degDif : 0.0, flag ? sq : 0.0, 0.0, 0.0);
             S = acc32(wave, lane, cnt, S);

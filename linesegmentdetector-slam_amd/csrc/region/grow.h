@@ -25,8 +25,8 @@ __device__ __noinline__ void exact_sums(int cw_, int n_) {
             const double2 v = c.sc[(size_t)(pk >> 16) * w + (pk & 0xffffu)];
             vs = v.x; vc = v.y;
         }
-        for (int half = 0; half < 2; half++) {
-            const int cnt = min(32, n - base - 32 * half);
+        for (int half = 0; half < kStageRounds; half++) {
+            const int cnt = min(kStage, n - base - kStage * half);
             if (cnt <= 0) break;
             stage4(wave, lane, half, vc, vs, 0.0, 0.0);
             S = acc32(wave, lane, cnt, S);
@@ -429,7 +429,11 @@ __device__ __noinline__ int grow(int cw_, int sx_, int sy_, double regDeg0_, dou
                     const unsigned long long inv = ~rest;
                     cnt = min(cnt, inv ? __builtin_ctzll(inv) : 64);
                 }
-                const int eidx = e < cnt ? (int)G_WL(wave)[wi + e] : 0;
+                // (the address is built from a scalar the compiler cannot see through: left alone it keeps "worklist + 2 e" in a register across
+                //  the whole sweep, which at 128 registers is a scratch reload in front of every batch)
+                uint32_t wl_at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)(G_WL(wave) + wi);
+                asm volatile("; worklist cursor %0" : "+s"(wl_at));
+                const int eidx = e < cnt ? (int)*(__attribute__((address_space(3))) const uint16_t*)(uintptr_t)(wl_at + 2u * (uint32_t)e) : 0;
                 wi += batch(cnt, eidx, false, Cf, Sf, rV, Vn, nrat);
             }
         }

@@ -6,16 +6,18 @@
 // One arena of 32-bit words per wave, used in two ways.  A full evaluation: [list ring, LCAP words (packed y<<16 | x)][the sweep
 // worklist, WCAP 16-bit entries + a dummy slot for predicated stores: list indices of the entries that still have a growable
 // neighbour; the next sweep's worklist is written IN PLACE behind the read cursor][tile cache, NT x 64 words: (fp32 angle & ~3) |
-// member << 1 | banned].  The small-region grower (seed loop): [eight 16x16-pixel windows][eight lists of SCAP entries] from the
+// member << 1 | banned].  The small-region grower (seed loop): [eight windows of 16 x kWinRows pixels][eight lists of SCAP entries] from the
 // start of the arena -- nothing of a full evaluation survives it (tw_small in the seed loop).
 constexpr int SCAP = 16;                  // list entries of a small-region group
-constexpr int kSmallWords = 8 * 256 + 8 * SCAP;
+constexpr int kSmallWords = 8 * kWinWords + 8 * SCAP;
 constexpr int WLW = ((kSmallWords - LCAP - NT * 64 >= 256 ? kSmallWords - LCAP - NT * 64 : 256) + 3) & ~3; // words of the worklist (16-byte multiple: windows and tiles are written as uint4)
 constexpr int WCAP = 2 * WLW - 2;                            // its entries; [WCAP]: the dummy slot
 constexpr int kTwOff = LCAP + WLW;
 constexpr int kArenaWords = kTwOff + NT * 64 > kSmallWords ? kTwOff + NT * 64 : kSmallWords;
 constexpr int kMvCap = kArenaWords - LCAP - 1;               // RegionRadiusReducer's scratch: worklist + tile cache (+ a dummy slot)
 static_assert(WLW >= 192, "the NFA's column scan keeps 3 x 64 ints in the worklist's place");
+// both layouts fit the arena; a neighbour one row or column outside a window is still read (and ignored), from inside the arena
+static_assert(kSmallWords <= kArenaWords && kTwOff + NT * 64 <= kArenaWords && 7 * kWinWords + 255 < kArenaWords, "the small grower's and the full evaluation's layouts both fit the arena");
 __shared__ __attribute__((aligned(16))) uint32_t g_arena[NW][kArenaWords];
 #define G_ARENA(w) (&g_arena[w][0])
 #define G_LST(w) (G_ARENA(w))
@@ -27,7 +29,7 @@ __shared__ WState g_ws[NW];
 __shared__ RCtx g_ctx[NW];                                // the wave's context: the out-of-line stages get the wave number and read it here
                                                           // (a struct passed by value travels through scratch memory at every call)
 __shared__ double g_tol0[3];                              // the global tolerance (degThre) with its sine and cosine: every first grow uses it
-__shared__ double g_acc[NW][32 * 4];                      // staging of the serial (bit-exact) sums: 32 list elements x up to 4 terms
+__shared__ double g_acc[NW][kStage * 4];                  // staging of the serial (bit-exact) sums: kStage list elements x up to 4 terms
 // what eval_seed() leaves for its caller (the rectangle itself stays in g_ws[wave].rec)
 struct EvalOut {
     int skip, outcome, num, num0, rec_pk;
@@ -42,16 +44,17 @@ __shared__ EvalOut g_eo[NW];
 __shared__ double g_par[4];                               // degThre, regThre, aliPro, denThre of the launch (Geom)
 
 // The reference's sums over a region (moments, angle sums, Refiner's statistics) are plain left-to-right fp64 additions, and
-// their rounding decides accept/reject ties, so they are added in exactly that order: the lanes compute the terms of 32 list
+// their rounding decides accept/reject ties, so they are added in exactly that order: the lanes compute the terms of kStage list
 // elements at a time and stage them in LDS, then lane j (j < 4) adds term j of the elements one after the other.  (One
 // ds_read + one v_add per element and sum, all sums at once, instead of broadcasting every term to every lane.)
-__device__ __forceinline__ void stage4(int wave, int lane, int half, double t0, double t1, double t2, double t3) {
-    if ((lane >> 5) == half) {
-        double* q = &g_acc[wave][(lane & 31) * 4];
+constexpr int kStageRounds = 64 / kStage;   // rounds that take the 64 elements of a wave's chunk through the staging
+__device__ __forceinline__ void stage4(int wave, int lane, int part, double t0, double t1, double t2, double t3) {
+    if (lane / kStage == part) {
+        double* q = &g_acc[wave][(lane % kStage) * 4];
         q[0] = t0; q[1] = t1; q[2] = t2; q[3] = t3;
     }
 }
-__device__ __forceinline__ double acc32(int wave, int lane, int cnt, double S) {   // cnt (wave-uniform) <= 32 staged elements
+__device__ __forceinline__ double acc32(int wave, int lane, int cnt, double S) {   // cnt (wave-uniform) <= kStage staged elements
     const double* q = &g_acc[wave][lane & 3];
     int e = 0;
     for (; e + 8 <= cnt; e += 8) {

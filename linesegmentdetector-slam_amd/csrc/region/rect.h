@@ -15,8 +15,8 @@ __device__ __noinline__ void rect_convert(int cw_, int num, double regdeg, doubl
         const int x = (int)(pkx & 0xffffu), y = (int)(pkx >> 16);
         const double wgt = valid ? c.mag[(size_t)y * w + x] : 0.0;
         const double ax = wgt * x, ay = wgt * y;
-        for (int half = 0; half < 2; half++) {
-            const int cnt = min(32, num - base - 32 * half);
+        for (int half = 0; half < kStageRounds; half++) {
+            const int cnt = min(kStage, num - base - kStage * half);
             if (cnt <= 0) break;
             stage4(wave, lane, half, ax, ay, wgt, 0.0);
             S = acc32(wave, lane, cnt, S);
@@ -35,8 +35,8 @@ __device__ __noinline__ void rect_convert(int cw_, int num, double regdeg, doubl
         const double wgt = valid ? c.mag[(size_t)y * w + x] : 0.0;
         const double ddy = y - cenY, ddx = x - cenX;
         const double a = wgt * (ddy * ddy), b = wgt * (ddx * ddx), cc = wgt * ddx * ddy;
-        for (int half = 0; half < 2; half++) {
-            const int cnt = min(32, num - base - 32 * half);
+        for (int half = 0; half < kStageRounds; half++) {
+            const int cnt = min(kStage, num - base - kStage * half);
             if (cnt <= 0) break;
             stage4(wave, lane, half, a, b, -cc, wgt);     // Ixy -= cc (:642): adding the negated term is the same operation
             S = acc32(wave, lane, cnt, S);
@@ -129,7 +129,7 @@ __device__ __noinline__ int radius_reduce_impl(int cw_, int sx, int sy, int num,
     double rad = rad1 > rad2 ? rad1 : rad2;
     bool removed_any = false;
     const int wave = __builtin_amdgcn_readfirstlane(c.wave);
-    unsigned long long* const msk = reinterpret_cast<unsigned long long*>(g_acc[wave]);   // keep-masks of up to 128 chunks of 64 entries
+    unsigned long long* const msk = reinterpret_cast<unsigned long long*>(g_acc[wave]);   // keep-masks of up to kStage * 4 chunks of 64 entries
     uint32_t* const mv = reinterpret_cast<uint32_t*>(G_WL(wave));                          // up to kMvCap moved entries: the worklist and the tile cache behind it
     while (den < denThre) {                                                        // :775
         rad *= 0.75;
@@ -140,7 +140,7 @@ __device__ __noinline__ int radius_reduce_impl(int cw_, int sx, int sy, int num,
         // holes among those slots (ascending) receive the kept points of the slots >= K, taken from the back (descending).
         // That is computed 64 entries at a time; lists too long for the scratch arrays take the reference's own loop below.
         const int nchunks = (num + 63) >> 6;
-        bool parallel = nchunks <= 128;
+        bool parallel = nchunks <= kStage * 4;
         int K = 0;
         if (parallel) {
             for (int ci = 0; ci < nchunks; ci++) {

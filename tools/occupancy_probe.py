@@ -2,7 +2,7 @@
 """Developer probe: how full the GPU is in the timed configuration (eight steps in flight, 4-wave region stage, help off).
 Every image's workgroup records when it ran (s_memrealtime at its start and end, its XCC); the probe reads those records of each
 step before the step's slot is used again and prints the number of resident region-stage workgroups over a steady window
-(768 = three per CU), per XCC, next to the event times of the step's kernels.
+(1 024 = four per CU; 768 = three with -DLSD_REGION_WAVES_PER_SIMD=3), per XCC, next to the event times of the step's kernels.
    tools/occupancy_probe.py [depth [steps]]"""
 import importlib, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -49,7 +49,7 @@ res = np.zeros_like(ts); rx = np.zeros((8, len(ts)))
 for (b, e, x) in zip(b0, e0, A[:, 2].astype(int)):
     i0, i1 = np.searchsorted(ts, [b, e])
     res[i0:i1] += 1; rx[x & 7, i0:i1] += 1
-print("resident region workgroups: mean %.0f of 768 (p10 %.0f p50 %.0f p90 %.0f max %.0f); per XCC mean: %s" % (
+print("resident region workgroups: mean %.0f of 1024 (p10 %.0f p50 %.0f p90 %.0f max %.0f); per XCC mean: %s" % (
     res.mean(), *np.percentile(res, [10, 50, 90]), res.max(), " ".join("%.0f" % v for v in rx.mean(1))))
 print("share of the window with < 384 resident: %.2f, < 576: %.2f, >= 700: %.2f" % ((res < 384).mean(), (res < 576).mean(), (res >= 700).mean()))
 print("workgroup time per image: mean %.1f ms (%.0f Mcycles), max %.1f ms" % ((e0 - b0).mean(), A[:, 3].mean() / 1e6, (e0 - b0).max()))
