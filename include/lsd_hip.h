@@ -451,6 +451,53 @@ int lsd_enqueue_localize_resume_maps_device(lsd_ctx *ctx, const lsd_map_ref *map
 typedef struct lsd_map_frame { double mapResol, mapOriX, mapOriY; } lsd_map_frame;
 int lsd_enqueue_fa_carry_rebase_device(lsd_ctx *ctx, lsd_fa_carry *d_carry, int n_seq, const int32_t *d_key, int32_t key,
                                        lsd_map_frame from, lsd_map_frame to, void *stream);
+/* The grid match response fused into the carry: a measurement update of the carry's 9-state filter with a response record (the section
+ * "the response around a match" below) as the measurement -- the filter's own closing lines (myfa::ukf: K = Pxz Pzz^-1, x += K Zdiff, P =
+ * P1 - K Pxz^T) with H = [I3 0], so that the NEXT tick starts from the corrected lastPose (csrc/k_facorrect.hip; restated
+ * in tests/fa_correct_cases.py).  In place on d_carry[0..n_seq), asynchronous on `stream`, one launch, no workspace, no atomics: it
+ * allocates nothing and waits for nothing.  fp64 without FMA; every sum runs ascending from 0.0; P(i,j) = state.P[j * 9 + i].
+ * Per sequence s: its carry, the frames_pitch ORIGINAL poses of its slots -- the first 24 bytes of the record at d_poses + (s *
+ * frames_pitch + t) * pose_pitch, the poses the match was given (a Localizer's tick: its states, pitch 720) -- and the response records
+ * d_resp[s * frames_pitch + t].  The first test that fires decides; each outcome is exactly one flag; report fields that were not
+ * computed are +0.0 and slot is -1; the carry keeps every byte unless the outcome is APPLIED:
+ *   0. d_key != NULL and d_key[s] != key, read ON THE DEVICE as the re-base reads it: nothing of s is written, carry or report
+ *   1. fabs(x[0] + 1) < 0.0001, the "no pose yet" test of the re-base: NO_POSE
+ *   2. any of the 90 doubles of the state not finite: NOT_FINITE
+ *   3. slot = the LARGEST t in 0..frames_pitch-1 whose original pose's 24 bytes equal the 24 bytes of state.x[0..2] (bytes, not values:
+ *      -0.0 is not +0.0); none: STALE.  The carry holds the state of the last frame the tick took and slots past n_frames hold zeroed
+ *      states, so this finds that frame without n_frames, a host copy or a wait -- and refuses a carry that has moved on since the match
+ *   4. r = d_resp[s * frames_pitch + slot]: VALID clear, or NONE, EMPTY or MISMATCH set: NO_RESPONSE (slot reported); r.x, r.y, r.ang or
+ *      one of r.cov[0..5] not finite: NOT_FINITE (slot reported).  The *_NOT_PEAK bits stop nothing: the offset of such an axis is zero and
+ *      its covariance weighs it
+ *   5. R(0,0) = cov[0] * cov_scale + floor_xy, R(1,1) = cov[2] * cov_scale + floor_xy, R(2,2) = cov[5] * cov_scale + floor_ang, R(0,1) =
+ *      R(1,0) = cov[1] * cov_scale, R(0,2) = R(2,0) = cov[3] * cov_scale, R(1,2) = R(2,1) = cov[4] * cov_scale;  S(r,q) = P(r,q) + R(r,q),
+ *      r, q < 3 (P is not symmetrised);  cof(r,q) = S(r1,q1) * S(r2,q2) - S(r1,q2) * S(r2,q1) with cyclic indices;  det = (cof(0,0) *
+ *      S(0,0) + cof(1,0) * S(1,0)) + cof(2,0) * S(2,0);  invdet = 1 / det;  Sinv(j,i) = cof(i,j) * invdet.  !(det > 0) or invdet not
+ *      finite: SINGULAR (det, slot reported)
+ *   6. innov[q] = z[q] - x[q], z = (r.x, r.y, r.ang), angles not wrapped;  t[i] = sum_j Sinv(i,j) * innov[j];  d2 = sum_i innov[i] * t[i].
+ *      gate > 0 and !(d2 <= gate): GATED, a NaN d2 included (innov, d2, det, slot reported)
+ *   7. APPLIED (innov, d2, det, slot reported):  K(i,q) = sum_{r<3} P(i,r) * Sinv(r,q), i < 9;  x'[i] = x[i] + sum_q K(i,q) * innov[q];
+ *      P'(i,j) = P(i,j) - sum_{r<3} K(i,r) * P(j,r).  odom, ang_sum, ang_count, frames and is_offset keep their bytes: the next frame
+ *      computes its own angle offset from the corrected x[2]
+ * (A NaN that the arithmetic itself makes of finite inputs -- an overflow -- is reported with the sign and payload the hardware gives it.)
+ * With frames_pitch > 1 only the response of the LAST frame taken is fused: the states of earlier frames are already consumed by the loop.
+ * d_rep may be NULL.  Refused before anything is enqueued, LSD_ERR_INVALID, outputs untouched: a null ctx, d_carry, d_poses or d_resp;
+ * n_seq <= 0; frames_pitch outside 1..4096; pose_pitch < 24 or not a multiple of 8; a pointer that is not 8-byte aligned (d_key: 4-byte);
+ * one of the four parameters not finite or negative. */
+typedef struct lsd_grid_response_rec lsd_grid_response_rec;
+typedef struct lsd_fa_correct_par { double cov_scale, floor_xy, floor_ang, gate; } lsd_fa_correct_par;   /* 32 bytes */
+typedef struct lsd_fa_correct_rep {                                                                       /* 48 bytes */
+    double innov[3]; double d2; double det; int32_t slot; uint32_t flags;
+} lsd_fa_correct_rep;
+enum { LSD_FA_CORRECT_APPLIED = 1, LSD_FA_CORRECT_NO_POSE = 2, LSD_FA_CORRECT_NOT_FINITE = 4, LSD_FA_CORRECT_STALE = 8,
+       LSD_FA_CORRECT_NO_RESPONSE = 16, LSD_FA_CORRECT_SINGULAR = 32, LSD_FA_CORRECT_GATED = 64 };
+int lsd_enqueue_fa_carry_correct_device(lsd_ctx *ctx, lsd_fa_carry *d_carry, int n_seq, int frames_pitch, const void *d_poses,
+                                        size_t pose_pitch, const lsd_grid_response_rec *d_resp, const int32_t *d_key, int32_t key,
+                                        lsd_fa_correct_par par, lsd_fa_correct_rep *d_rep /* may be NULL */, void *stream);
+/* Host convenience: carries (n_seq, updated in place), poses (n_seq x frames_pitch, packed), resp (n_seq x frames_pitch) and rep (n_seq,
+ * may be NULL) are host arrays; every sequence takes part (no key).  Blocking. */
+int lsd_fa_carry_correct(lsd_ctx *ctx, lsd_fa_carry *carries, int n_seq, int frames_pitch, const lsd_position *poses,
+                         const lsd_grid_response_rec *resp, lsd_fa_correct_par par, lsd_fa_correct_rep *rep);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:

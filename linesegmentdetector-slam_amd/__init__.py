@@ -130,6 +130,17 @@ FA_CARRY_DTYPE = np.dtype([("state", FA_STATE_DTYPE), ("odom", POS_DTYPE), ("ang
 assert FA_CARRY_DTYPE.itemsize == 768
 
 
+# the grid match response fused into a carry (include/lsd_hip.h): its parameters and its report
+class lsd_fa_correct(C.Structure):     # the C side's lsd_fa_correct_par
+    _fields_ = [("cov_scale", C.c_double), ("floor_xy", C.c_double), ("floor_ang", C.c_double), ("gate", C.c_double)]
+
+
+FA_CORRECT_DTYPE = np.dtype([("innov", "f8", (3,)), ("d2", "f8"), ("det", "f8"), ("slot", "i4"), ("flags", "u4")])   # lsd_fa_correct_rep
+assert FA_CORRECT_DTYPE.itemsize == 48 and C.sizeof(lsd_fa_correct) == 32
+(FA_CORRECT_APPLIED, FA_CORRECT_NO_POSE, FA_CORRECT_NOT_FINITE, FA_CORRECT_STALE, FA_CORRECT_NO_RESPONSE, FA_CORRECT_SINGULAR,
+ FA_CORRECT_GATED) = 1, 2, 4, 8, 16, 32, 64
+
+
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -209,6 +220,8 @@ _ABI = {
     "lsd_enqueue_localize_maps_device": (_i, _maps_args),
     "lsd_enqueue_localize_resume_maps_device": (_i, _maps_args),
     "lsd_enqueue_fa_carry_rebase_device": (_i, [_vp, _vp, _i, _vp, C.c_int32, lsd_map_frame, lsd_map_frame, _vp]),
+    "lsd_enqueue_fa_carry_correct_device": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, C.c_int32, lsd_fa_correct, _vp, _vp]),
+    "lsd_fa_carry_correct": (_i, [_vp, _vp, _i, _i, _vp, _vp, lsd_fa_correct, _vp]),
     "lsd_enqueue_map_update_device": (_i, [_vp, _vp, _i, _i, _dbl, _dbl, _ppar, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -628,6 +641,31 @@ class Context:
         if not d_carry or int(n_seq) <= 0:
             raise LsdError(LSD_ERR_INVALID, "a null carry, or n_seq <= 0")
         return self._chk(self.L.lsd_enqueue_fa_carry_rebase_device(self.h, d_carry, int(n_seq), d_key, int(key), f, t, stream))
+
+    def enqueue_fa_carry_correct_device(self, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_resp, d_key=None, key=0, correct=None,
+                                        d_rep=None, stream=None):
+        """lsd_enqueue_fa_carry_correct_device: the grid match response fused into the n_seq carries at d_carry, in place,
+        asynchronous on `stream`, on raw device addresses.  Per sequence: the frames_pitch ORIGINAL poses of its slots (the first 24 bytes
+        of the records at d_poses, pose_pitch apart: the poses the match was given) and its response records at d_resp
+        (GRID_RESPONSE_DTYPE); the slot whose pose equals the carry's, byte for byte, is the one fused.  d_key: None (every sequence), or
+        device int32 [n_seq]: sequence s takes part iff d_key[s] == key, read when the kernel runs.  correct: fa_correct().  d_rep: None,
+        or n_seq reports of FA_CORRECT_DTYPE."""
+        return self._chk(self.L.lsd_enqueue_fa_carry_correct_device(self.h, d_carry, int(n_seq), int(frames_pitch), d_poses, int(pose_pitch),
+                                                                    d_resp, d_key, int(key), fa_correct(correct), d_rep, stream))
+
+    def fa_carry_correct(self, carries, poses, resp, correct=None):
+        """lsd_fa_carry_correct from host arrays: carries FA_CARRY_DTYPE [n_seq], poses float64 [n_seq, frames_pitch, 3] (the poses the match
+        was given), resp GRID_RESPONSE_DTYPE [n_seq, frames_pitch].  Returns (the carries after the update, the reports: FA_CORRECT_DTYPE
+        [n_seq]); the arguments are not modified.  Blocking."""
+        cy = np.array(carries, FA_CARRY_DTYPE).reshape(-1)
+        po = np.ascontiguousarray(poses, np.float64)
+        rs = np.ascontiguousarray(resp)
+        if po.ndim != 3 or po.shape[0] != len(cy) or po.shape[2] != 3 or rs.dtype != GRID_RESPONSE_DTYPE or rs.shape != po.shape[:2]:
+            raise LsdError(LSD_ERR_INVALID, "carries FA_CARRY_DTYPE [n], poses [n, frames_pitch, 3], resp GRID_RESPONSE_DTYPE [n, frames_pitch]")
+        rep = np.zeros(len(cy), FA_CORRECT_DTYPE)
+        self._chk(self.L.lsd_fa_carry_correct(self.h, cy.ctypes.data, len(cy), po.shape[1], po.ctypes.data, rs.ctypes.data, fa_correct(correct),
+                                              rep.ctypes.data))
+        return cy, rep
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
@@ -1084,6 +1122,24 @@ def grid_response(response=None, rx=3, ry=3, ra=1, keep=(1, 2)):
     rx, ry, ra, kn, kd = response
     kn, kd = _u32s(kn, kd, limit=(1 << 32,) * 2)
     return lsd_grid_response(int(rx), int(ry), int(ra), kn, kd)
+
+
+def fa_correct(correct=None, cov_scale=1.0, floor_xy=1.0, floor_ang=1.0, gate=0.0):
+    """An lsd_fa_correct: `correct` itself, a dict of cov_scale / floor_xy / floor_ang / gate, a tuple of the four in that order, or
+    keywords (None / True: the defaults).  R = the response's covariance x cov_scale + the floors on its diagonal (pixels^2, pixels^2,
+    degrees^2; the defaults are the reference filter's own R = I); gate > 0 refuses a correction whose squared Mahalanobis distance
+    exceeds it (0: no gate, as the reference has none).  LsdError(LSD_ERR_INVALID) for a value that is not finite or negative."""
+    if isinstance(correct, lsd_fa_correct):
+        return correct
+    if isinstance(correct, dict):
+        a = dict(correct)
+        correct = (a.get("cov_scale", cov_scale), a.get("floor_xy", floor_xy), a.get("floor_ang", floor_ang), a.get("gate", gate))
+    if correct is None or correct is True:
+        correct = (cov_scale, floor_xy, floor_ang, gate)
+    vals = tuple(float(v) for v in correct)
+    if len(vals) != 4 or not all(np.isfinite(v) and v >= 0 for v in vals):
+        raise LsdError(LSD_ERR_INVALID, "cov_scale, floor_xy, floor_ang and gate must be finite and >= 0")
+    return lsd_fa_correct(*vals)
 
 
 def map_frame(frame):
@@ -1793,16 +1849,82 @@ class _Ticks:
         S, k, ts, _ = self._last_tick
         d_sc, d_ln, d_st = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
         b_state, b_scan = FA_STATE_DTYPE.itemsize, 16 * self.n_beams
+        for first, count in self._runs(robots, k):
+            mapper._enqueue(self.ctx, d_sc + first * b_scan, d_ln + first * 4, count, self.n_beams, d_st + first * b_state, b_state,
+                            ts.cuda_stream)
+
+    @staticmethod
+    def _runs(robots, k):
+        """(first slot, slot count) of every run of neighbouring robots among `robots` (ascending indices), k slots per robot."""
         robots = [int(r) for r in robots]
         a = 0
         while a < len(robots):
             b = a
             while b + 1 < len(robots) and robots[b + 1] == robots[b] + 1:
                 b += 1
-            first, count = robots[a] * k, (robots[b] - robots[a] + 1) * k
-            mapper._enqueue(self.ctx, d_sc + first * b_scan, d_ln + first * 4, count, self.n_beams, d_st + first * b_state, b_state,
-                            ts.cuda_stream)
+            yield robots[a] * k, (robots[b] - robots[a] + 1) * k
             a = b + 1
+
+    def _refine_and_integrate_last_tick(self, mapper, robots, key, search, refresh, smear, block, response, integrate_at, correct):
+        """refine_and_integrate_last_tick for the robots `robots` (ascending indices; None: all of them, in one chain): GridMapper._chain per
+        run of neighbouring robots on the tick's staging, the lookup plane refreshed once in front of the first; then, with `correct`, the
+        correction of the carries behind the response stage, for the sequences `key` = (d_key, key) selects on the device."""
+        import torch
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        if correct is not None and response is None:
+            raise LsdError(LSD_ERR_INVALID, "correct needs the response stage: give response")
+        par = None if correct is None else fa_correct(correct)
+        S, k, ts, _ = self._last_tick
+        d_sc, d_ln, d_st = self._scans.data_ptr(), self._lens.data_ptr(), self._out.data_ptr()
+        b_state, b_scan = FA_STATE_DTYPE.itemsize, 16 * self.n_beams
+        chain = lambda first, count, fresh: mapper._chain(self.ctx, d_sc + first * b_scan, d_ln + first * 4, count, self.n_beams,
+                                                          d_st + first * b_state, b_state, search, ts, block, response=response, integrate=True,
+                                                          refresh=fresh, smear=smear, integrate_at=integrate_at)
+        if robots is None:
+            got = chain(0, S * k, refresh)
+            parts = list(got) if isinstance(got, tuple) else [got]
+        else:
+            if integrate_at not in ("match", "response") or (integrate_at == "response" and response is None):
+                raise LsdError(LSD_ERR_INVALID, "integrate_at is 'match' or, with response given, 'response'")
+            widths = [GRID_MATCH_DTYPE.itemsize] + ([GRID_RESPONSE_DTYPE.itemsize] if response is not None else [])
+            with torch.cuda.stream(ts):
+                parts = [torch.zeros((S * k, w), dtype=torch.uint8, device=mapper._planes.device) for w in widths]
+            if refresh:
+                mapper.likelihood_device(smear, ts, block)                   # once: every run is matched on the plane of before the call
+            held = []
+            for first, count in self._runs(robots, k):
+                got = chain(first, count, False)
+                got = got if isinstance(got, tuple) else (got,)
+                with torch.cuda.stream(ts):
+                    for whole, run in zip(parts, got):
+                        whole[first:first + count].copy_(run)
+                held.append(got)
+            mapper._held_rec = held                                          # the integrations read them: alive until the next ones
+        if par is not None:
+            parts.append(self._correct_last_tick(parts[-1], par, key))
+        return tuple(parts) if len(parts) > 1 else parts[0]
+
+    def _correct_last_tick(self, responses, correct, key):
+        """correct_last_tick for the sequences `key` = (d_key, key) selects on the device: one launch on the tick's stream, the poses the
+        tick's states (pitch 720), the carries the localiser's own.  The reports: a new CUDA uint8 tensor [n_robots, 48], zero bytes for a
+        robot the key leaves out."""
+        import torch
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        S, k, ts, _ = self._last_tick
+        if (not isinstance(responses, torch.Tensor) or not responses.is_cuda or not responses.is_contiguous() or
+                responses.numel() * responses.element_size() != S * k * GRID_RESPONSE_DTYPE.itemsize):
+            raise LsdError(LSD_ERR_INVALID, "responses must be a contiguous CUDA tensor of n_robots * k records of 192 bytes")
+        par = fa_correct(correct)
+        with torch.cuda.stream(ts):
+            rep = torch.zeros((S, FA_CORRECT_DTYPE.itemsize), dtype=torch.uint8, device=responses.device)
+        self.ctx.enqueue_fa_carry_correct_device(self._carry.data_ptr(), S, k, self._out.data_ptr(), FA_STATE_DTYPE.itemsize, responses.data_ptr(),
+                                                 key[0], key[1], par, rep.data_ptr(), ts.cuda_stream)
+        self._held_correct = responses                                       # the launch reads it: alive until the next one
+        return rep
 
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """lidar float64 [S, k, n_beams, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames
@@ -2027,22 +2149,30 @@ class Localizer(_Ticks):
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
 
-    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match"):
+    def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match",
+                                       correct=None):
         """integrate_last_tick with the correlative match in front (GridMapper.match_and_integrate_device): on the last
         tick's stream and behind the tick, the mapper's lookup plane is refreshed (refresh=False: kept as it is), every frame of the tick is
         matched on it around the state it produced (pitch 720), and integrated at the record's pose.  Nothing is read back and nothing
         waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 56] (GRID_MATCH_DTYPE; slot s * k + t is frame t of robot s).
         block = 2..16: the same records by the coarse-to-fine search.  response (grid_response()) given: the response
         stage behind the match, and (records, response records: a CUDA uint8 tensor [n_robots * k, 192],
-        GRID_RESPONSE_DTYPE) is returned; then integrate_at="response" integrates at the refined poses instead of the records'."""
-        if self._last_tick is None:
-            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
-        if not isinstance(mapper, GridMapper):
-            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
-        S, k, ts, _ = self._last_tick
-        return mapper._chain(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
-                             FA_STATE_DTYPE.itemsize, search, ts, block, response=response, integrate=True, refresh=refresh, smear=smear,
-                             integrate_at=integrate_at)
+        GRID_RESPONSE_DTYPE) is returned; then integrate_at="response" integrates at the refined poses instead of the records'.
+        correct (fa_correct(); True: its defaults) given -- it needs response, else LSD_ERR_INVALID --: correct_last_tick behind the
+        response stage, and its reports are returned last in the tuple.  None, the default, enqueues nothing more."""
+        return self._refine_and_integrate_last_tick(mapper, None, (None, 0), search, refresh, smear, block, response, integrate_at, correct)
+
+    def correct_last_tick(self, responses, correct=None):
+        """The grid match response fused into the robots' carries (lsd_enqueue_fa_carry_correct_device): a measurement
+        update of each robot's 9-state filter with its response record as the measurement, weighed by the record's covariance (correct:
+        fa_correct(); None: its defaults), so that the NEXT tick starts from the corrected pose.  responses: the response records of the last
+        tick's slots, a CUDA uint8 tensor [n_robots * k, 192], as refine_and_integrate_last_tick(response=...) returns them for that tick.
+        On the last tick's stream and behind the tick; the poses are the tick's states (pitch 720), the carries the localiser's; nothing is
+        read back or waits.  Per robot the slot whose state equals the carry's pose, byte for byte, is the one fused -- the last frame the
+        tick took (with k > 1 the earlier frames' responses are not fused: the loop has consumed their states) --, so a second call on the
+        same tick finds no such slot and changes nothing (FA_CORRECT_STALE).  Returns the reports: a CUDA uint8 tensor [n_robots, 48]
+        (FA_CORRECT_DTYPE: the innovation, its squared Mahalanobis distance, det S, the slot and one FA_CORRECT_* flag)."""
+        return self._correct_last_tick(responses, correct, (None, 0))
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         cx, m = self.ctx, self._pairs[0].current
@@ -2226,6 +2356,25 @@ class FleetLocalizer(_Ticks):
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         self._integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i))
+
+    def refine_and_integrate_last_tick(self, mapper, map_id, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match",
+                                       correct=None):
+        """Localizer.refine_and_integrate_last_tick for the robots that were on map `map_id` when the last tick was enqueued, as
+        integrate_last_tick(mapper, map_id) selects them: the lookup plane is refreshed once, then match, response and integration are
+        enqueued per run of neighbouring robots.  The returned tensors cover all n_robots * k slots (the reports: n_robots); the slots of
+        the other robots are zero bytes.  correct given: the correction reads the robots' map ids on the device (d_key = the ids, key =
+        map_id), so a robot an assign() has moved off the map since keeps its carry; the other robots' carries keep every byte."""
+        i = self._map_id(map_id)
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        return self._refine_and_integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i), (self._map_of.data_ptr(), i), search,
+                                                    refresh, smear, block, response, integrate_at, correct)
+
+    def correct_last_tick(self, responses, map_id, correct=None):
+        """Localizer.correct_last_tick for the robots on map `map_id`, read on the device when the kernel runs (d_key = the robots' map ids,
+        key = map_id): responses covers all n_robots * k slots, as refine_and_integrate_last_tick(mapper, map_id, response=...) returns
+        them; a robot on another map keeps its carry and its report is zero bytes."""
+        return self._correct_last_tick(responses, correct, (self._map_of.data_ptr(), self._map_id(map_id)))
 
     def _feature_scan(self, n, k, d_scans, d_lens, d_n_lines, d_n_pts, stream):
         self.ctx.enqueue_feature_scan_maps_device(d_scans, d_lens, n, self.n_beams, self._table, self._map_of.data_ptr(), k, self._lines.data_ptr(), d_n_lines,

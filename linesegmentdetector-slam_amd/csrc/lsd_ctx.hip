@@ -1266,6 +1266,47 @@ int lsd_enqueue_fa_carry_rebase_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_
     return LSD_OK;
 }
 
+// The grid match response fused into the carries (k_facorrect.hip): the argument check of both entries, then one launch.
+static bool fa_correct_refused(const lsd_ctx* c, const void* carry, int n_seq, int frames_pitch, const void* poses, size_t pose_pitch,
+                               const void* resp, const void* key, const lsd_fa_correct_par& par, const void* rep) {
+    auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; };
+    auto bad = [](double v) { return !std::isfinite(v) || v < 0; };
+    return !c || !carry || !poses || !resp || n_seq <= 0 || frames_pitch < 1 || frames_pitch > 4096 || pose_pitch < 24 || pose_pitch % 8 != 0 ||
+           off8(carry) || off8(poses) || off8(resp) || off8(rep) || (reinterpret_cast<uintptr_t>(key) & 3) != 0 || bad(par.cov_scale) ||
+           bad(par.floor_xy) || bad(par.floor_ang) || bad(par.gate);
+}
+
+int lsd_enqueue_fa_carry_correct_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const void* d_poses, size_t pose_pitch,
+                                        const lsd_grid_response_rec* d_resp, const int32_t* d_key, int32_t key, lsd_fa_correct_par par,
+                                        lsd_fa_correct_rep* d_rep, void* stream) {
+    if (fa_correct_refused(c, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_resp, d_key, par, d_rep)) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_fa_correct(d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_resp, d_key, key, par, d_rep, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LSD_OK;
+}
+
+int lsd_fa_carry_correct(lsd_ctx* c, lsd_fa_carry* carries, int n_seq, int frames_pitch, const lsd_position* poses,
+                         const lsd_grid_response_rec* resp, lsd_fa_correct_par par, lsd_fa_correct_rep* rep) {
+    if (fa_correct_refused(c, carries, n_seq, frames_pitch, poses, sizeof(lsd_position), resp, nullptr, par, rep)) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_seq, n = ns * (size_t)frames_pitch;
+    lsd_fa_carry* d_cy; lsd_position* d_po; lsd_grid_response_rec* d_re; lsd_fa_correct_rep* d_rp;
+    auto regions = [&](Carver& k) { k(d_cy, ns); k(d_po, n); k(d_re, n); k(d_rp, ns); };
+    HIPCHK(c, carve(c->stage, regions));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_cy, carries, ns * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_po, poses, n * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_re, resp, n * sizeof(lsd_grid_response_rec), hipMemcpyHostToDevice, s));
+    const int st = lsd_enqueue_fa_carry_correct_device(c, d_cy, n_seq, frames_pitch, d_po, sizeof(lsd_position), d_re, nullptr, 0, par,
+                                                       rep ? d_rp : nullptr, s);
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(carries, d_cy, ns * sizeof(lsd_fa_carry), hipMemcpyDeviceToHost, s));
+    if (rep) HIPCHK(c, hipMemcpyAsync(rep, d_rp, ns * sizeof(lsd_fa_correct_rep), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LSD_OK;
+}
+
 // What the replay loop runs against.  One map: its fields; with d_n_map (the live-map entries) the map's line count is read on the device
 // and n_map is its capacity.  Or the table (the *_maps entries; a non-null `maps` is what selects it): sequence s runs against
 // maps[d_map_of[s]] and the single-map fields are unused.  Everything the host sizes is sized from n_map, resp. the table's largest.

@@ -231,6 +231,9 @@ struct FaArgs {
 void launch_fa_frame(const FaArgs& a, int n_seq, bool prepare, hipStream_t s);   // prepare = false: the fuse kernel alone (ctl, cand, counts given)
 // carries from one map frame to another, in place (k_fa.hip: k_fa_rebase): x[0..1] scaled and shifted, the rates and P scaled
 void launch_fa_rebase(lsd_fa_carry* carry, int n_seq, const int32_t* key_of, int32_t key, double sc, double tx, double ty, hipStream_t s);
+// the grid match response fused into the carries, in place (k_facorrect.hip: k_fa_correct): one launch, no workspace
+void launch_fa_correct(lsd_fa_carry* carry, int n_seq, int frames_pitch, const void* poses, size_t pose_pitch, const lsd_grid_response_rec* resp,
+                       const int32_t* key_of, int32_t key, lsd_fa_correct_par par, lsd_fa_correct_rep* rep, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and
