@@ -174,7 +174,9 @@ int lsd_gather_layout(int n_total, int world, int *per_rank, size_t *counts_word
  *   2. all-gather of the padded counts:  d_counts_all [world][per_rank + 2] int32 -- rank r's per-image counts (clamped to
  *      max_lines, zero-padded), then [per_rank] = rows in its slab, [per_rank + 1] = flags: bit 0 it had to drop rows (more than
  *      cap_rows lines or an image over max_lines), bit 1 an image the region stage gave up (lsd_gather_unpack: LSD_ERR_CAPACITY
- *      resp. LSD_ERR_INTERNAL, with everything that did arrive in its outputs);
+ *      resp. LSD_ERR_INTERNAL, with everything that did arrive in its outputs; LSD_ERR_INTERNAL outranks LSD_ERR_CAPACITY).  The torch
+ *      packer of the Python package (dist.pack_lines) builds the same slab and the same clamped counts but folds both bits into one
+ *      bool, over == (flags != 0): the two-bit word exists in this ABI only;
  *   3. all-gather of the slabs:          d_slabs_all [world][cap_rows] lsd_line.
  * Image g of the batch (rank r = its shard, local index j) has its lines at d_slabs_all[r][sum of counts[r][0..j)].
  * ~22 MB per GPU and step for the 512 x 2048^2 bench batch at cap_rows = 512 per image.
@@ -183,8 +185,9 @@ int lsd_gather_layout(int n_total, int world, int *per_rank, size_t *counts_word
 int lsd_gather_lines(lsd_ctx *ctx, const lsd_comm *comm, const lsd_line *d_lines, const int32_t *d_counts, int n_local, int max_lines,
                      int n_total, int cap_rows, int32_t *d_counts_all, lsd_line *d_slabs_all, void *stream);
 /* Host side of the hand-off: turns HOST copies of the two gathered arrays into offsets_out[n_total + 1] and (if lines_out is
- * not NULL) the lines of all images in global image order (lines_cap records available).  LSD_ERR_CAPACITY if a rank flagged
- * dropped rows (what arrived is still unpacked). */
+ * not NULL) the lines of all images in global image order (lines_cap records available; LSD_ERR_INVALID if more arrive).
+ * LSD_ERR_CAPACITY if a rank flagged dropped rows (flag bit 0), LSD_ERR_INTERNAL if one flagged an image given up (bit 1; it
+ * outranks the other); what arrived is still unpacked: the images of a rank from its slab's cut on are shorter by what it dropped. */
 int lsd_gather_unpack(const int32_t *counts_all, const lsd_line *slabs_all, int n_total, int world, int cap_rows, int32_t *offsets_out,
                       lsd_line *lines_out, size_t lines_cap);
 

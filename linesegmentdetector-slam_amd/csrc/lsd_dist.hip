@@ -187,15 +187,17 @@ int lsd_gather_lines(lsd_ctx* c, const lsd_comm* comm, const lsd_line* d_lines, 
     HIPCHK(c, hipMemsetAsync(c->ga_slab.get(), 0, sizeof(lsd_line) * (size_t)cap_rows, s));
     launch_pack_lines(d_lines, d_counts, n_local, max_lines, per, cap_rows, c->ga_cnt.get(), c->ga_cnt.get() + (per + 2), c->ga_slab.get(), s);
     HIPCHK(c, hipGetLastError());
-    if (comm->all_gather(comm->user, c->ga_cnt.get(), d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
-        comm->all_gather(comm->user, c->ga_slab.get(), d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0) {
-        c->err = "lsd_gather_lines: the communicator's all_gather failed";
-        return LSD_ERR_HIP;
-    }
+    const bool failed = comm->all_gather(comm->user, c->ga_cnt.get(), d_counts_all, sizeof(int32_t) * (size_t)(per + 2), s) != 0 ||
+                        comm->all_gather(comm->user, c->ga_slab.get(), d_slabs_all, sizeof(lsd_line) * (size_t)cap_rows, s) != 0;
+    // (recorded after a failed collective as well: the pack, and a first collective that did go out, still use the staging buffers on s)
     if (!c->ga_ev) HIPCHK(c, hipEventCreateWithFlags(&c->ga_ev, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ga_ev, s));
     c->ga_ev_valid = true;
     c->last_stream = s;
+    if (failed) {
+        c->err = "lsd_gather_lines: the communicator's all_gather failed";
+        return LSD_ERR_HIP;
+    }
     return LSD_OK;
 }
 

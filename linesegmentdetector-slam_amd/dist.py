@@ -136,8 +136,11 @@ def torch_comm(group=None):
 def gather_lines_abi(ctx, comm, lines_i64, counts, n_total, cap_rows, stream=None):
     """The C ABI's hand-off (lsd_gather_lines) on torch tensors: lines_i64 [n_local, max_lines, 10] int64 and counts [n_local] int32 of
     this rank's shard -> (counts_all int32 [world, per + 2], slabs int64 [world, cap_rows, 10]) on every rank, enqueued on `stream`
-    (a raw hipStream_t / torch stream .cuda_stream; None: the current torch stream), no host synchronisation.  Same packing as
-    pack_lines() above; lsd.gather_unpack turns host copies of the two arrays into offsets + lines in global image order."""
+    (a raw hipStream_t / torch stream .cuda_stream; None: the current torch stream), no host synchronisation.  The slab and the
+    clamped counts are those of pack_lines() above; the flags are NOT encoded alike: the C ABI's word counts_all[r, per + 1] carries two
+    bits (bit 0: rows were dropped -- more than cap_rows lines or an image over max_lines; bit 1: an image the region stage gave up,
+    count < 0), pack_lines() folds both into one bool (over == (word != 0)).  lsd.gather_unpack turns host copies of the two arrays
+    into offsets + lines in global image order."""
     import importlib
     lsd = importlib.import_module(__package__)
     per, _ = lsd.gather_layout(n_total, comm.world)

@@ -10,6 +10,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import gather_cases as gc
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -110,22 +112,6 @@ def test_gather_line_lists_padded_form_world2(cap_rows, expect_over):
             assert len(dense) <= slabs.shape[1] and not slabs[r, len(dense):].any()
 
 
-def _pack_like_the_device(lines, counts, per, cap_rows):
-    """What lsd_gather_lines' device pack leaves on one rank (include/lsd_hip.h): cpad int32[per + 2] and a slab of cap_rows records
-    (10 int64 words each), image-major, rows past cap_rows dropped and flagged."""
-    n, max_lines, _ = lines.shape
-    c = np.clip(counts, 0, max_lines).astype(np.int32)
-    cpad = np.zeros(per + 2, np.int32)
-    cpad[:n] = c
-    dense = np.concatenate([lines[j, :c[j]] for j in range(n)] + [np.zeros((0, 10), np.int64)])
-    slab = np.zeros((cap_rows, 10), np.int64)
-    keep = min(len(dense), cap_rows)
-    slab[:keep] = dense[:keep]
-    cpad[per] = keep
-    cpad[per + 1] = 1 if (len(dense) > cap_rows or (counts > max_lines).any() or (counts < 0).any()) else 0
-    return cpad, slab
-
-
 @pytest.mark.parametrize("n_total,world,cap_rows,expect_over", [(7, 2, 64, False), (8, 2, 64, False), (1, 2, 8, False), (13, 3, 64, False), (7, 2, 6, True)])
 def test_c_abi_hand_off_host_side_with_a_host_memory_communicator(n_total, world, cap_rows, expect_over, lsdmod):
     """The host side of the C ABI's multi-GPU hand-off (include/lsd_hip.h: lsd_shard_range, lsd_gather_layout, lsd_gather_unpack) for
@@ -142,7 +128,7 @@ def test_c_abi_hand_off_host_side_with_a_host_memory_communicator(n_total, world
         lo, hi = lsdmod.shard_range(n_total, world, r)
         assert (lo, hi) == ldist.shard_range(n_total, world, r)
         lines, counts = _fake_shard(lo, hi, 8)
-        ranks.append(_pack_like_the_device(lines.numpy(), counts.numpy(), per, cap_rows))
+        ranks.append(gc.pack(lines.numpy(), counts.numpy(), per, 8, cap_rows))    # the device layout, two-bit flag word included
     # the host-memory communicator: rank r's callback finds every rank's send buffer in a table keyed by the collective's number
     table = {}
     recv = {r: [np.zeros((world, per + 2), np.int32), np.zeros((world, cap_rows, 10), np.int64)] for r in range(world)}
