@@ -773,6 +773,11 @@ int lsd_debug_set_stamp_budget(lsd_ctx *ctx, unsigned grows);
  * result.  From the ENVIRONMENT the shipped library takes two settings only, when a context is created: LSD_REGION_HELP (as
  * lsd_set_region_help) and LSD_REGION_POOL (calls with at most that many images, 0..16, default 4, get helper-only workgroups). */
 int lsd_debug_set_tuning(lsd_ctx *ctx, const char *name, int value);
+/* Test hook: fills the workspace arrays that the front end writes (GaussImage, magMap, degMap, the (sin, cos) table, the packed pixel
+ * words, the sorted lists and their lengths) with 0xFF bytes over their whole capacity (synchronises).  The next call has to store
+ * every value itself: without this a store it leaves out hides behind what the previous call left at the same address.  Call it
+ * after a call of the same shape and batch size, so that the workspace is already the size the next call needs. */
+int lsd_debug_poison_front(lsd_ctx *ctx);
 
 /* Copies an intermediate of image `image` of the LAST run/enqueue to host memory (synchronises).
  *   GAUSS/MAG/DEG  h*w doubles      (GaussImage / magMap / degMap, myLSD.cpp:143-147)
@@ -791,13 +796,22 @@ int lsd_debug_set_tuning(lsd_ctx *ctx, const char *name, int value);
  *                                   cycles_select*, cycles_commit*, filter_skips*
  *                                   (summed over the wavefronts that share an image; * = counted by the developer build only,
  *                                   `make stats` -> liblsdhip_stats.so, and 0 in the product build)
+ *   SINCOS         h*w*2 doubles    (sin, cos) of degMap as the gradient pass leaves them for RegionGrower (myLSD.cpp:545-546), one pair
+ *                                   per pixel.  Entries are DEFINED ONLY WHERE THE PIXEL'S CODE IS 0 after the gradient pass (PW & 3,
+ *                                   == usedMap before the region stage): (0, 1) on row 0 / column 0 (an interior pixel without
+ *                                   gradient has code 1 whenever gradThre > 0); every other entry is whatever an earlier call left there
+ *   PW             h*w uint32       the packed pixel word itself, the only thing RegionGrower reads per neighbour: the fp32 angle
+ *                                   with its two lowest mantissa bits replaced by the code 0 free / 1 banned by the gradient threshold
+ *                                   / 2 marked by a rejected region / 3 banned by an accepted line (STATE is this word reduced to usedMap)
+ *   GRAD_TIES      1 int32          the gradient pass's share of lsd_last_sensitivity (which also needs the region stage to have run)
  * After a call that took the fused front end (lsd_set_fused_front) there is no GaussImage to copy: GAUSS runs the Gaussian kernel alone
  * on the requested image of the last call's INPUT, so for lsd_enqueue_batch_device the caller's d_maps must still be alive and
  * unchanged when GAUSS is fetched (a map the call itself rewrote, LSD_FLAG_WRITEBACK_MAP, is read as rewritten; the host entry points
  * keep their own copy).
  * Returns LSD_ERR_INVALID if `bytes` is smaller than the item. */
 enum { LSD_DBG_GAUSS = 1, LSD_DBG_MAG, LSD_DBG_DEG, LSD_DBG_STATE, LSD_DBG_ORDER, LSD_DBG_ORDER_VAL,
-       LSD_DBG_NB, LSD_DBG_MAXGRAD, LSD_DBG_RECS, LSD_DBG_SEEDS, LSD_DBG_NSEED, LSD_DBG_STATS };
+       LSD_DBG_NB, LSD_DBG_MAXGRAD, LSD_DBG_RECS, LSD_DBG_SEEDS, LSD_DBG_NSEED, LSD_DBG_STATS,
+       LSD_DBG_SINCOS, LSD_DBG_PW, LSD_DBG_GRAD_TIES };
 int lsd_debug_fetch(lsd_ctx *ctx, int image, int what, void *out, size_t bytes);
 
 /* Test hook: evaluates the DEVICE build of the path's transcendental functions on host arrays of n

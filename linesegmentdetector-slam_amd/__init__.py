@@ -22,7 +22,7 @@ LSD_OK, LSD_ERR_INVALID, LSD_ERR_NO_DEVICE, LSD_ERR_HIP, LSD_ERR_UNSUPPORTED, LS
 LSD_FLAG_WRITEBACK_MAP = 1
 STAGE_ALL, STAGE_GAUSS, STAGE_GRAD, STAGE_SORT, STAGE_REGION = range(5)
 (DBG_GAUSS, DBG_MAG, DBG_DEG, DBG_STATE, DBG_ORDER, DBG_ORDER_VAL, DBG_NB, DBG_MAXGRAD, DBG_RECS, DBG_SEEDS,
- DBG_NSEED, DBG_STATS) = range(1, 13)
+ DBG_NSEED, DBG_STATS, DBG_SINCOS, DBG_PW, DBG_GRAD_TIES) = range(1, 16)
 
 # LSD defaults, LSD/baseFunc.h:64-68
 lsd_sca, lsd_sig, lsd_angThre, lsd_denThre, pseBin = 0.3, 0.6, 22.5, 0.7, 1024
@@ -184,6 +184,7 @@ _ABI = {
     "lsd_set_region_waves": (_i, [_vp, _i]),
     "lsd_set_region_help": (_i, [_vp, _i]),
     "lsd_debug_set_stamp_budget": (_i, [_vp, C.c_uint]),
+    "lsd_debug_poison_front": (_i, [_vp]),
     "lsd_set_cost_history": (_i, [_vp, _i]),
     "lsd_debug_set_tuning": (_i, [_vp, C.c_char_p, _i]),
     "lsd_set_host_max_lines": (_i, [_vp, _i]),
@@ -868,6 +869,10 @@ class Context:
         """Test hook (lsd_debug_set_stamp_budget): curMap stamp ids per wavefront and run before the stamps are cleared."""
         self._chk(self.L.lsd_debug_set_stamp_budget(self.h, grows))
 
+    def debug_poison_front(self):
+        """Test hook (lsd_debug_poison_front): 0xFF bytes into every array the front end fills, so that the next call's omissions show."""
+        self._chk(self.L.lsd_debug_poison_front(self.h))
+
     def set_region_waves(self, waves):
         """0: automatic, 4 / 8: force the region-stage variant (results are identical)."""
         self._chk(self.L.lsd_set_region_waves(self.h, waves))
@@ -891,7 +896,11 @@ class Context:
             return get(what, np.float64, npx).reshape(h, w)
         if what == DBG_STATE:
             return get(what, np.uint32, npx).reshape(h, w)
-        if what == DBG_NB:
+        if what == DBG_PW:                               # the packed pixel word: fp32 angle & ~3 | code (STATE: its usedMap value)
+            return get(what, np.uint32, npx).reshape(h, w)
+        if what == DBG_SINCOS:                           # [..., 0] sin, [..., 1] cos; defined only where the pixel's code is 0
+            return get(what, np.float64, 2 * npx).reshape(h, w, 2)
+        if what in (DBG_NB, DBG_GRAD_TIES):
             return int(get(what, np.int32, 1)[0])
         if what == DBG_NSEED:
             return int(get(what, np.int32, 1)[0])

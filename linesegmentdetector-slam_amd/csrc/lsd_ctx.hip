@@ -425,6 +425,26 @@ int lsd_debug_set_stamp_budget(lsd_ctx* c, unsigned grows) {
     return LSD_OK;
 }
 
+// Test hook: every array the front end has to fill is set to 0xFF bytes (NaN doubles, words of all ones, a list length of -1) over its
+// whole capacity, so that a store the next call leaves out shows in what lsd_debug_fetch returns instead of hiding behind the previous
+// call's value at the same address.  The maxima and the near-tie counts are the call's own to clear and are left alone.
+int lsd_debug_poison_front(lsd_ctx* c) {
+    if (!c) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    Workspace& w = c->ws;
+    auto fill = [&](void* p, size_t bytes) { return (p && bytes) ? hipMemset(p, 0xFF, bytes) : hipSuccess; };
+    HIPCHK(c, fill(w.gauss.get(), w.gauss.capacity() * sizeof(double)));
+    HIPCHK(c, fill(w.mag.get(), w.mag.capacity() * sizeof(double)));
+    HIPCHK(c, fill(w.deg.get(), w.deg.capacity() * sizeof(double)));
+    HIPCHK(c, fill(w.sc.get(), w.sc.capacity() * sizeof(double2)));
+    HIPCHK(c, fill(w.pw.get(), w.pw.capacity() * sizeof(uint32_t)));
+    HIPCHK(c, fill(w.ord.get(), w.ord.capacity() * sizeof(uint32_t)));
+    HIPCHK(c, fill(w.nb.get(), w.nb.capacity() * sizeof(int32_t)));
+    HIPCHK(c, hipDeviceSynchronize());
+    return LSD_OK;
+}
+
 int lsd_set_trace(lsd_ctx* c, int on) {
     if (!c) return LSD_ERR_INVALID;
     c->trace = on != 0;
@@ -819,6 +839,9 @@ int lsd_debug_fetch(lsd_ctx* c, int image, int what, void* out, size_t bytes) {
             src = w.stats.get() + (size_t)image * kStatWords; need = 8 * kStatWords;
             if (bytes > need) { const size_t all = (size_t)(c->last_n - image) * need; need = bytes < all ? bytes / need * need : all; }
             break;
+        case LSD_DBG_SINCOS: src = w.sc.get() + off; need = npx * 16; break;      // (defined where the pixel's code is 0: lsd_hip.h)
+        case LSD_DBG_PW: src = w.pw.get() + off; need = npx * 4; break;           // (STATE without the reduction to usedMap below)
+        case LSD_DBG_GRAD_TIES: src = w.ties() + image; need = 4; break;
         default: return LSD_ERR_INVALID;
     }
     if (bytes < need) return LSD_ERR_INVALID;

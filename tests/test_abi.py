@@ -68,6 +68,19 @@ def test_scaled_size(built, lsdmod):
     assert lsdmod.scaled_size(2048, 2048) == (614, 614)
 
 
+def test_debug_items_keep_their_numbers(built, lsdmod):
+    """lsd_debug_fetch's items in the header and in the Python mirror: those up to STATS keep the values they always had, newer ones
+    are appended."""
+    src = open(os.path.join(ROOT, "include", "lsd_hip.h")).read()
+    m = re.search(r"enum \{ (LSD_DBG_GAUSS = 1,[^}]*)\};", src)
+    names = [n.strip().split(" ")[0] for n in m.group(1).split(",")]
+    assert names == ["LSD_DBG_" + n for n in ("GAUSS", "MAG", "DEG", "STATE", "ORDER", "ORDER_VAL", "NB", "MAXGRAD", "RECS", "SEEDS", "NSEED",
+                                               "STATS", "SINCOS", "PW", "GRAD_TIES")]
+    for i, n in enumerate(names):
+        assert getattr(lsdmod, n[4:]) == i + 1, n
+    assert (lsdmod.DBG_GAUSS, lsdmod.DBG_STATS, lsdmod.DBG_SINCOS) == (1, 12, 13)
+
+
 def test_strerror_and_version(built, lsdmod):
     lib = lsdmod.load_library()
     assert lib.lsd_abi_version() == 1
