@@ -729,6 +729,65 @@ int lsd_grid_response(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int
                       const lsd_grid_match_rec *records, lsd_map_param map_param, double range_max, const uint8_t *corr,
                       double ang_step, lsd_grid_response_par response, lsd_grid_response_rec *out, uint32_t *volume);
 
+/* --- ray casting on the grid: the expected range of every beam, its class against the map, a screened scan ---------------------- */
+/* What a scan should look like from a pose (csrc/k_gridray.hip; restated in tests/grid_ray_cases.py).  Scans, lengths
+ * and poses as lsd_enqueue_grid_integrate_device reads them; d_grid is an int8 rows x cols OccupancyGrid of map_param's frame, the layout
+ * lsd_enqueue_grid_publish_device writes and lsd_enqueue_map_update_device reads (an outside SLAM's map serves as well).  A cell is read
+ * as the map update reads it: byte 255 unknown, 0 free, every other byte occupied; a cell outside the grid is unknown.  fp64 without FMA,
+ * the integration's helpers.  For scan n at pose (x, y, ang):
+ *   a scan the integration skips whole is not cast; beam i < len is CAST iff its angle and th = angle + ang / 180.0 * pi are finite (the
+ *   measured range plays no part);  (s, c) = sin, cos(th);  x0 = (int)round(x), y0 = (int)round(y), x1 = (int)round(x + range_max * c /
+ *   mapResol), y1 = (int)round(y + range_max * s / mapResol);  the ray's cells k = 0 .. n: the integration's closed form, start cell included
+ *   k_hit = the smallest k whose cell is occupied, else -1;  k_unk = the smallest k whose cell is unknown and that lies before k_hit (any k
+ *   if there is no hit), else -1
+ *   dist(k) = sqrt(ddx * ddx + ddy * ddy) * mapResol with ddx = (double) cx_k - x, ddy = (double) cy_k - y;  r_exp = dist(k_hit) or +inf,
+ *   r_unk = dist(k_unk) or +inf;  (cx, cy) = the hit cell, or (x1, y1) without one
+ *   the class, with m the measured range and d = m - r_exp:  not cast: NOT_CAST, every other byte of the record 0;  m NaN or <= 0:
+ *   NO_MEASUREMENT;  m == +inf or m > range_max: LONG with a hit, else UNEXPLORED with an unknown cell, else AGREE_FREE;  otherwise
+ *   |d| <= tol: AGREE;  d > tol: LONG;  else r_unk <= m: UNEXPLORED;  else SHORT (something in front of what the map holds)
+ * The ray runs to the range_max end cell, not to the measured one, so it can pass one cell beside the cell in which the integration
+ * counted the beam's hit; tol absorbs that.
+ * d_out: the record of beam i of scan n at d_out[n * stride + i], i < len only (slots beyond stay untouched).  d_sum[n]: the input pose's
+ * bits, n[c] = the beams of class c over i < len, judged = n[2] + n[3] + n[4] + n[5]; CONSISTENT iff judged >= min_beams and (uint64)
+ * (n[2] + n[3]) * ok_den >= (uint64) judged * ok_num; a scan skipped whole: SKIPPED, all counts 0.  With gate != 0 a scan that was cast
+ * and is not consistent gets x = -1.0 (the "no pose" sentinel; y and ang stay): an array of these records IS a d_poses argument of pitch
+ * 64, and every grid entry then skips that scan by the rule it has.
+ * d_scans_out (may be NULL; rows at the pitch of d_scans): for i < len the angle's bits, and the range's bits unless (drop_mask >> class)
+ * & 1, then the quiet NaN 0x7FF8000000000000, which integration, both matchers and the response skip.  d_scans_out == d_scans is
+ * allowed (a beam is read and written by the same lane); any other overlap of the two is refused.
+ * Two launches, asynchronous on `stream`; no workspace, no allocation, copy or host wait.  LSD_ERR_INVALID before anything is enqueued,
+ * outputs untouched: whatever lsd_enqueue_grid_integrate_device refuses on the arguments the two share; d_grid, d_out or d_sum null; tol
+ * not finite or negative; drop_mask >= 128; ok_den == 0 or ok_num > ok_den; d_out or d_sum not 8-byte aligned; d_scans_out not 16-byte
+ * aligned or partially overlapping d_scans.  n_scans == 0 launches nothing.
+ * (The parameters' type is lsd_grid_ray_par and the record's lsd_grid_ray; the host entry is lsd_grid_raycast.) */
+typedef struct lsd_grid_ray_par { double tol; uint32_t drop_mask, min_beams, ok_num, ok_den; int gate; } lsd_grid_ray_par;
+typedef struct lsd_grid_ray {              /* 32 bytes */
+    double r_exp, r_unk; int32_t cx, cy, k_hit; uint32_t cls;
+} lsd_grid_ray;
+typedef struct lsd_grid_ray_sum {          /* 64 bytes; its head is a pose, so an array of these IS a d_poses argument (pitch 64) */
+    double x, y, ang; uint32_t n[7]; uint32_t judged; uint32_t flags; uint32_t pad;
+} lsd_grid_ray_sum;
+#define LSD_GRID_RAY_NOT_CAST 0u
+#define LSD_GRID_RAY_NO_MEASUREMENT 1u
+#define LSD_GRID_RAY_AGREE_FREE 2u
+#define LSD_GRID_RAY_AGREE 3u
+#define LSD_GRID_RAY_SHORT 4u
+#define LSD_GRID_RAY_LONG 5u
+#define LSD_GRID_RAY_UNEXPLORED 6u
+#define LSD_GRID_RAY_CONSISTENT 1u
+#define LSD_GRID_RAY_SKIPPED 2u
+int lsd_enqueue_grid_raycast_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                    const void *d_poses, size_t pose_pitch_bytes, lsd_map_param map_param, double range_max,
+                                    const int8_t *d_grid, lsd_grid_ray_par par, lsd_grid_ray *d_out, lsd_grid_ray_sum *d_sum,
+                                    lsd_polar *d_scans_out, void *stream);
+/* Host convenience: scans, lens, poses (n_scans packed lsd_position) and the grid (rows x cols of map_param) travel to the context's
+ * staging, lsd_enqueue_grid_raycast_device runs, and `out` (n_scans * stride records; those at i < len are written), `sum` (n_scans
+ * records) and, unless NULL, `scans_out` (n_scans * stride readings; those at i < len are written) come back.  Blocking.  lens[i]
+ * outside 0..stride: LSD_ERR_INVALID. */
+int lsd_grid_raycast(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
+                     lsd_map_param map_param, double range_max, const int8_t *grid, lsd_grid_ray_par par, lsd_grid_ray *out,
+                     lsd_grid_ray_sum *sum, lsd_polar *scans_out);
+
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */
 void lsd_scaled_size(int cols, int rows, double sca, int *w, int *h);

@@ -118,6 +118,22 @@ assert GRID_RESPONSE_DTYPE.itemsize == 192 == C.sizeof(lsd_grid_response_rec) an
  GRID_RESPONSE_MISMATCH) = 1, 2, 4, 8, 16, 32, 64
 SCORE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "f8")])   # lsd_match_score
 
+
+# ray casting on the grid (include/lsd_hip.h): its parameters, the record of a beam and the summary of a scan
+class lsd_grid_ray_par(C.Structure):
+    _fields_ = [("tol", C.c_double), ("drop_mask", C.c_uint32), ("min_beams", C.c_uint32), ("ok_num", C.c_uint32), ("ok_den", C.c_uint32),
+                ("gate", C.c_int)]
+
+
+GRID_RAY_DTYPE = np.dtype([("r_exp", "f8"), ("r_unk", "f8"), ("cx", "i4"), ("cy", "i4"), ("k_hit", "i4"), ("cls", "u4")])      # lsd_grid_ray
+GRID_RAY_SUM_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("n", "u4", (7,)), ("judged", "u4"), ("flags", "u4"),
+                               ("pad", "u4")])                                                                                # lsd_grid_ray_sum
+assert GRID_RAY_DTYPE.itemsize == 32 and GRID_RAY_SUM_DTYPE.itemsize == 64 and C.sizeof(lsd_grid_ray_par) == 32
+(GRID_RAY_NOT_CAST, GRID_RAY_NO_MEASUREMENT, GRID_RAY_AGREE_FREE, GRID_RAY_AGREE, GRID_RAY_SHORT, GRID_RAY_LONG,
+ GRID_RAY_UNEXPLORED) = range(7)
+GRID_RAY_CLASSES = ("not_cast", "no_measurement", "agree_free", "agree", "short", "long", "unexplored")
+GRID_RAY_CONSISTENT, GRID_RAY_SKIPPED = 1, 2
+
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
 FA_STATE_DTYPE = np.dtype([("x", "f8", (9,)), ("P", "f8", (81,))])
 FA_REPORT_DTYPE = np.dtype([("estimate", POS_DTYPE), ("score", "f8"), ("scan_pose", POS_DTYPE), ("n_pairs", "i4"), ("n_kept", "i4"),
@@ -242,6 +258,8 @@ _ABI = {
     "lsd_enqueue_grid_response_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, lsd_map_param, _dbl, _vp, _dbl, lsd_grid_response, _vp, _vp,
                                               _vp]),
     "lsd_grid_response": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, lsd_map_param, _dbl, _vp, _dbl, lsd_grid_response, _vp, _vp]),
+    "lsd_enqueue_grid_raycast_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, lsd_grid_ray_par, _vp, _vp, _vp, _vp]),
+    "lsd_grid_raycast": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, lsd_grid_ray_par, _vp, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -722,6 +740,35 @@ class Context:
                                             float(range_max), planes[0].ctypes.data, planes[1].ctypes.data))
         return planes[0], planes[1]
 
+    # -- ray casting on the grid (k_gridray.hip) -------------------------------------
+    def enqueue_grid_raycast_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, map_param, range_max, d_grid, ray, d_out,
+                                    d_sum, d_scans_out=None, stream=None):
+        """lsd_enqueue_grid_raycast_device on device addresses: scans, lengths and poses as enqueue_grid_integrate_device reads them, cast
+        through the int8 grid d_grid (rows x cols of map_param); ray: an lsd_grid_ray_par or what grid_ray() takes (its tol must be
+        given: no mapper is known here).  d_out receives n_scans x stride records of 32 bytes (GRID_RAY_DTYPE; those at i < len),
+        d_sum n_scans records of 64 bytes (GRID_RAY_SUM_DTYPE), which are a d_poses argument of pitch 64 themselves; d_scans_out (or
+        None; d_scans itself is allowed) the screened scans.  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_raycast_device(self.h, d_scans, d_lens, int(n_scans), int(stride), d_poses, int(pose_pitch),
+                                                                _map_param(map_param), float(range_max), d_grid, grid_ray(ray), d_out, d_sum,
+                                                                d_scans_out, stream))
+
+    def grid_raycast(self, scans, lens, poses, map_param, range_max, grid, ray, out=None, sums=None, scans_out=None):
+        """lsd_grid_raycast from host arrays: scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3], grid int8 [rows, cols].
+        Returns (records GRID_RAY_DTYPE [n, stride], summaries GRID_RAY_SUM_DTYPE [n], screened scans float64 [n, stride, 2]): new
+        arrays that start from out / sums / scans_out where given (zeros otherwise) -- only the slots at i < len are written.  Blocking."""
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
+        mp = _map_param(map_param)
+        gr = np.ascontiguousarray(grid, np.int8)
+        if not ok or gr.shape != (mp.oriMapRow, mp.oriMapCol):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], grid int8 [rows, cols]")
+        n, stride = sc.shape[:2]
+        o = np.zeros((n, stride), GRID_RAY_DTYPE) if out is None else np.array(out, GRID_RAY_DTYPE).reshape(n, stride)
+        su = np.zeros(n, GRID_RAY_SUM_DTYPE) if sums is None else np.array(sums, GRID_RAY_SUM_DTYPE).reshape(n)
+        so = np.zeros((n, stride, 2)) if scans_out is None else np.array(scans_out, np.float64).reshape(n, stride, 2)
+        self._chk(self.L.lsd_grid_raycast(self.h, sc.ctypes.data, ln.ctypes.data, n, max(stride, 0), po.ctypes.data, mp, float(range_max),
+                                          gr.ctypes.data, grid_ray(ray), o.ctypes.data, su.ctypes.data, so.ctypes.data))
+        return o, su, so
+
     # -- correlative scan-to-grid matching ----------------------------------------------------------
     def enqueue_grid_likelihood_device(self, d_pass, d_hit, cols, rows, d_corr, min_pass=2, occ_num=1, occ_den=10, smear=None, stream=None):
         """lsd_enqueue_grid_likelihood_device on device addresses: d_corr[y][x] (uint8, rows x cols) = the largest smear.w[|v|][|u|] over the
@@ -1133,6 +1180,37 @@ def grid_response(response=None, rx=3, ry=3, ra=1, keep=(1, 2)):
     return lsd_grid_response(int(rx), int(ry), int(ra), kn, kd)
 
 
+def grid_ray(ray=None, tol=None, drop=("short",), min_beams=1, ok=(1, 2), gate=False, mapResol=None):
+    """An lsd_grid_ray_par: `ray` itself, a dict of tol / drop (or drop_mask) / min_beams / ok (or ok_num, ok_den) / gate, a tuple (tol,
+    drop_mask, min_beams, ok_num, ok_den, gate), or keywords.  A beam agrees with the map iff its range is within tol metres of the
+    expected one; drop: the classes (names of GRID_RAY_CLASSES or their numbers) whose readings a screened scan loses; a scan is
+    consistent with at least min_beams judged beams of which ok[0] / ok[1] agree; gate: a cast scan that is not consistent loses its
+    pose.  tol=None means two cells of the mapper's mapResol and is resolved where the mapper is known (mapResol given); elsewhere it is
+    refused."""
+    if isinstance(ray, lsd_grid_ray_par):
+        return ray
+    if isinstance(ray, dict):
+        a = dict(ray)
+        if "ok" in a:
+            a["ok_num"], a["ok_den"] = a.pop("ok")
+        ray = (a.get("tol", tol), a.get("drop_mask", a.get("drop", drop)), a.get("min_beams", min_beams), a.get("ok_num", ok[0]),
+               a.get("ok_den", ok[1]), a.get("gate", gate))
+    if ray is None or ray is True:
+        ray = (tol, drop, min_beams, ok[0], ok[1], gate)
+    tol, mask, mb, on, od, gate = ray
+    if tol is None:
+        if mapResol is None:
+            raise LsdError(LSD_ERR_INVALID, "grid_ray: tol=None is two cells of a mapper's mapResol; give tol where no mapper is known")
+        tol = 2 * float(mapResol)
+    if not isinstance(mask, (int, np.integer)):
+        names = [GRID_RAY_CLASSES.index(c) if isinstance(c, str) and c in GRID_RAY_CLASSES else c for c in mask]
+        if any(not isinstance(c, (int, np.integer)) or not 0 <= c < 7 for c in names):
+            raise LsdError(LSD_ERR_INVALID, "grid_ray: drop names classes of GRID_RAY_CLASSES or their numbers 0..6")
+        mask = sum({1 << int(c) for c in names})
+    mask, mb, on, od = _u32s(mask, mb, on, od, limit=(1 << 32,) * 4)
+    return lsd_grid_ray_par(float(tol), mask, mb, on, od, 1 if gate else 0)
+
+
 def fa_correct(correct=None, cov_scale=1.0, floor_xy=1.0, floor_ang=1.0, gate=0.0):
     """An lsd_fa_correct: `correct` itself, a dict of cov_scale / floor_xy / floor_ang / gate, a tuple of the four in that order, or
     keywords (None / True: the defaults).  R = the response's covariance x cov_scale + the floors on its diagonal (pixels^2, pixels^2,
@@ -1351,6 +1429,74 @@ class GridMapper:
         self.ctx.enqueue_grid_publish_device(self.d_pass, self.d_hit, self.rows * self.cols, grid.data_ptr(), self.min_pass, self.occ_num,
                                              self.occ_den, ts.cuda_stream)
         return grid
+
+    # -- ray casting on the grid (k_gridray.hip) --
+    def _enqueue_raycast(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, ray, d_grid, screened, ts):
+        """(rays: a new CUDA uint8 tensor [n, stride, 32]; sums: [n, 64]; the screened scans: a new float64 tensor [n, stride, 2], or None;
+        the grid that was read) of the scans at device addresses on the stream ts.  d_grid None: the mapper's own planes are published
+        first, on ts."""
+        import torch
+        par = grid_ray(ray, mapResol=self.mapResol)
+        grid = self.publish_device(ts) if d_grid is None else _occupancy_grid(d_grid, self.cols, self.rows, self.ctx.device)
+        with torch.cuda.stream(ts):
+            rays = torch.empty((n, stride, GRID_RAY_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+            sums = torch.empty((n, GRID_RAY_SUM_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+            so = torch.empty((n, stride, 2), dtype=torch.float64, device=self._planes.device) if screened else None
+        ctx.enqueue_grid_raycast_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self.map_param, self.range_max, grid.data_ptr(), par,
+                                        rays.data_ptr(), sums.data_ptr(), so.data_ptr() if screened else None, ts.cuda_stream)
+        return rays, sums, so, grid
+
+    def raycast_device(self, d_scans, d_lens, d_poses, pose_pitch=24, ray=None, d_grid=None, screened=False, stream=None):
+        """Casts scans that are on the device (the arguments of integrate_device) through an int8 OccupancyGrid of the mapper's frame:
+        d_grid, a CUDA int8 tensor of rows x cols cells (an outside SLAM's map serves as well), or None: the mapper's own planes, published
+        first on the same stream.  ray: grid_ray() (None: its defaults; tol=None: two cells).  Returns (rays, sums): CUDA uint8 tensors
+        [n, stride, 32] (GRID_RAY_DTYPE; the slots at i < len are written) and [n, 64] (GRID_RAY_SUM_DTYPE; their heads are poses:
+        integrate_device(d_scans, d_lens, sums, 64) enters the scans there, a gated scan not at all); with screened also the screened
+        scans, a CUDA float64 tensor [n, stride, 2].  On `stream`; nothing waits."""
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
+        rays, sums, so, grid = self._enqueue_raycast(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch,
+                                                     ray, d_grid, screened, _cuda_stream(stream))
+        self._held_ray = (d_scans, d_lens, d_poses, grid)                    # the launches read them: alive until the next call
+        return (rays, sums, so) if screened else (rays, sums)
+
+    def raycast(self, scans, lens, poses, ray=None, grid=None):
+        """raycast_device for host arrays (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]; grid: int8 [rows, cols], or
+        None: the mapper's own).  Returns (rays GRID_RAY_DTYPE [n, stride], sums GRID_RAY_SUM_DTYPE [n]) as numpy arrays: a read-back,
+        which waits for the device.  The record slots at i >= len are zero."""
+        import torch
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
+        if not ok or ((ln < 0) | (ln > sc.shape[1])).any():
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride, poses [n, 3]")
+        dev = self._planes.device
+        d_grid = None if grid is None else torch.from_numpy(np.ascontiguousarray(grid, np.int8)).to(dev)
+        rays, sums = self.raycast_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), torch.from_numpy(po).to(dev), 24, ray, d_grid)
+        out = rays.cpu().numpy().reshape(-1).view(GRID_RAY_DTYPE).reshape(sc.shape[:2]).copy()
+        out[np.arange(sc.shape[1])[None, :] >= ln[:, None]] = np.zeros((), GRID_RAY_DTYPE)
+        return out, sums.cpu().numpy().reshape(-1).view(GRID_RAY_SUM_DTYPE).copy()
+
+    def _screen_and_integrate(self, ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, ray, d_grid, ts):
+        rays, sums, so, grid = self._enqueue_raycast(ctx, d_scans, d_lens, n, stride, d_poses, pose_pitch, ray, d_grid, True, ts)
+        self._enqueue(ctx, so.data_ptr(), d_lens, n, stride, sums.data_ptr(), GRID_RAY_SUM_DTYPE.itemsize, ts.cuda_stream)
+        self._held_screen = (rays, sums, so, grid)
+        return rays, sums
+
+    @property
+    def last_screened(self):
+        """The screened scans the last screen_and_integrate_device / screen_and_integrate_last_tick integrated: a CUDA float64 tensor
+        [n, stride, 2] (the readings at i < len are written), or None before the first."""
+        held = getattr(self, "_held_screen", None)
+        return held[2] if held else None
+
+    def screen_and_integrate_device(self, d_scans, d_lens, d_poses, pose_pitch=24, ray=None, d_grid=None, stream=None):
+        """Integration with the ray-casting stage in front, in stream order: the grid (d_grid, or None: the mapper's own planes published
+        now) is read by raycast_device with screened scans, and the screened scans are integrated at the summary records (pitch 64) -- the
+        readings of the classes grid_ray(drop=) names are gone, and with gate a scan that does not agree with the map adds nothing.
+        Every scan of the call is judged against the grid as it was before the call.  Returns (rays, sums); nothing waits."""
+        n, pitch = self._checked(d_scans, d_lens, d_poses, pose_pitch)
+        got = self._screen_and_integrate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, ray,
+                                         d_grid, _cuda_stream(stream))
+        self._held_ray = (d_scans, d_lens, d_poses)
+        return got
 
     # -- correlative scan-to-grid matching (k_gridmatch.hip; DESIGN.md 8.1.7) --
     @property
@@ -2157,6 +2303,20 @@ class Localizer(_Ticks):
         staging.  The poses are in pixels of the map the tick localised on: the mapper's mapResol / mapOriX / mapOriY are that map's.
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
+
+    def screen_and_integrate_last_tick(self, mapper, ray=None, d_grid=None):
+        """integrate_last_tick with the ray-casting stage in front (GridMapper.screen_and_integrate_device): on the last
+        tick's stream and behind the tick, every frame of the tick is cast through the grid (d_grid, or None: the mapper's planes
+        published now) from the state it produced (pitch 720), and its screened scan is integrated at its summary record.  Nothing is
+        read back and nothing waits.  Returns (rays, sums): CUDA uint8 tensors [n_robots * k, n_beams, 32] (GRID_RAY_DTYPE) and
+        [n_robots * k, 64] (GRID_RAY_SUM_DTYPE); slot s * k + t is frame t of robot s."""
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        S, k, ts, _ = self._last_tick
+        return mapper._screen_and_integrate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, self._out.data_ptr(),
+                                            FA_STATE_DTYPE.itemsize, ray, d_grid, ts)
 
     def refine_and_integrate_last_tick(self, mapper, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match",
                                        correct=None):

@@ -279,4 +279,65 @@ int lsd_grid_response(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n
     return LSD_OK;
 }
 
+// --- ray casting on the grid (k_gridray.hip) ---
+static_assert(sizeof(lsd_grid_ray) == 32 && offsetof(lsd_grid_ray, r_exp) == 0 && offsetof(lsd_grid_ray, r_unk) == 8 && offsetof(lsd_grid_ray, cx) == 16 &&
+              offsetof(lsd_grid_ray, cy) == 20 && offsetof(lsd_grid_ray, k_hit) == 24 && offsetof(lsd_grid_ray, cls) == 28,
+              "lsd_grid_ray is 32 bytes: two doubles, three int32, the class");
+static_assert(sizeof(lsd_grid_ray_sum) == 64 && offsetof(lsd_grid_ray_sum, x) == 0 && offsetof(lsd_grid_ray_sum, y) == 8 &&
+              offsetof(lsd_grid_ray_sum, ang) == 16 && offsetof(lsd_grid_ray_sum, n) == 24 && offsetof(lsd_grid_ray_sum, judged) == 52 &&
+              offsetof(lsd_grid_ray_sum, flags) == 56 && offsetof(lsd_grid_ray_sum, pad) == 60,
+              "lsd_grid_ray_sum is 64 bytes and starts with a pose: an array of them is a d_poses argument of pitch 64");
+static_assert(sizeof(lsd_grid_ray_par) == 32 && offsetof(lsd_grid_ray_par, drop_mask) == 8 && offsetof(lsd_grid_ray_par, gate) == 24, "lsd_grid_ray_par");
+
+// what both ray-casting entries refuse about the parameters
+static bool grid_ray_bad(const lsd_grid_ray_par& par) {
+    if (!std::isfinite(par.tol) || par.tol < 0 || par.drop_mask >= 128) return true;
+    return par.ok_den == 0 || par.ok_num > par.ok_den;
+}
+
+int lsd_enqueue_grid_raycast_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const void* d_poses,
+                                    size_t pose_pitch, lsd_map_param mp, double range_max, const int8_t* d_grid, lsd_grid_ray_par par,
+                                    lsd_grid_ray* d_out, lsd_grid_ray_sum* d_sum, lsd_polar* d_scans_out, void* stream) {
+    GridScans g;
+    if (!d_grid || !d_out || !d_sum || grid_ray_bad(par) ||
+        grid_scans_bad(c, "grid raycast", d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, mp, range_max, g))
+        return LSD_ERR_INVALID;
+    if (((addr(d_out) | addr(d_sum)) & 7) || (addr(d_scans_out) & 15)) {
+        c->err = "grid raycast: d_out and d_sum 8-byte, d_scans_out 16-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (d_scans_out && d_scans_out != d_scans) {                         // in place, or apart
+        const uintptr_t bytes = (uintptr_t)n_scans * stride * sizeof(lsd_polar), a = addr(d_scans), b = addr(d_scans_out);
+        if (a < b + bytes && b < a + bytes) {
+            c->err = "grid raycast: d_scans_out is d_scans itself or does not overlap it";
+            return LSD_ERR_INVALID;
+        }
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) { launch_grid_raycast(g, d_grid, par, d_out, d_sum, d_scans_out, s); return LSD_OK; });
+}
+
+int lsd_grid_raycast(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_map_param mp,
+                     double range_max, const int8_t* grid, lsd_grid_ray_par par, lsd_grid_ray* out, lsd_grid_ray_sum* sum, lsd_polar* scans_out) {
+    if (!grid || !out || !sum || grid_ray_bad(par) || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max)) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    const size_t ns = (size_t)n_scans, beams = ns * stride, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar *d_sc, *d_so; int* d_len; lsd_position* d_po; int8_t* d_gr; lsd_grid_ray* d_out; lsd_grid_ray_sum* d_sum;
+    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po,
+                         [&](Carver& k) { k(d_gr, cells); k(d_out, beams); k(d_sum, ns); k(d_so, scans_out ? beams : 0); });
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(d_gr, grid, cells, hipMemcpyHostToDevice, c->stream));
+    // (the slots at i >= len are the caller's: they make the round trip)
+    HIPCHK(c, hipMemcpyAsync(d_out, out, beams * sizeof(lsd_grid_ray), hipMemcpyHostToDevice, c->stream));
+    if (scans_out) HIPCHK(c, hipMemcpyAsync(d_so, scans_out, beams * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    st = lsd_enqueue_grid_raycast_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_gr, par, d_out, d_sum,
+                                         scans_out ? d_so : nullptr, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, beams * sizeof(lsd_grid_ray), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sum, d_sum, ns * sizeof(lsd_grid_ray_sum), hipMemcpyDeviceToHost, c->stream));
+    if (scans_out) HIPCHK(c, hipMemcpyAsync(scans_out, d_so, beams * sizeof(lsd_polar), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
 }  // extern "C"

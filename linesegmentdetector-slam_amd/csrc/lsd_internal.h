@@ -198,6 +198,10 @@ void launch_grid_match_mr(const GridScans& g, const uint8_t* corr, const uint8_t
 size_t grid_response_volume_bytes(int n_scans, const lsd_grid_response_par& rp);
 void launch_grid_response(const GridScans& g, const lsd_grid_match_rec* records, const uint8_t* corr, double ang_step, const lsd_grid_response_par& rp,
                           uint32_t* volume, lsd_grid_response_rec* out, hipStream_t s);
+// ray casting on the grid (k_gridray.hip): per beam the expected range and its class against the int8 grid, per scan the summary (and the
+// gate), and with scans_out (may be null, may be g.scans) the screened readings; two launches, no workspace
+void launch_grid_raycast(const GridScans& g, const int8_t* grid, const lsd_grid_ray_par& par, lsd_grid_ray* out, lsd_grid_ray_sum* sum,
+                         lsd_polar* scans_out, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
