@@ -2,10 +2,16 @@
 // sin/cos/atan/atan2 go through crmath.h (correctly rounded, see there for why); the rare inputs it
 // declines (non-finite, |x| > 64, subnormal range) fall back to the device math library.
 // exp / log10 / pow (RectangleNFACalculator): correctly rounded likewise (exp_g, log10_g, pow_g).
+// And one integer helper of the wavefront, lanes_below, for the kernels outside the region stage (which has its own wave.h).
 #pragma once
 #include "crmath.h"
 
 namespace lsdhip {
+
+// The set bits of a ballot below this lane: a kept lane's slot in an ordered compaction (k_ingest, the grid matchers, FeatureScan).
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
 
 // Out of line on purpose: the double-double bodies are ~2-3 KB of code each and the region kernel has to fit the
 // instruction cache; they are called a few times per region, never per pixel of the serial chain.

@@ -70,7 +70,7 @@ __device__ __forceinline__ int gm_end_cells(const double2* __restrict__ row, int
             }
         }
         const unsigned long long m = __ballot(keep);
-        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int below = lanes_below(m);
         if (lane == 0) s_cnt[wave] = __builtin_popcountll(m);
         __syncthreads();
         int at = n_list, total = 0;

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kGmLanes) void k_grid_match_fine(const double2* __r
             fine += (uint32_t)(min(b, nx - I * b) * min(b, ny - J * b));
         }
         const unsigned long long m = __ballot(keep);
-        const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int below = lanes_below(m);
         __syncthreads();                                             // (s_cnt: the last reads of the round before)
         if (lane == 0) s_cnt[wave] = __builtin_popcountll(m);
         __syncthreads();

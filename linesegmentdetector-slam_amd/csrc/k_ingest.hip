@@ -17,6 +17,7 @@
 // NOT reproduced: laserCallback stores a finite reading at lidarPointPolar[i], not [len_lp], and then hands the first len_lp entries to
 // FeatureScan, so with any infinite range it reads stale entries of earlier messages.  The file driver packs; so does this kernel.
 #include "lsd_internal.h"
+#include "devmath.h"
 
 namespace lsdhip {
 
@@ -46,8 +47,8 @@ __global__ __launch_bounds__(64) void k_ingest(const double2* __restrict__ raw /
                 }
             }
             const unsigned long long m = __ballot(keep);
-            const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (keep) out[base + below] = v;                                       // base + below <= i < n_beams <= stride
+            const int below = lanes_below(m);
+            if (keep) out[base + below] = v;                                      // base + below <= i < n_beams <= stride
             base += __builtin_popcountll(m);
         }
     }

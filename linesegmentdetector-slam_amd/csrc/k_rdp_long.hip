@@ -1,9 +1,9 @@
 // k_rdp_long.hip -- myrdp::FeatureScan for scans of 1025 .. 4096 readings (gfx950): one wavefront per scan, dynamic LDS.
 //
 // The same function as k_rdp.hip (LSD/myRDP.cpp:9-185 with RegionSegmentation, SplitMerge, SplitMergeAssistant and
-// getThresholdDeltaDist), the same outputs at the same strides, the same bits; launch_rdp / launch_rdp_maps send a launch here when its
-// stride is above k_rdp's 1024.  What differs:
-//   - the work arrays are dynamic LDS sized from the launch's stride (k_rdp_lds.h: 26 bytes per reading), indices are 16 bits wide;
+// getThresholdDeltaDist), the same outputs at the same strides, the same bits; launch_rdp sends a launch here when its stride is above
+// k_rdp's 1024.  The phases of a scan are rdp_dev.h's, shared with k_rdp.hip.  What differs:
+//   - the work arrays are dynamic LDS sized from the launch's stride (k_rdp_lds.h: 26 bytes per reading);
 //   - no lane walks over all readings.  k_rdp's two walks by lane 0 -- RegionSegmentation's cluster walk and the listing of the chords
 //     -- are ordered compactions here (ballot + the kept lanes below, over chunks of 64, the idiom of k_ingest):
 //       clusters  the readings behind which the gap is over the threshold are listed in order (B); run j is [B[j-1] + 1, B[j]] (the first
@@ -16,83 +16,43 @@
 //                 ascend.  Each reading lists itself once as its cluster's first reading, once as a split point, once as its
 //                 cluster's last reading (P, a compaction in that order); the chords are the neighbours (P[t-1], P[t]) where P[t]
 //                 does not begin a cluster.
-//     The RDP stack loop and the per-line raster loops are k_rdp's.
 // One wavefront, not four: the batch is the parallelism (one scan per workgroup, hundreds of scans per launch), the farthest-point
-// search keeps k_rdp's shuffle reduction with its first-maximum rule, and the barriers stay wave-local.
-// Kept as they are: everything k_rdp.hip's head lists (vertical chords with NaN distances, cvt_x86, 0 doubling as "invalid" in the
+// search keeps its shuffle reduction with its first-maximum rule, and the barriers stay wave-local.
+// Kept as they are: everything rdp_dev.h's head lists (vertical chords with NaN distances, cvt_x86, 0 doubling as "invalid" in the
 // raster, len_lp < 1 writing the six zeros, the first maximum under the strict '>').  Line records stay at 360 per scan: a scan with
 // more reports the full count and stores the first 360.
 // Domain: region_point_limit >= 1, the reference's.  Below 1 a cluster of ONE reading can exist, whose span the reference takes for
 // the whole scan plus one (its wrap-around formula at ep == sp); that is not restated here -- such a cluster gives one chord of
 // length 0 -- and every index stays inside its array.
-#include "lsd_internal.h"
-#include "devmath.h"
+#include "rdp_dev.h"
 #include "k_rdp_lds.h"
 
 namespace lsdhip {
 
-constexpr int kRdpLongMaxLines = 360;               // line records per scan (k_rdp's kRdpMaxLines)
-constexpr unsigned kFirstOfCluster = 0x8000u;       // flag on an entry of P
+constexpr unsigned kFirstOfCluster = 0x8000u;       // flag on an entry of P (the readings' indices take 15 bits at most)
 
 extern __shared__ double rdp_long_lds_base[];
-
-__device__ __forceinline__ double rdp_long_thre_delta(double val) {                 // getThresholdDeltaDist :347-368
-    if (val <= 0.3) return 0.02;
-    if (val <= 0.5) return 0.05;
-    if (val <= 0.8) return 0.11;
-    if (val <= 1) return 0.17;
-    if (val <= 2) return 0.6;
-    if (val <= 3) return 0.7;
-    if (val <= 4) return 0.85;
-    if (val <= 5) return 0.9;
-    if (val <= 6) return 1;
-    return 1.1;
-}
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // One scan (blockIdx.x) with the map's resolution and origin given: the body of both kernels below.
 __device__ __forceinline__ void rdp_long_scan(const double* __restrict__ scans /* n x stride x {range, angle} */, const int* __restrict__ lens,
                                               int stride, double mapResol, double mapOriX, double mapOriY, int region_point_limit,
-                                              double thre_line, double line_dist_thre_m, lsd_line* __restrict__ lines_out,
-                                              int* __restrict__ n_lines, double* __restrict__ pts_out, int pts_cap, int* __restrict__ n_pts,
-                                              double* __restrict__ lidar_pos, int* __restrict__ im_size) {
+                                              double thre_line, double line_dist_thre_m, const RdpOut& o) {
     // the launch's dynamic LDS, rdp_long_lds(stride) bytes: every array holds `stride` elements (stk: 2 x stride)
     double* px = rdp_long_lds_base;
     double* py = px + stride;
-    unsigned short* cs = reinterpret_cast<unsigned short*>(py + stride);           // clusters: first and last reading
+    unsigned short* cs = reinterpret_cast<unsigned short*>(py + stride);
     unsigned short* ce = cs + stride;
     unsigned short* stk = ce + stride;                 // in turn: the breaks B, the spans still to look at (RDP), the chord points P
     unsigned char* brk = reinterpret_cast<unsigned char*>(stk + 2 * stride);       // a gap behind the reading; later: first / last of a cluster
     unsigned char* split = brk + stride;
     const int stk_cap = 2 * stride;
+    const RdpLds<unsigned short, true> w{px, py, cs, ce, stk, brk, split, stk_cap};
     const size_t scan = blockIdx.x;
     const int lane = threadIdx.x;
     const int len_lp = min(lens[scan], stride);
     const double* sc = scans + scan * (size_t)stride * 2;
-    lsd_line* lout = lines_out + scan * (size_t)kRdpLongMaxLines;
-    double* pout = pts_out + scan * (size_t)pts_cap * 3;
-    if (len_lp < 1) {
-        if (lane == 0) { n_lines[scan] = 0; n_pts[scan] = 0; lidar_pos[scan * 2] = 0; lidar_pos[scan * 2 + 1] = 0; im_size[scan * 2] = 0; im_size[scan * 2 + 1] = 0; }
-        return;
-    }
-    // 1. metric coordinates (scanPose = 0, :11) and the gaps
-    for (int i = lane; i < len_lp; i += 64) {
-        double s, c;
-        sincos_g(sc[2 * i + 1] + 0.0, s, c);
-        px[i] = sc[2 * i] * c + 0.0;                                               // :286-287
-        py[i] = sc[2 * i] * s + 0.0;
-        split[i] = 0;
-    }
-    __syncthreads();
-    for (int i = lane; i < len_lp; i += 64) {
-        const int nx = i == len_lp - 1 ? 0 : i + 1;                                // :299-306
-        const double dX = px[i] - px[nx], dY = py[i] - py[nx];
-        brk[i] = sqrt(dX * dX + dY * dY) > rdp_long_thre_delta(sc[2 * i]) ? 1 : 0; // :307-309
-    }
-    __syncthreads();
+    if (rdp_empty_scan(len_lp, scan, o)) return;
+    rdp_metric_gaps(sc, len_lp, w);
     // RegionSegmentation's walk :297-330 as two compactions.  B: the readings with a gap behind them, in order
     int nb = 0;
     for (int c0 = 0; c0 < len_lp; c0 += 64) {
@@ -123,69 +83,9 @@ __device__ __forceinline__ void rdp_long_scan(const double* __restrict__ scans /
     __syncthreads();
     if (joins && cells > 0 && lane == 0) cs[0] = (unsigned short)lastStart;        // (lastStart <= len_lp - 1: the last reading is no break)
     __syncthreads();
-    // 2. SplitMerge :187-217 / SplitMergeAssistant :219-272 (k_rdp's loop)
-    for (int cidx = 0; cidx < cells; cidx++) {
-        int sp_top = 0;
-        if (lane == 0) { stk[0] = cs[cidx]; stk[1] = ce[cidx]; }
-        sp_top = 1;
-        __syncthreads();
-        while (sp_top > 0) {
-            sp_top--;
-            const int sp = stk[2 * sp_top], ep = stk[2 * sp_top + 1];
-            __syncthreads();
-            const int len = ep > sp ? ep - sp + 1 : len_lp + ep - sp + 1;          // :223-239
-            if (len <= 2) continue;
-            const double k = (py[ep] - py[sp]) / (px[ep] - px[sp]);                // :245-246
-            const double d = py[ep] - k * px[ep];
-            const double den = sqrt(k * k + 1);
-            double best = 0.0;                                                     // dist_max = 0: only a distance > 0 is taken (:257)
-            int besto = 0x7fffffff;                                                // its position in the span (first maximum wins)
-            for (int i = 1 + lane; i < len - 1; i += 64) {
-                int a = sp + i;
-                if (a >= len_lp) a -= len_lp;
-                const double dist = fabs(k * px[a] - py[a] + d) / den;             // :256
-                if (dist > best) { best = dist; besto = i; }                       // (ascending i per lane: the first of equal ones stays)
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(best, off);
-                const int oo = __shfl_xor(besto, off);
-                if (ob > best || (ob == best && oo < besto)) { best = ob; besto = oo; }
-            }
-            int i_max = 0;                                                         // :252 (reading 0 when nothing was farther than 0)
-            if (besto != 0x7fffffff) { i_max = sp + besto; if (i_max >= len_lp) i_max -= len_lp; }
-            const double r = sc[2 * i_max];
-            const double threDist = r > 9 ? r * thre_line : thre_line;             // :259-263
-            if (best > threDist && 2 * sp_top + 4 <= stk_cap) {                    // (spans on the stack share end points only: < len_lp of them)
-                if (lane == 0) {
-                    stk[2 * sp_top] = (unsigned short)sp; stk[2 * sp_top + 1] = (unsigned short)i_max;
-                    stk[2 * sp_top + 2] = (unsigned short)i_max; stk[2 * sp_top + 3] = (unsigned short)ep;
-                    split[i_max] = 1;
-                }
-                sp_top += 2;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    // 3. pixel coordinates and the size of the image :16-37
-    double minX = INFINITY, minY = INFINITY, maxX = 0, maxY = 0;
-    for (int i = lane; i < len_lp; i += 64) {
-        const double X = floor((px[i] - mapOriX) / mapResol), Y = floor((py[i] - mapOriY) / mapResol);
-        px[i] = X; py[i] = Y;
-        minX = fmin(minX, X); maxX = fmax(maxX, X); minY = fmin(minY, Y); maxY = fmax(maxY, Y);
-        brk[i] = 0;                                                                // from here: 1 = first reading of a cluster, 2 = last
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        minX = fmin(minX, __shfl_xor(minX, off)); maxX = fmax(maxX, __shfl_xor(maxX, off));
-        minY = fmin(minY, __shfl_xor(minY, off)); maxY = fmax(maxY, __shfl_xor(maxY, off));
-    }
-    const int oriXLim = cvt_x86(ceil(maxX - minX)), oriYLim = cvt_x86(ceil(maxY - minY));
-    if (lane == 0) {
-        lidar_pos[scan * 2] = floor((0.0 - mapOriX) / mapResol - minX);            // :35-36
-        lidar_pos[scan * 2 + 1] = floor((0.0 - mapOriY) / mapResol - minY);
-        im_size[scan * 2] = oriXLim; im_size[scan * 2 + 1] = oriYLim;
-    }
-    __syncthreads();
+    rdp_split_merge(sc, len_lp, cells, thre_line, w);
+    for (int i = lane; i < len_lp; i += 64) brk[i] = 0;                            // from here: 1 = first reading of a cluster, 2 = last
+    const RdpFrame f = rdp_pixel_frame(len_lp, mapResol, mapOriX, mapOriY, scan, o, w);
     for (int c = lane; c < cells; c += 64) brk[cs[c]] = 1;                         // (the clusters are disjoint: one writer per reading)
     __syncthreads();
     for (int c = lane; c < cells; c += 64) brk[ce[c]] |= 2;
@@ -211,69 +111,11 @@ __device__ __forceinline__ void rdp_long_scan(const double* __restrict__ scans /
     }
     n_p = min(n_p, stk_cap);                                                       // (in the domain n_p <= len_lp: a reading is one of the three)
     __syncthreads();
-    // (the reference puts the first reading in front of the collected split points and the last one behind, :68-69)
-    const double lineDistThre = line_dist_thre_m / mapResol;
-    int nl = 0, np = 0;                                                            // lines / pixels so far (wave-uniform)
-    for (int base = 1; base < n_p; base += 64) {
-        const int ci = base + lane;
-        bool keep = false;
-        double x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-        if (ci < n_p && !(stk[ci] & kFirstOfCluster)) {                            // the chord (P[ci - 1], P[ci])
-            const int a = stk[ci - 1] & (kFirstOfCluster - 1u), b = stk[ci];
-            const double ax = px[a], ay = py[a], bx = px[b], by = py[b];
-            const double ex = ax - bx, ey = ay - by;
-            keep = sqrt(ex * ex + ey * ey) >= lineDistThre;                        // :78-79
-            x1 = ax - minX; y1 = ay - minY; x2 = bx - minX; y2 = by - minY;        // :81-84
-        }
-        const unsigned long long km = __ballot(keep);
-        const int li = nl + lanes_below(km);
-        const double k = (y2 - y1) / (x2 - x1);                                    // :86
-        const int xLow = cvt_x86(floor(x1 > x2 ? x2 : x1)), xHigh = cvt_x86(ceil(x1 > x2 ? x1 : x2));   // :94-109
-        const int yLow = cvt_x86(floor(y1 > y2 ? y2 : y1)), yHigh = cvt_x86(ceil(y1 > y2 ? y1 : y2));
-        const bool along_x = fabs(x2 - x1) > fabs(y2 - y1);                        // :110-115 (integer coordinates: the same as xx_len > yy_len)
-        const int cnt = keep ? (along_x ? xHigh - xLow + 1 : yHigh - yLow + 1) : 0;
-        // the pixels this line marks (:116-153): count, then place behind the earlier lines' pixels
-        int mine = 0;
-        for (int m = 0; m < cnt; m++) {
-            int xx, yy;
-            if (along_x) { xx = m + xLow; yy = cvt_x86(round((xx - x1) * k + y1)); }
-            else { yy = m + yLow; xx = cvt_x86(round((yy - y1) / k + x1)); }
-            if (!(xx < 0 || xx >= oriXLim || yy < 0 || yy >= oriYLim) && xx != 0 && yy != 0) mine++;   // 0 doubles as "invalid"
-        }
-        int inc = mine;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(inc, off);
-            if (lane >= off) inc += t;
-        }
-        int wr = np + inc - mine;
-        for (int m = 0; m < cnt; m++) {
-            int xx, yy;
-            if (along_x) { xx = m + xLow; yy = cvt_x86(round((xx - x1) * k + y1)); }
-            else { yy = m + yLow; xx = cvt_x86(round((yy - y1) / k + x1)); }
-            if (!(xx < 0 || xx >= oriXLim || yy < 0 || yy >= oriYLim) && xx != 0 && yy != 0) {
-                if (wr < pts_cap) { pout[3 * (size_t)wr] = xx; pout[3 * (size_t)wr + 1] = yy; pout[3 * (size_t)wr + 2] = 0; }
-                wr++;
-            }
-        }
-        if (keep && li < kRdpLongMaxLines) {
-            double ang = atan_g(k) * 180.0 / kPi;                                  // atand, baseFunc.cpp:14-16
-            int orient = 1;
-            if (ang < 0) { ang += 180; orient = -1; }                              // :89-92
-            lsd_line L;
-            L.k = k;
-            L.b = (y1 + y2) / 2.0 - k * (x1 + x2) / 2.0;                           // :164
-            sincos_g(ang / 180.0 * kPi, L.dy, L.dx);                               // sind / cosd
-            L.x1 = x1; L.y1 = y1; L.x2 = x2; L.y2 = y2;
-            const double ey = y2 - y1, ex = x2 - x1;
-            L.len = sqrt(ey * ey + ex * ex);                                       // :171
-            L.orient = orient;
-            lout[li] = L;
-            reinterpret_cast<uint32_t*>(&lout[li])[19] = 0u;                       // the tail padding: defined bytes
-        }
-        nl += __builtin_popcountll(km);
-        np += __shfl(inc, 63);
-    }
-    if (lane == 0) { n_lines[scan] = nl; n_pts[scan] = np; }
+    rdp_chords(1, n_p, [&](int ci, int& a, int& b) {                               // the chord (P[ci - 1], P[ci])
+                   if (stk[ci] & kFirstOfCluster) return false;
+                   a = stk[ci - 1] & (kFirstOfCluster - 1u); b = stk[ci];
+                   return true;
+               }, f, line_dist_thre_m / mapResol, scan, o, w);
 }
 
 __global__ __launch_bounds__(64) void k_rdp_long(const double* __restrict__ scans, const int* __restrict__ lens, int stride, double mapResol,
@@ -281,25 +123,21 @@ __global__ __launch_bounds__(64) void k_rdp_long(const double* __restrict__ scan
                                                  double line_dist_thre_m, lsd_line* __restrict__ lines_out, int* __restrict__ n_lines,
                                                  double* __restrict__ pts_out, int pts_cap, int* __restrict__ n_pts,
                                                  double* __restrict__ lidar_pos, int* __restrict__ im_size) {
-    rdp_long_scan(scans, lens, stride, mapResol, mapOriX, mapOriY, region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines,
-                  pts_out, pts_cap, n_pts, lidar_pos, im_size);
+    rdp_long_scan(scans, lens, stride, mapResol, mapOriX, mapOriY, region_point_limit, thre_line, line_dist_thre_m,
+                  RdpOut{lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size});
 }
 
-// The fleet's form (k_rdp_maps): an id outside the table -> the sequence sits out, its scans get counts 0 and nothing else is written.
+// The fleet's form (k_rdp_maps)
 __global__ __launch_bounds__(64) void k_rdp_maps_long(const double* __restrict__ scans, const int* __restrict__ lens, int stride,
                                                       const lsd_map_ref* __restrict__ maps, int n_maps, const int32_t* __restrict__ map_of,
                                                       int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m,
                                                       lsd_line* __restrict__ lines_out, int* __restrict__ n_lines,
                                                       double* __restrict__ pts_out, int pts_cap, int* __restrict__ n_pts,
                                                       double* __restrict__ lidar_pos, int* __restrict__ im_size) {
-    const int id = map_of[blockIdx.x / (unsigned)scans_per_seq];
-    if ((unsigned)id >= (unsigned)n_maps) {
-        if (threadIdx.x == 0) { n_lines[blockIdx.x] = 0; n_pts[blockIdx.x] = 0; }
-        return;
-    }
-    const lsd_map_ref* __restrict__ m = maps + id;
-    rdp_long_scan(scans, lens, stride, m->mapResol, m->mapOriX, m->mapOriY, region_point_limit, thre_line, line_dist_thre_m, lines_out,
-                  n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
+    const RdpOut o{lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size};
+    const lsd_map_ref* __restrict__ m = rdp_map_of_scan(maps, n_maps, map_of, scans_per_seq, o);
+    if (!m) return;
+    rdp_long_scan(scans, lens, stride, m->mapResol, m->mapOriX, m->mapOriY, region_point_limit, thre_line, line_dist_thre_m, o);
 }
 
 // Once per context, before its first long launch: LDS above 64 KiB needs the kernels' dynamic-LDS limit raised (lsd_set_scan_capacity
@@ -311,17 +149,17 @@ hipError_t prepare_rdp_long(size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rdp_maps_long), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-void launch_rdp_long(const double* scans, const int* lens, int n, int stride, double mapResol, double mapOriX, double mapOriY,
-                     int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines, double* pts_out,
-                     int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
-    hipLaunchKernelGGL(k_rdp_long, dim3(n), dim3(64), rdp_long_lds(stride), s, scans, lens, stride, mapResol, mapOriX, mapOriY,
-                       region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
-}
-void launch_rdp_maps_long(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
-                          int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out,
-                          int* n_lines, double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s) {
-    hipLaunchKernelGGL(k_rdp_maps_long, dim3(n), dim3(64), rdp_long_lds(stride), s, scans, lens, stride, maps, n_maps, map_of, scans_per_seq,
-                       region_point_limit, thre_line, line_dist_thre_m, lines_out, n_lines, pts_out, pts_cap, n_pts, lidar_pos, im_size);
+// launch_rdp's other half (rdp_dev.h): this file's two kernels with the stride's dynamic LDS
+void rdp_long_launch(const RdpScans& a, const RdpOut& o, hipStream_t s) {
+    const size_t lds = rdp_long_lds(a.stride);
+    if (a.maps)
+        hipLaunchKernelGGL(k_rdp_maps_long, dim3(a.n), dim3(64), lds, s, a.scans, a.lens, a.stride, a.maps, a.n_maps, a.map_of, a.scans_per_seq,
+                           a.region_point_limit, a.thre_line, a.line_dist_thre_m, o.lines, o.n_lines, o.pts, o.pts_cap, o.n_pts, o.lidar_pos,
+                           o.im_size);
+    else
+        hipLaunchKernelGGL(k_rdp_long, dim3(a.n), dim3(64), lds, s, a.scans, a.lens, a.stride, a.mapResol, a.mapOriX, a.mapOriY,
+                           a.region_point_limit, a.thre_line, a.line_dist_thre_m, o.lines, o.n_lines, o.pts, o.pts_cap, o.n_pts, o.lidar_pos,
+                           o.im_size);
 }
 
 }  // namespace lsdhip

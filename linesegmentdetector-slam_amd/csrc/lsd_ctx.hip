@@ -1013,7 +1013,7 @@ int lsd_scan_to_map_match(lsd_ctx* c, const double* map_cache, int cols, int row
 // may be above the 64 KiB a kernel gets without asking.  Their limit is raised once per context (and again after the capacity changes),
 // to the capacity's need: every stride the entries let through fits.
 static hipError_t rdp_long_prepare(lsd_ctx* c, int stride) {
-    if (stride <= rdp_max_len() || c->rdp_long_ready) return hipSuccess;
+    if (stride <= kRdpShortMaxLen || c->rdp_long_ready) return hipSuccess;
     const hipError_t e = prepare_rdp_long(rdp_long_lds(c->scan_cap));
     if (e == hipSuccess) c->rdp_long_ready = true;
     return e;
@@ -1038,9 +1038,14 @@ int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, 
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
     HIPCHK(c, rdp_long_prepare(c, stride));
-    launch_rdp(reinterpret_cast<const double*>(d_scans), d_lens, n_scans, stride, mp.oriMapCol, mp.oriMapRow, mp.mapResol, mp.mapOriX, mp.mapOriY,
-               region_point_limit, thre_line, line_dist_thre_m, d_lines_out, d_n_lines, reinterpret_cast<double*>(d_pts_out), pts_cap, d_n_pts,
-               d_lidar_pos, d_im_size, s);
+    RdpScans a{};
+    a.scans = reinterpret_cast<const double*>(d_scans); a.lens = d_lens; a.n = n_scans; a.stride = stride;
+    a.region_point_limit = region_point_limit; a.thre_line = thre_line; a.line_dist_thre_m = line_dist_thre_m;
+    a.mapResol = mp.mapResol; a.mapOriX = mp.mapOriX; a.mapOriY = mp.mapOriY;
+    RdpOut o{};
+    o.lines = d_lines_out; o.n_lines = d_n_lines; o.pts = reinterpret_cast<double*>(d_pts_out); o.pts_cap = pts_cap;
+    o.n_pts = d_n_pts; o.lidar_pos = d_lidar_pos; o.im_size = d_im_size;
+    launch_rdp(a, o, s);
     HIPCHK(c, hipGetLastError());
     c->last_stream = s;
     return LSD_OK;
@@ -1098,9 +1103,14 @@ int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, c
     const lsd_map_ref* d_tab;
     const int u = map_table_upload(c, 0, maps, n_maps, s, &d_tab);
     if (u != LSD_OK) return u;
-    launch_rdp_maps(reinterpret_cast<const double*>(d_scans), d_lens, n_scans, stride, d_tab, n_maps, d_map_of, scans_per_seq,
-                    region_point_limit, thre_line, line_dist_thre_m, d_lines_out, d_n_lines, reinterpret_cast<double*>(d_pts_out), pts_cap,
-                    d_n_pts, d_lidar_pos, d_im_size, s);
+    RdpScans a{};
+    a.scans = reinterpret_cast<const double*>(d_scans); a.lens = d_lens; a.n = n_scans; a.stride = stride;
+    a.region_point_limit = region_point_limit; a.thre_line = thre_line; a.line_dist_thre_m = line_dist_thre_m;
+    a.maps = d_tab; a.n_maps = n_maps; a.map_of = d_map_of; a.scans_per_seq = scans_per_seq;
+    RdpOut o{};
+    o.lines = d_lines_out; o.n_lines = d_n_lines; o.pts = reinterpret_cast<double*>(d_pts_out); o.pts_cap = pts_cap;
+    o.n_pts = d_n_pts; o.lidar_pos = d_lidar_pos; o.im_size = d_im_size;
+    launch_rdp(a, o, s);
     HIPCHK(c, hipGetLastError());
     c->last_stream = s;
     return LSD_OK;

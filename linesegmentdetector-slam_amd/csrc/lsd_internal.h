@@ -148,23 +148,17 @@ void launch_lines(const Geom& g, const Buffers& b, int n, hipStream_t s);
 void launch_lines_of(const double* recs_scaled, const int32_t* count, lsd_line* lines, uint8_t* line_im, int n, int W, int H, hipStream_t s);
 void launch_clear(uint8_t* p, size_t bytes, int num_cus, hipStream_t s);   // lineIm = zeros (k_lines.hip)
 void launch_compact_lines(const lsd_line* lines, const int32_t* counts, int max_lines, int n, lsd_line* flat, int32_t* offsets, hipStream_t s);
-void launch_rdp(const double* scans, const int* lens, int n, int stride, int oriMapCol, int oriMapRow, double mapResol, double mapOriX,
-                double mapOriY, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
-                double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
-// the same with mapResol / mapOriX / mapOriY of scan i read from maps[map_of[i / scans_per_seq]] (a device table of n_maps records); a
-// scan whose id is outside 0..n_maps-1 gets counts 0 and nothing else
-void launch_rdp_maps(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
-                     int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
-                     double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
-int rdp_max_len();
-// k_rdp_long.hip: the same two for strides above rdp_max_len(), which launch_rdp / launch_rdp_maps send there; dynamic LDS of
-// rdp_long_lds(stride) bytes (k_rdp_lds.h), for which prepare_rdp_long raises the kernels' limit where it is above 64 KiB
-void launch_rdp_long(const double* scans, const int* lens, int n, int stride, double mapResol, double mapOriX, double mapOriY,
-                     int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines, double* pts_out,
-                     int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
-void launch_rdp_maps_long(const double* scans, const int* lens, int n, int stride, const lsd_map_ref* maps, int n_maps, const int32_t* map_of,
-                          int scans_per_seq, int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out,
-                          int* n_lines, double* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size, hipStream_t s);
+// FeatureScan (k_rdp.hip for strides up to kRdpShortMaxLen of k_rdp_lds.h, k_rdp_long.hip above: launch_rdp chooses).  What a launch
+// reads: n scans at `stride` readings each with the rdp parameters and the map's mapResol / mapOriX / mapOriY -- the three scalars
+// where maps is null, else those of scan i read from maps[map_of[i / scans_per_seq]] (a device table of n_maps records; a scan whose
+// id is outside 0..n_maps-1 gets counts 0 and nothing else).  And what it writes, per scan: LSD_RDP_MAX_LINES records, pts_cap pixels,
+// the two counts, lidar_pos and im_size (two values each)
+struct RdpScans { const double* scans; const int* lens; int n, stride; int region_point_limit; double thre_line, line_dist_thre_m;
+                  double mapResol, mapOriX, mapOriY; const lsd_map_ref* maps; int n_maps; const int32_t* map_of; int scans_per_seq; };
+struct RdpOut { lsd_line* lines; int* n_lines; double* pts; int pts_cap; int* n_pts; double* lidar_pos; int* im_size; };
+void launch_rdp(const RdpScans& a, const RdpOut& o, hipStream_t s);
+// the long kernels' dynamic LDS is rdp_long_lds(stride) bytes (k_rdp_lds.h), for which prepare_rdp_long raises their limit where it is
+// above 64 KiB
 hipError_t prepare_rdp_long(size_t bytes);
 // the drivers' scan read loop (k_ingest.hip): raw (pairs) or ranges + min_inc (LaserScan) -> scans / lens as launch_rdp reads them
 void launch_ingest(const lsd_polar* raw, const float* ranges, const float* min_inc, int n, int n_beams, const int* take, lsd_polar* scans,
