@@ -586,7 +586,8 @@ int lsd_grid_integrate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, in
  * each scan's rounded end cells are translated over a window of whole cells and whole angle steps around its pose and summed on that
  * plane.  The result is made of integers and has no iteration order: tests/grid_match_cases.py restates both rules and the device gives
  * the same bytes.  The same match as a coarse-to-fine search: the section after this one; a sub-cell pose and a covariance of the
- * response: the one after that.  NOT built: loop closure, the fleet classes.
+ * response: the one after that; the search WITHOUT a prior, over the whole grid and all headings: the section on global localisation
+ * below.  NOT built: loop closure, the fleet classes.
  * lsd_enqueue_grid_likelihood_device: a cell is OCCUPIED iff the publish rule gives it 100 (d_pass >= min_pass and (uint64) d_hit *
  * occ_den >= (uint64) d_pass * occ_num);  d_corr[y][x] = the maximum of smear.w[|v|][|u|] over all |u|, |v| <= smear.radius for which
  * (x + u, y + v) is inside the grid and occupied, 0 if there is none (a maximum has no order: the table need not be monotone).  One
@@ -787,6 +788,83 @@ int lsd_enqueue_grid_raycast_device(lsd_ctx *ctx, const lsd_polar *d_scans, cons
 int lsd_grid_raycast(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, const lsd_position *poses,
                      lsd_map_param map_param, double range_max, const int8_t *grid, lsd_grid_ray_par par, lsd_grid_ray *out,
                      lsd_grid_ray_sum *sum, lsd_polar *scans_out);
+
+/* --- global scan-to-grid localisation: the match without a prior, exact branch and bound over a pyramid of block maxima --------- */
+/* Every entry above searches at most +-63 cells and steps around a pose that is nearly right.  This one has no prior: it searches a whole
+ * box of lidar cells and a whole fan of headings on the lookup plane (csrc/k_gridlocate.hip; restated in
+ * tests/grid_locate_cases.py).  Branch and bound over a max-pyramid (Olson; Cartographer's fast correlative matcher), held to the
+ * exhaustive search byte for byte: the winner's order is made of integers.  fp64 without FMA, the integration's helpers.  The heading
+ * axis is not coarsened.  NOT built: writing the located pose into a reset carry, the fleet classes, loop closure proper.
+ *   candidates  (a, q, p), a < n_ang, q < ny, p < nx: the lidar at cell (x0 + p, y0 + q), the heading theta_a = ang0 + (double) a *
+ *   ang_step;  lin = ((uint64) a * ny + q) * nx + p.  The box may overhang or leave the grid
+ *   a beam is SCORED at a iff the integration does not skip it at the pose (0, 0, theta_a), range <= range_max and th = angle + theta_a /
+ *   180 * pi is finite; its offset is ox = (int)round(range * cos(th) / mapResol), oy likewise with sin -- the match's end cell at the
+ *   pose (0, 0, theta_a), NOT round(cx + d) -- once per (beam, heading); nb(a) counts the scored beams
+ *   S(a, q, p) = the sum over the beams scored at a of corr[y0 + q + oy][x0 + p + ox], 0 outside the grid
+ *   the winner: the largest S, then the smallest lin;  n_best = the candidates whose S is the winner's (the ambiguity a caller must see
+ *   before trusting a relocalisation)
+ *   the pyramid: plane_0 = corr; for h = 1..levels plane_h is (rows + 2^h - 1) x (cols + 2^h - 1) bytes, plane_h[y + 2^h - 1][x + 2^h - 1]
+ *   = the maximum of corr over [x, x + 2^h) x [y, y + 2^h) inside the grid, 0 if none (the coarse plane of the section above at b = 2^h),
+ *   built level from level: four reads of plane_(h-1) at stride 2^(h-1).  The planes 0..levels lie one behind the other in one caller-owned
+ *   buffer: lsd_grid_pyramid_bytes its size (0 for arguments the entry refuses), lsd_grid_pyramid_offset(cols, rows, h) where level h
+ *   starts ((size_t)-1 for arguments the entry refuses).  A buffer built with more levels serves a search with fewer
+ *   nodes: node (a, Q, P) of level h covers p in [P 2^h, min(nx, (P + 1) 2^h)) and q likewise; a node whose low corner is outside the box
+ *   does not exist.  U_h = the sum over the beams scored at a of plane_h at the cell (x0 + P 2^h + ox, y0 + Q 2^h + oy), 0 outside the
+ *   plane.  Beam by beam a node bounds its children: U_H >= .. >= U_1 >= U_0 = S
+ *   the lower bound: per heading start at the top node (h = H = levels) with the largest U_H, among equals the smallest Q nbx + P (nbx =
+ *   ceil(nx / 2^H)); descend to the existing child with the largest U, among equals the smallest (Q, P) in that order, down to a candidate;
+ *   L_a = its S;  L = max(max_a L_a, score_floor)
+ *   the frontier: F_H = the top nodes with U_H >= L; F_(h-1) = the existing children of F_h with U >= L; F_0 = the candidates reached with
+ *   S >= L.  Every candidate that ties the winner is in F_0 when score_floor <= S_win, so the maximum over F_0 and the count of its
+ *   equals are the exhaustive search's.  levels = 0: the top nodes are the candidates themselves
+ *   the outcome, exactly one of the flags:  EMPTY nb(a) == 0 for every heading, nothing is searched;  OVERFLOW some |F_h| > max_nodes, h in
+ *   1..H -- the count is exact, the level and those below it are not run (a featureless plane ends here: the right answer for an
+ *   ambiguous map);  NOT_FOUND F_0 is empty (only a score_floor above S_win does that);  REJECTED a winner, but n_beams < min_beams or
+ *   (uint64) score * min_den < (uint64) 255 * n_beams * min_num;  ACCEPTED otherwise
+ *   record: ACCEPTED: (x, y, ang) = ((double) cx, (double) cy, theta_a); every other outcome: the "no pose" sentinel (-1.0, -1.0, +0.0),
+ *   which the integration and the match skip.  cx = x0 + p, cy = y0 + q, a, score = S, n_beams = nb(a), n_best: the winner's, for REJECTED
+ *   too, 0 without a winner;  lower_bound = L, 0 for EMPTY;  reserved = 0.  An array of records IS a d_poses argument of pitch 64
+ *   statistics (d_stats, may be NULL; 48 bytes per scan): top_nodes = n_ang nbx nby;  frontier[h] = |F_h| for h <= H, 0 above H and below
+ *   an overflow;  scored = top_nodes + the existing children evaluated;  EMPTY: all 0
+ * lsd_enqueue_grid_pyramid_device: levels + 1 launches (level 0 copies d_corr), no workspace, asynchronous.  LSD_ERR_INVALID before
+ * anything is enqueued: a null pointer, cols or rows outside 1..65535, levels outside 0..8.
+ * lsd_enqueue_grid_locate_device: d_pyramid is what lsd_enqueue_grid_pyramid_device made of the lookup plane with at least par.levels
+ * levels.  levels + 5 launches (offsets, top level, bound, frontier seed, one expansion per level, pick), a number fixed by the
+ * parameters and never by the data; asynchronous on `stream`.  The workspace (lsd_grid_locate_workspace_bytes: 4 bytes per beam and
+ * heading, 4 bytes per top node, 16 bytes per node of max_nodes where levels > 0, and 16 KiB, all per scan; 0 for arguments the entry
+ * refuses) is the context's, grown before the first launch when needed -- that case alone synchronises; there is no other allocation,
+ * copy or host wait.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: whatever lsd_enqueue_grid_match_device refuses on
+ * n_scans, stride, map_param and range_max; x0 or y0 beyond +-2^20; nx or ny outside 1..65535; n_ang outside 1..4096; ang0 or ang_step not
+ * finite, ang_step negative, ang_step == 0 with n_ang > 1; levels outside 0..8; max_nodes outside 1..2^24; min_den == 0 or min_num >
+ * min_den; more than 2^28 top nodes; d_scans, d_lens, d_pyramid or d_out null; d_scans not 16-byte, d_out not 8-byte, d_stats not 4-byte
+ * aligned.  n_scans == 0 launches nothing.
+ * (The parameters' type is lsd_grid_locate_par and the record's lsd_grid_locate_rec: the host entry has the name lsd_grid_locate.) */
+#define LSD_GRID_LOCATE_MAX_LEVELS 8
+typedef struct lsd_grid_locate_par {       /* 64 bytes */
+    int x0, y0, nx, ny; double ang0, ang_step; int n_ang, levels; uint32_t max_nodes, score_floor, min_beams, min_num, min_den;
+} lsd_grid_locate_par;
+typedef struct lsd_grid_locate_rec {       /* 64 bytes; its head is a pose, so an array of these IS a d_poses argument (pitch 64) */
+    double x, y, ang; uint32_t score, n_beams; int32_t cx, cy, a; uint32_t flags, n_best, lower_bound, reserved[2];
+} lsd_grid_locate_rec;
+typedef struct lsd_grid_locate_stats { uint32_t top_nodes, frontier[9], scored, reserved; } lsd_grid_locate_stats;   /* 48 bytes */
+#define LSD_GRID_LOCATE_ACCEPTED 1u
+#define LSD_GRID_LOCATE_REJECTED 2u
+#define LSD_GRID_LOCATE_NOT_FOUND 4u
+#define LSD_GRID_LOCATE_OVERFLOW 8u
+#define LSD_GRID_LOCATE_EMPTY 16u
+size_t lsd_grid_pyramid_bytes(int cols, int rows, int levels);
+size_t lsd_grid_pyramid_offset(int cols, int rows, int h);
+int lsd_enqueue_grid_pyramid_device(lsd_ctx *ctx, const uint8_t *d_corr, int cols, int rows, int levels, uint8_t *d_pyramid, void *stream);
+size_t lsd_grid_locate_workspace_bytes(int n_scans, int stride, lsd_grid_locate_par par);
+int lsd_enqueue_grid_locate_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                   lsd_map_param map_param, double range_max, const uint8_t *d_pyramid, lsd_grid_locate_par par,
+                                   lsd_grid_locate_rec *d_out, lsd_grid_locate_stats *d_stats, void *stream);
+/* Host convenience: scans, lens and the lookup plane (rows x cols of map_param) travel to the context's staging, the pyramid is built
+ * there, lsd_enqueue_grid_locate_device runs, the n_scans records and, unless NULL, the n_scans statistics records come back.  Blocking.
+ * lens[i] outside 0..stride: LSD_ERR_INVALID. */
+int lsd_grid_locate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, lsd_map_param map_param,
+                    double range_max, const uint8_t *corr, lsd_grid_locate_par par, lsd_grid_locate_rec *out,
+                    lsd_grid_locate_stats *stats);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

@@ -134,6 +134,20 @@ assert GRID_RAY_DTYPE.itemsize == 32 and GRID_RAY_SUM_DTYPE.itemsize == 64 and C
 GRID_RAY_CLASSES = ("not_cast", "no_measurement", "agree_free", "agree", "short", "long", "unexplored")
 GRID_RAY_CONSISTENT, GRID_RAY_SKIPPED = 1, 2
 
+# global scan-to-grid localisation (include/lsd_hip.h): its parameters, the record of a scan and its statistics
+class lsd_grid_locate_par(C.Structure):
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("ang0", C.c_double), ("ang_step", C.c_double),
+                ("n_ang", C.c_int), ("levels", C.c_int), ("max_nodes", C.c_uint32), ("score_floor", C.c_uint32), ("min_beams", C.c_uint32),
+                ("min_num", C.c_uint32), ("min_den", C.c_uint32)]
+
+
+GRID_LOCATE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("score", "u4"), ("n_beams", "u4"), ("cx", "i4"), ("cy", "i4"),
+                              ("a", "i4"), ("flags", "u4"), ("n_best", "u4"), ("lower_bound", "u4"), ("reserved", "u4", (2,))])    # lsd_grid_locate_rec
+GRID_LOCATE_STATS_DTYPE = np.dtype([("top_nodes", "u4"), ("frontier", "u4", (9,)), ("scored", "u4"), ("reserved", "u4")])          # lsd_grid_locate_stats
+assert GRID_LOCATE_DTYPE.itemsize == 64 == C.sizeof(lsd_grid_locate_par) and GRID_LOCATE_STATS_DTYPE.itemsize == 48
+GRID_LOCATE_ACCEPTED, GRID_LOCATE_REJECTED, GRID_LOCATE_NOT_FOUND, GRID_LOCATE_OVERFLOW, GRID_LOCATE_EMPTY = 1, 2, 4, 8, 16
+GRID_LOCATE_MAX_LEVELS = 8
+
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
 FA_STATE_DTYPE = np.dtype([("x", "f8", (9,)), ("P", "f8", (81,))])
 FA_REPORT_DTYPE = np.dtype([("estimate", POS_DTYPE), ("score", "f8"), ("scan_pose", POS_DTYPE), ("n_pairs", "i4"), ("n_kept", "i4"),
@@ -260,6 +274,12 @@ _ABI = {
     "lsd_grid_response": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, lsd_map_param, _dbl, _vp, _dbl, lsd_grid_response, _vp, _vp]),
     "lsd_enqueue_grid_raycast_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, lsd_map_param, _dbl, _vp, lsd_grid_ray_par, _vp, _vp, _vp, _vp]),
     "lsd_grid_raycast": (_i, [_vp, _vp, _vp, _i, _i, _vp, lsd_map_param, _dbl, _vp, lsd_grid_ray_par, _vp, _vp, _vp]),
+    "lsd_grid_pyramid_bytes": (_sz, [_i, _i, _i]),
+    "lsd_grid_pyramid_offset": (_sz, [_i, _i, _i]),
+    "lsd_enqueue_grid_pyramid_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "lsd_grid_locate_workspace_bytes": (_sz, [_i, _i, lsd_grid_locate_par]),
+    "lsd_enqueue_grid_locate_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, _vp, _vp, _vp]),
+    "lsd_grid_locate": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -829,6 +849,37 @@ class Context:
                                            st.ctypes.data if stats else None))
         return (out, st) if stats else out
 
+    # -- global scan-to-grid localisation (k_gridlocate.hip) -------------------------
+    def enqueue_grid_pyramid_device(self, d_corr, cols, rows, levels, d_pyramid, stream=None):
+        """lsd_enqueue_grid_pyramid_device on device addresses: d_pyramid (uint8, grid_pyramid_bytes(cols, rows, levels) bytes) = the
+        planes 0..levels of block maxima of d_corr one behind the other (level h at grid_pyramid_offset(cols, rows, h)); asynchronous."""
+        return self._chk(self.L.lsd_enqueue_grid_pyramid_device(self.h, d_corr, int(cols), int(rows), int(levels), d_pyramid, stream))
+
+    def enqueue_grid_locate_device(self, d_scans, d_lens, n_scans, stride, map_param, range_max, d_pyramid, locate, d_out, d_stats=None,
+                                   stream=None):
+        """lsd_enqueue_grid_locate_device on device addresses: scans and lengths as enqueue_grid_integrate_device reads them, located
+        without a prior in the box and the headings `locate` names (an lsd_grid_locate_par or what grid_locate() takes) on the pyramid
+        enqueue_grid_pyramid_device made of the lookup plane; d_out receives n_scans records of 64 bytes (GRID_LOCATE_DTYPE), which are a
+        d_poses argument of pitch 64 themselves; d_stats (or None) n_scans records of 48 bytes (GRID_LOCATE_STATS_DTYPE); asynchronous."""
+        mp = _map_param(map_param)
+        return self._chk(self.L.lsd_enqueue_grid_locate_device(self.h, d_scans, d_lens, int(n_scans), int(stride), mp, float(range_max), d_pyramid,
+                                                               grid_locate(locate, cols=mp.oriMapCol, rows=mp.oriMapRow), d_out, d_stats, stream))
+
+    def grid_locate(self, scans, lens, map_param, range_max, corr, locate=None, stats=False):
+        """lsd_grid_locate from host arrays: scans float64 [n, stride, 2], lens int32 [n], corr uint8 [rows, cols].  Returns the n records as
+        a numpy array of GRID_LOCATE_DTYPE, and with stats=True (records, the n statistics records as GRID_LOCATE_STATS_DTYPE).  Blocking."""
+        sc, ln, _, ok = _host_scans(scans, lens, np.zeros((len(np.atleast_1d(lens)), 3)))
+        mp = _map_param(map_param)
+        co = np.ascontiguousarray(corr, np.uint8)
+        if not ok or co.shape != (mp.oriMapRow, mp.oriMapCol):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], corr uint8 [rows, cols]")
+        out = np.zeros(len(ln), GRID_LOCATE_DTYPE)
+        st = np.zeros(len(ln), GRID_LOCATE_STATS_DTYPE)
+        self._chk(self.L.lsd_grid_locate(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), mp, float(range_max), co.ctypes.data,
+                                         grid_locate(locate, cols=mp.oriMapCol, rows=mp.oriMapRow), out.ctypes.data,
+                                         st.ctypes.data if stats else None))
+        return (out, st) if stats else out
+
     # -- the response around a match (k_gridresponse.hip; DESIGN.md 8.1.9) -----------------------------
     def enqueue_grid_response_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, d_records, map_param, range_max, d_corr,
                                      ang_step, response, d_out, d_volume=None, stream=None):
@@ -1162,6 +1213,46 @@ def grid_search(search=None, **kw):
     return lsd_grid_search(int(wx), int(wy), int(na), float(step), mb, mn, md)
 
 
+GRID_LOCATE_KEYS = ("x0", "y0", "nx", "ny", "ang0", "ang_step", "n_ang", "levels", "max_nodes", "score_floor", "min_beams", "min_num", "min_den")
+
+
+def grid_locate(locate=None, cols=None, rows=None, **kw):
+    """An lsd_grid_locate_par: `locate` itself, a dict or a tuple of GRID_LOCATE_KEYS, or keywords.  The box is nx x ny lidar cells from
+    (x0, y0) -- by default the whole grid, which takes cols and rows (the methods of a GridMapper and of a Context pass their own) --, the
+    headings ang0 + a * ang_step degrees for a < n_ang; the search runs over `levels` pyramid levels with at most max_nodes nodes alive
+    per level; a location is accepted with at least min_beams scored beams and a mean response of at least 255 * min_num / min_den.
+    The defaults of levels (4), max_nodes (2^20), n_ang and ang_step (360 headings of 1 degree) are PLACEHOLDERS: nobody has measured
+    which suit real maps (DESIGN.md 8.1.12 has what the probe found on generated rooms)."""
+    if isinstance(locate, lsd_grid_locate_par):
+        return locate
+    if isinstance(locate, dict):
+        kw = dict(locate, **kw)
+        locate = None
+    if locate is None or locate is True:
+        a = dict(x0=0, y0=0, nx=cols, ny=rows, ang0=0.0, ang_step=1.0, n_ang=360, levels=4, max_nodes=1 << 20, score_floor=0, min_beams=30,
+                 min_num=1, min_den=4)
+        unknown = set(kw) - set(a)
+        if unknown:
+            raise LsdError(LSD_ERR_INVALID, "grid_locate: unknown keys %s" % sorted(unknown))
+        a.update(kw)
+        if a["nx"] is None or a["ny"] is None:
+            raise LsdError(LSD_ERR_INVALID, "grid_locate: the default box is the whole grid; give nx and ny where no grid is known")
+        locate = tuple(a[k] for k in GRID_LOCATE_KEYS)
+    x0, y0, nx, ny, ang0, step, n_ang, levels, mx, fl, mb, mn, md = locate
+    mx, fl, mb, mn, md = _u32s(mx, fl, mb, mn, md, limit=(1 << 32,) * 5)
+    return lsd_grid_locate_par(int(x0), int(y0), int(nx), int(ny), float(ang0), float(step), int(n_ang), int(levels), mx, fl, mb, mn, md)
+
+
+def grid_pyramid_bytes(cols, rows, levels):
+    """lsd_grid_pyramid_bytes: the size of the pyramid buffer of a cols x rows lookup plane with the levels 0..levels (0: refused)."""
+    return int(load_library().lsd_grid_pyramid_bytes(int(cols), int(rows), int(levels)))
+
+
+def grid_pyramid_offset(cols, rows, h):
+    """lsd_grid_pyramid_offset: where level h starts in the pyramid buffer."""
+    return int(load_library().lsd_grid_pyramid_offset(int(cols), int(rows), int(h)))
+
+
 def grid_response(response=None, rx=3, ry=3, ra=1, keep=(1, 2)):
     """An lsd_grid_response: `response` itself, a dict of rx / ry / ra / keep (or keep_num, keep_den), a tuple (rx, ry, ra, keep_num,
     keep_den), or keywords.  The neighbourhood is +-rx, +-ry cells and +-ra angle steps around the winner; a candidate enters the
@@ -1353,7 +1444,7 @@ def _occupancy_grid(d_grid, cols, rows, device):
 class GridMapper:
     """Mapping with known poses: localised scans integrated into an occupancy grid on the device (k_gridmap.hip; include/lsd_hip.h,
     "mapping with known poses").  The reference has no counterpart -- its maps come from an outside SLAM --, and this is
-    no full SLAM either: no loop closure; a pose is entered as it is unless the match_* methods below correct it first.  The mapper owns two planes of rows x cols counters
+    no full SLAM either: no loop closure; a pose is entered as it is unless the match_* methods below correct it first (locate_* finds one without a prior).  The mapper owns two planes of rows x cols counters
     (torch tensors: uint32 values in int32 storage): `pass`, the beams that crossed a cell, and `hit`, those that ended in it.  A scan at
     pose (x, y in pixels of THIS grid, ang in degrees) adds one ray per beam, cut at range_max (metres; a cut beam passes and does not
     hit); publish_device() turns the planes into the int8 OccupancyGrid (-1 below min_pass passes, 100 where hit / pass >= occ[0] /
@@ -1376,6 +1467,7 @@ class GridMapper:
         self._planes = torch.zeros((2, self.rows * self.cols), dtype=torch.int32, device="cuda:%d" % int(self.ctx.device))
         self._corr = torch.zeros((self.rows, self.cols), dtype=torch.uint8, device=self._planes.device)     # likelihood_device's plane
         self._coarse = {}                                                    # coarse_device's planes, by block size
+        self._pyramids = {}                                                  # pyramid_device's buffers, by the number of levels
 
     @property
     def map_param(self):
@@ -1552,16 +1644,21 @@ class GridMapper:
                                          self._coarse[b].data_ptr(), b, search, rec.data_ptr(), st.data_ptr() if stats else None, ts.cuda_stream)
         return (rec, st) if stats else rec
 
-    def _checked(self, d_scans, d_lens, d_poses, pose_pitch):
+    def _checked_scans(self, d_scans, d_lens):
         import torch
         for name, t, dt in (("d_scans", d_scans, torch.float64), ("d_lens", d_lens, torch.int32)):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
                 raise LsdError(LSD_ERR_INVALID, "%s must be a contiguous CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
-        if not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous():
-            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor")
-        n, pitch = d_lens.numel(), int(pose_pitch)
+        n = d_lens.numel()
         if d_scans.dim() != 3 or d_scans.shape[0] != n or d_scans.shape[2] != 2 or d_scans.shape[1] < 1:
             raise LsdError(LSD_ERR_INVALID, "d_scans must be [n, stride >= 1, 2] with one length per scan")
+        return n
+
+    def _checked(self, d_scans, d_lens, d_poses, pose_pitch):
+        import torch
+        n, pitch = self._checked_scans(d_scans, d_lens), int(pose_pitch)
+        if not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous():
+            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor")
         if pitch < 24 or (n and d_poses.numel() * d_poses.element_size() < (n - 1) * pitch + 24):
             raise LsdError(LSD_ERR_INVALID, "d_poses holds fewer than n records of pose_pitch >= 24 bytes")
         return n, pitch
@@ -1658,6 +1755,66 @@ class GridMapper:
                           _cuda_stream(stream), block, stats, response, integrate=True, refresh=refresh, smear=smear, integrate_at=integrate_at)
         self._held_match = (d_scans, d_lens, d_poses)
         return rec
+
+    # -- global scan-to-grid localisation (k_gridlocate.hip) --
+    def pyramid_device(self, levels, stream=None):
+        """Refreshes the pyramid of block maxima of the lookup plane as it is now, levels 0..levels, on `stream` (default: the current
+        one).  Returns the buffer, a CUDA uint8 tensor of grid_pyramid_bytes(cols, rows, levels) bytes the mapper owns (one per number of
+        levels, allocated at its first use); level h starts at grid_pyramid_offset(cols, rows, h)."""
+        import torch
+        H = int(levels)
+        if not 0 <= H <= GRID_LOCATE_MAX_LEVELS:
+            raise LsdError(LSD_ERR_INVALID, "levels must be 0..8")
+        ts = _cuda_stream(stream)
+        pyr = self._pyramids
+        if H not in pyr:
+            with torch.cuda.stream(ts):
+                pyr[H] = torch.zeros(grid_pyramid_bytes(self.cols, self.rows, H), dtype=torch.uint8, device=self._planes.device)
+        self.ctx.enqueue_grid_pyramid_device(self.d_corr, self.cols, self.rows, H, pyr[H].data_ptr(), ts.cuda_stream)
+        return pyr[H]
+
+    def _enqueue_locate(self, ctx, d_scans, d_lens, n, stride, locate, refresh, smear, stats, ts):
+        """In stream order on ts: likelihood_device(smear) (refresh), pyramid_device, the location of the scans at device addresses.  n
+        records (a new CUDA uint8 tensor [n, 64]); with stats (records, a new CUDA uint8 tensor [n, 48])."""
+        import torch
+        par = grid_locate(locate, cols=self.cols, rows=self.rows)
+        if refresh:
+            self.likelihood_device(smear, ts)
+        pyr = self.pyramid_device(par.levels, ts)
+        with torch.cuda.stream(ts):
+            rec = torch.empty((n, GRID_LOCATE_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
+            st = torch.empty((n, GRID_LOCATE_STATS_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device) if stats else None
+        ctx.enqueue_grid_locate_device(d_scans, d_lens, n, stride, self.map_param, self.range_max, pyr.data_ptr(), par, rec.data_ptr(),
+                                       st.data_ptr() if stats else None, ts.cuda_stream)
+        return (rec, st) if stats else rec
+
+    def locate_device(self, d_scans, d_lens, locate=None, refresh=True, smear=None, stats=False, stream=None):
+        """Locates scans that are on the device (d_scans, d_lens of integrate_device) on the mapper's grid WITHOUT a prior pose: in stream
+        order likelihood_device(smear) (refresh=False: the plane as it is), pyramid_device and the search over the box and the headings of
+        `locate` (grid_locate(); None: the whole grid, its placeholder defaults).  Returns the records: a CUDA uint8 tensor [n, 64]
+        (GRID_LOCATE_DTYPE) whose heads are poses -- the located one where flags is GRID_LOCATE_ACCEPTED, else the "no pose" sentinel, so
+        match_device(d_scans, d_lens, records, 64) and integrate_device(d_scans, d_lens, records, 64) take them and skip the rest.
+        n_best > 1 says the map is ambiguous.  stats=True: (records, statistics: a CUDA uint8 tensor [n, 48], GRID_LOCATE_STATS_DTYPE).
+        On `stream`; nothing waits."""
+        n = self._checked_scans(d_scans, d_lens)
+        got = self._enqueue_locate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], locate, refresh, smear, stats,
+                                   _cuda_stream(stream))
+        self._held_locate = (d_scans, d_lens)                                # the launches read them: alive until the next call
+        return got
+
+    def locate(self, scans, lens, locate=None, refresh=True, smear=None, stats=False):
+        """locate_device for host arrays (scans float64 [n, stride, 2], lens int32 [n]); returns the records as a numpy array of
+        GRID_LOCATE_DTYPE (stats=True: with the statistics as GRID_LOCATE_STATS_DTYPE): a read-back, which waits for the device."""
+        import torch
+        ln0 = np.atleast_1d(np.asarray(lens))
+        sc, ln, _, ok = _host_scans(scans, lens, np.zeros((len(ln0), 3)))
+        if not ok or ((ln < 0) | (ln > sc.shape[1])).any():
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride")
+        dev = self._planes.device
+        got = self.locate_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), locate, refresh, smear, stats)
+        if not stats:
+            return got.cpu().numpy().reshape(-1).view(GRID_LOCATE_DTYPE).copy()
+        return got[0].cpu().numpy().reshape(-1).view(GRID_LOCATE_DTYPE).copy(), got[1].cpu().numpy().reshape(-1).view(GRID_LOCATE_STATS_DTYPE).copy()
 
     def counts(self):
         """(pass, hit) as numpy uint32 [rows, cols]: a read-back, which waits for the device."""
@@ -2330,6 +2487,21 @@ class Localizer(_Ticks):
         correct (fa_correct(); True: its defaults) given -- it needs response, else LSD_ERR_INVALID --: correct_last_tick behind the
         response stage, and its reports are returned last in the tuple.  None, the default, enqueues nothing more."""
         return self._refine_and_integrate_last_tick(mapper, None, (None, 0), search, refresh, smear, block, response, integrate_at, correct)
+
+    def locate_last_tick(self, mapper, locate=None, refresh=True, smear=None, stats=False):
+        """Global localisation of the last tick's scans (GridMapper.locate_device): on the last tick's stream and behind
+        the tick, every frame slot of the tick is located on `mapper`'s grid from the tick's ingested scans alone -- the states the tick
+        produced play no part, so a robot whose tick ended in a reset, or one that has no pose yet, is located as well.  Nothing is read
+        back and nothing waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 64] (GRID_LOCATE_DTYPE; slot s * k + t is frame t
+        of robot s; a slot past a robot's n_frames holds an empty scan: GRID_LOCATE_EMPTY).  The located pose is NOT written into the
+        robot's carry: the replay loop's angle-offset bookkeeping has no defined state for a pose it did not find itself."""
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        S, k, ts, _ = self._last_tick
+        return mapper._enqueue_locate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, locate, refresh, smear, stats,
+                                      ts)
 
     def correct_last_tick(self, responses, correct=None):
         """The grid match response fused into the robots' carries (lsd_enqueue_fa_carry_correct_device): a measurement

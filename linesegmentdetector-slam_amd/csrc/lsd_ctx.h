@@ -88,6 +88,7 @@ struct lsd_ctx {
     DevBuf<uint8_t> fa_buf;
     DevBuf<uint8_t> gm_mr_ws;                           // lsd_enqueue_grid_match_mr_device: U, the coarse slots, the counts and the pick's slots
     DevBuf<uint32_t> gr_volume;                         // lsd_enqueue_grid_response_device: the volume of R where the caller gives none
+    DevBuf<uint8_t> gl_ws;                              // lsd_enqueue_grid_locate_device: the regions grid_locate_ws names
     DevBuf<uint8_t> gm_slots;                           // lsd_enqueue_grid_match_device: the per-(scan, angle) slots between its two kernels
     std::vector<int> fa_nf;                             // the host copy of the last localize enqueue's frame counts (its upload's source)
     // the fleet entries' map tables: the host copies their uploads read (as fa_nf) and the device records the kernels read; the first

@@ -1,6 +1,6 @@
 // lsd_grid.hip -- the grid stack's part of the C ABI (include/lsd_hip.h): mapping with known poses (k_gridmap.hip), the correlative
 // scan-to-grid match, plain (k_gridmatch.hip) and coarse to fine (k_gridmatch_mr.hip), and the response around a match
-// (k_gridresponse.hip).  The four scan-taking device entries receive the scans of a frame the same way: one check (grid_scans_bad)
+// (k_gridresponse.hip), ray casting (k_gridray.hip) and the global localisation (k_gridlocate.hip).  The scan-taking device entries receive the scans of a frame the same way: one check (grid_scans_bad)
 // turns those arguments into the view the launchers take, and each entry adds only what is its own.  Their host conveniences share one
 // check and one staging path (host_scans_bad, stage_scans) in the same way.
 #include <math.h>
@@ -336,6 +336,100 @@ int lsd_grid_raycast(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_
     HIPCHK(c, hipMemcpyAsync(out, d_out, beams * sizeof(lsd_grid_ray), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(sum, d_sum, ns * sizeof(lsd_grid_ray_sum), hipMemcpyDeviceToHost, c->stream));
     if (scans_out) HIPCHK(c, hipMemcpyAsync(scans_out, d_so, beams * sizeof(lsd_polar), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+// --- global scan-to-grid localisation (k_gridlocate.hip) ---
+static_assert(sizeof(lsd_grid_locate_par) == 64 && offsetof(lsd_grid_locate_par, nx) == 8 && offsetof(lsd_grid_locate_par, ang0) == 16 &&
+              offsetof(lsd_grid_locate_par, n_ang) == 32 && offsetof(lsd_grid_locate_par, max_nodes) == 40 && offsetof(lsd_grid_locate_par, min_den) == 56,
+              "lsd_grid_locate_par is 64 bytes: four int32, two doubles, two int32, five uint32");
+static_assert(sizeof(lsd_grid_locate_rec) == 64 && offsetof(lsd_grid_locate_rec, x) == 0 && offsetof(lsd_grid_locate_rec, y) == 8 &&
+              offsetof(lsd_grid_locate_rec, ang) == 16 && offsetof(lsd_grid_locate_rec, reserved) == 56,
+              "lsd_grid_locate_rec is 64 bytes and starts with a pose: an array of them is a d_poses argument of pitch 64");
+
+static bool grid_pyramid_bad(int cols, int rows, int levels) {
+    return cols <= 0 || rows <= 0 || cols > 65535 || rows > 65535 || levels < 0 || levels > LSD_GRID_LOCATE_MAX_LEVELS;
+}
+
+size_t lsd_grid_pyramid_bytes(int cols, int rows, int levels) {
+    return grid_pyramid_bad(cols, rows, levels) ? 0 : grid_pyramid_offset(cols, rows, levels + 1);
+}
+
+size_t lsd_grid_pyramid_offset(int cols, int rows, int h) {
+    return grid_pyramid_bad(cols, rows, h) ? (size_t)-1 : grid_pyramid_offset(cols, rows, h);
+}
+
+int lsd_enqueue_grid_pyramid_device(lsd_ctx* c, const uint8_t* d_corr, int cols, int rows, int levels, uint8_t* d_pyramid, void* stream) {
+    if (!c || !d_corr || !d_pyramid || grid_pyramid_bad(cols, rows, levels)) return LSD_ERR_INVALID;
+    return enqueue_on(c, stream, [&](hipStream_t s) { launch_grid_pyramid(d_corr, cols, rows, levels, d_pyramid, s); return LSD_OK; });
+}
+
+// what the locate entries refuse about the box, the headings, the levels and the acceptance
+static bool grid_locate_bad(const lsd_grid_locate_par& p) {
+    if (p.x0 < -(1 << 20) || p.x0 > (1 << 20) || p.y0 < -(1 << 20) || p.y0 > (1 << 20)) return true;
+    if (p.nx < 1 || p.nx > 65535 || p.ny < 1 || p.ny > 65535 || p.n_ang < 1 || p.n_ang > 4096) return true;
+    if (!std::isfinite(p.ang0) || !std::isfinite(p.ang_step) || p.ang_step < 0 || (p.ang_step == 0 && p.n_ang > 1)) return true;
+    if (p.levels < 0 || p.levels > LSD_GRID_LOCATE_MAX_LEVELS || p.max_nodes < 1 || p.max_nodes > (1u << 24)) return true;
+    if (p.min_den == 0 || p.min_num > p.min_den) return true;
+    return grid_locate_top_nodes(p) > ((size_t)1 << 28);
+}
+
+size_t lsd_grid_locate_workspace_bytes(int n_scans, int stride, lsd_grid_locate_par par) {
+    if (n_scans < 0 || stride <= 0 || stride > LSD_SCAN_MAX_LEN || grid_locate_bad(par)) return 0;
+    size_t bytes[kGridLocateRegions];
+    grid_locate_ws(n_scans, stride, par, bytes);
+    Carver measure(nullptr);
+    uint8_t* r;
+    for (int i = 0; i < kGridLocateRegions; i++) measure(r, bytes[i]);
+    return measure.bytes_from(nullptr);
+}
+
+int lsd_enqueue_grid_locate_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, lsd_map_param mp,
+                                   double range_max, const uint8_t* d_pyramid, lsd_grid_locate_par par, lsd_grid_locate_rec* d_out,
+                                   lsd_grid_locate_stats* d_stats, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_pyramid || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_locate_bad(par))
+        return LSD_ERR_INVALID;
+    if ((addr(d_scans) & 15) || (addr(d_lens) & 3) || (addr(d_out) & 7) || (addr(d_stats) & 3)) {
+        c->err = "grid locate: d_scans 16-byte, d_out 8-byte, d_lens and d_stats 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        size_t bytes[kGridLocateRegions];
+        grid_locate_ws(n_scans, stride, par, bytes);
+        uint8_t* r[kGridLocateRegions];
+        auto regions = [&](Carver& k) { for (int i = 0; i < kGridLocateRegions; i++) k(r[i], bytes[i]); };
+        HIPCHK(c, carve(c->gl_ws, regions));                         // (grown: one synchronisation; else nothing but pointer arithmetic)
+        void* ws[kGridLocateRegions];
+        for (int i = 0; i < kGridLocateRegions; i++) ws[i] = r[i];
+        launch_grid_locate(d_scans, d_lens, n_scans, stride, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_pyramid, par, ws, d_out, d_stats, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_locate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp, double range_max,
+                    const uint8_t* corr, lsd_grid_locate_par par, lsd_grid_locate_rec* out, lsd_grid_locate_stats* stats) {
+    if (!c || !scans || !lens || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_locate_bad(par)) return LSD_ERR_INVALID;
+    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (n_scans == 0) return LSD_OK;
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    lsd_polar* d_sc; int* d_len; uint8_t *d_co, *d_py; lsd_grid_locate_rec* d_out; lsd_grid_locate_stats* d_st;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) {
+        k(d_sc, ns * stride); k(d_len, ns); k(d_co, cells); k(d_py, lsd_grid_pyramid_bytes(mp.oriMapCol, mp.oriMapRow, par.levels)); k(d_out, ns);
+        k(d_st, ns);
+    };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
+    int st = lsd_enqueue_grid_pyramid_device(c, d_co, mp.oriMapCol, mp.oriMapRow, par.levels, d_py, c->stream);
+    if (st == LSD_OK)
+        st = lsd_enqueue_grid_locate_device(c, d_sc, d_len, n_scans, stride, mp, range_max, d_py, par, d_out, stats ? d_st : nullptr, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_locate_rec), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_locate_stats), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
 }

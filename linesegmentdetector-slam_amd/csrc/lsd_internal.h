@@ -196,6 +196,18 @@ void launch_grid_response(const GridScans& g, const lsd_grid_match_rec* records,
 // gate), and with scans_out (may be null, may be g.scans) the screened readings; two launches, no workspace
 void launch_grid_raycast(const GridScans& g, const int8_t* grid, const lsd_grid_ray_par& par, lsd_grid_ray* out, lsd_grid_ray_sum* sum,
                          lsd_polar* scans_out, hipStream_t s);
+// global scan-to-grid localisation (k_gridlocate.hip): the pyramid of block maxima of a lookup plane (levels 0..levels one behind the other,
+// level h at grid_pyramid_offset), and the scans located in a box of cells and a fan of headings through kGridLocateRegions regions of
+// workspace -- the offsets, nb, L_a, the dense U_H, two node lists, the counters, the slots -- whose sizes grid_locate_ws gives; stats may
+// be null
+constexpr int kGridLocateRegions = 8;
+size_t grid_pyramid_offset(int cols, int rows, int h);
+void launch_grid_pyramid(const uint8_t* corr, int cols, int rows, int levels, uint8_t* pyramid, hipStream_t s);
+size_t grid_locate_top_nodes(const lsd_grid_locate_par& par);
+void grid_locate_ws(int n_scans, int stride, const lsd_grid_locate_par& par, size_t bytes[kGridLocateRegions]);
+void launch_grid_locate(const lsd_polar* scans, const int* lens, int n_scans, int stride, int cols, int rows, double resol, double range_max,
+                        const uint8_t* pyramid, const lsd_grid_locate_par& par, void* const ws[kGridLocateRegions], lsd_grid_locate_rec* out,
+                        lsd_grid_locate_stats* stats, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t
