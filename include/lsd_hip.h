@@ -501,6 +501,82 @@ int lsd_enqueue_fa_carry_correct_device(lsd_ctx *ctx, lsd_fa_carry *d_carry, int
  * may be NULL) are host arrays; every sequence takes part (no key).  Blocking. */
 int lsd_fa_carry_correct(lsd_ctx *ctx, lsd_fa_carry *carries, int n_seq, int frames_pitch, const lsd_position *poses,
                          const lsd_grid_response_rec *resp, lsd_fa_correct_par par, lsd_fa_correct_rep *rep);
+/* Relocalisation on the device: the robots whose tick left them without a pose are gathered, located on the grid (the section "global
+ * scan-to-grid localisation" below, its entry unchanged) and their carries seeded with the located pose, all on the tick's stream
+ * (csrc/k_falost.hip, csrc/k_faseed.hip; restated in tests/fa_relocate_cases.py).
+ * lsd_enqueue_fa_lost_gather_device picks the lost sequences of a tick and packs their scans into a batch of max_lost rows: what
+ * lsd_enqueue_grid_locate_device takes with n_scans = max_lost, so that its launches and its workspace follow max_lost and not the fleet.
+ * d_carry[n_seq], d_poses / pose_pitch (the tick's states, pitch 720) and d_key / key are the correction's; d_scans / d_lens / stride are
+ * the tick's ingested scans, slot s * frames_pitch + t.  Sequence s is LOST iff all of these hold:
+ *   - d_key is NULL or d_key[s] == key, read ON THE DEVICE as the re-base reads it
+ *   - fabs(x[0] + 1) < 0.0001, the "no pose" test of the re-base (a NaN x[0] is not lost)
+ *   - a slot exists: the LARGEST t in 0..frames_pitch-1 whose original pose's 24 bytes equal the 24 bytes of state.x[0..2] (the
+ *     correction's step 3: bytes, not values) AND whose d_lens[s * frames_pitch + t] > 0 -- the frame had a scan.  A lost robot whose tick
+ *     took no frame, or only empty scans, has no slot and is not gathered
+ * The lost sequences take the ranks j = 0, 1, .. in ASCENDING s (a fleet with more lost robots than max_lost serves the lowest indices
+ * first; rotating the start is the caller's).  For j < max_lost: d_pick[j] = s * frames_pitch + slot, row j of d_scans_out is that slot's
+ * `stride` readings byte for byte, d_lens_out[j] its length.  For the rows at and past the number gathered: d_lens_out[j] = 0 (the locate
+ * entry ends such a row in LSD_GRID_LOCATE_EMPTY without a search), d_pick[j] = -1, and the scan row keeps its bytes.  d_n_lost[0] = the
+ * number of lost sequences, exact, possibly above max_lost; d_n_lost[1] = min(d_n_lost[0], max_lost).
+ * Asynchronous on `stream`, ONE launch of min(max_lost, 128) workgroups whatever the data, no workspace, no atomics (the ranks are a
+ * ballot / mbcnt prefix count in one pass over n_seq, made by every workgroup for the ranks it copies), no allocation and no wait.  The
+ * slot search of a lost sequence runs on one lane, latest slot first: frames_pitch is a tick's few frames, not a log.  d_scans_out must
+ * not overlap d_scans.  Refused before anything is enqueued, LSD_ERR_INVALID, outputs untouched: a null pointer (d_key may be NULL); n_seq
+ * outside 1..65536; frames_pitch outside 1..4096; pose_pitch < 24 or not a multiple of 8; stride outside 1..the context's scan capacity;
+ * max_lost outside 1..4096; d_carry or d_poses not 8-byte, d_scans or d_scans_out not 16-byte, d_key, d_lens, d_lens_out, d_pick or
+ * d_n_lost not 4-byte aligned. */
+int lsd_enqueue_fa_lost_gather_device(lsd_ctx *ctx, const lsd_fa_carry *d_carry, int n_seq, int frames_pitch, const void *d_poses,
+                                      size_t pose_pitch, const lsd_polar *d_scans, const int *d_lens, int stride, const int32_t *d_key,
+                                      int32_t key, int max_lost, lsd_polar *d_scans_out, int *d_lens_out, int32_t *d_pick,
+                                      int32_t *d_n_lost /* [2] */, void *stream);
+/* lsd_enqueue_fa_carry_seed_device writes located poses into carries that have none, in place on d_carry[0..n_seq), asynchronous on
+ * `stream`, one launch, no workspace, no atomics: it allocates nothing and waits for nothing.  d_pick[n_pick] is the gather's, d_loc[n_pick]
+ * the locate records of the gathered rows, d_resp[n_pick] (may be NULL) the response records at those rows.  fp64 without FMA.  Per j the
+ * first test that fires decides; each outcome is exactly one flag; the carry keeps every byte unless the outcome is SEEDED.  Report: pose
+ * and ang_diff are +0.0 unless SEEDED; seq and slot are -1 for UNUSED, else d_pick[j] / frames_pitch and d_pick[j] % frames_pitch;
+ * loc_flags is d_loc[j].flags from step 3 on, 0 before:
+ *   0. d_pick[j] < 0: UNUSED
+ *   1. s = d_pick[j] / frames_pitch >= n_seq: BAD_PICK; nothing is touched
+ *   2. the carry's x[0] no longer passes fabs(x[0] + 1) < 0.0001: HAS_POSE -- the robot found itself, or was seeded, since the gather
+ *   3. d_loc[j].flags != LSD_GRID_LOCATE_ACCEPTED: NOT_LOCATED
+ *   4. d_loc[j].n_best > par.max_best: AMBIGUOUS (several candidates tie the winner: the map does not tell them apart)
+ *   5. with d_resp: VALID clear, or NONE, EMPTY or MISMATCH set: NO_RESPONSE; x, y, ang or one of cov[0..5] not finite: NOT_FINITE (the
+ *      correction's step 4).  Without d_resp: the located x, y or ang not finite: NOT_FINITE
+ *   6. SEEDED.  z = the located (x, y, ang); with d_resp the response's.  state.x = (z[0], z[1], z[2], +0.0 x 6).  state.P = +0.0 but for
+ *      the entries 3..8 of the diagonal, (1, 1, 1, .1, .1, .1) as lsd_fa_initial_state has them, and the leading block: without d_resp the
+ *      diagonal (var_xy, var_xy, var_ang); with d_resp R of the correction's step 5 from cov_scale, floor_xy and floor_ang, written
+ *      symmetric.  The loop's bookkeeping is its own lines (k_fa.hip; the reference's main_on_windows.cpp:165-172) applied as to a first
+ *      frame, REPLACING what the carry held:  d = z[2] - atand(carry.odom.ang);  off = fabs(d) > 90;  if (off && d < 0) d += 360;
+ *      ang_sum = 0.0 + d;  ang_count = 1.0;  is_offset = off.  odom and frames keep their bytes, so the cnt_frame == 1 test of the next
+ *      frame stays the sequence's own, and its theta is d / 1 where a hand-made carry with no offsets gives 0 / 0 (see
+ *      lsd_enqueue_localize_device).  Replaced and not appended: the reset frames in front have each pushed 0 - atand(odom) into the mean,
+ *      which is no offset between the map and the odometry at all
+ * Two j never name one sequence when d_pick is the gather's; a hand-made d_pick that names a sequence twice is the caller's error (the
+ * two writes race).  d_rep may be NULL.  Refused before anything is enqueued, LSD_ERR_INVALID, outputs untouched: a null ctx, d_carry,
+ * d_pick or d_loc; n_seq <= 0; frames_pitch outside 1..4096; n_pick outside 1..4096; max_best == 0; one of the five real parameters not
+ * finite or negative; var_xy or var_ang not > 0 where d_resp is NULL; d_carry, d_loc, d_resp or d_rep not 8-byte, d_pick not 4-byte
+ * aligned. */
+typedef struct lsd_grid_locate_rec lsd_grid_locate_rec;
+typedef struct lsd_fa_seed_par { double var_xy, var_ang, cov_scale, floor_xy, floor_ang; uint32_t max_best, reserved; } lsd_fa_seed_par;   /* 48 bytes */
+typedef struct lsd_fa_seed_rep {                                                                                                          /* 48 bytes */
+    double pose[3]; double ang_diff; int32_t seq, slot; uint32_t flags, loc_flags;
+} lsd_fa_seed_rep;
+enum { LSD_FA_SEED_SEEDED = 1, LSD_FA_SEED_UNUSED = 2, LSD_FA_SEED_BAD_PICK = 4, LSD_FA_SEED_HAS_POSE = 8, LSD_FA_SEED_NOT_LOCATED = 16,
+       LSD_FA_SEED_AMBIGUOUS = 32, LSD_FA_SEED_NO_RESPONSE = 64, LSD_FA_SEED_NOT_FINITE = 128 };
+int lsd_enqueue_fa_carry_seed_device(lsd_ctx *ctx, lsd_fa_carry *d_carry, int n_seq, int frames_pitch, const int32_t *d_pick, int n_pick,
+                                     const lsd_grid_locate_rec *d_loc, const lsd_grid_response_rec *d_resp /* may be NULL */,
+                                     lsd_fa_seed_par par, lsd_fa_seed_rep *d_rep /* may be NULL */, void *stream);
+/* Host conveniences: the arrays are host arrays of any alignment (the rules above are about device memory, which the context's staging
+ * supplies), every sequence takes part (no key).  Blocking.
+ * lsd_fa_lost_gather: carries (n_seq), poses (n_seq x frames_pitch, packed), scans (n_seq x frames_pitch x stride) and lens (n_seq x
+ * frames_pitch) travel to the context's staging with scans_out (max_lost x stride: the rows past the gathered ones come back as they
+ * went), the gather runs, scans_out, lens_out, pick and n_lost come back.  lens[i] outside 0..stride: LSD_ERR_INVALID.
+ * lsd_fa_carry_seed: carries (n_seq, updated in place), pick, loc, resp (n_pick each; resp may be NULL) and rep (n_pick, may be NULL). */
+int lsd_fa_lost_gather(lsd_ctx *ctx, const lsd_fa_carry *carries, int n_seq, int frames_pitch, const lsd_position *poses,
+                       const lsd_polar *scans, const int *lens, int stride, int max_lost, lsd_polar *scans_out, int *lens_out,
+                       int32_t *pick, int32_t *n_lost /* [2] */);
+int lsd_fa_carry_seed(lsd_ctx *ctx, lsd_fa_carry *carries, int n_seq, int frames_pitch, const int32_t *pick, int n_pick,
+                      const lsd_grid_locate_rec *loc, const lsd_grid_response_rec *resp, lsd_fa_seed_par par, lsd_fa_seed_rep *rep);
 /* Host convenience: replays one whole log.  scans: n_frames lidar frames at a pitch of `stride` readings, frame t holding lens[t]
  * finite readings (the driver drops the infinite ranges, :115-121); odom: n_frames + 1 rows (the Odom vector); init NULL: the
  * initial state (a reset state, see lsd_enqueue_localize_device).  Runs FeatureScan on every frame, then the loop; states / reports:
@@ -794,7 +870,8 @@ int lsd_grid_raycast(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int 
  * box of lidar cells and a whole fan of headings on the lookup plane (csrc/k_gridlocate.hip; restated in
  * tests/grid_locate_cases.py).  Branch and bound over a max-pyramid (Olson; Cartographer's fast correlative matcher), held to the
  * exhaustive search byte for byte: the winner's order is made of integers.  fp64 without FMA, the integration's helpers.  The heading
- * axis is not coarsened.  NOT built: writing the located pose into a reset carry, the fleet classes, loop closure proper.
+ * axis is not coarsened.  Writing the located pose into a reset carry is lsd_enqueue_fa_lost_gather_device / lsd_enqueue_fa_carry_seed_device
+ * above (the section "relocalisation on the device"), around this entry as it is.  NOT built: loop closure proper.
  *   candidates  (a, q, p), a < n_ang, q < ny, p < nx: the lidar at cell (x0 + p, y0 + q), the heading theta_a = ang0 + (double) a *
  *   ang_step;  lin = ((uint64) a * ny + q) * nx + p.  The box may overhang or leave the grid
  *   a beam is SCORED at a iff the integration does not skip it at the pose (0, 0, theta_a), range <= range_max and th = angle + theta_a /

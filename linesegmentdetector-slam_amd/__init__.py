@@ -171,6 +171,18 @@ assert FA_CORRECT_DTYPE.itemsize == 48 and C.sizeof(lsd_fa_correct) == 32
  FA_CORRECT_GATED) = 1, 2, 4, 8, 16, 32, 64
 
 
+# relocalisation on the device (include/lsd_hip.h): the seed's parameters and its report
+class lsd_fa_seed(C.Structure):        # the C side's lsd_fa_seed_par
+    _fields_ = [("var_xy", C.c_double), ("var_ang", C.c_double), ("cov_scale", C.c_double), ("floor_xy", C.c_double), ("floor_ang", C.c_double),
+                ("max_best", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FA_SEED_DTYPE = np.dtype([("pose", "f8", (3,)), ("ang_diff", "f8"), ("seq", "i4"), ("slot", "i4"), ("flags", "u4"), ("loc_flags", "u4")])   # lsd_fa_seed_rep
+assert FA_SEED_DTYPE.itemsize == 48 and C.sizeof(lsd_fa_seed) == 48
+(FA_SEED_SEEDED, FA_SEED_UNUSED, FA_SEED_BAD_PICK, FA_SEED_HAS_POSE, FA_SEED_NOT_LOCATED, FA_SEED_AMBIGUOUS, FA_SEED_NO_RESPONSE,
+ FA_SEED_NOT_FINITE) = 1, 2, 4, 8, 16, 32, 64, 128
+
+
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -253,6 +265,10 @@ _ABI = {
     "lsd_enqueue_fa_carry_rebase_device": (_i, [_vp, _vp, _i, _vp, C.c_int32, lsd_map_frame, lsd_map_frame, _vp]),
     "lsd_enqueue_fa_carry_correct_device": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, C.c_int32, lsd_fa_correct, _vp, _vp]),
     "lsd_fa_carry_correct": (_i, [_vp, _vp, _i, _i, _vp, _vp, lsd_fa_correct, _vp]),
+    "lsd_enqueue_fa_lost_gather_device": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, C.c_int32, _i, _vp, _vp, _vp, _vp, _vp]),
+    "lsd_fa_lost_gather": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_fa_carry_seed_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, lsd_fa_seed, _vp, _vp]),
+    "lsd_fa_carry_seed": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, lsd_fa_seed, _vp]),
     "lsd_enqueue_map_update_device": (_i, [_vp, _vp, _i, _i, _dbl, _dbl, _ppar, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "lsd_reserve_map_update": (_i, [_vp, _i, _i]),
     "lsd_enqueue_scan_ingest_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
@@ -704,6 +720,60 @@ class Context:
         rep = np.zeros(len(cy), FA_CORRECT_DTYPE)
         self._chk(self.L.lsd_fa_carry_correct(self.h, cy.ctypes.data, len(cy), po.shape[1], po.ctypes.data, rs.ctypes.data, fa_correct(correct),
                                               rep.ctypes.data))
+        return cy, rep
+
+    # -- relocalisation: gather the lost, (locate,) seed the carries (k_falost.hip, k_faseed.hip) --
+    def enqueue_fa_lost_gather_device(self, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_scans, d_lens, stride, d_key, key, max_lost,
+                                      d_scans_out, d_lens_out, d_pick, d_n_lost, stream=None):
+        """lsd_enqueue_fa_lost_gather_device on raw device addresses: the sequences without a pose whose tick had a scan (d_key: None, or
+        device int32 [n_seq] with sequence s taking part iff d_key[s] == key) take ranks in ascending s; the first max_lost have their slot
+        written to d_pick (int32 [max_lost], -1 beyond), their scan row copied to d_scans_out ([max_lost, stride, 2] doubles) and its length
+        to d_lens_out (0 beyond); d_n_lost: int32 [2], the number lost and the number gathered.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_fa_lost_gather_device(self.h, d_carry, int(n_seq), int(frames_pitch), d_poses, int(pose_pitch), d_scans,
+                                                                  d_lens, int(stride), d_key, int(key), int(max_lost), d_scans_out, d_lens_out,
+                                                                  d_pick, d_n_lost, stream))
+
+    def fa_lost_gather(self, carries, poses, scans, lens, max_lost, scans_out=None):
+        """lsd_fa_lost_gather from host arrays: carries FA_CARRY_DTYPE [n_seq], poses float64 [n_seq, frames_pitch, 3], scans float64 [n_seq,
+        frames_pitch, stride, 2], lens int32 [n_seq, frames_pitch]; scans_out (float64 [max_lost, stride, 2]; None: zeros) is what the rows
+        past the gathered ones keep.  Returns (scans_out, lens_out int32 [max_lost], pick int32 [max_lost], n_lost int32 [2]); the arguments
+        are not modified.  Blocking."""
+        cy = np.ascontiguousarray(carries, FA_CARRY_DTYPE).reshape(-1)
+        po, sc, ln = np.ascontiguousarray(poses, np.float64), np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32)
+        n = int(max_lost)
+        if (po.ndim != 3 or po.shape[0] != len(cy) or po.shape[2] != 3 or sc.ndim != 4 or sc.shape[:2] != po.shape[:2] or sc.shape[3] != 2 or
+                ln.shape != po.shape[:2] or not 1 <= n <= 4096):
+            raise LsdError(LSD_ERR_INVALID, "carries [n], poses [n, frames_pitch, 3], scans [n, frames_pitch, stride, 2], lens [n, frames_pitch], "
+                                            "max_lost 1..4096")
+        so = np.zeros((n, sc.shape[2], 2)) if scans_out is None else np.array(scans_out, np.float64)
+        if so.shape != (n, sc.shape[2], 2):
+            raise LsdError(LSD_ERR_INVALID, "scans_out must be [max_lost, stride, 2]")
+        lo, pk, nl = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(2, np.int32)
+        self._chk(self.L.lsd_fa_lost_gather(self.h, cy.ctypes.data, len(cy), po.shape[1], po.ctypes.data, sc.ctypes.data, ln.ctypes.data, sc.shape[2],
+                                            n, so.ctypes.data, lo.ctypes.data, pk.ctypes.data, nl.ctypes.data))
+        return so, lo, pk, nl
+
+    def enqueue_fa_carry_seed_device(self, d_carry, n_seq, frames_pitch, d_pick, n_pick, d_loc, d_resp=None, seed=None, d_rep=None, stream=None):
+        """lsd_enqueue_fa_carry_seed_device on raw device addresses: for each of the n_pick slots of d_pick (the gather's) whose carry still
+        has no pose, whose locate record at d_loc (GRID_LOCATE_DTYPE) is accepted and names at most seed.max_best equal winners, the carry
+        becomes the located pose -- d_resp (GRID_RESPONSE_DTYPE [n_pick]) given: the response's, with its covariance -- at rest, and the
+        loop's angle bookkeeping the one offset a first frame there would push.  seed: fa_seed().  d_rep: None, or n_pick reports of
+        FA_SEED_DTYPE.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_fa_carry_seed_device(self.h, d_carry, int(n_seq), int(frames_pitch), d_pick, int(n_pick), d_loc, d_resp,
+                                                                 fa_seed(seed), d_rep, stream))
+
+    def fa_carry_seed(self, carries, frames_pitch, pick, loc, resp=None, seed=None):
+        """lsd_fa_carry_seed from host arrays: carries FA_CARRY_DTYPE [n_seq], pick int32 [n_pick], loc GRID_LOCATE_DTYPE [n_pick], resp None or
+        GRID_RESPONSE_DTYPE [n_pick].  Returns (the carries after, the reports: FA_SEED_DTYPE [n_pick]); the arguments are not modified.
+        Blocking."""
+        cy = np.array(carries, FA_CARRY_DTYPE).reshape(-1)
+        pk, lc = np.ascontiguousarray(pick, np.int32).reshape(-1), np.ascontiguousarray(loc)
+        rs = None if resp is None else np.ascontiguousarray(resp)
+        if lc.dtype != GRID_LOCATE_DTYPE or lc.shape != pk.shape or (rs is not None and (rs.dtype != GRID_RESPONSE_DTYPE or rs.shape != pk.shape)):
+            raise LsdError(LSD_ERR_INVALID, "pick int32 [n], loc GRID_LOCATE_DTYPE [n], resp None or GRID_RESPONSE_DTYPE [n]")
+        rep = np.zeros(len(pk), FA_SEED_DTYPE)
+        self._chk(self.L.lsd_fa_carry_seed(self.h, cy.ctypes.data, len(cy), int(frames_pitch), pk.ctypes.data, len(pk), lc.ctypes.data,
+                                           None if rs is None else rs.ctypes.data, fa_seed(seed), rep.ctypes.data))
         return cy, rep
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
@@ -1318,6 +1388,37 @@ def fa_correct(correct=None, cov_scale=1.0, floor_xy=1.0, floor_ang=1.0, gate=0.
     if len(vals) != 4 or not all(np.isfinite(v) and v >= 0 for v in vals):
         raise LsdError(LSD_ERR_INVALID, "cov_scale, floor_xy, floor_ang and gate must be finite and >= 0")
     return lsd_fa_correct(*vals)
+
+
+FA_SEED_KEYS = ("var_xy", "var_ang", "cov_scale", "floor_xy", "floor_ang", "max_best")
+
+
+def fa_seed(seed=None, var_xy=1.0, var_ang=1.0, cov_scale=1.0, floor_xy=1.0, floor_ang=1.0, max_best=1):
+    """An lsd_fa_seed: `seed` itself, a dict of FA_SEED_KEYS, a tuple of the six in that order, or keywords (None / True: the defaults).
+    Without response records the seeded covariance of (x, y, ang) is diag(var_xy, var_xy, var_ang) (pixels^2, pixels^2, degrees^2; the
+    search's own resolution, one cell and one degree, by default); with them it is the response's covariance x cov_scale + the floors, as
+    fa_correct()'s R.  max_best: the most equal winners (the locate record's n_best) a seed accepts; 1 refuses every tie.
+    LsdError(LSD_ERR_INVALID) for a real value that is not finite or negative, or max_best outside 1..2^32-1."""
+    if isinstance(seed, lsd_fa_seed):
+        return seed
+    if isinstance(seed, dict):
+        a = dict(var_xy=var_xy, var_ang=var_ang, cov_scale=cov_scale, floor_xy=floor_xy, floor_ang=floor_ang, max_best=max_best)
+        unknown = set(seed) - set(a)
+        if unknown:
+            raise LsdError(LSD_ERR_INVALID, "fa_seed: unknown keys %s" % sorted(unknown))
+        a.update(seed)
+        seed = tuple(a[k] for k in FA_SEED_KEYS)
+    if seed is None or seed is True:
+        seed = (var_xy, var_ang, cov_scale, floor_xy, floor_ang, max_best)
+    if len(seed) != 6:
+        raise LsdError(LSD_ERR_INVALID, "fa_seed takes var_xy, var_ang, cov_scale, floor_xy, floor_ang, max_best")
+    vals = tuple(float(v) for v in seed[:5])
+    if not all(np.isfinite(v) and v >= 0 for v in vals):
+        raise LsdError(LSD_ERR_INVALID, "var_xy, var_ang, cov_scale, floor_xy and floor_ang must be finite and >= 0")
+    mb, = _u32s(seed[5], limit=(1 << 32,))
+    if mb == 0:
+        raise LsdError(LSD_ERR_INVALID, "max_best must be at least 1")
+    return lsd_fa_seed(*vals, mb, 0)
 
 
 def map_frame(frame):
@@ -2238,6 +2339,50 @@ class _Ticks:
         self._held_correct = responses                                       # the launch reads it: alive until the next one
         return rep
 
+    def _checked_tick(self, mapper):
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
+        return self._last_tick
+
+    def _relocate_last_tick(self, mapper, key, locate, seed, max_lost, refresh, smear, response, search, stats, write=True):
+        """relocate_last_tick for the sequences `key` = (d_key, key) selects on the device, on the tick's stream and behind the tick: the
+        gather (the carries, the tick's states at pitch 720, its ingested scans), the mapper's locate on the gathered batch, with `response`
+        a match of zero window at the locate records (pitch 64: the response stage reads a match record's di / dj / da, which a locate
+        record does not have) and the response stage at those, then the seed (write=False: none, and no report)."""
+        import torch
+        S, k, ts, _ = self._checked_tick(mapper)
+        n, par = int(max_lost), fa_seed(seed) if write else None
+        if not 1 <= n <= 4096:
+            raise LsdError(LSD_ERR_INVALID, "max_lost must be 1..4096")
+        rp = None if response is None else grid_response(response)
+        if rp is not None:
+            se = grid_search(search)
+            se = lsd_grid_search(0, 0, 0, se.ang_step, se.min_beams, se.min_num, se.min_den)
+        locate = grid_locate(locate, cols=mapper.cols, rows=mapper.rows)         # (refused here: before the gather is enqueued)
+        dev, B = self._carry.device, self.n_beams
+        with torch.cuda.stream(ts):
+            sc = torch.zeros((n, B, 2), dtype=torch.float64, device=dev)         # rows past the gathered ones keep these zeros
+            ln, pick, n_lost = (torch.empty(c, dtype=torch.int32, device=dev) for c in (n, n, 2))
+            rep = torch.empty((n, FA_SEED_DTYPE.itemsize), dtype=torch.uint8, device=dev) if write else None
+        cx, d_cy = self.ctx, self._carry.data_ptr()
+        cx.enqueue_fa_lost_gather_device(d_cy, S, k, self._out.data_ptr(), FA_STATE_DTYPE.itemsize, self._scans.data_ptr(), self._lens.data_ptr(), B,
+                                         key[0], key[1], n, sc.data_ptr(), ln.data_ptr(), pick.data_ptr(), n_lost.data_ptr(), ts.cuda_stream)
+        got = mapper._enqueue_locate(cx, sc.data_ptr(), ln.data_ptr(), n, B, locate, refresh, smear, stats, ts)
+        parts = list(got) if stats else [got]
+        resp = rec0 = None
+        if rp is not None:
+            rec0 = mapper._enqueue_match(cx, sc.data_ptr(), ln.data_ptr(), n, B, parts[0].data_ptr(), GRID_LOCATE_DTYPE.itemsize, se, ts)
+            resp = mapper._enqueue_response(cx, sc.data_ptr(), ln.data_ptr(), n, B, parts[0].data_ptr(), GRID_LOCATE_DTYPE.itemsize, rec0.data_ptr(),
+                                            se, rp, ts)
+            parts.append(resp)
+        if write:
+            cx.enqueue_fa_carry_seed_device(d_cy, S, k, pick.data_ptr(), n, parts[0].data_ptr(), None if resp is None else resp.data_ptr(), par,
+                                            rep.data_ptr(), ts.cuda_stream)
+        self._held_relocate = (sc, ln, rec0, pick, n_lost, rep) + tuple(parts)  # the launches read them: alive until the next call
+        return (pick, n_lost) + tuple(parts) + ((rep,) if write else ())
+
     def step(self, lidar=None, odom=None, n_frames=None, *, ranges=None, angle_min_inc=None):
         """lidar float64 [S, k, n_beams, 2] raw frames (range, angle) as laserCallback reads them (infinite ranges dropped as lidar_frames
         does, on the device: k_ingest), odom float64 [S, k, 3] the NEW odometry row of each frame (Odom[cnt_frame]); S = n_robots; n_beams
@@ -2493,8 +2638,9 @@ class Localizer(_Ticks):
         the tick, every frame slot of the tick is located on `mapper`'s grid from the tick's ingested scans alone -- the states the tick
         produced play no part, so a robot whose tick ended in a reset, or one that has no pose yet, is located as well.  Nothing is read
         back and nothing waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 64] (GRID_LOCATE_DTYPE; slot s * k + t is frame t
-        of robot s; a slot past a robot's n_frames holds an empty scan: GRID_LOCATE_EMPTY).  The located pose is NOT written into the
-        robot's carry: the replay loop's angle-offset bookkeeping has no defined state for a pose it did not find itself."""
+        of robot s; a slot past a robot's n_frames holds an empty scan: GRID_LOCATE_EMPTY).  This call only reports: no carry is written,
+        and every slot is searched, the robots that know where they are included.  relocate_last_tick locates the lost robots alone and
+        writes the poses into their carries."""
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         if not isinstance(mapper, GridMapper):
@@ -2502,6 +2648,22 @@ class Localizer(_Ticks):
         S, k, ts, _ = self._last_tick
         return mapper._enqueue_locate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, locate, refresh, smear, stats,
                                       ts)
+
+    def relocate_last_tick(self, mapper, locate=None, seed=None, max_lost=1, refresh=True, smear=None, response=None, search=None, stats=False):
+        """Relocalisation of the robots the last tick left without a pose, on the last tick's stream and behind the tick,
+        in this order: the lost robots -- a carry without a pose whose tick had a scan -- are gathered in ascending index, the first
+        max_lost of them with their scans packed into a batch of max_lost rows (lsd_enqueue_fa_lost_gather_device); that batch is located
+        on `mapper`'s grid as locate_device locates (locate, refresh, smear, stats: its arguments), so the launches and the workspace
+        follow max_lost and not the fleet; with response (grid_response(); True: its defaults) a match of zero window at the located poses
+        -- the response stage reads a match record, which a locate record is not -- and the response stage behind it (search: its
+        ang_step and acceptance thresholds; the window is forced to zero); then the accepted, unambiguous poses are written into the
+        carries (lsd_enqueue_fa_carry_seed_device; seed: fa_seed()) with the loop's angle bookkeeping replaced by the one offset a first
+        frame at that pose would push, so the NEXT tick tracks from the located pose.  Nothing is read back and nothing waits.  Returns
+        CUDA tensors (pick int32 [max_lost]: the slot s * k + t gathered into each row, -1 for an unused row; n_lost int32 [2]: the robots
+        lost -- it may exceed max_lost: call again, the seeded ones are no longer lost -- and the robots gathered; the locate records
+        uint8 [max_lost, 64]; with stats their statistics [max_lost, 48]; with response the response records [max_lost, 192]; the seed
+        reports uint8 [max_lost, 48], FA_SEED_DTYPE)."""
+        return self._relocate_last_tick(mapper, (None, 0), locate, seed, max_lost, refresh, smear, response, search, stats)
 
     def correct_last_tick(self, responses, correct=None):
         """The grid match response fused into the robots' carries (lsd_enqueue_fa_carry_correct_device): a measurement
@@ -2710,6 +2872,24 @@ class FleetLocalizer(_Ticks):
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         return self._refine_and_integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i), (self._map_of.data_ptr(), i), search,
                                                     refresh, smear, block, response, integrate_at, correct)
+
+    def locate_last_tick(self, mapper, map_id, locate=None, max_lost=1, refresh=True, smear=None, stats=False):
+        """Global localisation of the LOST robots on map `map_id` from the last tick's scans, without writing a carry: relocate_last_tick's
+        gather and locate alone.  The robots' map ids are read on the device (d_key = the ids, key = map_id), so the call stays right
+        behind an assign() on the stream; there is no host-side selection as integrate_last_tick makes one, and hence no locate of every
+        slot as Localizer.locate_last_tick runs it -- a robot with a pose has its states, and GridMapper.locate_device takes any scans a
+        caller holds.  Returns CUDA tensors (pick int32 [max_lost], n_lost int32 [2], the locate records uint8 [max_lost, 64]; with stats
+        their statistics [max_lost, 48]); row j belongs to slot pick[j]."""
+        return self._relocate_last_tick(mapper, (self._map_of.data_ptr(), self._map_id(map_id)), locate, None, max_lost, refresh, smear, None, None,
+                                        stats, write=False)
+
+    def relocate_last_tick(self, mapper, map_id, locate=None, seed=None, max_lost=1, refresh=True, smear=None, response=None, search=None,
+                           stats=False):
+        """Localizer.relocate_last_tick for the lost robots on map `map_id`, read on the device when the kernels run (d_key = the robots' map
+        ids, key = map_id): right behind an assign() on the stream, and the robots on other maps keep every byte of their carries.  The
+        mapper's frame is that map's."""
+        return self._relocate_last_tick(mapper, (self._map_of.data_ptr(), self._map_id(map_id)), locate, seed, max_lost, refresh, smear, response,
+                                        search, stats)
 
     def correct_last_tick(self, responses, map_id, correct=None):
         """Localizer.correct_last_tick for the robots on map `map_id`, read on the device when the kernel runs (d_key = the robots' map ids,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "lsd_ctx.h"
+#include "fa_relocate_host.h"
 #include "k1_lds.h"
 #include "k_rdp_lds.h"
 
@@ -1336,6 +1337,84 @@ int lsd_fa_carry_correct(lsd_ctx* c, lsd_fa_carry* carries, int n_seq, int frame
     if (st != LSD_OK) return st;
     HIPCHK(c, hipMemcpyAsync(carries, d_cy, ns * sizeof(lsd_fa_carry), hipMemcpyDeviceToHost, s));
     if (rep) HIPCHK(c, hipMemcpyAsync(rep, d_rp, ns * sizeof(lsd_fa_correct_rep), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LSD_OK;
+}
+
+// Relocalisation (k_falost.hip, k_faseed.hip): the checks of fa_relocate_host.h, then one launch each.
+int lsd_enqueue_fa_lost_gather_device(lsd_ctx* c, const lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const void* d_poses, size_t pose_pitch,
+                                      const lsd_polar* d_scans, const int* d_lens, int stride, const int32_t* d_key, int32_t key, int max_lost,
+                                      lsd_polar* d_scans_out, int* d_lens_out, int32_t* d_pick, int32_t* d_n_lost, void* stream) {
+    if (fa_lost_refused(c != nullptr, c ? c->scan_cap : 0, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_scans, d_lens, stride, d_key, max_lost,
+                        d_scans_out, d_lens_out, d_pick, d_n_lost))
+        return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_fa_lost_gather(d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_scans, d_lens, stride, d_key, key, max_lost, d_scans_out, d_lens_out,
+                          d_pick, d_n_lost, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LSD_OK;
+}
+
+int lsd_fa_lost_gather(lsd_ctx* c, const lsd_fa_carry* carries, int n_seq, int frames_pitch, const lsd_position* poses, const lsd_polar* scans,
+                       const int* lens, int stride, int max_lost, lsd_polar* scans_out, int* lens_out, int32_t* pick, int32_t* n_lost) {
+    auto there = fa_host_stand_in;                               // (host arrays: the alignment rules are the staging's to keep)
+    if (fa_lost_refused(c != nullptr, c ? c->scan_cap : 0, there(carries), n_seq, frames_pitch, there(poses), sizeof(lsd_position), there(scans),
+                        there(lens), stride, nullptr, max_lost, there(scans_out), there(lens_out), there(pick), there(n_lost)))
+        return LSD_ERR_INVALID;
+    const FaLostStage n = fa_lost_stage(n_seq, frames_pitch, stride, max_lost);
+    if (fa_lost_bad_len(lens, n.slots, stride) >= 0) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    lsd_fa_carry* d_cy; lsd_position* d_po; lsd_polar *d_sc, *d_so; int *d_ln, *d_lo; int32_t *d_pk, *d_nl;
+    auto regions = [&](Carver& k) { k(d_cy, n.carries); k(d_po, n.slots); k(d_sc, n.readings); k(d_ln, n.slots); k(d_so, n.readings_out);
+                                    k(d_lo, n.rows); k(d_pk, n.rows); k(d_nl, 2); };
+    HIPCHK(c, carve(c->stage, regions));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_cy, carries, n.carries * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_po, poses, n.slots * sizeof(lsd_position), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, n.readings * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_ln, lens, n.slots * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_so, scans_out, n.readings_out * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
+    const int st = lsd_enqueue_fa_lost_gather_device(c, d_cy, n_seq, frames_pitch, d_po, sizeof(lsd_position), d_sc, d_ln, stride, nullptr, 0,
+                                                     max_lost, d_so, d_lo, d_pk, d_nl, s);
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(scans_out, d_so, n.readings_out * sizeof(lsd_polar), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(lens_out, d_lo, n.rows * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(pick, d_pk, n.rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(n_lost, d_nl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return LSD_OK;
+}
+
+int lsd_enqueue_fa_carry_seed_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const int32_t* d_pick, int n_pick,
+                                     const lsd_grid_locate_rec* d_loc, const lsd_grid_response_rec* d_resp, lsd_fa_seed_par par,
+                                     lsd_fa_seed_rep* d_rep, void* stream) {
+    if (fa_seed_refused(c != nullptr, d_carry, n_seq, frames_pitch, d_pick, n_pick, d_loc, d_resp, par, d_rep)) return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_fa_seed(d_carry, n_seq, frames_pitch, d_pick, n_pick, d_loc, d_resp, par, d_rep, (hipStream_t)stream);
+    HIPCHK(c, hipGetLastError());
+    return LSD_OK;
+}
+
+int lsd_fa_carry_seed(lsd_ctx* c, lsd_fa_carry* carries, int n_seq, int frames_pitch, const int32_t* pick, int n_pick,
+                      const lsd_grid_locate_rec* loc, const lsd_grid_response_rec* resp, lsd_fa_seed_par par, lsd_fa_seed_rep* rep) {
+    auto there = fa_host_stand_in;                               // (host arrays: the alignment rules are the staging's to keep)
+    if (fa_seed_refused(c != nullptr, there(carries), n_seq, frames_pitch, there(pick), n_pick, there(loc), there(resp), par, there(rep)))
+        return LSD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ns = (size_t)n_seq, np = (size_t)n_pick;
+    lsd_fa_carry* d_cy; int32_t* d_pk; lsd_grid_locate_rec* d_lc; lsd_grid_response_rec* d_re; lsd_fa_seed_rep* d_rp;
+    auto regions = [&](Carver& k) { k(d_cy, ns); k(d_pk, np); k(d_lc, np); k(d_re, np); k(d_rp, np); };
+    HIPCHK(c, carve(c->stage, regions));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_cy, carries, ns * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_pk, pick, np * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_lc, loc, np * sizeof(lsd_grid_locate_rec), hipMemcpyHostToDevice, s));
+    if (resp) HIPCHK(c, hipMemcpyAsync(d_re, resp, np * sizeof(lsd_grid_response_rec), hipMemcpyHostToDevice, s));
+    const int st = lsd_enqueue_fa_carry_seed_device(c, d_cy, n_seq, frames_pitch, d_pk, n_pick, d_lc, resp ? d_re : nullptr, par,
+                                                    rep ? d_rp : nullptr, s);
+    if (st != LSD_OK) return st;
+    HIPCHK(c, hipMemcpyAsync(carries, d_cy, ns * sizeof(lsd_fa_carry), hipMemcpyDeviceToHost, s));
+    if (rep) HIPCHK(c, hipMemcpyAsync(rep, d_rp, np * sizeof(lsd_fa_seed_rep), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return LSD_OK;
 }

@@ -244,6 +244,12 @@ void launch_fa_rebase(lsd_fa_carry* carry, int n_seq, const int32_t* key_of, int
 // the grid match response fused into the carries, in place (k_facorrect.hip: k_fa_correct): one launch, no workspace
 void launch_fa_correct(lsd_fa_carry* carry, int n_seq, int frames_pitch, const void* poses, size_t pose_pitch, const lsd_grid_response_rec* resp,
                        const int32_t* key_of, int32_t key, lsd_fa_correct_par par, lsd_fa_correct_rep* rep, hipStream_t s);
+// relocalisation (k_falost.hip: k_fa_lost_gather; k_faseed.hip: k_fa_seed): one launch each, no workspace
+void launch_fa_lost_gather(const lsd_fa_carry* carry, int n_seq, int frames_pitch, const void* poses, size_t pose_pitch, const lsd_polar* scans,
+                           const int* lens, int stride, const int32_t* key_of, int32_t key, int max_lost, lsd_polar* scans_out, int* lens_out,
+                           int32_t* pick, int32_t* n_lost, hipStream_t s);
+void launch_fa_seed(lsd_fa_carry* carry, int n_seq, int frames_pitch, const int32_t* pick, int n_pick, const lsd_grid_locate_rec* loc,
+                    const lsd_grid_response_rec* resp, lsd_fa_seed_par par, lsd_fa_seed_rep* rep, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and
