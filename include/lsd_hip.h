@@ -943,6 +943,51 @@ int lsd_grid_locate(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n
                     double range_max, const uint8_t *corr, lsd_grid_locate_par par, lsd_grid_locate_rec *out,
                     lsd_grid_locate_stats *stats);
 
+/* --- the same search with the bound tightened level by level, and a level that overflows retried once ------------------------------- */
+/* The entry above fixes L once, from one greedy descent per heading that starts at the top level, and never raises it.  This one
+ * (csrc/k_gridlocate_tight.hip; restated in tests/grid_locate_tight_cases.py) is the same search -- the same candidates,
+ * offsets, S, pyramid, nodes, U, outcome and record -- under this rule.  Write L_H for the L above, H = levels, G_H = F_H.  For h = H .. 1:
+ *   1. expand: G_(h-1) = the existing children of the nodes of G_h with U_(h-1) >= L_h.  At h = 1 they are the candidates and the search
+ *      ends as above: the key maximum and the count of equals (L_0 = L_1)
+ *   2. probe (h - 1 >= 1 and LSD_GRID_LOCATE_TIGHT_PROBE), per heading a: the node of G_(h-1) at heading a with the largest U_(h-1), among
+ *      equals the smallest Q nbx_(h-1) + P (nbx_(h-1) = ceil(nx / 2^(h-1))) -- of the WHOLE set, the nodes that did not fit the list
+ *      included; a heading without a node has no probe.  From it the greedy descent of the entry above, unchanged, ends at a candidate of
+ *      score S_a.  L_(h-1) = max(L_h, max_a S_a); without the flag L_(h-1) = L_h
+ *   3. retry (LSD_GRID_LOCATE_TIGHT_RETRY and |G_(h-1)| > max_nodes): G_(h-1) is rebuilt once, the children of G_h with U_(h-1) >= L_(h-1);
+ *      the first count is kept in first_count[h-1] and bit h - 1 of `retried` is set.  No second probe follows
+ *   4. OVERFLOW iff |G_(h-1)| > max_nodes for some h - 1 >= 1 after the retry where there was one, or |G_H| > max_nodes (no retry: no bound
+ *      was raised yet).  The count is exact; the level and those below it are not run
+ * Filtering is lazy: a node of G_(h-1) whose U is below a raised L_(h-1) stays and yields no children (a child's U never exceeds its
+ * parent's), so the sets above ARE what the lists hold.  Correctness: every L_h is score_floor or the S of an existing candidate, so with
+ * score_floor <= S_win every L_h <= S_win; every ancestor of a candidate that ties the winner has U >= S_win >= L_h and survives the
+ * expansion and the retry: winner, n_best, outcome and pose are the exhaustive search's.
+ * The record is lsd_grid_locate_rec; lower_bound = the last L_h reached.  The statistics (d_stats, may be NULL; 128 bytes per scan), whose
+ * first 48 bytes read as lsd_grid_locate_stats: frontier[h] = |G_h| (a retried level: the second count);  scored = top_nodes + every child
+ * evaluated, a retried level's twice;  retried;  bound[h] = L_h for h <= H, 0 above H and below an overflow;  first_count[h] = the count
+ * before a retry, else 0;  EMPTY: all 0.
+ * tight = 0: every record byte and the first 48 statistics bytes are the entry's above; levels <= 1 has no probe and no retry, whatever
+ * `tight`.
+ * lsd_enqueue_grid_locate_tight_device: levels + 6 + max(levels - 1, 0) * (1 + probe + retry) launches, probe and retry 1 where the flag
+ * is set: offsets, top level, bound, frontier seed, the tight words, one expansion per level, between two levels the level kernel and
+ * with their flags the probes and the retry, pick.  A number fixed by par and tight, never by the data: a retry that is not needed is a
+ * launch that returns.  Asynchronous on `stream`; the workspace (lsd_grid_locate_tight_workspace_bytes: the entry's above, 128 bytes per
+ * scan and 8 per scan and heading) is the context's, the same buffer, grown before the first launch when needed -- that case alone
+ * synchronises; no other allocation, copy or host wait.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: whatever the
+ * entry above refuses; `tight` with a bit beyond the two flags; d_stats not 4-byte aligned.  n_scans == 0 launches nothing. */
+#define LSD_GRID_LOCATE_TIGHT_PROBE 1u
+#define LSD_GRID_LOCATE_TIGHT_RETRY 2u
+typedef struct lsd_grid_locate_tight_stats {   /* 128 bytes */
+    uint32_t top_nodes, frontier[9], scored, retried, bound[9], first_count[9], reserved[2];
+} lsd_grid_locate_tight_stats;
+size_t lsd_grid_locate_tight_workspace_bytes(int n_scans, int stride, lsd_grid_locate_par par);
+int lsd_enqueue_grid_locate_tight_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_scans, int stride,
+                                         lsd_map_param map_param, double range_max, const uint8_t *d_pyramid, lsd_grid_locate_par par,
+                                         uint32_t tight, lsd_grid_locate_rec *d_out, lsd_grid_locate_tight_stats *d_stats, void *stream);
+/* Host convenience: lsd_grid_locate with the tight entry in its place.  Blocking. */
+int lsd_grid_locate_tight(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_scans, int stride, lsd_map_param map_param,
+                          double range_max, const uint8_t *corr, lsd_grid_locate_par par, uint32_t tight, lsd_grid_locate_rec *out,
+                          lsd_grid_locate_tight_stats *stats);
+
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */
 void lsd_scaled_size(int cols, int rows, double sca, int *w, int *h);

@@ -147,6 +147,10 @@ GRID_LOCATE_STATS_DTYPE = np.dtype([("top_nodes", "u4"), ("frontier", "u4", (9,)
 assert GRID_LOCATE_DTYPE.itemsize == 64 == C.sizeof(lsd_grid_locate_par) and GRID_LOCATE_STATS_DTYPE.itemsize == 48
 GRID_LOCATE_ACCEPTED, GRID_LOCATE_REJECTED, GRID_LOCATE_NOT_FOUND, GRID_LOCATE_OVERFLOW, GRID_LOCATE_EMPTY = 1, 2, 4, 8, 16
 GRID_LOCATE_MAX_LEVELS = 8
+GRID_LOCATE_TIGHT_STATS_DTYPE = np.dtype([("top_nodes", "u4"), ("frontier", "u4", (9,)), ("scored", "u4"), ("retried", "u4"), ("bound", "u4", (9,)),
+                                          ("first_count", "u4", (9,)), ("reserved", "u4", (2,))])                                      # lsd_grid_locate_tight_stats
+assert GRID_LOCATE_TIGHT_STATS_DTYPE.itemsize == 128
+GRID_LOCATE_TIGHT_PROBE, GRID_LOCATE_TIGHT_RETRY = 1, 2
 
 # FeatureAssociation (include/lsd_hip.h): the 9-state filter (P column-major, as Eigen stores kalman_P) and the per-frame report
 FA_STATE_DTYPE = np.dtype([("x", "f8", (9,)), ("P", "f8", (81,))])
@@ -296,6 +300,9 @@ _ABI = {
     "lsd_grid_locate_workspace_bytes": (_sz, [_i, _i, lsd_grid_locate_par]),
     "lsd_enqueue_grid_locate_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, _vp, _vp, _vp]),
     "lsd_grid_locate": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, _vp, _vp]),
+    "lsd_grid_locate_tight_workspace_bytes": (_sz, [_i, _i, lsd_grid_locate_par]),
+    "lsd_enqueue_grid_locate_tight_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, C.c_uint32, _vp, _vp, _vp]),
+    "lsd_grid_locate_tight": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, C.c_uint32, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -950,6 +957,31 @@ class Context:
                                          st.ctypes.data if stats else None))
         return (out, st) if stats else out
 
+    def enqueue_grid_locate_tight_device(self, d_scans, d_lens, n_scans, stride, map_param, range_max, d_pyramid, locate, tight, d_out,
+                                         d_stats=None, stream=None):
+        """lsd_enqueue_grid_locate_tight_device on device addresses: enqueue_grid_locate_device with the bound raised level by level
+        (DESIGN.md 8.1.14); tight: what grid_locate_tight() takes, 0 included; d_stats (or None) receives n_scans records of 128 bytes
+        (GRID_LOCATE_TIGHT_STATS_DTYPE); asynchronous."""
+        mp = _map_param(map_param)
+        return self._chk(self.L.lsd_enqueue_grid_locate_tight_device(self.h, d_scans, d_lens, int(n_scans), int(stride), mp, float(range_max),
+                                                                     d_pyramid, grid_locate(locate, cols=mp.oriMapCol, rows=mp.oriMapRow),
+                                                                     grid_locate_tight(tight), d_out, d_stats, stream))
+
+    def grid_locate_tight(self, scans, lens, map_param, range_max, corr, locate=None, tight=True, stats=False):
+        """lsd_grid_locate_tight from host arrays: grid_locate under the tight rule (tight: what grid_locate_tight() takes; the entry is
+        taken with 0 as well); with stats=True the statistics are GRID_LOCATE_TIGHT_STATS_DTYPE.  Blocking."""
+        sc, ln, _, ok = _host_scans(scans, lens, np.zeros((len(np.atleast_1d(lens)), 3)))
+        mp = _map_param(map_param)
+        co = np.ascontiguousarray(corr, np.uint8)
+        if not ok or co.shape != (mp.oriMapRow, mp.oriMapCol):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], corr uint8 [rows, cols]")
+        out = np.zeros(len(ln), GRID_LOCATE_DTYPE)
+        st = np.zeros(len(ln), GRID_LOCATE_TIGHT_STATS_DTYPE)
+        self._chk(self.L.lsd_grid_locate_tight(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), mp, float(range_max),
+                                               co.ctypes.data, grid_locate(locate, cols=mp.oriMapCol, rows=mp.oriMapRow), grid_locate_tight(tight),
+                                               out.ctypes.data, st.ctypes.data if stats else None))
+        return (out, st) if stats else out
+
     # -- the response around a match (k_gridresponse.hip; DESIGN.md 8.1.9) -----------------------------
     def enqueue_grid_response_device(self, d_scans, d_lens, n_scans, stride, d_poses, pose_pitch, d_records, map_param, range_max, d_corr,
                                      ang_step, response, d_out, d_volume=None, stream=None):
@@ -1284,6 +1316,22 @@ def grid_search(search=None, **kw):
 
 
 GRID_LOCATE_KEYS = ("x0", "y0", "nx", "ny", "ang0", "ang_step", "n_ang", "levels", "max_nodes", "score_floor", "min_beams", "min_num", "min_den")
+
+
+def grid_locate_tight(tight):
+    """The flag word of a `tight=` argument: None, 0 or False the existing search (0); True both flags; "probe" or "retry" one of them; or
+    a word of GRID_LOCATE_TIGHT_PROBE | GRID_LOCATE_TIGHT_RETRY."""
+    if tight is None or tight is False:
+        return 0
+    if tight is True:
+        return GRID_LOCATE_TIGHT_PROBE | GRID_LOCATE_TIGHT_RETRY
+    if isinstance(tight, str):
+        if tight not in ("probe", "retry"):
+            raise LsdError(LSD_ERR_INVALID, 'tight: "probe" or "retry"')
+        return GRID_LOCATE_TIGHT_PROBE if tight == "probe" else GRID_LOCATE_TIGHT_RETRY
+    if not isinstance(tight, (int, np.integer)) or not 0 <= int(tight) <= 3:
+        raise LsdError(LSD_ERR_INVALID, "tight: None, a bool, \"probe\", \"retry\" or a word of GRID_LOCATE_TIGHT_PROBE | GRID_LOCATE_TIGHT_RETRY")
+    return int(tight)
 
 
 def grid_locate(locate=None, cols=None, rows=None, **kw):
@@ -1874,48 +1922,59 @@ class GridMapper:
         self.ctx.enqueue_grid_pyramid_device(self.d_corr, self.cols, self.rows, H, pyr[H].data_ptr(), ts.cuda_stream)
         return pyr[H]
 
-    def _enqueue_locate(self, ctx, d_scans, d_lens, n, stride, locate, refresh, smear, stats, ts):
+    def _enqueue_locate(self, ctx, d_scans, d_lens, n, stride, locate, refresh, smear, stats, ts, tight=None):
         """In stream order on ts: likelihood_device(smear) (refresh), pyramid_device, the location of the scans at device addresses.  n
-        records (a new CUDA uint8 tensor [n, 64]); with stats (records, a new CUDA uint8 tensor [n, 48])."""
+        records (a new CUDA uint8 tensor [n, 64]); with stats (records, a new CUDA uint8 tensor [n, 48]).  tight (grid_locate_tight())
+        other than None / 0 / False: the tight entry, whose statistics are [n, 128]."""
         import torch
         par = grid_locate(locate, cols=self.cols, rows=self.rows)
+        word = grid_locate_tight(tight)
         if refresh:
             self.likelihood_device(smear, ts)
         pyr = self.pyramid_device(par.levels, ts)
         with torch.cuda.stream(ts):
             rec = torch.empty((n, GRID_LOCATE_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device)
-            st = torch.empty((n, GRID_LOCATE_STATS_DTYPE.itemsize), dtype=torch.uint8, device=self._planes.device) if stats else None
-        ctx.enqueue_grid_locate_device(d_scans, d_lens, n, stride, self.map_param, self.range_max, pyr.data_ptr(), par, rec.data_ptr(),
-                                       st.data_ptr() if stats else None, ts.cuda_stream)
+            width = (GRID_LOCATE_TIGHT_STATS_DTYPE if word else GRID_LOCATE_STATS_DTYPE).itemsize
+            st = torch.empty((n, width), dtype=torch.uint8, device=self._planes.device) if stats else None
+        if word:
+            ctx.enqueue_grid_locate_tight_device(d_scans, d_lens, n, stride, self.map_param, self.range_max, pyr.data_ptr(), par, word, rec.data_ptr(),
+                                                 st.data_ptr() if stats else None, ts.cuda_stream)
+        else:
+            ctx.enqueue_grid_locate_device(d_scans, d_lens, n, stride, self.map_param, self.range_max, pyr.data_ptr(), par, rec.data_ptr(),
+                                           st.data_ptr() if stats else None, ts.cuda_stream)
         return (rec, st) if stats else rec
 
-    def locate_device(self, d_scans, d_lens, locate=None, refresh=True, smear=None, stats=False, stream=None):
+    def locate_device(self, d_scans, d_lens, locate=None, refresh=True, smear=None, stats=False, stream=None, tight=None):
         """Locates scans that are on the device (d_scans, d_lens of integrate_device) on the mapper's grid WITHOUT a prior pose: in stream
         order likelihood_device(smear) (refresh=False: the plane as it is), pyramid_device and the search over the box and the headings of
         `locate` (grid_locate(); None: the whole grid, its placeholder defaults).  Returns the records: a CUDA uint8 tensor [n, 64]
         (GRID_LOCATE_DTYPE) whose heads are poses -- the located one where flags is GRID_LOCATE_ACCEPTED, else the "no pose" sentinel, so
         match_device(d_scans, d_lens, records, 64) and integrate_device(d_scans, d_lens, records, 64) take them and skip the rest.
         n_best > 1 says the map is ambiguous.  stats=True: (records, statistics: a CUDA uint8 tensor [n, 48], GRID_LOCATE_STATS_DTYPE).
-        On `stream`; nothing waits."""
+        tight (None, 0, False: this search as it is; True, "probe", "retry" or a flag word: grid_locate_tight()): the bound raised level by
+        level and a level that overflows retried once -- the same records wherever neither search overflows, fewer
+        overflows; the statistics are then [n, 128], GRID_LOCATE_TIGHT_STATS_DTYPE.  On `stream`; nothing waits."""
         n = self._checked_scans(d_scans, d_lens)
         got = self._enqueue_locate(self.ctx, d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], locate, refresh, smear, stats,
-                                   _cuda_stream(stream))
+                                   _cuda_stream(stream), tight)
         self._held_locate = (d_scans, d_lens)                                # the launches read them: alive until the next call
         return got
 
-    def locate(self, scans, lens, locate=None, refresh=True, smear=None, stats=False):
+    def locate(self, scans, lens, locate=None, refresh=True, smear=None, stats=False, tight=None):
         """locate_device for host arrays (scans float64 [n, stride, 2], lens int32 [n]); returns the records as a numpy array of
-        GRID_LOCATE_DTYPE (stats=True: with the statistics as GRID_LOCATE_STATS_DTYPE): a read-back, which waits for the device."""
+        GRID_LOCATE_DTYPE (stats=True: with the statistics as GRID_LOCATE_STATS_DTYPE, under `tight` GRID_LOCATE_TIGHT_STATS_DTYPE): a
+        read-back, which waits for the device."""
         import torch
         ln0 = np.atleast_1d(np.asarray(lens))
         sc, ln, _, ok = _host_scans(scans, lens, np.zeros((len(ln0), 3)))
         if not ok or ((ln < 0) | (ln > sc.shape[1])).any():
             raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n] within 0..stride")
         dev = self._planes.device
-        got = self.locate_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), locate, refresh, smear, stats)
+        got = self.locate_device(torch.from_numpy(sc).to(dev), torch.from_numpy(ln).to(dev), locate, refresh, smear, stats, tight=tight)
         if not stats:
             return got.cpu().numpy().reshape(-1).view(GRID_LOCATE_DTYPE).copy()
-        return got[0].cpu().numpy().reshape(-1).view(GRID_LOCATE_DTYPE).copy(), got[1].cpu().numpy().reshape(-1).view(GRID_LOCATE_STATS_DTYPE).copy()
+        st_dtype = GRID_LOCATE_TIGHT_STATS_DTYPE if grid_locate_tight(tight) else GRID_LOCATE_STATS_DTYPE
+        return got[0].cpu().numpy().reshape(-1).view(GRID_LOCATE_DTYPE).copy(), got[1].cpu().numpy().reshape(-1).view(st_dtype).copy()
 
     def counts(self):
         """(pass, hit) as numpy uint32 [rows, cols]: a read-back, which waits for the device."""
@@ -2346,7 +2405,7 @@ class _Ticks:
             raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
         return self._last_tick
 
-    def _relocate_last_tick(self, mapper, key, locate, seed, max_lost, refresh, smear, response, search, stats, write=True):
+    def _relocate_last_tick(self, mapper, key, locate, seed, max_lost, refresh, smear, response, search, stats, write=True, tight=None):
         """relocate_last_tick for the sequences `key` = (d_key, key) selects on the device, on the tick's stream and behind the tick: the
         gather (the carries, the tick's states at pitch 720, its ingested scans), the mapper's locate on the gathered batch, with `response`
         a match of zero window at the locate records (pitch 64: the response stage reads a match record's di / dj / da, which a locate
@@ -2361,6 +2420,7 @@ class _Ticks:
             se = grid_search(search)
             se = lsd_grid_search(0, 0, 0, se.ang_step, se.min_beams, se.min_num, se.min_den)
         locate = grid_locate(locate, cols=mapper.cols, rows=mapper.rows)         # (refused here: before the gather is enqueued)
+        tight = grid_locate_tight(tight)
         dev, B = self._carry.device, self.n_beams
         with torch.cuda.stream(ts):
             sc = torch.zeros((n, B, 2), dtype=torch.float64, device=dev)         # rows past the gathered ones keep these zeros
@@ -2369,7 +2429,7 @@ class _Ticks:
         cx, d_cy = self.ctx, self._carry.data_ptr()
         cx.enqueue_fa_lost_gather_device(d_cy, S, k, self._out.data_ptr(), FA_STATE_DTYPE.itemsize, self._scans.data_ptr(), self._lens.data_ptr(), B,
                                          key[0], key[1], n, sc.data_ptr(), ln.data_ptr(), pick.data_ptr(), n_lost.data_ptr(), ts.cuda_stream)
-        got = mapper._enqueue_locate(cx, sc.data_ptr(), ln.data_ptr(), n, B, locate, refresh, smear, stats, ts)
+        got = mapper._enqueue_locate(cx, sc.data_ptr(), ln.data_ptr(), n, B, locate, refresh, smear, stats, ts, tight)
         parts = list(got) if stats else [got]
         resp = rec0 = None
         if rp is not None:
@@ -2633,23 +2693,24 @@ class Localizer(_Ticks):
         response stage, and its reports are returned last in the tuple.  None, the default, enqueues nothing more."""
         return self._refine_and_integrate_last_tick(mapper, None, (None, 0), search, refresh, smear, block, response, integrate_at, correct)
 
-    def locate_last_tick(self, mapper, locate=None, refresh=True, smear=None, stats=False):
+    def locate_last_tick(self, mapper, locate=None, refresh=True, smear=None, stats=False, tight=None):
         """Global localisation of the last tick's scans (GridMapper.locate_device): on the last tick's stream and behind
         the tick, every frame slot of the tick is located on `mapper`'s grid from the tick's ingested scans alone -- the states the tick
         produced play no part, so a robot whose tick ended in a reset, or one that has no pose yet, is located as well.  Nothing is read
         back and nothing waits.  Returns the records, a CUDA uint8 tensor [n_robots * k, 64] (GRID_LOCATE_DTYPE; slot s * k + t is frame t
         of robot s; a slot past a robot's n_frames holds an empty scan: GRID_LOCATE_EMPTY).  This call only reports: no carry is written,
         and every slot is searched, the robots that know where they are included.  relocate_last_tick locates the lost robots alone and
-        writes the poses into their carries."""
+        writes the poses into their carries.  tight: GridMapper.locate_device's (the statistics are then [n, 128])."""
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         if not isinstance(mapper, GridMapper):
             raise LsdError(LSD_ERR_INVALID, "mapper must be a GridMapper")
         S, k, ts, _ = self._last_tick
         return mapper._enqueue_locate(self.ctx, self._scans.data_ptr(), self._lens.data_ptr(), S * k, self.n_beams, locate, refresh, smear, stats,
-                                      ts)
+                                      ts, tight)
 
-    def relocate_last_tick(self, mapper, locate=None, seed=None, max_lost=1, refresh=True, smear=None, response=None, search=None, stats=False):
+    def relocate_last_tick(self, mapper, locate=None, seed=None, max_lost=1, refresh=True, smear=None, response=None, search=None, stats=False,
+                           tight=None):
         """Relocalisation of the robots the last tick left without a pose, on the last tick's stream and behind the tick,
         in this order: the lost robots -- a carry without a pose whose tick had a scan -- are gathered in ascending index, the first
         max_lost of them with their scans packed into a batch of max_lost rows (lsd_enqueue_fa_lost_gather_device); that batch is located
@@ -2662,8 +2723,10 @@ class Localizer(_Ticks):
         CUDA tensors (pick int32 [max_lost]: the slot s * k + t gathered into each row, -1 for an unused row; n_lost int32 [2]: the robots
         lost -- it may exceed max_lost: call again, the seeded ones are no longer lost -- and the robots gathered; the locate records
         uint8 [max_lost, 64]; with stats their statistics [max_lost, 48]; with response the response records [max_lost, 192]; the seed
-        reports uint8 [max_lost, 48], FA_SEED_DTYPE)."""
-        return self._relocate_last_tick(mapper, (None, 0), locate, seed, max_lost, refresh, smear, response, search, stats)
+        reports uint8 [max_lost, 48], FA_SEED_DTYPE).  tight: GridMapper.locate_device's -- the locate of the chain under the tight rule
+        (DESIGN.md 8.1.14): a robot whose search overflows is not seeded, and the tight rule overflows less; the statistics are then
+        [max_lost, 128]."""
+        return self._relocate_last_tick(mapper, (None, 0), locate, seed, max_lost, refresh, smear, response, search, stats, tight=tight)
 
     def correct_last_tick(self, responses, correct=None):
         """The grid match response fused into the robots' carries (lsd_enqueue_fa_carry_correct_device): a measurement
@@ -2873,23 +2936,23 @@ class FleetLocalizer(_Ticks):
         return self._refine_and_integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i), (self._map_of.data_ptr(), i), search,
                                                     refresh, smear, block, response, integrate_at, correct)
 
-    def locate_last_tick(self, mapper, map_id, locate=None, max_lost=1, refresh=True, smear=None, stats=False):
+    def locate_last_tick(self, mapper, map_id, locate=None, max_lost=1, refresh=True, smear=None, stats=False, tight=None):
         """Global localisation of the LOST robots on map `map_id` from the last tick's scans, without writing a carry: relocate_last_tick's
         gather and locate alone.  The robots' map ids are read on the device (d_key = the ids, key = map_id), so the call stays right
         behind an assign() on the stream; there is no host-side selection as integrate_last_tick makes one, and hence no locate of every
         slot as Localizer.locate_last_tick runs it -- a robot with a pose has its states, and GridMapper.locate_device takes any scans a
         caller holds.  Returns CUDA tensors (pick int32 [max_lost], n_lost int32 [2], the locate records uint8 [max_lost, 64]; with stats
-        their statistics [max_lost, 48]); row j belongs to slot pick[j]."""
+        their statistics [max_lost, 48]); row j belongs to slot pick[j].  tight: GridMapper.locate_device's (statistics [max_lost, 128])."""
         return self._relocate_last_tick(mapper, (self._map_of.data_ptr(), self._map_id(map_id)), locate, None, max_lost, refresh, smear, None, None,
-                                        stats, write=False)
+                                        stats, write=False, tight=tight)
 
     def relocate_last_tick(self, mapper, map_id, locate=None, seed=None, max_lost=1, refresh=True, smear=None, response=None, search=None,
-                           stats=False):
+                           stats=False, tight=None):
         """Localizer.relocate_last_tick for the lost robots on map `map_id`, read on the device when the kernels run (d_key = the robots' map
         ids, key = map_id): right behind an assign() on the stream, and the robots on other maps keep every byte of their carries.  The
-        mapper's frame is that map's."""
+        mapper's frame is that map's.  tight: Localizer.relocate_last_tick's."""
         return self._relocate_last_tick(mapper, (self._map_of.data_ptr(), self._map_id(map_id)), locate, seed, max_lost, refresh, smear, response,
-                                        search, stats)
+                                        search, stats, tight=tight)
 
     def correct_last_tick(self, responses, map_id, correct=None):
         """Localizer.correct_last_tick for the robots on map `map_id`, read on the device when the kernel runs (d_key = the robots' map ids,

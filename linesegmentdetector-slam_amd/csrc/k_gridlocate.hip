@@ -20,33 +20,17 @@
 // k_grid_locate_pick: one wavefront per scan: the key maximum over the workgroups' slots (S, then 2^44 - 1 - lin), n_best, the outcome,
 //   the record and the statistics.
 //
+// gridlocate_dev.h holds what k_gridlocate_tight.hip shares with this file: the workspace's records, loc_cell, the wave reductions, the slot
+// merge; launch_grid_locate_head is the four launches both searches begin with.
+//
 // Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950, -O3): DESIGN.md 8.1.12.
 #include <algorithm>
 
 #include "lsd_internal.h"
 #include "gridmatch_dev.h"
+#include "gridlocate_dev.h"
 
 namespace lsdhip {
-
-constexpr int kLocWaves = kGmLanes / 64;
-constexpr int kLocCtl = 16;                                          // words per scan: |F_h| for h = 0..8, then ...
-constexpr int kLcScored = 9, kLcBound = 10, kLcBeams = 11;           // ... the children evaluated, L, the sum of nb(a)
-constexpr int kLocSlots = 1024;                                      // the most workgroups per scan the seed and expansion kernels get
-constexpr int kLocLinBits = 44;                                      // lin < 4096 * 65535^2 < 2^44 - 1; S < 2^20
-constexpr unsigned long long kLocLinMask = (1ull << kLocLinBits) - 1;
-static_assert(4096ull * 65535 * 65535 < kLocLinMask && kLocLinBits + 20 <= 64, "the key holds the score and the index");
-
-struct LocSlot { unsigned long long key; uint32_t cnt, pad; };       // per (scan, workgroup): the best key and the candidates with its S
-static_assert(sizeof(LocSlot) == 16, "grid_locate_ws sizes the workspace by 16 bytes a slot");
-
-struct LocBox { int cols, rows, x0, y0, nx, ny, n_ang, stride, H; uint32_t max_nodes; };
-struct LocPlanes { size_t off[LSD_GRID_LOCATE_MAX_LEVELS + 1]; };    // the levels' offsets in the pyramid buffer
-
-// plane_h at the cell (x, y) of the grid's frame, x = -(2^h - 1) .. cols - 1 and y likewise; 0 outside the plane
-__device__ __forceinline__ uint32_t loc_cell(const uint8_t* __restrict__ plane, int cols, int rows, int h, int x, int y) {
-    const int m = (1 << h) - 1, cx = x + m, cy = y + m, pc = cols + m;
-    return (cx >= 0 && cx < pc && cy >= 0 && cy < rows + m) ? plane[(size_t)cy * pc + cx] : 0u;
-}
 
 __global__ __launch_bounds__(256) void k_grid_pyramid_level(const uint8_t* __restrict__ prev, int cols, int rows, int h, uint8_t* __restrict__ out) {
     const int m = (1 << h) - 1, pc = cols + m, pr = rows + m;
@@ -61,42 +45,6 @@ __global__ __launch_bounds__(256) void k_grid_pyramid_level(const uint8_t* __res
                 max(loc_cell(prev, cols, rows, h - 1, x, y + half), loc_cell(prev, cols, rows, h - 1, x + half, y + half)));
     }
     out[(size_t)oy * pc + ox] = (uint8_t)v;
-}
-
-__device__ __forceinline__ uint32_t loc_wave_sum(uint32_t v) {
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
-// (key, cnt): the largest key and the number of candidates whose S is its S; cnt == 0: none yet
-__device__ __forceinline__ void loc_merge(unsigned long long& key, uint32_t& cnt, unsigned long long k2, uint32_t c2) {
-    if (c2 == 0) return;
-    if (cnt == 0) { key = k2; cnt = c2; return; }
-    const unsigned long long s1 = key >> kLocLinBits, s2 = k2 >> kLocLinBits;
-    if (s1 == s2) { cnt += c2; key = k2 > key ? k2 : key; }
-    else if (s2 > s1) { key = k2; cnt = c2; }
-}
-
-__device__ __forceinline__ void loc_wave_merge(unsigned long long& key, uint32_t& cnt) {      // every lane gets the result
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long k2 = shfl_xor_u64(key, d);
-        const uint32_t c2 = (uint32_t)__shfl_xor((int)cnt, d, 64);
-        loc_merge(key, cnt, k2, c2);
-    }
-}
-
-// the workgroup's (key, cnt) into its slot; every lane calls it
-__device__ __forceinline__ void loc_store_slot(unsigned long long key, uint32_t cnt, LocSlot* slot, unsigned long long* s_key, uint32_t* s_c) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    loc_wave_merge(key, cnt);
-    if (lane == 0) { s_key[wave] = key; s_c[wave] = cnt; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < kLocWaves; w++) loc_merge(key, cnt, s_key[w], s_c[w]);
-        LocSlot out;
-        out.key = cnt ? key : 0; out.cnt = cnt; out.pad = 0;
-        *slot = out;
-    }
 }
 
 __global__ __launch_bounds__(kGmLanes) void k_grid_locate_offsets(const double2* __restrict__ scans, const int* __restrict__ lens, int stride,
@@ -379,12 +327,6 @@ __global__ __launch_bounds__(64) void k_grid_locate_pick(LocBox g, int n_slots, 
         for (int i = 0; i < 12; i++) stats[(size_t)scan * 12 + i] = st[i];
 }
 
-static_assert(sizeof(lsd_grid_locate_rec) == 64 && offsetof(lsd_grid_locate_rec, score) == 24 && offsetof(lsd_grid_locate_rec, cx) == 32 &&
-              offsetof(lsd_grid_locate_rec, a) == 40 && offsetof(lsd_grid_locate_rec, flags) == 44 && offsetof(lsd_grid_locate_rec, n_best) == 48 &&
-              offsetof(lsd_grid_locate_rec, lower_bound) == 52, "k_grid_locate_pick writes the record as eight 64-bit words");
-static_assert(sizeof(lsd_grid_locate_stats) == 48 && offsetof(lsd_grid_locate_stats, frontier) == 4 && offsetof(lsd_grid_locate_stats, scored) == 40,
-              "k_grid_locate_pick writes the statistics as twelve words");
-
 size_t grid_pyramid_offset(int cols, int rows, int h) {
     size_t at = 0;
     for (int l = 0; l < h; l++) at += (size_t)(cols + (1 << l) - 1) * (rows + (1 << l) - 1);
@@ -417,34 +359,45 @@ void grid_locate_ws(int n_scans, int stride, const lsd_grid_locate_par& par, siz
     bytes[7] = ns * kLocSlots * sizeof(LocSlot);
 }
 
+// the launches both searches begin with: the offsets, the top level with the descent of every heading, the bound, the seed of F_H
+LocGeom launch_grid_locate_head(const lsd_polar* scans, const int* lens, int n_scans, int stride, int cols, int rows, double resol, double range_max,
+                                const uint8_t* pyramid, const lsd_grid_locate_par& par, void* const ws[kGridLocateRegions], hipStream_t s) {
+    short2* offs = static_cast<short2*>(ws[0]);
+    uint32_t *nbs = static_cast<uint32_t*>(ws[1]), *la = static_cast<uint32_t*>(ws[2]), *U = static_cast<uint32_t*>(ws[3]);
+    uint32_t* ctl = static_cast<uint32_t*>(ws[6]);
+    LocSlot* slots = static_cast<LocSlot*>(ws[7]);
+    LocGeom q;
+    q.g = LocBox{cols, rows, par.x0, par.y0, par.nx, par.ny, par.n_ang, stride, par.levels, par.max_nodes};
+    for (int h = 0; h <= LSD_GRID_LOCATE_MAX_LEVELS; h++) q.pl.off[h] = grid_pyramid_offset(cols, rows, h);
+    const dim3 per_heading(n_scans, par.n_ang);
+    hipLaunchKernelGGL(k_grid_locate_offsets, per_heading, dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride, resol,
+                       range_max, par.ang0, par.ang_step, par.n_ang, offs, nbs);
+    hipLaunchKernelGGL(k_grid_locate_top, per_heading, dim3(kGmLanes), 0, s, q.g, q.pl, pyramid, offs, nbs, U, la);
+    hipLaunchKernelGGL(k_grid_locate_bound, dim3(n_scans), dim3(kGmLanes), 0, s, par.n_ang, par.score_floor, nbs, la, ctl);
+    // the geometry of the seed and the expansions comes from the parameters, never from the data
+    const size_t top = grid_locate_top_nodes(par);
+    q.g_seed = (int)std::min<size_t>((top + kGmLanes - 1) / kGmLanes, kLocSlots);
+    q.g_exp = (int)std::min<size_t>(((size_t)par.max_nodes + kLocWaves - 1) / kLocWaves, kLocSlots);
+    hipLaunchKernelGGL(k_grid_locate_seed, dim3(n_scans, q.g_seed), dim3(kGmLanes), 0, s, q.g, U, ctl, static_cast<uint2*>(ws[4]), slots);
+    return q;
+}
+
 void launch_grid_locate(const lsd_polar* scans, const int* lens, int n_scans, int stride, int cols, int rows, double resol, double range_max,
                         const uint8_t* pyramid, const lsd_grid_locate_par& par, void* const ws[kGridLocateRegions], lsd_grid_locate_rec* out,
                         lsd_grid_locate_stats* stats, hipStream_t s) {
-    short2* offs = static_cast<short2*>(ws[0]);
-    uint32_t *nbs = static_cast<uint32_t*>(ws[1]), *la = static_cast<uint32_t*>(ws[2]), *U = static_cast<uint32_t*>(ws[3]);
+    const LocGeom q = launch_grid_locate_head(scans, lens, n_scans, stride, cols, rows, resol, range_max, pyramid, par, ws, s);
+    const short2* offs = static_cast<const short2*>(ws[0]);
+    const uint32_t* nbs = static_cast<const uint32_t*>(ws[1]);
     uint2* lists[2] = {static_cast<uint2*>(ws[4]), static_cast<uint2*>(ws[5])};
     uint32_t* ctl = static_cast<uint32_t*>(ws[6]);
     LocSlot* slots = static_cast<LocSlot*>(ws[7]);
     const int H = par.levels;
-    const LocBox g{cols, rows, par.x0, par.y0, par.nx, par.ny, par.n_ang, stride, H, par.max_nodes};
-    LocPlanes pl;
-    for (int h = 0; h <= LSD_GRID_LOCATE_MAX_LEVELS; h++) pl.off[h] = grid_pyramid_offset(cols, rows, h);
-    const dim3 per_heading(n_scans, par.n_ang);
-    hipLaunchKernelGGL(k_grid_locate_offsets, per_heading, dim3(kGmLanes), 0, s, reinterpret_cast<const double2*>(scans), lens, stride, resol,
-                       range_max, par.ang0, par.ang_step, par.n_ang, offs, nbs);
-    hipLaunchKernelGGL(k_grid_locate_top, per_heading, dim3(kGmLanes), 0, s, g, pl, pyramid, offs, nbs, U, la);
-    hipLaunchKernelGGL(k_grid_locate_bound, dim3(n_scans), dim3(kGmLanes), 0, s, par.n_ang, par.score_floor, nbs, la, ctl);
-    // the geometry of the seed and the expansions comes from the parameters, never from the data
-    const size_t top = grid_locate_top_nodes(par);
-    const int g_seed = (int)std::min<size_t>((top + kGmLanes - 1) / kGmLanes, kLocSlots);
-    const int g_exp = (int)std::min<size_t>(((size_t)par.max_nodes + kLocWaves - 1) / kLocWaves, kLocSlots);
-    hipLaunchKernelGGL(k_grid_locate_seed, dim3(n_scans, g_seed), dim3(kGmLanes), 0, s, g, U, ctl, lists[0], slots);
     int cur = 0;
     for (int h = H; h >= 1; h--, cur ^= 1)
-        hipLaunchKernelGGL(k_grid_locate_expand, dim3(n_scans, g_exp), dim3(kGmLanes), 0, s, g, h, pyramid + pl.off[h - 1], offs, nbs, ctl,
+        hipLaunchKernelGGL(k_grid_locate_expand, dim3(n_scans, q.g_exp), dim3(kGmLanes), 0, s, q.g, h, pyramid + q.pl.off[h - 1], offs, nbs, ctl,
                            lists[cur], lists[cur ^ 1], slots);
-    hipLaunchKernelGGL(k_grid_locate_pick, dim3(n_scans), dim3(64), 0, s, g, H ? g_exp : g_seed, par.ang0, par.ang_step, par.min_beams, par.min_num,
-                       par.min_den, nbs, ctl, slots, reinterpret_cast<unsigned long long*>(out), reinterpret_cast<uint32_t*>(stats));
+    hipLaunchKernelGGL(k_grid_locate_pick, dim3(n_scans), dim3(64), 0, s, q.g, H ? q.g_exp : q.g_seed, par.ang0, par.ang_step, par.min_beams,
+                       par.min_num, par.min_den, nbs, ctl, slots, reinterpret_cast<unsigned long long*>(out), reinterpret_cast<uint32_t*>(stats));
 }
 
 }  // namespace lsdhip

@@ -408,30 +408,96 @@ int lsd_enqueue_grid_locate_device(lsd_ctx* c, const lsd_polar* d_scans, const i
     });
 }
 
-int lsd_grid_locate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp, double range_max,
-                    const uint8_t* corr, lsd_grid_locate_par par, lsd_grid_locate_rec* out, lsd_grid_locate_stats* stats) {
+// the host convenience of both locate entries: the uploads, the pyramid, `enqueue` on the staged arrays, the read-back of the records and
+// of stats_bytes per scan
+extern "C++" {
+template <class Enqueue>
+static int grid_locate_host(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp, double range_max,
+                            const uint8_t* corr, lsd_grid_locate_par par, lsd_grid_locate_rec* out, void* stats, size_t stats_bytes, Enqueue enqueue) {
     if (!c || !scans || !lens || !corr || !out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_locate_bad(par)) return LSD_ERR_INVALID;
     for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
-    lsd_polar* d_sc; int* d_len; uint8_t *d_co, *d_py; lsd_grid_locate_rec* d_out; lsd_grid_locate_stats* d_st;
+    lsd_polar* d_sc; int* d_len; uint8_t *d_co, *d_py; lsd_grid_locate_rec* d_out; uint64_t* d_st;
     HIPCHK(c, hipSetDevice(c->device));
     auto regions = [&](Carver& k) {
         k(d_sc, ns * stride); k(d_len, ns); k(d_co, cells); k(d_py, lsd_grid_pyramid_bytes(mp.oriMapCol, mp.oriMapRow, par.levels)); k(d_out, ns);
-        k(d_st, ns);
+        k(d_st, ns * stats_bytes / sizeof(uint64_t));
     };
     HIPCHK(c, carve(c->stage, regions));
     HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
     int st = lsd_enqueue_grid_pyramid_device(c, d_co, mp.oriMapCol, mp.oriMapRow, par.levels, d_py, c->stream);
-    if (st == LSD_OK)
-        st = lsd_enqueue_grid_locate_device(c, d_sc, d_len, n_scans, stride, mp, range_max, d_py, par, d_out, stats ? d_st : nullptr, c->stream);
+    if (st == LSD_OK) st = enqueue(d_sc, d_len, d_py, d_out, stats ? d_st : nullptr);
     if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
     HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_locate_rec), hipMemcpyDeviceToHost, c->stream));
-    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_locate_stats), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * stats_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LSD_OK;
+}
+}  // extern "C++"
+
+int lsd_grid_locate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp, double range_max,
+                    const uint8_t* corr, lsd_grid_locate_par par, lsd_grid_locate_rec* out, lsd_grid_locate_stats* stats) {
+    return grid_locate_host(c, scans, lens, n_scans, stride, mp, range_max, corr, par, out, stats, sizeof(lsd_grid_locate_stats),
+                            [&](lsd_polar* d_sc, int* d_len, uint8_t* d_py, lsd_grid_locate_rec* d_out, uint64_t* d_st) {
+                                return lsd_enqueue_grid_locate_device(c, d_sc, d_len, n_scans, stride, mp, range_max, d_py, par, d_out,
+                                                                      reinterpret_cast<lsd_grid_locate_stats*>(d_st), c->stream);
+                            });
+}
+
+// --- the tight search (k_gridlocate_tight.hip) ---
+static_assert(sizeof(lsd_grid_locate_tight_stats) == 128 && sizeof(lsd_grid_locate_stats) % 8 == 0, "the statistics records, staged as 64-bit words");
+
+static bool grid_locate_tight_bad(uint32_t tight) { return (tight & ~(LSD_GRID_LOCATE_TIGHT_PROBE | LSD_GRID_LOCATE_TIGHT_RETRY)) != 0; }
+
+size_t lsd_grid_locate_tight_workspace_bytes(int n_scans, int stride, lsd_grid_locate_par par) {
+    if (n_scans < 0 || stride <= 0 || stride > LSD_SCAN_MAX_LEN || grid_locate_bad(par)) return 0;
+    size_t bytes[kGridLocateTightRegions];
+    grid_locate_tight_ws(n_scans, stride, par, bytes);
+    Carver measure(nullptr);
+    uint8_t* r;
+    for (int i = 0; i < kGridLocateTightRegions; i++) measure(r, bytes[i]);
+    return measure.bytes_from(nullptr);
+}
+
+int lsd_enqueue_grid_locate_tight_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, lsd_map_param mp,
+                                         double range_max, const uint8_t* d_pyramid, lsd_grid_locate_par par, uint32_t tight,
+                                         lsd_grid_locate_rec* d_out, lsd_grid_locate_tight_stats* d_stats, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_pyramid || !d_out || grid_frame_bad(c, n_scans, stride, mp, range_max) || grid_locate_bad(par))
+        return LSD_ERR_INVALID;
+    if (grid_locate_tight_bad(tight)) {
+        c->err = "grid locate: tight is LSD_GRID_LOCATE_TIGHT_PROBE | LSD_GRID_LOCATE_TIGHT_RETRY at the most";
+        return LSD_ERR_INVALID;
+    }
+    if ((addr(d_scans) & 15) || (addr(d_lens) & 3) || (addr(d_out) & 7) || (addr(d_stats) & 3)) {
+        c->err = "grid locate: d_scans 16-byte, d_out 8-byte, d_lens and d_stats 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_scans == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        size_t bytes[kGridLocateTightRegions];
+        grid_locate_tight_ws(n_scans, stride, par, bytes);
+        uint8_t* r[kGridLocateTightRegions];
+        auto regions = [&](Carver& k) { for (int i = 0; i < kGridLocateTightRegions; i++) k(r[i], bytes[i]); };
+        HIPCHK(c, carve(c->gl_ws, regions));                         // (grown: one synchronisation; else nothing but pointer arithmetic)
+        void* ws[kGridLocateTightRegions];
+        for (int i = 0; i < kGridLocateTightRegions; i++) ws[i] = r[i];
+        launch_grid_locate_tight(d_scans, d_lens, n_scans, stride, mp.oriMapCol, mp.oriMapRow, mp.mapResol, range_max, d_pyramid, par, tight, ws, d_out,
+                                 d_stats, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_grid_locate_tight(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp, double range_max,
+                          const uint8_t* corr, lsd_grid_locate_par par, uint32_t tight, lsd_grid_locate_rec* out, lsd_grid_locate_tight_stats* stats) {
+    if (grid_locate_tight_bad(tight)) return LSD_ERR_INVALID;
+    return grid_locate_host(c, scans, lens, n_scans, stride, mp, range_max, corr, par, out, stats, sizeof(lsd_grid_locate_tight_stats),
+                            [&](lsd_polar* d_sc, int* d_len, uint8_t* d_py, lsd_grid_locate_rec* d_out, uint64_t* d_st) {
+                                return lsd_enqueue_grid_locate_tight_device(c, d_sc, d_len, n_scans, stride, mp, range_max, d_py, par, tight, d_out,
+                                                                            reinterpret_cast<lsd_grid_locate_tight_stats*>(d_st), c->stream);
+                            });
 }
 
 }  // extern "C"

@@ -208,6 +208,12 @@ void grid_locate_ws(int n_scans, int stride, const lsd_grid_locate_par& par, siz
 void launch_grid_locate(const lsd_polar* scans, const int* lens, int n_scans, int stride, int cols, int rows, double resol, double range_max,
                         const uint8_t* pyramid, const lsd_grid_locate_par& par, void* const ws[kGridLocateRegions], lsd_grid_locate_rec* out,
                         lsd_grid_locate_stats* stats, hipStream_t s);
+// the tight search (k_gridlocate_tight.hip): the same regions and two more -- kLocTight words per scan, a 64-bit key per scan and heading
+constexpr int kGridLocateTightRegions = kGridLocateRegions + 2;
+void grid_locate_tight_ws(int n_scans, int stride, const lsd_grid_locate_par& par, size_t bytes[kGridLocateTightRegions]);
+void launch_grid_locate_tight(const lsd_polar* scans, const int* lens, int n_scans, int stride, int cols, int rows, double resol, double range_max,
+                              const uint8_t* pyramid, const lsd_grid_locate_par& par, uint32_t tight, void* const ws[kGridLocateTightRegions],
+                              lsd_grid_locate_rec* out, lsd_grid_locate_tight_stats* stats, hipStream_t s);
 void launch_pack_lines(const lsd_line* lines, const int32_t* counts, int n_local, int max_lines, int per, int cap_rows, int32_t* cpad,
                        int32_t* offs, lsd_line* slab, hipStream_t s);
 // Device FeatureAssociation (k_fa.hip): one frame index of n_seq sequences.  Frame t of sequence s lives in slot s * frames_pitch + t

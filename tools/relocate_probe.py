@@ -10,6 +10,7 @@ minimum and the maximum of REPS calls; the carries are put back between the call
              workspace of a locate of max_lost scans
   locate_all Localizer.locate_last_tick on the same inputs: pyramid and locate of every slot -- the only route before, which leaves the
              carries to the host --, and the workspace of a locate of every slot
+  relocate_tight (--tight) relocate with tight=True on the same inputs in the same process
 720 headings of 0.5 degrees over the whole grid at levels = 8, no refresh of the lookup plane in either (it is the same launch in both).
 Usage: tools/relocate_probe.py --lost 1 [--robots 64] [--max-lost 4] [--beams 360] [--reps 20] [--size 2048]"""
 import argparse, importlib, json, os, sys
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--beams", type=int, default=360)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--size", type=int, default=2048)
+    ap.add_argument("--tight", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -55,11 +57,11 @@ def main():
     ws = lambda n: ctx.L.lsd_grid_locate_workspace_bytes(n, beams, par)
     got = {}
 
-    def relocate():
+    def relocate(tight=None):
         loc._carry.copy_(saved)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        got["r"] = loc.relocate_last_tick(mapper, par, dict(max_best=1), max_lost=args.max_lost, refresh=False)
+        got["r"] = loc.relocate_last_tick(mapper, par, dict(max_best=1), max_lost=args.max_lost, refresh=False, tight=tight)
         b.record()
         return a, b
 
@@ -77,15 +79,16 @@ def main():
             a, b = fn(); torch.cuda.synchronize()
             ms.append(a.elapsed_time(b))
         return float(np.median(ms)), float(min(ms)), float(max(ms))
-    med, lo, hi = timed(relocate)
-    pick, n_lost, rec, rep = (t.cpu().numpy() for t in got["r"])
-    rep, rec = rep.reshape(-1).view(lsd.FA_SEED_DTYPE), rec.reshape(-1).view(lsd.GRID_LOCATE_DTYPE)
-    seeded = rep["flags"] == lsd.FA_SEED_SEEDED
-    near = [bool(abs(r["pose"][0] - poses[r["seq"], 0]) <= 2 and abs(r["pose"][1] - poses[r["seq"], 1]) <= 2) for r in rep[seeded]]
-    print(json.dumps(dict(what="relocate", grid=size, robots=S, lost=args.lost, max_lost=args.max_lost, beams=beams, headings=N_ANG, levels=LEVELS,
-                          ms_median=med, ms_min=lo, ms_max=hi, workspace_mb=ws(args.max_lost) / 2 ** 20, n_lost=n_lost.tolist(), pick=pick.tolist(),
-                          seed_flags=[int(f) for f in rep["flags"]], locate_flags=[int(f) for f in rec["flags"]], seeded=int(seeded.sum()),
-                          within_two_cells_of_the_generated_pose=int(sum(near)))), flush=True)
+    for what, fn in [("relocate", relocate)] + ([("relocate_tight", lambda: relocate(True))] if args.tight else []):
+        med, lo, hi = timed(fn)
+        pick, n_lost, rec, rep = (t.cpu().numpy() for t in got["r"])
+        rep, rec = rep.reshape(-1).view(lsd.FA_SEED_DTYPE), rec.reshape(-1).view(lsd.GRID_LOCATE_DTYPE)
+        seeded = rep["flags"] == lsd.FA_SEED_SEEDED
+        near = [bool(abs(r["pose"][0] - poses[r["seq"], 0]) <= 2 and abs(r["pose"][1] - poses[r["seq"], 1]) <= 2) for r in rep[seeded]]
+        print(json.dumps(dict(what=what, grid=size, robots=S, lost=args.lost, max_lost=args.max_lost, beams=beams, headings=N_ANG, levels=LEVELS,
+                              ms_median=med, ms_min=lo, ms_max=hi, workspace_mb=ws(args.max_lost) / 2 ** 20, n_lost=n_lost.tolist(), pick=pick.tolist(),
+                              seed_flags=[int(f) for f in rep["flags"]], locate_flags=[int(f) for f in rec["flags"]], seeded=int(seeded.sum()),
+                              within_two_cells_of_the_generated_pose=int(sum(near)))), flush=True)
     med, lo, hi = timed(locate_all)
     rec = got["l"].cpu().numpy().reshape(-1).view(lsd.GRID_LOCATE_DTYPE)
     print(json.dumps(dict(what="locate_all", grid=size, robots=S, lost=args.lost, slots=S, beams=beams, headings=N_ANG, levels=LEVELS, ms_median=med,
