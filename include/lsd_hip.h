@@ -988,6 +988,162 @@ int lsd_grid_locate_tight(lsd_ctx *ctx, const lsd_polar *scans, const int *lens,
                           double range_max, const uint8_t *corr, lsd_grid_locate_par par, uint32_t tight, lsd_grid_locate_rec *out,
                           lsd_grid_locate_tight_stats *stats);
 
+/* --- pose graph: keyframes, loop closures and their relaxation, so that a grid can be drawn again from moved poses ---------------- */
+/* Every grid entry above enters a scan at one pose and that pose is final.  This section keeps what was entered where (nodes and their
+ * scans), the constraints between the entries (edges), redistributes the error (a relaxation) and leaves the nodes as a d_poses argument
+ * of pitch 64 for lsd_enqueue_grid_integrate_device, which draws the grid again (csrc/k_pgbuild.hip, csrc/k_posegraph.hip,
+ * csrc/posegraph_dev.h; restated in tests/pose_graph_cases.py).  All records are caller-owned device memory, 8-byte
+ * aligned; a pose is map pixels and degrees, the integration's.  fp64 without FMA; every sum runs ascending from 0.0 unless its
+ * parentheses say otherwise; sin / cos are the integration's: (s, c)(a) = sincos(a / 180.0 * pi).
+ *   wrap(v) = v - 360.0 * floor((v + 180.0) / 360.0)
+ *   rel(p, q), q in the frame of p:  dx = q.x - p.x, dy = q.y - p.y, (s, c)(p.ang);  (c * dx + s * dy, c * dy - s * dx, wrap(q.ang - p.ang))
+ *   comp(p, z):  (s, c)(p.ang);  (p.x + (c * z.x - s * z.y), p.y + (s * z.x + c * z.y), wrap(p.ang + z.ang))
+ *   inv3(S): the cofactor form of lsd_enqueue_fa_carry_correct_device's step 5, failing where !(det > 0) or 1 / det is not finite
+ * A graph: one lsd_pg_head, nodes_cap nodes, edges_cap edges.  n_nodes and n_edges are read and written ON THE DEVICE; every entry uses
+ * min(max(n, 0), cap) of them.  The keyframe store: nodes_cap rows of store_stride readings and nodes_cap lengths, row k node k's scan;
+ * lengths start at 0, so the rows past n_nodes are empty scans to the integration. */
+typedef struct lsd_pg_head { int32_t n_nodes, n_edges; } lsd_pg_head;                                   /* 8 bytes */
+typedef struct lsd_pg_node {               /* 64 bytes; its head is a pose, so an array of these IS a d_poses argument (pitch 64) */
+    double x, y, ang;
+    double raw[3];                         /* the pose the node was appended from */
+    uint32_t flags; int32_t track;
+    uint64_t reserved;
+} lsd_pg_node;
+#define LSD_PG_NODE_FIXED 1u
+typedef struct lsd_pg_edge {               /* 96 bytes */
+    int32_t i, j; uint32_t flags, reserved;
+    double z[3];                           /* the pose of j in the frame of i: pixels, pixels, degrees */
+    double info[6];                        /* the information matrix: xx, xy, yy, xa, ya, aa */
+    double chi2;                           /* written by the relaxation */
+} lsd_pg_edge;
+#define LSD_PG_EDGE_DISABLED 1u
+#define LSD_PG_EDGE_CLOSURE 2u
+typedef struct lsd_pg_track { int32_t last, reserved; double raw[3]; } lsd_pg_track;                    /* 32 bytes; last = -1: empty */
+/* lsd_enqueue_pg_append_device: keyframes and odometry edges.  n_cand candidate frames, their scans, lengths, stride and poses at a pitch
+ * exactly as lsd_enqueue_grid_integrate_device reads them, decided IN ORDER against one track record d_track (track: the id its nodes
+ * get).  Candidate t with pose q is DROPPED when the integration would skip its scan whole (q not finite, fabs(q.x + 1) < 1e-4, |q.x| or
+ * |q.y| > 1048576) or d_lens[t] <= 0.  Else, with the track empty (last outside 0..n_nodes-1): it becomes node n_nodes at pose q, raw = q,
+ * flags = LSD_PG_NODE_FIXED iff it is node 0, and no edge.  Else z = rel(track.raw, q); it is a keyframe iff z.x * z.x + z.y * z.y >=
+ * min_dist * min_dist or fabs(z.ang) >= min_ang; a keyframe becomes node n_nodes at comp(pose[last], z) -- the last node's CURRENT pose,
+ * moved or not --, raw = q, flags = 0, and the edge (last, new, z, info, flags 0, chi2 +0.0) is appended.  A new node's reserved word is
+ * 0; track.last = new, track.raw = q; store row `new` receives the first min(stride, store_stride) readings of the scan row byte for byte
+ * and the length min(d_lens[t], stride, store_stride).  A candidate that is no keyframe changes nothing.  A keyframe that finds n_nodes ==
+ * nodes_cap sets LSD_PG_APPEND_NODES_FULL, one that needs an edge and finds n_edges == edges_cap sets LSD_PG_APPEND_EDGES_FULL; either
+ * appends nothing, neither node nor edge, and leaves the track as it is.  Report: nodes and edges appended, candidates dropped, flags.
+ * One launch of one workgroup (a lane decides, all lanes copy the row), no workspace, no allocation, no host wait.  LSD_ERR_INVALID
+ * before anything is enqueued, outputs untouched: a null pointer (d_rep may be NULL); n_cand < 0; stride or store_stride outside 1..the
+ * context's scan capacity; pose_pitch < 24 or not a multiple of 8; nodes_cap outside 1..16384, edges_cap outside 1..65536; min_dist,
+ * min_ang or one of info[6] not finite, min_dist or min_ang negative; scans or store not 16-byte, a record array not 8-byte, lengths not
+ * 4-byte aligned.  n_cand == 0 launches nothing. */
+typedef struct lsd_pg_append_par { double min_dist, min_ang, info[6]; } lsd_pg_append_par;              /* 64 bytes */
+typedef struct lsd_pg_append_rep { int32_t nodes, edges, dropped; uint32_t flags; } lsd_pg_append_rep;  /* 16 bytes */
+#define LSD_PG_APPEND_NODES_FULL 1u
+#define LSD_PG_APPEND_EDGES_FULL 2u
+int lsd_enqueue_pg_append_device(lsd_ctx *ctx, const lsd_polar *d_scans, const int *d_lens, int n_cand, int stride, const void *d_poses,
+                                 size_t pose_pitch, lsd_pg_head *d_head, lsd_pg_node *d_nodes, int nodes_cap, lsd_pg_edge *d_edges,
+                                 int edges_cap, lsd_pg_track *d_track, int32_t track, lsd_polar *d_store, int *d_store_lens,
+                                 int store_stride, lsd_pg_append_par par, lsd_pg_append_rep *d_rep /* may be NULL */, void *stream);
+/* lsd_enqueue_pg_near_device: the loop candidate.  The query j = d_track->last, read on the device.  With j in 0..n_nodes-1 the
+ * candidates are the nodes i <= j - gap with d2_i = dx * dx + dy * dy <= radius * radius, dx = x_i - x_j, dy = y_i - y_j; the anchor is the
+ * candidate of the smallest d2, among equals the smallest i; with no candidate, or j outside the nodes, the anchor is -1.  It writes
+ *   (a) d_rec: anchor, query = j, the number of candidates, d2 of the anchor (+0.0 without one)
+ *   (b) d_sel[nodes_cap], packed poses (24 bytes): node k's pose iff anchor >= 0, |k - anchor| <= window and k <= j - gap; otherwise the
+ *       "no pose" sentinel (-1.0, +0.0, +0.0).  Integrating the WHOLE store at d_sel draws the anchor's neighbourhood alone, without the
+ *       host knowing the anchor
+ *   (c) the query gathered into a batch of one row, as lsd_enqueue_fa_lost_gather_device gathers: with j in the nodes d_q_scan receives
+ *       store row j (store_stride readings), d_q_len its length and d_q_pose node j's pose -- the sentinel without an anchor; with j
+ *       outside the nodes d_q_len = 0, d_q_pose = the sentinel and the row keeps its bytes
+ * One launch of one workgroup, no workspace, no atomics.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer;
+ * nodes_cap outside 1..16384; store_stride outside 1..the context's scan capacity; gap < 1 or window < 0; radius not finite or negative;
+ * the alignments of the append. */
+typedef struct lsd_pg_near_rec { int32_t anchor, query, n_cand, reserved; double d2; } lsd_pg_near_rec; /* 24 bytes */
+int lsd_enqueue_pg_near_device(lsd_ctx *ctx, const lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap,
+                               const lsd_pg_track *d_track, const lsd_polar *d_store, const int *d_store_lens, int store_stride, int gap,
+                               double radius, int window, lsd_pg_near_rec *d_rec, lsd_position *d_sel, lsd_polar *d_q_scan, int *d_q_len,
+                               lsd_position *d_q_pose, void *stream);
+/* lsd_enqueue_pg_closure_device: the edge from the response record r of the query matched against the anchor's neighbourhood.  The first
+ * test that fires decides; each outcome is exactly one flag; report: edge = the new edge's index or -1, det as far as computed, else +0.0:
+ *   1. anchor or query outside 0..n_nodes-1, or anchor == query: NO_ANCHOR
+ *   2. r.flags: VALID clear, or NONE, EMPTY or MISMATCH set: NO_RESPONSE (the correction's step 4)
+ *   3. r.x, r.y, r.ang or one of r.cov[0..5] not finite: NOT_FINITE
+ *   4. R exactly as the correction's step 5 builds it from cov_scale, floor_xy, floor_ang; I = inv3(R); on failure SINGULAR
+ *   5. n_edges == edges_cap: FULL
+ *   6. APPENDED: the edge (anchor, query), z = rel(pose[anchor], (r.x, r.y, r.ang)), flags = LSD_PG_EDGE_CLOSURE, chi2 = +0.0, and the
+ *      information turned into the anchor's frame, (s, c)(pose[anchor].ang):  T(r,0) = I(r,0) * c + I(r,1) * s,  T(r,1) = I(r,1) * c -
+ *      I(r,0) * s,  T(r,2) = I(r,2);  J(0,q) = c * T(0,q) + s * T(1,q),  J(1,q) = c * T(1,q) - s * T(0,q),  J(2,q) = T(2,q);
+ *      info = J(0,0), J(0,1), J(1,1), J(0,2), J(1,2), J(2,2);  n_edges += 1
+ * One launch, one lane.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer (d_rep may be NULL); the caps as
+ * above; a parameter not finite or negative; a pointer not 8-byte aligned. */
+typedef struct lsd_pg_closure_par { double cov_scale, floor_xy, floor_ang; } lsd_pg_closure_par;        /* 24 bytes */
+typedef struct lsd_pg_closure_rep { int32_t edge; uint32_t flags; double det; } lsd_pg_closure_rep;     /* 16 bytes */
+enum { LSD_PG_CLOSURE_APPENDED = 1, LSD_PG_CLOSURE_NO_ANCHOR = 2, LSD_PG_CLOSURE_NO_RESPONSE = 4, LSD_PG_CLOSURE_NOT_FINITE = 8,
+       LSD_PG_CLOSURE_SINGULAR = 16, LSD_PG_CLOSURE_FULL = 32 };
+int lsd_enqueue_pg_closure_device(lsd_ctx *ctx, lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap, lsd_pg_edge *d_edges,
+                                  int edges_cap, const lsd_pg_near_rec *d_near, const lsd_grid_response_rec *d_resp,
+                                  lsd_pg_closure_par par, lsd_pg_closure_rep *d_rep /* may be NULL */, void *stream);
+/* lsd_enqueue_pg_relax_device: Levenberg-Marquardt over SE(2), the linear step by conjugate gradients preconditioned with the inverse
+ * 3 x 3 diagonal blocks.  n_graphs graphs in one launch, ONE WORKGROUP PER GRAPH: graph g is d_heads[g], d_nodes + g * nodes_cap, d_edges
+ * + g * edges_cap, d_rep[g] and the workspace bytes from g * lsd_pg_workspace_bytes(nodes_cap, edges_cap) on.  N and E are its clamped
+ * counts.
+ * Edge e = (i, j, z, info) is SKIPPED (counted; its chi2 is +0.0) when it is DISABLED, i == j, i or j is outside 0..N-1, or one of z[3],
+ * info[6] or the poses of i and j, as they are when the call begins, is not finite.  W is the symmetric matrix of info.  At poses p:
+ *   (s, c)(a_i);  dx = x_j - x_i, dy = y_j - y_i;  e = ((c * dx + s * dy) - z[0], (c * dy - s * dx) - z[1], wrap((a_j - a_i) - z[2]))
+ *   k = pi / 180.0;  A = [(-c, -s, k * (c * dy - s * dx)), (s, -c, k * ((-c) * dx - s * dy)), (0.0, 0.0, -1.0)]
+ *   B = [(c, s, 0.0), (-s, c, 0.0), (0.0, 0.0, 1.0)]
+ *   WA(r,q) = sum_t W(r,t) * A(t,q), WB likewise, We(r) = sum_t W(r,t) * e[t]     (every product is made, the zeros' too)
+ *   Haa(r,q) = sum_t A(t,r) * WA(t,q), Hab(r,q) = sum_t A(t,r) * WB(t,q), Hbb(r,q) = sum_t B(t,r) * WB(t,q),
+ *   ba(r) = sum_t A(t,r) * We(t), bb(r) = sum_t B(t,r) * We(t), chi2_e = sum_t e[t] * We(t)
+ * A node's list holds its edges that are not skipped, in ASCENDING EDGE INDEX.  A node is FREE unless it is FIXED or singular (below).
+ * REDUCTIONS have one shape, which depends on the element count n alone: s[t] = v[t] + v[t + 1024] + .. (left to right) for t < 1024 and
+ * t < n, +0.0 for t >= n; then s[t] = s[t] + s[t + h] for t < h, h = 512, 256, .. 1; the result is s[0].  dot(u, v) over nodes reduces
+ * d_n = sum_q u_n[q] * v_n[q]; chi2 reduces chi2_e over all E edges; the largest |delta| is a maximum and has no order.
+ *   chi2 = the reduction at the nodes' poses;  chi2_before = chi2;  lambda = lambda0.  chi2 not finite: NOT_FINITE, nothing more is done.
+ *   An outer iteration, while done < iters:
+ *   1. the blocks of every edge at the current poses
+ *   2. H_n = the sum over the list of n of Haa (n is the edge's i) or Hbb (its j), b_n of ba or bb
+ *   3. D_n = H_n with D(r,r) = H(r,r) + lambda * H(r,r);  M_n = inv3(D_n).  A node that is not FIXED and fails is SINGULAR from here to the
+ *      end of the call (a node without edges is one)
+ *   4. PCG on D delta = -b over the free nodes; delta, r, z, p are +0.0 at every other node.  delta = 0;  r_n = -b_n;  z_n = M_n r_n;  p = z;
+ *      rz = rz0 = dot(r, z);  thr = (cg_tol * cg_tol) * rz0.  While steps < cg_iters and !(rz <= thr):  q_n = D_n p_n, then along the list
+ *      q_n = q_n + Hab p_j (n is the edge's i) or q_n + Hab^T p_i (its j);  pq = dot(p, q);  !(pq > 0): BREAKDOWN, the loop ends;  alpha = rz /
+ *      pq;  delta = delta + alpha * p;  r = r - alpha * q;  z_n = M_n r_n;  rz' = dot(r, z);  beta = rz' / rz;  p = z + beta * p;  rz = rz';
+ *      steps += 1
+ *   5. trial poses: (x + delta[0], y + delta[1], wrap(ang + delta[2])) at a free node, the node's own bytes elsewhere;  chi2' = the
+ *      reduction at the trial poses;  done += 1.  chi2' <= chi2: ACCEPTED -- the trial poses become the poses, chi2 = chi2', lambda =
+ *      max(lambda / down, lambda_min), and with max |delta[q]| over all nodes < eps: CONVERGED, the loop ends.  Otherwise REJECTED: lambda =
+ *      lambda * up
+ * Outputs: the nodes' x, y, ang in place, every other byte of a node kept; edge.chi2 = chi2_e at the final poses; the report: chi2_before,
+ * chi2_after = chi2, the last lambda, outer iterations done, CG steps summed, steps accepted and rejected, edges skipped, nodes singular,
+ * flags.  iters == 0 computes chi2 and edge.chi2 only.
+ * Asynchronous on `stream`, one launch of n_graphs workgroups; every loop is bounded by a parameter and no workgroup waits for another.
+ * The lists are built on the device once per call (count, scan, fill, order).  The workspace is the caller's; no allocation, no atomics
+ * on fp64, no host wait.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; n_graphs < 0; nodes_cap outside
+ * 1..16384, edges_cap outside 1..65536; a parameter not finite or negative; up <= 1, down < 1; iters or cg_iters outside 0..65535; a pointer
+ * not 8-byte aligned.  n_graphs == 0 launches nothing.  lsd_pg_workspace_bytes: 0 for caps outside the limits. */
+typedef struct lsd_pg_relax_par {          /* 56 bytes */
+    double lambda0, lambda_min, up, down, cg_tol, eps; int32_t iters, cg_iters;
+} lsd_pg_relax_par;
+typedef struct lsd_pg_relax_rep {          /* 56 bytes */
+    double chi2_before, chi2_after, lambda;
+    int32_t iters, cg_iters, accepted, rejected, skipped_edges, singular_nodes; uint32_t flags, reserved;
+} lsd_pg_relax_rep;
+#define LSD_PG_RELAX_CONVERGED 1u
+#define LSD_PG_RELAX_BREAKDOWN 2u
+#define LSD_PG_RELAX_NOT_FINITE 4u
+size_t lsd_pg_workspace_bytes(int nodes_cap, int edges_cap);
+int lsd_enqueue_pg_relax_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_node *d_nodes, int nodes_cap,
+                                lsd_pg_edge *d_edges, int edges_cap, lsd_pg_relax_par par, void *d_workspace, lsd_pg_relax_rep *d_rep,
+                                void *stream);
+/* Host conveniences: host arrays of any alignment, staged through the context; blocking.
+ * lsd_pg_relax: one graph; nodes[n_nodes] and edges[n_edges] are updated in place, rep receives the report.
+ * lsd_pg_append: the graph (head, nodes[nodes_cap], edges[edges_cap], track, store, store_lens) makes the round trip around the device
+ * entry with the n_cand candidates; lens[t] outside 0..stride: LSD_ERR_INVALID. */
+int lsd_pg_relax(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
+                 lsd_pg_relax_rep *rep);
+int lsd_pg_append(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_cand, int stride, const lsd_position *poses,
+                  lsd_pg_head *head, lsd_pg_node *nodes, int nodes_cap, lsd_pg_edge *edges, int edges_cap, lsd_pg_track *track_rec,
+                  int32_t track, lsd_polar *store, int *store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep *rep);
+
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */
 void lsd_scaled_size(int cols, int rows, double sca, int *w, int *h);

@@ -187,6 +187,40 @@ assert FA_SEED_DTYPE.itemsize == 48 and C.sizeof(lsd_fa_seed) == 48
  FA_SEED_NOT_FINITE) = 1, 2, 4, 8, 16, 32, 64, 128
 
 
+# the pose graph (include/lsd_hip.h, "pose graph"): its records, parameters and reports
+class lsd_pg_append(C.Structure):      # the C side's lsd_pg_append_par
+    _fields_ = [("min_dist", C.c_double), ("min_ang", C.c_double), ("info", C.c_double * 6)]
+
+
+class lsd_pg_closure(C.Structure):     # the C side's lsd_pg_closure_par
+    _fields_ = [("cov_scale", C.c_double), ("floor_xy", C.c_double), ("floor_ang", C.c_double)]
+
+
+class lsd_pg_relax(C.Structure):       # the C side's lsd_pg_relax_par
+    _fields_ = [("lambda0", C.c_double), ("lambda_min", C.c_double), ("up", C.c_double), ("down", C.c_double), ("cg_tol", C.c_double),
+                ("eps", C.c_double), ("iters", C.c_int32), ("cg_iters", C.c_int32)]
+
+
+PG_HEAD_DTYPE = np.dtype([("n_nodes", "i4"), ("n_edges", "i4")])
+PG_NODE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("raw", "f8", (3,)), ("flags", "u4"), ("track", "i4"), ("reserved", "u8")])
+PG_EDGE_DTYPE = np.dtype([("i", "i4"), ("j", "i4"), ("flags", "u4"), ("reserved", "u4"), ("z", "f8", (3,)), ("info", "f8", (6,)), ("chi2", "f8")])
+PG_TRACK_DTYPE = np.dtype([("last", "i4"), ("reserved", "i4"), ("raw", "f8", (3,))])
+PG_APPEND_REP_DTYPE = np.dtype([("nodes", "i4"), ("edges", "i4"), ("dropped", "i4"), ("flags", "u4")])
+PG_NEAR_DTYPE = np.dtype([("anchor", "i4"), ("query", "i4"), ("n_cand", "i4"), ("reserved", "i4"), ("d2", "f8")])
+PG_CLOSURE_REP_DTYPE = np.dtype([("edge", "i4"), ("flags", "u4"), ("det", "f8")])
+PG_RELAX_REP_DTYPE = np.dtype([("chi2_before", "f8"), ("chi2_after", "f8"), ("lambda", "f8"), ("iters", "i4"), ("cg_iters", "i4"), ("accepted", "i4"),
+                               ("rejected", "i4"), ("skipped_edges", "i4"), ("singular_nodes", "i4"), ("flags", "u4"), ("reserved", "u4")])
+assert (PG_HEAD_DTYPE.itemsize, PG_NODE_DTYPE.itemsize, PG_EDGE_DTYPE.itemsize, PG_TRACK_DTYPE.itemsize) == (8, 64, 96, 32)
+assert (PG_APPEND_REP_DTYPE.itemsize, PG_NEAR_DTYPE.itemsize, PG_CLOSURE_REP_DTYPE.itemsize, PG_RELAX_REP_DTYPE.itemsize) == (16, 24, 16, 56)
+assert (C.sizeof(lsd_pg_append), C.sizeof(lsd_pg_closure), C.sizeof(lsd_pg_relax)) == (64, 24, 56)
+PG_NODE_FIXED = 1
+PG_EDGE_DISABLED, PG_EDGE_CLOSURE = 1, 2
+PG_APPEND_NODES_FULL, PG_APPEND_EDGES_FULL = 1, 2
+PG_CLOSURE_APPENDED, PG_CLOSURE_NO_ANCHOR, PG_CLOSURE_NO_RESPONSE, PG_CLOSURE_NOT_FINITE, PG_CLOSURE_SINGULAR, PG_CLOSURE_FULL = 1, 2, 4, 8, 16, 32
+PG_RELAX_CONVERGED, PG_RELAX_BREAKDOWN, PG_RELAX_NOT_FINITE = 1, 2, 4
+PG_MAX_NODES, PG_MAX_EDGES = 16384, 65536
+
+
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -303,6 +337,13 @@ _ABI = {
     "lsd_grid_locate_tight_workspace_bytes": (_sz, [_i, _i, lsd_grid_locate_par]),
     "lsd_enqueue_grid_locate_tight_device": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, C.c_uint32, _vp, _vp, _vp]),
     "lsd_grid_locate_tight": (_i, [_vp, _vp, _vp, _i, _i, lsd_map_param, _dbl, _vp, lsd_grid_locate_par, C.c_uint32, _vp, _vp]),
+    "lsd_enqueue_pg_append_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp, _vp]),
+    "lsd_enqueue_pg_near_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _dbl, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_pg_closure_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, lsd_pg_closure, _vp, _vp]),
+    "lsd_pg_workspace_bytes": (_sz, [_i, _i]),
+    "lsd_enqueue_pg_relax_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, _vp, _vp, _vp]),
+    "lsd_pg_relax": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, _vp]),
+    "lsd_pg_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -782,6 +823,66 @@ class Context:
         self._chk(self.L.lsd_fa_carry_seed(self.h, cy.ctypes.data, len(cy), int(frames_pitch), pk.ctypes.data, len(pk), lc.ctypes.data,
                                            None if rs is None else rs.ctypes.data, fa_seed(seed), rep.ctypes.data))
         return cy, rep
+
+    # -- the pose graph: keyframes, the loop candidate, the closure edge, the relaxation (k_pgbuild.hip, k_posegraph.hip) --
+    def enqueue_pg_append_device(self, d_scans, d_lens, n_cand, stride, d_poses, pose_pitch, d_head, d_nodes, nodes_cap, d_edges, edges_cap,
+                                 d_track, track, d_store, d_store_lens, store_stride, append=None, d_rep=None, stream=None):
+        """lsd_enqueue_pg_append_device on raw device addresses: n_cand candidate frames (scans, lengths, stride and poses at a pitch as
+        enqueue_grid_integrate_device reads them) decided in order against the track record at d_track; a keyframe becomes a node, its
+        scan a row of the store, the motion since the last one an edge.  append: pg_append().  d_rep: None, or one PG_APPEND_REP_DTYPE.
+        Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_append_device(self.h, d_scans, d_lens, int(n_cand), int(stride), d_poses, int(pose_pitch), d_head,
+                                                             d_nodes, int(nodes_cap), d_edges, int(edges_cap), d_track, int(track), d_store,
+                                                             d_store_lens, int(store_stride), pg_append(append), d_rep, stream))
+
+    def enqueue_pg_near_device(self, d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, gap, radius, window, d_rec, d_sel,
+                               d_q_scan, d_q_len, d_q_pose, stream=None):
+        """lsd_enqueue_pg_near_device on raw device addresses: the loop candidate of the track's last node -- the nearest node at least
+        `gap` indices back and within `radius` pixels -- into d_rec (PG_NEAR_DTYPE), the poses of the nodes within `window` of it into
+        d_sel (float64 [nodes_cap, 3], the "no pose" sentinel elsewhere) and the query's scan, length and pose into a batch of one row.
+        Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_near_device(self.h, d_head, d_nodes, int(nodes_cap), d_track, d_store, d_store_lens,
+                                                           int(store_stride), int(gap), float(radius), int(window), d_rec, d_sel, d_q_scan, d_q_len,
+                                                           d_q_pose, stream))
+
+    def enqueue_pg_closure_device(self, d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_near, d_resp, closure=None, d_rep=None, stream=None):
+        """lsd_enqueue_pg_closure_device on raw device addresses: the edge (anchor, query) from the near record and the response record
+        (GRID_RESPONSE_DTYPE) of the query matched against the anchor's neighbourhood.  closure: pg_closure().  d_rep: None, or one
+        PG_CLOSURE_REP_DTYPE.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_closure_device(self.h, d_head, d_nodes, int(nodes_cap), d_edges, int(edges_cap), d_near, d_resp,
+                                                              pg_closure(closure), d_rep, stream))
+
+    def enqueue_pg_relax_device(self, n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, d_workspace, d_rep, relax=None, stream=None):
+        """lsd_enqueue_pg_relax_device on raw device addresses: n_graphs graphs (heads [n_graphs], nodes [n_graphs, nodes_cap], edges
+        [n_graphs, edges_cap], n_graphs x pg_workspace_bytes(nodes_cap, edges_cap) bytes of workspace) relaxed in one launch, one
+        workgroup each; the nodes' poses in place, edge.chi2, one PG_RELAX_REP_DTYPE per graph.  relax: pg_relax().  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_relax_device(self.h, int(n_graphs), d_heads, d_nodes, int(nodes_cap), d_edges, int(edges_cap),
+                                                            pg_relax(relax), d_workspace, d_rep, stream))
+
+    def pg_relax(self, nodes, edges, relax=None):
+        """lsd_pg_relax from host arrays: nodes PG_NODE_DTYPE [n], edges PG_EDGE_DTYPE [m].  Returns (nodes, edges, report) after the
+        relaxation; the arguments are not modified.  Blocking."""
+        no, ed = np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        rep = np.zeros(1, PG_RELAX_REP_DTYPE)
+        self._chk(self.L.lsd_pg_relax(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
+                                      pg_relax(relax), rep.ctypes.data))
+        return no, ed, rep[0]
+
+    def pg_append(self, scans, lens, poses, head, nodes, edges, track_rec, store, store_lens, track=0, append=None):
+        """lsd_pg_append from host arrays: the candidates (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]) against the
+        graph head (PG_HEAD_DTYPE), nodes [nodes_cap], edges [edges_cap], track_rec (PG_TRACK_DTYPE), store float64 [nodes_cap,
+        store_stride, 2], store_lens int32 [nodes_cap].  Returns (head, nodes, edges, track_rec, store, store_lens, report): new arrays.
+        Blocking."""
+        sc, ln, po, ok = _host_scans(scans, lens, poses)
+        hd, no, ed = np.array(head, PG_HEAD_DTYPE).reshape(1), np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        tr, st, sl = np.array(track_rec, PG_TRACK_DTYPE).reshape(1), np.array(store, np.float64), np.array(store_lens, np.int32).reshape(-1)
+        if not ok or st.ndim != 3 or st.shape[0] != len(no) or st.shape[2] != 2 or len(sl) != len(no):
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n], poses [n, 3], store [nodes_cap, store_stride, 2], store_lens [nodes_cap]")
+        rep = np.zeros(1, PG_APPEND_REP_DTYPE)
+        self._chk(self.L.lsd_pg_append(self.h, sc.ctypes.data, ln.ctypes.data, len(ln), max(sc.shape[1], 0), po.ctypes.data, hd.ctypes.data,
+                                       no.ctypes.data, len(no), ed.ctypes.data, len(ed), tr.ctypes.data, int(track), st.ctypes.data, sl.ctypes.data,
+                                       st.shape[1], pg_append(append), rep.ctypes.data))
+        return hd[0], no, ed, tr[0], st, sl, rep[0]
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
@@ -1438,6 +1539,65 @@ def fa_correct(correct=None, cov_scale=1.0, floor_xy=1.0, floor_ang=1.0, gate=0.
     return lsd_fa_correct(*vals)
 
 
+def _pg_par(cls, given, defaults, kw):
+    """A parameter struct of the pose graph: `given` itself, or a dict over the defaults, or keywords; the C entries do the refusing."""
+    if isinstance(given, cls):
+        return given
+    a = dict(defaults)
+    a.update({k: v for k, v in kw.items() if v is not None})
+    if isinstance(given, dict):
+        unknown = set(given) - set(a)
+        if unknown:
+            raise LsdError(LSD_ERR_INVALID, "%s: unknown keys %s" % (cls.__name__, sorted(unknown)))
+        a.update(given)
+    elif given is not None and given is not True:
+        raise LsdError(LSD_ERR_INVALID, "%s takes a dict, keywords or the struct itself" % cls.__name__)
+    return a
+
+
+PG_APPEND_DEFAULTS = dict(min_dist=4.0, min_ang=10.0, info=(1.0, 0.0, 1.0, 0.0, 0.0, 1.0))
+PG_CLOSURE_DEFAULTS = dict(cov_scale=1.0, floor_xy=1.0, floor_ang=1.0)
+PG_RELAX_DEFAULTS = dict(lambda0=1e-3, lambda_min=1e-9, up=10.0, down=10.0, cg_tol=1e-8, eps=1e-9, iters=20, cg_iters=200)
+
+
+def pg_append(append=None, min_dist=None, min_ang=None, info=None):
+    """An lsd_pg_append: a frame becomes a keyframe once it is min_dist pixels or min_ang degrees from the last one; info is the
+    information of an odometry edge (xx, xy, yy, xa, ya, aa; 1 / pixels^2 and 1 / degrees^2)."""
+    a = _pg_par(lsd_pg_append, append, PG_APPEND_DEFAULTS, dict(min_dist=min_dist, min_ang=min_ang, info=info))
+    if isinstance(a, lsd_pg_append):
+        return a
+    inf = tuple(float(v) for v in a["info"])
+    if len(inf) != 6:
+        raise LsdError(LSD_ERR_INVALID, "info is xx, xy, yy, xa, ya, aa")
+    return lsd_pg_append(float(a["min_dist"]), float(a["min_ang"]), (C.c_double * 6)(*inf))
+
+
+def pg_closure(closure=None, cov_scale=None, floor_xy=None, floor_ang=None):
+    """An lsd_pg_closure: R = the response's covariance x cov_scale + the floors on its diagonal, as fa_correct()'s; the closure edge's
+    information is its inverse in the anchor's frame."""
+    a = _pg_par(lsd_pg_closure, closure, PG_CLOSURE_DEFAULTS, dict(cov_scale=cov_scale, floor_xy=floor_xy, floor_ang=floor_ang))
+    return a if isinstance(a, lsd_pg_closure) else lsd_pg_closure(float(a["cov_scale"]), float(a["floor_xy"]), float(a["floor_ang"]))
+
+
+def pg_relax(relax=None, lambda0=None, lambda_min=None, up=None, down=None, cg_tol=None, eps=None, iters=None, cg_iters=None):
+    """An lsd_pg_relax: Levenberg-Marquardt's damping (lambda0, divided by `down` after an accepted step but never below lambda_min,
+    multiplied by `up` after a rejected one), at most `iters` outer iterations of at most cg_iters conjugate-gradient steps each, which
+    end once r.z <= cg_tol^2 of its start; an accepted step whose largest component is below eps ends the call."""
+    a = _pg_par(lsd_pg_relax, relax, PG_RELAX_DEFAULTS, dict(lambda0=lambda0, lambda_min=lambda_min, up=up, down=down, cg_tol=cg_tol, eps=eps,
+                                                              iters=iters, cg_iters=cg_iters))
+    if isinstance(a, lsd_pg_relax):
+        return a
+    it, cg = int(a["iters"]), int(a["cg_iters"])
+    if not (-2 ** 31 <= it < 2 ** 31 and -2 ** 31 <= cg < 2 ** 31):
+        raise LsdError(LSD_ERR_INVALID, "iters and cg_iters are int32")
+    return lsd_pg_relax(*(float(a[k]) for k in ("lambda0", "lambda_min", "up", "down", "cg_tol", "eps")), it, cg)
+
+
+def pg_workspace_bytes(nodes_cap, edges_cap):
+    """lsd_pg_workspace_bytes: the workspace of ONE graph of the relaxation; 0 for caps outside 1..16384 / 1..65536."""
+    return int(load_library().lsd_pg_workspace_bytes(int(nodes_cap), int(edges_cap)))
+
+
 FA_SEED_KEYS = ("var_xy", "var_ang", "cov_scale", "floor_xy", "floor_ang", "max_best")
 
 
@@ -1593,7 +1753,7 @@ def _occupancy_grid(d_grid, cols, rows, device):
 class GridMapper:
     """Mapping with known poses: localised scans integrated into an occupancy grid on the device (k_gridmap.hip; include/lsd_hip.h,
     "mapping with known poses").  The reference has no counterpart -- its maps come from an outside SLAM --, and this is
-    no full SLAM either: no loop closure; a pose is entered as it is unless the match_* methods below correct it first (locate_* finds one without a prior).  The mapper owns two planes of rows x cols counters
+    no full SLAM either: a pose is entered as it is (PoseGraph closes loops and rerender_device draws the grid again from the moved poses) unless the match_* methods below correct it first (locate_* finds one without a prior).  The mapper owns two planes of rows x cols counters
     (torch tensors: uint32 values in int32 storage): `pass`, the beams that crossed a cell, and `hit`, those that ended in it.  A scan at
     pose (x, y in pixels of THIS grid, ang in degrees) adds one ray per beam, cut at range_max (metres; a cut beam passes and does not
     hit); publish_device() turns the planes into the int8 OccupancyGrid (-1 below min_pass passes, 100 where hit / pass >= occ[0] /
@@ -1981,6 +2141,160 @@ class GridMapper:
         both = self._planes.cpu().numpy().view(np.uint32).reshape(2, self.rows, self.cols)
         return both[0].copy(), both[1].copy()
 
+    def rerender_device(self, graph, stream=None):
+        """The grid drawn again from a PoseGraph's nodes as they are now: clear(), then the graph's WHOLE keyframe
+        store integrated at its nodes (pitch 64) -- the rows past n_nodes have length 0 and fall out as empty scans, so the host does
+        not need n_nodes.  On `stream` (default: the current one); nothing waits."""
+        if not isinstance(graph, PoseGraph):
+            raise LsdError(LSD_ERR_INVALID, "graph must be a PoseGraph")
+        ts = _cuda_stream(stream)
+        self.clear(ts)
+        self._enqueue(graph.ctx, graph._store.data_ptr(), graph._store_lens.data_ptr(), graph.nodes_cap, graph.n_beams, graph._nodes.data_ptr(),
+                      PG_NODE_DTYPE.itemsize, ts.cuda_stream)
+
+
+class PoseGraph:
+    """A pose graph on the device (k_pgbuild.hip, k_posegraph.hip; include/lsd_hip.h, "pose graph"): keyframes with
+    their scans, odometry edges between neighbours of a track, closure edges from a scan matched against the neighbourhood of an old node,
+    and the relaxation that redistributes the error; GridMapper.rerender_device(graph) then draws the grid again from the moved poses.
+    The graph owns head, nodes, edges, tracks, the keyframe store and the workspace as torch tensors; the counts live on the device.
+    Everything but nodes(), edges(), report() and disable_edges() is enqueued without waiting for the device."""
+
+    def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
+        import torch
+        self.ctx = ctx or default_context()
+        self.nodes_cap, self.edges_cap, self.n_beams, self.n_tracks = int(nodes_cap), int(edges_cap), int(n_beams), int(n_tracks)
+        ws = pg_workspace_bytes(self.nodes_cap, self.edges_cap)
+        if ws == 0 or self.n_beams < 1 or self.n_tracks < 1:
+            raise LsdError(LSD_ERR_INVALID, "nodes_cap 1..16384, edges_cap 1..65536, n_beams >= 1, n_tracks >= 1")
+        dev = "cuda:%d" % int(self.ctx.device)
+
+        def z(*shape, dtype=torch.uint8):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+        self._head, self._nodes, self._edges = z(PG_HEAD_DTYPE.itemsize), z(self.nodes_cap, PG_NODE_DTYPE.itemsize), z(self.edges_cap, PG_EDGE_DTYPE.itemsize)
+        tracks = np.zeros(self.n_tracks, PG_TRACK_DTYPE)
+        tracks["last"] = -1
+        self._tracks = torch.from_numpy(tracks.view(np.uint8).reshape(self.n_tracks, -1)).to(dev)
+        self._store, self._store_lens = z(self.nodes_cap, self.n_beams, 2, dtype=torch.float64), z(self.nodes_cap, dtype=torch.int32)
+        self._ws = z(ws)
+        self._append_rep, self._near, self._closure_rep = z(PG_APPEND_REP_DTYPE.itemsize), z(PG_NEAR_DTYPE.itemsize), z(PG_CLOSURE_REP_DTYPE.itemsize)
+        self._relax_rep = z(PG_RELAX_REP_DTYPE.itemsize)
+        self._sel = z(self.nodes_cap, 3, dtype=torch.float64)
+        self._q_scan, self._q_len, self._q_pose = z(1, self.n_beams, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(1, 3, dtype=torch.float64)
+
+    def _track(self, track):
+        t = int(track)
+        if not 0 <= t < self.n_tracks:
+            raise LsdError(LSD_ERR_INVALID, "track must be 0..%d" % (self.n_tracks - 1))
+        return t, self._tracks.data_ptr() + t * PG_TRACK_DTYPE.itemsize
+
+    def _append(self, d_scans, d_lens, n, stride, d_poses, pose_pitch, track, append, ts):
+        t, d_track = self._track(track)
+        self.ctx.enqueue_pg_append_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self._head.data_ptr(), self._nodes.data_ptr(),
+                                          self.nodes_cap, self._edges.data_ptr(), self.edges_cap, d_track, t, self._store.data_ptr(),
+                                          self._store_lens.data_ptr(), self.n_beams, append, self._append_rep.data_ptr(), ts.cuda_stream)
+
+    def append_device(self, d_scans, d_lens, d_poses, pose_pitch=24, track=0, append=None, stream=None):
+        """Candidate frames that are on the device (the arguments of GridMapper.integrate_device), in order, against `track`: a frame
+        min_dist pixels or min_ang degrees from the track's last keyframe (pg_append()) becomes a node, its scan a row of the store,
+        the measured motion an edge.  Node 0 is appended fixed.  On `stream` (default: the current one)."""
+        import torch
+        for name, t, dt in (("d_scans", d_scans, torch.float64), ("d_lens", d_lens, torch.int32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise LsdError(LSD_ERR_INVALID, "%s must be a contiguous CUDA %s tensor" % (name, str(dt).replace("torch.", "")))
+        n, pitch = d_lens.numel(), int(pose_pitch)
+        if d_scans.dim() != 3 or d_scans.shape[0] != n or d_scans.shape[2] != 2 or d_scans.shape[1] < 1:
+            raise LsdError(LSD_ERR_INVALID, "d_scans must be [n, stride >= 1, 2] with one length per scan")
+        if (not isinstance(d_poses, torch.Tensor) or not d_poses.is_cuda or not d_poses.is_contiguous() or pitch < 24 or
+                (n and d_poses.numel() * d_poses.element_size() < (n - 1) * pitch + 24)):
+            raise LsdError(LSD_ERR_INVALID, "d_poses must be a contiguous CUDA tensor of n records of pose_pitch >= 24 bytes")
+        self._append(d_scans.data_ptr(), d_lens.data_ptr(), n, d_scans.shape[1], d_poses.data_ptr(), pitch, track, append, _cuda_stream(stream))
+        self._held = (d_scans, d_lens, d_poses)                              # the launch reads them: alive until the next one
+
+    def near_device(self, track=0, gap=10, radius=10.0, window=2, stream=None):
+        """The loop candidate of the track's last node (lsd_enqueue_pg_near_device), into the graph's own near record, selection and
+        one-row batch.  On `stream`."""
+        _, d_track = self._track(track)
+        self.ctx.enqueue_pg_near_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, self._store.data_ptr(),
+                                        self._store_lens.data_ptr(), self.n_beams, gap, radius, window, self._near.data_ptr(), self._sel.data_ptr(),
+                                        self._q_scan.data_ptr(), self._q_len.data_ptr(), self._q_pose.data_ptr(), _cuda_stream(stream).cuda_stream)
+
+    def close_device(self, scratch_mapper, track=0, gap=10, radius=10.0, window=2, search=None, response=None, smear=None, closure=None,
+                     stream=None):
+        """One attempt at a loop closure for the last node of `track`, on one stream, in this order: near_device; scratch_mapper.clear();
+        the WHOLE store integrated at the selection -- the anchor's neighbourhood alone, without the host knowing the anchor --;
+        scratch_mapper.likelihood_device(smear); match plus response of the one gathered row; the closure edge.  scratch_mapper: a
+        GridMapper of the map's frame that this call overwrites.  Returns the response record of the query, a CUDA uint8 tensor
+        [1, 192]; closure_report() says what came of it.  Nothing waits."""
+        if not isinstance(scratch_mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        ts = _cuda_stream(stream)
+        self.near_device(track, gap, radius, window, ts)
+        scratch_mapper.clear(ts)
+        scratch_mapper._enqueue(self.ctx, self._store.data_ptr(), self._store_lens.data_ptr(), self.nodes_cap, self.n_beams, self._sel.data_ptr(), 24,
+                                ts.cuda_stream)
+        scratch_mapper.likelihood_device(smear, ts)
+        rec, resp = scratch_mapper._chain(self.ctx, self._q_scan.data_ptr(), self._q_len.data_ptr(), 1, self.n_beams, self._q_pose.data_ptr(), 24,
+                                          search, ts, response=True if response is None else response)
+        self.ctx.enqueue_pg_closure_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                           self._near.data_ptr(), resp.data_ptr(), closure, self._closure_rep.data_ptr(), ts.cuda_stream)
+        self._held_close = (rec, resp)                                       # the launches read them: alive until the next call
+        return resp
+
+    def relax_device(self, relax=None, stream=None, **kw):
+        """The relaxation (lsd_enqueue_pg_relax_device) of this graph: relax is pg_relax(), or its keywords (iters=, cg_iters=, cg_tol=,
+        lambda0=, ..).  The nodes move in place, edge.chi2 and report() are written.  On `stream`; nothing waits."""
+        self.ctx.enqueue_pg_relax_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                         self._ws.data_ptr(), self._relax_rep.data_ptr(), pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
+
+    def fix(self, node, stream=None):
+        """Sets LSD_PG_NODE_FIXED on a node, on `stream`; nothing waits."""
+        import torch
+        n = int(node)
+        if not 0 <= n < self.nodes_cap:
+            raise LsdError(LSD_ERR_INVALID, "node must be 0..nodes_cap-1")
+        with torch.cuda.stream(_cuda_stream(stream)):
+            self._nodes.view(torch.int32)[n, 12] |= PG_NODE_FIXED            # (flags: byte 48 of the record)
+
+    def _read(self, t, dtype):
+        return t.cpu().numpy().reshape(-1).view(dtype).copy()
+
+    def head(self):
+        """(n_nodes, n_edges), clamped to the capacities: a read-back, which waits for the device."""
+        h = self._read(self._head, PG_HEAD_DTYPE)[0]
+        return min(max(int(h["n_nodes"]), 0), self.nodes_cap), min(max(int(h["n_edges"]), 0), self.edges_cap)
+
+    def nodes(self):
+        """The nodes as a numpy array of PG_NODE_DTYPE [n_nodes]: a read-back, which waits for the device."""
+        return self._read(self._nodes, PG_NODE_DTYPE)[:self.head()[0]]
+
+    def edges(self):
+        """The edges as a numpy array of PG_EDGE_DTYPE [n_edges]: a read-back, which waits for the device."""
+        return self._read(self._edges, PG_EDGE_DTYPE)[:self.head()[1]]
+
+    def report(self):
+        """The last relax_device's report (PG_RELAX_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._relax_rep, PG_RELAX_REP_DTYPE)[0]
+
+    def closure_report(self):
+        """(the near record PG_NEAR_DTYPE, the closure report PG_CLOSURE_REP_DTYPE) of the last close_device: a read-back."""
+        return self._read(self._near, PG_NEAR_DTYPE)[0], self._read(self._closure_rep, PG_CLOSURE_REP_DTYPE)[0]
+
+    def append_report(self):
+        """The last append's report (PG_APPEND_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._append_rep, PG_APPEND_REP_DTYPE)[0]
+
+    def disable_edges(self, chi2_above):
+        """Sets LSD_PG_EDGE_DISABLED on every edge whose chi2 (the last relaxation's) exceeds chi2_above; returns their indices.  A host
+        convenience over edges(): it waits for the device."""
+        import torch
+        ed = self.edges()
+        hit = np.flatnonzero(ed["chi2"] > float(chi2_above))
+        if len(hit):
+            ed["flags"][hit] |= PG_EDGE_DISABLED
+            self._edges[:len(ed)].copy_(torch.from_numpy(ed.view(np.uint8).reshape(len(ed), -1)))
+        return hit
+
 
 class _MapSlot:
     """One of a Localizer's two maps on the device: the map bytes, the cache, the line records and their count, the geometry the ticks
@@ -2325,6 +2639,18 @@ class _Ticks:
             mapper._enqueue(self.ctx, d_sc + first * b_scan, d_ln + first * 4, count, self.n_beams, d_st + first * b_state, b_state,
                             ts.cuda_stream)
 
+    def _append_last_tick(self, graph, robot, track, append):
+        """append_last_tick for one robot: its k slots of the tick's staging (scans, lengths, the states at pitch 720) as the candidates of
+        PoseGraph's append, on the tick's stream."""
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not isinstance(graph, PoseGraph) or not 0 <= int(robot) < self.n_robots:
+            raise LsdError(LSD_ERR_INVALID, "graph must be a PoseGraph, robot one of the localizer's")
+        S, k, ts, _ = self._last_tick
+        first, b_state = int(robot) * k, FA_STATE_DTYPE.itemsize
+        graph._append(self._scans.data_ptr() + first * 16 * self.n_beams, self._lens.data_ptr() + first * 4, k, self.n_beams,
+                      self._out.data_ptr() + first * b_state, b_state, track, append, ts)
+
     @staticmethod
     def _runs(robots, k):
         """(first slot, slot count) of every run of neighbouring robots among `robots` (ascending indices), k slots per robot."""
@@ -2666,6 +2992,12 @@ class Localizer(_Ticks):
         With mapper.publish_device() feeding set_map_device(grid, *mapper.map_param) the loop closes on the device."""
         self._integrate_last_tick(mapper, range(self.n_robots))
 
+    def append_last_tick(self, graph, robot=0, track=None, append=None):
+        """Keyframes of the last tick into a PoseGraph: on the tick's stream and behind it, the frames of `robot` are
+        the candidates of graph.append_device, each at the state it produced (pitch 720), read from the tick's staging; nothing is read
+        back and nothing waits.  track: the graph's track they continue (None: the robot's index).  Call it before the next tick."""
+        self._append_last_tick(graph, robot, int(robot) if track is None else track, append)
+
     def screen_and_integrate_last_tick(self, mapper, ray=None, d_grid=None):
         """integrate_last_tick with the ray-casting stage in front (GridMapper.screen_and_integrate_device): on the last
         tick's stream and behind the tick, every frame of the tick is cast through the grid (d_grid, or None: the mapper's planes
@@ -2922,6 +3254,17 @@ class FleetLocalizer(_Ticks):
         if self._last_tick is None:
             raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
         self._integrate_last_tick(mapper, np.flatnonzero(self._last_tick[3] == i))
+
+    def append_last_tick(self, graph, map_id, robot, track=None, append=None):
+        """Localizer.append_last_tick for `robot`, which was on map `map_id` when the last tick was enqueued (LsdError otherwise): a fleet
+        has one graph per map, and the robot's poses are in that map's pixels.  track: None, the robot's index -- the graph needs that
+        many tracks."""
+        i = self._map_id(map_id)
+        if self._last_tick is None:
+            raise LsdError(LSD_ERR_INVALID, "no tick has been enqueued yet")
+        if not 0 <= int(robot) < self.n_robots or self._last_tick[3][int(robot)] != i:
+            raise LsdError(LSD_ERR_INVALID, "robot %r was not on map %r in the last tick" % (robot, map_id))
+        self._append_last_tick(graph, robot, int(robot) if track is None else track, append)
 
     def refine_and_integrate_last_tick(self, mapper, map_id, search=None, refresh=True, smear=None, block=0, response=None, integrate_at="match",
                                        correct=None):

@@ -256,6 +256,19 @@ void launch_fa_lost_gather(const lsd_fa_carry* carry, int n_seq, int frames_pitc
                            int32_t* pick, int32_t* n_lost, hipStream_t s);
 void launch_fa_seed(lsd_fa_carry* carry, int n_seq, int frames_pitch, const int32_t* pick, int n_pick, const lsd_grid_locate_rec* loc,
                     const lsd_grid_response_rec* resp, lsd_fa_seed_par par, lsd_fa_seed_rep* rep, hipStream_t s);
+// the pose graph (host side: lsd_pg.hip).  Building it (k_pgbuild.hip): one launch each, no workspace
+void launch_pg_append(const lsd_polar* scans, const int* lens, int n_cand, int stride, const void* poses, size_t pose_pitch, lsd_pg_head* head,
+                      lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* track, int32_t track_id, lsd_polar* store,
+                      int* store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep* rep, hipStream_t s);
+void launch_pg_near(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track, const lsd_polar* store,
+                    const int* store_lens, int store_stride, int gap, double radius, int window, lsd_pg_near_rec* rec, lsd_position* sel,
+                    lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t s);
+void launch_pg_closure(lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, const lsd_pg_near_rec* near_rec,
+                       const lsd_grid_response_rec* resp, lsd_pg_closure_par par, lsd_pg_closure_rep* rep, hipStream_t s);
+// its relaxation (k_posegraph.hip): one workgroup per graph; pg_ws_bytes: the workspace of one graph
+size_t pg_ws_bytes(int nodes_cap, int edges_cap);
+void launch_pg_relax(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
+                     lsd_pg_relax_par par, void* ws, lsd_pg_relax_rep* rep, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

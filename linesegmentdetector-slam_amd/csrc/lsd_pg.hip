@@ -1,0 +1,166 @@
+// lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the four device entries
+// (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation) and the two host conveniences, staged through the context's carver
+// as every other host entry.
+#include <math.h>
+#include <stddef.h>
+
+#include "lsd_ctx.h"
+
+static_assert(sizeof(lsd_pg_head) == 8 && sizeof(lsd_pg_node) == 64 && offsetof(lsd_pg_node, x) == 0 && offsetof(lsd_pg_node, y) == 8 &&
+              offsetof(lsd_pg_node, ang) == 16 && offsetof(lsd_pg_node, raw) == 24 && offsetof(lsd_pg_node, flags) == 48 &&
+              offsetof(lsd_pg_node, track) == 52 && offsetof(lsd_pg_node, reserved) == 56,
+              "lsd_pg_node is 64 bytes and starts with a pose: an array of them is a d_poses argument of pitch 64");
+static_assert(sizeof(lsd_pg_edge) == 96 && offsetof(lsd_pg_edge, flags) == 8 && offsetof(lsd_pg_edge, z) == 16 && offsetof(lsd_pg_edge, info) == 40 &&
+              offsetof(lsd_pg_edge, chi2) == 88, "lsd_pg_edge is 96 bytes");
+static_assert(sizeof(lsd_pg_track) == 32 && offsetof(lsd_pg_track, raw) == 8 && sizeof(lsd_pg_append_par) == 64 && sizeof(lsd_pg_append_rep) == 16 &&
+              sizeof(lsd_pg_near_rec) == 24 && offsetof(lsd_pg_near_rec, d2) == 16 && sizeof(lsd_pg_closure_par) == 24 && sizeof(lsd_pg_closure_rep) == 16 &&
+              offsetof(lsd_pg_closure_rep, det) == 8, "the records of building a pose graph");
+static_assert(sizeof(lsd_pg_relax_par) == 56 && offsetof(lsd_pg_relax_par, iters) == 48 && sizeof(lsd_pg_relax_rep) == 56 &&
+              offsetof(lsd_pg_relax_rep, iters) == 24 && offsetof(lsd_pg_relax_rep, flags) == 48, "the relaxation's parameters and report");
+
+constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
+
+static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+static bool pg_caps_bad(int nodes_cap, int edges_cap) { return nodes_cap < 1 || nodes_cap > kPgMaxNodes || edges_cap < 1 || edges_cap > kPgMaxEdges; }
+static bool pg_real_bad(double v) { return !std::isfinite(v) || v < 0; }
+
+static bool pg_append_par_bad(const lsd_pg_append_par& p) {
+    for (int k = 0; k < 6; k++) if (!std::isfinite(p.info[k])) return true;
+    return pg_real_bad(p.min_dist) || pg_real_bad(p.min_ang);
+}
+
+static bool pg_relax_par_bad(const lsd_pg_relax_par& p) {
+    if (pg_real_bad(p.lambda0) || pg_real_bad(p.lambda_min) || pg_real_bad(p.up) || pg_real_bad(p.down) || pg_real_bad(p.cg_tol) || pg_real_bad(p.eps))
+        return true;
+    return p.up <= 1 || p.down < 1 || p.iters < 0 || p.iters > 65535 || p.cg_iters < 0 || p.cg_iters > 65535;
+}
+
+extern "C" {
+
+int lsd_enqueue_pg_append_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_cand, int stride, const void* d_poses,
+                                 size_t pose_pitch, lsd_pg_head* d_head, lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges, int edges_cap,
+                                 lsd_pg_track* d_track, int32_t track, lsd_polar* d_store, int* d_store_lens, int store_stride,
+                                 lsd_pg_append_par par, lsd_pg_append_rep* d_rep, void* stream) {
+    if (!c || !d_scans || !d_lens || !d_poses || !d_head || !d_nodes || !d_edges || !d_track || !d_store || !d_store_lens) return LSD_ERR_INVALID;
+    if (n_cand < 0 || stride <= 0 || stride > c->scan_cap || store_stride <= 0 || store_stride > c->scan_cap) return LSD_ERR_INVALID;
+    if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || pg_caps_bad(nodes_cap, edges_cap) || pg_append_par_bad(par)) return LSD_ERR_INVALID;
+    if (((addr(d_scans) | addr(d_store)) & 15) || ((addr(d_poses) | addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_track) | addr(d_rep)) & 7) ||
+        ((addr(d_lens) | addr(d_store_lens)) & 3)) {
+        c->err = "pg append: scans and store 16-byte, the records 8-byte, the lengths 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_cand == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_append(d_scans, d_lens, n_cand, stride, d_poses, pose_pitch, d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_track, track, d_store,
+                         d_store_lens, store_stride, par, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_near_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, const lsd_pg_track* d_track,
+                               const lsd_polar* d_store, const int* d_store_lens, int store_stride, int gap, double radius, int window,
+                               lsd_pg_near_rec* d_rec, lsd_position* d_sel, lsd_polar* d_q_scan, int* d_q_len, lsd_position* d_q_pose, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || !d_rec || !d_sel || !d_q_scan || !d_q_len || !d_q_pose)
+        return LSD_ERR_INVALID;
+    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || gap < 1 || window < 0 || pg_real_bad(radius))
+        return LSD_ERR_INVALID;
+    if (((addr(d_store) | addr(d_q_scan)) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_track) | addr(d_rec) | addr(d_sel) | addr(d_q_pose)) & 7) ||
+        ((addr(d_store_lens) | addr(d_q_len)) & 3)) {
+        c->err = "pg near: store and d_q_scan 16-byte, the records 8-byte, the lengths 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_near(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, gap, radius, window, d_rec, d_sel, d_q_scan, d_q_len,
+                       d_q_pose, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_closure_device(lsd_ctx* c, lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges, int edges_cap,
+                                  const lsd_pg_near_rec* d_near, const lsd_grid_response_rec* d_resp, lsd_pg_closure_par par,
+                                  lsd_pg_closure_rep* d_rep, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_edges || !d_near || !d_resp || pg_caps_bad(nodes_cap, edges_cap)) return LSD_ERR_INVALID;
+    if (pg_real_bad(par.cov_scale) || pg_real_bad(par.floor_xy) || pg_real_bad(par.floor_ang)) return LSD_ERR_INVALID;
+    if ((addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_near) | addr(d_resp) | addr(d_rep)) & 7) {
+        c->err = "pg closure: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_closure(d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_near, d_resp, par, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+size_t lsd_pg_workspace_bytes(int nodes_cap, int edges_cap) { return pg_caps_bad(nodes_cap, edges_cap) ? 0 : pg_ws_bytes(nodes_cap, edges_cap); }
+
+int lsd_enqueue_pg_relax_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_heads, lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges,
+                                int edges_cap, lsd_pg_relax_par par, void* d_workspace, lsd_pg_relax_rep* d_rep, void* stream) {
+    if (!c || !d_heads || !d_nodes || !d_edges || !d_workspace || !d_rep || n_graphs < 0) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_relax_par_bad(par)) return LSD_ERR_INVALID;
+    if ((addr(d_heads) | addr(d_nodes) | addr(d_edges) | addr(d_workspace) | addr(d_rep)) & 7) {
+        c->err = "pg relax: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_graphs == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_relax(n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, par, d_workspace, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_relax(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_relax_rep* rep) {
+    if (!c || !rep || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
+        return LSD_ERR_INVALID;
+    if (pg_relax_par_bad(par)) return LSD_ERR_INVALID;
+    const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
+    const lsd_pg_head head{n_nodes, n_edges};
+    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; uint8_t* d_ws;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) { k(d_head, 1); k(d_no, nc); k(d_ed, ec); k(d_rep, 1); k(d_ws, pg_ws_bytes(nc, ec)); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
+    if (n_nodes) HIPCHK(c, hipMemcpyAsync(d_no, nodes, n_nodes * sizeof(lsd_pg_node), hipMemcpyHostToDevice, c->stream));
+    if (n_edges) HIPCHK(c, hipMemcpyAsync(d_ed, edges, n_edges * sizeof(lsd_pg_edge), hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    if (n_nodes) HIPCHK(c, hipMemcpyAsync(nodes, d_no, n_nodes * sizeof(lsd_pg_node), hipMemcpyDeviceToHost, c->stream));
+    if (n_edges) HIPCHK(c, hipMemcpyAsync(edges, d_ed, n_edges * sizeof(lsd_pg_edge), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_cand, int stride, const lsd_position* poses, lsd_pg_head* head,
+                  lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* track_rec, int32_t track, lsd_polar* store,
+                  int* store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep* rep) {
+    if (!c || !scans || !lens || !poses || !head || !nodes || !edges || !track_rec || !store || !store_lens || !rep) return LSD_ERR_INVALID;
+    if (n_cand < 0 || stride <= 0 || stride > c->scan_cap || store_stride <= 0 || store_stride > c->scan_cap) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_append_par_bad(par)) return LSD_ERR_INVALID;
+    for (int i = 0; i < n_cand; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
+    if (n_cand == 0) return LSD_OK;
+    const size_t nc = (size_t)n_cand, rows = (size_t)nodes_cap * store_stride;
+    lsd_polar *d_sc, *d_store; int *d_len, *d_sl; lsd_position* d_po; lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_track* d_tr;
+    lsd_pg_append_rep* d_rep;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) {
+        k(d_sc, nc * stride); k(d_len, nc); k(d_po, nc); k(d_head, 1); k(d_no, nodes_cap); k(d_ed, edges_cap); k(d_tr, 1); k(d_store, rows);
+        k(d_sl, nodes_cap); k(d_rep, 1);
+    };
+    HIPCHK(c, carve(c->stage, regions));
+    struct Trip { void* dev; void* host; size_t bytes; };
+    const Trip in[] = {{d_sc, const_cast<lsd_polar*>(scans), nc * stride * sizeof(lsd_polar)}, {d_len, const_cast<int*>(lens), nc * sizeof(int)},
+                       {d_po, const_cast<lsd_position*>(poses), nc * sizeof(lsd_position)}};
+    const Trip both[] = {{d_head, head, sizeof *head}, {d_no, nodes, nodes_cap * sizeof(lsd_pg_node)}, {d_ed, edges, edges_cap * sizeof(lsd_pg_edge)},
+                         {d_tr, track_rec, sizeof *track_rec}, {d_store, store, rows * sizeof(lsd_polar)}, {d_sl, store_lens, nodes_cap * sizeof(int)}};
+    for (const Trip& t : in) HIPCHK(c, hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, c->stream));
+    for (const Trip& t : both) HIPCHK(c, hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, c->stream));
+    const int st = lsd_enqueue_pg_append_device(c, d_sc, d_len, n_cand, stride, d_po, sizeof(lsd_position), d_head, d_no, nodes_cap, d_ed, edges_cap,
+                                                d_tr, track, d_store, d_sl, store_stride, par, d_rep, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    for (const Trip& t : both) HIPCHK(c, hipMemcpyAsync(t.host, t.dev, t.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+}  // extern "C"
