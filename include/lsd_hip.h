@@ -1210,7 +1210,9 @@ int lsd_debug_poison_front(lsd_ctx *ctx);
  *                                   resweep_batches*, slow_batches*, cycles_eval*, cycles_sums*, cycles_refine*, cycles_idle*,
  *                                   cycles_select*, cycles_commit*, filter_skips*
  *                                   (summed over the wavefronts that share an image; * = counted by the developer build only,
- *                                   `make stats` -> liblsdhip_stats.so, and 0 in the product build)
+ *                                   `make stats` -> liblsdhip_stats.so, and 0 in the product build).  Word 45 of the record (48 words
+ *                                   are kept per image): bits 3..0 the XCC the image ran on, bits 8.. the RegionGrower calls that took
+ *                                   the any-tolerance function (tolerances of 1.5 rad and more, NaN: csrc/region/grow.h, grow_any())
  *   SINCOS         h*w*2 doubles    (sin, cos) of degMap as the gradient pass leaves them for RegionGrower (myLSD.cpp:545-546), one pair
  *                                   per pixel.  Entries are DEFINED ONLY WHERE THE PIXEL'S CODE IS 0 after the gradient pass (PW & 3,
  *                                   == usedMap before the region stage): (0, 1) on row 0 / column 0 (an interior pixel without

@@ -1223,6 +1223,7 @@ class Context:
                          [int(x) for x in v]))
             d["set_answers"], d["sets_founded"] = int(v[41]), int(v[42])   # evaluations answered by a certified uniform set / sets founded (region/eval.h)
             d["cycles_nfa_count"], d["nfa_tail_iters"] = int(v[43]), int(v[44])   # developer build: cycles of the NFA's pixel count, iterations of its tail sum
+            d["grow_any_calls"] = int(v[45]) >> 8   # RegionGrower calls that took the any-tolerance function (region/grow.h: grow_any; tolerances of 1.5 rad and more, NaN); bits 3..0 of the word: the image's XCC
             d["nfa_bracket_misses"] = int(v[40])   # stopping tests of the NFA's tail left to the correctly rounded pow / log10 (an image the watchdog gave up keeps its record here instead)
             # how close RectangleImprover's comparisons came to a tie, as margins (distance of the operands over what an ulp of exp / log10 /
             # pow can move them; region/nfa.h: improve()): smallest for a logNFA compared with 0, smallest for two compared NFA values (inf: none seen)

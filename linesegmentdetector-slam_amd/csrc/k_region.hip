@@ -41,7 +41,7 @@
 //   lds.h     the namespace-scope LDS: per-wave arena and its views, the g_* objects, EvalOut, stage4 / acc32
 //   wave.h    wave primitives: ballots, L2 accesses and fences, uni / uglobal, DPP reductions, lget / lset
 //   tiles.h   the LDS tile cache and the member masks in HBM
-//   grow.h    exact_sums, grow() (RegionGrower)
+//   grow.h    exact_sums, grow() / grow_any() (RegionGrower, by tolerance class)
 //   rect.h    rect_convert, rec_density, radius_reduce (RegionRadiusReducer)
 //   nfa.h     log_gamma_dev, nfa_count, nfa_tail, improve (RectangleImprover)
 //   eval.h    refine_tol (Refiner), mark_region, list_bbox, certify_set, eval_seed
@@ -1157,7 +1157,7 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
     }
     if (b.stats && !pool) {
         unsigned long long* st = reinterpret_cast<unsigned long long*>(b.stats + img * kStatWords);
-        if (lane == 0 && wave == 0 && !lds_ld(&s_abort)) { b.stats[img * kStatWords + 45] = (long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15); b.stats[img * kStatWords + 46] = rt_begin; b.stats[img * kStatWords + 47] = (long long)__builtin_amdgcn_s_memrealtime(); }   // (developer record: when the image ran)
+        if (lane == 0 && wave == 0 && !lds_ld(&s_abort)) { atomicAdd(&st[kStatGrowAnyWord], (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15)); b.stats[img * kStatWords + 46] = rt_begin; b.stats[img * kStatWords + 47] = (long long)__builtin_amdgcn_s_memrealtime(); }   // (developer record: when the image ran)
         if (lane == 0 && wave == 0) {
             // shader clocks of this workgroup on the image.  s_memtime is a counter of the XCD the wavefront runs on: a workgroup that was
             // preempted (more hardware queues in use than the device has -- e.g. two processes with 16 each -- make the scheduler time-slice
@@ -1169,10 +1169,11 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
             if (tot <= 0 || tot > 4 * rt + 1000000) tot = rt > 0 ? rt : 1;
             g_stat[c.wave][sslot(ST_TOTAL)] = (unsigned long long)tot; g_stat[c.wave][sslot(ST_SEEDS)] = (unsigned long long)nseeds; DSTAT(ST_DEPTHEND, lds_ld(&s_depth));
         }
-        if (lane < ST_COUNT && !lds_ld(&s_abort) && (sslot(lane) != 11 || lane == ST_NFASLOW || kStatSlots == ST_COUNT)) {
+        if (lane < ST_COUNT && !lds_ld(&s_abort) && (sslot(lane) != 11 || lane == ST_NFASLOW || kStatSlots > ST_COUNT)) {   // (kStatSlots > ST_COUNT: the developer build, a slot per counter)
             if (lane == ST_MINNFA || lane == ST_MINGAP) atomicMax(&st[lane], g_stat[c.wave][sslot(lane)]);
             else atomicAdd(&st[lane], g_stat[c.wave][sslot(lane)]);
         }
+        if (lane == 0 && !lds_ld(&s_abort)) atomicAdd(&st[kStatGrowAnyWord], g_stat[c.wave][sslot(ST_GROWANY)] << 8);   // (the record starts from zero: the XCC above and the waves' counts add up in any order)
         g_stat[c.wave][sslot(ST_XHELP)] = 0ull;
         // (what a helper adds to ANOTHER image's record below starts from zero: not from this image's own margins and ties)
         g_stat[c.wave][sslot(ST_MINNFA)] = 0ull; g_stat[c.wave][sslot(ST_MINGAP)] = 0ull; g_stat[c.wave][sslot(ST_NFASLOW)] = 0ull; g_stat[c.wave][sslot(ST_TIES)] = 0ull;

@@ -13,6 +13,7 @@ constexpr int kLgTable = 16384;                 // host-tabulated log-gamma entr
 constexpr int kLgTableMax = 1 << 23;            //    pixel count a rectangle can have, + 1), up to this many
 constexpr int kStatWords = 48;                  // counters per image of the region stage (lsd_debug_fetch LSD_DBG_STATS)
 constexpr int kStatTiesWord = 39;               // ... and this one its decisions within the libm's noise (region/stats.h: ST_TIES; lsd_last_sensitivity)
+constexpr int kStatGrowAnyWord = 45;            // ... bits 8.. of this one count the calls of grow_any() (region/grow.h; region/stats.h: ST_GROWANY), bits 3..0: the XCC the image ran on
 constexpr int kStatTotalWord = 8;               // ... of which this one holds the shader clocks the stage spent on the image (region/stats.h: ST_TOTAL)
 constexpr int kPTable = 16;                     // host-tabulated log(p), log10(p), log(1-p) for p = aliPro/2^k
 // Help across workgroups in the region stage (k_region.hip): a control block of 32-bit words per launch, cleared before it.

@@ -280,7 +280,8 @@ __device__ __noinline__ void eval_seed(int cw_, uint32_t pp_, int spec_, int slo
         double tol = p_degThre, regdeg = seedDeg;
         bool done = false;
         for (int pass = 0; pass < 2 && !done; pass++) {
-            num = uni(grow(wave, sx, sy, seedDeg, tol));                               // :225 / :857
+            // (by tolerance class, region/grow.h: tol is wave-uniform, a NaN goes with the large ones)
+            num = uni(uni((int)(tol < 1.5)) ? grow(wave, sx, sy, seedDeg, tol) : grow_any(wave, sx, sy, seedDeg, tol));   // :225 / :857
             if (pass == 0 && spec && num <= gcap) {                // keep the first list for the validation at the cursor
                 EVAL_CTX();
                 uint32_t* const gl0 = EVAL_GL0();

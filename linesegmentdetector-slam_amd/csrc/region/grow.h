@@ -1,5 +1,5 @@
 // region/grow.h -- RegionGrower (myLSD.cpp:491-590) with all 64 lanes of a wave: exact_sums (the angle sums, :545-546), the helpers of the fp32 estimate
-// (inv_ub, kEpsU, fast_sincos) and grow().  Touches the whole arena (list ring G_LST, worklist G_WL, tile cache through tiles.h), g_ws, g_ctx[].llo,
+// (inv_ub, kEpsU, fast_sincos) and grow() / grow_any().  Touches the whole arena (list ring G_LST, worklist G_WL, tile cache through tiles.h), g_ws, g_ctx[].llo,
 // g_tol0 and g_acc; list entries that left the ring and the slack records are in HBM (RCtx::spill, RCtx::meta).  GROW_ESTIMATE begins and ends in grow().
 // ---------------------------------------------------------------------------------------------
 // The exact angle sums of the current region (sinDeg, cosDeg of RegionGrower, :545-546) over the list prefix
@@ -74,7 +74,14 @@ __device__ __forceinline__ void fast_sincos(float a, float& s, float& co) {   //
     co = __builtin_amdgcn_cosf(r);
 }
 
-__device__ __noinline__ int grow(int cw_, int sx_, int sy_, double regDeg0_, double tol_) {
+// Written once, compiled per TOLERANCE CLASS (the callers are grow() and grow_any() below): kTolSmall -- tol < 1.5, every first grow at the
+// default angThre and nearly all of Refiner's regrows: the circular-distance form alone; else -- any other tolerance, NaN included: the
+// pixel-by-pixel form with the reference's wrapped difference (fp64 atan2) alone.  Every decision is taken by the same expressions as when
+// one function held both; each class lacks only the code that cannot run for it.  Under the 4-wave build's 128 registers that is what
+// matters: a function saves its callee-saved registers at every call whether or not the path that needs them runs, and without the
+// any-tolerance path grow() puts away 22 registers instead of 52 ("grow() by tolerance class").
+template <bool kTolSmall>
+__device__ __forceinline__ int grow_body(int cw_, int sx_, int sy_, double regDeg0_, double tol_) {
     RCtx c = g_ctx[__builtin_amdgcn_readfirstlane(cw_)];
     c.lane = (int)(threadIdx.x & 63u);
     const int lane = c.lane;
@@ -127,12 +134,12 @@ __device__ __noinline__ int grow(int cw_, int sx_, int sy_, double regDeg0_, dou
     }
     int n = 1;
     bool wt = false;                                         // the list has outgrown the ring: entries are also written through to `spill`
-    if (!(tol == tol)) {                                     // NaN tolerance (Refiner, :855): no test ever passes
+    if (!kTolSmall && !(tol == tol)) {                       // NaN tolerance (Refiner, :855): no test ever passes (NaN < 1.5 is false: never in class 1)
         if (lane == 0) g_ws[wave].gnum = 1;
-        STAT(ST_GROW, 1); STAT(ST_GROWN, 1);
+        STAT(ST_GROW, 1); STAT(ST_GROWN, 1); STAT(ST_GROWANY, 1);
         return 1;
     }
-    const bool tol_small = tol < 1.5;                        // the circular-distance form applies, and accepted vectors never shorten the sum
+    constexpr bool tol_small = kTolSmall;                    // (tol < 1.5: eval_seed() chooses) the circular-distance form applies, and accepted vectors never shorten the sum
     const float turn = (float)(tol < 1.1 ? tol : 1.1) * 1.0032f;   // >= sin(tol) resp. the asin(1/L)*L bound, x (|V| estimate / its lower bound)
     const float tolf_lo = (float)tol * 0.9999999f;           // <= tol
     float cos_tol, sin_tol;
@@ -454,6 +461,10 @@ __device__ __noinline__ int grow(int cw_, int sx_, int sy_, double regDeg0_, dou
     if (wt) wg_fence();                                      // the written-through part is read back by the stages that follow
     STAT(ST_GROW, 1);
     STAT(ST_GROWN, n);
+    if (!tol_small) STAT(ST_GROWANY, 1);
     DSTAT(ST_TGROW, NOW() - t0);
     return n;
 }
+// The two out-of-line functions eval_seed() chooses between by the wave-uniform tolerance (region/eval.h)
+__device__ __noinline__ int grow(int cw_, int sx_, int sy_, double regDeg0_, double tol_) { return grow_body<true>(cw_, sx_, sy_, regDeg0_, tol_); }        // tol < 1.5
+__device__ __noinline__ int grow_any(int cw_, int sx_, int sy_, double regDeg0_, double tol_) { return grow_body<false>(cw_, sx_, sy_, regDeg0_, tol_); }   // every other tolerance (counted: ST_GROWANY)

@@ -33,7 +33,8 @@ for i in range(K + depth):
     j = i % depth
     prev = i - depth
     if lo <= prev < hi:
-        st = ctxs[j].fetch_stats_block(n)                 # slots 46 / 47: s_memrealtime (100 MHz) at the image's start / end, 45: its XCC, 8: clocks
+        st = ctxs[j].fetch_stats_block(n)                 # slots 46 / 47: s_memrealtime (100 MHz) at the image's start / end, 45: its XCC (bits 3..0), 8: clocks
+        st[:, 45] &= 15
         rec[prev] = st[:, [46, 47, 45, 8]].astype(float)
         tms[prev] = ctxs[j].timings()
     if i < K: step(i)
