@@ -1134,12 +1134,62 @@ size_t lsd_pg_workspace_bytes(int nodes_cap, int edges_cap);
 int lsd_enqueue_pg_relax_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_node *d_nodes, int nodes_cap,
                                 lsd_pg_edge *d_edges, int edges_cap, lsd_pg_relax_par par, void *d_workspace, lsd_pg_relax_rep *d_rep,
                                 void *stream);
+/* lsd_enqueue_pg_relax_robust_device: the relaxation above with a robust kernel on its edges, so that a closure that is confidently wrong
+ * loses its pull instead of bending the graph (csrc/k_posegraph.hip, the same body compiled a second time; restated in
+ * tests/pose_graph_robust_cases.py).  The arguments of lsd_enqueue_pg_relax_device, the kernel `rob` and one lsd_pg_robust_rep per graph
+ * (d_rob_rep may be NULL).  Everything that is not named here is the text above, word for word: the skipping of edges, the lists, the one
+ * reduction shape, PCG, the singular nodes, the stops.
+ *   An edge is IN SCOPE when it is not skipped and either scope == LSD_PG_ROBUST_ALL or LSD_PG_EDGE_CLOSURE is set.
+ *   s = chi2_e, the plain value at the poses in question;  c = delta * delta.  The weight w and the cost rho of an edge:
+ *     out of scope, or kernel NONE:  w = 1.0, rho = s
+ *     HUBER:  s <= c:  w = 1.0, rho = s;  otherwise  r = sqrt(s), w = delta / r, rho = (2.0 * delta) * r - c      (sqrt of a NaN: that NaN)
+ *     GM (Geman-McClure):  t = c / (c + s), w = t * t, rho = (c * s) / (c + s)
+ *     a skipped edge:  rho = +0.0
+ *   The objective F = the reduction over all E edges of rho_e stands wherever the plain rule says chi2: the value at the start (not finite:
+ *   NOT_FINITE, nothing more is done), the test F' <= F at the trial poses, chi2_before and chi2_after of the lsd_pg_relax_rep.
+ *   Step 1: w_e at the current poses; W'(r,t) = w_e * W(r,t) -- all nine products, also when w_e is 1.0 --; WA, WB and the We of ba and bb
+ *   come from W'; chi2_e itself comes from W.  Multiplying by 1.0 is exact: kernel NONE, and HUBER with a delta above every sqrt(chi2_e)
+ *   met, give the bytes of lsd_enqueue_pg_relax_device.
+ * Outputs: the nodes in place; edge.chi2 = the PLAIN chi2_e at the final poses (lsd_enqueue_pg_prune_device reads it); d_rep as above with
+ * F in the place of chi2; d_rob_rep: chi2_plain = the reduction of those plain values; downweighted = the edges in scope with w < 1.0 at the
+ * final poses; w_min = the smallest w among the edges in scope and w_min_edge the smallest index that has it -- 1.0 and -1 when no edge is
+ * in scope; when some w is a NaN, that NaN and the smallest index that holds one.  (A NaN that the device makes out of finite numbers is
+ * the quiet one with the sign set, 0xfff8000000000000, and no operation of the rule turns its sign; an input that is not finite is skipped.)
+ * The workspace is lsd_pg_workspace_bytes per graph: a weight is made again from chi2_e where it is needed and never stored.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: everything lsd_enqueue_pg_relax_device refuses; kernel outside 0..2;
+ * scope outside 0..1; with kernel != NONE a delta that is not finite or not > 0; d_rob_rep not 8-byte aligned. */
+typedef struct lsd_pg_robust_par { int32_t kernel; uint32_t scope; double delta; } lsd_pg_robust_par;   /* 16 bytes */
+enum { LSD_PG_KERNEL_NONE = 0, LSD_PG_KERNEL_HUBER = 1, LSD_PG_KERNEL_GM = 2 };
+enum { LSD_PG_ROBUST_CLOSURES = 0, LSD_PG_ROBUST_ALL = 1 };
+typedef struct lsd_pg_robust_rep { double chi2_plain, w_min; int32_t downweighted, w_min_edge; } lsd_pg_robust_rep;  /* 24 bytes */
+int lsd_enqueue_pg_relax_robust_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_node *d_nodes, int nodes_cap,
+                                       lsd_pg_edge *d_edges, int edges_cap, lsd_pg_relax_par par, lsd_pg_robust_par rob, void *d_workspace,
+                                       lsd_pg_relax_rep *d_rep, lsd_pg_robust_rep *d_rob_rep /* may be NULL */, void *stream);
+/* lsd_enqueue_pg_prune_device: closures whose chi2 -- the last relaxation's -- is beyond a gate are taken out of the graph, on the device
+ * (csrc/k_pgprune.hip).  Graph g is d_heads[g], d_edges + g * edges_cap and d_rep[g]; E is its clamped n_edges.
+ *   A CANDIDATE is an edge e < E with CLOSURE set, DISABLED clear and !(chi2 <= gate): a NaN is one.
+ *   Candidates are ordered by chi2 descending, a NaN counting as +infinity, equals by ascending index.
+ *   The first min(max_reject, candidates) of that order get flags |= LSD_PG_EDGE_DISABLED | LSD_PG_EDGE_REJECTED.  No other byte of any
+ *   edge changes; nothing at or beyond E changes.
+ *   Report: candidates; rejected; worst_edge and worst_chi2 = the first of the order, its chi2 as it stands (-1 and +0.0 without a
+ *   candidate); closures_left = the CLOSURE edges below E that are not DISABLED afterwards.  max_reject == 0 only counts.
+ * One launch, ONE WORKGROUP PER GRAPH: at most max(max_reject, 1) rounds of one arg-max each, no workspace, no atomics on fp64, no host
+ * wait.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; n_graphs < 0; edges_cap outside 1..65536; gate not
+ * finite or negative; max_reject outside 0..64; a pointer not 8-byte aligned.  n_graphs == 0 launches nothing. */
+typedef struct lsd_pg_prune_par { double gate; int32_t max_reject, reserved; } lsd_pg_prune_par;        /* 16 bytes */
+typedef struct lsd_pg_prune_rep { int32_t candidates, rejected, worst_edge, closures_left; double worst_chi2; } lsd_pg_prune_rep; /* 24 bytes */
+#define LSD_PG_EDGE_REJECTED 4u
+int lsd_enqueue_pg_prune_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_edge *d_edges, int edges_cap,
+                                lsd_pg_prune_par par, lsd_pg_prune_rep *d_rep, void *stream);
 /* Host conveniences: host arrays of any alignment, staged through the context; blocking.
  * lsd_pg_relax: one graph; nodes[n_nodes] and edges[n_edges] are updated in place, rep receives the report.
+ * lsd_pg_relax_robust: the same around lsd_enqueue_pg_relax_robust_device; rep and rob_rep receive the two reports.
  * lsd_pg_append: the graph (head, nodes[nodes_cap], edges[edges_cap], track, store, store_lens) makes the round trip around the device
  * entry with the n_cand candidates; lens[t] outside 0..stride: LSD_ERR_INVALID. */
 int lsd_pg_relax(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
                  lsd_pg_relax_rep *rep);
+int lsd_pg_relax_robust(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
+                        lsd_pg_robust_par rob, lsd_pg_relax_rep *rep, lsd_pg_robust_rep *rob_rep);
 int lsd_pg_append(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_cand, int stride, const lsd_position *poses,
                   lsd_pg_head *head, lsd_pg_node *nodes, int nodes_cap, lsd_pg_edge *edges, int edges_cap, lsd_pg_track *track_rec,
                   int32_t track, lsd_polar *store, int *store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep *rep);

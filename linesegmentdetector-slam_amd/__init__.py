@@ -201,6 +201,14 @@ class lsd_pg_relax(C.Structure):       # the C side's lsd_pg_relax_par
                 ("eps", C.c_double), ("iters", C.c_int32), ("cg_iters", C.c_int32)]
 
 
+class lsd_pg_robust(C.Structure):      # the C side's lsd_pg_robust_par
+    _fields_ = [("kernel", C.c_int32), ("scope", C.c_uint32), ("delta", C.c_double)]
+
+
+class lsd_pg_prune(C.Structure):       # the C side's lsd_pg_prune_par
+    _fields_ = [("gate", C.c_double), ("max_reject", C.c_int32), ("reserved", C.c_int32)]
+
+
 PG_HEAD_DTYPE = np.dtype([("n_nodes", "i4"), ("n_edges", "i4")])
 PG_NODE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("raw", "f8", (3,)), ("flags", "u4"), ("track", "i4"), ("reserved", "u8")])
 PG_EDGE_DTYPE = np.dtype([("i", "i4"), ("j", "i4"), ("flags", "u4"), ("reserved", "u4"), ("z", "f8", (3,)), ("info", "f8", (6,)), ("chi2", "f8")])
@@ -219,6 +227,14 @@ PG_APPEND_NODES_FULL, PG_APPEND_EDGES_FULL = 1, 2
 PG_CLOSURE_APPENDED, PG_CLOSURE_NO_ANCHOR, PG_CLOSURE_NO_RESPONSE, PG_CLOSURE_NOT_FINITE, PG_CLOSURE_SINGULAR, PG_CLOSURE_FULL = 1, 2, 4, 8, 16, 32
 PG_RELAX_CONVERGED, PG_RELAX_BREAKDOWN, PG_RELAX_NOT_FINITE = 1, 2, 4
 PG_MAX_NODES, PG_MAX_EDGES = 16384, 65536
+# the robust relaxation and the rejection of closures
+PG_ROBUST_REP_DTYPE = np.dtype([("chi2_plain", "f8"), ("w_min", "f8"), ("downweighted", "i4"), ("w_min_edge", "i4")])
+PG_PRUNE_REP_DTYPE = np.dtype([("candidates", "i4"), ("rejected", "i4"), ("worst_edge", "i4"), ("closures_left", "i4"), ("worst_chi2", "f8")])
+assert (PG_ROBUST_REP_DTYPE.itemsize, PG_PRUNE_REP_DTYPE.itemsize, C.sizeof(lsd_pg_robust), C.sizeof(lsd_pg_prune)) == (24, 24, 16, 16)
+PG_EDGE_REJECTED = 4
+PG_KERNEL_NONE, PG_KERNEL_HUBER, PG_KERNEL_GM = 0, 1, 2
+PG_ROBUST_CLOSURES, PG_ROBUST_ALL = 0, 1
+PG_MAX_REJECT = 64
 
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
@@ -343,6 +359,9 @@ _ABI = {
     "lsd_pg_workspace_bytes": (_sz, [_i, _i]),
     "lsd_enqueue_pg_relax_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, _vp, _vp, _vp]),
     "lsd_pg_relax": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, _vp]),
+    "lsd_enqueue_pg_relax_robust_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_pg_prune_device": (_i, [_vp, _i, _vp, _vp, _i, lsd_pg_prune, _vp, _vp]),
+    "lsd_pg_relax_robust": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, _vp, _vp]),
     "lsd_pg_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
@@ -867,6 +886,33 @@ class Context:
         self._chk(self.L.lsd_pg_relax(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
                                       pg_relax(relax), rep.ctypes.data))
         return no, ed, rep[0]
+
+    def enqueue_pg_relax_robust_device(self, n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, d_workspace, d_rep, robust, d_rob_rep=None,
+                                       relax=None, stream=None):
+        """lsd_enqueue_pg_relax_robust_device on raw device addresses: enqueue_pg_relax_device with a robust kernel on the edges (robust:
+        pg_robust()) -- an edge in scope pulls with a weight made from its own chi2, and the objective is the kernel's cost.  edge.chi2
+        stays the plain value.  d_rob_rep: None, or one PG_ROBUST_REP_DTYPE per graph.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_relax_robust_device(self.h, int(n_graphs), d_heads, d_nodes, int(nodes_cap), d_edges, int(edges_cap),
+                                                                   pg_relax(relax), pg_robust(robust), d_workspace, d_rep, d_rob_rep, stream))
+
+    def enqueue_pg_prune_device(self, n_graphs, d_heads, d_edges, edges_cap, d_rep, gate, max_reject=8, stream=None):
+        """lsd_enqueue_pg_prune_device on raw device addresses: in every graph the closure edges that are not disabled and whose chi2
+        is not <= gate are candidates; the max_reject (0..64) largest become DISABLED | REJECTED.  One PG_PRUNE_REP_DTYPE per graph.
+        Asynchronous on `stream`."""
+        mr = int(max_reject)
+        if not -2 ** 31 <= mr < 2 ** 31:
+            raise LsdError(LSD_ERR_INVALID, "max_reject is int32")
+        return self._chk(self.L.lsd_enqueue_pg_prune_device(self.h, int(n_graphs), d_heads, d_edges, int(edges_cap), lsd_pg_prune(float(gate), mr, 0),
+                                                            d_rep, stream))
+
+    def pg_relax_robust(self, nodes, edges, robust, relax=None):
+        """lsd_pg_relax_robust from host arrays, as pg_relax(): returns (nodes, edges, report, robust report) after the relaxation with
+        the kernel `robust` (pg_robust()); blocking."""
+        no, ed = np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        rep, rob = np.zeros(1, PG_RELAX_REP_DTYPE), np.zeros(1, PG_ROBUST_REP_DTYPE)
+        self._chk(self.L.lsd_pg_relax_robust(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
+                                             pg_relax(relax), pg_robust(robust), rep.ctypes.data, rob.ctypes.data))
+        return no, ed, rep[0], rob[0]
 
     def pg_append(self, scans, lens, poses, head, nodes, edges, track_rec, store, store_lens, track=0, append=None):
         """lsd_pg_append from host arrays: the candidates (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]) against the
@@ -1594,6 +1640,27 @@ def pg_relax(relax=None, lambda0=None, lambda_min=None, up=None, down=None, cg_t
     return lsd_pg_relax(*(float(a[k]) for k in ("lambda0", "lambda_min", "up", "down", "cg_tol", "eps")), it, cg)
 
 
+PG_ROBUST_DEFAULTS = dict(kernel="huber", delta=1.0, scope="closures")
+_PG_KERNELS = {"none": PG_KERNEL_NONE, "huber": PG_KERNEL_HUBER, "gm": PG_KERNEL_GM}
+_PG_SCOPES = {"closures": PG_ROBUST_CLOSURES, "all": PG_ROBUST_ALL}
+
+
+def pg_robust(robust=None, kernel=None, delta=None, scope=None):
+    """An lsd_pg_robust: the kernel on the edges of a robust relaxation -- "huber" (for a first relaxation from drifted poses), "gm"
+    (Geman-McClure: for a closure that arrives on a graph that is already relaxed), "none" or the C side's number --, its width delta
+    in units of sqrt(chi2), and the scope: "closures" (edges with PG_EDGE_CLOSURE) or "all".  DESIGN.md 8.1.16 has the cases."""
+    a = _pg_par(lsd_pg_robust, robust, PG_ROBUST_DEFAULTS, dict(kernel=kernel, delta=delta, scope=scope))
+    if isinstance(a, lsd_pg_robust):
+        return a
+    k, s = a["kernel"], a["scope"]
+    if isinstance(k, str) and k not in _PG_KERNELS or isinstance(s, str) and s not in _PG_SCOPES:
+        raise LsdError(LSD_ERR_INVALID, "kernel is one of %s or an int, scope one of %s or an int" % (sorted(_PG_KERNELS), sorted(_PG_SCOPES)))
+    k, s = int(_PG_KERNELS.get(k, k)), int(_PG_SCOPES.get(s, s))
+    if not (-2 ** 31 <= k < 2 ** 31 and 0 <= s < 2 ** 32):
+        raise LsdError(LSD_ERR_INVALID, "kernel is int32, scope uint32")
+    return lsd_pg_robust(k, s, float(a["delta"]))
+
+
 def pg_workspace_bytes(nodes_cap, edges_cap):
     """lsd_pg_workspace_bytes: the workspace of ONE graph of the relaxation; 0 for caps outside 1..16384 / 1..65536."""
     return int(load_library().lsd_pg_workspace_bytes(int(nodes_cap), int(edges_cap)))
@@ -2159,7 +2226,8 @@ class PoseGraph:
     their scans, odometry edges between neighbours of a track, closure edges from a scan matched against the neighbourhood of an old node,
     and the relaxation that redistributes the error; GridMapper.rerender_device(graph) then draws the grid again from the moved poses.
     The graph owns head, nodes, edges, tracks, the keyframe store and the workspace as torch tensors; the counts live on the device.
-    Everything but nodes(), edges(), report() and disable_edges() is enqueued without waiting for the device."""
+    optimize_device() makes the relaxation robust against closures that are confidently wrong and takes them out on the device (DESIGN.md
+    8.1.16).  Everything but nodes(), edges(), the *report() methods and disable_edges() is enqueued without waiting for the device."""
 
     def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
         import torch
@@ -2180,6 +2248,7 @@ class PoseGraph:
         self._ws = z(ws)
         self._append_rep, self._near, self._closure_rep = z(PG_APPEND_REP_DTYPE.itemsize), z(PG_NEAR_DTYPE.itemsize), z(PG_CLOSURE_REP_DTYPE.itemsize)
         self._relax_rep = z(PG_RELAX_REP_DTYPE.itemsize)
+        self._robust_rep, self._prune_rep = z(PG_ROBUST_REP_DTYPE.itemsize), z(PG_PRUNE_REP_DTYPE.itemsize)
         self._sel = z(self.nodes_cap, 3, dtype=torch.float64)
         self._q_scan, self._q_len, self._q_pose = z(1, self.n_beams, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(1, 3, dtype=torch.float64)
 
@@ -2242,11 +2311,34 @@ class PoseGraph:
         self._held_close = (rec, resp)                                       # the launches read them: alive until the next call
         return resp
 
-    def relax_device(self, relax=None, stream=None, **kw):
+    def relax_device(self, relax=None, stream=None, robust=None, **kw):
         """The relaxation (lsd_enqueue_pg_relax_device) of this graph: relax is pg_relax(), or its keywords (iters=, cg_iters=, cg_tol=,
-        lambda0=, ..).  The nodes move in place, edge.chi2 and report() are written.  On `stream`; nothing waits."""
-        self.ctx.enqueue_pg_relax_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
-                                         self._ws.data_ptr(), self._relax_rep.data_ptr(), pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
+        lambda0=, ..).  The nodes move in place, edge.chi2 and report() are written.  robust: None, or pg_robust() for the robust
+        relaxation (lsd_enqueue_pg_relax_robust_device), which also writes robust_report().  On `stream`; nothing waits."""
+        if robust is None:
+            self.ctx.enqueue_pg_relax_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                             self._ws.data_ptr(), self._relax_rep.data_ptr(), pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
+            return
+        self.ctx.enqueue_pg_relax_robust_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(),
+                                                self.edges_cap, self._ws.data_ptr(), self._relax_rep.data_ptr(), pg_robust(robust),
+                                                self._robust_rep.data_ptr(), pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
+
+    def prune_device(self, gate, max_reject=8, stream=None):
+        """The rejection of closures (lsd_enqueue_pg_prune_device): the closure edges that are not disabled and whose chi2 -- the last
+        relaxation's -- is not <= gate are candidates; the max_reject (0..64) largest become DISABLED | REJECTED.  prune_report() says
+        what was done.  On `stream`; nothing waits."""
+        self.ctx.enqueue_pg_prune_device(1, self._head.data_ptr(), self._edges.data_ptr(), self.edges_cap, self._prune_rep.data_ptr(), gate, max_reject,
+                                         _cuda_stream(stream).cuda_stream)
+
+    def optimize_device(self, robust, gate, max_reject=8, relax=None, refit=None, stream=None):
+        """Three launches on one stream: the robust relaxation (robust: pg_robust(); relax: pg_relax()), prune_device(gate, max_reject)
+        on the plain chi2 it leaves, and the plain relaxation over the edges that survive (refit: pg_relax(), default: relax).  Huber
+        for a first relaxation from drifted poses, Geman-McClure for a closure on a relaxed graph.  report() is the
+        refit's, robust_report() and prune_report() those of the first two.  Nothing waits."""
+        ts = _cuda_stream(stream)
+        self.relax_device(relax, ts, robust=robust)
+        self.prune_device(gate, max_reject, ts)
+        self.relax_device(relax if refit is None else refit, ts)
 
     def fix(self, node, stream=None):
         """Sets LSD_PG_NODE_FIXED on a node, on `stream`; nothing waits."""
@@ -2276,6 +2368,15 @@ class PoseGraph:
     def report(self):
         """The last relax_device's report (PG_RELAX_REP_DTYPE): a read-back, which waits for the device."""
         return self._read(self._relax_rep, PG_RELAX_REP_DTYPE)[0]
+
+    def robust_report(self):
+        """The second report (PG_ROBUST_REP_DTYPE) of the last ROBUST relaxation -- relax_device(robust=) or optimize_device; a plain
+        relax_device after it leaves this record as it was, so it is older than report() then.  A read-back, which waits for the device."""
+        return self._read(self._robust_rep, PG_ROBUST_REP_DTYPE)[0]
+
+    def prune_report(self):
+        """The last prune_device's report (PG_PRUNE_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._prune_rep, PG_PRUNE_REP_DTYPE)[0]
 
     def closure_report(self):
         """(the near record PG_NEAR_DTYPE, the closure report PG_CLOSURE_REP_DTYPE) of the last close_device: a read-back."""

@@ -8,6 +8,11 @@
 // the poses and at the trial poses, H, M, b and the five CG vectors, the trial poses; then the words: an edge's validity, the lists
 // (2 E entries, entry = 2 e + side), their offsets and fill cursors, a node's state.  The lists are built once per call: count (integer
 // atomics), scan, fill 256 edges at a time -- so an entry is at most 2 x 256 places from where it belongs -- and an insertion sort per node.
+//
+// The body is compiled twice.  kRobust = false is lsd_enqueue_pg_relax_device.  kRobust = true is lsd_enqueue_pg_relax_robust_device (the
+// header's rule; restated in tests/pose_graph_robust_cases.py): an edge in scope gets a weight w_e from its plain chi2_e at
+// the current poses, its blocks come from w_e * W, and the objective that is accepted against is the reduction of rho(chi2_e); ce / cen keep
+// the PLAIN values, so a weight costs no workspace.  valid[e] carries the scope in bit 1.
 #include "lsd_internal.h"
 #include "posegraph_dev.h"
 
@@ -81,6 +86,30 @@ __device__ inline double pg_dot3(const double* u, const double* v) {
     return t;
 }
 
+// the robust kernels (the header's rule): w and rho of an edge whose plain chi2_e is s; in: the edge is in scope
+__device__ inline void pg_weight(const lsd_pg_robust_par& rp, bool in, double s, double& w, double& rho) {
+    w = 1.0;
+    rho = s;
+    if (!in || rp.kernel == LSD_PG_KERNEL_NONE) return;
+    const double c = rp.delta * rp.delta;
+    if (rp.kernel == LSD_PG_KERNEL_HUBER) {
+        if (s <= c) return;
+        const double r = s != s ? s : sqrt(s);      // (IEEE: the square root of a NaN is that NaN)
+        w = rp.delta / r;
+        rho = (2.0 * rp.delta) * r - c;
+    } else {
+        const double t = c / (c + s);
+        w = t * t;
+        rho = (c * s) / (c + s);
+    }
+}
+
+__device__ inline double pg_rho(const lsd_pg_robust_par& rp, int valid, double s) {
+    double w, rho;
+    pg_weight(rp, (valid & 2) != 0, s, w, rho);
+    return rho;
+}
+
 // the error of an edge at the poses pi, pj, and (s, c) of pi's angle, dx, dy for the blocks
 __device__ inline void pg_error(const PgPose& pi, const PgPose& pj, const double* z, double* e, double& s, double& c, double& dx, double& dy) {
     sincos_g(deg2rad_ref(pi.a), s, c);
@@ -100,10 +129,12 @@ __device__ inline void pg_info(const lsd_pg_edge& ed, double* W) {
 __device__ inline PgPose pg_pose_of(const lsd_pg_node& n) { return PgPose{n.x, n.y, n.ang}; }
 
 // chi2_e of every edge into out[], at the nodes' poses (trial == nullptr) or at the trial poses; with blocks: the blocks too
+template <bool kRobust>
 __device__ inline void pg_edges(const lsd_pg_node* nodes, const lsd_pg_edge* edges, int E, int ec, const PgWs& w, const double* trial, double* out,
-                                bool blocks) {
+                                bool blocks, const lsd_pg_robust_par& rp) {
     for (int e = (int)threadIdx.x; e < E; e += kPgLanes) {
-        if (!w.valid[e]) { out[e] = 0.0; continue; }
+        const int vl = w.valid[e];
+        if (!vl) { out[e] = 0.0; continue; }
         const lsd_pg_edge ed = edges[e];
         PgPose pi, pj;
         if (trial) {
@@ -118,8 +149,17 @@ __device__ inline void pg_edges(const lsd_pg_node* nodes, const lsd_pg_edge* edg
         pg_info(ed, W);
 #pragma unroll
         for (int r = 0; r < 3; r++) We[r] = pg_dot3(W + 3 * r, er);
-        out[e] = pg_dot3(er, We);
+        const double ce = pg_dot3(er, We);
+        out[e] = ce;
         if (!blocks) continue;
+        if constexpr (kRobust) {                                                                     // W' = w_e * W, We from W'
+            double we, rho;
+            pg_weight(rp, (vl & 2) != 0, ce, we, rho);
+#pragma unroll
+            for (int q = 0; q < 9; q++) W[q] = we * W[q];
+#pragma unroll
+            for (int r = 0; r < 3; r++) We[r] = pg_dot3(W + 3 * r, er);
+        }
         const double k = kPi / 180.0;
         const double A[9] = {-c, -s, k * (c * dy - s * dx), s, -c, k * ((-c) * dx - s * dy), 0.0, 0.0, -1.0};
         const double B[9] = {c, s, 0.0, -s, c, 0.0, 0.0, 0.0, 1.0};
@@ -160,11 +200,13 @@ __device__ inline void pg_edges(const lsd_pg_node* nodes, const lsd_pg_edge* edg
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads, lsd_pg_node* all_nodes, int nc, lsd_pg_edge* all_edges, int ec,
-                                                       lsd_pg_relax_par par, uint8_t* ws_all, size_t ws_bytes, lsd_pg_relax_rep* reps) {
+template <bool kRobust>
+__device__ __forceinline__ void pg_relax_body(const lsd_pg_head* heads, lsd_pg_node* all_nodes, int nc, lsd_pg_edge* all_edges, int ec,
+                                              const lsd_pg_relax_par& par, uint8_t* ws_all, size_t ws_bytes, lsd_pg_relax_rep* reps,
+                                              const lsd_pg_robust_par& rp, lsd_pg_robust_rep* rob_reps) {
     __shared__ double s_red[kPgShape];
     __shared__ int s_cnt[kPgLanes];
-    __shared__ int s_int[2];
+    __shared__ int s_int[kRobust ? 3 : 2];
     const int g = (int)blockIdx.x, tid = (int)threadIdx.x;
     lsd_pg_node* nodes = all_nodes + (size_t)g * nc;
     lsd_pg_edge* edges = all_edges + (size_t)g * ec;
@@ -172,7 +214,7 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
     const int N = min(max(heads[g].n_nodes, 0), nc), E = min(max(heads[g].n_edges, 0), ec);
 
     // --- the edges that count, the nodes' states, the lists -----------------------------------------------------------------------------
-    if (tid < 2) s_int[tid] = 0;
+    if (tid < (kRobust ? 3 : 2)) s_int[tid] = 0;
     for (int n = tid; n < N; n += kPgLanes) {
         w.cur[n] = 0;
         w.st[n] = (nodes[n].flags & LSD_PG_NODE_FIXED) ? kPgFixed : kPgFree;
@@ -190,7 +232,8 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
             const lsd_pg_node &a = nodes[ed.i], &b = nodes[ed.j];
             ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.ang) && isfinite(b.x) && isfinite(b.y) && isfinite(b.ang);
         }
-        w.valid[e] = ok ? 1 : 0;
+        if constexpr (kRobust) w.valid[e] = ok ? ((rp.scope == LSD_PG_ROBUST_ALL || (ed.flags & LSD_PG_EDGE_CLOSURE)) ? 3 : 1) : 0;
+        else w.valid[e] = ok ? 1 : 0;
         if (ok) { atomicAdd(&w.cur[ed.i], 1); atomicAdd(&w.cur[ed.j], 1); }
         else skipped++;
     }
@@ -228,8 +271,13 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
     __syncthreads();
 
     // --- chi2 at the poses ------------------------------------------------------------------------------------------------------------------
-    pg_edges(nodes, edges, E, ec, w, nullptr, w.ce, false);
-    double chi2 = pg_reduce(E, [&](int e) { return w.ce[e]; }, s_red);
+    // (kRobust: chi2 is the objective F, the reduction of rho; ce and cen hold the plain chi2_e)
+    auto objective = [&](const double* v) {
+        if constexpr (kRobust) return pg_reduce(E, [&](int e) { return pg_rho(rp, w.valid[e], v[e]); }, s_red);
+        else return pg_reduce(E, [&](int e) { return v[e]; }, s_red);
+    };
+    pg_edges<kRobust>(nodes, edges, E, ec, w, nullptr, w.ce, false, rp);
+    double chi2 = objective(w.ce);
     const double chi2_before = chi2;
     double lambda = par.lambda0;
     int done = 0, cg_total = 0, accepted = 0, rejected = 0;
@@ -237,7 +285,7 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
     if (!isfinite(chi2)) flags |= LSD_PG_RELAX_NOT_FINITE;
 
     while (!(flags & LSD_PG_RELAX_NOT_FINITE) && done < par.iters) {
-        pg_edges(nodes, edges, E, ec, w, nullptr, w.ce, true);                                        // 1
+        pg_edges<kRobust>(nodes, edges, E, ec, w, nullptr, w.ce, true, rp);                           // 1
         for (int n = tid; n < N; n += kPgLanes) {                                                     // 2, 3
             double H[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};
             for (int m = w.off[n]; m < w.off[n + 1]; m++) {
@@ -299,11 +347,16 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
                         const int en = w.ent[m], e = en >> 1, side = en & 1;
                         const double* o = w.blk + e + (size_t)9 * ec;
                         const double* po = w.p + 3 * (side ? edges[e].i : edges[e].j);
+                        double hb[9], pv[3];                                                      // (all twelve loads in front of the sums)
+#pragma unroll
+                        for (int q = 0; q < 9; q++) hb[q] = o[(size_t)q * ec];
+#pragma unroll
+                        for (int q = 0; q < 3; q++) pv[q] = po[q];
 #pragma unroll
                         for (int r = 0; r < 3; r++) {
                             double t = 0.0;
 #pragma unroll
-                            for (int q = 0; q < 3; q++) t += o[(size_t)(side ? 3 * q + r : 3 * r + q) * ec] * po[q];
+                            for (int q = 0; q < 3; q++) t += hb[side ? 3 * q + r : 3 * r + q] * pv[q];
                             qv[r] = qv[r] + t;
                         }
                     }
@@ -357,8 +410,8 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
         double maxd = 0.0;
         for (int t = 0; t < kPgLanes; t++) maxd = s_red[t] > maxd ? s_red[t] : maxd;
         __syncthreads();
-        pg_edges(nodes, edges, E, ec, w, w.tp, w.cen, false);
-        const double chi2n = pg_reduce(E, [&](int e) { return w.cen[e]; }, s_red);
+        pg_edges<kRobust>(nodes, edges, E, ec, w, w.tp, w.cen, false, rp);
+        const double chi2n = objective(w.cen);
         done++;
         if (chi2n <= chi2) {
             for (int n = tid; n < N; n += kPgLanes) {
@@ -389,12 +442,60 @@ __global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads,
         o->iters = done; o->cg_iters = cg_total; o->accepted = accepted; o->rejected = rejected;
         o->skipped_edges = s_int[0]; o->singular_nodes = s_int[1]; o->flags = flags; o->reserved = 0;
     }
+    if constexpr (kRobust) {
+        if (!rob_reps) return;
+        // the robust report: the plain chi2, and the weights at the final poses.  A lane keeps the first of the order (a NaN before every
+        // number, then the smaller w, among equals the smaller index) over its edges, lane 0 the first over the lanes.
+        const double plain = pg_reduce(E, [&](int e) { return w.ce[e]; }, s_red);
+        auto before = [](double wa, int ia, double wb, int ib) {      // (wa, ia) comes before (wb, ib); ib < 0: nothing there yet
+            if (ib < 0) return true;
+            const bool na = wa != wa, nb = wb != wb;
+            if (na || nb) return na && (!nb || ia < ib);
+            return wa < wb || (wa == wb && ia < ib);
+        };
+        double wm = 1.0;
+        int im = -1, down = 0;
+        for (int e = tid; e < E; e += kPgLanes) {
+            if (!(w.valid[e] & 2)) continue;
+            double we, rho;
+            pg_weight(rp, true, w.ce[e], we, rho);
+            down += we < 1.0;
+            if (before(we, e, wm, im)) { wm = we; im = e; }
+        }
+        if (down) atomicAdd(&s_int[2], down);
+        s_red[tid] = wm;
+        s_cnt[tid] = im;
+        __syncthreads();
+        if (tid == 0) {
+            for (int t = 1; t < kPgLanes; t++)
+                if (s_cnt[t] >= 0 && before(s_red[t], s_cnt[t], wm, im)) { wm = s_red[t]; im = s_cnt[t]; }
+            lsd_pg_robust_rep* o = rob_reps + g;
+            o->chi2_plain = plain; o->w_min = wm; o->downweighted = s_int[2]; o->w_min_edge = im;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kPgLanes) void k_pg_relax(const lsd_pg_head* heads, lsd_pg_node* all_nodes, int nc, lsd_pg_edge* all_edges, int ec,
+                                                       lsd_pg_relax_par par, uint8_t* ws_all, size_t ws_bytes, lsd_pg_relax_rep* reps) {
+    pg_relax_body<false>(heads, all_nodes, nc, all_edges, ec, par, ws_all, ws_bytes, reps, lsd_pg_robust_par{}, nullptr);
+}
+
+__global__ __launch_bounds__(kPgLanes) void k_pg_relax_robust(const lsd_pg_head* heads, lsd_pg_node* all_nodes, int nc, lsd_pg_edge* all_edges,
+                                                              int ec, lsd_pg_relax_par par, uint8_t* ws_all, size_t ws_bytes,
+                                                              lsd_pg_relax_rep* reps, lsd_pg_robust_par rp, lsd_pg_robust_rep* rob_reps) {
+    pg_relax_body<true>(heads, all_nodes, nc, all_edges, ec, par, ws_all, ws_bytes, reps, rp, rob_reps);
 }
 
 void launch_pg_relax(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
                      lsd_pg_relax_par par, void* ws, lsd_pg_relax_rep* rep, hipStream_t st) {
     hipLaunchKernelGGL(k_pg_relax, dim3(n_graphs), dim3(kPgLanes), 0, st, heads, nodes, nodes_cap, edges, edges_cap, par,
                        static_cast<uint8_t*>(ws), pg_ws_bytes(nodes_cap, edges_cap), rep);
+}
+
+void launch_pg_relax_robust(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
+                            lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, hipStream_t st) {
+    hipLaunchKernelGGL(k_pg_relax_robust, dim3(n_graphs), dim3(kPgLanes), 0, st, heads, nodes, nodes_cap, edges, edges_cap, par,
+                       static_cast<uint8_t*>(ws), pg_ws_bytes(nodes_cap, edges_cap), rep, rob, rob_rep);
 }
 
 }  // namespace lsdhip

@@ -270,6 +270,11 @@ void launch_pg_closure(lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_ca
 size_t pg_ws_bytes(int nodes_cap, int edges_cap);
 void launch_pg_relax(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
                      lsd_pg_relax_par par, void* ws, lsd_pg_relax_rep* rep, hipStream_t s);
+// the same body with a robust kernel on the edges (rob_rep may be null), and the rejection of closures by their chi2 (k_pgprune.hip)
+void launch_pg_relax_robust(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
+                            lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, hipStream_t s);
+void launch_pg_prune(int n_graphs, const lsd_pg_head* heads, lsd_pg_edge* edges, int edges_cap, lsd_pg_prune_par par, lsd_pg_prune_rep* rep,
+                     hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

@@ -1,6 +1,6 @@
-// lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the four device entries
-// (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation) and the two host conveniences, staged through the context's carver
-// as every other host entry.
+// lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the six device entries
+// (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures) and
+// the three host conveniences, staged through the context's carver as every other host entry.
 #include <math.h>
 #include <stddef.h>
 
@@ -17,6 +17,9 @@ static_assert(sizeof(lsd_pg_track) == 32 && offsetof(lsd_pg_track, raw) == 8 && 
               offsetof(lsd_pg_closure_rep, det) == 8, "the records of building a pose graph");
 static_assert(sizeof(lsd_pg_relax_par) == 56 && offsetof(lsd_pg_relax_par, iters) == 48 && sizeof(lsd_pg_relax_rep) == 56 &&
               offsetof(lsd_pg_relax_rep, iters) == 24 && offsetof(lsd_pg_relax_rep, flags) == 48, "the relaxation's parameters and report");
+static_assert(sizeof(lsd_pg_robust_par) == 16 && offsetof(lsd_pg_robust_par, delta) == 8 && sizeof(lsd_pg_robust_rep) == 24 &&
+              offsetof(lsd_pg_robust_rep, downweighted) == 16 && sizeof(lsd_pg_prune_par) == 16 && offsetof(lsd_pg_prune_par, max_reject) == 8 &&
+              sizeof(lsd_pg_prune_rep) == 24 && offsetof(lsd_pg_prune_rep, worst_chi2) == 16, "the robust relaxation's and the prune's records");
 
 constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
 
@@ -34,6 +37,15 @@ static bool pg_relax_par_bad(const lsd_pg_relax_par& p) {
         return true;
     return p.up <= 1 || p.down < 1 || p.iters < 0 || p.iters > 65535 || p.cg_iters < 0 || p.cg_iters > 65535;
 }
+
+static bool pg_robust_par_bad(const lsd_pg_robust_par& r) {
+    if (r.kernel < LSD_PG_KERNEL_NONE || r.kernel > LSD_PG_KERNEL_GM || r.scope > LSD_PG_ROBUST_ALL) return true;
+    return r.kernel != LSD_PG_KERNEL_NONE && !(std::isfinite(r.delta) && r.delta > 0);
+}
+
+// the two host relaxations: one graph around the device entry, rob == nullptr for the plain one
+static int pg_relax_host(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par,
+                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep);
 
 extern "C" {
 
@@ -108,26 +120,45 @@ int lsd_enqueue_pg_relax_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_h
     });
 }
 
-int lsd_pg_relax(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_relax_rep* rep) {
-    if (!c || !rep || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
+int lsd_enqueue_pg_relax_robust_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_heads, lsd_pg_node* d_nodes, int nodes_cap,
+                                       lsd_pg_edge* d_edges, int edges_cap, lsd_pg_relax_par par, lsd_pg_robust_par rob, void* d_workspace,
+                                       lsd_pg_relax_rep* d_rep, lsd_pg_robust_rep* d_rob_rep, void* stream) {
+    if (!c || !d_heads || !d_nodes || !d_edges || !d_workspace || !d_rep || n_graphs < 0) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_relax_par_bad(par) || pg_robust_par_bad(rob)) return LSD_ERR_INVALID;
+    if ((addr(d_heads) | addr(d_nodes) | addr(d_edges) | addr(d_workspace) | addr(d_rep) | addr(d_rob_rep)) & 7) {
+        c->err = "pg relax robust: every pointer 8-byte aligned";
         return LSD_ERR_INVALID;
-    if (pg_relax_par_bad(par)) return LSD_ERR_INVALID;
-    const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
-    const lsd_pg_head head{n_nodes, n_edges};
-    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; uint8_t* d_ws;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) { k(d_head, 1); k(d_no, nc); k(d_ed, ec); k(d_rep, 1); k(d_ws, pg_ws_bytes(nc, ec)); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
-    if (n_nodes) HIPCHK(c, hipMemcpyAsync(d_no, nodes, n_nodes * sizeof(lsd_pg_node), hipMemcpyHostToDevice, c->stream));
-    if (n_edges) HIPCHK(c, hipMemcpyAsync(d_ed, edges, n_edges * sizeof(lsd_pg_edge), hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    if (n_nodes) HIPCHK(c, hipMemcpyAsync(nodes, d_no, n_nodes * sizeof(lsd_pg_node), hipMemcpyDeviceToHost, c->stream));
-    if (n_edges) HIPCHK(c, hipMemcpyAsync(edges, d_ed, n_edges * sizeof(lsd_pg_edge), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    }
+    if (n_graphs == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_relax_robust(n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, par, rob, d_workspace, d_rep, d_rob_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_prune_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_heads, lsd_pg_edge* d_edges, int edges_cap, lsd_pg_prune_par par,
+                                lsd_pg_prune_rep* d_rep, void* stream) {
+    if (!c || !d_heads || !d_edges || !d_rep || n_graphs < 0 || edges_cap < 1 || edges_cap > kPgMaxEdges) return LSD_ERR_INVALID;
+    if (pg_real_bad(par.gate) || par.max_reject < 0 || par.max_reject > 64) return LSD_ERR_INVALID;
+    if ((addr(d_heads) | addr(d_edges) | addr(d_rep)) & 7) {
+        c->err = "pg prune: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_graphs == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_prune(n_graphs, d_heads, d_edges, edges_cap, par, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_relax(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_relax_rep* rep) {
+    return pg_relax_host(c, nodes, n_nodes, edges, n_edges, par, nullptr, rep, nullptr);
+}
+
+int lsd_pg_relax_robust(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_robust_par rob,
+                        lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep) {
+    if (!rob_rep || pg_robust_par_bad(rob)) return LSD_ERR_INVALID;
+    return pg_relax_host(c, nodes, n_nodes, edges, n_edges, par, &rob, rep, rob_rep);
 }
 
 int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_cand, int stride, const lsd_position* poses, lsd_pg_head* head,
@@ -164,3 +195,31 @@ int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_can
 }
 
 }  // extern "C"
+
+static int pg_relax_host(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par,
+                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep) {
+    if (!c || !rep || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
+        return LSD_ERR_INVALID;
+    if (pg_relax_par_bad(par)) return LSD_ERR_INVALID;
+    const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
+    const lsd_pg_head head{n_nodes, n_edges};
+    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; lsd_pg_robust_rep* d_rob = nullptr; uint8_t* d_ws;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) {                                        // (the plain entry stages what it always staged)
+        k(d_head, 1); k(d_no, nc); k(d_ed, ec); k(d_rep, 1); k(d_ws, pg_ws_bytes(nc, ec));
+        if (rob) k(d_rob, 1);
+    };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
+    if (n_nodes) HIPCHK(c, hipMemcpyAsync(d_no, nodes, n_nodes * sizeof(lsd_pg_node), hipMemcpyHostToDevice, c->stream));
+    if (n_edges) HIPCHK(c, hipMemcpyAsync(d_ed, edges, n_edges * sizeof(lsd_pg_edge), hipMemcpyHostToDevice, c->stream));
+    const int st = rob ? lsd_enqueue_pg_relax_robust_device(c, 1, d_head, d_no, nc, d_ed, ec, par, *rob, d_ws, d_rep, d_rob, c->stream)
+                       : lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    if (n_nodes) HIPCHK(c, hipMemcpyAsync(nodes, d_no, n_nodes * sizeof(lsd_pg_node), hipMemcpyDeviceToHost, c->stream));
+    if (n_edges) HIPCHK(c, hipMemcpyAsync(edges, d_ed, n_edges * sizeof(lsd_pg_edge), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
+    if (rob) HIPCHK(c, hipMemcpyAsync(rob_rep, d_rob, sizeof *rob_rep, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}

@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
-"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip), measured, with no threshold.  One JSON line each:
+"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip, csrc/k_pgprune.hip), measured, with no
+threshold.  One JSON line each:
 
   relax     lsd_enqueue_pg_relax_device on closed loops of 64 / 512 / 4096 nodes with one closure per 64 nodes, 1 and 64 graphs per launch:
             events around the launch from a warm context, the median, minimum and maximum of REPS launches.  The nodes are put back from a
             pristine copy in front of the first event, since the update is in place.  The report of graph 0 says what the time bought: outer
             iterations, CG steps, chi2 before and after.
+  robust    lsd_enqueue_pg_relax_robust_device on the same graphs and settings, Huber (delta 1) and Geman-McClure (delta 3) on the closures:
+            the same figures and the robust report of graph 0.
   close     one PoseGraph.close_device chain (near, clear, the store integrated at the selection, likelihood, match + response of one row,
             closure) on a 2048 x 2048 scratch grid, a loop of 64 keyframes of 360 beams in a square room of 160 cells: events around the call.
+  optimize  one PoseGraph.optimize_device chain (robust relaxation, prune, refit) on that graph of 65 keyframes after its closure, with a
+            false closure 10 -> 40 written into the edge tensor: events around the call, and what the three reports say.
 Usage: tools/pg_probe.py [--reps 20] > profiles/pg_probe.log"""
 import argparse, importlib, json, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,6 +61,18 @@ def main():
                                   outer=int(r["iters"]), cg_steps=int(r["cg_iters"]), accepted=int(r["accepted"]), flags=int(r["flags"]),
                                   chi2_before=float(r["chi2_before"]), chi2_after=float(r["chi2_after"]),
                                   us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1))), flush=True)
+            d_rr = torch.zeros(graphs * 24, dtype=torch.uint8, device="cuda")
+            for kernel, delta in (("huber", 1.0), ("gm", 3.0)):
+                rob = lsd.pg_robust(kernel=kernel, delta=delta)
+                fn = lambda: ctx.enqueue_pg_relax_robust_device(graphs, d_hd.data_ptr(), d_no.data_ptr(), len(nodes), d_ed.data_ptr(), len(edges),
+                                                                d_ws.data_ptr(), d_rp.data_ptr(), rob, d_rr.data_ptr(), par, s)
+                med, lo, hi = timed(fn, lambda: d_no.copy_(pristine))
+                r, rr = d_rp.cpu().numpy().view(lsd.PG_RELAX_REP_DTYPE)[0], d_rr.cpu().numpy().view(lsd.PG_ROBUST_REP_DTYPE)[0]
+                print(json.dumps(dict(what="robust", kernel=kernel, delta=delta, nodes=len(nodes), edges=len(edges), graphs=graphs, ms_median=med,
+                                      ms_min=lo, ms_max=hi, outer=int(r["iters"]), cg_steps=int(r["cg_iters"]), accepted=int(r["accepted"]),
+                                      flags=int(r["flags"]), cost_before=float(r["chi2_before"]), cost_after=float(r["chi2_after"]),
+                                      chi2_plain=float(rr["chi2_plain"]), downweighted=int(rr["downweighted"]), w_min=float(rr["w_min"]),
+                                      us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1))), flush=True)
 
     # 2. one close_device chain on a 2048 x 2048 scratch grid
     cols = rows = 2048
@@ -92,6 +109,25 @@ def main():
     print(json.dumps(dict(what="close", grid=[cols, rows], keyframes=int(graph.head()[0]), beams=n_beams, window=2, search=search, ms_median=med,
                           ms_min=lo, ms_max=hi, anchor=int(near["anchor"]), query=int(near["query"]), candidates=int(near["n_cand"]),
                           closure_flags=int(rep["flags"]))), flush=True)
+
+    # 3. one optimize_device chain on that graph: its closure stays, a false one 10 -> 40 is written behind it
+    n_nodes, n_edges = graph.head()
+    false = pg.edge(10, 40, tuple(v + o for v, o in zip(pg.rel(truth[10], truth[40]), (6.0, -5.0, 25.0))), (25.0, 0.0, 25.0, 0.0, 0.0, 9.0), lsd.PG_EDGE_CLOSURE)
+    graph._edges[n_edges:n_edges + 1].copy_(dev(np.array([false], lsd.PG_EDGE_DTYPE).view(np.uint8).reshape(1, -1)))
+    graph._head.copy_(dev(np.array([(n_nodes, n_edges + 1)], lsd.PG_HEAD_DTYPE).view(np.uint8).reshape(-1)))
+    pristine = graph._edges.clone(), graph._nodes.clone()
+
+    def restore2():
+        graph._edges.copy_(pristine[0]); graph._nodes.copy_(pristine[1])
+    relax = dict(iters=20, cg_iters=3 * n_nodes)
+    fn = lambda: graph.optimize_device(dict(kernel="huber", delta=1.0), 11.345, relax=relax)
+    med, lo, hi = timed(fn, restore2)
+    rr, pr, rf = graph.robust_report(), graph.prune_report(), graph.report()
+    print(json.dumps(dict(what="optimize", keyframes=n_nodes, edges=n_edges + 1, kernel="huber", delta=1.0, gate=11.345, relax=relax, ms_median=med,
+                          ms_min=lo, ms_max=hi, downweighted=int(rr["downweighted"]), w_min=float(rr["w_min"]), candidates=int(pr["candidates"]),
+                          rejected=int(pr["rejected"]), worst_edge=int(pr["worst_edge"]), worst_chi2=float(pr["worst_chi2"]),
+                          closures_left=int(pr["closures_left"]), refit_outer=int(rf["iters"]), refit_cg_steps=int(rf["cg_iters"]),
+                          refit_chi2=float(rf["chi2_after"]))), flush=True)
     ctx.close()
     return 0
 
