@@ -1181,7 +1181,62 @@ typedef struct lsd_pg_prune_rep { int32_t candidates, rejected, worst_edge, clos
 #define LSD_PG_EDGE_REJECTED 4u
 int lsd_enqueue_pg_prune_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_edge *d_edges, int edges_cap,
                                 lsd_pg_prune_par par, lsd_pg_prune_rep *d_rep, void *stream);
+/* Place recognition: loop candidates by the APPEARANCE of a keyframe's scan instead of its drifted pose, so that a loop is found when
+ * lsd_enqueue_pg_near_device's radius no longer reaches (csrc/k_pgplace.hip; restated in
+ * tests/pose_graph_place_cases.py).  One quantisation in fp64 without FMA, integers from there on.
+ * lsd_enqueue_pg_describe_device: one lsd_pg_desc per keyframe.  N = min(max(d_head->n_nodes, 0), nodes_cap), read on the device.  Every
+ * row k < N with d_desc[k].valid == 0 is described; a row with valid != 0 and every row >= N keep their bytes, so the launch needs no count
+ * from the host and may be repeated freely (a store of zeroed records is "nothing described yet").  Row k:
+ *   1. len = min(max(d_store_lens[k], 0), store_stride); the readings d_store[k * store_stride + 0..len-1]
+ *   2. a reading is USED iff range is finite, range > 0, range <= range_max and angle is finite (the integration's hit test)
+ *   3. its sector: t = angle / 6.283185307179586; f = t - floor(t); s = (int)(f * 64.0); s > 63 becomes 63 (f == 1.0 from a tiny negative
+ *      angle)
+ *   4. its value: q = (int)(range / range_max * 255.0); q > 254 becomes 254
+ *   5. per sector, in uint32: sum[s] += q, cnt[s] += 1 (no order: integers)
+ *   6. v[s] = cnt[s] ? sum[s] / cnt[s] : 255 (no return reads as "farther than range_max"); n_hits = the sum of cnt; n_sectors = the number
+ *      of sectors with cnt > 0; valid = 1
+ * One launch, one workgroup per row (a grid-stride over the rows), every row written by exactly one workgroup: no counter, no workspace.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; nodes_cap outside 1..16384; store_stride outside 1..the
+ * context's scan capacity; range_max not finite or not > 0; d_store not 16-byte, d_head or d_desc not 8-byte, d_store_lens not 4-byte
+ * aligned. */
+#define LSD_PG_DESC_SECTORS 64
+#define LSD_PG_PLACE_MAX 8
+typedef struct lsd_pg_desc { uint8_t v[LSD_PG_DESC_SECTORS]; uint32_t n_hits; uint16_t n_sectors, valid; } lsd_pg_desc;   /* 72 bytes */
+int lsd_enqueue_pg_describe_device(lsd_ctx *ctx, const lsd_pg_head *d_head, int nodes_cap, const lsd_polar *d_store,
+                                   const int *d_store_lens, int store_stride, double range_max, lsd_pg_desc *d_desc, void *stream);
+/* lsd_enqueue_pg_recognize_device: the places a query looks like.  The distance of a query a and a candidate c:
+ *   D_s = sum over k = 0..63 of |a.v[(k + s) mod 64] - c.v[k]|, s = 0..63;  dist = the smallest D_s;  shift = the smallest s that has it
+ * The query j = d_track->last and N (as above) are read on the device.  The query is USABLE iff j is in 0..N-1, d_desc[j].valid != 0 and
+ * d_desc[j].n_sectors >= min_sectors.  Node i is a CANDIDATE iff the query is usable, i <= j - gap, d_desc[i].valid != 0,
+ * d_desc[i].n_sectors >= min_sectors and dist_i <= max_dist; n_cand counts them.
+ *   d_work[i], i < N: (dist_i << 6) | shift_i of a candidate, 0xffffffff of every other node; d_work[i], i >= N, keeps its bytes.
+ *   Rounds r = 0..k-1: the candidate that is not suppressed with the smallest (dist, i) becomes d_recs[r] = (anchor, shift, dist, 0) and
+ *   suppresses every i' with |i' - anchor| <= spread for the later rounds; a round without a candidate writes (-1, 0, 0, 0).  n_picked is
+ *   the number of rounds filled.  d_rep = (query = j, n_cand, n_picked, 0).
+ *   With A = d_recs[pick].anchor the outputs d_near, d_sel, d_q_scan, d_q_len and d_q_pose are written exactly as
+ *   lsd_enqueue_pg_near_device writes them for the anchor A (its (a), (b), (c), every "no anchor" and "no query" case included), but
+ *   d_near->d2 = (double)dist (+0.0 without an anchor), d_near->n_cand = n_cand, and with A >= 0
+ *   d_q_pose = (x_A, y_A, wrap(ang_A - shift * 5.625)):  a direction at angle th in the anchor's frame is seen at th + shift * 5.625 degrees
+ *   in the query's, so the query's heading is the anchor's MINUS the shift.  The match that follows searches around the anchor's pose
+ *   turned that way, not around the query's drifted one.
+ * Two launches: one scores (many workgroups, a grid-stride over i, one lane per candidate, integers only), one of one workgroup does the
+ * rounds, the records, d_sel and the gather.  d_work: nodes_cap uint32 of the caller's.  No host wait, no allocation, no workgroup waits
+ * for another.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; nodes_cap outside 1..16384; store_stride
+ * outside 1..the context's scan capacity; gap < 1; window < 0 or spread < 0; k outside 1..LSD_PG_PLACE_MAX; pick outside 0..k-1; max_dist >
+ * 16320; min_sectors outside 1..64; d_store or d_q_scan not 16-byte, a record array or d_desc not 8-byte, d_store_lens, d_q_len or d_work
+ * not 4-byte aligned. */
+typedef struct lsd_pg_place_par { int32_t gap, window, spread, k, pick; uint32_t max_dist, min_sectors, reserved; } lsd_pg_place_par; /* 32 bytes */
+typedef struct lsd_pg_place_rec { int32_t anchor, shift; uint32_t dist, reserved; } lsd_pg_place_rec;   /* 16 bytes */
+typedef struct lsd_pg_place_rep { int32_t query, n_cand, n_picked, reserved; } lsd_pg_place_rep;        /* 16 bytes */
+int lsd_enqueue_pg_recognize_device(lsd_ctx *ctx, const lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap,
+                                    const lsd_pg_track *d_track, const lsd_polar *d_store, const int *d_store_lens, int store_stride,
+                                    const lsd_pg_desc *d_desc, lsd_pg_place_par par, uint32_t *d_work, lsd_pg_place_rec *d_recs,
+                                    lsd_pg_place_rep *d_rep, lsd_pg_near_rec *d_near, lsd_position *d_sel, lsd_polar *d_q_scan,
+                                    int *d_q_len, lsd_position *d_q_pose, void *stream);
 /* Host conveniences: host arrays of any alignment, staged through the context; blocking.
+ * lsd_pg_describe: n scans (scans[n * stride], lens[n]) -> desc_out[n], every row described; n outside 0..16384: LSD_ERR_INVALID.
+ * lsd_pg_recognize: desc[n_nodes] and a query index -> recs[par.k] and rep; no selection and no gather are written, par.window is
+ * checked and not used; n_nodes outside 1..16384: LSD_ERR_INVALID.
  * lsd_pg_relax: one graph; nodes[n_nodes] and edges[n_edges] are updated in place, rep receives the report.
  * lsd_pg_relax_robust: the same around lsd_enqueue_pg_relax_robust_device; rep and rob_rep receive the two reports.
  * lsd_pg_append: the graph (head, nodes[nodes_cap], edges[edges_cap], track, store, store_lens) makes the round trip around the device
@@ -1193,6 +1248,9 @@ int lsd_pg_relax_robust(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_ed
 int lsd_pg_append(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_cand, int stride, const lsd_position *poses,
                   lsd_pg_head *head, lsd_pg_node *nodes, int nodes_cap, lsd_pg_edge *edges, int edges_cap, lsd_pg_track *track_rec,
                   int32_t track, lsd_polar *store, int *store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep *rep);
+int lsd_pg_describe(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n, int stride, double range_max, lsd_pg_desc *desc_out);
+int lsd_pg_recognize(lsd_ctx *ctx, const lsd_pg_desc *desc, int n_nodes, int query, lsd_pg_place_par par, lsd_pg_place_rec *recs,
+                     lsd_pg_place_rep *rep);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

@@ -235,6 +235,19 @@ PG_EDGE_REJECTED = 4
 PG_KERNEL_NONE, PG_KERNEL_HUBER, PG_KERNEL_GM = 0, 1, 2
 PG_ROBUST_CLOSURES, PG_ROBUST_ALL = 0, 1
 PG_MAX_REJECT = 64
+# place recognition
+
+
+class lsd_pg_place(C.Structure):       # the C side's lsd_pg_place_par
+    _fields_ = [("gap", C.c_int32), ("window", C.c_int32), ("spread", C.c_int32), ("k", C.c_int32), ("pick", C.c_int32), ("max_dist", C.c_uint32),
+                ("min_sectors", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PG_DESC_SECTORS, PG_PLACE_MAX = 64, 8
+PG_DESC_DTYPE = np.dtype([("v", "u1", (PG_DESC_SECTORS,)), ("n_hits", "u4"), ("n_sectors", "u2"), ("valid", "u2")])
+PG_PLACE_REC_DTYPE = np.dtype([("anchor", "i4"), ("shift", "i4"), ("dist", "u4"), ("reserved", "u4")])
+PG_PLACE_REP_DTYPE = np.dtype([("query", "i4"), ("n_cand", "i4"), ("n_picked", "i4"), ("reserved", "i4")])
+assert (PG_DESC_DTYPE.itemsize, PG_PLACE_REC_DTYPE.itemsize, PG_PLACE_REP_DTYPE.itemsize, C.sizeof(lsd_pg_place)) == (72, 16, 16, 32)
 
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
@@ -363,6 +376,10 @@ _ABI = {
     "lsd_enqueue_pg_prune_device": (_i, [_vp, _i, _vp, _vp, _i, lsd_pg_prune, _vp, _vp]),
     "lsd_pg_relax_robust": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, _vp, _vp]),
     "lsd_pg_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp]),
+    "lsd_enqueue_pg_describe_device": (_i, [_vp, _vp, _i, _vp, _vp, _i, _dbl, _vp, _vp]),
+    "lsd_enqueue_pg_recognize_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, lsd_pg_place, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsd_pg_describe": (_i, [_vp, _vp, _vp, _i, _i, _dbl, _vp]),
+    "lsd_pg_recognize": (_i, [_vp, _vp, _i, _i, lsd_pg_place, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -929,6 +946,40 @@ class Context:
                                        no.ctypes.data, len(no), ed.ctypes.data, len(ed), tr.ctypes.data, int(track), st.ctypes.data, sl.ctypes.data,
                                        st.shape[1], pg_append(append), rep.ctypes.data))
         return hd[0], no, ed, tr[0], st, sl, rep[0]
+
+    def enqueue_pg_describe_device(self, d_head, nodes_cap, d_store, d_store_lens, store_stride, range_max, d_desc, stream=None):
+        """lsd_enqueue_pg_describe_device on raw device addresses: every keyframe below n_nodes whose record in d_desc (PG_DESC_DTYPE
+        [nodes_cap]) has valid == 0 gets its 64-sector descriptor; the others keep their bytes.  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_describe_device(self.h, d_head, int(nodes_cap), d_store, d_store_lens, int(store_stride), float(range_max),
+                                                               d_desc, stream))
+
+    def enqueue_pg_recognize_device(self, d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, d_desc, place, d_work, d_recs, d_rep,
+                                    d_near, d_sel, d_q_scan, d_q_len, d_q_pose, stream=None):
+        """lsd_enqueue_pg_recognize_device on raw device addresses: the track's last node scored against every old keyframe's descriptor at
+        every circular shift; the best distinct places into d_recs (PG_PLACE_REC_DTYPE [k]) and d_rep (PG_PLACE_REP_DTYPE); the place of
+        round `pick` leaves what enqueue_pg_near_device leaves, with the anchor's pose turned by the shift as the query's.  place:
+        pg_place(); d_work: nodes_cap uint32.  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_recognize_device(self.h, d_head, d_nodes, int(nodes_cap), d_track, d_store, d_store_lens, int(store_stride),
+                                                                d_desc, pg_place(place), d_work, d_recs, d_rep, d_near, d_sel, d_q_scan, d_q_len,
+                                                                d_q_pose, stream))
+
+    def pg_describe(self, scans, lens, range_max):
+        """lsd_pg_describe from host arrays: scans float64 [n, stride, 2], lens int32 [n] -> PG_DESC_DTYPE [n].  Blocking."""
+        sc, ln = np.ascontiguousarray(scans, np.float64), np.ascontiguousarray(lens, np.int32).reshape(-1)
+        if sc.ndim != 3 or sc.shape[0] != len(ln) or sc.shape[2] != 2:
+            raise LsdError(LSD_ERR_INVALID, "scans [n, stride, 2], lens [n]")
+        out = np.zeros(len(ln), PG_DESC_DTYPE)
+        self._chk(self.L.lsd_pg_describe(self.h, sc.ctypes.data if len(ln) else None, ln.ctypes.data if len(ln) else None, len(ln), sc.shape[1],
+                                         float(range_max), out.ctypes.data if len(ln) else None))
+        return out
+
+    def pg_recognize(self, desc, query, place=None):
+        """lsd_pg_recognize from host arrays: desc PG_DESC_DTYPE [n] and the query's index -> (records PG_PLACE_REC_DTYPE [k], report
+        PG_PLACE_REP_DTYPE); no selection and no gather.  place: pg_place().  Blocking."""
+        de, par = np.ascontiguousarray(desc, PG_DESC_DTYPE).reshape(-1), pg_place(place)
+        recs, rep = np.zeros(min(max(int(par.k), 1), PG_PLACE_MAX), PG_PLACE_REC_DTYPE), np.zeros(1, PG_PLACE_REP_DTYPE)
+        self._chk(self.L.lsd_pg_recognize(self.h, de.ctypes.data if len(de) else None, len(de), int(query), par, recs.ctypes.data, rep.ctypes.data))
+        return recs, rep[0]
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
@@ -1661,6 +1712,25 @@ def pg_robust(robust=None, kernel=None, delta=None, scope=None):
     return lsd_pg_robust(k, s, float(a["delta"]))
 
 
+PG_PLACE_DEFAULTS = dict(gap=10, window=2, spread=2, k=4, pick=0, max_dist=1024, min_sectors=16)
+
+
+def pg_place(place=None, gap=None, window=None, spread=None, k=None, pick=None, max_dist=None, min_sectors=None):
+    """An lsd_pg_place: place recognition's parameters -- a candidate is at least `gap` nodes older than the query, has at least
+    min_sectors sectors with a return and a descriptor distance of at most max_dist (0..16320: 64 sectors of 0..255); the k (1..8) best
+    are reported, each suppressing the nodes within `spread` of it; round `pick` is the place that is matched, with the nodes within
+    `window` of it drawn as its neighbourhood.  DESIGN.md 8.1.17."""
+    a = _pg_par(lsd_pg_place, place, PG_PLACE_DEFAULTS, dict(gap=gap, window=window, spread=spread, k=k, pick=pick, max_dist=max_dist,
+                                                             min_sectors=min_sectors))
+    if isinstance(a, lsd_pg_place):
+        return a
+    ints = [int(a[n]) for n in ("gap", "window", "spread", "k", "pick")]
+    us = [int(a[n]) for n in ("max_dist", "min_sectors")]
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in ints) or not all(0 <= v < 2 ** 32 for v in us):
+        raise LsdError(LSD_ERR_INVALID, "gap, window, spread, k and pick are int32, max_dist and min_sectors uint32")
+    return lsd_pg_place(*ints, *us, 0)
+
+
 def pg_workspace_bytes(nodes_cap, edges_cap):
     """lsd_pg_workspace_bytes: the workspace of ONE graph of the relaxation; 0 for caps outside 1..16384 / 1..65536."""
     return int(load_library().lsd_pg_workspace_bytes(int(nodes_cap), int(edges_cap)))
@@ -2227,7 +2297,9 @@ class PoseGraph:
     and the relaxation that redistributes the error; GridMapper.rerender_device(graph) then draws the grid again from the moved poses.
     The graph owns head, nodes, edges, tracks, the keyframe store and the workspace as torch tensors; the counts live on the device.
     optimize_device() makes the relaxation robust against closures that are confidently wrong and takes them out on the device (DESIGN.md
-    8.1.16).  Everything but nodes(), edges(), the *report() methods and disable_edges() is enqueued without waiting for the device."""
+    8.1.16); close_place_device() finds the anchor of a closure by the appearance of the scan where the drift has carried the pose out of
+    close_device()'s radius.  Everything but nodes(), edges(), place_records(), the *report() methods
+    and disable_edges() is enqueued without waiting for the device."""
 
     def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
         import torch
@@ -2251,6 +2323,10 @@ class PoseGraph:
         self._robust_rep, self._prune_rep = z(PG_ROBUST_REP_DTYPE.itemsize), z(PG_PRUNE_REP_DTYPE.itemsize)
         self._sel = z(self.nodes_cap, 3, dtype=torch.float64)
         self._q_scan, self._q_len, self._q_pose = z(1, self.n_beams, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(1, 3, dtype=torch.float64)
+        # place recognition: zeroed descriptors are "not described yet"
+        self._desc, self._place_work = z(self.nodes_cap, PG_DESC_DTYPE.itemsize), z(self.nodes_cap, dtype=torch.int32)
+        self._place_recs, self._place_rep = z(PG_PLACE_MAX, PG_PLACE_REC_DTYPE.itemsize), z(PG_PLACE_REP_DTYPE.itemsize)
+        self._desc_range_max = None
 
     def _track(self, track):
         t = int(track)
@@ -2300,6 +2376,11 @@ class PoseGraph:
             raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
         ts = _cuda_stream(stream)
         self.near_device(track, gap, radius, window, ts)
+        return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+
+    def _close_tail(self, scratch_mapper, search, response, smear, closure, ts):
+        """What follows the choice of an anchor, by pose (near_device) or by appearance (recognize_device): the neighbourhood drawn from
+        the selection, the gathered row matched on it with its response, the closure edge."""
         scratch_mapper.clear(ts)
         scratch_mapper._enqueue(self.ctx, self._store.data_ptr(), self._store_lens.data_ptr(), self.nodes_cap, self.n_beams, self._sel.data_ptr(), 24,
                                 ts.cuda_stream)
@@ -2310,6 +2391,42 @@ class PoseGraph:
                                            self._near.data_ptr(), resp.data_ptr(), closure, self._closure_rep.data_ptr(), ts.cuda_stream)
         self._held_close = (rec, resp)                                       # the launches read them: alive until the next call
         return resp
+
+    def describe_device(self, range_max, stream=None):
+        """The descriptors (lsd_enqueue_pg_describe_device) of the keyframes that have none yet; the count is read on the device, so this
+        may be called after every append.  A descriptor depends on range_max: a graph keeps the first one and refuses another.  On
+        `stream`; nothing waits."""
+        rm = float(range_max)
+        if self._desc_range_max is not None and rm != self._desc_range_max:
+            raise LsdError(LSD_ERR_INVALID, "this graph's descriptors were made with range_max %r" % self._desc_range_max)
+        self.ctx.enqueue_pg_describe_device(self._head.data_ptr(), self.nodes_cap, self._store.data_ptr(), self._store_lens.data_ptr(), self.n_beams, rm,
+                                            self._desc.data_ptr(), _cuda_stream(stream).cuda_stream)
+        self._desc_range_max = rm
+
+    def recognize_device(self, range_max, track=0, place=None, stream=None):
+        """The loop candidate of the track's last node by the appearance of its scan (describe_device, then
+        lsd_enqueue_pg_recognize_device), into the graph's own near record, selection and one-row batch -- what near_device leaves, with
+        the anchor's pose turned by the descriptors' shift as the query's pose.  place: pg_place().  place_records() and place_report()
+        say what was found.  On `stream`; nothing waits."""
+        _, d_track = self._track(track)
+        ts = _cuda_stream(stream)
+        par = pg_place(place)
+        self.describe_device(range_max, ts)
+        self.ctx.enqueue_pg_recognize_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, self._store.data_ptr(),
+                                             self._store_lens.data_ptr(), self.n_beams, self._desc.data_ptr(), par, self._place_work.data_ptr(),
+                                             self._place_recs.data_ptr(), self._place_rep.data_ptr(), self._near.data_ptr(), self._sel.data_ptr(),
+                                             self._q_scan.data_ptr(), self._q_len.data_ptr(), self._q_pose.data_ptr(), ts.cuda_stream)
+        self._place_k = int(par.k)
+
+    def close_place_device(self, scratch_mapper, track=0, place=None, search=None, response=None, smear=None, closure=None, stream=None):
+        """close_device with the anchor found by recognize_device instead of near_device: a loop that odometry has NOT almost closed.
+        range_max is the scratch mapper's.  Returns the response record of the query; closure_report(), place_report() and
+        place_records() say what came of it.  Nothing waits."""
+        if not isinstance(scratch_mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        ts = _cuda_stream(stream)
+        self.recognize_device(scratch_mapper.range_max, track, place, ts)
+        return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
 
     def relax_device(self, relax=None, stream=None, robust=None, **kw):
         """The relaxation (lsd_enqueue_pg_relax_device) of this graph: relax is pg_relax(), or its keywords (iters=, cg_iters=, cg_tol=,
@@ -2381,6 +2498,14 @@ class PoseGraph:
     def closure_report(self):
         """(the near record PG_NEAR_DTYPE, the closure report PG_CLOSURE_REP_DTYPE) of the last close_device: a read-back."""
         return self._read(self._near, PG_NEAR_DTYPE)[0], self._read(self._closure_rep, PG_CLOSURE_REP_DTYPE)[0]
+
+    def place_report(self):
+        """The last recognize_device's report (PG_PLACE_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._place_rep, PG_PLACE_REP_DTYPE)[0]
+
+    def place_records(self):
+        """The last recognize_device's places (PG_PLACE_REC_DTYPE [k], anchor -1 in a round that found none): a read-back."""
+        return self._read(self._place_recs, PG_PLACE_REC_DTYPE)[:getattr(self, "_place_k", PG_PLACE_MAX)]
 
     def append_report(self):
         """The last append's report (PG_APPEND_REP_DTYPE): a read-back, which waits for the device."""

@@ -275,6 +275,14 @@ void launch_pg_relax_robust(int n_graphs, const lsd_pg_head* heads, lsd_pg_node*
                             lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, hipStream_t s);
 void launch_pg_prune(int n_graphs, const lsd_pg_head* heads, lsd_pg_edge* edges, int edges_cap, lsd_pg_prune_par par, lsd_pg_prune_rep* rep,
                      hipStream_t s);
+// place recognition (k_pgplace.hip): the descriptors of the rows that have none; and score + pick (near_rec == nullptr: the records and
+// the report only -- nodes, store, store_lens, sel, q_scan, q_len and q_pose are not read or written then)
+void launch_pg_describe(const lsd_pg_head* head, int nodes_cap, const lsd_polar* store, const int* store_lens, int store_stride, double range_max,
+                        lsd_pg_desc* desc, hipStream_t s);
+void launch_pg_recognize(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track, const lsd_polar* store,
+                         const int* store_lens, int store_stride, const lsd_pg_desc* desc, lsd_pg_place_par par, uint32_t* work,
+                         lsd_pg_place_rec* recs, lsd_pg_place_rep* rep, lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len,
+                         lsd_position* q_pose, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

@@ -1,6 +1,6 @@
 // lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the six device entries
-// (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures) and
-// the three host conveniences, staged through the context's carver as every other host entry.
+// (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures), of
+// place recognition's two (k_pgplace.hip) and the host conveniences, staged through the context's carver as every other host entry.
 #include <math.h>
 #include <stddef.h>
 
@@ -20,6 +20,8 @@ static_assert(sizeof(lsd_pg_relax_par) == 56 && offsetof(lsd_pg_relax_par, iters
 static_assert(sizeof(lsd_pg_robust_par) == 16 && offsetof(lsd_pg_robust_par, delta) == 8 && sizeof(lsd_pg_robust_rep) == 24 &&
               offsetof(lsd_pg_robust_rep, downweighted) == 16 && sizeof(lsd_pg_prune_par) == 16 && offsetof(lsd_pg_prune_par, max_reject) == 8 &&
               sizeof(lsd_pg_prune_rep) == 24 && offsetof(lsd_pg_prune_rep, worst_chi2) == 16, "the robust relaxation's and the prune's records");
+static_assert(sizeof(lsd_pg_desc) == 72 && sizeof(lsd_pg_place_par) == 32 && offsetof(lsd_pg_place_par, max_dist) == 20 && sizeof(lsd_pg_place_rec) == 16 &&
+              offsetof(lsd_pg_place_rec, dist) == 8 && sizeof(lsd_pg_place_rep) == 16, "place recognition's records");
 
 constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
 
@@ -41,6 +43,11 @@ static bool pg_relax_par_bad(const lsd_pg_relax_par& p) {
 static bool pg_robust_par_bad(const lsd_pg_robust_par& r) {
     if (r.kernel < LSD_PG_KERNEL_NONE || r.kernel > LSD_PG_KERNEL_GM || r.scope > LSD_PG_ROBUST_ALL) return true;
     return r.kernel != LSD_PG_KERNEL_NONE && !(std::isfinite(r.delta) && r.delta > 0);
+}
+
+static bool pg_place_par_bad(const lsd_pg_place_par& p) {
+    return p.gap < 1 || p.window < 0 || p.spread < 0 || p.k < 1 || p.k > LSD_PG_PLACE_MAX || p.pick < 0 || p.pick >= p.k || p.max_dist > 16320u ||
+           p.min_sectors < 1 || p.min_sectors > (uint32_t)LSD_PG_DESC_SECTORS;
 }
 
 // the two host relaxations: one graph around the device entry, rob == nullptr for the plain one
@@ -149,6 +156,87 @@ int lsd_enqueue_pg_prune_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_h
         launch_pg_prune(n_graphs, d_heads, d_edges, edges_cap, par, d_rep, s);
         return LSD_OK;
     });
+}
+
+int lsd_enqueue_pg_describe_device(lsd_ctx* c, const lsd_pg_head* d_head, int nodes_cap, const lsd_polar* d_store, const int* d_store_lens,
+                                   int store_stride, double range_max, lsd_pg_desc* d_desc, void* stream) {
+    if (!c || !d_head || !d_store || !d_store_lens || !d_desc) return LSD_ERR_INVALID;
+    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || !(std::isfinite(range_max) && range_max > 0))
+        return LSD_ERR_INVALID;
+    if ((addr(d_store) & 15) || ((addr(d_head) | addr(d_desc)) & 7) || (addr(d_store_lens) & 3)) {
+        c->err = "pg describe: store 16-byte, head and descriptors 8-byte, the lengths 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_describe(d_head, nodes_cap, d_store, d_store_lens, store_stride, range_max, d_desc, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_recognize_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, const lsd_pg_track* d_track,
+                                    const lsd_polar* d_store, const int* d_store_lens, int store_stride, const lsd_pg_desc* d_desc,
+                                    lsd_pg_place_par par, uint32_t* d_work, lsd_pg_place_rec* d_recs, lsd_pg_place_rep* d_rep, lsd_pg_near_rec* d_near,
+                                    lsd_position* d_sel, lsd_polar* d_q_scan, int* d_q_len, lsd_position* d_q_pose, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || !d_desc || !d_work || !d_recs || !d_rep || !d_near || !d_sel || !d_q_scan ||
+        !d_q_len || !d_q_pose)
+        return LSD_ERR_INVALID;
+    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || pg_place_par_bad(par)) return LSD_ERR_INVALID;
+    if (((addr(d_store) | addr(d_q_scan)) & 15) ||
+        ((addr(d_head) | addr(d_nodes) | addr(d_track) | addr(d_desc) | addr(d_recs) | addr(d_rep) | addr(d_near) | addr(d_sel) | addr(d_q_pose)) & 7) ||
+        ((addr(d_store_lens) | addr(d_q_len) | addr(d_work)) & 3)) {
+        c->err = "pg recognize: store and d_q_scan 16-byte, the records and descriptors 8-byte, the lengths and d_work 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_recognize(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, d_desc, par, d_work, d_recs, d_rep, d_near, d_sel,
+                            d_q_scan, d_q_len, d_q_pose, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_describe(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n, int stride, double range_max, lsd_pg_desc* desc_out) {
+    if (!c || n < 0 || n > kPgMaxNodes || stride <= 0 || stride > c->scan_cap || !(std::isfinite(range_max) && range_max > 0)) return LSD_ERR_INVALID;
+    if (n == 0) return LSD_OK;
+    if (!scans || !lens || !desc_out) return LSD_ERR_INVALID;
+    const size_t nn = (size_t)n;
+    const lsd_pg_head head{n, 0};
+    lsd_pg_head* d_head; lsd_polar* d_sc; int* d_len; lsd_pg_desc* d_desc;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) { k(d_sc, nn * stride); k(d_head, 1); k(d_desc, nn); k(d_len, nn); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_sc, scans, nn * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, lens, nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_desc, 0, nn * sizeof(lsd_pg_desc), c->stream));      // (valid == 0: every row is described)
+    const int st = lsd_enqueue_pg_describe_device(c, d_head, n, d_sc, d_len, stride, range_max, d_desc, c->stream);
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(desc_out, d_desc, nn * sizeof(lsd_pg_desc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
+}
+
+int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query, lsd_pg_place_par par, lsd_pg_place_rec* recs, lsd_pg_place_rep* rep) {
+    if (!c || !desc || !recs || !rep || n_nodes < 1 || n_nodes > kPgMaxNodes || pg_place_par_bad(par)) return LSD_ERR_INVALID;
+    const size_t nn = (size_t)n_nodes;
+    const lsd_pg_head head{n_nodes, 0};
+    const lsd_pg_track track{query, 0, {0.0, 0.0, 0.0}};
+    lsd_pg_head* d_head; lsd_pg_track* d_tr; lsd_pg_desc* d_desc; uint32_t* d_work; lsd_pg_place_rec* d_recs; lsd_pg_place_rep* d_rep;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto regions = [&](Carver& k) { k(d_head, 1); k(d_tr, 1); k(d_desc, nn); k(d_recs, par.k); k(d_rep, 1); k(d_work, nn); };
+    HIPCHK(c, carve(c->stage, regions));
+    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tr, &track, sizeof track, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_desc, desc, nn * sizeof(lsd_pg_desc), hipMemcpyHostToDevice, c->stream));
+    const int st = enqueue_on(c, c->stream, [&](hipStream_t s) {
+        launch_pg_recognize(d_head, nullptr, n_nodes, d_tr, nullptr, nullptr, 1, d_desc, par, d_work, d_recs, d_rep, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, s);
+        return LSD_OK;
+    });
+    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
+    HIPCHK(c, hipMemcpyAsync(recs, d_recs, par.k * sizeof(lsd_pg_place_rec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LSD_OK;
 }
 
 int lsd_pg_relax(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_relax_rep* rep) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip, csrc/k_pgprune.hip), measured, with no
-threshold.  One JSON line each:
+"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip, csrc/k_pgprune.hip, csrc/k_pgplace.hip; DESIGN.md 8.1.15, 8.1.16,
+8.1.17), measured, with no threshold.  One JSON line each:
 
   relax     lsd_enqueue_pg_relax_device on closed loops of 64 / 512 / 4096 nodes with one closure per 64 nodes, 1 and 64 graphs per launch:
             events around the launch from a warm context, the median, minimum and maximum of REPS launches.  The nodes are put back from a
@@ -12,7 +12,13 @@ threshold.  One JSON line each:
             closure) on a 2048 x 2048 scratch grid, a loop of 64 keyframes of 360 beams in a square room of 160 cells: events around the call.
   optimize  one PoseGraph.optimize_device chain (robust relaxation, prune, refit) on that graph of 65 keyframes after its closure, with a
             false closure 10 -> 40 written into the edge tensor: events around the call, and what the three reports say.
-Usage: tools/pg_probe.py [--reps 20] > profiles/pg_probe.log"""
+  describe  lsd_enqueue_pg_describe_device on a store of 64 / 4096 / 16384 keyframes of 360 readings: the whole store (every record's valid
+            word cleared in front of the first event) and one new row (the last record's alone).
+  recognize lsd_enqueue_pg_recognize_device (score + pick) for the last node of the same stores, and lsd_enqueue_pg_near_device on the same
+            graphs next to it: events around the launches.
+  close_place  one PoseGraph.close_place_device chain (describe, recognize, then close_device's tail) on the graph and the scratch grid of
+            `close`.
+Usage: tools/pg_probe.py [--reps 20] [--only relax,close,optimize,place] > profiles/pg_probe.log"""
 import argparse, importlib, json, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,7 +28,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--only", default="relax,close,optimize,place", help="the sections to run, comma separated")
     args = ap.parse_args()
+    only = set(args.only.split(","))
     import numpy as np
     import torch
     import pose_graph_cases as pg
@@ -42,7 +50,7 @@ def main():
 
     # 1. the relaxation
     par = dict(pg.RELAX_DEFAULTS, iters=10, cg_iters=300, cg_tol=1e-6, eps=1e-6)
-    for n in (64, 512, 4096):
+    for n in (64, 512, 4096) if "relax" in only else ():
         nodes, edges, _ = pg.loop_graph(n, np.random.default_rng(n), radius=n / 4.0, bias=0.3 * 64 / n, closures=n // 64)
         for graphs in (1, 64):
             heads = np.zeros(graphs, lsd.PG_HEAD_DTYPE)
@@ -74,7 +82,42 @@ def main():
                                       chi2_plain=float(rr["chi2_plain"]), downweighted=int(rr["downweighted"]), w_min=float(rr["w_min"]),
                                       us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1))), flush=True)
 
-    # 2. one close_device chain on a 2048 x 2048 scratch grid
+    # 2. place recognition: describe, recognize and near on stores of 360 readings
+    for n in (64, 4096, 16384) if "place" in only else ():
+        rng = np.random.default_rng(n)
+        nodes = np.zeros(n, lsd.PG_NODE_DTYPE)
+        nodes["x"], nodes["y"], nodes["ang"] = rng.uniform(0, 2000, n), rng.uniform(0, 2000, n), rng.uniform(-180, 180, n)
+        nodes["x"][n - 1], nodes["y"][n - 1] = nodes["x"][n // 4] + 1.0, nodes["y"][n // 4]      # near has a candidate as well
+        store = np.stack([rng.uniform(0.5, 30.0, (n, 360)), np.tile(-math.pi + 2 * math.pi * (np.arange(360) + 0.5) / 360, (n, 1))], axis=2)
+        store[n // 4, :, 0] = np.roll(store[n - 1, :, 0], 45)                      # the query's scan an eighth of a turn earlier
+        head, track = np.array([(n, 0)], lsd.PG_HEAD_DTYPE), np.array([(n - 1, 0, (0.0, 0.0, 0.0))], lsd.PG_TRACK_DTYPE)
+        d_hd, d_no, d_tr, d_st, d_ln = dev(head.view(np.uint8)), dev(nodes.view(np.uint8)), dev(track.view(np.uint8)), dev(store), dev(np.full(n, 360, np.int32))
+        z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")
+        d_desc, d_work, d_recs, d_rep, d_near, d_sel = z(n, 72), z(n, dtype=torch.int32), z(8, 16), z(16), z(24), z(n, 3, dtype=torch.float64)
+        d_row, d_len, d_pose = z(360, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(3, dtype=torch.float64)
+        valid = d_desc.view(torch.int16)[:, 35]                                  # (valid: bytes 70..71 of a record)
+        fn = lambda: ctx.enqueue_pg_describe_device(d_hd.data_ptr(), n, d_st.data_ptr(), d_ln.data_ptr(), 360, 30.0, d_desc.data_ptr(), s)
+        for what, before in (("describe_all", lambda: valid.zero_()), ("describe_one", lambda: valid[n - 1:].zero_())):
+            med, lo, hi = timed(fn, before)
+            print(json.dumps(dict(what=what, nodes=n, readings=360, ms_median=med, ms_min=lo, ms_max=hi)), flush=True)
+        place = lsd.pg_place(gap=min(10, n // 2), window=2, spread=2, k=4, pick=0, max_dist=2000, min_sectors=32)
+        fn = lambda: ctx.enqueue_pg_recognize_device(d_hd.data_ptr(), d_no.data_ptr(), n, d_tr.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), 360,
+                                                     d_desc.data_ptr(), place, d_work.data_ptr(), d_recs.data_ptr(), d_rep.data_ptr(), d_near.data_ptr(),
+                                                     d_sel.data_ptr(), d_row.data_ptr(), d_len.data_ptr(), d_pose.data_ptr(), s)
+        med, lo, hi = timed(fn)
+        rec, rep = d_recs.cpu().numpy().reshape(-1).view(lsd.PG_PLACE_REC_DTYPE)[0], d_rep.cpu().numpy().view(lsd.PG_PLACE_REP_DTYPE)[0]
+        print(json.dumps(dict(what="recognize", nodes=n, ms_median=med, ms_min=lo, ms_max=hi, anchor=int(rec["anchor"]), shift=int(rec["shift"]),
+                              dist=int(rec["dist"]), candidates=int(rep["n_cand"]), planted=n // 4)), flush=True)
+        fn = lambda: ctx.enqueue_pg_near_device(d_hd.data_ptr(), d_no.data_ptr(), n, d_tr.data_ptr(), d_st.data_ptr(), d_ln.data_ptr(), 360, min(10, n // 2),
+                                                10.0, 2, d_near.data_ptr(), d_sel.data_ptr(), d_row.data_ptr(), d_len.data_ptr(), d_pose.data_ptr(), s)
+        med, lo, hi = timed(fn)
+        nr = d_near.cpu().numpy().view(lsd.PG_NEAR_DTYPE)[0]
+        print(json.dumps(dict(what="near", nodes=n, ms_median=med, ms_min=lo, ms_max=hi, anchor=int(nr["anchor"]), candidates=int(nr["n_cand"]))), flush=True)
+    if not only & {"close", "optimize", "place"}:
+        ctx.close()
+        return 0
+
+    # 3. one close_device chain on a 2048 x 2048 scratch grid
     cols = rows = 2048
     resol, range_max, n_key, n_beams = 0.05, 60.0, 64, 360
     lo_w, hi_w = 944.0, 1104.0                                                  # the room's walls, in cells
@@ -104,13 +147,29 @@ def main():
     def restore():
         graph._edges.copy_(pristine[0]); graph._head.copy_(pristine[1])
     fn = lambda: graph.close_device(scratch, gap=n_key // 2, radius=10.0, window=2, search=search, response=dict(rx=2, ry=2, ra=1))
+    if "place" in only:
+        place = dict(gap=n_key // 2, window=2, spread=2, k=4, pick=0, max_dist=2000, min_sectors=32)
+        fp = lambda: graph.close_place_device(scratch, place=place, search=search, response=dict(rx=2, ry=2, ra=1))
+        med, lo, hi = timed(fp, restore)
+        near, rep = graph.closure_report()
+        rec = graph.place_records()[0]
+        print(json.dumps(dict(what="close_place", grid=[cols, rows], keyframes=int(graph.head()[0]), beams=n_beams, place=place, search=search,
+                              ms_median=med, ms_min=lo, ms_max=hi, anchor=int(near["anchor"]), shift=int(rec["shift"]), dist=int(rec["dist"]),
+                              query=int(near["query"]), candidates=int(near["n_cand"]), closure_flags=int(rep["flags"]))), flush=True)
+        restore()
+    if not only & {"close", "optimize"}:
+        ctx.close()
+        return 0
     med, lo, hi = timed(fn, restore)
     near, rep = graph.closure_report()
     print(json.dumps(dict(what="close", grid=[cols, rows], keyframes=int(graph.head()[0]), beams=n_beams, window=2, search=search, ms_median=med,
                           ms_min=lo, ms_max=hi, anchor=int(near["anchor"]), query=int(near["query"]), candidates=int(near["n_cand"]),
                           closure_flags=int(rep["flags"]))), flush=True)
 
-    # 3. one optimize_device chain on that graph: its closure stays, a false one 10 -> 40 is written behind it
+    # 4. one optimize_device chain on that graph: its closure stays, a false one 10 -> 40 is written behind it
+    if "optimize" not in only:
+        ctx.close()
+        return 0
     n_nodes, n_edges = graph.head()
     false = pg.edge(10, 40, tuple(v + o for v, o in zip(pg.rel(truth[10], truth[40]), (6.0, -5.0, 25.0))), (25.0, 0.0, 25.0, 0.0, 0.0, 9.0), lsd.PG_EDGE_CLOSURE)
     graph._edges[n_edges:n_edges + 1].copy_(dev(np.array([false], lsd.PG_EDGE_DTYPE).view(np.uint8).reshape(1, -1)))
