@@ -1,6 +1,6 @@
 // fa_relocate_host.h -- the host side of the relocalisation entries (lsd_enqueue_fa_lost_gather_device, lsd_enqueue_fa_carry_seed_device
 // and their host conveniences; include/lsd_hip.h) that needs no device: the argument checks and the element counts of the staging
-// regions.  Plain C++, no HIP: lsd_ctx.hip uses it, and tests/fa_relocate_host.cpp drives it under the host sanitizers.
+// regions.  Plain C++, no HIP: lsd_loc.hip uses it, and tests/fa_relocate_host.cpp drives it under the host sanitizers.
 #pragma once
 #include <cmath>
 #include <cstddef>

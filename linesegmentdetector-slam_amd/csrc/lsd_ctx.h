@@ -1,7 +1,8 @@
-// lsd_ctx.h -- the context of liblsdhip.so as the host files see it (lsd_ctx.hip: the detector, the map cache, FeatureScan and
-// FeatureAssociation; lsd_grid.hip: the grid stack; lsd_dist.hip: the hand-off between GPUs): the struct, the status macro and the tail
-// every enqueue entry ends with.  Nothing here depends on LSD_DEVELOPER_KNOBS: the developer build's lsd_ctx_dev.o and every other
-// object have to agree on the struct's layout.
+// lsd_ctx.h -- the context of liblsdhip.so as the host files see it (lsd_ctx.hip: the context, the detector, the map cache and the map
+// update; lsd_loc.hip: localisation -- scan matching, FeatureScan, FeatureAssociation, the carries and the replay loop; lsd_grid.hip: the
+// grid stack; lsd_pg.hip: the pose graph; lsd_dist.hip: the hand-off between GPUs): the struct, the status macro, the tail every enqueue
+// entry ends with and the round trip through the staging arena every host convenience makes.  Nothing here depends on
+// LSD_DEVELOPER_KNOBS: the developer build's lsd_ctx_dev.o and every other object have to agree on the struct's layout.
 #pragma once
 #include <string>
 #include <vector>
@@ -146,5 +147,50 @@ int enqueue_on(lsd_ctx* c, void* stream, Launch&& launch) {
     if (st != LSD_OK) return st;
     HIPCHK(c, hipGetLastError());
     c->last_stream = s;
+    return LSD_OK;
+}
+
+// One pass over the staged regions of a host convenience (stage_round_trip below): each region is named once -- its device pointer, the
+// host array it mirrors, the element count -- by the way it travels: in, out, both, or scratch, which only the device uses.
+class StagePass {
+public:
+    enum What { kCarve = 0, kUp = 1, kDown = 2 };
+    StagePass(What what, Carver* carver, hipStream_t s) : what_(what), carver_(carver), s_(s) {}
+    template <class T> void in(T*& d, const T* h, size_t n) { region(d, const_cast<T*>(h), n, kUp); }
+    template <class T> void out(T*& d, T* h, size_t n) { region(d, h, n, kDown); }
+    template <class T> void both(T*& d, T* h, size_t n) { region(d, h, n, kUp | kDown); }
+    template <class T> void scratch(T*& d, size_t n) { region(d, static_cast<T*>(nullptr), n, 0); }
+    hipError_t status = hipSuccess;   // of the pass's copies: nothing is queued behind one that failed
+
+private:
+    template <class T> void region(T*& d, T* h, size_t n, int travels) {
+        if (what_ == kCarve) (*carver_)(d, n);
+        else if ((travels & what_) && h && n && status == hipSuccess)
+            status = what_ == kUp ? hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s_)
+                                  : hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, s_);
+    }
+    What what_;
+    Carver* carver_;
+    hipStream_t s_;
+};
+
+// What a host convenience does once it has accepted its arguments: one round trip through c->stage.  `plan(k)` names the regions
+// (StagePass); they are carved in that order (lsd_devbuf.h: carve), the uploads queued on c->stream, `body()` run -- the device entry on
+// the staged pointers and whatever else the convenience queues with it, on c->stream -- the downloads queued behind it and the stream
+// drained.  A region whose host pointer is null or whose count is 0 is carved and not copied.  From the first upload on nothing returns
+// before the stream is drained, whether HIP failed or the body refused: the uploads still read the caller's arrays.
+template <class Plan, class Body>
+int stage_round_trip(lsd_ctx* c, Plan&& plan, Body&& body) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, carve(c->stage, [&](Carver& k) { StagePass place(StagePass::kCarve, &k, nullptr); plan(place); }));
+    StagePass up(StagePass::kUp, nullptr, c->stream), down(StagePass::kDown, nullptr, c->stream);
+    plan(up);
+    const int st = up.status == hipSuccess ? body() : LSD_OK;
+    if (up.status == hipSuccess && st == LSD_OK) plan(down);
+    const hipError_t drained = hipStreamSynchronize(c->stream);
+    HIPCHK(c, up.status);
+    if (st != LSD_OK) return st;
+    HIPCHK(c, down.status);
+    HIPCHK(c, drained);
     return LSD_OK;
 }

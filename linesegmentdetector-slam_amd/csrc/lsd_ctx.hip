@@ -1,5 +1,6 @@
 // lsd_ctx.hip -- host side of liblsdhip.so: context, HBM workspace, host-computed tables, launch
-// sequencing and the C ABI declared in include/lsd_hip.h.
+// sequencing and the detector's, the map cache's and the map update's part of the C ABI declared in
+// include/lsd_hip.h (localisation: lsd_loc.hip; the grid stack: lsd_grid.hip; the pose graph: lsd_pg.hip).
 //
 // Everything numerical on the hot path runs in the HIP kernels (k_*.hip).  The host computes only
 // what the reference also computes once per call on scalars: the Gaussian taps (myLSD.cpp:398-417),
@@ -17,7 +18,6 @@
 #include <vector>
 
 #include "lsd_ctx.h"
-#include "fa_relocate_host.h"
 #include "k1_lds.h"
 #include "k_rdp_lds.h"
 
@@ -508,8 +508,9 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     if (st != LSD_OK) return st;
     const bool fused = use_front(c, g);
     if (!fused) HIPCHK(c, prepare_gauss(g));
-    // the workspace is shared by every enqueue of this context: work queued on another stream must be over first
-    if (c->done_valid && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
+    // the workspace is shared by every detector run of this context: one queued on another stream (done_stream: where ev_done was recorded)
+    // must be over first
+    if (c->done_valid && c->done_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_done, 0));
 
     Workspace& w = c->ws;
     Buffers b{};
@@ -964,649 +965,6 @@ int lsd_enqueue_map_update_device(lsd_ctx* c, const int8_t* d_grid, int cols, in
     st = lsd_enqueue_map_cache_device(c, d_map, 1, cols, rows, res, z_occ_max_dis, d_map_cache, s);        // :130, before the detector rewrites the map
     if (st != LSD_OK) return st;
     return lsd_enqueue_batch_device(c, d_map, 1, cols, rows, p, LSD_FLAG_WRITEBACK_MAP, d_line_im, d_lines, max_lines, d_count, s);   // :132
-}
-
-int lsd_enqueue_scan_to_map_match_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
-                                         const lsd_line* d_scan_lines, const lsd_position* d_pts, int n_points,
-                                         lsd_position lidar, lsd_position last, const int* d_pairs, int n_pairs,
-                                         double z_occ_max_dis, double max_esti_dist, lsd_match_score* d_out, void* stream) {
-    if (!c || !d_map_cache || !d_map_lines || !d_scan_lines || !d_pairs || !d_out || cols <= 0 || rows <= 0 || n_pairs <= 0 ||
-        n_points < 0 || (n_points > 0 && !d_pts))
-        return LSD_ERR_INVALID;
-    if (n_pairs > (1 << 28)) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
-    launch_match(d_map_cache, cols, rows, d_map_lines, d_scan_lines, reinterpret_cast<const double*>(d_pts), n_points, lidar.x,
-                 lidar.y, last.x, last.y, d_pairs, n_pairs, z_occ_max_dis, max_esti_dist, reinterpret_cast<double*>(d_out), s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_scan_to_map_match(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map,
-                          const lsd_line* scan_lines, int n_scan, const lsd_position* pts, int n_points, lsd_position lidar,
-                          lsd_position last, const int* pairs, int n_pairs, double z_occ_max_dis, double max_esti_dist,
-                          lsd_match_score* out) {
-    if (!c || !map_cache || !map_lines || !scan_lines || !pairs || !out || cols <= 0 || rows <= 0 || n_map <= 0 || n_scan <= 0 ||
-        n_pairs <= 0 || n_points < 0 || (n_points > 0 && !pts))
-        return LSD_ERR_INVALID;
-    for (int p = 0; p < n_pairs; p++)
-        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_map || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_scan) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n_mc = (size_t)cols * rows, n_pr = (size_t)n_pairs * 2, n_out = (size_t)n_pairs * 4;
-    double* d_mc; lsd_line *d_ml, *d_sl; lsd_position* d_pt; int* d_pr; lsd_match_score* d_out;
-    auto regions = [&](Carver& k) { k(d_mc, n_mc); k(d_ml, n_map); k(d_sl, n_scan); k(d_pt, n_points); k(d_pr, n_pr); k(d_out, n_out); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sl, scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, c->stream));
-    if (n_points > 0) HIPCHK(c, hipMemcpyAsync(d_pt, pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_pr, pairs, n_pr * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_scan_to_map_match_device(c, d_mc, cols, rows, d_ml, d_sl, d_pt, n_points, lidar, last, d_pr, n_pairs,
-                                                        z_occ_max_dis, max_esti_dist, d_out, c->stream);
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(out, d_out, n_out * sizeof(lsd_match_score), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
-}
-
-// Before a FeatureScan launch: a stride above 1024 goes to the long kernels (k_rdp_long.hip), whose dynamic LDS at this context's capacity
-// may be above the 64 KiB a kernel gets without asking.  Their limit is raised once per context (and again after the capacity changes),
-// to the capacity's need: every stride the entries let through fits.
-static hipError_t rdp_long_prepare(lsd_ctx* c, int stride) {
-    if (stride <= kRdpShortMaxLen || c->rdp_long_ready) return hipSuccess;
-    const hipError_t e = prepare_rdp_long(rdp_long_lds(c->scan_cap));
-    if (e == hipSuccess) c->rdp_long_ready = true;
-    return e;
-}
-
-// the two FeatureScan enqueue entries: the argument check they share
-static bool feature_scan_args_bad(const lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride, const lsd_line* d_lines_out,
-                                  const int* d_n_lines, const lsd_position* d_pts_out, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
-                                  const int* d_im_size) {
-    return !c || !d_scans || !d_lens || n_scans <= 0 || stride <= 0 || !d_lines_out || !d_n_lines || !d_n_pts || !d_lidar_pos || !d_im_size ||
-           pts_cap < 0 || (pts_cap > 0 && !d_pts_out);
-}
-
-int lsd_enqueue_feature_scan_batch_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride,
-                                          lsd_map_param mp, int region_point_limit, double thre_line, double line_dist_thre_m,
-                                          lsd_line* d_lines_out, int* d_n_lines, lsd_position* d_pts_out, int pts_cap, int* d_n_pts,
-                                          double* d_lidar_pos, int* d_im_size, void* stream) {
-    if (feature_scan_args_bad(c, d_scans, d_lens, n_scans, stride, d_lines_out, d_n_lines, d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size) ||
-        !(mp.mapResol > 0))
-        return LSD_ERR_INVALID;
-    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;              // NULL: the default (null) stream, as everywhere in HIP
-    HIPCHK(c, rdp_long_prepare(c, stride));
-    RdpScans a{};
-    a.scans = reinterpret_cast<const double*>(d_scans); a.lens = d_lens; a.n = n_scans; a.stride = stride;
-    a.region_point_limit = region_point_limit; a.thre_line = thre_line; a.line_dist_thre_m = line_dist_thre_m;
-    a.mapResol = mp.mapResol; a.mapOriX = mp.mapOriX; a.mapOriY = mp.mapOriY;
-    RdpOut o{};
-    o.lines = d_lines_out; o.n_lines = d_n_lines; o.pts = reinterpret_cast<double*>(d_pts_out); o.pts_cap = pts_cap;
-    o.n_pts = d_n_pts; o.lidar_pos = d_lidar_pos; o.im_size = d_im_size;
-    launch_rdp(a, o, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-static_assert(LSD_SCAN_MAX_LEN == kRdpLongMaxLen, "the header's limit is the long kernel's");
-static_assert(sizeof(lsd_map_ref) == 64 && offsetof(lsd_map_ref, d_map_cache) == 0 && offsetof(lsd_map_ref, d_map_lines) == 8 &&
-              offsetof(lsd_map_ref, d_n_map) == 16 && offsetof(lsd_map_ref, cols) == 24 && offsetof(lsd_map_ref, rows) == 28 &&
-              offsetof(lsd_map_ref, n_map) == 32 && offsetof(lsd_map_ref, mapResol) == 40 && offsetof(lsd_map_ref, mapOriX) == 48 &&
-              offsetof(lsd_map_ref, mapOriY) == 56,
-              "lsd_map_ref has the layout the Python mirror (MAP_REF_DTYPE) assumes");
-
-// The fleet entries' table, checked field by field on the host (nothing the kernels follow is left to the device); *max_n_map: the
-// largest n_map, what the loops size their workspace from.
-static int map_table_check(const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int* max_n_map) {
-    if (!maps || n_maps <= 0 || !d_map_of) return LSD_ERR_INVALID;
-    if (n_maps > LSD_MAX_MAPS) return LSD_ERR_UNSUPPORTED;
-    int mx = 0;
-    for (int i = 0; i < n_maps; i++) {
-        const lsd_map_ref& m = maps[i];
-        if (!m.d_map_cache || m.cols <= 0 || m.rows <= 0 || m.n_map < 0 || (m.n_map > 0 && !m.d_map_lines) || !(m.mapResol > 0))
-            return LSD_ERR_INVALID;
-        mx = std::max(mx, m.n_map);
-    }
-    if (max_n_map) *max_n_map = mx;
-    return LSD_OK;
-}
-
-// The checked table to the device, asynchronously on `s`, the way n_frames travels: a host copy the context owns is the upload's source,
-// so the caller's array is free when the entry returns.  half 0: FeatureScan's records, 1: the loops'.
-static int map_table_upload(lsd_ctx* c, int half, const lsd_map_ref* maps, int n_maps, hipStream_t s, const lsd_map_ref** d_tab) {
-    HIPCHK(c, c->map_tab.reserve(2 * LSD_MAX_MAPS));             // (the first fleet call of a context: one synchronisation)
-    lsd_map_ref* h = c->map_tab_host.data() + (size_t)half * LSD_MAX_MAPS;
-    lsd_map_ref* d = c->map_tab.get() + (size_t)half * LSD_MAX_MAPS;
-    std::copy(maps, maps + n_maps, h);
-    HIPCHK(c, hipMemcpyAsync(d, h, sizeof(lsd_map_ref) * (size_t)n_maps, hipMemcpyHostToDevice, s));
-    *d_tab = d;
-    return LSD_OK;
-}
-
-int lsd_enqueue_feature_scan_maps_device(lsd_ctx* c, const lsd_polar* d_scans, const int* d_lens, int n_scans, int stride,
-                                         const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int scans_per_seq,
-                                         int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* d_lines_out,
-                                         int* d_n_lines, lsd_position* d_pts_out, int pts_cap, int* d_n_pts, double* d_lidar_pos,
-                                         int* d_im_size, void* stream) {
-    if (feature_scan_args_bad(c, d_scans, d_lens, n_scans, stride, d_lines_out, d_n_lines, d_pts_out, pts_cap, d_n_pts, d_lidar_pos, d_im_size) ||
-        scans_per_seq <= 0)
-        return LSD_ERR_INVALID;
-    const int r = map_table_check(maps, n_maps, d_map_of, nullptr);
-    if (r != LSD_OK) return r;
-    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(c, rdp_long_prepare(c, stride));
-    const lsd_map_ref* d_tab;
-    const int u = map_table_upload(c, 0, maps, n_maps, s, &d_tab);
-    if (u != LSD_OK) return u;
-    RdpScans a{};
-    a.scans = reinterpret_cast<const double*>(d_scans); a.lens = d_lens; a.n = n_scans; a.stride = stride;
-    a.region_point_limit = region_point_limit; a.thre_line = thre_line; a.line_dist_thre_m = line_dist_thre_m;
-    a.maps = d_tab; a.n_maps = n_maps; a.map_of = d_map_of; a.scans_per_seq = scans_per_seq;
-    RdpOut o{};
-    o.lines = d_lines_out; o.n_lines = d_n_lines; o.pts = reinterpret_cast<double*>(d_pts_out); o.pts_cap = pts_cap;
-    o.n_pts = d_n_pts; o.lidar_pos = d_lidar_pos; o.im_size = d_im_size;
-    launch_rdp(a, o, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-// the two ingest entries: the checks they share, then one launch of k_ingest
-static int enqueue_ingest(lsd_ctx* c, const lsd_polar* d_raw, const float* d_ranges, const float* d_min_inc, int n_scans, int n_beams,
-                          const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
-    if (!c || n_scans <= 0 || n_beams <= 0 || stride <= 0 || !d_scans || !d_lens || n_beams > stride) return LSD_ERR_INVALID;
-    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(d_raw) | reinterpret_cast<uintptr_t>(d_scans)) & 15) {        // the kernel moves a pair in one 16-byte access
-        c->err = "scan ingest: d_raw and d_scans must be 16-byte aligned";
-        return LSD_ERR_INVALID;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    launch_ingest(d_raw, d_ranges, d_min_inc, n_scans, n_beams, d_take, d_scans, d_lens, stride, s);
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_enqueue_scan_ingest_device(lsd_ctx* c, const lsd_polar* d_raw, int n_scans, int n_beams, const int* d_take, lsd_polar* d_scans,
-                                   int* d_lens, int stride, void* stream) {
-    if (!d_raw) return LSD_ERR_INVALID;
-    return enqueue_ingest(c, d_raw, nullptr, nullptr, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream);
-}
-
-int lsd_enqueue_laserscan_ingest_device(lsd_ctx* c, const float* d_ranges, const float* d_angle_min_inc, int n_scans, int n_beams,
-                                        const int* d_take, lsd_polar* d_scans, int* d_lens, int stride, void* stream) {
-    if (!d_ranges || !d_angle_min_inc) return LSD_ERR_INVALID;
-    return enqueue_ingest(c, nullptr, d_ranges, d_angle_min_inc, n_scans, n_beams, d_take, d_scans, d_lens, stride, stream);
-}
-
-int lsd_feature_scan_batch(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, lsd_map_param mp,
-                           int region_point_limit, double thre_line, double line_dist_thre_m, lsd_line* lines_out, int* n_lines,
-                           lsd_position* pts_out, int pts_cap, int* n_pts, double* lidar_pos, int* im_size) {
-    if (!c || !scans || !lens || n_scans <= 0 || stride <= 0 || !lines_out || !n_lines || !n_pts || !lidar_pos || !im_size || pts_cap < 0 ||
-        (pts_cap > 0 && !pts_out))
-        return LSD_ERR_INVALID;
-    for (int i = 0; i < n_scans; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans, b_sc = ns * stride * sizeof(lsd_polar), b_len = ns * sizeof(int), b_li = ns * LSD_RDP_MAX_LINES * sizeof(lsd_line);
-    lsd_polar* d_sc; int *d_len, *d_nl, *d_np, *d_sz; lsd_line* d_li; lsd_position* d_pt; double* d_lp;
-    auto regions = [&](Carver& k) {
-        k(d_sc, ns * stride); k(d_len, ns); k(d_li, ns * LSD_RDP_MAX_LINES); k(d_pt, ns * pts_cap);
-        k(d_nl, ns); k(d_np, ns); k(d_lp, ns * 2); k(d_sz, ns * 2);
-    };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, b_sc, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, b_len, hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_feature_scan_batch_device(c, d_sc, d_len, n_scans, stride, mp, region_point_limit, thre_line, line_dist_thre_m,
-                                                         d_li, d_nl, d_pt, pts_cap, d_np, d_lp, d_sz, c->stream);
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(lines_out, d_li, b_li, hipMemcpyDeviceToHost, c->stream));
-    if (pts_cap > 0) HIPCHK(c, hipMemcpyAsync(pts_out, d_pt, ns * pts_cap * sizeof(lsd_position), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(n_lines, d_nl, b_len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(n_pts, d_np, b_len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(lidar_pos, d_lp, ns * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(im_size, d_sz, ns * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n_scans; i++)
-        if (n_lines[i] > LSD_RDP_MAX_LINES) return LSD_ERR_CAPACITY;      // more chords than the 360 records per scan hold (the first 360 are valid)
-    return LSD_OK;
-}
-
-// --- device FeatureAssociation (k_fa.hip) ------------------------------------------------------------------------------
-// Carves the per-sequence workspace of n_seq sequences with pair_cap pairs each out of c->fa_buf (grown with one synchronisation; while
-// it is large enough this is pointer arithmetic only: Localizer.step_device never waits for the device).
-static int fa_workspace(lsd_ctx* c, int n_seq, int pair_cap, FaArgs& a) {
-    const size_t ns = (size_t)n_seq, pc = (size_t)pair_cap;
-    auto regions = [&](Carver& k) {
-        k(a.pairs, ns * pc * 2); k(a.n_pairs, ns); k(a.n_cand, ns); k(a.n_frames, ns);
-        k(a.cand, ns * pc * 16); k(a.scratch, ns * pc * 8); k(a.ctl, ns * kFaCtl); k(a.aux, ns * kFaAux);
-    };
-    HIPCHK(c, carve(c->fa_buf, regions));
-    a.pair_cap = pair_cap;
-    a.lds_bound = c->fa_lds_bound;
-    return LSD_OK;
-}
-
-void lsd_fa_initial_state(lsd_fa_state* o) {                    // LSD/main_on_windows.cpp:84-93
-    if (!o) return;
-    memset(o, 0, sizeof(*o));
-    o->x[0] = -1; o->x[1] = -1;
-    const double d[9] = {100, 100, 100, 1, 1, 1, 0.1, 0.1, 0.1};
-    for (int i = 0; i < 9; i++) o->P[i * 10] = d[i];
-}
-
-int lsd_feature_association(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map,
-                            const lsd_line* scan_lines, int n_scan, const lsd_position* pts, int n_points, lsd_position lidar,
-                            lsd_position last, lsd_position sp, const lsd_fa_state* in, lsd_fa_state* out, lsd_fa_report* report) {
-    if (!c || !map_cache || cols <= 0 || rows <= 0 || n_map < 0 || n_scan < 0 || n_points < 0 || (n_map > 0 && !map_lines) ||
-        (n_scan > 0 && !scan_lines) || (n_points > 0 && !pts) || !in || !out || !report)
-        return LSD_ERR_INVALID;
-    if ((long long)n_map * n_scan > (1 << 26)) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n_mc = (size_t)cols * rows;
-    double *d_mc, *d_sc;                                          // d_sc: lidarPose (2), then lastPose + ScanPose (6)
-    lsd_line *d_ml, *d_sl; lsd_position* d_pts; lsd_fa_state* d_st; lsd_fa_report* d_rep;
-    auto regions = [&](Carver& k) { k(d_mc, n_mc); k(d_ml, n_map); k(d_sl, n_scan); k(d_pts, n_points); k(d_st, 2); k(d_rep, 1); k(d_sc, 8); };
-    HIPCHK(c, carve(c->stage, regions));
-    FaArgs a{};
-    const int pair_cap = std::max(1, n_map * n_scan);
-    const int r = fa_workspace(c, 1, pair_cap, a);
-    if (r != LSD_OK) return r;
-    const double sc[8] = {lidar.x, lidar.y, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, s));
-    if (n_map) HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    if (n_scan) HIPCHK(c, hipMemcpyAsync(d_sl, scan_lines, (size_t)n_scan * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    if (n_points) HIPCHK(c, hipMemcpyAsync(d_pts, pts, (size_t)n_points * sizeof(lsd_position), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_sc, sc, sizeof(sc), hipMemcpyHostToDevice, s));
-    a.map_cache = d_mc; a.cols = cols; a.rows = rows;
-    a.map_lines = d_ml; a.n_map = n_map;
-    a.scan_lines = d_sl; a.n_lines = nullptr; a.n_scan_given = n_scan; a.line_pitch = std::max(n_scan, 1);
-    a.pts = reinterpret_cast<const double*>(d_pts); a.n_pts = nullptr; a.n_pts_given = n_points; a.pts_pitch = std::max(n_points, 1);
-    a.lidar_pos = d_sc; a.given = d_sc + 2;
-    a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0;
-    a.odom = nullptr; a.map_resol = 1;
-    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = d_rep;
-    launch_fa_frame(a, 1, true, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(report, d_rep, sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_debug_fa_fuse(lsd_ctx* c, const lsd_match_score* cands, int n, lsd_position last, lsd_position sp, const lsd_fa_state* in,
-                      lsd_fa_state* out, lsd_fa_report* report) {
-    if (!c || n < 0 || (n > 0 && !cands) || !in || !out || !report) return LSD_ERR_INVALID;
-    if (n > (1 << 26)) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    lsd_fa_state* d_st; lsd_fa_report* d_rep;
-    auto regions = [&](Carver& k) { k(d_st, 2); k(d_rep, 1); };
-    HIPCHK(c, carve(c->stage, regions));
-    FaArgs a{};
-    const int r = fa_workspace(c, 1, std::max(1, (n + 3) / 4), a);
-    if (r != LSD_OK) return r;
-    hipStream_t s = c->stream;
-    const double ctl[kFaCtl] = {0, 0, last.x, last.y, last.ang, sp.x, sp.y, sp.ang};
-    const int cnt[2] = {0, n};
-    if (n) HIPCHK(c, hipMemcpyAsync(a.cand, cands, (size_t)n * sizeof(lsd_match_score), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(a.ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(a.n_pairs, &cnt[0], 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(a.n_cand, &cnt[1], 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_st, in, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
-    a.n_frames = nullptr; a.frames_pitch = 1; a.t = 0; a.odom = nullptr;
-    a.init = d_st; a.state_in = d_st; a.states = d_st + 1; a.reports = d_rep;
-    launch_fa_frame(a, 1, false, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_st + 1, sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(report, d_rep, sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return LSD_OK;
-}
-
-static_assert(sizeof(lsd_fa_carry) == 768 && offsetof(lsd_fa_carry, odom) == 720 && offsetof(lsd_fa_carry, ang_sum) == 744 &&
-              offsetof(lsd_fa_carry, ang_count) == 752 && offsetof(lsd_fa_carry, frames) == 760 && offsetof(lsd_fa_carry, is_offset) == 764,
-              "lsd_fa_carry is plain bytes with the layout the Python mirror (FA_CARRY_DTYPE) assumes");
-
-void lsd_fa_carry_init(lsd_fa_carry* o, const lsd_fa_state* state, lsd_position odom0) {
-    if (!o) return;
-    memset(o, 0, sizeof(*o));
-    if (state) o->state = *state;
-    else lsd_fa_initial_state(&o->state);
-    o->odom = odom0;
-}
-
-int lsd_enqueue_fa_carry_rebase_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, const int32_t* d_key, int32_t key, lsd_map_frame from,
-                                       lsd_map_frame to, void* stream) {
-    if (!c) return LSD_ERR_INVALID;
-    auto bad = [](const lsd_map_frame& f) {
-        return !(std::isfinite(f.mapResol) && f.mapResol > 0) || !std::isfinite(f.mapOriX) || !std::isfinite(f.mapOriY);
-    };
-    if (!d_carry || n_seq <= 0 || bad(from) || bad(to)) return LSD_ERR_INVALID;
-    if (from.mapResol == to.mapResol && from.mapOriX == to.mapOriX && from.mapOriY == to.mapOriY) return LSD_OK;   // the same frame: no launch
-    HIPCHK(c, hipSetDevice(c->device));
-    const double sc = from.mapResol / to.mapResol;
-    const double tx = (from.mapOriX - to.mapOriX) / to.mapResol, ty = (from.mapOriY - to.mapOriY) / to.mapResol;
-    launch_fa_rebase(d_carry, n_seq, d_key, key, sc, tx, ty, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return LSD_OK;
-}
-
-// The grid match response fused into the carries (k_facorrect.hip): the argument check of both entries, then one launch.
-static bool fa_correct_refused(const lsd_ctx* c, const void* carry, int n_seq, int frames_pitch, const void* poses, size_t pose_pitch,
-                               const void* resp, const void* key, const lsd_fa_correct_par& par, const void* rep) {
-    auto off8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; };
-    auto bad = [](double v) { return !std::isfinite(v) || v < 0; };
-    return !c || !carry || !poses || !resp || n_seq <= 0 || frames_pitch < 1 || frames_pitch > 4096 || pose_pitch < 24 || pose_pitch % 8 != 0 ||
-           off8(carry) || off8(poses) || off8(resp) || off8(rep) || (reinterpret_cast<uintptr_t>(key) & 3) != 0 || bad(par.cov_scale) ||
-           bad(par.floor_xy) || bad(par.floor_ang) || bad(par.gate);
-}
-
-int lsd_enqueue_fa_carry_correct_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const void* d_poses, size_t pose_pitch,
-                                        const lsd_grid_response_rec* d_resp, const int32_t* d_key, int32_t key, lsd_fa_correct_par par,
-                                        lsd_fa_correct_rep* d_rep, void* stream) {
-    if (fa_correct_refused(c, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_resp, d_key, par, d_rep)) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_fa_correct(d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_resp, d_key, key, par, d_rep, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return LSD_OK;
-}
-
-int lsd_fa_carry_correct(lsd_ctx* c, lsd_fa_carry* carries, int n_seq, int frames_pitch, const lsd_position* poses,
-                         const lsd_grid_response_rec* resp, lsd_fa_correct_par par, lsd_fa_correct_rep* rep) {
-    if (fa_correct_refused(c, carries, n_seq, frames_pitch, poses, sizeof(lsd_position), resp, nullptr, par, rep)) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_seq, n = ns * (size_t)frames_pitch;
-    lsd_fa_carry* d_cy; lsd_position* d_po; lsd_grid_response_rec* d_re; lsd_fa_correct_rep* d_rp;
-    auto regions = [&](Carver& k) { k(d_cy, ns); k(d_po, n); k(d_re, n); k(d_rp, ns); };
-    HIPCHK(c, carve(c->stage, regions));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_cy, carries, ns * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_po, poses, n * sizeof(lsd_position), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_re, resp, n * sizeof(lsd_grid_response_rec), hipMemcpyHostToDevice, s));
-    const int st = lsd_enqueue_fa_carry_correct_device(c, d_cy, n_seq, frames_pitch, d_po, sizeof(lsd_position), d_re, nullptr, 0, par,
-                                                       rep ? d_rp : nullptr, s);
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(carries, d_cy, ns * sizeof(lsd_fa_carry), hipMemcpyDeviceToHost, s));
-    if (rep) HIPCHK(c, hipMemcpyAsync(rep, d_rp, ns * sizeof(lsd_fa_correct_rep), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return LSD_OK;
-}
-
-// Relocalisation (k_falost.hip, k_faseed.hip): the checks of fa_relocate_host.h, then one launch each.
-int lsd_enqueue_fa_lost_gather_device(lsd_ctx* c, const lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const void* d_poses, size_t pose_pitch,
-                                      const lsd_polar* d_scans, const int* d_lens, int stride, const int32_t* d_key, int32_t key, int max_lost,
-                                      lsd_polar* d_scans_out, int* d_lens_out, int32_t* d_pick, int32_t* d_n_lost, void* stream) {
-    if (fa_lost_refused(c != nullptr, c ? c->scan_cap : 0, d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_scans, d_lens, stride, d_key, max_lost,
-                        d_scans_out, d_lens_out, d_pick, d_n_lost))
-        return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_fa_lost_gather(d_carry, n_seq, frames_pitch, d_poses, pose_pitch, d_scans, d_lens, stride, d_key, key, max_lost, d_scans_out, d_lens_out,
-                          d_pick, d_n_lost, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return LSD_OK;
-}
-
-int lsd_fa_lost_gather(lsd_ctx* c, const lsd_fa_carry* carries, int n_seq, int frames_pitch, const lsd_position* poses, const lsd_polar* scans,
-                       const int* lens, int stride, int max_lost, lsd_polar* scans_out, int* lens_out, int32_t* pick, int32_t* n_lost) {
-    auto there = fa_host_stand_in;                               // (host arrays: the alignment rules are the staging's to keep)
-    if (fa_lost_refused(c != nullptr, c ? c->scan_cap : 0, there(carries), n_seq, frames_pitch, there(poses), sizeof(lsd_position), there(scans),
-                        there(lens), stride, nullptr, max_lost, there(scans_out), there(lens_out), there(pick), there(n_lost)))
-        return LSD_ERR_INVALID;
-    const FaLostStage n = fa_lost_stage(n_seq, frames_pitch, stride, max_lost);
-    if (fa_lost_bad_len(lens, n.slots, stride) >= 0) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    lsd_fa_carry* d_cy; lsd_position* d_po; lsd_polar *d_sc, *d_so; int *d_ln, *d_lo; int32_t *d_pk, *d_nl;
-    auto regions = [&](Carver& k) { k(d_cy, n.carries); k(d_po, n.slots); k(d_sc, n.readings); k(d_ln, n.slots); k(d_so, n.readings_out);
-                                    k(d_lo, n.rows); k(d_pk, n.rows); k(d_nl, 2); };
-    HIPCHK(c, carve(c->stage, regions));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_cy, carries, n.carries * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_po, poses, n.slots * sizeof(lsd_position), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, n.readings * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_ln, lens, n.slots * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_so, scans_out, n.readings_out * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
-    const int st = lsd_enqueue_fa_lost_gather_device(c, d_cy, n_seq, frames_pitch, d_po, sizeof(lsd_position), d_sc, d_ln, stride, nullptr, 0,
-                                                     max_lost, d_so, d_lo, d_pk, d_nl, s);
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(scans_out, d_so, n.readings_out * sizeof(lsd_polar), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(lens_out, d_lo, n.rows * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(pick, d_pk, n.rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(n_lost, d_nl, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return LSD_OK;
-}
-
-int lsd_enqueue_fa_carry_seed_device(lsd_ctx* c, lsd_fa_carry* d_carry, int n_seq, int frames_pitch, const int32_t* d_pick, int n_pick,
-                                     const lsd_grid_locate_rec* d_loc, const lsd_grid_response_rec* d_resp, lsd_fa_seed_par par,
-                                     lsd_fa_seed_rep* d_rep, void* stream) {
-    if (fa_seed_refused(c != nullptr, d_carry, n_seq, frames_pitch, d_pick, n_pick, d_loc, d_resp, par, d_rep)) return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_fa_seed(d_carry, n_seq, frames_pitch, d_pick, n_pick, d_loc, d_resp, par, d_rep, (hipStream_t)stream);
-    HIPCHK(c, hipGetLastError());
-    return LSD_OK;
-}
-
-int lsd_fa_carry_seed(lsd_ctx* c, lsd_fa_carry* carries, int n_seq, int frames_pitch, const int32_t* pick, int n_pick,
-                      const lsd_grid_locate_rec* loc, const lsd_grid_response_rec* resp, lsd_fa_seed_par par, lsd_fa_seed_rep* rep) {
-    auto there = fa_host_stand_in;                               // (host arrays: the alignment rules are the staging's to keep)
-    if (fa_seed_refused(c != nullptr, there(carries), n_seq, frames_pitch, there(pick), n_pick, there(loc), there(resp), par, there(rep)))
-        return LSD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_seq, np = (size_t)n_pick;
-    lsd_fa_carry* d_cy; int32_t* d_pk; lsd_grid_locate_rec* d_lc; lsd_grid_response_rec* d_re; lsd_fa_seed_rep* d_rp;
-    auto regions = [&](Carver& k) { k(d_cy, ns); k(d_pk, np); k(d_lc, np); k(d_re, np); k(d_rp, np); };
-    HIPCHK(c, carve(c->stage, regions));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_cy, carries, ns * sizeof(lsd_fa_carry), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_pk, pick, np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_lc, loc, np * sizeof(lsd_grid_locate_rec), hipMemcpyHostToDevice, s));
-    if (resp) HIPCHK(c, hipMemcpyAsync(d_re, resp, np * sizeof(lsd_grid_response_rec), hipMemcpyHostToDevice, s));
-    const int st = lsd_enqueue_fa_carry_seed_device(c, d_cy, n_seq, frames_pitch, d_pk, n_pick, d_lc, resp ? d_re : nullptr, par,
-                                                    rep ? d_rp : nullptr, s);
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(carries, d_cy, ns * sizeof(lsd_fa_carry), hipMemcpyDeviceToHost, s));
-    if (rep) HIPCHK(c, hipMemcpyAsync(rep, d_rp, np * sizeof(lsd_fa_seed_rep), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return LSD_OK;
-}
-
-// What the replay loop runs against.  One map: its fields; with d_n_map (the live-map entries) the map's line count is read on the device
-// and n_map is its capacity.  Or the table (the *_maps entries; a non-null `maps` is what selects it): sequence s runs against
-// maps[d_map_of[s]] and the single-map fields are unused.  Everything the host sizes is sized from n_map, resp. the table's largest.
-struct FaLoopMap {
-    const double* d_map_cache; int cols, rows; const lsd_line* d_map_lines; int n_map; const int32_t* d_n_map; double map_resol;
-    const lsd_map_ref* maps; int n_maps; const int32_t* d_map_of;
-};
-
-// The frames of the loop: FeatureScan's outputs, the odometry, where each sequence starts from -- d_init (lsd_enqueue_localize_device,
-// odometry n_seq x (frames_pitch + 1)) or d_carry (lsd_enqueue_localize_resume_device, odometry n_seq x frames_pitch), exactly one of
-// them -- and the outputs.
-struct FaLoopFrames {
-    int n_seq, frames_pitch; const int* n_frames;
-    const lsd_line* d_lines; const int* d_n_lines; const lsd_position* d_pts; int pts_cap; const int* d_n_pts; const double* d_lidar_pos;
-    const lsd_position* d_odom; const lsd_fa_state* d_init; lsd_fa_carry* d_carry; lsd_fa_state* d_states; lsd_fa_report* d_reports;
-};
-
-// The replay loop of every device entry point.
-static int fa_enqueue_loop(lsd_ctx* c, const FaLoopMap& m, const FaLoopFrames& f, void* stream) {
-    const int n_seq = f.n_seq;
-    if (!c || n_seq <= 0 || f.frames_pitch <= 0 || !f.n_frames || !f.d_lines || !f.d_n_lines || f.pts_cap < 0 || (f.pts_cap > 0 && !f.d_pts) ||
-        !f.d_n_pts || !f.d_lidar_pos || !f.d_odom || !(f.d_init || f.d_carry) || !f.d_states || !f.d_reports)
-        return LSD_ERR_INVALID;
-    if (!m.maps && (!m.d_map_cache || m.cols <= 0 || m.rows <= 0 || m.n_map < 0 || (m.n_map > 0 && !m.d_map_lines) || !(m.map_resol > 0)))
-        return LSD_ERR_INVALID;
-    int max_frames = 0;
-    for (int i = 0; i < n_seq; i++) {
-        if (f.n_frames[i] < 0 || f.n_frames[i] > f.frames_pitch) return LSD_ERR_INVALID;
-        max_frames = std::max(max_frames, f.n_frames[i]);
-    }
-    int n_map = m.n_map;
-    if (m.maps) {
-        const int r = map_table_check(m.maps, m.n_maps, m.d_map_of, &n_map);
-        if (r != LSD_OK) return r;
-    }
-    if ((long long)n_map * LSD_RDP_MAX_LINES > (1 << 26)) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    FaArgs a{};
-    const int r = fa_workspace(c, n_seq, std::max(1, n_map * LSD_RDP_MAX_LINES), a);
-    if (r != LSD_OK) return r;
-    hipStream_t s = (hipStream_t)stream;
-    c->fa_nf.assign(f.n_frames, f.n_frames + n_seq);
-    HIPCHK(c, hipMemcpyAsync(const_cast<int*>(a.n_frames), c->fa_nf.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
-    if (m.maps) {
-        const int u = map_table_upload(c, 1, m.maps, m.n_maps, s, &a.maps);
-        if (u != LSD_OK) return u;
-        a.map_of = m.d_map_of; a.n_maps = m.n_maps;
-    }
-    a.map_cache = m.d_map_cache; a.cols = m.cols; a.rows = m.rows; a.map_lines = m.d_map_lines; a.n_map = n_map; a.d_n_map = m.d_n_map;
-    a.scan_lines = f.d_lines; a.n_lines = f.d_n_lines; a.line_pitch = LSD_RDP_MAX_LINES;
-    a.pts = reinterpret_cast<const double*>(f.d_pts); a.n_pts = f.d_n_pts; a.pts_pitch = f.pts_cap;
-    a.lidar_pos = f.d_lidar_pos; a.frames_pitch = f.frames_pitch; a.odom = f.d_odom; a.given = nullptr;
-    a.map_resol = m.maps ? 1.0 : m.map_resol;                    // (the table carries each map's own)
-    a.init = f.d_init; a.carry = f.d_carry; a.state_in = nullptr; a.states = f.d_states; a.reports = f.d_reports;
-    for (int t = 0; t < max_frames; t++) {
-        a.t = t;
-        launch_fa_frame(a, n_seq, true, s);
-    }
-    HIPCHK(c, hipGetLastError());
-    c->last_stream = s;
-    return LSD_OK;
-}
-
-int lsd_enqueue_localize_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
-                                int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
-                                const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
-                                const lsd_position* d_odom, double map_resol, const lsd_fa_state* d_init, lsd_fa_state* d_states,
-                                lsd_fa_report* d_reports, void* stream) {
-    if (!d_init) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = n_map,
-                           .map_resol = map_resol};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_enqueue_localize_resume_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines, int n_map,
-                                       int n_seq, int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
-                                       const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
-                                       const lsd_position* d_odom, double map_resol, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
-                                       lsd_fa_report* d_reports, void* stream) {
-    if (!d_carry) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = n_map,
-                           .map_resol = map_resol};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_enqueue_localize_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
-                                         int map_lines_cap, const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames,
-                                         const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts, int pts_cap,
-                                         const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
-                                         const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
-    if (!d_init || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = map_lines_cap,
-                           .d_n_map = d_n_map, .map_resol = map_resol};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_enqueue_localize_resume_live_map_device(lsd_ctx* c, const double* d_map_cache, int cols, int rows, const lsd_line* d_map_lines,
-                                                int map_lines_cap, const int32_t* d_n_map, int n_seq, int frames_pitch, const int* n_frames,
-                                                const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts, int pts_cap,
-                                                const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom, double map_resol,
-                                                lsd_fa_carry* d_carry, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
-    if (!d_carry || !d_n_map || map_lines_cap <= 0) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.d_map_cache = d_map_cache, .cols = cols, .rows = rows, .d_map_lines = d_map_lines, .n_map = map_lines_cap,
-                           .d_n_map = d_n_map, .map_resol = map_resol};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_enqueue_localize_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq, int frames_pitch,
-                                     const int* n_frames, const lsd_line* d_lines, const int* d_n_lines, const lsd_position* d_pts,
-                                     int pts_cap, const int* d_n_pts, const double* d_lidar_pos, const lsd_position* d_odom,
-                                     const lsd_fa_state* d_init, lsd_fa_state* d_states, lsd_fa_report* d_reports, void* stream) {
-    if (!d_init) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.maps = maps, .n_maps = n_maps, .d_map_of = d_map_of};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_init = d_init, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_enqueue_localize_resume_maps_device(lsd_ctx* c, const lsd_map_ref* maps, int n_maps, const int32_t* d_map_of, int n_seq,
-                                            int frames_pitch, const int* n_frames, const lsd_line* d_lines, const int* d_n_lines,
-                                            const lsd_position* d_pts, int pts_cap, const int* d_n_pts, const double* d_lidar_pos,
-                                            const lsd_position* d_odom, lsd_fa_carry* d_carry, lsd_fa_state* d_states,
-                                            lsd_fa_report* d_reports, void* stream) {
-    if (!d_carry) return LSD_ERR_INVALID;
-    const FaLoopMap map = {.maps = maps, .n_maps = n_maps, .d_map_of = d_map_of};
-    const FaLoopFrames frames = {.n_seq = n_seq, .frames_pitch = frames_pitch, .n_frames = n_frames, .d_lines = d_lines, .d_n_lines = d_n_lines,
-                               .d_pts = d_pts, .pts_cap = pts_cap, .d_n_pts = d_n_pts, .d_lidar_pos = d_lidar_pos, .d_odom = d_odom,
-                               .d_carry = d_carry, .d_states = d_states, .d_reports = d_reports};
-    return fa_enqueue_loop(c, map, frames, stream);
-}
-
-int lsd_localize(lsd_ctx* c, const double* map_cache, int cols, int rows, const lsd_line* map_lines, int n_map, const lsd_polar* scans,
-                 const int* lens, int n_frames, int stride, const lsd_position* odom, lsd_map_param mp, const lsd_fa_state* init,
-                 lsd_fa_state* states, lsd_fa_report* reports) {
-    if (!c || !map_cache || cols <= 0 || rows <= 0 || n_map < 0 || (n_map > 0 && !map_lines) || !scans || !lens || n_frames <= 0 ||
-        stride <= 0 || !odom || !states || !reports || !(mp.mapResol > 0))
-        return LSD_ERR_INVALID;
-    for (int i = 0; i < n_frames; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
-    if (stride > c->scan_cap) return LSD_ERR_UNSUPPORTED;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int pts_cap = 8192;
-    const size_t nf = (size_t)n_frames, n_mc = (size_t)cols * rows;
-    double *d_mc, *d_lp; lsd_line *d_ml, *d_lines; lsd_polar* d_scans; int *d_lens, *d_nl, *d_np, *d_sz; lsd_position *d_odom, *d_pts;
-    lsd_fa_state *d_init, *d_states; lsd_fa_report* d_reports;
-    auto regions = [&](Carver& k) {
-        k(d_mc, n_mc); k(d_ml, n_map); k(d_scans, nf * stride); k(d_lens, nf); k(d_odom, nf + 1); k(d_init, 1);
-        k(d_lines, nf * LSD_RDP_MAX_LINES); k(d_nl, nf); k(d_pts, nf * pts_cap); k(d_np, nf); k(d_lp, nf * 2); k(d_sz, nf * 2);
-        k(d_states, nf); k(d_reports, nf);
-    };
-    HIPCHK(c, carve(c->stage, regions));
-    hipStream_t s = c->stream;
-    lsd_fa_state h_init;
-    if (init) h_init = *init;
-    else lsd_fa_initial_state(&h_init);
-    HIPCHK(c, hipMemcpyAsync(d_mc, map_cache, n_mc * sizeof(double), hipMemcpyHostToDevice, s));
-    if (n_map) HIPCHK(c, hipMemcpyAsync(d_ml, map_lines, (size_t)n_map * sizeof(lsd_line), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_scans, scans, nf * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_lens, lens, nf * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_odom, odom, (nf + 1) * sizeof(lsd_position), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_init, &h_init, sizeof(lsd_fa_state), hipMemcpyHostToDevice, s));
-    int r = lsd_enqueue_feature_scan_batch_device(c, d_scans, d_lens, n_frames, stride, mp, 3, 0.08, 0.5, d_lines, d_nl, d_pts, pts_cap, d_np,
-                                                  d_lp, d_sz, s);   // rdp defaults, baseFunc.h:70-72
-    if (r != LSD_OK) return r;
-    r = lsd_enqueue_localize_device(c, d_mc, cols, rows, d_ml, n_map, 1, n_frames, &n_frames, d_lines, d_nl, d_pts, pts_cap, d_np, d_lp, d_odom,
-                                    mp.mapResol, d_init, d_states, d_reports, s);
-    if (r != LSD_OK) return r;
-    std::vector<int> nl(nf), np(nf);
-    HIPCHK(c, hipMemcpyAsync(states, d_states, nf * sizeof(lsd_fa_state), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(reports, d_reports, nf * sizeof(lsd_fa_report), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(nl.data(), d_nl, nf * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(np.data(), d_np, nf * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (size_t i = 0; i < nf; i++)
-        if (nl[i] > LSD_RDP_MAX_LINES || np[i] > pts_cap) return LSD_ERR_CAPACITY;
-    return LSD_OK;
 }
 
 int lsd_debug_calibrate(lsd_ctx* c, size_t bytes) {

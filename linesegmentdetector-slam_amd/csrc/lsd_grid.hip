@@ -2,7 +2,8 @@
 // scan-to-grid match, plain (k_gridmatch.hip) and coarse to fine (k_gridmatch_mr.hip), and the response around a match
 // (k_gridresponse.hip), ray casting (k_gridray.hip) and the global localisation (k_gridlocate.hip).  The scan-taking device entries receive the scans of a frame the same way: one check (grid_scans_bad)
 // turns those arguments into the view the launchers take, and each entry adds only what is its own.  Their host conveniences share one
-// check and one staging path (host_scans_bad, stage_scans) in the same way.
+// check (host_scans_bad) in the same way, and every host convenience here is one round trip through the context's staging (lsd_ctx.h:
+// stage_round_trip).
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
@@ -44,23 +45,6 @@ static bool host_scans_bad(const lsd_ctx* c, const lsd_polar* scans, const int* 
     return false;
 }
 
-// The staging of a host entry that has accepted its arguments: c->stage carved into the scans, the lengths, the poses and the regions
-// `more` names behind them, and the three uploads queued on c->stream.  d_sc, d_len, d_po: what the device entry is given then.
-template <class More>
-static int stage_scans(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_scans, int stride, const lsd_position* poses, lsd_polar*& d_sc,
-                       int*& d_len, lsd_position*& d_po, More&& more) {
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t ns = (size_t)n_scans;
-    auto regions = [&](Carver& k) { k(d_sc, ns * stride); k(d_len, ns); k(d_po, ns); more(k); };
-    HIPCHK(c, carve(c->stage, regions));
-    if (ns) {
-        HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_po, poses, ns * sizeof(lsd_position), hipMemcpyHostToDevice, c->stream));
-    }
-    return LSD_OK;
-}
-
 extern "C" {
 
 // --- mapping with known poses (k_gridmap.hip) ---
@@ -87,18 +71,14 @@ int lsd_grid_integrate(lsd_ctx* c, const lsd_polar* scans, const int* lens, int 
                        double range_max, uint32_t* pass, uint32_t* hit) {
     if (!pass || !hit || host_scans_bad(c, scans, lens, n_scans, stride, poses, mp, range_max)) return LSD_ERR_INVALID;
     // (no scans: the planes still make the round trip)
-    const size_t cells = (size_t)mp.oriMapCol * mp.oriMapRow;
+    const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
     lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint32_t *d_pa, *d_hi;
-    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) { k(d_pa, cells); k(d_hi, cells); });
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(d_pa, pass, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_hi, hit, cells * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_grid_integrate_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_pa, d_hi, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(pass, d_pa, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hit, d_hi, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_po, poses, ns); k.both(d_pa, pass, cells); k.both(d_hi, hit, cells);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_grid_integrate_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_pa, d_hi, c->stream);
+    });
 }
 
 // --- correlative scan-to-grid matching (k_gridmatch.hip) ---
@@ -153,14 +133,12 @@ int lsd_grid_match(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_sc
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
     lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t* d_co; lsd_grid_match_rec* d_out;
-    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) { k(d_co, cells); k(d_out, ns); });
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_po, poses, ns); k.in(d_co, corr, cells); k.out(d_out, out, ns);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_grid_match_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, se, d_out, c->stream);
+    });
 }
 
 // --- the same match, coarse to fine (k_gridmatch_mr.hip) ---
@@ -205,20 +183,16 @@ int lsd_grid_match_mr(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
     lsd_polar* d_sc; int* d_len; lsd_position* d_po; uint8_t *d_co, *d_cs; lsd_grid_match_rec* d_out; lsd_grid_match_mr_stats* d_st;
-    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po, [&](Carver& k) {
-        k(d_co, cells); k(d_cs, lsd_grid_coarse_bytes(mp.oriMapCol, mp.oriMapRow, block)); k(d_out, ns); k(d_st, ns);
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_po, poses, ns);
+        k.in(d_co, corr, cells); k.scratch(d_cs, lsd_grid_coarse_bytes(mp.oriMapCol, mp.oriMapRow, block)); k.out(d_out, out, ns); k.out(d_st, stats, ns);
+    };
+    return stage_round_trip(c, plan, [&] {
+        const int st = lsd_enqueue_grid_coarse_device(c, d_co, mp.oriMapCol, mp.oriMapRow, block, d_cs, c->stream);
+        if (st != LSD_OK) return st;
+        return lsd_enqueue_grid_match_mr_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, d_cs, block, se, d_out,
+                                                stats ? d_st : nullptr, c->stream);
     });
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_grid_coarse_device(c, d_co, mp.oriMapCol, mp.oriMapRow, block, d_cs, c->stream);
-    if (st == LSD_OK)
-        st = lsd_enqueue_grid_match_mr_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_co, d_cs, block, se, d_out,
-                                              stats ? d_st : nullptr, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_match_rec), hipMemcpyDeviceToHost, c->stream));
-    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * sizeof(lsd_grid_match_mr_stats), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
 }
 
 // --- the response around a match (k_gridresponse.hip) ---
@@ -265,18 +239,14 @@ int lsd_grid_response(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow, n_vol = grid_response_volume_bytes(n_scans, rp) / sizeof(uint32_t);
     lsd_polar* d_sc; int* d_len; lsd_position* d_po; lsd_grid_match_rec* d_rec; uint8_t* d_co; lsd_grid_response_rec* d_out; uint32_t* d_vol;
-    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po,
-                         [&](Carver& k) { k(d_rec, ns); k(d_co, cells); k(d_out, ns); k(d_vol, n_vol); });
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(d_rec, records, ns * sizeof(lsd_grid_match_rec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_grid_response_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), d_rec, mp, range_max, d_co, ang_step, rp,
-                                          d_out, d_vol, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_response_rec), hipMemcpyDeviceToHost, c->stream));
-    if (volume) HIPCHK(c, hipMemcpyAsync(volume, d_vol, n_vol * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_po, poses, ns);
+        k.in(d_rec, records, ns); k.in(d_co, corr, cells); k.out(d_out, out, ns); k.out(d_vol, volume, n_vol);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_grid_response_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), d_rec, mp, range_max, d_co, ang_step, rp, d_out,
+                                                d_vol, c->stream);
+    });
 }
 
 // --- ray casting on the grid (k_gridray.hip) ---
@@ -323,21 +293,14 @@ int lsd_grid_raycast(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, beams = ns * stride, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
     lsd_polar *d_sc, *d_so; int* d_len; lsd_position* d_po; int8_t* d_gr; lsd_grid_ray* d_out; lsd_grid_ray_sum* d_sum;
-    int st = stage_scans(c, scans, lens, n_scans, stride, poses, d_sc, d_len, d_po,
-                         [&](Carver& k) { k(d_gr, cells); k(d_out, beams); k(d_sum, ns); k(d_so, scans_out ? beams : 0); });
-    if (st != LSD_OK) return st;
-    HIPCHK(c, hipMemcpyAsync(d_gr, grid, cells, hipMemcpyHostToDevice, c->stream));
-    // (the slots at i >= len are the caller's: they make the round trip)
-    HIPCHK(c, hipMemcpyAsync(d_out, out, beams * sizeof(lsd_grid_ray), hipMemcpyHostToDevice, c->stream));
-    if (scans_out) HIPCHK(c, hipMemcpyAsync(d_so, scans_out, beams * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    st = lsd_enqueue_grid_raycast_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_gr, par, d_out, d_sum,
-                                         scans_out ? d_so : nullptr, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, beams * sizeof(lsd_grid_ray), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sum, d_sum, ns * sizeof(lsd_grid_ray_sum), hipMemcpyDeviceToHost, c->stream));
-    if (scans_out) HIPCHK(c, hipMemcpyAsync(scans_out, d_so, beams * sizeof(lsd_polar), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    auto plan = [&](StagePass& k) {                                      // (the slots of `out` at i >= len are the caller's: they make the round trip)
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_po, poses, ns);
+        k.in(d_gr, grid, cells); k.both(d_out, out, beams); k.out(d_sum, sum, ns); k.both(d_so, scans_out, scans_out ? beams : 0);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_grid_raycast_device(c, d_sc, d_len, n_scans, stride, d_po, sizeof(lsd_position), mp, range_max, d_gr, par, d_out, d_sum,
+                                               scans_out ? d_so : nullptr, c->stream);
+    });
 }
 
 // --- global scan-to-grid localisation (k_gridlocate.hip) ---
@@ -419,22 +382,15 @@ static int grid_locate_host(lsd_ctx* c, const lsd_polar* scans, const int* lens,
     if (n_scans == 0) return LSD_OK;
     const size_t ns = (size_t)n_scans, cells = (size_t)mp.oriMapCol * mp.oriMapRow;
     lsd_polar* d_sc; int* d_len; uint8_t *d_co, *d_py; lsd_grid_locate_rec* d_out; uint64_t* d_st;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) {
-        k(d_sc, ns * stride); k(d_len, ns); k(d_co, cells); k(d_py, lsd_grid_pyramid_bytes(mp.oriMapCol, mp.oriMapRow, par.levels)); k(d_out, ns);
-        k(d_st, ns * stats_bytes / sizeof(uint64_t));
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, ns * stride); k.in(d_len, lens, ns); k.in(d_co, corr, cells);
+        k.scratch(d_py, lsd_grid_pyramid_bytes(mp.oriMapCol, mp.oriMapRow, par.levels)); k.out(d_out, out, ns);
+        k.out(d_st, static_cast<uint64_t*>(stats), ns * stats_bytes / sizeof(uint64_t));
     };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, ns * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_co, corr, cells, hipMemcpyHostToDevice, c->stream));
-    int st = lsd_enqueue_grid_pyramid_device(c, d_co, mp.oriMapCol, mp.oriMapRow, par.levels, d_py, c->stream);
-    if (st == LSD_OK) st = enqueue(d_sc, d_len, d_py, d_out, stats ? d_st : nullptr);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(out, d_out, ns * sizeof(lsd_grid_locate_rec), hipMemcpyDeviceToHost, c->stream));
-    if (stats) HIPCHK(c, hipMemcpyAsync(stats, d_st, ns * stats_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    return stage_round_trip(c, plan, [&] {
+        const int st = lsd_enqueue_grid_pyramid_device(c, d_co, mp.oriMapCol, mp.oriMapRow, par.levels, d_py, c->stream);
+        return st != LSD_OK ? st : enqueue(d_sc, d_len, d_py, d_out, stats ? d_st : nullptr);
+    });
 }
 }  // extern "C++"
 

@@ -1,4 +1,4 @@
-// lsd_internal.h -- shared between the host side (lsd_ctx.hip, lsd_grid.hip, lsd_dist.hip) and the gfx950 kernels.
+// lsd_internal.h -- shared between the host side (lsd_ctx.hip, lsd_loc.hip, lsd_grid.hip, lsd_pg.hip, lsd_dist.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

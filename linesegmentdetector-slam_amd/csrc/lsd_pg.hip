@@ -1,6 +1,6 @@
 // lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the six device entries
 // (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures), of
-// place recognition's two (k_pgplace.hip) and the host conveniences, staged through the context's carver as every other host entry.
+// place recognition's two (k_pgplace.hip) and the host conveniences, each one round trip through the context's staging (lsd_ctx.h: stage_round_trip).
 #include <math.h>
 #include <stddef.h>
 
@@ -201,18 +201,11 @@ int lsd_pg_describe(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n, 
     const size_t nn = (size_t)n;
     const lsd_pg_head head{n, 0};
     lsd_pg_head* d_head; lsd_polar* d_sc; int* d_len; lsd_pg_desc* d_desc;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) { k(d_sc, nn * stride); k(d_head, 1); k(d_desc, nn); k(d_len, nn); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans, nn * stride * sizeof(lsd_polar), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_len, lens, nn * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_desc, 0, nn * sizeof(lsd_pg_desc), c->stream));      // (valid == 0: every row is described)
-    const int st = lsd_enqueue_pg_describe_device(c, d_head, n, d_sc, d_len, stride, range_max, d_desc, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(desc_out, d_desc, nn * sizeof(lsd_pg_desc), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    auto plan = [&](StagePass& k) { k.in(d_sc, scans, nn * stride); k.in(d_head, &head, 1); k.out(d_desc, desc_out, nn); k.in(d_len, lens, nn); };
+    return stage_round_trip(c, plan, [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(d_desc, 0, nn * sizeof(lsd_pg_desc), c->stream));      // (valid == 0: every row is described)
+        return lsd_enqueue_pg_describe_device(c, d_head, n, d_sc, d_len, stride, range_max, d_desc, c->stream);
+    });
 }
 
 int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query, lsd_pg_place_par par, lsd_pg_place_rec* recs, lsd_pg_place_rep* rep) {
@@ -221,22 +214,16 @@ int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query
     const lsd_pg_head head{n_nodes, 0};
     const lsd_pg_track track{query, 0, {0.0, 0.0, 0.0}};
     lsd_pg_head* d_head; lsd_pg_track* d_tr; lsd_pg_desc* d_desc; uint32_t* d_work; lsd_pg_place_rec* d_recs; lsd_pg_place_rep* d_rep;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) { k(d_head, 1); k(d_tr, 1); k(d_desc, nn); k(d_recs, par.k); k(d_rep, 1); k(d_work, nn); };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tr, &track, sizeof track, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_desc, desc, nn * sizeof(lsd_pg_desc), hipMemcpyHostToDevice, c->stream));
-    const int st = enqueue_on(c, c->stream, [&](hipStream_t s) {
-        launch_pg_recognize(d_head, nullptr, n_nodes, d_tr, nullptr, nullptr, 1, d_desc, par, d_work, d_recs, d_rep, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, s);
-        return LSD_OK;
+    auto plan = [&](StagePass& k) {
+        k.in(d_head, &head, 1); k.in(d_tr, &track, 1); k.in(d_desc, desc, nn); k.out(d_recs, recs, par.k); k.out(d_rep, rep, 1); k.scratch(d_work, nn);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return enqueue_on(c, c->stream, [&](hipStream_t s) {
+            launch_pg_recognize(d_head, nullptr, n_nodes, d_tr, nullptr, nullptr, 1, d_desc, par, d_work, d_recs, d_rep, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, s);
+            return LSD_OK;
+        });
     });
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    HIPCHK(c, hipMemcpyAsync(recs, d_recs, par.k * sizeof(lsd_pg_place_rec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
 }
 
 int lsd_pg_relax(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_relax_rep* rep) {
@@ -260,26 +247,14 @@ int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_can
     const size_t nc = (size_t)n_cand, rows = (size_t)nodes_cap * store_stride;
     lsd_polar *d_sc, *d_store; int *d_len, *d_sl; lsd_position* d_po; lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_track* d_tr;
     lsd_pg_append_rep* d_rep;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) {
-        k(d_sc, nc * stride); k(d_len, nc); k(d_po, nc); k(d_head, 1); k(d_no, nodes_cap); k(d_ed, edges_cap); k(d_tr, 1); k(d_store, rows);
-        k(d_sl, nodes_cap); k(d_rep, 1);
+    auto plan = [&](StagePass& k) {
+        k.in(d_sc, scans, nc * stride); k.in(d_len, lens, nc); k.in(d_po, poses, nc); k.both(d_head, head, 1); k.both(d_no, nodes, nodes_cap);
+        k.both(d_ed, edges, edges_cap); k.both(d_tr, track_rec, 1); k.both(d_store, store, rows); k.both(d_sl, store_lens, nodes_cap); k.out(d_rep, rep, 1);
     };
-    HIPCHK(c, carve(c->stage, regions));
-    struct Trip { void* dev; void* host; size_t bytes; };
-    const Trip in[] = {{d_sc, const_cast<lsd_polar*>(scans), nc * stride * sizeof(lsd_polar)}, {d_len, const_cast<int*>(lens), nc * sizeof(int)},
-                       {d_po, const_cast<lsd_position*>(poses), nc * sizeof(lsd_position)}};
-    const Trip both[] = {{d_head, head, sizeof *head}, {d_no, nodes, nodes_cap * sizeof(lsd_pg_node)}, {d_ed, edges, edges_cap * sizeof(lsd_pg_edge)},
-                         {d_tr, track_rec, sizeof *track_rec}, {d_store, store, rows * sizeof(lsd_polar)}, {d_sl, store_lens, nodes_cap * sizeof(int)}};
-    for (const Trip& t : in) HIPCHK(c, hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, c->stream));
-    for (const Trip& t : both) HIPCHK(c, hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, c->stream));
-    const int st = lsd_enqueue_pg_append_device(c, d_sc, d_len, n_cand, stride, d_po, sizeof(lsd_position), d_head, d_no, nodes_cap, d_ed, edges_cap,
-                                                d_tr, track, d_store, d_sl, store_stride, par, d_rep, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    for (const Trip& t : both) HIPCHK(c, hipMemcpyAsync(t.host, t.dev, t.bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_append_device(c, d_sc, d_len, n_cand, stride, d_po, sizeof(lsd_position), d_head, d_no, nodes_cap, d_ed, edges_cap, d_tr,
+                                            track, d_store, d_sl, store_stride, par, d_rep, c->stream);
+    });
 }
 
 }  // extern "C"
@@ -291,23 +266,13 @@ static int pg_relax_host(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edg
     if (pg_relax_par_bad(par)) return LSD_ERR_INVALID;
     const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
     const lsd_pg_head head{n_nodes, n_edges};
-    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; lsd_pg_robust_rep* d_rob = nullptr; uint8_t* d_ws;
-    HIPCHK(c, hipSetDevice(c->device));
-    auto regions = [&](Carver& k) {                                        // (the plain entry stages what it always staged)
-        k(d_head, 1); k(d_no, nc); k(d_ed, ec); k(d_rep, 1); k(d_ws, pg_ws_bytes(nc, ec));
-        if (rob) k(d_rob, 1);
+    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; lsd_pg_robust_rep* d_rob; uint8_t* d_ws;
+    auto plan = [&](StagePass& k) {                                        // (no nodes, no edges: the region of one still has its address)
+        k.in(d_head, &head, 1); k.both(d_no, nodes, n_nodes); k.both(d_ed, edges, n_edges); k.out(d_rep, rep, 1); k.scratch(d_ws, pg_ws_bytes(nc, ec));
+        k.out(d_rob, rob_rep, 1);
     };
-    HIPCHK(c, carve(c->stage, regions));
-    HIPCHK(c, hipMemcpyAsync(d_head, &head, sizeof head, hipMemcpyHostToDevice, c->stream));
-    if (n_nodes) HIPCHK(c, hipMemcpyAsync(d_no, nodes, n_nodes * sizeof(lsd_pg_node), hipMemcpyHostToDevice, c->stream));
-    if (n_edges) HIPCHK(c, hipMemcpyAsync(d_ed, edges, n_edges * sizeof(lsd_pg_edge), hipMemcpyHostToDevice, c->stream));
-    const int st = rob ? lsd_enqueue_pg_relax_robust_device(c, 1, d_head, d_no, nc, d_ed, ec, par, *rob, d_ws, d_rep, d_rob, c->stream)
-                       : lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
-    if (st != LSD_OK) { (void)hipStreamSynchronize(c->stream); return st; }      // (a HIP failure: the uploads still read the caller's arrays)
-    if (n_nodes) HIPCHK(c, hipMemcpyAsync(nodes, d_no, n_nodes * sizeof(lsd_pg_node), hipMemcpyDeviceToHost, c->stream));
-    if (n_edges) HIPCHK(c, hipMemcpyAsync(edges, d_ed, n_edges * sizeof(lsd_pg_edge), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rep, d_rep, sizeof *rep, hipMemcpyDeviceToHost, c->stream));
-    if (rob) HIPCHK(c, hipMemcpyAsync(rob_rep, d_rob, sizeof *rob_rep, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LSD_OK;
+    return stage_round_trip(c, plan, [&] {
+        return rob ? lsd_enqueue_pg_relax_robust_device(c, 1, d_head, d_no, nc, d_ed, ec, par, *rob, d_ws, d_rep, d_rob, c->stream)
+                   : lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
+    });
 }
