@@ -1233,10 +1233,66 @@ int lsd_enqueue_pg_recognize_device(lsd_ctx *ctx, const lsd_pg_head *d_head, con
                                     const lsd_pg_desc *d_desc, lsd_pg_place_par par, uint32_t *d_work, lsd_pg_place_rec *d_recs,
                                     lsd_pg_place_rep *d_rep, lsd_pg_near_rec *d_near, lsd_position *d_sel, lsd_polar *d_q_scan,
                                     int *d_q_len, lsd_position *d_q_pose, void *stream);
+/* Every loop of a track in one pass (csrc/k_pgloops.hip; restated in tests/pose_graph_loops_cases.py): the entry above
+ * asks for ONE keyframe, the track's last; these three ask for a range of them, choose the distinct loops among the answers and hand each
+ * to the closure chain, all on the device.  Integers only.
+ * lsd_enqueue_pg_recognize_all_device: the keyframes q_lo .. q_lo + n_q - 1 as queries in one launch.  For q = 0..n_q-1, j = q_lo + q:
+ *   d_recs[q * k .. q * k + k - 1] and d_reps[q] receive exactly the bytes lsd_enqueue_pg_recognize_device writes to d_recs and d_rep when
+ *   d_track->last == j: N clamped on the device, the usability test, the candidates i <= j - gap, (dist, shift) with the smallest shift
+ *   among equals, k rounds with `spread`, (-1, 0, 0, 0) for a round without a candidate, and the report of a j outside the nodes
+ *   (query = j, no candidate, nothing picked).  No near record, selection or gather; par.pick and par.window are checked and not used.
+ * One launch, ONE WORKGROUP PER QUERY, the heaviest (largest j) first; the keys of a query live in the workgroup's LDS (nodes_cap words) in
+ * the place of d_work: no workspace.  Every loop is bounded by a parameter, no workgroup waits for another, no host wait.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; nodes_cap outside 1..16384; the parameters the entry
+ * above refuses; q_lo < 0, n_q < 0 or q_lo + n_q > nodes_cap; d_head, d_desc, d_recs or d_reps not 8-byte aligned.  n_q == 0 launches
+ * nothing. */
+int lsd_enqueue_pg_recognize_all_device(lsd_ctx *ctx, const lsd_pg_head *d_head, int nodes_cap, const lsd_pg_desc *d_desc,
+                                        lsd_pg_place_par par, int q_lo, int n_q, lsd_pg_place_rec *d_recs /* n_q * par.k */,
+                                        lsd_pg_place_rep *d_reps /* n_q */, void *stream);
+/* lsd_enqueue_pg_loops_device: the distinct loops among the records d_recs[n_q * k], d_reps[n_q] that the entry above left for (q_lo,
+ * n_q, k), given the closures the graph already has (d_head, d_edges; E = min(max(n_edges, 0), edges_cap), read on the device).
+ *   A PAIR is a record with anchor >= 0; its query is d_reps[q].query.  n_pairs counts them.
+ *   A pair (q, a) is KNOWN iff some edge e < E has LSD_PG_EDGE_CLOSURE set, |q - max(e.i, e.j)| <= spread and |a - min(e.i, e.j)| <=
+ *   spread -- DISABLED and REJECTED or not.  n_known counts them; a known pair takes no part in the rounds.
+ *   Rounds m = 0..max_loops-1: among the pairs neither known nor suppressed the one with the smallest (dist, query, anchor) becomes
+ *   d_loops[m] = (query, anchor, shift, dist) and suppresses every pair with |q' - q| <= spread and |a' - a| <= spread; a round without a
+ *   pair writes (-1, -1, 0, 0).  n_loops is the number of rounds filled.  d_rep = (n_pairs, n_known, n_loops, 0).
+ * Three launches: the closure edges compacted (one workgroup), one lane per record against them (known or not), the rounds in one
+ * workgroup -- keys of distinct integers, so no reduction order matters.  d_workspace: lsd_pg_loops_workspace_bytes(n_q, k, edges_cap)
+ * bytes of the caller's, 8-byte aligned, their contents unspecified (0 for arguments this entry refuses).  n_q == 0 is "no pair".
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer; nodes_cap outside 1..16384, edges_cap outside
+ * 1..65536; max_loops outside 1..LSD_PG_LOOPS_MAX; spread < 0; k outside 1..LSD_PG_PLACE_MAX; q_lo < 0, n_q < 0 or q_lo + n_q >
+ * nodes_cap; a pointer not 8-byte aligned. */
+typedef struct lsd_pg_loops_par { int32_t max_loops, spread; } lsd_pg_loops_par;                          /* 8 bytes */
+typedef struct lsd_pg_loop_rec  { int32_t query, anchor, shift; uint32_t dist; } lsd_pg_loop_rec;          /* 16 bytes */
+typedef struct lsd_pg_loops_rep { int32_t n_pairs, n_known, n_loops, reserved; } lsd_pg_loops_rep;         /* 16 bytes */
+#define LSD_PG_LOOPS_MAX 64
+size_t lsd_pg_loops_workspace_bytes(int n_q, int k, int edges_cap);
+int lsd_enqueue_pg_loops_device(lsd_ctx *ctx, const lsd_pg_place_rec *d_recs, const lsd_pg_place_rep *d_reps, int q_lo, int n_q, int k,
+                                const lsd_pg_head *d_head, int nodes_cap, const lsd_pg_edge *d_edges, int edges_cap, lsd_pg_loops_par par,
+                                void *d_workspace, lsd_pg_loop_rec *d_loops /* par.max_loops */, lsd_pg_loops_rep *d_rep, void *stream);
+/* lsd_enqueue_pg_loop_select_device: what lsd_enqueue_pg_recognize_device leaves, for loop m.  With L = d_loops[m] (d_loops holds at least
+ * m + 1 records) the outputs d_near, d_sel, d_q_scan, d_q_len and d_q_pose are written exactly as that entry writes them for the anchor
+ * L.anchor, shift L.shift, dist L.dist and the query j = L.query: d_near = (anchor, j, n_cand = d_loops_rep->n_loops, 0, d2 = (double)dist);
+ * d_sel[k] = node k's pose iff |k - anchor| <= window and k <= j - gap, else the sentinel; the gathered row is store row j with its
+ * length; d_q_pose = (x_A, y_A, wrap(ang_A - shift * 5.625)).  An unfilled m (query == -1) gives that entry's "no query" outputs: anchor
+ * -1, d_q_len = 0, the sentinel pose, the row keeps its bytes, d_sel all sentinels.  (A query outside 0..N-1 reads as no query and an anchor
+ * outside 0..N-1 as no anchor: records that no batch left.)  lsd_enqueue_pg_closure_device takes the query from the near record, so the
+ * chain behind lsd_enqueue_pg_near_device runs on these outputs unchanged.  One launch of one workgroup.  LSD_ERR_INVALID before anything
+ * is enqueued, outputs untouched: a null pointer; nodes_cap outside 1..16384; store_stride outside 1..the context's scan capacity; gap < 1
+ * or window < 0; m outside 0..LSD_PG_LOOPS_MAX-1; the alignments of lsd_enqueue_pg_near_device, d_loops and d_loops_rep 8-byte. */
+int lsd_enqueue_pg_loop_select_device(lsd_ctx *ctx, const lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap,
+                                      const lsd_polar *d_store, const int *d_store_lens, int store_stride, int gap, int window,
+                                      const lsd_pg_loop_rec *d_loops, const lsd_pg_loops_rep *d_loops_rep, int m, lsd_pg_near_rec *d_near,
+                                      lsd_position *d_sel, lsd_polar *d_q_scan, int *d_q_len, lsd_position *d_q_pose, void *stream);
 /* Host conveniences: host arrays of any alignment, staged through the context; blocking.
  * lsd_pg_describe: n scans (scans[n * stride], lens[n]) -> desc_out[n], every row described; n outside 0..16384: LSD_ERR_INVALID.
  * lsd_pg_recognize: desc[n_nodes] and a query index -> recs[par.k] and rep; no selection and no gather are written, par.window is
  * checked and not used; n_nodes outside 1..16384: LSD_ERR_INVALID.
+ * lsd_pg_recognize_all: desc[n_nodes] and the queries q_lo .. q_lo + n_q - 1 -> recs[n_q * par.k] and reps[n_q], around
+ * lsd_enqueue_pg_recognize_all_device with nodes_cap = n_nodes; n_nodes outside 1..16384: LSD_ERR_INVALID; n_q == 0 writes nothing.
+ * lsd_pg_loops: recs[n_q * k], reps[n_q] and the graph's edges[n_edges] -> loops[par.max_loops] and rep, around
+ * lsd_enqueue_pg_loops_device; n_q outside 0..16384 or n_edges outside 0..65536: LSD_ERR_INVALID.
  * lsd_pg_relax: one graph; nodes[n_nodes] and edges[n_edges] are updated in place, rep receives the report.
  * lsd_pg_relax_robust: the same around lsd_enqueue_pg_relax_robust_device; rep and rob_rep receive the two reports.
  * lsd_pg_append: the graph (head, nodes[nodes_cap], edges[edges_cap], track, store, store_lens) makes the round trip around the device
@@ -1251,6 +1307,10 @@ int lsd_pg_append(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_c
 int lsd_pg_describe(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n, int stride, double range_max, lsd_pg_desc *desc_out);
 int lsd_pg_recognize(lsd_ctx *ctx, const lsd_pg_desc *desc, int n_nodes, int query, lsd_pg_place_par par, lsd_pg_place_rec *recs,
                      lsd_pg_place_rep *rep);
+int lsd_pg_recognize_all(lsd_ctx *ctx, const lsd_pg_desc *desc, int n_nodes, int q_lo, int n_q, lsd_pg_place_par par,
+                         lsd_pg_place_rec *recs, lsd_pg_place_rep *reps);
+int lsd_pg_loops(lsd_ctx *ctx, const lsd_pg_place_rec *recs, const lsd_pg_place_rep *reps, int n_q, int k, const lsd_pg_edge *edges,
+                 int n_edges, lsd_pg_loops_par par, lsd_pg_loop_rec *loops, lsd_pg_loops_rep *rep);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

@@ -248,6 +248,17 @@ PG_DESC_DTYPE = np.dtype([("v", "u1", (PG_DESC_SECTORS,)), ("n_hits", "u4"), ("n
 PG_PLACE_REC_DTYPE = np.dtype([("anchor", "i4"), ("shift", "i4"), ("dist", "u4"), ("reserved", "u4")])
 PG_PLACE_REP_DTYPE = np.dtype([("query", "i4"), ("n_cand", "i4"), ("n_picked", "i4"), ("reserved", "i4")])
 assert (PG_DESC_DTYPE.itemsize, PG_PLACE_REC_DTYPE.itemsize, PG_PLACE_REP_DTYPE.itemsize, C.sizeof(lsd_pg_place)) == (72, 16, 16, 32)
+# every loop of a track in one pass
+
+
+class lsd_pg_loops(C.Structure):       # the C side's lsd_pg_loops_par
+    _fields_ = [("max_loops", C.c_int32), ("spread", C.c_int32)]
+
+
+PG_LOOPS_MAX = 64
+PG_LOOP_REC_DTYPE = np.dtype([("query", "i4"), ("anchor", "i4"), ("shift", "i4"), ("dist", "u4")])
+PG_LOOPS_REP_DTYPE = np.dtype([("n_pairs", "i4"), ("n_known", "i4"), ("n_loops", "i4"), ("reserved", "i4")])
+assert (PG_LOOP_REC_DTYPE.itemsize, PG_LOOPS_REP_DTYPE.itemsize, C.sizeof(lsd_pg_loops)) == (16, 16, 8)
 
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
@@ -380,6 +391,12 @@ _ABI = {
     "lsd_enqueue_pg_recognize_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, lsd_pg_place, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lsd_pg_describe": (_i, [_vp, _vp, _vp, _i, _i, _dbl, _vp]),
     "lsd_pg_recognize": (_i, [_vp, _vp, _i, _i, lsd_pg_place, _vp, _vp]),
+    "lsd_enqueue_pg_recognize_all_device": (_i, [_vp, _vp, _i, _vp, lsd_pg_place, _i, _i, _vp, _vp, _vp]),
+    "lsd_pg_loops_workspace_bytes": (_sz, [_i, _i, _i]),
+    "lsd_enqueue_pg_loops_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, lsd_pg_loops, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_pg_loop_select_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lsd_pg_recognize_all": (_i, [_vp, _vp, _i, _i, _i, lsd_pg_place, _vp, _vp]),
+    "lsd_pg_loops": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, lsd_pg_loops, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -980,6 +997,54 @@ class Context:
         recs, rep = np.zeros(min(max(int(par.k), 1), PG_PLACE_MAX), PG_PLACE_REC_DTYPE), np.zeros(1, PG_PLACE_REP_DTYPE)
         self._chk(self.L.lsd_pg_recognize(self.h, de.ctypes.data if len(de) else None, len(de), int(query), par, recs.ctypes.data, rep.ctypes.data))
         return recs, rep[0]
+
+    def enqueue_pg_recognize_all_device(self, d_head, nodes_cap, d_desc, place, q_lo, n_q, d_recs, d_reps, stream=None):
+        """lsd_enqueue_pg_recognize_all_device on raw device addresses: the keyframes q_lo .. q_lo + n_q - 1 as queries in one launch;
+        d_recs (PG_PLACE_REC_DTYPE [n_q, k]) and d_reps (PG_PLACE_REP_DTYPE [n_q]) receive, per query, the bytes
+        enqueue_pg_recognize_device writes for it.  place: pg_place().  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_recognize_all_device(self.h, d_head, int(nodes_cap), d_desc, pg_place(place), int(q_lo), int(n_q), d_recs,
+                                                                    d_reps, stream))
+
+    def enqueue_pg_loops_device(self, d_recs, d_reps, q_lo, n_q, k, d_head, nodes_cap, d_edges, edges_cap, loops, d_workspace, d_loops, d_rep,
+                                stream=None):
+        """lsd_enqueue_pg_loops_device on raw device addresses: the distinct loops (d_loops: PG_LOOP_REC_DTYPE [max_loops]; d_rep: one
+        PG_LOOPS_REP_DTYPE) among the records enqueue_pg_recognize_all_device left for (q_lo, n_q, k), pairs near a closure edge of the
+        graph left out.  loops: pg_loops(); d_workspace: pg_loops_workspace_bytes(n_q, k, edges_cap) bytes.  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_loops_device(self.h, d_recs, d_reps, int(q_lo), int(n_q), int(k), d_head, int(nodes_cap), d_edges,
+                                                            int(edges_cap), pg_loops(loops), d_workspace, d_loops, d_rep, stream))
+
+    def enqueue_pg_loop_select_device(self, d_head, d_nodes, nodes_cap, d_store, d_store_lens, store_stride, gap, window, d_loops, d_loops_rep, m,
+                                      d_near, d_sel, d_q_scan, d_q_len, d_q_pose, stream=None):
+        """lsd_enqueue_pg_loop_select_device on raw device addresses: what enqueue_pg_recognize_device leaves -- near record, selection, the
+        gathered query, the anchor's pose turned by the shift -- for loop m of enqueue_pg_loops_device's records.  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_loop_select_device(self.h, d_head, d_nodes, int(nodes_cap), d_store, d_store_lens, int(store_stride),
+                                                                  int(gap), int(window), d_loops, d_loops_rep, int(m), d_near, d_sel, d_q_scan,
+                                                                  d_q_len, d_q_pose, stream))
+
+    def pg_recognize_all(self, desc, q_lo=0, n_q=None, place=None):
+        """lsd_pg_recognize_all from host arrays: desc PG_DESC_DTYPE [n] and the queries q_lo .. q_lo + n_q - 1 (n_q None: up to n) ->
+        (records PG_PLACE_REC_DTYPE [n_q, k], reports PG_PLACE_REP_DTYPE [n_q]).  place: pg_place().  Blocking."""
+        de, par = np.ascontiguousarray(desc, PG_DESC_DTYPE).reshape(-1), pg_place(place)
+        nq = len(de) - int(q_lo) if n_q is None else int(n_q)
+        recs, reps = np.zeros((max(nq, 0), max(par.k, 0)), PG_PLACE_REC_DTYPE), np.zeros(max(nq, 0), PG_PLACE_REP_DTYPE)
+        self._chk(self.L.lsd_pg_recognize_all(self.h, de.ctypes.data if len(de) else None, len(de), int(q_lo), nq, par, recs.ctypes.data,
+                                              reps.ctypes.data))
+        return recs, reps
+
+    def pg_loops(self, recs, reps, edges, loops=None):
+        """lsd_pg_loops from host arrays: recs PG_PLACE_REC_DTYPE [n_q, k] and reps PG_PLACE_REP_DTYPE [n_q] as pg_recognize_all returns
+        them, the graph's edges PG_EDGE_DTYPE [m] -> (loops PG_LOOP_REC_DTYPE [max_loops], report PG_LOOPS_REP_DTYPE).  loops:
+        pg_loops().  Blocking."""
+        rp = np.ascontiguousarray(reps, PG_PLACE_REP_DTYPE).reshape(-1)
+        rc = np.ascontiguousarray(recs, PG_PLACE_REC_DTYPE)
+        k = rc.shape[-1] if rc.ndim == 2 else (rc.size // len(rp) if len(rp) else 1)
+        rc, ed, par = rc.reshape(-1), np.ascontiguousarray(edges, PG_EDGE_DTYPE).reshape(-1), pg_loops(loops)
+        if len(rc) != len(rp) * k:
+            raise LsdError(LSD_ERR_INVALID, "recs must be [n_q, k] with one report per query")
+        out, rep = np.zeros(min(max(par.max_loops, 1), PG_LOOPS_MAX), PG_LOOP_REC_DTYPE), np.zeros(1, PG_LOOPS_REP_DTYPE)
+        self._chk(self.L.lsd_pg_loops(self.h, rc.ctypes.data if len(rc) else None, rp.ctypes.data if len(rp) else None, len(rp), int(k),
+                                      ed.ctypes.data if len(ed) else None, len(ed), par, out.ctypes.data, rep.ctypes.data))
+        return out, rep[0]
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
@@ -1731,6 +1796,27 @@ def pg_place(place=None, gap=None, window=None, spread=None, k=None, pick=None, 
     return lsd_pg_place(*ints, *us, 0)
 
 
+PG_LOOPS_DEFAULTS = dict(max_loops=8, spread=2)
+
+
+def pg_loops(loops=None, max_loops=None, spread=None):
+    """An lsd_pg_loops: at most max_loops (1..64) distinct loops are chosen among the records of a batch of queries; a chosen loop
+    (query, anchor) suppresses every pair within `spread` of it on both axes, and a pair that near to a closure edge the graph already
+    has is left out.  DESIGN.md 8.1.18."""
+    a = _pg_par(lsd_pg_loops, loops, PG_LOOPS_DEFAULTS, dict(max_loops=max_loops, spread=spread))
+    if isinstance(a, lsd_pg_loops):
+        return a
+    ints = [int(a[n]) for n in ("max_loops", "spread")]
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in ints):
+        raise LsdError(LSD_ERR_INVALID, "max_loops and spread are int32")
+    return lsd_pg_loops(*ints)
+
+
+def pg_loops_workspace_bytes(n_q, k, edges_cap):
+    """lsd_pg_loops_workspace_bytes: the workspace of enqueue_pg_loops_device; 0 for arguments it refuses."""
+    return int(load_library().lsd_pg_loops_workspace_bytes(int(n_q), int(k), int(edges_cap)))
+
+
 def pg_workspace_bytes(nodes_cap, edges_cap):
     """lsd_pg_workspace_bytes: the workspace of ONE graph of the relaxation; 0 for caps outside 1..16384 / 1..65536."""
     return int(load_library().lsd_pg_workspace_bytes(int(nodes_cap), int(edges_cap)))
@@ -2298,8 +2384,9 @@ class PoseGraph:
     The graph owns head, nodes, edges, tracks, the keyframe store and the workspace as torch tensors; the counts live on the device.
     optimize_device() makes the relaxation robust against closures that are confidently wrong and takes them out on the device (DESIGN.md
     8.1.16); close_place_device() finds the anchor of a closure by the appearance of the scan where the drift has carried the pose out of
-    close_device()'s radius.  Everything but nodes(), edges(), place_records(), the *report() methods
-    and disable_edges() is enqueued without waiting for the device."""
+    close_device()'s radius; close_all_device() asks that of every keyframe in one launch and closes every distinct
+    loop it finds.  Everything but nodes(), edges(), place_records(), loop_records(), the *report() and *reports()
+    methods and disable_edges() is enqueued without waiting for the device."""
 
     def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
         import torch
@@ -2327,6 +2414,13 @@ class PoseGraph:
         self._desc, self._place_work = z(self.nodes_cap, PG_DESC_DTYPE.itemsize), z(self.nodes_cap, dtype=torch.int32)
         self._place_recs, self._place_rep = z(PG_PLACE_MAX, PG_PLACE_REC_DTYPE.itemsize), z(PG_PLACE_REP_DTYPE.itemsize)
         self._desc_range_max = None
+        # every loop of a track: the batch's records, the loops, and per loop what a closure attempt leaves
+        self._all_recs, self._all_reps = z(self.nodes_cap * PG_PLACE_MAX, PG_PLACE_REC_DTYPE.itemsize), z(self.nodes_cap, PG_PLACE_REP_DTYPE.itemsize)
+        self._loops_ws = z(pg_loops_workspace_bytes(self.nodes_cap, PG_PLACE_MAX, self.edges_cap))
+        self._loops, self._loops_rep = z(PG_LOOPS_MAX, PG_LOOP_REC_DTYPE.itemsize), z(PG_LOOPS_REP_DTYPE.itemsize)
+        self._loop_near, self._loop_closure_rep = z(PG_LOOPS_MAX, PG_NEAR_DTYPE.itemsize), z(PG_LOOPS_MAX, PG_CLOSURE_REP_DTYPE.itemsize)
+        self._all_q = None                                                   # (q_lo, n_q, k, gap, window) of the last recognize_all_device
+        self._loops_max = 0                                                  # max_loops of the last find_loops_device
 
     def _track(self, track):
         t = int(track)
@@ -2378,9 +2472,10 @@ class PoseGraph:
         self.near_device(track, gap, radius, window, ts)
         return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
 
-    def _close_tail(self, scratch_mapper, search, response, smear, closure, ts):
-        """What follows the choice of an anchor, by pose (near_device) or by appearance (recognize_device): the neighbourhood drawn from
-        the selection, the gathered row matched on it with its response, the closure edge."""
+    def _close_tail(self, scratch_mapper, search, response, smear, closure, ts, d_near=None, d_closure_rep=None):
+        """What follows the choice of an anchor, by pose (near_device) or by appearance (recognize_device, or loop m of
+        close_all_device, which names its own near record and closure report): the neighbourhood drawn from the selection, the gathered
+        row matched on it with its response, the closure edge."""
         scratch_mapper.clear(ts)
         scratch_mapper._enqueue(self.ctx, self._store.data_ptr(), self._store_lens.data_ptr(), self.nodes_cap, self.n_beams, self._sel.data_ptr(), 24,
                                 ts.cuda_stream)
@@ -2388,7 +2483,8 @@ class PoseGraph:
         rec, resp = scratch_mapper._chain(self.ctx, self._q_scan.data_ptr(), self._q_len.data_ptr(), 1, self.n_beams, self._q_pose.data_ptr(), 24,
                                           search, ts, response=True if response is None else response)
         self.ctx.enqueue_pg_closure_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
-                                           self._near.data_ptr(), resp.data_ptr(), closure, self._closure_rep.data_ptr(), ts.cuda_stream)
+                                           d_near or self._near.data_ptr(), resp.data_ptr(), closure,
+                                           d_closure_rep or self._closure_rep.data_ptr(), ts.cuda_stream)
         self._held_close = (rec, resp)                                       # the launches read them: alive until the next call
         return resp
 
@@ -2427,6 +2523,60 @@ class PoseGraph:
         ts = _cuda_stream(stream)
         self.recognize_device(scratch_mapper.range_max, track, place, ts)
         return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+
+    def recognize_all_device(self, range_max, place=None, q_lo=0, n_q=None, stream=None):
+        """Every keyframe of a range as a query in one launch (describe_device, then lsd_enqueue_pg_recognize_all_device): per query the
+        records and the report recognize_device would leave with that keyframe as the track's last.  n_q None: nodes_cap - q_lo; the
+        device clamps to the nodes there are.  find_loops_device chooses among the records.  On `stream`; nothing waits."""
+        ts, par = _cuda_stream(stream), pg_place(place)
+        lo = int(q_lo)
+        nq = self.nodes_cap - lo if n_q is None else int(n_q)
+        self.describe_device(range_max, ts)
+        self.ctx.enqueue_pg_recognize_all_device(self._head.data_ptr(), self.nodes_cap, self._desc.data_ptr(), par, lo, nq, self._all_recs.data_ptr(),
+                                                 self._all_reps.data_ptr(), ts.cuda_stream)
+        self._all_q = (lo, nq, int(par.k), int(par.gap), int(par.window))
+
+    def find_loops_device(self, loops=None, stream=None):
+        """The distinct loops (lsd_enqueue_pg_loops_device) among the records of the last recognize_all_device, pairs near a closure the
+        graph already has left out.  loops: pg_loops().  loop_records() and loops_report() say what was found.  On `stream`; nothing
+        waits."""
+        if self._all_q is None:
+            raise LsdError(LSD_ERR_INVALID, "find_loops_device follows recognize_all_device")
+        lo, nq, k = self._all_q[:3]
+        par = pg_loops(loops)
+        self.ctx.enqueue_pg_loops_device(self._all_recs.data_ptr(), self._all_reps.data_ptr(), lo, nq, k, self._head.data_ptr(), self.nodes_cap,
+                                         self._edges.data_ptr(), self.edges_cap, par, self._loops_ws.data_ptr(), self._loops.data_ptr(),
+                                         self._loops_rep.data_ptr(), _cuda_stream(stream).cuda_stream)
+        self._loops_max = int(par.max_loops)
+
+    def close_all_device(self, scratch_mapper, place=None, loops=None, search=None, response=None, smear=None, closure=None, stream=None):
+        """Every loop of the graph closed in one pass, on one stream: recognize_all_device over all keyframes, find_loops_device, then for
+        m = 0..max_loops-1 lsd_enqueue_pg_loop_select_device and close_device's tail with a near record, a closure report and a response
+        record of its own.  An unfilled round ends as NO_ANCHOR.  The anchors' poses do not move between the tails (closures are appended,
+        nothing is relaxed); optimize_device and rerender_device follow as after any closure.  range_max is the scratch mapper's.
+        Returns the response records, a CUDA uint8 tensor [max_loops, 192]; loop_records(), loops_report() and closure_reports() say
+        what came of it.  Nothing waits."""
+        import torch
+        if not isinstance(scratch_mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        ts = _cuda_stream(stream)
+        self.recognize_all_device(scratch_mapper.range_max, place, 0, None, ts)
+        self.find_loops_device(loops, ts)
+        gap, window = self._all_q[3:]
+        held, resps = [], []
+        for m in range(self._loops_max):
+            d_near = self._loop_near.data_ptr() + m * PG_NEAR_DTYPE.itemsize
+            self.ctx.enqueue_pg_loop_select_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._store.data_ptr(),
+                                                   self._store_lens.data_ptr(), self.n_beams, gap, window, self._loops.data_ptr(),
+                                                   self._loops_rep.data_ptr(), m, d_near, self._sel.data_ptr(), self._q_scan.data_ptr(),
+                                                   self._q_len.data_ptr(), self._q_pose.data_ptr(), ts.cuda_stream)
+            resps.append(self._close_tail(scratch_mapper, search, response, smear, closure, ts, d_near,
+                                          self._loop_closure_rep.data_ptr() + m * PG_CLOSURE_REP_DTYPE.itemsize))
+            held.append(self._held_close)
+        with torch.cuda.stream(ts):
+            out = torch.cat(resps, dim=0)
+        self._held_close = (held, out)                                       # the launches read them: alive until the next call
+        return out
 
     def relax_device(self, relax=None, stream=None, robust=None, **kw):
         """The relaxation (lsd_enqueue_pg_relax_device) of this graph: relax is pg_relax(), or its keywords (iters=, cg_iters=, cg_tol=,
@@ -2506,6 +2656,20 @@ class PoseGraph:
     def place_records(self):
         """The last recognize_device's places (PG_PLACE_REC_DTYPE [k], anchor -1 in a round that found none): a read-back."""
         return self._read(self._place_recs, PG_PLACE_REC_DTYPE)[:getattr(self, "_place_k", PG_PLACE_MAX)]
+
+    def loop_records(self):
+        """The last find_loops_device's loops (PG_LOOP_REC_DTYPE [max_loops], query -1 in a round that found none): a read-back."""
+        return self._read(self._loops, PG_LOOP_REC_DTYPE)[:self._loops_max]
+
+    def loops_report(self):
+        """The last find_loops_device's report (PG_LOOPS_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._loops_rep, PG_LOOPS_REP_DTYPE)[0]
+
+    def closure_reports(self):
+        """(the near records PG_NEAR_DTYPE [max_loops], the closure reports PG_CLOSURE_REP_DTYPE [max_loops]) of the last
+        close_all_device, one per round: a read-back."""
+        n = self._loops_max
+        return self._read(self._loop_near, PG_NEAR_DTYPE)[:n], self._read(self._loop_closure_rep, PG_CLOSURE_REP_DTYPE)[:n]
 
     def append_report(self):
         """The last append's report (PG_APPEND_REP_DTYPE): a read-back, which waits for the device."""

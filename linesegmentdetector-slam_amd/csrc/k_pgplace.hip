@@ -4,15 +4,13 @@
 // record, the selection and the gathered query of the chosen one (k_pg_place_pick, after k_pg_prune's rounds and k_pg_near's outputs).
 // One quantisation in fp64 without FMA; every sum after it is an integer's, so no order matters.
 #include "lsd_internal.h"
+#include "pgplace_dev.h"
 #include "posegraph_dev.h"
 
 namespace lsdhip {
 
-constexpr int kPlLanes = 256, kPlScoreLanes = 64, kPlSectors = LSD_PG_DESC_SECTORS;
-constexpr uint32_t kPlNone = 0xffffffffu;                         // d_work of a node that is no candidate
-static_assert(sizeof(lsd_pg_desc) == 72 && offsetof(lsd_pg_desc, n_hits) == 64 && offsetof(lsd_pg_desc, n_sectors) == 68 &&
-              offsetof(lsd_pg_desc, valid) == 70, "lsd_pg_desc: 64 sector bytes, the counts behind them");
-static_assert(sizeof(lsd_polar) == 16 && kPlSectors == 64, "a reading is one 16-byte access; a descriptor is 16 dwords");
+constexpr int kPlLanes = 256, kPlScoreLanes = 64;
+static_assert(sizeof(lsd_polar) == 16, "a reading is one 16-byte access");
 
 // One workgroup per row: the lanes stride over the readings (16 bytes each), two arrays of 64 counters in LDS, 64 lanes write the record.
 __global__ __launch_bounds__(kPlLanes) void k_pg_describe(const lsd_pg_head* head, int nodes_cap, const lsd_polar* __restrict__ store,
@@ -52,27 +50,7 @@ __global__ __launch_bounds__(kPlLanes) void k_pg_describe(const lsd_pg_head* hea
     }
 }
 
-__device__ __forceinline__ uint32_t pl_sad(uint32_t a, uint32_t b, uint32_t acc) {
-#if __has_builtin(__builtin_amdgcn_sad_u8)
-    return __builtin_amdgcn_sad_u8(a, b, acc);                               // four |byte - byte| added to acc
-#else
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int d = (int)((a >> (8 * k)) & 255u) - (int)((b >> (8 * k)) & 255u);
-        acc += (uint32_t)(d < 0 ? -d : d);
-    }
-    return acc;
-#endif
-}
-
-__device__ __forceinline__ bool pl_usable(const lsd_pg_desc* desc, int j, int n_nodes, uint32_t min_sectors) {
-    return j >= 0 && j < n_nodes && desc[j].valid != 0 && desc[j].n_sectors >= min_sectors;
-}
-
-// One lane per candidate, its 64 bytes in 16 registers.  The query is the same for every lane: it sits in LDS doubled and turned by
-// 0..3 bytes -- s_q[r][w] holds a.v[(4 w + r + 0..3) mod 64] --, so that shift s = 4 m + r pairs the candidate's dword k with
-// s_q[r][k + m]: one row of 32 broadcast dwords per r, no byte shuffles, 16 packed SADs per shift.  The key (D_s << 6) | s makes the
-// smallest shift win among equal distances in one unsigned minimum.
+// One lane per candidate (pgplace_dev.h: pl_score); the query is the same for every lane and sits in LDS (pl_stage_query).
 // Workgroups of one wavefront: 16384 nodes are 256 of them, one per CU.
 __global__ __launch_bounds__(kPlScoreLanes) void k_pg_place_score(const lsd_pg_head* head, int nodes_cap, const lsd_pg_track* track,
                                                              const lsd_pg_desc* __restrict__ desc, int gap, uint32_t max_dist,
@@ -81,45 +59,11 @@ __global__ __launch_bounds__(kPlScoreLanes) void k_pg_place_score(const lsd_pg_h
     const int tid = (int)threadIdx.x;
     const int n_nodes = min(max(head->n_nodes, 0), nodes_cap), j = track->last;
     const bool usable = pl_usable(desc, j, n_nodes, min_sectors);
-    if (usable) {
-        for (int t = tid; t < 128; t += kPlScoreLanes) {
-            const int r = t >> 5, w = t & 31;
-            uint32_t d = 0u;
-#pragma unroll
-            for (int b = 0; b < 4; b++) d |= (uint32_t)desc[j].v[(4 * w + r + b) & 63] << (8 * b);
-            s_q[r][w] = d;
-        }
-    }
+    if (usable) pl_stage_query(desc, j, s_q, tid, kPlScoreLanes);
     __syncthreads();
     const int limit = usable ? j - gap : -1;                                  // the last index that can be a candidate
-    for (int i = (int)blockIdx.x * kPlScoreLanes + tid; i < n_nodes; i += (int)gridDim.x * kPlScoreLanes) {
-        uint32_t key = kPlNone;
-        if (i <= limit) {
-            const uint2* cw = reinterpret_cast<const uint2*>(desc + i);      // (72-byte records, 8-byte aligned)
-            const uint32_t tail = cw[8].y;                                    // (n_sectors: bytes 68..69, valid: 70..71)
-            if ((tail >> 16) != 0u && (tail & 0xffffu) >= min_sectors) {
-                uint32_t c[16];
-#pragma unroll
-                for (int k = 0; k < 8; k++) { const uint2 v = cw[k]; c[2 * k] = v.x; c[2 * k + 1] = v.y; }
-                uint32_t best = kPlNone;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    uint32_t q[32];
-#pragma unroll
-                    for (int w = 0; w < 32; w++) q[w] = s_q[r][w];
-#pragma unroll
-                    for (int m = 0; m < 16; m++) {
-                        uint32_t d = 0u;
-#pragma unroll
-                        for (int k = 0; k < 16; k++) d = pl_sad(q[k + m], c[k], d);
-                        best = min(best, (d << 6) | (uint32_t)(4 * m + r));
-                    }
-                }
-                if ((best >> 6) <= max_dist) key = best;
-            }
-        }
-        work[i] = key;
-    }
+    for (int i = (int)blockIdx.x * kPlScoreLanes + tid; i < n_nodes; i += (int)gridDim.x * kPlScoreLanes)
+        work[i] = i <= limit ? pl_score(desc, i, s_q, min_sectors, max_dist) : kPlNone;
 }
 
 // The rounds of k_pg_prune with (dist, i) ascending as the order, then the outputs of k_pg_near for the anchor of round `pick`.  The host

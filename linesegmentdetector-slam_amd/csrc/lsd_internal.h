@@ -283,6 +283,16 @@ void launch_pg_recognize(const lsd_pg_head* head, const lsd_pg_node* nodes, int 
                          const int* store_lens, int store_stride, const lsd_pg_desc* desc, lsd_pg_place_par par, uint32_t* work,
                          lsd_pg_place_rec* recs, lsd_pg_place_rep* rep, lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len,
                          lsd_position* q_pose, hipStream_t s);
+// every loop of a track (k_pgloops.hip): a range of queries in one launch (an error of the runtime before anything is queued is
+// returned); the distinct loops of the batch's records (three launches; pg_loops_ws_bytes: its workspace); what recognize leaves, for loop m
+hipError_t launch_pg_recognize_all(const lsd_pg_head* head, int nodes_cap, const lsd_pg_desc* desc, lsd_pg_place_par par, int q_lo, int n_q,
+                                   lsd_pg_place_rec* recs, lsd_pg_place_rep* reps, hipStream_t s);
+size_t pg_loops_ws_bytes(int n_q, int k, int edges_cap);
+void launch_pg_loops(const lsd_pg_place_rec* recs, const lsd_pg_place_rep* reps, int n_q, int k, const lsd_pg_head* head, const lsd_pg_edge* edges,
+                     int edges_cap, lsd_pg_loops_par par, void* ws, lsd_pg_loop_rec* loops, lsd_pg_loops_rep* rep, hipStream_t s);
+void launch_pg_loop_select(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_polar* store, const int* store_lens,
+                           int store_stride, int gap, int window, const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m,
+                           lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

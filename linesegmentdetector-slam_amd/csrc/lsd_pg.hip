@@ -1,6 +1,6 @@
 // lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the six device entries
 // (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures), of
-// place recognition's two (k_pgplace.hip) and the host conveniences, each one round trip through the context's staging (lsd_ctx.h: stage_round_trip).
+// place recognition's two (k_pgplace.hip), the three that find every loop of a track (k_pgloops.hip) and the host conveniences, each one round trip through the context's staging (lsd_ctx.h: stage_round_trip).
 #include <math.h>
 #include <stddef.h>
 
@@ -22,6 +22,8 @@ static_assert(sizeof(lsd_pg_robust_par) == 16 && offsetof(lsd_pg_robust_par, del
               sizeof(lsd_pg_prune_rep) == 24 && offsetof(lsd_pg_prune_rep, worst_chi2) == 16, "the robust relaxation's and the prune's records");
 static_assert(sizeof(lsd_pg_desc) == 72 && sizeof(lsd_pg_place_par) == 32 && offsetof(lsd_pg_place_par, max_dist) == 20 && sizeof(lsd_pg_place_rec) == 16 &&
               offsetof(lsd_pg_place_rec, dist) == 8 && sizeof(lsd_pg_place_rep) == 16, "place recognition's records");
+static_assert(sizeof(lsd_pg_loops_par) == 8 && sizeof(lsd_pg_loop_rec) == 16 && offsetof(lsd_pg_loop_rec, dist) == 12 && sizeof(lsd_pg_loops_rep) == 16,
+              "the loops' records");
 
 constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
 
@@ -48,6 +50,11 @@ static bool pg_robust_par_bad(const lsd_pg_robust_par& r) {
 static bool pg_place_par_bad(const lsd_pg_place_par& p) {
     return p.gap < 1 || p.window < 0 || p.spread < 0 || p.k < 1 || p.k > LSD_PG_PLACE_MAX || p.pick < 0 || p.pick >= p.k || p.max_dist > 16320u ||
            p.min_sectors < 1 || p.min_sectors > (uint32_t)LSD_PG_DESC_SECTORS;
+}
+
+static bool pg_queries_bad(int q_lo, int n_q, int nodes_cap) { return q_lo < 0 || n_q < 0 || q_lo > nodes_cap - n_q; }
+static bool pg_loops_par_bad(const lsd_pg_loops_par& p, int k) {
+    return p.max_loops < 1 || p.max_loops > LSD_PG_LOOPS_MAX || p.spread < 0 || k < 1 || k > LSD_PG_PLACE_MAX;
 }
 
 // the two host relaxations: one graph around the device entry, rob == nullptr for the plain one
@@ -223,6 +230,95 @@ int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query
                                 nullptr, nullptr, s);
             return LSD_OK;
         });
+    });
+}
+
+int lsd_enqueue_pg_recognize_all_device(lsd_ctx* c, const lsd_pg_head* d_head, int nodes_cap, const lsd_pg_desc* d_desc, lsd_pg_place_par par,
+                                        int q_lo, int n_q, lsd_pg_place_rec* d_recs, lsd_pg_place_rep* d_reps, void* stream) {
+    if (!c || !d_head || !d_desc || !d_recs || !d_reps) return LSD_ERR_INVALID;
+    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, nodes_cap)) return LSD_ERR_INVALID;
+    if ((addr(d_head) | addr(d_desc) | addr(d_recs) | addr(d_reps)) & 7) {
+        c->err = "pg recognize all: head, descriptors, records and reports 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_q == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        HIPCHK(c, launch_pg_recognize_all(d_head, nodes_cap, d_desc, par, q_lo, n_q, d_recs, d_reps, s));
+        return LSD_OK;
+    });
+}
+
+size_t lsd_pg_loops_workspace_bytes(int n_q, int k, int edges_cap) {
+    if (n_q < 0 || n_q > kPgMaxNodes || k < 1 || k > LSD_PG_PLACE_MAX || edges_cap < 1 || edges_cap > kPgMaxEdges) return 0;
+    return pg_loops_ws_bytes(n_q, k, edges_cap);
+}
+
+int lsd_enqueue_pg_loops_device(lsd_ctx* c, const lsd_pg_place_rec* d_recs, const lsd_pg_place_rep* d_reps, int q_lo, int n_q, int k,
+                                const lsd_pg_head* d_head, int nodes_cap, const lsd_pg_edge* d_edges, int edges_cap, lsd_pg_loops_par par,
+                                void* d_workspace, lsd_pg_loop_rec* d_loops, lsd_pg_loops_rep* d_rep, void* stream) {
+    if (!c || !d_recs || !d_reps || !d_head || !d_edges || !d_workspace || !d_loops || !d_rep) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_loops_par_bad(par, k) || pg_queries_bad(q_lo, n_q, nodes_cap)) return LSD_ERR_INVALID;
+    if ((addr(d_recs) | addr(d_reps) | addr(d_head) | addr(d_edges) | addr(d_workspace) | addr(d_loops) | addr(d_rep)) & 7) {
+        c->err = "pg loops: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_loops(d_recs, d_reps, n_q, k, d_head, d_edges, edges_cap, par, d_workspace, d_loops, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_loop_select_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, const lsd_polar* d_store,
+                                      const int* d_store_lens, int store_stride, int gap, int window, const lsd_pg_loop_rec* d_loops,
+                                      const lsd_pg_loops_rep* d_loops_rep, int m, lsd_pg_near_rec* d_near, lsd_position* d_sel, lsd_polar* d_q_scan,
+                                      int* d_q_len, lsd_position* d_q_pose, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_store || !d_store_lens || !d_loops || !d_loops_rep || !d_near || !d_sel || !d_q_scan || !d_q_len || !d_q_pose)
+        return LSD_ERR_INVALID;
+    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || gap < 1 || window < 0 || m < 0 ||
+        m >= LSD_PG_LOOPS_MAX)
+        return LSD_ERR_INVALID;
+    if (((addr(d_store) | addr(d_q_scan)) & 15) ||
+        ((addr(d_head) | addr(d_nodes) | addr(d_loops) | addr(d_loops_rep) | addr(d_near) | addr(d_sel) | addr(d_q_pose)) & 7) ||
+        ((addr(d_store_lens) | addr(d_q_len)) & 3)) {
+        c->err = "pg loop select: store and d_q_scan 16-byte, the records 8-byte, the lengths 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_loop_select(d_head, d_nodes, nodes_cap, d_store, d_store_lens, store_stride, gap, window, d_loops, d_loops_rep, m, d_near, d_sel,
+                              d_q_scan, d_q_len, d_q_pose, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_recognize_all(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int q_lo, int n_q, lsd_pg_place_par par, lsd_pg_place_rec* recs,
+                         lsd_pg_place_rep* reps) {
+    if (!c || !desc || n_nodes < 1 || n_nodes > kPgMaxNodes || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, n_nodes)) return LSD_ERR_INVALID;
+    if (n_q == 0) return LSD_OK;
+    if (!recs || !reps) return LSD_ERR_INVALID;
+    const size_t nn = (size_t)n_nodes, nq = (size_t)n_q;
+    const lsd_pg_head head{n_nodes, 0};
+    lsd_pg_head* d_head; lsd_pg_desc* d_desc; lsd_pg_place_rec* d_recs; lsd_pg_place_rep* d_reps;
+    auto plan = [&](StagePass& k) { k.in(d_head, &head, 1); k.in(d_desc, desc, nn); k.out(d_recs, recs, nq * par.k); k.out(d_reps, reps, nq); };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_recognize_all_device(c, d_head, n_nodes, d_desc, par, q_lo, n_q, d_recs, d_reps, c->stream);
+    });
+}
+
+int lsd_pg_loops(lsd_ctx* c, const lsd_pg_place_rec* recs, const lsd_pg_place_rep* reps, int n_q, int k, const lsd_pg_edge* edges, int n_edges,
+                 lsd_pg_loops_par par, lsd_pg_loop_rec* loops, lsd_pg_loops_rep* rep) {
+    if (!c || !loops || !rep || n_q < 0 || n_q > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || pg_loops_par_bad(par, k)) return LSD_ERR_INVALID;
+    if ((n_q && (!recs || !reps)) || (n_edges && !edges)) return LSD_ERR_INVALID;
+    const int nc = n_q ? n_q : 1, ec = n_edges ? n_edges : 1;              // (a cap is at least 1)
+    const size_t nq = (size_t)n_q;
+    const lsd_pg_head head{nc, n_edges};
+    lsd_pg_head* d_head; lsd_pg_place_rec* d_recs; lsd_pg_place_rep* d_reps; lsd_pg_edge* d_ed; uint8_t* d_ws; lsd_pg_loop_rec* d_loops;
+    lsd_pg_loops_rep* d_rep;
+    auto plan = [&](StagePass& p) {
+        p.in(d_head, &head, 1); p.in(d_recs, recs, nq * k); p.in(d_reps, reps, nq); p.in(d_ed, edges, n_edges); p.scratch(d_ws, pg_loops_ws_bytes(n_q, k, ec));
+        p.out(d_loops, loops, par.max_loops); p.out(d_rep, rep, 1);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_loops_device(c, d_recs, d_reps, 0, n_q, k, d_head, nc, d_ed, ec, par, d_ws, d_loops, d_rep, c->stream);
     });
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip, csrc/k_pgprune.hip, csrc/k_pgplace.hip; DESIGN.md 8.1.15, 8.1.16,
-8.1.17), measured, with no threshold.  One JSON line each:
+"""Developer probe: the pose graph (csrc/k_posegraph.hip, csrc/k_pgbuild.hip, csrc/k_pgprune.hip, csrc/k_pgplace.hip, csrc/k_pgloops.hip;
+DESIGN.md 8.1.15 .. 8.1.18), measured, with no threshold.  One JSON line each:
 
   relax     lsd_enqueue_pg_relax_device on closed loops of 64 / 512 / 4096 nodes with one closure per 64 nodes, 1 and 64 graphs per launch:
             events around the launch from a warm context, the median, minimum and maximum of REPS launches.  The nodes are put back from a
@@ -18,7 +18,12 @@
             graphs next to it: events around the launches.
   close_place  one PoseGraph.close_place_device chain (describe, recognize, then close_device's tail) on the graph and the scratch grid of
             `close`.
-Usage: tools/pg_probe.py [--reps 20] [--only relax,close,optimize,place] > profiles/pg_probe.log"""
+  loops     (--only loops) on stores of 64 / 4096 / 16384 keyframes with EVERY keyframe as a query: lsd_enqueue_pg_recognize_all_device (one
+            launch) beside the same queries put through lsd_enqueue_pg_recognize_device one call each, in the same session; then
+            lsd_enqueue_pg_loops_device on the batch's records at max_loops 8 and 64; and one PoseGraph.close_all_device chain (max_loops 8)
+            on the graph and the scratch grid of `close`.
+Usage: tools/pg_probe.py [--reps 20] [--only relax,close,optimize,place] > profiles/pg_probe.log
+       tools/pg_probe.py --only loops >> profiles/pg_probe.log"""
 import argparse, importlib, json, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -113,7 +118,53 @@ def main():
         med, lo, hi = timed(fn)
         nr = d_near.cpu().numpy().view(lsd.PG_NEAR_DTYPE)[0]
         print(json.dumps(dict(what="near", nodes=n, ms_median=med, ms_min=lo, ms_max=hi, anchor=int(nr["anchor"]), candidates=int(nr["n_cand"]))), flush=True)
-    if not only & {"close", "optimize", "place"}:
+    # 2b. every keyframe as a query: the batch beside the looped single entry, then the choice of the loops
+    for n in (64, 4096, 16384) if "loops" in only else ():
+        rng = np.random.default_rng(n)
+        desc = np.zeros(n, lsd.PG_DESC_DTYPE)
+        desc["v"], desc["n_hits"], desc["n_sectors"], desc["valid"] = rng.integers(0, 256, (n, 64)), 360, 64, 1
+        gap = min(10, n // 2)
+        for j in range(2 * gap, n, 7):                                            # every seventh keyframe has been seen before, turned
+            desc["v"][j] = np.roll(desc["v"][(j * 5) % (j - gap)], j % 64)
+        tracks = np.zeros(n, lsd.PG_TRACK_DTYPE)
+        tracks["last"] = np.arange(n)
+        z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")
+        d_hd, d_desc, d_tr = dev(np.array([(n, 0)], lsd.PG_HEAD_DTYPE).view(np.uint8)), dev(desc.view(np.uint8)), dev(tracks.view(np.uint8))
+        d_no, d_st, d_ln = z(n, 64), z(n, 1, 2, dtype=torch.float64), z(n, dtype=torch.int32)
+        k = 4
+        place = lsd.pg_place(gap=gap, window=2, spread=2, k=k, pick=0, max_dist=2000, min_sectors=32)
+        d_recs, d_reps, d_recs1, d_reps1 = z(n * k, 16), z(n, 16), z(n * k, 16), z(n, 16)
+        d_work, d_near, d_sel, d_row, d_len, d_pose = z(n, dtype=torch.int32), z(24), z(n, 3, dtype=torch.float64), z(1, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(3, dtype=torch.float64)
+        batch = lambda: ctx.enqueue_pg_recognize_all_device(d_hd.data_ptr(), n, d_desc.data_ptr(), place, 0, n, d_recs.data_ptr(), d_reps.data_ptr(), s)
+
+        def looped():
+            for q in range(n):
+                ctx.enqueue_pg_recognize_device(d_hd.data_ptr(), d_no.data_ptr(), n, d_tr.data_ptr() + 32 * q, d_st.data_ptr(), d_ln.data_ptr(), 1,
+                                                d_desc.data_ptr(), place, d_work.data_ptr(), d_recs1.data_ptr() + 16 * k * q, d_reps1.data_ptr() + 16 * q,
+                                                d_near.data_ptr(), d_sel.data_ptr(), d_row.data_ptr(), d_len.data_ptr(), d_pose.data_ptr(), s)
+        med, lo, hi = timed(batch)
+        med1, lo1, hi1 = timed(looped)
+        equal = bool(torch.equal(d_recs, d_recs1) and torch.equal(d_reps, d_reps1))
+        print(json.dumps(dict(what="recognize_all", nodes=n, queries=n, k=k, ms_median=med, ms_min=lo, ms_max=hi, looped_single_ms_median=med1,
+                              looped_single_ms_min=lo1, looped_single_ms_max=hi1, speedup=med1 / med, same_bytes=equal,
+                              pairs=int((d_recs.cpu().numpy().reshape(-1).view(lsd.PG_PLACE_REC_DTYPE)["anchor"] >= 0).sum()))), flush=True)
+        ecap = 4 * n
+        d_ed, d_ws, d_loops, d_lrep = z(ecap, 96), z(lsd.pg_loops_workspace_bytes(n, k, ecap)), z(64, 16), z(16)
+        d_hd2 = dev(np.array([(n, n - 1 + n // 64)], lsd.PG_HEAD_DTYPE).view(np.uint8))
+        ed = np.zeros(ecap, lsd.PG_EDGE_DTYPE)
+        ed["i"][:n - 1], ed["j"][:n - 1] = np.arange(n - 1), np.arange(1, n)
+        for c in range(n // 64):                                                  # one closure per 64 nodes that the graph already has
+            ed[n - 1 + c] = (c * 64 // 2, c * 64 + 63, lsd.PG_EDGE_CLOSURE, 0, (0, 0, 0), (1, 0, 1, 0, 0, 1), 0)
+        d_ed.copy_(dev(ed.view(np.uint8).reshape(ecap, 96)))
+        for max_loops in (8, 64):
+            lp = lsd.pg_loops(max_loops=max_loops, spread=2)
+            fn = lambda: ctx.enqueue_pg_loops_device(d_recs.data_ptr(), d_reps.data_ptr(), 0, n, k, d_hd2.data_ptr(), n, d_ed.data_ptr(), ecap, lp,
+                                                     d_ws.data_ptr(), d_loops.data_ptr(), d_lrep.data_ptr(), s)
+            med, lo, hi = timed(fn)
+            r = d_lrep.cpu().numpy().view(lsd.PG_LOOPS_REP_DTYPE)[0]
+            print(json.dumps(dict(what="find_loops", nodes=n, records=n * k, edges=int(n - 1 + n // 64), max_loops=max_loops, ms_median=med, ms_min=lo,
+                                  ms_max=hi, pairs=int(r["n_pairs"]), known=int(r["n_known"]), loops=int(r["n_loops"]))), flush=True)
+    if not only & {"close", "optimize", "place", "loops"}:
         ctx.close()
         return 0
 
@@ -156,6 +207,16 @@ def main():
         print(json.dumps(dict(what="close_place", grid=[cols, rows], keyframes=int(graph.head()[0]), beams=n_beams, place=place, search=search,
                               ms_median=med, ms_min=lo, ms_max=hi, anchor=int(near["anchor"]), shift=int(rec["shift"]), dist=int(rec["dist"]),
                               query=int(near["query"]), candidates=int(near["n_cand"]), closure_flags=int(rep["flags"]))), flush=True)
+        restore()
+    if "loops" in only:
+        place = dict(gap=n_key // 2, window=2, spread=2, k=4, pick=0, max_dist=2000, min_sectors=32)
+        fa = lambda: graph.close_all_device(scratch, place=place, loops=dict(max_loops=8, spread=2), search=search, response=dict(rx=2, ry=2, ra=1))
+        med, lo, hi = timed(fa, restore)
+        rep, (nears, creps) = graph.loops_report(), graph.closure_reports()
+        print(json.dumps(dict(what="close_all", grid=[cols, rows], keyframes=int(graph.head()[0]), beams=n_beams, place=place, max_loops=8, search=search,
+                              ms_median=med, ms_min=lo, ms_max=hi, pairs=int(rep["n_pairs"]), known=int(rep["n_known"]), loops=int(rep["n_loops"]),
+                              anchors=[int(v) for v in nears["anchor"]], queries=[int(v) for v in nears["query"]],
+                              closure_flags=[int(v) for v in creps["flags"]])), flush=True)
         restore()
     if not only & {"close", "optimize"}:
         ctx.close()
