@@ -2428,11 +2428,25 @@ class PoseGraph:
             raise LsdError(LSD_ERR_INVALID, "track must be 0..%d" % (self.n_tracks - 1))
         return t, self._tracks.data_ptr() + t * PG_TRACK_DTYPE.itemsize
 
+    def _store_args(self):
+        """The store as every entry takes it: the rows, their lengths, the stride."""
+        return self._store.data_ptr(), self._store_lens.data_ptr(), self.n_beams
+
+    def _hand_over(self, d_near=None):
+        """What near, recognize and loop_select leave for _close_tail: the near record (the graph's own, or d_near), the selection, the
+        one-row batch, its length and its pose."""
+        return d_near or self._near.data_ptr(), self._sel.data_ptr(), self._q_scan.data_ptr(), self._q_len.data_ptr(), self._q_pose.data_ptr()
+
+    @staticmethod
+    def _scratch(scratch_mapper):
+        if not isinstance(scratch_mapper, GridMapper):
+            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+
     def _append(self, d_scans, d_lens, n, stride, d_poses, pose_pitch, track, append, ts):
         t, d_track = self._track(track)
         self.ctx.enqueue_pg_append_device(d_scans, d_lens, n, stride, d_poses, pose_pitch, self._head.data_ptr(), self._nodes.data_ptr(),
-                                          self.nodes_cap, self._edges.data_ptr(), self.edges_cap, d_track, t, self._store.data_ptr(),
-                                          self._store_lens.data_ptr(), self.n_beams, append, self._append_rep.data_ptr(), ts.cuda_stream)
+                                          self.nodes_cap, self._edges.data_ptr(), self.edges_cap, d_track, t, *self._store_args(), append,
+                                          self._append_rep.data_ptr(), ts.cuda_stream)
 
     def append_device(self, d_scans, d_lens, d_poses, pose_pitch=24, track=0, append=None, stream=None):
         """Candidate frames that are on the device (the arguments of GridMapper.integrate_device), in order, against `track`: a frame
@@ -2455,9 +2469,8 @@ class PoseGraph:
         """The loop candidate of the track's last node (lsd_enqueue_pg_near_device), into the graph's own near record, selection and
         one-row batch.  On `stream`."""
         _, d_track = self._track(track)
-        self.ctx.enqueue_pg_near_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, self._store.data_ptr(),
-                                        self._store_lens.data_ptr(), self.n_beams, gap, radius, window, self._near.data_ptr(), self._sel.data_ptr(),
-                                        self._q_scan.data_ptr(), self._q_len.data_ptr(), self._q_pose.data_ptr(), _cuda_stream(stream).cuda_stream)
+        self.ctx.enqueue_pg_near_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, *self._store_args(), gap, radius, window,
+                                        *self._hand_over(), _cuda_stream(stream).cuda_stream)
 
     def close_device(self, scratch_mapper, track=0, gap=10, radius=10.0, window=2, search=None, response=None, smear=None, closure=None,
                      stream=None):
@@ -2466,8 +2479,7 @@ class PoseGraph:
         scratch_mapper.likelihood_device(smear); match plus response of the one gathered row; the closure edge.  scratch_mapper: a
         GridMapper of the map's frame that this call overwrites.  Returns the response record of the query, a CUDA uint8 tensor
         [1, 192]; closure_report() says what came of it.  Nothing waits."""
-        if not isinstance(scratch_mapper, GridMapper):
-            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
         self.near_device(track, gap, radius, window, ts)
         return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
@@ -2495,8 +2507,8 @@ class PoseGraph:
         rm = float(range_max)
         if self._desc_range_max is not None and rm != self._desc_range_max:
             raise LsdError(LSD_ERR_INVALID, "this graph's descriptors were made with range_max %r" % self._desc_range_max)
-        self.ctx.enqueue_pg_describe_device(self._head.data_ptr(), self.nodes_cap, self._store.data_ptr(), self._store_lens.data_ptr(), self.n_beams, rm,
-                                            self._desc.data_ptr(), _cuda_stream(stream).cuda_stream)
+        self.ctx.enqueue_pg_describe_device(self._head.data_ptr(), self.nodes_cap, *self._store_args(), rm, self._desc.data_ptr(),
+                                            _cuda_stream(stream).cuda_stream)
         self._desc_range_max = rm
 
     def recognize_device(self, range_max, track=0, place=None, stream=None):
@@ -2508,18 +2520,16 @@ class PoseGraph:
         ts = _cuda_stream(stream)
         par = pg_place(place)
         self.describe_device(range_max, ts)
-        self.ctx.enqueue_pg_recognize_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, self._store.data_ptr(),
-                                             self._store_lens.data_ptr(), self.n_beams, self._desc.data_ptr(), par, self._place_work.data_ptr(),
-                                             self._place_recs.data_ptr(), self._place_rep.data_ptr(), self._near.data_ptr(), self._sel.data_ptr(),
-                                             self._q_scan.data_ptr(), self._q_len.data_ptr(), self._q_pose.data_ptr(), ts.cuda_stream)
+        self.ctx.enqueue_pg_recognize_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, d_track, *self._store_args(),
+                                             self._desc.data_ptr(), par, self._place_work.data_ptr(), self._place_recs.data_ptr(),
+                                             self._place_rep.data_ptr(), *self._hand_over(), ts.cuda_stream)
         self._place_k = int(par.k)
 
     def close_place_device(self, scratch_mapper, track=0, place=None, search=None, response=None, smear=None, closure=None, stream=None):
         """close_device with the anchor found by recognize_device instead of near_device: a loop that odometry has NOT almost closed.
         range_max is the scratch mapper's.  Returns the response record of the query; closure_report(), place_report() and
         place_records() say what came of it.  Nothing waits."""
-        if not isinstance(scratch_mapper, GridMapper):
-            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
         self.recognize_device(scratch_mapper.range_max, track, place, ts)
         return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
@@ -2557,8 +2567,7 @@ class PoseGraph:
         Returns the response records, a CUDA uint8 tensor [max_loops, 192]; loop_records(), loops_report() and closure_reports() say
         what came of it.  Nothing waits."""
         import torch
-        if not isinstance(scratch_mapper, GridMapper):
-            raise LsdError(LSD_ERR_INVALID, "scratch_mapper must be a GridMapper")
+        self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
         self.recognize_all_device(scratch_mapper.range_max, place, 0, None, ts)
         self.find_loops_device(loops, ts)
@@ -2566,10 +2575,8 @@ class PoseGraph:
         held, resps = [], []
         for m in range(self._loops_max):
             d_near = self._loop_near.data_ptr() + m * PG_NEAR_DTYPE.itemsize
-            self.ctx.enqueue_pg_loop_select_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._store.data_ptr(),
-                                                   self._store_lens.data_ptr(), self.n_beams, gap, window, self._loops.data_ptr(),
-                                                   self._loops_rep.data_ptr(), m, d_near, self._sel.data_ptr(), self._q_scan.data_ptr(),
-                                                   self._q_len.data_ptr(), self._q_pose.data_ptr(), ts.cuda_stream)
+            self.ctx.enqueue_pg_loop_select_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, *self._store_args(), gap, window,
+                                                   self._loops.data_ptr(), self._loops_rep.data_ptr(), m, *self._hand_over(d_near), ts.cuda_stream)
             resps.append(self._close_tail(scratch_mapper, search, response, smear, closure, ts, d_near,
                                           self._loop_closure_rep.data_ptr() + m * PG_CLOSURE_REP_DTYPE.itemsize))
             held.append(self._held_close)

@@ -1,6 +1,6 @@
 // k_pgbuild.hip -- what builds a pose graph on the device (include/lsd_hip.h, "pose graph", is the rule; restated in
 // tests/pose_graph_cases.py): keyframes and odometry edges from a tick's frames (k_pg_append), the loop candidate of a track's last node
-// with the poses of its neighbourhood and the query gathered into a batch of one row (k_pg_near), and the closure edge from the response
+// with the poses of its neighbourhood and the query gathered into a batch of one row (k_pg_near; posegraph_dev.h: pg_hand_over), and the closure edge from the response
 // record of that query (k_pg_closure).  One launch each, no workspace, no atomics; fp64 without FMA.
 #include "lsd_internal.h"
 #include "posegraph_dev.h"
@@ -23,8 +23,8 @@ __global__ __launch_bounds__(kPgBuildLanes) void k_pg_append(const lsd_polar* __
     uint32_t flags = 0;
     PgPose raw{0.0, 0.0, 0.0};
     if (tid == 0) {
-        n_nodes = min(max(head->n_nodes, 0), nodes_cap);
-        n_edges = min(max(head->n_edges, 0), edges_cap);
+        n_nodes = pg_n_nodes(head, nodes_cap);
+        n_edges = pg_n_edges(head, edges_cap);
         last = track->last;
         raw = PgPose{track->raw[0], track->raw[1], track->raw[2]};
     }
@@ -99,15 +99,14 @@ __global__ __launch_bounds__(kPgBuildLanes) void k_pg_append(const lsd_polar* __
 }
 
 // A lane keeps the nearest candidate of its nodes (ascending i, strictly nearer replaces: the smallest i among equals), a tree over the
-// lanes keeps (d2, i) in that order; then every lane writes its share of d_sel and of the query's row.
+// lanes keeps (d2, i) in that order; then pg_hand_over with the query's own pose.
 __global__ __launch_bounds__(kPgBuildLanes) void k_pg_near(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track,
                                                            const lsd_polar* store, const int* store_lens, int store_stride, int gap, double radius,
-                                                           int window, lsd_pg_near_rec* rec, lsd_position* sel, lsd_polar* q_scan, int* q_len,
-                                                           lsd_position* q_pose) {
+                                                           int window, PgHandOver out) {
     __shared__ double s_d2[kPgBuildLanes];
     __shared__ int s_i[kPgBuildLanes], s_n[kPgBuildLanes];
     const int tid = (int)threadIdx.x;
-    const int n_nodes = min(max(head->n_nodes, 0), nodes_cap), j = track->last;
+    const int n_nodes = pg_n_nodes(head, nodes_cap), j = track->last;
     const bool has_q = j >= 0 && j < n_nodes;
     double best = 0.0;
     int best_i = -1, count = 0;
@@ -133,30 +132,14 @@ __global__ __launch_bounds__(kPgBuildLanes) void k_pg_near(const lsd_pg_head* he
         __syncthreads();
     }
     const int anchor = s_i[0];
-    if (tid == 0) {
-        rec->anchor = anchor; rec->query = j; rec->n_cand = s_n[0]; rec->reserved = 0;
-        rec->d2 = anchor >= 0 ? s_d2[0] : 0.0;
-        q_pose->x = anchor >= 0 ? nodes[j].x : -1.0;
-        q_pose->y = anchor >= 0 ? nodes[j].y : 0.0;
-        q_pose->ang = anchor >= 0 ? nodes[j].ang : 0.0;
-        *q_len = has_q ? store_lens[j] : 0;
-    }
-    for (int k = tid; k < nodes_cap; k += kPgBuildLanes) {
-        const bool in = anchor >= 0 && abs(k - anchor) <= window && k <= j - gap;
-        sel[k].x = in ? nodes[k].x : -1.0;
-        sel[k].y = in ? nodes[k].y : 0.0;
-        sel[k].ang = in ? nodes[k].ang : 0.0;
-    }
-    if (has_q) {
-        const lsd_polar* src = store + (size_t)j * (size_t)store_stride;
-        for (int i = tid; i < store_stride; i += kPgBuildLanes) q_scan[i] = src[i];
-    }
+    const PgPose qp = tid == 0 && anchor >= 0 ? PgPose{nodes[j].x, nodes[j].y, nodes[j].ang} : PgPose{0.0, 0.0, 0.0};
+    pg_hand_over(nodes, nodes_cap, n_nodes, store, store_lens, store_stride, gap, window, j, anchor, s_n[0], s_d2[0], qp, out, tid, kPgBuildLanes);
 }
 
 __global__ void k_pg_closure(lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, const lsd_pg_near_rec* near_rec,
                              const lsd_grid_response_rec* resp, lsd_pg_closure_par par, lsd_pg_closure_rep* rep) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int n_nodes = min(max(head->n_nodes, 0), nodes_cap), n_edges = min(max(head->n_edges, 0), edges_cap);
+    const int n_nodes = pg_n_nodes(head, nodes_cap), n_edges = pg_n_edges(head, edges_cap);
     const int anchor = near_rec->anchor, query = near_rec->query;
     const uint32_t rf = resp->flags;
     const double z[3] = {resp->x, resp->y, resp->ang};
@@ -216,10 +199,9 @@ void launch_pg_append(const lsd_polar* scans, const int* lens, int n_cand, int s
 }
 
 void launch_pg_near(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track, const lsd_polar* store,
-                    const int* store_lens, int store_stride, int gap, double radius, int window, lsd_pg_near_rec* rec, lsd_position* sel,
-                    lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t st) {
+                    const int* store_lens, int store_stride, int gap, double radius, int window, PgHandOver out, hipStream_t st) {
     hipLaunchKernelGGL(k_pg_near, dim3(1), dim3(kPgBuildLanes), 0, st, head, nodes, nodes_cap, track, store, store_lens, store_stride, gap, radius,
-                       window, rec, sel, q_scan, q_len, q_pose);
+                       window, out);
 }
 
 void launch_pg_closure(lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, const lsd_pg_near_rec* near_rec,

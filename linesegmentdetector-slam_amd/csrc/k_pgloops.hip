@@ -2,7 +2,7 @@
 // tests/pose_graph_loops_cases.py): place recognition with a RANGE of keyframes as queries in one launch (k_pg_recognize_all: the hot
 // path, integers only; a query's records are the bytes lsd_enqueue_pg_recognize_device writes for it), the distinct loops among the
 // records of the batch (k_pg_loops_closures, k_pg_loops_mark, k_pg_loops_pick, after k_pg_prune's rounds) and what recognize leaves for
-// one of them (k_pg_loop_select, after k_pg_place_pick's tail), so that the closure chain runs on it unchanged.
+// one of them (k_pg_loop_select: posegraph_dev.h's pg_hand_over), so that the closure chain runs on it unchanged.
 #include "lsd_internal.h"
 #include "pgplace_dev.h"
 #include "posegraph_dev.h"
@@ -10,11 +10,12 @@
 namespace lsdhip {
 
 constexpr int kLpLanes = 256;
+static_assert(kLpLanes == kPlLanes, "pl_pick_rounds is written for workgroups of kPlLanes");
 static_assert(sizeof(lsd_polar) == 16 && sizeof(lsd_pg_loop_rec) == 16 && sizeof(lsd_pg_loops_rep) == 16, "the loops' records");
 
 // ONE WORKGROUP PER QUERY; block b takes query n_q - 1 - b, so that the heaviest (largest j: the work is triangular) start first and the
 // tail of the launch is the light ones.  The lanes stride over the candidates i <= j - gap (pl_score, the single entry's text); the keys
-// go into an LDS row of nodes_cap words in the place of d_work; k_pg_place_pick's rounds run over that row.  Keys are integers and a
+// go into an LDS row of nodes_cap words in the place of d_work; k_pg_place_pick's rounds (pl_pick_rounds) run over that row.  Keys are integers and a
 // round's winner is the minimum of distinct (dist, i): nothing depends on the schedule.  No workgroup waits for another.
 __global__ __launch_bounds__(kLpLanes) void k_pg_recognize_all(const lsd_pg_head* head, int nodes_cap, const lsd_pg_desc* __restrict__ desc,
                                                                lsd_pg_place_par par, int q_lo, int n_q, lsd_pg_place_rec* recs,
@@ -25,7 +26,7 @@ __global__ __launch_bounds__(kLpLanes) void k_pg_recognize_all(const lsd_pg_head
     __shared__ int s_n;
     const int tid = (int)threadIdx.x;
     const int q = n_q - 1 - (int)blockIdx.x, j = q_lo + q;
-    const int n_nodes = min(max(head->n_nodes, 0), nodes_cap);
+    const int n_nodes = pg_n_nodes(head, nodes_cap);
     const bool usable = pl_usable(desc, j, n_nodes, par.min_sectors);         // (q_lo + n_q <= nodes_cap: desc[j] exists)
     if (usable) pl_stage_query(desc, j, s_q, tid, kLpLanes);
     if (tid == 0) s_n = 0;
@@ -40,44 +41,8 @@ __global__ __launch_bounds__(kLpLanes) void k_pg_recognize_all(const lsd_pg_head
     if (cand) atomicAdd(&s_n, cand);
     __syncthreads();
 
-    lsd_pg_place_rec* out = recs + (size_t)q * (size_t)par.k;
-    int picked[LSD_PG_PLACE_MAX];                                             // the anchors so far: the same in every lane
-    int n_picked = 0;
-    bool dry = false;
-#pragma unroll
-    for (int r = 0; r < LSD_PG_PLACE_MAX; r++) {
-        if (r >= par.k) break;
-        int best_i = -1, best_shift = 0;
-        uint32_t best_dist = 0u;
-        if (!dry) {
-            unsigned long long km = ~0ull;
-            for (int i = tid; i <= limit; i += kLpLanes) {
-                const uint32_t w = s_row[i];
-                if (w == kPlNone) continue;
-                bool open = true;
-#pragma unroll
-                for (int p = 0; p < LSD_PG_PLACE_MAX; p++) if (p < n_picked && abs(i - picked[p]) <= par.spread) open = false;
-                if (open) km = min(km, ((unsigned long long)(w >> 6) << 32) | (unsigned long long)(uint32_t)i);
-            }
-            s_key[tid] = km;
-            __syncthreads();
-            for (int h = kLpLanes / 2; h >= 1; h >>= 1) {
-                if (tid < h) s_key[tid] = min(s_key[tid], s_key[tid + h]);
-                __syncthreads();
-            }
-            const unsigned long long top = s_key[0];
-            __syncthreads();                                                  // (every lane has read s_key[0] before the next round writes)
-            if (top == ~0ull) dry = true;                                     // (the same for every lane: no later round finds one either)
-            else {
-                best_i = (int)(uint32_t)top;
-                best_dist = (uint32_t)(top >> 32);
-                best_shift = (int)(s_row[best_i] & 63u);
-            }
-        }
-        picked[r] = best_i;
-        if (best_i >= 0) n_picked++;
-        if (tid == 0) { out[r].anchor = best_i; out[r].shift = best_shift; out[r].dist = best_dist; out[r].reserved = 0u; }
-    }
+    lsd_pg_place_rec unused;
+    const int n_picked = pl_pick_rounds([&](int i) { return s_row[i]; }, limit, par, recs + (size_t)q * (size_t)par.k, s_key, tid, unused);
     if (tid == 0) { reps[q].query = j; reps[q].n_cand = s_n; reps[q].n_picked = n_picked; reps[q].reserved = 0; }
 }
 
@@ -98,7 +63,7 @@ __host__ __device__ inline LpWs lp_carve(void* ws, int edges_cap) {
 __global__ __launch_bounds__(kLpLanes) void k_pg_loops_closures(const lsd_pg_head* head, const lsd_pg_edge* edges, int edges_cap, void* ws) {
     __shared__ int s_n;
     const LpWs w = lp_carve(ws, edges_cap);
-    const int tid = (int)threadIdx.x, E = min(max(head->n_edges, 0), edges_cap);
+    const int tid = (int)threadIdx.x, E = pg_n_edges(head, edges_cap);
     if (tid == 0) s_n = 0;
     __syncthreads();
     for (int e = tid; e < E; e += kLpLanes) {
@@ -190,36 +155,18 @@ __global__ __launch_bounds__(kLpLanes) void k_pg_loops_pick(const lsd_pg_place_r
     if (tid == 0) { rep->n_pairs = s_int[0]; rep->n_known = s_int[1]; rep->n_loops = n_loops; rep->reserved = 0; }
 }
 
-// One workgroup: k_pg_place_pick's tail for loop m.  An anchor or a query outside the nodes (records that no batch left) reads as none.
+// One workgroup: pg_hand_over for loop m.  An anchor or a query outside the nodes (records that no batch left) reads as none.
 __global__ __launch_bounds__(kLpLanes) void k_pg_loop_select(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_polar* store,
                                                              const int* store_lens, int store_stride, int gap, int window,
-                                                             const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m,
-                                                             lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len,
-                                                             lsd_position* q_pose) {
+                                                             const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m, PgHandOver out) {
     const int tid = (int)threadIdx.x;
-    const int n_nodes = min(max(head->n_nodes, 0), nodes_cap);
+    const int n_nodes = pg_n_nodes(head, nodes_cap);
     const lsd_pg_loop_rec L = loops[m];
     const int j = L.query;
     const bool has_q = j >= 0 && j < n_nodes;
     const int anchor = has_q && L.anchor >= 0 && L.anchor < n_nodes ? L.anchor : -1;
-    if (tid == 0) {
-        near_rec->anchor = anchor; near_rec->query = j; near_rec->n_cand = loops_rep->n_loops; near_rec->reserved = 0;
-        near_rec->d2 = anchor >= 0 ? (double)L.dist : 0.0;
-        q_pose->x = anchor >= 0 ? nodes[anchor].x : -1.0;
-        q_pose->y = anchor >= 0 ? nodes[anchor].y : 0.0;
-        q_pose->ang = anchor >= 0 ? pg_wrap(nodes[anchor].ang - (double)L.shift * 5.625) : 0.0;
-        *q_len = has_q ? store_lens[j] : 0;
-    }
-    for (int k = tid; k < nodes_cap; k += kLpLanes) {
-        const bool in = anchor >= 0 && abs(k - anchor) <= window && k <= j - gap;
-        sel[k].x = in ? nodes[k].x : -1.0;
-        sel[k].y = in ? nodes[k].y : 0.0;
-        sel[k].ang = in ? nodes[k].ang : 0.0;
-    }
-    if (has_q) {
-        const lsd_polar* src = store + (size_t)j * (size_t)store_stride;
-        for (int i = tid; i < store_stride; i += kLpLanes) q_scan[i] = src[i];
-    }
+    const PgPose qp = tid == 0 && anchor >= 0 ? pg_turned(nodes, anchor, L.shift) : PgPose{0.0, 0.0, 0.0};
+    pg_hand_over(nodes, nodes_cap, n_nodes, store, store_lens, store_stride, gap, window, j, anchor, loops_rep->n_loops, (double)L.dist, qp, out, tid, kLpLanes);
 }
 
 hipError_t launch_pg_recognize_all(const lsd_pg_head* head, int nodes_cap, const lsd_pg_desc* desc, lsd_pg_place_par par, int q_lo, int n_q,
@@ -245,9 +192,9 @@ void launch_pg_loops(const lsd_pg_place_rec* recs, const lsd_pg_place_rep* reps,
 
 void launch_pg_loop_select(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_polar* store, const int* store_lens,
                            int store_stride, int gap, int window, const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m,
-                           lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t st) {
+                           PgHandOver out, hipStream_t st) {
     hipLaunchKernelGGL(k_pg_loop_select, dim3(1), dim3(kLpLanes), 0, st, head, nodes, nodes_cap, store, store_lens, store_stride, gap, window, loops,
-                       loops_rep, m, near_rec, sel, q_scan, q_len, q_pose);
+                       loops_rep, m, out);
 }
 
 }  // namespace lsdhip

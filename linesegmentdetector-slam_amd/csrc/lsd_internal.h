@@ -257,13 +257,15 @@ void launch_fa_lost_gather(const lsd_fa_carry* carry, int n_seq, int frames_pitc
                            int32_t* pick, int32_t* n_lost, hipStream_t s);
 void launch_fa_seed(lsd_fa_carry* carry, int n_seq, int frames_pitch, const int32_t* pick, int n_pick, const lsd_grid_locate_rec* loc,
                     const lsd_grid_response_rec* resp, lsd_fa_seed_par par, lsd_fa_seed_rep* rep, hipStream_t s);
-// the pose graph (host side: lsd_pg.hip).  Building it (k_pgbuild.hip): one launch each, no workspace
+// the pose graph (host side: lsd_pg.hip).  What near, recognize and loop_select leave for a closure chain (posegraph_dev.h: pg_hand_over):
+// the near record, the selection of nodes_cap poses, the query's row of store_stride readings, its length and the pose the search starts from
+struct PgHandOver { lsd_pg_near_rec* rec; lsd_position* sel; lsd_polar* q_scan; int* q_len; lsd_position* q_pose; };
+// Building it (k_pgbuild.hip): one launch each, no workspace
 void launch_pg_append(const lsd_polar* scans, const int* lens, int n_cand, int stride, const void* poses, size_t pose_pitch, lsd_pg_head* head,
                       lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* track, int32_t track_id, lsd_polar* store,
                       int* store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep* rep, hipStream_t s);
 void launch_pg_near(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track, const lsd_polar* store,
-                    const int* store_lens, int store_stride, int gap, double radius, int window, lsd_pg_near_rec* rec, lsd_position* sel,
-                    lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t s);
+                    const int* store_lens, int store_stride, int gap, double radius, int window, PgHandOver out, hipStream_t s);
 void launch_pg_closure(lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, const lsd_pg_near_rec* near_rec,
                        const lsd_grid_response_rec* resp, lsd_pg_closure_par par, lsd_pg_closure_rep* rep, hipStream_t s);
 // its relaxation (k_posegraph.hip): one workgroup per graph; pg_ws_bytes: the workspace of one graph
@@ -275,14 +277,13 @@ void launch_pg_relax_robust(int n_graphs, const lsd_pg_head* heads, lsd_pg_node*
                             lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, hipStream_t s);
 void launch_pg_prune(int n_graphs, const lsd_pg_head* heads, lsd_pg_edge* edges, int edges_cap, lsd_pg_prune_par par, lsd_pg_prune_rep* rep,
                      hipStream_t s);
-// place recognition (k_pgplace.hip): the descriptors of the rows that have none; and score + pick (near_rec == nullptr: the records and
-// the report only -- nodes, store, store_lens, sel, q_scan, q_len and q_pose are not read or written then)
+// place recognition (k_pgplace.hip): the descriptors of the rows that have none; and score + pick (out.rec == nullptr: the records and
+// the report only -- nodes, store, store_lens and the rest of out are not read or written then)
 void launch_pg_describe(const lsd_pg_head* head, int nodes_cap, const lsd_polar* store, const int* store_lens, int store_stride, double range_max,
                         lsd_pg_desc* desc, hipStream_t s);
 void launch_pg_recognize(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_track* track, const lsd_polar* store,
                          const int* store_lens, int store_stride, const lsd_pg_desc* desc, lsd_pg_place_par par, uint32_t* work,
-                         lsd_pg_place_rec* recs, lsd_pg_place_rep* rep, lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len,
-                         lsd_position* q_pose, hipStream_t s);
+                         lsd_pg_place_rec* recs, lsd_pg_place_rep* rep, PgHandOver out, hipStream_t s);
 // every loop of a track (k_pgloops.hip): a range of queries in one launch (an error of the runtime before anything is queued is
 // returned); the distinct loops of the batch's records (three launches; pg_loops_ws_bytes: its workspace); what recognize leaves, for loop m
 hipError_t launch_pg_recognize_all(const lsd_pg_head* head, int nodes_cap, const lsd_pg_desc* desc, lsd_pg_place_par par, int q_lo, int n_q,
@@ -292,7 +293,7 @@ void launch_pg_loops(const lsd_pg_place_rec* recs, const lsd_pg_place_rep* reps,
                      int edges_cap, lsd_pg_loops_par par, void* ws, lsd_pg_loop_rec* loops, lsd_pg_loops_rep* rep, hipStream_t s);
 void launch_pg_loop_select(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_polar* store, const int* store_lens,
                            int store_stride, int gap, int window, const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m,
-                           lsd_pg_near_rec* near_rec, lsd_position* sel, lsd_polar* q_scan, int* q_len, lsd_position* q_pose, hipStream_t s);
+                           PgHandOver out, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

@@ -28,7 +28,15 @@ static_assert(sizeof(lsd_pg_loops_par) == 8 && sizeof(lsd_pg_loop_rec) == 16 && 
 constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
 
 static uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
-static bool pg_caps_bad(int nodes_cap, int edges_cap) { return nodes_cap < 1 || nodes_cap > kPgMaxNodes || edges_cap < 1 || edges_cap > kPgMaxEdges; }
+static bool pg_nodes_cap_bad(int nodes_cap) { return nodes_cap < 1 || nodes_cap > kPgMaxNodes; }
+static bool pg_caps_bad(int nodes_cap, int edges_cap) { return pg_nodes_cap_bad(nodes_cap) || edges_cap < 1 || edges_cap > kPgMaxEdges; }
+static bool pg_stride_bad(const lsd_ctx* c, int stride) { return stride <= 0 || stride > c->scan_cap; }
+// the hand-over's five pointers (lsd_internal.h: PgHandOver): 0 where they are all there and aligned, 1 where one is null, 2 where one is
+// not aligned -- q_scan 16-byte, the records 8-byte, q_len 4-byte
+static int pg_hand_over_bad(const PgHandOver& o) {
+    if (!o.rec || !o.sel || !o.q_scan || !o.q_len || !o.q_pose) return 1;
+    return (addr(o.q_scan) & 15) || ((addr(o.rec) | addr(o.sel) | addr(o.q_pose)) & 7) || (addr(o.q_len) & 3) ? 2 : 0;
+}
 static bool pg_real_bad(double v) { return !std::isfinite(v) || v < 0; }
 
 static bool pg_append_par_bad(const lsd_pg_append_par& p) {
@@ -68,7 +76,7 @@ int lsd_enqueue_pg_append_device(lsd_ctx* c, const lsd_polar* d_scans, const int
                                  lsd_pg_track* d_track, int32_t track, lsd_polar* d_store, int* d_store_lens, int store_stride,
                                  lsd_pg_append_par par, lsd_pg_append_rep* d_rep, void* stream) {
     if (!c || !d_scans || !d_lens || !d_poses || !d_head || !d_nodes || !d_edges || !d_track || !d_store || !d_store_lens) return LSD_ERR_INVALID;
-    if (n_cand < 0 || stride <= 0 || stride > c->scan_cap || store_stride <= 0 || store_stride > c->scan_cap) return LSD_ERR_INVALID;
+    if (n_cand < 0 || pg_stride_bad(c, stride) || pg_stride_bad(c, store_stride)) return LSD_ERR_INVALID;
     if (pose_pitch < sizeof(lsd_position) || pose_pitch % 8 || pg_caps_bad(nodes_cap, edges_cap) || pg_append_par_bad(par)) return LSD_ERR_INVALID;
     if (((addr(d_scans) | addr(d_store)) & 15) || ((addr(d_poses) | addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_track) | addr(d_rep)) & 7) ||
         ((addr(d_lens) | addr(d_store_lens)) & 3)) {
@@ -86,18 +94,16 @@ int lsd_enqueue_pg_append_device(lsd_ctx* c, const lsd_polar* d_scans, const int
 int lsd_enqueue_pg_near_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, const lsd_pg_track* d_track,
                                const lsd_polar* d_store, const int* d_store_lens, int store_stride, int gap, double radius, int window,
                                lsd_pg_near_rec* d_rec, lsd_position* d_sel, lsd_polar* d_q_scan, int* d_q_len, lsd_position* d_q_pose, void* stream) {
-    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || !d_rec || !d_sel || !d_q_scan || !d_q_len || !d_q_pose)
-        return LSD_ERR_INVALID;
-    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || gap < 1 || window < 0 || pg_real_bad(radius))
-        return LSD_ERR_INVALID;
-    if (((addr(d_store) | addr(d_q_scan)) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_track) | addr(d_rec) | addr(d_sel) | addr(d_q_pose)) & 7) ||
-        ((addr(d_store_lens) | addr(d_q_len)) & 3)) {
+    const PgHandOver out{d_rec, d_sel, d_q_scan, d_q_len, d_q_pose};
+    const int out_bad = pg_hand_over_bad(out);
+    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || out_bad == 1) return LSD_ERR_INVALID;
+    if (pg_nodes_cap_bad(nodes_cap) || pg_stride_bad(c, store_stride) || gap < 1 || window < 0 || pg_real_bad(radius)) return LSD_ERR_INVALID;
+    if ((addr(d_store) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_track)) & 7) || (addr(d_store_lens) & 3) || out_bad) {
         c->err = "pg near: store and d_q_scan 16-byte, the records 8-byte, the lengths 4-byte aligned";
         return LSD_ERR_INVALID;
     }
     return enqueue_on(c, stream, [&](hipStream_t s) {
-        launch_pg_near(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, gap, radius, window, d_rec, d_sel, d_q_scan, d_q_len,
-                       d_q_pose, s);
+        launch_pg_near(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, gap, radius, window, out, s);
         return LSD_OK;
     });
 }
@@ -168,8 +174,7 @@ int lsd_enqueue_pg_prune_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_h
 int lsd_enqueue_pg_describe_device(lsd_ctx* c, const lsd_pg_head* d_head, int nodes_cap, const lsd_polar* d_store, const int* d_store_lens,
                                    int store_stride, double range_max, lsd_pg_desc* d_desc, void* stream) {
     if (!c || !d_head || !d_store || !d_store_lens || !d_desc) return LSD_ERR_INVALID;
-    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || !(std::isfinite(range_max) && range_max > 0))
-        return LSD_ERR_INVALID;
+    if (pg_nodes_cap_bad(nodes_cap) || pg_stride_bad(c, store_stride) || !(std::isfinite(range_max) && range_max > 0)) return LSD_ERR_INVALID;
     if ((addr(d_store) & 15) || ((addr(d_head) | addr(d_desc)) & 7) || (addr(d_store_lens) & 3)) {
         c->err = "pg describe: store 16-byte, head and descriptors 8-byte, the lengths 4-byte aligned";
         return LSD_ERR_INVALID;
@@ -184,25 +189,24 @@ int lsd_enqueue_pg_recognize_device(lsd_ctx* c, const lsd_pg_head* d_head, const
                                     const lsd_polar* d_store, const int* d_store_lens, int store_stride, const lsd_pg_desc* d_desc,
                                     lsd_pg_place_par par, uint32_t* d_work, lsd_pg_place_rec* d_recs, lsd_pg_place_rep* d_rep, lsd_pg_near_rec* d_near,
                                     lsd_position* d_sel, lsd_polar* d_q_scan, int* d_q_len, lsd_position* d_q_pose, void* stream) {
-    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || !d_desc || !d_work || !d_recs || !d_rep || !d_near || !d_sel || !d_q_scan ||
-        !d_q_len || !d_q_pose)
+    const PgHandOver out{d_near, d_sel, d_q_scan, d_q_len, d_q_pose};
+    const int out_bad = pg_hand_over_bad(out);
+    if (!c || !d_head || !d_nodes || !d_track || !d_store || !d_store_lens || !d_desc || !d_work || !d_recs || !d_rep || out_bad == 1)
         return LSD_ERR_INVALID;
-    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || pg_place_par_bad(par)) return LSD_ERR_INVALID;
-    if (((addr(d_store) | addr(d_q_scan)) & 15) ||
-        ((addr(d_head) | addr(d_nodes) | addr(d_track) | addr(d_desc) | addr(d_recs) | addr(d_rep) | addr(d_near) | addr(d_sel) | addr(d_q_pose)) & 7) ||
-        ((addr(d_store_lens) | addr(d_q_len) | addr(d_work)) & 3)) {
+    if (pg_nodes_cap_bad(nodes_cap) || pg_stride_bad(c, store_stride) || pg_place_par_bad(par)) return LSD_ERR_INVALID;
+    if ((addr(d_store) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_track) | addr(d_desc) | addr(d_recs) | addr(d_rep)) & 7) ||
+        ((addr(d_store_lens) | addr(d_work)) & 3) || out_bad) {
         c->err = "pg recognize: store and d_q_scan 16-byte, the records and descriptors 8-byte, the lengths and d_work 4-byte aligned";
         return LSD_ERR_INVALID;
     }
     return enqueue_on(c, stream, [&](hipStream_t s) {
-        launch_pg_recognize(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, d_desc, par, d_work, d_recs, d_rep, d_near, d_sel,
-                            d_q_scan, d_q_len, d_q_pose, s);
+        launch_pg_recognize(d_head, d_nodes, nodes_cap, d_track, d_store, d_store_lens, store_stride, d_desc, par, d_work, d_recs, d_rep, out, s);
         return LSD_OK;
     });
 }
 
 int lsd_pg_describe(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n, int stride, double range_max, lsd_pg_desc* desc_out) {
-    if (!c || n < 0 || n > kPgMaxNodes || stride <= 0 || stride > c->scan_cap || !(std::isfinite(range_max) && range_max > 0)) return LSD_ERR_INVALID;
+    if (!c || n < 0 || n > kPgMaxNodes || pg_stride_bad(c, stride) || !(std::isfinite(range_max) && range_max > 0)) return LSD_ERR_INVALID;
     if (n == 0) return LSD_OK;
     if (!scans || !lens || !desc_out) return LSD_ERR_INVALID;
     const size_t nn = (size_t)n;
@@ -216,7 +220,7 @@ int lsd_pg_describe(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n, 
 }
 
 int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query, lsd_pg_place_par par, lsd_pg_place_rec* recs, lsd_pg_place_rep* rep) {
-    if (!c || !desc || !recs || !rep || n_nodes < 1 || n_nodes > kPgMaxNodes || pg_place_par_bad(par)) return LSD_ERR_INVALID;
+    if (!c || !desc || !recs || !rep || pg_nodes_cap_bad(n_nodes) || pg_place_par_bad(par)) return LSD_ERR_INVALID;
     const size_t nn = (size_t)n_nodes;
     const lsd_pg_head head{n_nodes, 0};
     const lsd_pg_track track{query, 0, {0.0, 0.0, 0.0}};
@@ -226,8 +230,7 @@ int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query
     };
     return stage_round_trip(c, plan, [&] {
         return enqueue_on(c, c->stream, [&](hipStream_t s) {
-            launch_pg_recognize(d_head, nullptr, n_nodes, d_tr, nullptr, nullptr, 1, d_desc, par, d_work, d_recs, d_rep, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, s);
+            launch_pg_recognize(d_head, nullptr, n_nodes, d_tr, nullptr, nullptr, 1, d_desc, par, d_work, d_recs, d_rep, PgHandOver{}, s);   // no hand-over
             return LSD_OK;
         });
     });
@@ -236,7 +239,7 @@ int lsd_pg_recognize(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int query
 int lsd_enqueue_pg_recognize_all_device(lsd_ctx* c, const lsd_pg_head* d_head, int nodes_cap, const lsd_pg_desc* d_desc, lsd_pg_place_par par,
                                         int q_lo, int n_q, lsd_pg_place_rec* d_recs, lsd_pg_place_rep* d_reps, void* stream) {
     if (!c || !d_head || !d_desc || !d_recs || !d_reps) return LSD_ERR_INVALID;
-    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, nodes_cap)) return LSD_ERR_INVALID;
+    if (pg_nodes_cap_bad(nodes_cap) || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, nodes_cap)) return LSD_ERR_INVALID;
     if ((addr(d_head) | addr(d_desc) | addr(d_recs) | addr(d_reps)) & 7) {
         c->err = "pg recognize all: head, descriptors, records and reports 8-byte aligned";
         return LSD_ERR_INVALID;
@@ -272,27 +275,23 @@ int lsd_enqueue_pg_loop_select_device(lsd_ctx* c, const lsd_pg_head* d_head, con
                                       const int* d_store_lens, int store_stride, int gap, int window, const lsd_pg_loop_rec* d_loops,
                                       const lsd_pg_loops_rep* d_loops_rep, int m, lsd_pg_near_rec* d_near, lsd_position* d_sel, lsd_polar* d_q_scan,
                                       int* d_q_len, lsd_position* d_q_pose, void* stream) {
-    if (!c || !d_head || !d_nodes || !d_store || !d_store_lens || !d_loops || !d_loops_rep || !d_near || !d_sel || !d_q_scan || !d_q_len || !d_q_pose)
-        return LSD_ERR_INVALID;
-    if (nodes_cap < 1 || nodes_cap > kPgMaxNodes || store_stride <= 0 || store_stride > c->scan_cap || gap < 1 || window < 0 || m < 0 ||
-        m >= LSD_PG_LOOPS_MAX)
-        return LSD_ERR_INVALID;
-    if (((addr(d_store) | addr(d_q_scan)) & 15) ||
-        ((addr(d_head) | addr(d_nodes) | addr(d_loops) | addr(d_loops_rep) | addr(d_near) | addr(d_sel) | addr(d_q_pose)) & 7) ||
-        ((addr(d_store_lens) | addr(d_q_len)) & 3)) {
+    const PgHandOver out{d_near, d_sel, d_q_scan, d_q_len, d_q_pose};
+    const int out_bad = pg_hand_over_bad(out);
+    if (!c || !d_head || !d_nodes || !d_store || !d_store_lens || !d_loops || !d_loops_rep || out_bad == 1) return LSD_ERR_INVALID;
+    if (pg_nodes_cap_bad(nodes_cap) || pg_stride_bad(c, store_stride) || gap < 1 || window < 0 || m < 0 || m >= LSD_PG_LOOPS_MAX) return LSD_ERR_INVALID;
+    if ((addr(d_store) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_loops) | addr(d_loops_rep)) & 7) || (addr(d_store_lens) & 3) || out_bad) {
         c->err = "pg loop select: store and d_q_scan 16-byte, the records 8-byte, the lengths 4-byte aligned";
         return LSD_ERR_INVALID;
     }
     return enqueue_on(c, stream, [&](hipStream_t s) {
-        launch_pg_loop_select(d_head, d_nodes, nodes_cap, d_store, d_store_lens, store_stride, gap, window, d_loops, d_loops_rep, m, d_near, d_sel,
-                              d_q_scan, d_q_len, d_q_pose, s);
+        launch_pg_loop_select(d_head, d_nodes, nodes_cap, d_store, d_store_lens, store_stride, gap, window, d_loops, d_loops_rep, m, out, s);
         return LSD_OK;
     });
 }
 
 int lsd_pg_recognize_all(lsd_ctx* c, const lsd_pg_desc* desc, int n_nodes, int q_lo, int n_q, lsd_pg_place_par par, lsd_pg_place_rec* recs,
                          lsd_pg_place_rep* reps) {
-    if (!c || !desc || n_nodes < 1 || n_nodes > kPgMaxNodes || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, n_nodes)) return LSD_ERR_INVALID;
+    if (!c || !desc || pg_nodes_cap_bad(n_nodes) || pg_place_par_bad(par) || pg_queries_bad(q_lo, n_q, n_nodes)) return LSD_ERR_INVALID;
     if (n_q == 0) return LSD_OK;
     if (!recs || !reps) return LSD_ERR_INVALID;
     const size_t nn = (size_t)n_nodes, nq = (size_t)n_q;
@@ -336,7 +335,7 @@ int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_can
                   lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* track_rec, int32_t track, lsd_polar* store,
                   int* store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep* rep) {
     if (!c || !scans || !lens || !poses || !head || !nodes || !edges || !track_rec || !store || !store_lens || !rep) return LSD_ERR_INVALID;
-    if (n_cand < 0 || stride <= 0 || stride > c->scan_cap || store_stride <= 0 || store_stride > c->scan_cap) return LSD_ERR_INVALID;
+    if (n_cand < 0 || pg_stride_bad(c, stride) || pg_stride_bad(c, store_stride)) return LSD_ERR_INVALID;
     if (pg_caps_bad(nodes_cap, edges_cap) || pg_append_par_bad(par)) return LSD_ERR_INVALID;
     for (int i = 0; i < n_cand; i++) if (lens[i] < 0 || lens[i] > stride) return LSD_ERR_INVALID;
     if (n_cand == 0) return LSD_OK;

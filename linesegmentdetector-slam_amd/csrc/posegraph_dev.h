@@ -1,6 +1,8 @@
 // posegraph_dev.h -- what the pose graph's kernels share as ONE text (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the
-// relaxation): the wrap of an angle in degrees, a pose in the frame of another, a pose composed with a motion, and the 3 x 3 inverse in the
-// cofactor form of lsd_enqueue_fa_carry_correct_device's step 5.  include/lsd_hip.h, "pose graph", is the rule; fp64 without FMA.
+// relaxation; k_pgplace.hip, k_pgloops.hip: place recognition): the wrap of an angle in degrees, a pose in the frame of another, a pose
+// composed with a motion, the 3 x 3 inverse in the cofactor form of lsd_enqueue_fa_carry_correct_device's step 5, the counts of a head
+// clamped to the arrays (pg_n_nodes, pg_n_edges) and what near, recognize and loop_select leave for a closure chain (pg_hand_over).
+// include/lsd_hip.h, "pose graph", is the rule; fp64 without FMA.
 #pragma once
 #include "lsd_internal.h"
 #include "match_dev.h"
@@ -45,6 +47,42 @@ __device__ __forceinline__ bool pg_inv3(const double* S, double* inv, double& de
 // the integration's test for a scan skipped whole (k_gridmap.hip): not finite, the "no pose" sentinel, or far outside
 __device__ __forceinline__ bool pg_pose_skipped(const PgPose& p) {
     return !(isfinite(p.x) && isfinite(p.y) && isfinite(p.a)) || fabs(p.x + 1) < 1e-4 || fabs(p.x) > 1048576.0 || fabs(p.y) > 1048576.0;
+}
+
+// a head's counts as every kernel reads them: never below 0, never beyond the arrays
+__device__ __forceinline__ int pg_n_nodes(const lsd_pg_head* head, int nodes_cap) { return min(max(head->n_nodes, 0), nodes_cap); }
+__device__ __forceinline__ int pg_n_edges(const lsd_pg_head* head, int edges_cap) { return min(max(head->n_edges, 0), edges_cap); }
+
+// where place recognition puts a query whose scan it found at node `anchor`, `shift` sectors of 5.625 degrees on: the search's first pose
+__device__ __forceinline__ PgPose pg_turned(const lsd_pg_node* nodes, int anchor, int shift) {
+    return PgPose{nodes[anchor].x, nodes[anchor].y, pg_wrap(nodes[anchor].ang - (double)shift * 5.625)};
+}
+
+// What k_pg_near, k_pg_place_pick and k_pg_loop_select leave for a closure chain, by every lane of ONE workgroup of `lanes`: the near
+// record, the pose the search starts from (qp: read where anchor >= 0 only), the query's length, ALL nodes_cap rows of the selection -- the
+// anchor's window among the nodes a query may close on, the sentinel elsewhere -- and the query's row.
+__device__ __forceinline__ void pg_hand_over(const lsd_pg_node* nodes, int nodes_cap, int n_nodes, const lsd_polar* store, const int* store_lens,
+                                             int store_stride, int gap, int window, int j, int anchor, int n_cand, double d2, const PgPose& qp,
+                                             const PgHandOver& out, int tid, int lanes) {
+    const bool has_q = j >= 0 && j < n_nodes;
+    if (tid == 0) {
+        out.rec->anchor = anchor; out.rec->query = j; out.rec->n_cand = n_cand; out.rec->reserved = 0;
+        out.rec->d2 = anchor >= 0 ? d2 : 0.0;
+        out.q_pose->x = anchor >= 0 ? qp.x : -1.0;
+        out.q_pose->y = anchor >= 0 ? qp.y : 0.0;
+        out.q_pose->ang = anchor >= 0 ? qp.a : 0.0;
+        *out.q_len = has_q ? store_lens[j] : 0;
+    }
+    for (int k = tid; k < nodes_cap; k += lanes) {
+        const bool in = anchor >= 0 && abs(k - anchor) <= window && k <= j - gap;
+        out.sel[k].x = in ? nodes[k].x : -1.0;
+        out.sel[k].y = in ? nodes[k].y : 0.0;
+        out.sel[k].ang = in ? nodes[k].ang : 0.0;
+    }
+    if (has_q) {
+        const lsd_polar* src = store + (size_t)j * (size_t)store_stride;
+        for (int i = tid; i < store_stride; i += lanes) out.q_scan[i] = src[i];
+    }
 }
 
 }  // namespace lsdhip

@@ -3,7 +3,6 @@ lsd_enqueue_pg_closure_device, lsd_enqueue_pg_relax_device, lsd_pg_relax, lsd_pg
 Localizer.append_last_tick) against the restatement of tests/pose_graph_cases.py.  The rule fixes every operation and every order, so
 every comparison is byte equality."""
 import math
-import time
 
 import numpy as np
 import pytest
@@ -11,57 +10,15 @@ import pytest
 import fa_restatement as fr
 import grid_match_cases as gm
 import pose_graph_cases as pg
+from pose_graph_device import INV, Guarded, dev, filled, returns_in_front_of_the_device, same, stream
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 256                                    # bytes in front of and behind every buffer
-FILL = 0x5A
-INV = 1                                        # LSD_ERR_INVALID
-
 
 @pytest.fixture(scope="module")
 def ctx(lsdmod):
     c = lsdmod.Context(0)
     yield c
     c.close()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-class Guarded:
-    """The bytes of `a` on the device with GUARD bytes of the fill pattern on either side."""
-
-    def __init__(self, a):
-        self.raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()
-        pad = np.full(GUARD, FILL, np.uint8)
-        self.t = dev(np.concatenate([pad, self.raw, pad]))
-        self.ptr = self.t.data_ptr() + GUARD
-
-    def back(self):
-        """(the bytes now, True if both guards are untouched)."""
-        a = self.t.cpu().numpy()
-        n = len(self.raw)
-        return a[GUARD:GUARD + n], bool((a[:GUARD] == FILL).all() and (a[GUARD + n:] == FILL).all())
-
-    def unchanged(self):
-        got, ok = self.back()
-        return ok and got.tobytes() == self.raw.tobytes()
-
-
-def filled(n_bytes):
-    return Guarded(np.full(n_bytes, FILL, np.uint8))
-
-
-def stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def same(got, want):
-    return np.ascontiguousarray(got).view(np.uint8).tobytes() == np.ascontiguousarray(want).view(np.uint8).tobytes()
 
 
 # ---- 1. the relaxation: the campaign in launches of 1, 2 and 5 graphs ------------------------------------------------------------------
@@ -327,33 +284,12 @@ def test_chain_equals_the_restatement(lsdmod, ctx):
 
 
 def test_chain_does_not_synchronise(lsdmod, ctx):
-    import torch
     E = pg.end_to_end()
     graph, (scratch, mapper) = room_objects(lsdmod, ctx, E)
     d_in = (dev(E["scans"]), dev(E["lens"]), dev(E["odom"]))
     run_chain(lsdmod, graph, scratch, mapper, E, d_in)                                  # warm: every workspace has its size
     graph2, _ = room_objects(lsdmod, ctx, E)
-    a = torch.randn(4096, 4096, device="cuda")
-
-    def burn(count):
-        for _ in range(count):
-            a @ a
-    burn(3)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    burn(10)
-    torch.cuda.synchronize()
-    per = (time.perf_counter() - t0) / 10
-    count = max(10, min(5000, int(math.ceil(0.08 / per))))                             # ~80 ms of work in front of the chain
-    done = torch.cuda.Event()
-    burn(count)
-    done.record()
-    if done.query():
-        pytest.skip("the stream drained before the calls were made (%d matmuls of %.3f ms): the host was too slow to tell" % (count, per * 1e3))
-    run_chain(lsdmod, graph2, scratch, mapper, E, d_in)
-    still_running = not done.query()
-    torch.cuda.synchronize()
-    assert still_running, "append / close / relax / rerender returned only after the work in front of them had finished"
+    returns_in_front_of_the_device(lambda: run_chain(lsdmod, graph2, scratch, mapper, E, d_in), "append / close / relax / rerender")
     assert same(graph2.nodes(), E["g3"]["nodes"][:E["n_nodes"]])
 
 

@@ -165,4 +165,5 @@ def test_kernels_stay_out_of_scratch(tmp_path):
         found[name] = int(m.group(1))
     assert found == dict.fromkeys(names, 0), found
     assert re.findall(r"; ScratchSize: (\d+)", text) == ["0"] * len(names)
+    assert "flat_load" not in text                                          # every row and record is read in its own address space
     assert text.count("v_sad_u8") == 64 * 16

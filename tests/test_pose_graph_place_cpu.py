@@ -146,4 +146,5 @@ def test_kernels_stay_out_of_scratch(tmp_path):
         found[name] = int(m.group(1))
     assert found == {"k_pg_describe": 0, "k_pg_place_score": 0, "k_pg_place_pick": 0}, found
     assert re.findall(r"; ScratchSize: (\d+)", text) == ["0", "0", "0"]
+    assert "flat_load" not in text                                          # every row and record is read in its own address space
     assert text.count("v_sad_u8") == 64 * 16

@@ -3,7 +3,6 @@ lsd_enqueue_pg_relax_robust_device, lsd_enqueue_pg_prune_device, lsd_pg_relax_ro
 tests/pose_graph_robust_cases.py.  The rule fixes every operation and every order, so every comparison is byte equality."""
 import collections
 import math
-import time
 
 import numpy as np
 import pytest
@@ -12,11 +11,10 @@ import grid_cases as gc
 import grid_match_cases as gm
 import pose_graph_cases as pg
 import pose_graph_robust_cases as rc
-from test_pose_graph_gpu import Guarded, dev, filled, laid_out, room_objects, run_chain, same, stream
+from pose_graph_device import INV, Guarded, dev, filled, returns_in_front_of_the_device, same, stream
+from test_pose_graph_gpu import laid_out, room_objects, run_chain
 
 pytestmark = pytest.mark.gpu
-
-INV = 1                                        # LSD_ERR_INVALID
 
 
 @pytest.fixture(scope="module")
@@ -271,7 +269,6 @@ def test_optimize_device_does_not_synchronise(lsdmod, ctx):
     """The robust relaxation, prune_device, the refit and rerender_device return while work enqueued in front of them is still running
     (as tests/test_pose_graph_gpu.py holds the chain of 8.1.15 to it: the work in front is sized on this device, ~80 ms), and the result
     behind that work is still the restated chain's."""
-    import torch
     E = pg.end_to_end()
     nn, ne = E["n_nodes"], E["n_edges"]
     nodes, clean, edges, bad = rc.relaxed_with_false_closure()
@@ -293,25 +290,5 @@ def test_optimize_device_does_not_synchronise(lsdmod, ctx):
         mapper.rerender_device(graph)
     chain(*loaded())                                                                    # warm: every workspace has its size
     graph, mapper = loaded()
-    a = torch.randn(4096, 4096, device="cuda")
-
-    def burn(count):
-        for _ in range(count):
-            a @ a
-    burn(3)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    burn(10)
-    torch.cuda.synchronize()
-    per = (time.perf_counter() - t0) / 10
-    count = max(10, min(5000, int(math.ceil(0.08 / per))))                             # ~80 ms of work in front of the chain
-    done = torch.cuda.Event()
-    burn(count)
-    done.record()
-    if done.query():
-        pytest.skip("the stream drained before the calls were made (%d matmuls of %.3f ms): the host was too slow to tell" % (count, per * 1e3))
-    chain(graph, mapper)
-    still_running = not done.query()
-    torch.cuda.synchronize()
-    assert still_running, "optimize_device / rerender_device returned only after the work in front of them had finished"
+    returns_in_front_of_the_device(lambda: chain(graph, mapper), "optimize_device / rerender_device")
     assert same(graph.nodes(), want["nodes"]) and same(graph.edges(), want["edges"]) and same(graph.prune_report(), want["prune"])
