@@ -1327,6 +1327,11 @@ int lsd_set_trace(lsd_ctx *ctx, int on);
  * reports the kernel under "gauss" and "gradient" as exactly 0, the per-image Gaussian workspace (8 B per scaled pixel) is not
  * allocated, and LSD_DBG_GAUSS is recomputed on demand (lsd_debug_fetch). */
 int lsd_set_fused_front(lsd_ctx *ctx, int on);
+/* Lines in the region stage (default 1): the region stage's workgroup writes the line records and the lineIm marks of an image when it
+ * has finished that image, instead of a kernel behind the whole batch -- one kernel launch less per call, and an image's lines do not
+ * wait for the slowest image.  0 runs that kernel, as lsd_set_trace and lsd_set_region_help do anyway.  Results are identical.  On the
+ * fused path lsd_last_timings reports "lines" as exactly 0 (the work is under "region"). */
+int lsd_set_fused_lines(lsd_ctx *ctx, int on);
 /* Region stage variant: 4 wavefronts per image (three images per CU: the throughput build) or 8 (one image per CU, ~1.5x lower
  * latency per image, images taken heaviest first).  0 (default) picks 8 while the batch has at most four images per CU (the step is
  * bounded by its heaviest image until then) and 4 beyond.  Results do not depend on the choice.  Set it before lsd_reserve: the

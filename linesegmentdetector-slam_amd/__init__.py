@@ -301,6 +301,7 @@ _ABI = {
     "lsd_set_stop_after": (_i, [_vp, _i]),
     "lsd_set_trace": (_i, [_vp, _i]),
     "lsd_set_fused_front": (_i, [_vp, _i]),
+    "lsd_set_fused_lines": (_i, [_vp, _i]),
     "lsd_set_region_waves": (_i, [_vp, _i]),
     "lsd_set_region_help": (_i, [_vp, _i]),
     "lsd_debug_set_stamp_budget": (_i, [_vp, C.c_uint]),
@@ -1315,6 +1316,10 @@ class Context:
     def set_fused_front(self, on):
         """lsd_set_fused_front: Gaussian and gradient pass as one kernel where that applies (default on; results are identical)."""
         self._chk(self.L.lsd_set_fused_front(self.h, 1 if on else 0))
+
+    def set_fused_lines(self, on):
+        """lsd_set_fused_lines: the region stage writes an image's lines when it has finished it, no kernel behind the batch (default on; results are identical)."""
+        self._chk(self.L.lsd_set_fused_lines(self.h, 1 if on else 0))
 
     def set_host_max_lines(self, max_lines):
         """Line capacity per image of run / run_batch (default HOST_MAX_LINES_DEFAULT); more lines -> LsdError(LSD_ERR_CAPACITY)."""

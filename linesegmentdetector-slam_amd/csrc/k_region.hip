@@ -48,6 +48,7 @@
 // This file keeps the commit ring, region_image (the scheduler), the kernel and the two launchers.
 #include "lsd_internal.h"
 #include "devmath.h"
+#include "lines_dev.h"
 
 // The file is compiled twice (Makefile): LSD_REGION_NW = 4 (two images per CU: the batch path, all 512 workgroups of the
 // bench batch resident at once) and LSD_REGION_NW = 8 (one image per CU, 8 speculative wavefronts per image: lower
@@ -1345,6 +1346,21 @@ __device__ __forceinline__ void region_image(const Geom& g, const Buffers& b, ui
 }
 #undef LT
 
+// K5 by the workgroup that has just finished the image at place `bid` of the launch's order (b.fuse_lines; lsd_ctx.hip says when): the
+// records of its accepted rectangles are final, so their lines are written here, by all of its wavefronts, instead of by a kernel behind
+// the whole launch -- one dispatch less per step, and an image's lines no longer wait for the slowest image of the batch.  Out of line,
+// called from the kernel function with nothing of the image's own state live any more: the kernel body's register allocation is
+// untouched (DESIGN_NOTES.md, "the lean kernel body").  The caller has passed a barrier since the image's last commit: the records
+// and the count, written by whichever wavefront moved the cursor, are visible to all of the workgroup's.
+// (The arguments one by one, not the Buffers record: a reference to it would make the kernel keep a copy of its arguments in scratch.)
+__device__ __noinline__ void region_lines(const uint32_t* order, const int32_t* counts, const double* recs_scaled, lsd_line* lines, uint8_t* line_im,
+                                          int max_lines, int W, int H, int bid) {
+    const size_t img = order[bid];
+    const int count = __hip_atomic_load(&counts[img], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    lines_of_image(recs_scaled + img * (size_t)max_lines * 4, count, lines + img * (size_t)max_lines,
+                   line_im ? line_im + img * (size_t)W * H : nullptr, max_lines, W, H, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63), NW);
+}
+
 // The launch.  One workgroup per image (+ b.npool helper-only workgroups), dispatched in the order of k_order -- or, on the 8-wave
 // build, PERSISTENT workgroups (b.pcount, lsd_ctx.hip: a batch of more images than the device has CUs, help off): as many workgroups
 // as CUs, each taking the next image of that order from the launch's counter until none is left.  The hardware deals the workgroups
@@ -1367,11 +1383,13 @@ __global__ __launch_bounds__(64 * NW, LSD_REGION_WAVES_PER_SIMD) void k_region(G
             if (bid >= nimg) return;
         }
         region_image(g, b, id_base, bid, nimg);
+        if (b.fuse_lines) { __syncthreads(); region_lines(b.order, b.counts, b.recs_scaled, b.lines, b.line_im, b.max_lines, g.W, g.H, bid); }   // (never with help across workgroups: every workgroup owns an image and all its wavefronts arrive)
         if (!b.pcount) return;
         __syncthreads();                                    // every wavefront is out of the image before its shared state is set up again
     }
 #else
     region_image(g, b, id_base, (int)blockIdx.x, (int)gridDim.x - b.npool);
+    if (b.fuse_lines) { __syncthreads(); region_lines(b.order, b.counts, b.recs_scaled, b.lines, b.line_im, b.max_lines, g.W, g.H, (int)blockIdx.x); }
 #endif
 }
 

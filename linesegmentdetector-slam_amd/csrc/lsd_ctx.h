@@ -108,6 +108,8 @@ struct lsd_ctx {
     DevBuf<int> pcount;                 // ... and the launch's image counter
     bool trace = false;
     bool fused_front = true;            // lsd_set_fused_front: K1 + K2 as one kernel where it applies (use_front)
+    bool fused_lines = true;            // lsd_set_fused_lines: K5 by the region stage's workgroups, image by image, where it applies
+    bool last_lines_fused = false;      // the last launch wrote its lines in the region stage: "lines" of lsd_last_timings reads exactly 0
     int scan_cap = kRdpShortMaxLen;     // lsd_set_scan_capacity: readings per scan (the stride) FeatureScan and the ingest entries take
     bool rdp_long_ready = false;        // the long FeatureScan kernels' dynamic-LDS limit covers scan_cap (prepare_rdp_long)
     int host_max_lines = 8192;

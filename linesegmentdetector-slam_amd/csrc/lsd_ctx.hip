@@ -458,6 +458,12 @@ int lsd_set_fused_front(lsd_ctx* c, int on) {
     return LSD_OK;
 }
 
+int lsd_set_fused_lines(lsd_ctx* c, int on) {
+    if (!c) return LSD_ERR_INVALID;
+    c->fused_lines = on != 0;
+    return LSD_OK;
+}
+
 // The scan capacity: the largest stride the FeatureScan and ingest entries take.  1024 (k_rdp's static arrays) unless the caller asks
 // for more; above it the launches go to k_rdp_long, whose LDS grows with the stride (k_rdp_lds.h): a capacity whose scans would not fit
 // this device's LDS is refused here, before anything is enqueued -- make_geom's rule for K1's window.
@@ -546,7 +552,10 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     // Every dispatch of a batch in flight has to get onto a hardware pipe that the launches of other batches may be holding (a region launch
     // waits for workgroup slots for tens of milliseconds), so a batch costs as few dispatches as it can: ONE fill in front of the kernels (the
     // gradient maxima and, behind them, the gradient pass's near-tie counts); the region stage clears its own counter records and tile epochs
-    // image by image; the line counts and list lengths are written by the kernels that own them unless the pipeline is cut short.
+    // image by image; the line counts and list lengths are written by the kernels that own them unless the pipeline is cut short; an image's
+    // lines are written by the region stage's workgroup that finished it (fused_lines) -- not behind a seed trace, not with help across
+    // workgroups (the owner's wavefronts go on to help others: they do not meet at the image's end), not where stop_after cuts the lines off.
+    b.fuse_lines = (c->fused_lines && c->stop_after == 0 && !c->trace && !b.xq) ? 1 : 0;
     HIPCHK(c, hipMemsetAsync(w.maxbits.get(), 0, sizeof(unsigned long long) * w.cap_n + sizeof(int32_t) * (size_t)n, s));
     const bool full_region = c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION;
     if (!full_region) HIPCHK(c, hipMemsetAsync(d_counts, 0, sizeof(int32_t) * n, s));            // (else k_region writes every image's count)
@@ -592,7 +601,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
         else launch_region_w4(g, b, grid, w.run_id << 20, sr);
     }
     HIPCHK(c, hipEventRecord(c->ev[4], s));
-    if (c->stop_after == 0) launch_lines(g, b, n, s);
+    if (c->stop_after == 0 && !b.fuse_lines) launch_lines(g, b, n, s);
     HIPCHK(c, hipEventRecord(c->ev[5], s));
     HIPCHK(c, hipEventRecord(c->ev_done, s));
     c->done_valid = true; c->done_stream = s;
@@ -601,6 +610,7 @@ int lsd_enqueue_batch_device(lsd_ctx* c, uint8_t* d_maps, int n, int cols, int r
     c->hist_n = (c->stop_after == 0 || c->stop_after >= LSD_STAGE_REGION) ? n : 0;     // (the counter records of this launch: the next one's cost history)
     c->geom = g; c->last_n = n; c->last_max_lines = max_lines; c->last_counts = d_counts; c->last_stream = s;
     c->last_fused = fused; c->last_in = d_maps; c->last_remapped = b.in_rw != nullptr;
+    c->last_lines_fused = b.fuse_lines != 0;
     return LSD_OK;
 }
 
@@ -618,6 +628,7 @@ int lsd_last_timings(lsd_ctx* c, float ms[6]) {
     for (int i = 0; i < 5; i++) HIPCHK(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     HIPCHK(c, hipEventElapsedTime(&ms[5], c->ev[0], c->ev[5]));
     if (c->last_fused) ms[1] = 0.0f;                                 // (the fused front end: all of it is under "gauss")
+    if (c->last_lines_fused) ms[4] = 0.0f;                           // (... and the lines written by the region stage under "region")
     return LSD_OK;
 }
 

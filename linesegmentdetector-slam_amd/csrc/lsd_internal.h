@@ -111,6 +111,7 @@ struct Buffers {
     void* seeds;           // n x npx trace records or null
     int32_t* nseed;        // n
     long long* stats;      // n x kStatWords
+    int fuse_lines;        // the region stage's workgroup writes the lines of an image it has finished (lines_dev.h): no k_lines behind it (lsd_ctx.hip says when)
 };
 
 struct SeedRec {  // mirrors oracle's orc_seed
