@@ -1165,6 +1165,56 @@ typedef struct lsd_pg_robust_rep { double chi2_plain, w_min; int32_t downweighte
 int lsd_enqueue_pg_relax_robust_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_node *d_nodes, int nodes_cap,
                                        lsd_pg_edge *d_edges, int edges_cap, lsd_pg_relax_par par, lsd_pg_robust_par rob, void *d_workspace,
                                        lsd_pg_relax_rep *d_rep, lsd_pg_robust_rep *d_rob_rep /* may be NULL */, void *stream);
+/* lsd_enqueue_pg_relax_pc_device: the robust relaxation above with a choice of preconditioner (csrc/k_pgchain.hip, csrc/pgrelax_dev.h: the
+ * same body compiled a third time; restated in tests/pose_graph_chain_cases.py).  The arguments of
+ * lsd_enqueue_pg_relax_robust_device, `pc` and one lsd_pg_precond_rep per graph (d_pc_rep may be NULL).  The workspace of graph g begins at
+ * g * lsd_pg_workspace_pc_bytes(nodes_cap, edges_cap, pc.kind).
+ * kind BLOCK launches lsd_enqueue_pg_relax_robust_device's kernel and gives its bytes (with kernel NONE those of
+ * lsd_enqueue_pg_relax_device); every d_pc_rep[g] is zeros.
+ * kind CHAIN: M is the block-tridiagonal part of the damped normal matrix D along the graph's odometry chains, and z = M^-1 r stands
+ * wherever the rule says z_n = M_n r_n.  A track's graph is a chain plus a few closures, D differs from M by the closures' off-diagonal
+ * blocks alone, and PCG needs a number of steps that follows the closures, not the length of the track.  Everything that is not named
+ * here is the text of the two entries above, word for word: the skipping of edges, the lists, the weights, the one reduction shape, the
+ * singular and fixed nodes, PCG, BREAKDOWN, the stops.  fp64 without FMA, every sum left to right from +0.0, no atomics on fp64.
+ *   CHAIN EDGES, once per call, integers only.  A CANDIDATE is an edge that is not skipped and has LSD_PG_EDGE_CLOSURE clear; lo = min(i, j),
+ *   hi = max(i, j); up[n] = the smallest candidate index whose lo is n, down[n] = the smallest whose hi is n.  Edge e is a CHAIN edge iff
+ *   up[lo(e)] == e and down[hi(e)] == e.  No order of the edges enters.  A node has at most one chain edge upwards and one downwards, so
+ *   the chain edges form disjoint PATHS with ascending node indices; a node's RANK is its distance from its path's head (the node with no
+ *   chain edge downwards); a node on no chain edge is a path of one.
+ *   POSITIONS t = 0 .. N-1: the paths one after another in ascending head index, each in rank order; node(t) is the node at t.
+ *   BLOCKS, per outer iteration behind step 3.  Dg[t] = D_n of node(t) where it is FREE, the identity elsewhere.  C[t], t < N-1, rows
+ *   belonging to node(t): where a chain edge e joins node(t) and node(t+1) and both are free, e's Hab (node(t) is e.i) or Hab transposed
+ *   (node(t) is e.j) -- the weighted blocks of step 1 --; every entry +0.0 elsewhere.
+ *   FACTOR, block cyclic reduction.  Levels s = 1, 2, 4, .. while s < N.  At a level every t with t mod 2s == s is eliminated; a = t - s,
+ *   c = t + s; L = the current coupling (a, t), R = the current coupling (t, c) where c < N (at s = 1 they are C[a] and C[t]):
+ *     P_t = inv3(Dg[t]);  GL_t(r,q) = sum_u L(r,u) * P_t(u,q);  with c < N: GU_t(r,q) = sum_u R(u,r) * P_t(u,q)
+ *     Dg[a](r,q) = Dg[a](r,q) - sum_u GL_t(r,u) * L(q,u);  with c < N: Dg[c](r,q) = Dg[c](r,q) - sum_u GU_t(r,u) * R(u,q)
+ *     with c < N the new coupling (a, c)(r,q) = -(sum_u GL_t(r,u) * R(u,q))
+ *   A position that receives from both sides at one level takes the lower side (t = c' - s) first, the upper side (t = c' + s) second.
+ *   Dg[t] is read as it stands when t's level begins.  Position 0 is never eliminated: P_0 = inv3(Dg[0]) behind the last level.
+ *   APPLY.  y[t] = r of node(t).  Forward over the same levels, a position again taking the lower side first:
+ *     y[c](r) = y[c](r) - sum_q GU_t(r,q) * y[t](q);  y[a](r) = y[a](r) - sum_q GL_t(r,q) * y[t](q)
+ *   x[0](r) = sum_q P_0(r,q) * y[0](q).  Backward, s descending over the same levels, L and R as they were when t was eliminated:
+ *     v(r) = y[t](r) - sum_q L(q,r) * x[a](q);  with c < N: v(r) = v(r) - sum_q R(r,q) * x[c](q);  x[t](r) = sum_q P_t(r,q) * v(q)
+ *   z of node(t) = x[t] where it is free, +0.0 elsewhere.
+ *   FALLBACK.  Where an inv3 of the factor fails, this outer iteration runs on the Jacobi blocks M_n exactly as the plain rule does -- its
+ *   bytes are the plain rule's -- and `fallbacks` counts it.  (M is symmetric positive definite for information matrices that are: the sum
+ *   of the chain edges' own terms, the diagonal blocks of all other edges and lambda * diag(H).)
+ * d_pc_rep: the chain edges, the paths (those of one node too), the nodes of the longest path, the outer iterations that fell back; all 0
+ * for N == 0.  iters == 0 still reports the chain.
+ * One launch, ONE WORKGROUP PER GRAPH; ranks by pointer doubling, up and down by integer atomics; no allocation, no host wait.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: everything lsd_enqueue_pg_relax_robust_device refuses; kind outside 0..1;
+ * reserved != 0; d_pc_rep not 8-byte aligned.  lsd_pg_workspace_pc_bytes: lsd_pg_workspace_bytes for BLOCK; for CHAIN that plus the
+ * factor's planes and the positions (51 doubles and 6 words per node, rounded up to 256 bytes); 0 for caps outside the limits or a kind
+ * outside 0..1. */
+typedef struct lsd_pg_precond_par { int32_t kind; int32_t reserved; } lsd_pg_precond_par;               /* 8 bytes */
+enum { LSD_PG_PRECOND_BLOCK = 0, LSD_PG_PRECOND_CHAIN = 1 };
+typedef struct lsd_pg_precond_rep { int32_t chain_edges, paths, longest_path, fallbacks; } lsd_pg_precond_rep;   /* 16 bytes */
+size_t lsd_pg_workspace_pc_bytes(int nodes_cap, int edges_cap, int kind);
+int lsd_enqueue_pg_relax_pc_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_node *d_nodes, int nodes_cap,
+                                   lsd_pg_edge *d_edges, int edges_cap, lsd_pg_relax_par par, lsd_pg_robust_par rob, lsd_pg_precond_par pc,
+                                   void *d_workspace, lsd_pg_relax_rep *d_rep, lsd_pg_robust_rep *d_rob_rep /* may be NULL */,
+                                   lsd_pg_precond_rep *d_pc_rep /* may be NULL */, void *stream);
 /* lsd_enqueue_pg_prune_device: closures whose chi2 -- the last relaxation's -- is beyond a gate are taken out of the graph, on the device
  * (csrc/k_pgprune.hip).  Graph g is d_heads[g], d_edges + g * edges_cap and d_rep[g]; E is its clamped n_edges.
  *   A CANDIDATE is an edge e < E with CLOSURE set, DISABLED clear and !(chi2 <= gate): a NaN is one.
@@ -1295,12 +1345,16 @@ int lsd_enqueue_pg_loop_select_device(lsd_ctx *ctx, const lsd_pg_head *d_head, c
  * lsd_enqueue_pg_loops_device; n_q outside 0..16384 or n_edges outside 0..65536: LSD_ERR_INVALID.
  * lsd_pg_relax: one graph; nodes[n_nodes] and edges[n_edges] are updated in place, rep receives the report.
  * lsd_pg_relax_robust: the same around lsd_enqueue_pg_relax_robust_device; rep and rob_rep receive the two reports.
+ * lsd_pg_relax_pc: the same around lsd_enqueue_pg_relax_pc_device; rep, rob_rep and pc_rep receive the three reports.
  * lsd_pg_append: the graph (head, nodes[nodes_cap], edges[edges_cap], track, store, store_lens) makes the round trip around the device
  * entry with the n_cand candidates; lens[t] outside 0..stride: LSD_ERR_INVALID. */
 int lsd_pg_relax(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
                  lsd_pg_relax_rep *rep);
 int lsd_pg_relax_robust(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
                         lsd_pg_robust_par rob, lsd_pg_relax_rep *rep, lsd_pg_robust_rep *rob_rep);
+int lsd_pg_relax_pc(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
+                    lsd_pg_robust_par rob, lsd_pg_precond_par pc, lsd_pg_relax_rep *rep, lsd_pg_robust_rep *rob_rep,
+                    lsd_pg_precond_rep *pc_rep);
 int lsd_pg_append(lsd_ctx *ctx, const lsd_polar *scans, const int *lens, int n_cand, int stride, const lsd_position *poses,
                   lsd_pg_head *head, lsd_pg_node *nodes, int nodes_cap, lsd_pg_edge *edges, int edges_cap, lsd_pg_track *track_rec,
                   int32_t track, lsd_polar *store, int *store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep *rep);

@@ -209,6 +209,10 @@ class lsd_pg_prune(C.Structure):       # the C side's lsd_pg_prune_par
     _fields_ = [("gate", C.c_double), ("max_reject", C.c_int32), ("reserved", C.c_int32)]
 
 
+class lsd_pg_precond(C.Structure):     # the C side's lsd_pg_precond_par
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
 PG_HEAD_DTYPE = np.dtype([("n_nodes", "i4"), ("n_edges", "i4")])
 PG_NODE_DTYPE = np.dtype([("x", "f8"), ("y", "f8"), ("ang", "f8"), ("raw", "f8", (3,)), ("flags", "u4"), ("track", "i4"), ("reserved", "u8")])
 PG_EDGE_DTYPE = np.dtype([("i", "i4"), ("j", "i4"), ("flags", "u4"), ("reserved", "u4"), ("z", "f8", (3,)), ("info", "f8", (6,)), ("chi2", "f8")])
@@ -235,6 +239,10 @@ PG_EDGE_REJECTED = 4
 PG_KERNEL_NONE, PG_KERNEL_HUBER, PG_KERNEL_GM = 0, 1, 2
 PG_ROBUST_CLOSURES, PG_ROBUST_ALL = 0, 1
 PG_MAX_REJECT = 64
+# the relaxation's preconditioner
+PG_PRECOND_REP_DTYPE = np.dtype([("chain_edges", "i4"), ("paths", "i4"), ("longest_path", "i4"), ("fallbacks", "i4")])
+assert (PG_PRECOND_REP_DTYPE.itemsize, C.sizeof(lsd_pg_precond)) == (16, 8)
+PG_PRECOND_BLOCK, PG_PRECOND_CHAIN = 0, 1
 # place recognition
 
 
@@ -387,6 +395,9 @@ _ABI = {
     "lsd_enqueue_pg_relax_robust_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, _vp, _vp, _vp, _vp]),
     "lsd_enqueue_pg_prune_device": (_i, [_vp, _i, _vp, _vp, _i, lsd_pg_prune, _vp, _vp]),
     "lsd_pg_relax_robust": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, _vp, _vp]),
+    "lsd_pg_workspace_pc_bytes": (_sz, [_i, _i, _i]),
+    "lsd_enqueue_pg_relax_pc_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, lsd_pg_precond, _vp, _vp, _vp, _vp, _vp]),
+    "lsd_pg_relax_pc": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, lsd_pg_precond, _vp, _vp, _vp]),
     "lsd_pg_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp]),
     "lsd_enqueue_pg_describe_device": (_i, [_vp, _vp, _i, _vp, _vp, _i, _dbl, _vp, _vp]),
     "lsd_enqueue_pg_recognize_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, lsd_pg_place, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -948,6 +959,28 @@ class Context:
         self._chk(self.L.lsd_pg_relax_robust(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
                                              pg_relax(relax), pg_robust(robust), rep.ctypes.data, rob.ctypes.data))
         return no, ed, rep[0], rob[0]
+
+    def enqueue_pg_relax_pc_device(self, n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, d_workspace, d_rep, precond, robust=None,
+                                   d_rob_rep=None, d_pc_rep=None, relax=None, stream=None):
+        """lsd_enqueue_pg_relax_pc_device on raw device addresses: enqueue_pg_relax_robust_device with a choice of preconditioner
+        (precond: pg_precond(); robust: pg_robust(), None is the kernel "none").  "block" gives the robust entry's bytes; "chain" solves
+        the block-tridiagonal part of the normal matrix along the odometry chains, so that PCG's steps follow the number of closures and
+        not the length of the track.  The workspace is n_graphs x pg_workspace_pc_bytes(nodes_cap, edges_cap, precond) bytes.  d_rob_rep,
+        d_pc_rep: None, or one PG_ROBUST_REP_DTYPE / PG_PRECOND_REP_DTYPE per graph.  Asynchronous on `stream`."""
+        rob = pg_robust(kernel="none") if robust is None else pg_robust(robust)
+        return self._chk(self.L.lsd_enqueue_pg_relax_pc_device(self.h, int(n_graphs), d_heads, d_nodes, int(nodes_cap), d_edges, int(edges_cap),
+                                                               pg_relax(relax), rob, pg_precond(precond), d_workspace, d_rep, d_rob_rep, d_pc_rep,
+                                                               stream))
+
+    def pg_relax_pc(self, nodes, edges, precond, robust=None, relax=None):
+        """lsd_pg_relax_pc from host arrays, as pg_relax_robust(): returns (nodes, edges, report, robust report, preconditioner's
+        report) after the relaxation preconditioned as `precond` says (pg_precond()); blocking."""
+        no, ed = np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        rep, rob, pc = np.zeros(1, PG_RELAX_REP_DTYPE), np.zeros(1, PG_ROBUST_REP_DTYPE), np.zeros(1, PG_PRECOND_REP_DTYPE)
+        rb = pg_robust(kernel="none") if robust is None else pg_robust(robust)
+        self._chk(self.L.lsd_pg_relax_pc(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
+                                         pg_relax(relax), rb, pg_precond(precond), rep.ctypes.data, rob.ctypes.data, pc.ctypes.data))
+        return no, ed, rep[0], rob[0], pc[0]
 
     def pg_append(self, scans, lens, poses, head, nodes, edges, track_rec, store, store_lens, track=0, append=None):
         """lsd_pg_append from host arrays: the candidates (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]) against the
@@ -1782,6 +1815,28 @@ def pg_robust(robust=None, kernel=None, delta=None, scope=None):
     return lsd_pg_robust(k, s, float(a["delta"]))
 
 
+_PG_PRECONDS = {"block": PG_PRECOND_BLOCK, "chain": PG_PRECOND_CHAIN}
+
+
+def pg_precond(precond=None, kind=None):
+    """An lsd_pg_precond: the preconditioner of the relaxation's conjugate gradients -- "block" (the inverse 3 x 3 diagonal blocks: the
+    default of every entry), "chain" (the block-tridiagonal part of the normal matrix along the odometry chains) or
+    the C side's number."""
+    if isinstance(precond, lsd_pg_precond):
+        return precond
+    k = kind if kind is not None else ("block" if precond is None else precond)
+    if isinstance(k, dict):
+        if set(k) - {"kind"}:
+            raise LsdError(LSD_ERR_INVALID, "lsd_pg_precond: unknown keys %s" % sorted(set(k) - {"kind"}))
+        k = k.get("kind", "block")
+    if isinstance(k, str) and k not in _PG_PRECONDS:
+        raise LsdError(LSD_ERR_INVALID, "precond is one of %s or an int" % sorted(_PG_PRECONDS))
+    k = int(_PG_PRECONDS.get(k, k))
+    if not -2 ** 31 <= k < 2 ** 31:
+        raise LsdError(LSD_ERR_INVALID, "precond is int32")
+    return lsd_pg_precond(k, 0)
+
+
 PG_PLACE_DEFAULTS = dict(gap=10, window=2, spread=2, k=4, pick=0, max_dist=1024, min_sectors=16)
 
 
@@ -1820,6 +1875,12 @@ def pg_loops(loops=None, max_loops=None, spread=None):
 def pg_loops_workspace_bytes(n_q, k, edges_cap):
     """lsd_pg_loops_workspace_bytes: the workspace of enqueue_pg_loops_device; 0 for arguments it refuses."""
     return int(load_library().lsd_pg_loops_workspace_bytes(int(n_q), int(k), int(edges_cap)))
+
+
+def pg_workspace_pc_bytes(nodes_cap, edges_cap, precond):
+    """lsd_pg_workspace_pc_bytes: the workspace of ONE graph of enqueue_pg_relax_pc_device for a preconditioner (pg_precond()); 0 for
+    caps or a kind outside the limits."""
+    return int(load_library().lsd_pg_workspace_pc_bytes(int(nodes_cap), int(edges_cap), int(pg_precond(precond).kind)))
 
 
 def pg_workspace_bytes(nodes_cap, edges_cap):
@@ -2390,7 +2451,9 @@ class PoseGraph:
     optimize_device() makes the relaxation robust against closures that are confidently wrong and takes them out on the device (DESIGN.md
     8.1.16); close_place_device() finds the anchor of a closure by the appearance of the scan where the drift has carried the pose out of
     close_device()'s radius; close_all_device() asks that of every keyframe in one launch and closes every distinct
-    loop it finds.  Everything but nodes(), edges(), place_records(), loop_records(), the *report() and *reports()
+    loop it finds; relax_device() and optimize_device() take precond="chain" for long tracks, and
+    the workspace has that preconditioner's size from the construction on -- 432 bytes per node of nodes_cap more than the default one
+    needs, whether precond is ever used or not --, so that no enqueue allocates.  Everything but nodes(), edges(), place_records(), loop_records(), the *report() and *reports()
     methods and disable_edges() is enqueued without waiting for the device."""
 
     def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
@@ -2409,10 +2472,11 @@ class PoseGraph:
         tracks["last"] = -1
         self._tracks = torch.from_numpy(tracks.view(np.uint8).reshape(self.n_tracks, -1)).to(dev)
         self._store, self._store_lens = z(self.nodes_cap, self.n_beams, 2, dtype=torch.float64), z(self.nodes_cap, dtype=torch.int32)
-        self._ws = z(ws)
+        self._ws = z(max(ws, pg_workspace_pc_bytes(self.nodes_cap, self.edges_cap, "chain")))      # (the larger of the two preconditioners')
         self._append_rep, self._near, self._closure_rep = z(PG_APPEND_REP_DTYPE.itemsize), z(PG_NEAR_DTYPE.itemsize), z(PG_CLOSURE_REP_DTYPE.itemsize)
         self._relax_rep = z(PG_RELAX_REP_DTYPE.itemsize)
         self._robust_rep, self._prune_rep = z(PG_ROBUST_REP_DTYPE.itemsize), z(PG_PRUNE_REP_DTYPE.itemsize)
+        self._precond_rep = z(PG_PRECOND_REP_DTYPE.itemsize)
         self._sel = z(self.nodes_cap, 3, dtype=torch.float64)
         self._q_scan, self._q_len, self._q_pose = z(1, self.n_beams, 2, dtype=torch.float64), z(1, dtype=torch.int32), z(1, 3, dtype=torch.float64)
         # place recognition: zeroed descriptors are "not described yet"
@@ -2590,10 +2654,18 @@ class PoseGraph:
         self._held_close = (held, out)                                       # the launches read them: alive until the next call
         return out
 
-    def relax_device(self, relax=None, stream=None, robust=None, **kw):
+    def relax_device(self, relax=None, stream=None, robust=None, precond=None, **kw):
         """The relaxation (lsd_enqueue_pg_relax_device) of this graph: relax is pg_relax(), or its keywords (iters=, cg_iters=, cg_tol=,
         lambda0=, ..).  The nodes move in place, edge.chi2 and report() are written.  robust: None, or pg_robust() for the robust
-        relaxation (lsd_enqueue_pg_relax_robust_device), which also writes robust_report().  On `stream`; nothing waits."""
+        relaxation (lsd_enqueue_pg_relax_robust_device), which also writes robust_report().  precond: None for the two entries above,
+        or "block" / "chain" (pg_precond()) for lsd_enqueue_pg_relax_pc_device, which also writes precond_report(): "chain" is the one
+        for a long track.  On `stream`; nothing waits."""
+        if precond is not None:
+            self.ctx.enqueue_pg_relax_pc_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(),
+                                                self.edges_cap, self._ws.data_ptr(), self._relax_rep.data_ptr(), precond, robust,
+                                                None if robust is None else self._robust_rep.data_ptr(), self._precond_rep.data_ptr(),
+                                                pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
+            return
         if robust is None:
             self.ctx.enqueue_pg_relax_device(1, self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
                                              self._ws.data_ptr(), self._relax_rep.data_ptr(), pg_relax(relax, **kw), _cuda_stream(stream).cuda_stream)
@@ -2609,15 +2681,16 @@ class PoseGraph:
         self.ctx.enqueue_pg_prune_device(1, self._head.data_ptr(), self._edges.data_ptr(), self.edges_cap, self._prune_rep.data_ptr(), gate, max_reject,
                                          _cuda_stream(stream).cuda_stream)
 
-    def optimize_device(self, robust, gate, max_reject=8, relax=None, refit=None, stream=None):
+    def optimize_device(self, robust, gate, max_reject=8, relax=None, refit=None, stream=None, precond=None):
         """Three launches on one stream: the robust relaxation (robust: pg_robust(); relax: pg_relax()), prune_device(gate, max_reject)
         on the plain chi2 it leaves, and the plain relaxation over the edges that survive (refit: pg_relax(), default: relax).  Huber
         for a first relaxation from drifted poses, Geman-McClure for a closure on a relaxed graph.  report() is the
-        refit's, robust_report() and prune_report() those of the first two.  Nothing waits."""
+        refit's, robust_report() and prune_report() those of the first two.  precond: relax_device()'s, for both relaxations
+        (precond_report() is the refit's).  Nothing waits."""
         ts = _cuda_stream(stream)
-        self.relax_device(relax, ts, robust=robust)
+        self.relax_device(relax, ts, robust=robust, precond=precond)
         self.prune_device(gate, max_reject, ts)
-        self.relax_device(relax if refit is None else refit, ts)
+        self.relax_device(relax if refit is None else refit, ts, precond=precond)
 
     def fix(self, node, stream=None):
         """Sets LSD_PG_NODE_FIXED on a node, on `stream`; nothing waits."""
@@ -2652,6 +2725,11 @@ class PoseGraph:
         """The second report (PG_ROBUST_REP_DTYPE) of the last ROBUST relaxation -- relax_device(robust=) or optimize_device; a plain
         relax_device after it leaves this record as it was, so it is older than report() then.  A read-back, which waits for the device."""
         return self._read(self._robust_rep, PG_ROBUST_REP_DTYPE)[0]
+
+    def precond_report(self):
+        """The preconditioner's report (PG_PRECOND_REP_DTYPE) of the last relaxation that was given precond=: the chain edges, the paths,
+        the longest path's nodes, the outer iterations that fell back to the diagonal blocks.  A read-back, which waits for the device."""
+        return self._read(self._precond_rep, PG_PRECOND_REP_DTYPE)[0]
 
     def prune_report(self):
         """The last prune_device's report (PG_PRUNE_REP_DTYPE): a read-back, which waits for the device."""

@@ -278,6 +278,12 @@ void launch_pg_relax_robust(int n_graphs, const lsd_pg_head* heads, lsd_pg_node*
                             lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, hipStream_t s);
 void launch_pg_prune(int n_graphs, const lsd_pg_head* heads, lsd_pg_edge* edges, int edges_cap, lsd_pg_prune_par par, lsd_pg_prune_rep* rep,
                      hipStream_t s);
+// the robust body with the block-tridiagonal preconditioner (k_pgchain.hip; rob_rep and pc_rep may be null); pg_ws_pc_bytes: the workspace
+// of one graph for a kind of preconditioner
+size_t pg_ws_pc_bytes(int nodes_cap, int edges_cap, int kind);
+void launch_pg_relax_chain(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
+                           lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep,
+                           lsd_pg_precond_rep* pc_rep, hipStream_t s);
 // place recognition (k_pgplace.hip): the descriptors of the rows that have none; and score + pick (out.rec == nullptr: the records and
 // the report only -- nodes, store, store_lens and the rest of out are not read or written then)
 void launch_pg_describe(const lsd_pg_head* head, int nodes_cap, const lsd_polar* store, const int* store_lens, int store_stride, double range_max,

@@ -20,6 +20,8 @@ static_assert(sizeof(lsd_pg_relax_par) == 56 && offsetof(lsd_pg_relax_par, iters
 static_assert(sizeof(lsd_pg_robust_par) == 16 && offsetof(lsd_pg_robust_par, delta) == 8 && sizeof(lsd_pg_robust_rep) == 24 &&
               offsetof(lsd_pg_robust_rep, downweighted) == 16 && sizeof(lsd_pg_prune_par) == 16 && offsetof(lsd_pg_prune_par, max_reject) == 8 &&
               sizeof(lsd_pg_prune_rep) == 24 && offsetof(lsd_pg_prune_rep, worst_chi2) == 16, "the robust relaxation's and the prune's records");
+static_assert(sizeof(lsd_pg_precond_par) == 8 && sizeof(lsd_pg_precond_rep) == 16 && offsetof(lsd_pg_precond_rep, fallbacks) == 12,
+              "the preconditioner's records");
 static_assert(sizeof(lsd_pg_desc) == 72 && sizeof(lsd_pg_place_par) == 32 && offsetof(lsd_pg_place_par, max_dist) == 20 && sizeof(lsd_pg_place_rec) == 16 &&
               offsetof(lsd_pg_place_rec, dist) == 8 && sizeof(lsd_pg_place_rep) == 16, "place recognition's records");
 static_assert(sizeof(lsd_pg_loops_par) == 8 && sizeof(lsd_pg_loop_rec) == 16 && offsetof(lsd_pg_loop_rec, dist) == 12 && sizeof(lsd_pg_loops_rep) == 16,
@@ -65,9 +67,13 @@ static bool pg_loops_par_bad(const lsd_pg_loops_par& p, int k) {
     return p.max_loops < 1 || p.max_loops > LSD_PG_LOOPS_MAX || p.spread < 0 || k < 1 || k > LSD_PG_PLACE_MAX;
 }
 
-// the two host relaxations: one graph around the device entry, rob == nullptr for the plain one
+static bool pg_precond_par_bad(const lsd_pg_precond_par& p) { return p.kind < LSD_PG_PRECOND_BLOCK || p.kind > LSD_PG_PRECOND_CHAIN || p.reserved != 0; }
+
+// the three host relaxations: one graph around the device entry, rob == nullptr for the plain one, pc != nullptr for the choice of
+// preconditioner
 static int pg_relax_host(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par,
-                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep);
+                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, const lsd_pg_precond_par* pc = nullptr,
+                         lsd_pg_precond_rep* pc_rep = nullptr);
 
 extern "C" {
 
@@ -152,6 +158,32 @@ int lsd_enqueue_pg_relax_robust_device(lsd_ctx* c, int n_graphs, const lsd_pg_he
     if (n_graphs == 0) return LSD_OK;
     return enqueue_on(c, stream, [&](hipStream_t s) {
         launch_pg_relax_robust(n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, par, rob, d_workspace, d_rep, d_rob_rep, s);
+        return LSD_OK;
+    });
+}
+
+size_t lsd_pg_workspace_pc_bytes(int nodes_cap, int edges_cap, int kind) {
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_precond_par_bad(lsd_pg_precond_par{kind, 0})) return 0;
+    return pg_ws_pc_bytes(nodes_cap, edges_cap, kind);
+}
+
+int lsd_enqueue_pg_relax_pc_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_heads, lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges,
+                                   int edges_cap, lsd_pg_relax_par par, lsd_pg_robust_par rob, lsd_pg_precond_par pc, void* d_workspace,
+                                   lsd_pg_relax_rep* d_rep, lsd_pg_robust_rep* d_rob_rep, lsd_pg_precond_rep* d_pc_rep, void* stream) {
+    if (!c || !d_heads || !d_nodes || !d_edges || !d_workspace || !d_rep || n_graphs < 0) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_relax_par_bad(par) || pg_robust_par_bad(rob) || pg_precond_par_bad(pc)) return LSD_ERR_INVALID;
+    if ((addr(d_heads) | addr(d_nodes) | addr(d_edges) | addr(d_workspace) | addr(d_rep) | addr(d_rob_rep) | addr(d_pc_rep)) & 7) {
+        c->err = "pg relax pc: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_graphs == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        if (pc.kind == LSD_PG_PRECOND_CHAIN) {
+            launch_pg_relax_chain(n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, par, rob, d_workspace, d_rep, d_rob_rep, d_pc_rep, s);
+            return LSD_OK;
+        }
+        launch_pg_relax_robust(n_graphs, d_heads, d_nodes, nodes_cap, d_edges, edges_cap, par, rob, d_workspace, d_rep, d_rob_rep, s);
+        if (d_pc_rep) HIPCHK(c, hipMemsetAsync(d_pc_rep, 0, (size_t)n_graphs * sizeof(lsd_pg_precond_rep), s));
         return LSD_OK;
     });
 }
@@ -331,6 +363,12 @@ int lsd_pg_relax_robust(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge
     return pg_relax_host(c, nodes, n_nodes, edges, n_edges, par, &rob, rep, rob_rep);
 }
 
+int lsd_pg_relax_pc(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par, lsd_pg_robust_par rob,
+                    lsd_pg_precond_par pc, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, lsd_pg_precond_rep* pc_rep) {
+    if (!rob_rep || !pc_rep || pg_robust_par_bad(rob) || pg_precond_par_bad(pc)) return LSD_ERR_INVALID;
+    return pg_relax_host(c, nodes, n_nodes, edges, n_edges, par, &rob, rep, rob_rep, &pc, pc_rep);
+}
+
 int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_cand, int stride, const lsd_position* poses, lsd_pg_head* head,
                   lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* track_rec, int32_t track, lsd_polar* store,
                   int* store_lens, int store_stride, lsd_pg_append_par par, lsd_pg_append_rep* rep) {
@@ -355,18 +393,23 @@ int lsd_pg_append(lsd_ctx* c, const lsd_polar* scans, const int* lens, int n_can
 }  // extern "C"
 
 static int pg_relax_host(lsd_ctx* c, lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, lsd_pg_relax_par par,
-                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep) {
+                         const lsd_pg_robust_par* rob, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep, const lsd_pg_precond_par* pc,
+                         lsd_pg_precond_rep* pc_rep) {
     if (!c || !rep || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
         return LSD_ERR_INVALID;
     if (pg_relax_par_bad(par)) return LSD_ERR_INVALID;
     const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
     const lsd_pg_head head{n_nodes, n_edges};
     lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_relax_rep* d_rep; lsd_pg_robust_rep* d_rob; uint8_t* d_ws;
+    lsd_pg_precond_rep* d_pc;
+    const size_t ws_bytes = pc ? pg_ws_pc_bytes(nc, ec, pc->kind) : pg_ws_bytes(nc, ec);
     auto plan = [&](StagePass& k) {                                        // (no nodes, no edges: the region of one still has its address)
-        k.in(d_head, &head, 1); k.both(d_no, nodes, n_nodes); k.both(d_ed, edges, n_edges); k.out(d_rep, rep, 1); k.scratch(d_ws, pg_ws_bytes(nc, ec));
+        k.in(d_head, &head, 1); k.both(d_no, nodes, n_nodes); k.both(d_ed, edges, n_edges); k.out(d_rep, rep, 1); k.scratch(d_ws, ws_bytes);
         k.out(d_rob, rob_rep, 1);
+        if (pc) k.out(d_pc, pc_rep, 1);
     };
     return stage_round_trip(c, plan, [&] {
+        if (pc) return lsd_enqueue_pg_relax_pc_device(c, 1, d_head, d_no, nc, d_ed, ec, par, *rob, *pc, d_ws, d_rep, d_rob, d_pc, c->stream);
         return rob ? lsd_enqueue_pg_relax_robust_device(c, 1, d_head, d_no, nc, d_ed, ec, par, *rob, d_ws, d_rep, d_rob, c->stream)
                    : lsd_enqueue_pg_relax_device(c, 1, d_head, d_no, nc, d_ed, ec, par, d_ws, d_rep, c->stream);
     });

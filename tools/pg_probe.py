@@ -22,8 +22,14 @@ DESIGN.md 8.1.15 .. 8.1.18), measured, with no threshold.  One JSON line each:
             launch) beside the same queries put through lsd_enqueue_pg_recognize_device one call each, in the same session; then
             lsd_enqueue_pg_loops_device on the batch's records at max_loops 8 and 64; and one PoseGraph.close_all_device chain (max_loops 8)
             on the graph and the scratch grid of `close`.
+  chain     (--only chain) lsd_enqueue_pg_relax_device beside lsd_enqueue_pg_relax_pc_device with the block-tridiagonal preconditioner
+             on `relax`'s closed loops of 64 / 512 / 4096 nodes, with one closure per 64 nodes and with 6 closures, 1 and
+            64 graphs per launch: the two entries ALTERNATE launch by launch in one session, events around each launch, the median, minimum
+            and maximum of REPS launches each.  Per entry: outer iterations, CG steps, microseconds per CG step, and the solves that ended at
+            cg_iters -- counted from calls of 1, 2, .. outer iterations, whose reports are each other's beginnings.
 Usage: tools/pg_probe.py [--reps 20] [--only relax,close,optimize,place] > profiles/pg_probe.log
-       tools/pg_probe.py --only loops >> profiles/pg_probe.log"""
+       tools/pg_probe.py --only loops >> profiles/pg_probe.log
+       tools/pg_probe.py --only chain >> profiles/pg_probe.log"""
 import argparse, importlib, json, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -86,6 +92,49 @@ def main():
                                       flags=int(r["flags"]), cost_before=float(r["chi2_before"]), cost_after=float(r["chi2_after"]),
                                       chi2_plain=float(rr["chi2_plain"]), downweighted=int(rr["downweighted"]), w_min=float(rr["w_min"]),
                                       us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1))), flush=True)
+
+    # 1b. the plain entry beside the chain preconditioner, alternating
+    for n, closures in [(n, c) for n in (64, 512, 4096) for c in sorted({n // 64, 6})] if "chain" in only else ():
+        nodes, edges, _ = pg.loop_graph(n, np.random.default_rng(n), radius=n / 4.0, bias=0.3 * 64 / n, closures=closures)
+        for graphs in (1, 64):
+            heads = np.zeros(graphs, lsd.PG_HEAD_DTYPE)
+            heads["n_nodes"], heads["n_edges"] = len(nodes), len(edges)
+            pristine = dev(np.tile(nodes.view(np.uint8), graphs))
+            d_no, d_ed, d_hd = pristine.clone(), dev(np.tile(edges.view(np.uint8), graphs)), dev(heads.view(np.uint8))
+            d_ws = torch.zeros(graphs * lsd.pg_workspace_pc_bytes(len(nodes), len(edges), "chain"), dtype=torch.uint8, device="cuda")
+            d_rp, d_pc = torch.zeros(graphs * 56, dtype=torch.uint8, device="cuda"), torch.zeros(graphs * 16, dtype=torch.uint8, device="cuda")
+
+            def entry(kind, p):
+                if kind == "plain":
+                    return ctx.enqueue_pg_relax_device(graphs, d_hd.data_ptr(), d_no.data_ptr(), len(nodes), d_ed.data_ptr(), len(edges), d_ws.data_ptr(),
+                                                       d_rp.data_ptr(), p, s)
+                return ctx.enqueue_pg_relax_pc_device(graphs, d_hd.data_ptr(), d_no.data_ptr(), len(nodes), d_ed.data_ptr(), len(edges), d_ws.data_ptr(),
+                                                      d_rp.data_ptr(), "chain", None, None, d_pc.data_ptr(), p, s)
+            ms, reps = {"plain": [], "chain": []}, {}
+            for k in range(args.reps + 1):                                       # (the first round warms both)
+                for kind in ("plain", "chain"):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    d_no.copy_(pristine); a.record(); entry(kind, par); b.record(); torch.cuda.synchronize()
+                    if k:
+                        ms[kind].append(a.elapsed_time(b))
+                    reps[kind] = d_rp.cpu().numpy().view(lsd.PG_RELAX_REP_DTYPE).copy()
+            pc = d_pc.cpu().numpy().view(lsd.PG_PRECOND_REP_DTYPE)[0]
+            for kind in ("plain", "chain"):
+                assert all(r.tobytes() == reps[kind][0].tobytes() for r in reps[kind])
+                r, at_cap, before = reps[kind][0], 0, 0
+                for it in range(1, int(r["iters"]) + 1):                         # the CG steps of each solve, from calls that stop after `it`
+                    d_no.copy_(pristine); entry(kind, dict(par, iters=it)); torch.cuda.synchronize()
+                    total = int(d_rp.cpu().numpy().view(lsd.PG_RELAX_REP_DTYPE)[0]["cg_iters"])
+                    at_cap += total - before == par["cg_iters"]
+                    before = total
+                med = float(np.median(ms[kind]))
+                print(json.dumps(dict(what="chain", entry=kind, nodes=len(nodes), edges=len(edges), closures=closures, graphs=graphs, ms_median=med,
+                                      ms_min=float(min(ms[kind])), ms_max=float(max(ms[kind])), outer=int(r["iters"]), cg_steps=int(r["cg_iters"]),
+                                      solves_at_cg_iters=int(at_cap), accepted=int(r["accepted"]), flags=int(r["flags"]),
+                                      chi2_before=float(r["chi2_before"]), chi2_after=float(r["chi2_after"]),
+                                      us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1),
+                                      **(dict(chain_edges=int(pc["chain_edges"]), paths=int(pc["paths"]), fallbacks=int(pc["fallbacks"])) if kind == "chain" else {}))),
+                      flush=True)
 
     # 2. place recognition: describe, recognize and near on stores of 360 readings
     for n in (64, 4096, 16384) if "place" in only else ():
