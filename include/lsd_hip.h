@@ -1231,6 +1231,99 @@ typedef struct lsd_pg_prune_rep { int32_t candidates, rejected, worst_edge, clos
 #define LSD_PG_EDGE_REJECTED 4u
 int lsd_enqueue_pg_prune_device(lsd_ctx *ctx, int n_graphs, const lsd_pg_head *d_heads, lsd_pg_edge *d_edges, int edges_cap,
                                 lsd_pg_prune_par par, lsd_pg_prune_rep *d_rep, void *stream);
+/* lsd_enqueue_pg_marginals_device: marginal covariances of ONE graph -- of a node, of one node relative to another, of the two ends of an
+ * edge that was appended since a copy of the head was taken -- by solves with the relaxation's normal matrix (csrc/k_pgmarg.hip; DESIGN.md
+ * 8.1.20; restated in tests/pose_graph_marginal_cases.py).  Nothing of the graph changes.  fp64 without FMA, every sum left to right from
+ * +0.0, no atomics on fp64, the one reduction shape wherever a dot product is reduced.  Everything that is not named here is the text of
+ * lsd_enqueue_pg_relax_device and lsd_enqueue_pg_relax_pc_device, word for word.
+ *   THE MATRIX.  N and E are the clamped counts of d_head.  E_h = E without d_prior; with it E_h = min(E, clamp(d_prior->n_edges)), the
+ *   clamp being min(max(., 0), edges_cap), read on the device: the matrix is the graph as it stood when d_prior was copied, so that the
+ *   edges appended since do not vouch for themselves.  Only the edges e < E_h exist for the matrix; they are skipped exactly as the
+ *   relaxation skips them.  The blocks are those of the relaxation's step 1 at the nodes' poses with plain weights (no robust kernel),
+ *   H_n is step 2's, lambda = 0.0: D(r,r) = H(r,r) + 0.0 * H(r,r), M_n = inv3(D_n).  A node is FIXED or SINGULAR as there (a node without
+ *   an edge below E_h is singular).  precond CHAIN: the chain edges, positions, blocks and factor of lsd_enqueue_pg_relax_pc_device over the
+ *   edges e < E_h at lambda = 0.0; where an inv3 of the factor fails the WHOLE call runs on the Jacobi blocks and fallbacks = 1.
+ *   A QUERY is {kind, a, b}.  U is a right-hand side of three columns over the nodes, +0.0 at every node that is not free.
+ *     NODE (a): a outside 0..N-1: BAD_QUERY.  a FIXED: the flag FIXED; a SINGULAR: the flag SINGULAR; neither is solved.  Else column c
+ *       of U is the unit vector c at node a, and cov(r,c) = x_c[a][r].
+ *     PAIR (a, b): a or b outside 0..N-1, or a == b: BAD_QUERY.  With (s, c), dx, dy, A and B of the relaxation's rule for an edge (i = a,
+ *       j = b) at the nodes' poses: column c of U is row c of A at node a and row c of B at node b, the part of a node that is not free
+ *       dropped (the flags FIXED and SINGULAR say that some end is; the solves are made all the same).
+ *       cov(r,c) = (sum_q A(r,q) * x_c[a][q]) + (sum_q B(r,q) * x_c[b][q]), every product made, x being +0.0 at a node that is not free:
+ *       the covariance of rel(pose_a, pose_b) in pixels, pixels and degrees, in the frame of a.
+ *     NEW_EDGE (k = a): without d_prior, or k < 0: BAD_QUERY.  e = clamp(d_prior->n_edges) + k; e >= E: NO_EDGE.  Else the PAIR
+ *       (edges[e].i, edges[e].j), both read on the device.
+ *     Any other kind: BAD_QUERY.
+ *   THE SOLVE, column after column, c = 0, 1, 2: PCG on H x = u exactly as step 4 of the relaxation with u in the place of -b: x = 0;
+ *   r = u; z = M^-1 r (z_n = M_n r_n, or the chain's apply); p = z; rz = rz0 = dot(r, z); thr = (cg_tol * cg_tol) * rz0; while steps <
+ *   cg_iters and !(rz <= thr): the step of the relaxation; !(pq > 0) ends the column as BREAKDOWN.  A column that ends with rz <= thr is
+ *   CONVERGED (rz0 == 0: with 0 steps and x = 0), one that ends otherwise without a breakdown is MAXED: exactly one of the three per column.
+ *   THE RECORD: cov[3 * r + c] as computed -- NOT symmetrised --, +0.0 nine times where nothing was solved; steps[c]; flags; the query's
+ *   kind; edge = e for NEW_EDGE with a prior and k >= 0 (also when NO_EDGE; beyond int32: 2147483647), else -1; i, j = the two nodes (a
+ *   and b as given for NODE and PAIR; -1, -1 where NEW_EDGE found no edge).
+ *   A GRAPH WITHOUT A FIXED NODE (or a component that no edge joins to one) has a singular matrix.  Its columns usually end MAXED or in
+ *   BREAKDOWN, but nothing in the rule forbids CONVERGED: with CHAIN the factor of the singular matrix need not fail, z is then enormous
+ *   along the free directions, rz0 with it, and the relative stop is met -- the covariance that comes out is enormous, not small, and
+ *   lsd_enqueue_pg_vet_device passes every closure on it: the gate is vacuous on such a graph.  Fix a node.
+ *   INDEPENDENCE: a record depends on the graph, d_prior and its query alone -- not on n_q, on slots, on its place in d_queries or on the
+ *   workgroup that served it.
+ *   THE REPORT: n_nodes = N, n_edges = E_h, the edges skipped among them, the singular nodes, the chain's three counts (0 for BLOCK),
+ *   fallbacks.
+ * Two launches on `stream`: the matrix by one workgroup into the shared part of the workspace, then min(n_q, slots) workgroups of which
+ * workgroup s serves the queries s, s + slots, .. with its vectors in slice s.  Every loop is bounded by a parameter, no workgroup waits
+ * for another, no allocation, no host wait.  lsd_pg_marginals_workspace_bytes = lsd_pg_workspace_pc_bytes(nodes_cap, edges_cap, precond)
+ * + slots slices of 15 (BLOCK) or 21 (CHAIN) doubles per node of nodes_cap, each rounded up to 256 bytes; 0 for arguments outside the limits.
+ * LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer other than d_prior (d_queries and d_recs may be null
+ * with n_q == 0); the caps of the relaxation; cg_tol not finite or negative; cg_iters outside 0..65535; precond outside 0..1; slots
+ * outside 1..1024; reserved != 0; n_q outside 0..65536; a pointer not 8-byte aligned.  n_q == 0 launches nothing and writes nothing. */
+typedef struct lsd_pg_marg_query { int32_t kind, a, b, reserved; } lsd_pg_marg_query;                   /* 16 bytes */
+enum { LSD_PG_MARG_NODE = 0, LSD_PG_MARG_PAIR = 1, LSD_PG_MARG_NEW_EDGE = 2 };
+typedef struct lsd_pg_marg_par { double cg_tol; int32_t cg_iters, precond, slots, reserved; } lsd_pg_marg_par;   /* 24 bytes */
+typedef struct lsd_pg_marg_rec {           /* 104 bytes */
+    double cov[9]; int32_t steps[3]; uint32_t flags; int32_t kind, edge, i, j;
+} lsd_pg_marg_rec;
+#define LSD_PG_MARG_CONVERGED_0 0x1u       /* column c: << c */
+#define LSD_PG_MARG_MAXED_0 0x10u
+#define LSD_PG_MARG_BREAKDOWN_0 0x100u
+#define LSD_PG_MARG_CONVERGED 0x7u         /* all three columns */
+#define LSD_PG_MARG_FIXED 0x1000u
+#define LSD_PG_MARG_SINGULAR 0x2000u
+#define LSD_PG_MARG_BAD_QUERY 0x4000u
+#define LSD_PG_MARG_NO_EDGE 0x8000u
+typedef struct lsd_pg_marg_rep {           /* 32 bytes */
+    int32_t n_nodes, n_edges, skipped_edges, singular_nodes, chain_edges, paths, longest_path, fallbacks;
+} lsd_pg_marg_rep;
+size_t lsd_pg_marginals_workspace_bytes(int nodes_cap, int edges_cap, int precond, int slots);
+int lsd_enqueue_pg_marginals_device(lsd_ctx *ctx, const lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap,
+                                    const lsd_pg_edge *d_edges, int edges_cap, const lsd_pg_head *d_prior /* may be NULL */,
+                                    const lsd_pg_marg_query *d_queries, int n_q, lsd_pg_marg_par par, void *d_workspace,
+                                    lsd_pg_marg_rec *d_recs, lsd_pg_marg_rep *d_rep, void *stream);
+/* lsd_enqueue_pg_vet_device: the gate on new closures -- is a closure's error at the current poses plausible, given what the graph knew
+ * of its two nodes before it?  d_queries[n_q] and d_recs[n_q] are those of lsd_enqueue_pg_marginals_device; N and E are d_head's clamped
+ * counts.  A query whose kind is not NEW_EDGE is not looked at: UNUSED.  For the others the first test that fires decides, and the outcome
+ * is exactly one flag:
+ *   1. the record says NO_EDGE or BAD_QUERY, or its edge is outside 0..E-1: NO_EDGE
+ *   2. edge e = the record's edge, as it stands when the launch begins: CLOSURE clear, DISABLED set, or skipped by the relaxation (i == j,
+ *      i or j outside 0..N-1, z, info or the two poses not finite): SKIPPED
+ *   3. the record is not CONVERGED in all three columns: NO_MARGINAL -- an unknown covariance rejects nothing
+ *   4. R = inv3(W), W the symmetric matrix of the edge's info, fails: SINGULAR, det = det(W)
+ *   5. S[q] = cov[q] + R[q] for q = 0..8 (not symmetrised); inv3(S) fails: SINGULAR, det = det(S)
+ *   6. e = the edge's error at the current poses; t(r) = sum_q S^-1(r,q) * e[q]; d2 = sum_r e[r] * t(r); det = det(S).  !(d2 <= gate), a NaN
+ *      included: REJECTED -- flags |= LSD_PG_EDGE_DISABLED | LSD_PG_EDGE_REJECTED, the bits the prune sets, and no other byte of any edge
+ *      changes
+ *   7. otherwise PASSED
+ * d_rep[q] (d_rep may be NULL): d2 and det (+0.0 where the test that computes them was not reached), the edge (-1 for UNUSED and NO_EDGE)
+ * and the flag.  Every outcome is decided from the edges as they stand when the launch begins and the bits are set behind that, so two
+ * queries that name one edge decide alike and write the same bits.  One launch of ONE workgroup, a lane per query and round, no
+ * workspace, no host wait.  LSD_ERR_INVALID before anything is enqueued, outputs untouched: a null pointer other than d_rep (d_queries
+ * and d_recs may be null with n_q == 0); the caps of the relaxation; gate not finite or negative; n_q outside 0..65536; a pointer not
+ * 8-byte aligned.  n_q == 0 launches nothing. */
+typedef struct lsd_pg_vet_rep { double d2, det; int32_t edge; uint32_t flags; } lsd_pg_vet_rep;         /* 24 bytes */
+enum { LSD_PG_VET_UNUSED = 1, LSD_PG_VET_NO_EDGE = 2, LSD_PG_VET_SKIPPED = 4, LSD_PG_VET_NO_MARGINAL = 8, LSD_PG_VET_SINGULAR = 16,
+       LSD_PG_VET_REJECTED = 32, LSD_PG_VET_PASSED = 64 };
+int lsd_enqueue_pg_vet_device(lsd_ctx *ctx, const lsd_pg_head *d_head, const lsd_pg_node *d_nodes, int nodes_cap, lsd_pg_edge *d_edges,
+                              int edges_cap, const lsd_pg_marg_query *d_queries, const lsd_pg_marg_rec *d_recs, int n_q, double gate,
+                              lsd_pg_vet_rep *d_rep /* may be NULL */, void *stream);
 /* Place recognition: loop candidates by the APPEARANCE of a keyframe's scan instead of its drifted pose, so that a loop is found when
  * lsd_enqueue_pg_near_device's radius no longer reaches (csrc/k_pgplace.hip; restated in
  * tests/pose_graph_place_cases.py).  One quantisation in fp64 without FMA, integers from there on.
@@ -1350,6 +1443,14 @@ int lsd_enqueue_pg_loop_select_device(lsd_ctx *ctx, const lsd_pg_head *d_head, c
  * entry with the n_cand candidates; lens[t] outside 0..stride: LSD_ERR_INVALID. */
 int lsd_pg_relax(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
                  lsd_pg_relax_rep *rep);
+/* lsd_pg_marginals: one graph (nodes[n_nodes], edges[n_edges], neither changed) and queries[n_q] -> recs[n_q] and rep, around
+ * lsd_enqueue_pg_marginals_device; prior_edges < 0: no prior, else a prior head whose n_edges is prior_edges.
+ * lsd_pg_vet: the graph, queries[n_q] and recs[n_q] -> the edges' flags in place and reps[n_q] (may be NULL), around
+ * lsd_enqueue_pg_vet_device. */
+int lsd_pg_marginals(lsd_ctx *ctx, const lsd_pg_node *nodes, int n_nodes, const lsd_pg_edge *edges, int n_edges, int prior_edges,
+                     const lsd_pg_marg_query *queries, int n_q, lsd_pg_marg_par par, lsd_pg_marg_rec *recs, lsd_pg_marg_rep *rep);
+int lsd_pg_vet(lsd_ctx *ctx, const lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, const lsd_pg_marg_query *queries,
+               const lsd_pg_marg_rec *recs, int n_q, double gate, lsd_pg_vet_rep *reps);
 int lsd_pg_relax_robust(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,
                         lsd_pg_robust_par rob, lsd_pg_relax_rep *rep, lsd_pg_robust_rep *rob_rep);
 int lsd_pg_relax_pc(lsd_ctx *ctx, lsd_pg_node *nodes, int n_nodes, lsd_pg_edge *edges, int n_edges, lsd_pg_relax_par par,

@@ -243,6 +243,25 @@ PG_MAX_REJECT = 64
 PG_PRECOND_REP_DTYPE = np.dtype([("chain_edges", "i4"), ("paths", "i4"), ("longest_path", "i4"), ("fallbacks", "i4")])
 assert (PG_PRECOND_REP_DTYPE.itemsize, C.sizeof(lsd_pg_precond)) == (16, 8)
 PG_PRECOND_BLOCK, PG_PRECOND_CHAIN = 0, 1
+# marginal covariances and the gate on new closures
+
+
+class lsd_pg_marg(C.Structure):        # the C side's lsd_pg_marg_par
+    _fields_ = [("cg_tol", C.c_double), ("cg_iters", C.c_int32), ("precond", C.c_int32), ("slots", C.c_int32), ("reserved", C.c_int32)]
+
+
+PG_MARG_QUERY_DTYPE = np.dtype([("kind", "i4"), ("a", "i4"), ("b", "i4"), ("reserved", "i4")])
+PG_MARG_REC_DTYPE = np.dtype([("cov", "f8", (9,)), ("steps", "i4", (3,)), ("flags", "u4"), ("kind", "i4"), ("edge", "i4"), ("i", "i4"), ("j", "i4")])
+PG_MARG_REP_DTYPE = np.dtype([("n_nodes", "i4"), ("n_edges", "i4"), ("skipped_edges", "i4"), ("singular_nodes", "i4"), ("chain_edges", "i4"),
+                              ("paths", "i4"), ("longest_path", "i4"), ("fallbacks", "i4")])
+PG_VET_REP_DTYPE = np.dtype([("d2", "f8"), ("det", "f8"), ("edge", "i4"), ("flags", "u4")])
+assert (PG_MARG_QUERY_DTYPE.itemsize, PG_MARG_REC_DTYPE.itemsize, PG_MARG_REP_DTYPE.itemsize, PG_VET_REP_DTYPE.itemsize,
+        C.sizeof(lsd_pg_marg)) == (16, 104, 32, 24, 24)
+PG_MARG_NODE, PG_MARG_PAIR, PG_MARG_NEW_EDGE = 0, 1, 2
+PG_MARG_CONVERGED_0, PG_MARG_MAXED_0, PG_MARG_BREAKDOWN_0, PG_MARG_CONVERGED = 0x1, 0x10, 0x100, 0x7
+PG_MARG_FIXED, PG_MARG_SINGULAR, PG_MARG_BAD_QUERY, PG_MARG_NO_EDGE = 0x1000, 0x2000, 0x4000, 0x8000
+PG_VET_UNUSED, PG_VET_NO_EDGE, PG_VET_SKIPPED, PG_VET_NO_MARGINAL, PG_VET_SINGULAR, PG_VET_REJECTED, PG_VET_PASSED = 1, 2, 4, 8, 16, 32, 64
+PG_MARG_MAX_QUERIES, PG_MARG_MAX_SLOTS = 65536, 1024
 # place recognition
 
 
@@ -398,6 +417,11 @@ _ABI = {
     "lsd_pg_workspace_pc_bytes": (_sz, [_i, _i, _i]),
     "lsd_enqueue_pg_relax_pc_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, lsd_pg_precond, _vp, _vp, _vp, _vp, _vp]),
     "lsd_pg_relax_pc": (_i, [_vp, _vp, _i, _vp, _i, lsd_pg_relax, lsd_pg_robust, lsd_pg_precond, _vp, _vp, _vp]),
+    "lsd_pg_marginals_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "lsd_enqueue_pg_marginals_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, lsd_pg_marg, _vp, _vp, _vp, _vp]),
+    "lsd_enqueue_pg_vet_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _dbl, _vp, _vp]),
+    "lsd_pg_marginals": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, lsd_pg_marg, _vp, _vp]),
+    "lsd_pg_vet": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _dbl, _vp]),
     "lsd_pg_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_int32, _vp, _vp, _i, lsd_pg_append, _vp]),
     "lsd_enqueue_pg_describe_device": (_i, [_vp, _vp, _i, _vp, _vp, _i, _dbl, _vp, _vp]),
     "lsd_enqueue_pg_recognize_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, lsd_pg_place, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -981,6 +1005,46 @@ class Context:
         self._chk(self.L.lsd_pg_relax_pc(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
                                          pg_relax(relax), rb, pg_precond(precond), rep.ctypes.data, rob.ctypes.data, pc.ctypes.data))
         return no, ed, rep[0], rob[0], pc[0]
+
+    def enqueue_pg_marginals_device(self, d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_queries, n_q, d_workspace, d_recs, d_rep, marg=None,
+                                    d_prior=None, stream=None):
+        """lsd_enqueue_pg_marginals_device on raw device addresses: the covariance of a node (PG_MARG_NODE), of one node relative to
+        another (PG_MARG_PAIR) or of the two ends of the k-th edge appended since the head was copied to d_prior (PG_MARG_NEW_EDGE),
+        one PG_MARG_QUERY_DTYPE -> one PG_MARG_REC_DTYPE each, and one PG_MARG_REP_DTYPE; the graph is not changed.  marg: pg_marg().
+        The workspace is pg_marginals_workspace_bytes(nodes_cap, edges_cap, precond, slots) bytes.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_marginals_device(self.h, d_head, d_nodes, int(nodes_cap), d_edges, int(edges_cap), d_prior, d_queries,
+                                                                int(n_q), pg_marg(marg), d_workspace, d_recs, d_rep, stream))
+
+    def enqueue_pg_vet_device(self, d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_queries, d_recs, n_q, gate, d_rep=None, stream=None):
+        """lsd_enqueue_pg_vet_device on raw device addresses: every PG_MARG_NEW_EDGE query whose closure's error at the current poses
+        is not plausible under its record's covariance plus the edge's own (!(d2 <= gate)) becomes DISABLED | REJECTED.  d_rep: None,
+        or one PG_VET_REP_DTYPE per query.  Asynchronous on `stream`."""
+        return self._chk(self.L.lsd_enqueue_pg_vet_device(self.h, d_head, d_nodes, int(nodes_cap), d_edges, int(edges_cap), d_queries, d_recs,
+                                                          int(n_q), float(gate), d_rep, stream))
+
+    def pg_marginals(self, nodes, edges, queries, marg=None, prior_edges=-1):
+        """lsd_pg_marginals from host arrays: returns (records PG_MARG_REC_DTYPE [n_q], report PG_MARG_REP_DTYPE); blocking.  queries:
+        pg_queries().  prior_edges < 0: no prior head."""
+        no, ed = np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        qu = pg_queries(queries)
+        recs, rep = np.zeros(len(qu), PG_MARG_REC_DTYPE), np.zeros(1, PG_MARG_REP_DTYPE)
+        self._chk(self.L.lsd_pg_marginals(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
+                                          int(prior_edges), qu.ctypes.data if len(qu) else None, len(qu), pg_marg(marg),
+                                          recs.ctypes.data if len(qu) else None, rep.ctypes.data))
+        return recs, rep[0]
+
+    def pg_vet(self, nodes, edges, queries, recs, gate):
+        """lsd_pg_vet from host arrays: returns (edges, reports PG_VET_REP_DTYPE [n_q]) -- the edges with the rejected closures
+        flagged; blocking."""
+        no, ed = np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        qu, rc = pg_queries(queries), np.array(recs, PG_MARG_REC_DTYPE).reshape(-1)
+        if len(rc) != len(qu):
+            raise LsdError(LSD_ERR_INVALID, "one record per query")
+        reps = np.zeros(len(qu), PG_VET_REP_DTYPE)
+        self._chk(self.L.lsd_pg_vet(self.h, no.ctypes.data if len(no) else None, len(no), ed.ctypes.data if len(ed) else None, len(ed),
+                                    qu.ctypes.data if len(qu) else None, rc.ctypes.data if len(qu) else None, len(qu), float(gate),
+                                    reps.ctypes.data if len(qu) else None))
+        return ed, reps
 
     def pg_append(self, scans, lens, poses, head, nodes, edges, track_rec, store, store_lens, track=0, append=None):
         """lsd_pg_append from host arrays: the candidates (scans float64 [n, stride, 2], lens int32 [n], poses float64 [n, 3]) against the
@@ -1883,6 +1947,54 @@ def pg_workspace_pc_bytes(nodes_cap, edges_cap, precond):
     return int(load_library().lsd_pg_workspace_pc_bytes(int(nodes_cap), int(edges_cap), int(pg_precond(precond).kind)))
 
 
+PG_MARG_DEFAULTS = dict(cg_tol=1e-8, cg_iters=200, precond="chain", slots=256)
+
+
+def pg_marg(marg=None, cg_tol=None, cg_iters=None, precond=None, slots=None):
+    """An lsd_pg_marg: the solves behind marginal covariances -- at most cg_iters conjugate-gradient steps per column, ended once r.z <=
+    cg_tol^2 of its start; precond as pg_precond() ("chain" by default: a track's matrix is a chain plus a few closures); slots (1..1024):
+    how many workgroups share the queries, each with vectors of its own in the workspace.  A record does not depend on slots."""
+    a = _pg_par(lsd_pg_marg, marg, PG_MARG_DEFAULTS, dict(cg_tol=cg_tol, cg_iters=cg_iters, precond=precond, slots=slots))
+    if isinstance(a, lsd_pg_marg):
+        return a
+    cg, sl = int(a["cg_iters"]), int(a["slots"])
+    if not (-2 ** 31 <= cg < 2 ** 31 and -2 ** 31 <= sl < 2 ** 31):
+        raise LsdError(LSD_ERR_INVALID, "cg_iters and slots are int32")
+    return lsd_pg_marg(float(a["cg_tol"]), cg, int(pg_precond(a["precond"]).kind), sl, 0)
+
+
+def pg_queries(queries):
+    """Queries of the marginals as PG_MARG_QUERY_DTYPE [n]: such an array itself, or rows (kind, a, b) of integers."""
+    if isinstance(queries, np.ndarray) and queries.dtype == PG_MARG_QUERY_DTYPE:
+        return np.ascontiguousarray(queries).reshape(-1)
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    if len(q) and (q.min() < -2 ** 31 or q.max() >= 2 ** 31):
+        raise LsdError(LSD_ERR_INVALID, "kind, a and b are int32")
+    out = np.zeros(len(q), PG_MARG_QUERY_DTYPE)
+    out["kind"], out["a"], out["b"] = q[:, 0], q[:, 1], q[:, 2]
+    return out
+
+
+def pg_vet(vet=None, gate=None, marg=None):
+    """The setting of a vetted closure chain (PoseGraph.close_device(.., vet=) and its kin): {"gate": the bound on the closure's squared
+    Mahalanobis distance under the pair's covariance plus its own -- 16.27 is the 0.999 quantile of chi-square with 3 degrees of freedom
+    --, "marg": pg_marg()}."""
+    a = dict(gate=16.27, marg=None)
+    if isinstance(vet, dict):
+        if set(vet) - set(a):
+            raise LsdError(LSD_ERR_INVALID, "vet: unknown keys %s" % sorted(set(vet) - set(a)))
+        a.update(vet)
+    elif vet is not None and vet is not True:
+        raise LsdError(LSD_ERR_INVALID, "vet takes a dict or keywords")
+    a.update({k: v for k, v in dict(gate=gate, marg=marg).items() if v is not None})
+    return dict(gate=float(a["gate"]), marg=pg_marg(a["marg"]))
+
+
+def pg_marginals_workspace_bytes(nodes_cap, edges_cap, precond, slots):
+    """lsd_pg_marginals_workspace_bytes: pg_workspace_pc_bytes plus one slice of vectors per slot; 0 for arguments outside the limits."""
+    return int(load_library().lsd_pg_marginals_workspace_bytes(int(nodes_cap), int(edges_cap), int(pg_precond(precond).kind), int(slots)))
+
+
 def pg_workspace_bytes(nodes_cap, edges_cap):
     """lsd_pg_workspace_bytes: the workspace of ONE graph of the relaxation; 0 for caps outside 1..16384 / 1..65536."""
     return int(load_library().lsd_pg_workspace_bytes(int(nodes_cap), int(edges_cap)))
@@ -2490,6 +2602,15 @@ class PoseGraph:
         self._loop_near, self._loop_closure_rep = z(PG_LOOPS_MAX, PG_NEAR_DTYPE.itemsize), z(PG_LOOPS_MAX, PG_CLOSURE_REP_DTYPE.itemsize)
         self._all_q = None                                                   # (q_lo, n_q, k, gap, window) of the last recognize_all_device
         self._loops_max = 0                                                  # max_loops of the last find_loops_device
+        # marginal covariances and the gate: the copy of the head, the queries "every node" and "new edge k", one report;
+        # the records and the workspace get their size with the first call that needs it (slots slices of vectors: marginals_device)
+        self._prior, self._marg_rep = z(PG_HEAD_DTYPE.itemsize), z(PG_MARG_REP_DTYPE.itemsize)
+        every = np.zeros(max(self.nodes_cap, PG_LOOPS_MAX), PG_MARG_QUERY_DTYPE)
+        every["a"] = np.arange(len(every))
+        new = every[:PG_LOOPS_MAX].copy()
+        new["kind"] = PG_MARG_NEW_EDGE
+        self._q_every, self._q_new = (torch.from_numpy(q.view(np.int32).reshape(len(q), 4)).to(dev) for q in (every[:self.nodes_cap], new))
+        self._marg_q, self._marg_n, self._marg_every, self._marg_recs, self._vet_reps, self._marg_ws = None, 0, False, None, None, None
 
     def _track(self, track):
         t = int(track)
@@ -2542,16 +2663,25 @@ class PoseGraph:
                                         *self._hand_over(), _cuda_stream(stream).cuda_stream)
 
     def close_device(self, scratch_mapper, track=0, gap=10, radius=10.0, window=2, search=None, response=None, smear=None, closure=None,
-                     stream=None):
+                     stream=None, vet=None):
         """One attempt at a loop closure for the last node of `track`, on one stream, in this order: near_device; scratch_mapper.clear();
         the WHOLE store integrated at the selection -- the anchor's neighbourhood alone, without the host knowing the anchor --;
         scratch_mapper.likelihood_device(smear); match plus response of the one gathered row; the closure edge.  scratch_mapper: a
         GridMapper of the map's frame that this call overwrites.  Returns the response record of the query, a CUDA uint8 tensor
-        [1, 192]; closure_report() says what came of it.  Nothing waits."""
+        [1, 192]; closure_report() says what came of it.  vet: None, or pg_vet()'s dict(gate=, marg=): snapshot_device() in front, and
+        behind the closure the marginal of the new edge's two ends on the graph without it and the gate, which takes a closure the
+        graph finds implausible out again before anything is relaxed (vet_reports(), marginal_records()).  Nothing
+        waits."""
         self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
+        vet = None if vet is None else pg_vet(vet)
+        if vet:
+            self.snapshot_device(ts)
         self.near_device(track, gap, radius, window, ts)
-        return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+        resp = self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+        if vet:
+            self._vetted(vet, 1, ts)
+        return resp
 
     def _close_tail(self, scratch_mapper, search, response, smear, closure, ts, d_near=None, d_closure_rep=None):
         """What follows the choice of an anchor, by pose (near_device) or by appearance (recognize_device, or loop m of
@@ -2594,14 +2724,20 @@ class PoseGraph:
                                              self._place_rep.data_ptr(), *self._hand_over(), ts.cuda_stream)
         self._place_k = int(par.k)
 
-    def close_place_device(self, scratch_mapper, track=0, place=None, search=None, response=None, smear=None, closure=None, stream=None):
+    def close_place_device(self, scratch_mapper, track=0, place=None, search=None, response=None, smear=None, closure=None, stream=None, vet=None):
         """close_device with the anchor found by recognize_device instead of near_device: a loop that odometry has NOT almost closed.
         range_max is the scratch mapper's.  Returns the response record of the query; closure_report(), place_report() and
-        place_records() say what came of it.  Nothing waits."""
+        place_records() say what came of it.  vet: as close_device's.  Nothing waits."""
         self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
+        vet = None if vet is None else pg_vet(vet)
+        if vet:
+            self.snapshot_device(ts)
         self.recognize_device(scratch_mapper.range_max, track, place, ts)
-        return self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+        resp = self._close_tail(scratch_mapper, search, response, smear, closure, ts)
+        if vet:
+            self._vetted(vet, 1, ts)
+        return resp
 
     def recognize_all_device(self, range_max, place=None, q_lo=0, n_q=None, stream=None):
         """Every keyframe of a range as a query in one launch (describe_device, then lsd_enqueue_pg_recognize_all_device): per query the
@@ -2628,16 +2764,21 @@ class PoseGraph:
                                          self._loops_rep.data_ptr(), _cuda_stream(stream).cuda_stream)
         self._loops_max = int(par.max_loops)
 
-    def close_all_device(self, scratch_mapper, place=None, loops=None, search=None, response=None, smear=None, closure=None, stream=None):
+    def close_all_device(self, scratch_mapper, place=None, loops=None, search=None, response=None, smear=None, closure=None, stream=None,
+                         vet=None):
         """Every loop of the graph closed in one pass, on one stream: recognize_all_device over all keyframes, find_loops_device, then for
         m = 0..max_loops-1 lsd_enqueue_pg_loop_select_device and close_device's tail with a near record, a closure report and a response
         record of its own.  An unfilled round ends as NO_ANCHOR.  The anchors' poses do not move between the tails (closures are appended,
         nothing is relaxed); optimize_device and rerender_device follow as after any closure.  range_max is the scratch mapper's.
         Returns the response records, a CUDA uint8 tensor [max_loops, 192]; loop_records(), loops_report() and closure_reports() say
-        what came of it.  Nothing waits."""
+        what came of it.  vet: as close_device's, with one NEW_EDGE query per round (k = 0 .. max_loops - 1; a round that appended
+        nothing leaves NO_EDGE).  Nothing waits."""
         import torch
         self._scratch(scratch_mapper)
         ts = _cuda_stream(stream)
+        vet = None if vet is None else pg_vet(vet)
+        if vet:
+            self.snapshot_device(ts)
         self.recognize_all_device(scratch_mapper.range_max, place, 0, None, ts)
         self.find_loops_device(loops, ts)
         gap, window = self._all_q[3:]
@@ -2652,6 +2793,8 @@ class PoseGraph:
         with torch.cuda.stream(ts):
             out = torch.cat(resps, dim=0)
         self._held_close = (held, out)                                       # the launches read them: alive until the next call
+        if vet:
+            self._vetted(vet, self._loops_max, ts)
         return out
 
     def relax_device(self, relax=None, stream=None, robust=None, precond=None, **kw):
@@ -2691,6 +2834,95 @@ class PoseGraph:
         self.relax_device(relax, ts, robust=robust, precond=precond)
         self.prune_device(gate, max_reject, ts)
         self.relax_device(relax if refit is None else refit, ts, precond=precond)
+
+    def snapshot_device(self, stream=None):
+        """An 8-byte device copy of the head on `stream`: the prior of the NEW_EDGE queries and of the matrix they are solved with --
+        the graph as it stands now, in front of the closures that are to be vetted.  Nothing waits."""
+        import torch
+        with torch.cuda.stream(_cuda_stream(stream)):
+            self._prior.copy_(self._head)
+
+    def marginals_device(self, queries=None, marg=None, stream=None, prior=False):
+        """Marginal covariances (lsd_enqueue_pg_marginals_device) of this graph at its current poses.  queries: None for every node
+        (nodes_cap NODE queries; marginal_records() keeps those of the nodes there are), "tracks" for the last node of every track --
+        read from the track records on the device, nothing waits --, "new" for the PG_LOOPS_MAX NEW_EDGE queries k = 0, 1, .., a CUDA
+        int32 tensor [n, 4] of (kind, a, b, 0) used where it is, or anything pg_queries() takes, which is uploaded (a host array in
+        pageable memory: that copy may wait for the stream).  marg: pg_marg(); its slots are capped by the number of queries, which
+        changes no record.  prior: True to solve on the graph as snapshot_device() saw it (what NEW_EDGE queries need).  The records'
+        and the workspace's tensors grow with the first call that needs them -- an allocation, never a wait; the tensors they replace
+        go back to torch's allocator on `stream`, so ONE stream must carry every marginals_device, vet_device and vetted closure chain of
+        a graph (a call on another stream while an earlier one is in flight could be handed memory that is still read).  A graph needs
+        a FIXED node: without one the matrix is singular and a solve may still end CONVERGED with an enormous covariance (DESIGN.md
+        8.1.20).  On `stream`."""
+        import torch
+        ts, par = _cuda_stream(stream), pg_marg(marg)
+        dev = self._head.device
+        with torch.cuda.stream(ts):
+            if queries is None:
+                q = self._q_every
+            elif isinstance(queries, str) and queries == "new":
+                q = self._q_new
+            elif isinstance(queries, str) and queries == "tracks":
+                q = torch.zeros((self.n_tracks, 4), dtype=torch.int32, device=dev)
+                q[:, 1] = self._tracks.view(torch.int32)[:, 0]
+            elif isinstance(queries, torch.Tensor) and queries.is_cuda:
+                if queries.dtype != torch.int32 or queries.dim() != 2 or queries.shape[1] != 4 or not queries.is_contiguous():
+                    raise LsdError(LSD_ERR_INVALID, "device queries are a contiguous int32 tensor [n, 4] of (kind, a, b, 0)")
+                q = queries
+            else:
+                if isinstance(queries, torch.Tensor):
+                    queries = queries.numpy()
+                h = pg_queries(queries)
+                q = torch.from_numpy(h.view(np.int32).reshape(len(h), 4).copy()).to(dev)
+            n = int(q.shape[0])
+            if n > PG_MARG_MAX_QUERIES:
+                raise LsdError(LSD_ERR_INVALID, "at most %d queries" % PG_MARG_MAX_QUERIES)
+            par = lsd_pg_marg(par.cg_tol, par.cg_iters, par.precond, max(1, min(int(par.slots), n)) if 1 <= par.slots <= PG_MARG_MAX_SLOTS else par.slots, 0)
+            need = pg_marginals_workspace_bytes(self.nodes_cap, self.edges_cap, par.precond, par.slots)
+            if self._marg_ws is None or self._marg_ws.numel() < need:
+                self._marg_ws = torch.zeros(max(need, 8), dtype=torch.uint8, device=dev)
+            if self._marg_recs is None or self._marg_recs.shape[0] < n:
+                self._marg_recs = torch.zeros((max(n, 1), PG_MARG_REC_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                self._vet_reps = torch.zeros((max(n, 1), PG_VET_REP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        self.ctx.enqueue_pg_marginals_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                             q.data_ptr() if n else None, n, self._marg_ws.data_ptr(), self._marg_recs.data_ptr() if n else None,
+                                             self._marg_rep.data_ptr(), par, self._prior.data_ptr() if prior else None, ts.cuda_stream)
+        self._marg_q, self._marg_n, self._marg_every = q, n, queries is None
+
+    def vet_device(self, gate, stream=None):
+        """The gate (lsd_enqueue_pg_vet_device) on the NEW_EDGE queries of the last marginals_device: a closure whose error at the
+        current poses is not plausible under the pair's covariance plus its own becomes DISABLED | REJECTED, as the prune flags an
+        edge.  vet_reports() says what was decided.  On a graph without a FIXED node the covariances are enormous where they converge
+        at all, and the gate passes everything: it is vacuous there.  On the stream of the marginals_device before it; nothing waits."""
+        if self._marg_q is None:
+            raise LsdError(LSD_ERR_INVALID, "vet_device follows marginals_device")
+        n = self._marg_n
+        self.ctx.enqueue_pg_vet_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                       self._marg_q.data_ptr() if n else None, self._marg_recs.data_ptr() if n else None, n, gate,
+                                       self._vet_reps.data_ptr() if n else None, _cuda_stream(stream).cuda_stream)
+
+    def _vetted(self, vet, n_new, ts):
+        """Behind the closures of a chain that began with snapshot_device(): the marginals of the first n_new new edges, then the gate."""
+        self.marginals_device(self._q_new[:n_new], vet["marg"], ts, prior=True)
+        self.vet_device(vet["gate"], ts)
+
+    def marginal_records(self):
+        """The last marginals_device's records (PG_MARG_REC_DTYPE, one per query; for queries=None those of the nodes there are): a
+        read-back, which waits for the device."""
+        if self._marg_q is None:
+            return np.zeros(0, PG_MARG_REC_DTYPE)
+        n = self.head()[0] if self._marg_every else self._marg_n
+        return self._read(self._marg_recs, PG_MARG_REC_DTYPE)[:n]
+
+    def marginals_report(self):
+        """The last marginals_device's report (PG_MARG_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._marg_rep, PG_MARG_REP_DTYPE)[0]
+
+    def vet_reports(self):
+        """The last vet_device's reports (PG_VET_REP_DTYPE, one per query of the marginals before it): a read-back."""
+        if self._vet_reps is None:
+            return np.zeros(0, PG_VET_REP_DTYPE)
+        return self._read(self._vet_reps, PG_VET_REP_DTYPE)[:self._marg_n]
 
     def fix(self, node, stream=None):
         """Sets LSD_PG_NODE_FIXED on a node, on `stream`; nothing waits."""

@@ -284,6 +284,16 @@ size_t pg_ws_pc_bytes(int nodes_cap, int edges_cap, int kind);
 void launch_pg_relax_chain(int n_graphs, const lsd_pg_head* heads, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
                            lsd_pg_relax_par par, lsd_pg_robust_par rob, void* ws, lsd_pg_relax_rep* rep, lsd_pg_robust_rep* rob_rep,
                            lsd_pg_precond_rep* pc_rep, hipStream_t s);
+// marginal covariances and the gate on new closures (k_pgmarg.hip): prepare (one workgroup) and solve (min(n_q, slots) workgroups) on one
+// stream, prior may be null; pg_marg_ws_bytes: the shared part (pg_ws_pc_bytes) and `slots` slices of pg_marg_slice_bytes; the vet is one
+// workgroup (reps may be null)
+size_t pg_marg_slice_bytes(int nodes_cap, int kind);
+size_t pg_marg_ws_bytes(int nodes_cap, int edges_cap, int kind, int slots);
+void launch_pg_marginals(const lsd_pg_head* head, const lsd_pg_head* prior, const lsd_pg_node* nodes, int nodes_cap, const lsd_pg_edge* edges,
+                         int edges_cap, const lsd_pg_marg_query* queries, int n_q, lsd_pg_marg_par par, void* ws, lsd_pg_marg_rec* recs,
+                         lsd_pg_marg_rep* rep, hipStream_t s);
+void launch_pg_vet(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap,
+                   const lsd_pg_marg_query* queries, const lsd_pg_marg_rec* recs, int n_q, double gate, lsd_pg_vet_rep* reps, hipStream_t s);
 // place recognition (k_pgplace.hip): the descriptors of the rows that have none; and score + pick (out.rec == nullptr: the records and
 // the report only -- nodes, store, store_lens and the rest of out are not read or written then)
 void launch_pg_describe(const lsd_pg_head* head, int nodes_cap, const lsd_polar* store, const int* store_lens, int store_stride, double range_max,

@@ -1,6 +1,6 @@
 // lsd_pg.hip -- the pose graph's part of the C ABI (include/lsd_hip.h, "pose graph"): the argument checks of the six device entries
 // (k_pgbuild.hip: append, near, closure; k_posegraph.hip: the relaxation, plain and robust; k_pgprune.hip: the rejection of closures), of
-// place recognition's two (k_pgplace.hip), the three that find every loop of a track (k_pgloops.hip) and the host conveniences, each one round trip through the context's staging (lsd_ctx.h: stage_round_trip).
+// place recognition's two (k_pgplace.hip), the three that find every loop of a track (k_pgloops.hip), the marginals and the vet (k_pgmarg.hip) and the host conveniences, each one round trip through the context's staging (lsd_ctx.h: stage_round_trip).
 #include <math.h>
 #include <stddef.h>
 
@@ -22,6 +22,10 @@ static_assert(sizeof(lsd_pg_robust_par) == 16 && offsetof(lsd_pg_robust_par, del
               sizeof(lsd_pg_prune_rep) == 24 && offsetof(lsd_pg_prune_rep, worst_chi2) == 16, "the robust relaxation's and the prune's records");
 static_assert(sizeof(lsd_pg_precond_par) == 8 && sizeof(lsd_pg_precond_rep) == 16 && offsetof(lsd_pg_precond_rep, fallbacks) == 12,
               "the preconditioner's records");
+static_assert(sizeof(lsd_pg_marg_query) == 16 && sizeof(lsd_pg_marg_par) == 24 && offsetof(lsd_pg_marg_par, cg_iters) == 8 &&
+              sizeof(lsd_pg_marg_rec) == 104 && offsetof(lsd_pg_marg_rec, steps) == 72 && offsetof(lsd_pg_marg_rec, flags) == 84 &&
+              offsetof(lsd_pg_marg_rec, kind) == 88 && sizeof(lsd_pg_marg_rep) == 32 && sizeof(lsd_pg_vet_rep) == 24 &&
+              offsetof(lsd_pg_vet_rep, edge) == 16, "the marginals' and the vet's records");
 static_assert(sizeof(lsd_pg_desc) == 72 && sizeof(lsd_pg_place_par) == 32 && offsetof(lsd_pg_place_par, max_dist) == 20 && sizeof(lsd_pg_place_rec) == 16 &&
               offsetof(lsd_pg_place_rec, dist) == 8 && sizeof(lsd_pg_place_rep) == 16, "place recognition's records");
 static_assert(sizeof(lsd_pg_loops_par) == 8 && sizeof(lsd_pg_loop_rec) == 16 && offsetof(lsd_pg_loop_rec, dist) == 12 && sizeof(lsd_pg_loops_rep) == 16,
@@ -68,6 +72,13 @@ static bool pg_loops_par_bad(const lsd_pg_loops_par& p, int k) {
 }
 
 static bool pg_precond_par_bad(const lsd_pg_precond_par& p) { return p.kind < LSD_PG_PRECOND_BLOCK || p.kind > LSD_PG_PRECOND_CHAIN || p.reserved != 0; }
+
+constexpr int kPgMaxSlots = 1024, kPgMaxQueries = 65536;
+static bool pg_queries_n_bad(int n_q) { return n_q < 0 || n_q > kPgMaxQueries; }
+static bool pg_marg_par_bad(const lsd_pg_marg_par& p) {
+    return pg_real_bad(p.cg_tol) || p.cg_iters < 0 || p.cg_iters > 65535 || pg_precond_par_bad(lsd_pg_precond_par{p.precond, 0}) || p.slots < 1 ||
+           p.slots > kPgMaxSlots || p.reserved != 0;
+}
 
 // the three host relaxations: one graph around the device entry, rob == nullptr for the plain one, pc != nullptr for the choice of
 // preconditioner
@@ -200,6 +211,82 @@ int lsd_enqueue_pg_prune_device(lsd_ctx* c, int n_graphs, const lsd_pg_head* d_h
     return enqueue_on(c, stream, [&](hipStream_t s) {
         launch_pg_prune(n_graphs, d_heads, d_edges, edges_cap, par, d_rep, s);
         return LSD_OK;
+    });
+}
+
+size_t lsd_pg_marginals_workspace_bytes(int nodes_cap, int edges_cap, int precond, int slots) {
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_precond_par_bad(lsd_pg_precond_par{precond, 0}) || slots < 1 || slots > kPgMaxSlots) return 0;
+    return pg_marg_ws_bytes(nodes_cap, edges_cap, precond, slots);
+}
+
+int lsd_enqueue_pg_marginals_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, const lsd_pg_edge* d_edges,
+                                    int edges_cap, const lsd_pg_head* d_prior, const lsd_pg_marg_query* d_queries, int n_q, lsd_pg_marg_par par,
+                                    void* d_workspace, lsd_pg_marg_rec* d_recs, lsd_pg_marg_rep* d_rep, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_edges || !d_workspace || !d_rep || pg_queries_n_bad(n_q) || (n_q && (!d_queries || !d_recs)))
+        return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_marg_par_bad(par)) return LSD_ERR_INVALID;
+    if ((addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_prior) | addr(d_queries) | addr(d_workspace) | addr(d_recs) | addr(d_rep)) & 7) {
+        c->err = "pg marginals: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_q == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_marginals(d_head, d_prior, d_nodes, nodes_cap, d_edges, edges_cap, d_queries, n_q, par, d_workspace, d_recs, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_enqueue_pg_vet_device(lsd_ctx* c, const lsd_pg_head* d_head, const lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges, int edges_cap,
+                              const lsd_pg_marg_query* d_queries, const lsd_pg_marg_rec* d_recs, int n_q, double gate, lsd_pg_vet_rep* d_rep,
+                              void* stream) {
+    if (!c || !d_head || !d_nodes || !d_edges || pg_queries_n_bad(n_q) || (n_q && (!d_queries || !d_recs))) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_real_bad(gate)) return LSD_ERR_INVALID;
+    if ((addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_queries) | addr(d_recs) | addr(d_rep)) & 7) {
+        c->err = "pg vet: every pointer 8-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    if (n_q == 0) return LSD_OK;
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_vet(d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_queries, d_recs, n_q, gate, d_rep, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_marginals(lsd_ctx* c, const lsd_pg_node* nodes, int n_nodes, const lsd_pg_edge* edges, int n_edges, int prior_edges,
+                     const lsd_pg_marg_query* queries, int n_q, lsd_pg_marg_par par, lsd_pg_marg_rec* recs, lsd_pg_marg_rep* rep) {
+    if (!c || !rep || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
+        return LSD_ERR_INVALID;
+    if (pg_queries_n_bad(n_q) || (n_q && (!queries || !recs)) || pg_marg_par_bad(par)) return LSD_ERR_INVALID;
+    if (n_q == 0) return LSD_OK;
+    const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;      // (a cap is at least 1)
+    const lsd_pg_head head{n_nodes, n_edges}, prior{n_nodes, prior_edges};
+    lsd_pg_head *d_head, *d_prior; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_marg_query* d_qu; lsd_pg_marg_rec* d_recs; lsd_pg_marg_rep* d_rep;
+    uint8_t* d_ws;
+    auto plan = [&](StagePass& k) {
+        k.in(d_head, &head, 1); k.in(d_prior, &prior, 1); k.in(d_no, nodes, n_nodes); k.in(d_ed, edges, n_edges); k.in(d_qu, queries, n_q);
+        k.out(d_recs, recs, n_q); k.out(d_rep, rep, 1); k.scratch(d_ws, pg_marg_ws_bytes(nc, ec, par.precond, par.slots));
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_marginals_device(c, d_head, d_no, nc, d_ed, ec, prior_edges < 0 ? nullptr : d_prior, d_qu, n_q, par, d_ws, d_recs, d_rep,
+                                               c->stream);
+    });
+}
+
+int lsd_pg_vet(lsd_ctx* c, const lsd_pg_node* nodes, int n_nodes, lsd_pg_edge* edges, int n_edges, const lsd_pg_marg_query* queries,
+               const lsd_pg_marg_rec* recs, int n_q, double gate, lsd_pg_vet_rep* reps) {
+    if (!c || n_nodes < 0 || n_nodes > kPgMaxNodes || n_edges < 0 || n_edges > kPgMaxEdges || (n_nodes && !nodes) || (n_edges && !edges))
+        return LSD_ERR_INVALID;
+    if (pg_queries_n_bad(n_q) || (n_q && (!queries || !recs)) || pg_real_bad(gate)) return LSD_ERR_INVALID;
+    if (n_q == 0) return LSD_OK;
+    const int nc = n_nodes ? n_nodes : 1, ec = n_edges ? n_edges : 1;
+    const lsd_pg_head head{n_nodes, n_edges};
+    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_marg_query* d_qu; lsd_pg_marg_rec* d_recs; lsd_pg_vet_rep* d_reps;
+    auto plan = [&](StagePass& k) {
+        k.in(d_head, &head, 1); k.in(d_no, nodes, n_nodes); k.both(d_ed, edges, n_edges); k.in(d_qu, queries, n_q); k.in(d_recs, recs, n_q);
+        k.out(d_reps, reps, n_q);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_vet_device(c, d_head, d_no, nc, d_ed, ec, d_qu, d_recs, n_q, gate, reps ? d_reps : nullptr, c->stream);
     });
 }
 

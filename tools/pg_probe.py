@@ -27,9 +27,14 @@ DESIGN.md 8.1.15 .. 8.1.18), measured, with no threshold.  One JSON line each:
             64 graphs per launch: the two entries ALTERNATE launch by launch in one session, events around each launch, the median, minimum
             and maximum of REPS launches each.  Per entry: outer iterations, CG steps, microseconds per CG step, and the solves that ended at
             cg_iters -- counted from calls of 1, 2, .. outer iterations, whose reports are each other's beginnings.
+  marginals (--only marginals,vet) lsd_enqueue_pg_marginals_device: every node's covariance on the closed loops of 64 / 512 / 4096 nodes by
+            both preconditioners, the prepare launch apart, the solve over slots = 1, 16, 256, 1024 on 4096 nodes, one iteration of
+            lsd_enqueue_pg_relax_pc_device beside it; vet: one close_all_device chain without and with vet=.
+
 Usage: tools/pg_probe.py [--reps 20] [--only relax,close,optimize,place] > profiles/pg_probe.log
        tools/pg_probe.py --only loops >> profiles/pg_probe.log
-       tools/pg_probe.py --only chain >> profiles/pg_probe.log"""
+       tools/pg_probe.py --only chain >> profiles/pg_probe.log
+       tools/pg_probe.py --only marginals,vet >> profiles/pg_probe.log"""
 import argparse, importlib, json, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -50,10 +55,10 @@ def main():
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     s = torch.cuda.current_stream().cuda_stream
 
-    def timed(fn, before=lambda: None):
+    def timed(fn, before=lambda: None, reps=None):
         before(); fn(); torch.cuda.synchronize()                                # warm
         ms = []
-        for _ in range(args.reps):
+        for _ in range(args.reps if reps is None else reps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             before(); a.record(); fn(); b.record(); torch.cuda.synchronize()
             ms.append(a.elapsed_time(b))
@@ -136,6 +141,51 @@ def main():
                                       **(dict(chain_edges=int(pc["chain_edges"]), paths=int(pc["paths"]), fallbacks=int(pc["fallbacks"])) if kind == "chain" else {}))),
                       flush=True)
 
+    # 1c. marginal covariances: every node's, by both preconditioners; the prepare launch apart (a call whose one query, the fixed node's,
+    # is not solved); the solve over `slots`; one CG step of lsd_enqueue_pg_relax_pc_device on the same graph beside it
+    for n in (64, 512, 4096) if "marginals" in only else ():
+        nodes, edges, _ = pg.loop_graph(n, np.random.default_rng(n), radius=n / 4.0, bias=0.3 * 64 / n, closures=n // 64)
+        head = np.array([(len(nodes), len(edges))], lsd.PG_HEAD_DTYPE)
+        d_no, d_ed, d_hd = dev(nodes.view(np.uint8)), dev(edges.view(np.uint8)), dev(head.view(np.uint8))
+        every = lsd.pg_queries([(lsd.PG_MARG_NODE, k, 0) for k in range(n)])
+        d_rep = torch.zeros(32, dtype=torch.uint8, device="cuda")
+
+        def measure(what, qu, kind, slots, cg_iters=300, **more):
+            d_q, d_recs = dev(qu.view(np.uint8)), torch.zeros(len(qu) * 104, dtype=torch.uint8, device="cuda")
+            d_ws = torch.zeros(lsd.pg_marginals_workspace_bytes(n, len(edges), kind, slots), dtype=torch.uint8, device="cuda")
+            marg = lsd.pg_marg(cg_tol=1e-6, cg_iters=cg_iters, precond=kind, slots=slots)
+            fn = lambda: ctx.enqueue_pg_marginals_device(d_hd.data_ptr(), d_no.data_ptr(), n, d_ed.data_ptr(), len(edges), d_q.data_ptr(), len(qu),
+                                                         d_ws.data_ptr(), d_recs.data_ptr(), d_rep.data_ptr(), marg, None, s)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); torch.cuda.synchronize()                # (a first call sizes the repetitions: 5 where one takes 0.3 s)
+            med, lo, hi = timed(fn, reps=5 if a.elapsed_time(b) > 300.0 else None)
+            recs = d_recs.cpu().numpy().view(lsd.PG_MARG_REC_DTYPE)
+            solved = recs[(recs["flags"] & 0x777) != 0]
+            steps = solved["steps"].reshape(-1) if len(solved) else np.zeros(1)
+            rp = d_rep.cpu().numpy().view(lsd.PG_MARG_REP_DTYPE)[0]
+            print(json.dumps(dict(what=what, nodes=n, edges=len(edges), precond=kind, queries=len(qu), slots=slots, workgroups=min(slots, len(qu)),
+                                  ms_median=med, ms_min=lo, ms_max=hi, steps_per_column_mean=float(steps.mean()), steps_per_column_max=int(steps.max()),
+                                  converged=int(((recs["flags"] & 7) == 7).sum()), fallbacks=int(rp["fallbacks"]),
+                                  us_per_cg_step_and_workgroup=1e3 * med * min(slots, len(qu)) / max(float(steps.sum()), 1.0), **more)), flush=True)
+        for kind in ("block", "chain"):
+            measure("marginals_prepare", every[:1], kind, 1)
+            measure("marginals_all_nodes", every, kind, 256)
+        if n == 4096:
+            for slots in (1, 16, 256, 1024):                                     # equal work at every setting: 1024 queries of 3 x 10 steps
+                measure("marginals_slots", every[::4].copy(), "chain", slots, cg_iters=10, cg_iters_cap=10)
+        d_ws = torch.zeros(lsd.pg_workspace_pc_bytes(n, len(edges), "chain"), dtype=torch.uint8, device="cuda")
+        d_rp, pristine = torch.zeros(56, dtype=torch.uint8, device="cuda"), d_no.clone()
+        one = dict(pg.RELAX_DEFAULTS, iters=1, cg_iters=300, cg_tol=1e-6, lambda0=0.0, lambda_min=0.0)
+        fn = lambda: ctx.enqueue_pg_relax_pc_device(1, d_hd.data_ptr(), d_no.data_ptr(), n, d_ed.data_ptr(), len(edges), d_ws.data_ptr(), d_rp.data_ptr(),
+                                                    "chain", None, None, None, one, s)
+        med, lo, hi = timed(fn, lambda: d_no.copy_(pristine))
+        r = d_rp.cpu().numpy().view(lsd.PG_RELAX_REP_DTYPE)[0]
+        print(json.dumps(dict(what="marginals_baseline_relax_pc_one_iteration", nodes=n, edges=len(edges), ms_median=med, ms_min=lo, ms_max=hi,
+                              cg_steps=int(r["cg_iters"]), us_per_cg_step=1e3 * med / max(int(r["cg_iters"]), 1))), flush=True)
+    if only == {"marginals"}:
+        ctx.close()
+        return 0
+
     # 2. place recognition: describe, recognize and near on stores of 360 readings
     for n in (64, 4096, 16384) if "place" in only else ():
         rng = np.random.default_rng(n)
@@ -213,7 +263,7 @@ def main():
             r = d_lrep.cpu().numpy().view(lsd.PG_LOOPS_REP_DTYPE)[0]
             print(json.dumps(dict(what="find_loops", nodes=n, records=n * k, edges=int(n - 1 + n // 64), max_loops=max_loops, ms_median=med, ms_min=lo,
                                   ms_max=hi, pairs=int(r["n_pairs"]), known=int(r["n_known"]), loops=int(r["n_loops"]))), flush=True)
-    if not only & {"close", "optimize", "place", "loops"}:
+    if not only & {"close", "optimize", "place", "loops", "vet"}:
         ctx.close()
         return 0
 
@@ -267,6 +317,19 @@ def main():
                               anchors=[int(v) for v in nears["anchor"]], queries=[int(v) for v in nears["query"]],
                               closure_flags=[int(v) for v in creps["flags"]])), flush=True)
         restore()
+    if "vet" in only:                                                           # one close_all_device chain without and with vet=
+        place = dict(gap=n_key // 2, window=2, spread=2, k=4, pick=0, max_dist=2000, min_sectors=32)
+        for vet in (None, dict(gate=16.27, marg=dict(cg_tol=1e-8, cg_iters=200, precond="chain", slots=256))):
+            fa = lambda: graph.close_all_device(scratch, place=place, loops=dict(max_loops=8, spread=2), search=search, response=dict(rx=2, ry=2, ra=1),
+                                                vet=vet)
+            med, lo, hi = timed(fa, restore)
+            more = {}
+            if vet:
+                vr, mr = graph.vet_reports(), graph.marginal_records()
+                more = dict(vet_flags=[int(v) for v in vr["flags"]], d2=[float(v) for v in vr["d2"]], steps=[[int(x) for x in r["steps"]] for r in mr])
+            print(json.dumps(dict(what="close_all_vet" if vet else "close_all_no_vet", keyframes=int(graph.head()[0]), max_loops=8, ms_median=med, ms_min=lo,
+                                  ms_max=hi, closure_flags=[int(v) for v in graph.closure_reports()[1]["flags"]], **more)), flush=True)
+            restore()
     if not only & {"close", "optimize"}:
         ctx.close()
         return 0
