@@ -1428,7 +1428,67 @@ int lsd_enqueue_pg_loop_select_device(lsd_ctx *ctx, const lsd_pg_head *d_head, c
                                       const lsd_polar *d_store, const int *d_store_lens, int store_stride, int gap, int window,
                                       const lsd_pg_loop_rec *d_loops, const lsd_pg_loops_rep *d_loops_rep, int m, lsd_pg_near_rec *d_near,
                                       lsd_position *d_sel, lsd_polar *d_q_scan, int *d_q_len, lsd_position *d_q_pose, void *stream);
+/* lsd_enqueue_pg_reduce_device: keyframes that add nothing are taken out, the odometry chain is contracted across them, and nodes, edges,
+ * tracks, store rows, lengths and descriptors are compacted in place, so that a graph that patrols the same places stops growing
+ * (csrc/k_pgreduce.hip; restated in tests/pose_graph_reduce_cases.py).  d_tracks: ALL n_tracks track records of the graph;
+ * d_desc: the descriptors of lsd_enqueue_pg_describe_device, or NULL for a graph that keeps none.  N and E are the clamped counts.  fp64
+ * without FMA; every sum runs ascending from 0.0; SKIPPED is the relaxation's definition above, W the symmetric matrix of an edge's info.
+ *   CELL.  A node whose x, y and ang are finite has the cell (floor(x / cell), floor(y / cell), floor(wrap(ang) / ang_bin)).  The three
+ *   components are kept as the fp64 values floor returns -- integers of any size, or an infinity where the quotient overflows -- and two
+ *   cells are the same where all three compare == : there is no integer type whose range could be left.  Any other node has no cell.
+ *   rank(k) = the number of nodes i < k that have k's cell (a count: no order).  REDUNDANT: k has a cell and rank(k) >= keep.
+ *   REMOVABLE: k is not LSD_PG_NODE_FIXED; no track record has last == k; among the edges that are not skipped exactly two touch k, one
+ *   with j == k (its INCOMING edge) and one with i == k (its OUTGOING edge); both have LSD_PG_EDGE_CLOSURE clear; inv3(W) of both succeeds.
+ *   MARKED: redundant and removable.  (Degrees and edge ids come from integer sums and minima.)
+ *   RUNS.  An edge e = (a, r) that is not skipped, with a not marked and r marked, HEADS a run.  z = e.z, S = inv3(W_e), len = 1, cur = r.
+ *   A step: with f = (cur, b) the outgoing edge of cur, zn = f.z, Sn = inv3(W_f), (s, c)(z.ang), k = pi / 180.0,
+ *     J1 = [(1.0, 0.0, k * ((-s) * zn.x - c * zn.y)), (0.0, 1.0, k * (c * zn.x - s * zn.y)), (0.0, 0.0, 1.0)]
+ *     J2 = [(c, -s, 0.0), (s, c, 0.0), (0.0, 0.0, 1.0)]
+ *     T(r,q) = sum_t J1(r,t) * S(t,q), U1(r,q) = sum_t T(r,t) * J1(q,t);  T'(r,q) = sum_t J2(r,t) * Sn(t,q), U2(r,q) = sum_t T'(r,t) * J2(q,t)
+ *     S = U1 + U2 (all nine elements, every product made, the zeros' too);  then z = comp(z, zn)
+ *   b not marked: the run ends at b.  b marked and len == max_run: b is UN-MARKED, the run ends at b, and where the outgoing edge of b leads
+ *   to a marked node that edge heads the next run, walked by the same owner.  Otherwise cur = b, len += 1, the next step.
+ *   A run is CONTRACTED when b != a, z[3] and S[9] are finite and I = inv3(S) succeeds: its len nodes are RETIRED, the slot of the heading
+ *   edge receives (i = a, j = b, flags = LSD_PG_EDGE_CONTRACTED, reserved = 0, z, info = I(0,0), I(0,1), I(1,1), I(0,2), I(1,2), I(2,2), chi2 =
+ *   +0.0) and the outgoing edges of its len nodes are dropped.  Any other run is KEPT WHOLE: nothing of it changes.  A marked node that no
+ *   run reached (a ring without an unmarked node) stays as well.
+ *   EDGES.  An edge with both ends in 0..N-1 and a retired end that is neither heading nor part of a contracted run (only a skipped edge
+ *   can be one) is dropped and counted.  The surviving edges keep their relative order; one with both ends in 0..N-1 has them renumbered,
+ *   one with an end outside keeps all its bytes.
+ *   COMPACTION.  d_map[k] = the new index of node k, k < N; -1 for a retired one and for N <= k < nodes_cap.  The surviving node records
+ *   (64 bytes), store rows (store_stride readings), lengths and descriptors (72 bytes) are at their new index, the order kept; a track's
+ *   last in 0..N-1 is renumbered, every other byte of a track kept; the head has the new counts.  From the new n_nodes up to N the
+ *   lengths are 0 -- empty scans to the integration -- and the descriptors all zero -- "not described", so that
+ *   lsd_enqueue_pg_describe_device describes what is appended there next --; node records and store rows there, and the edge records
+ *   from the new n_edges on, keep the bytes they had when the call began.
+ *   REPORT: nodes and edges before and after; nodes redundant, marked, retired; runs contracted and kept whole; the most nodes of one
+ *   contracted run; edges dropped for a retired end; flags: RETIRED iff a node was retired, SPLIT iff max_run ended a run.
+ *   A call that reports no SPLIT is idempotent: the same call again changes no byte but rewrites the map and the report.  A call that
+ *   reports SPLIT is NOT: a node that max_run un-marked is still redundant and removable, so the next call retires it (it and no other
+ *   node), and repeated calls end at a graph that no further call changes.
+ * A fixed number of launches on `stream` that depends on nodes_cap alone (8 + 1 + ceil(nodes_cap / 1024)); no workgroup waits for
+ * another, every loop is bounded by N, E or a parameter (a walk visits no node twice: a marked node has one incoming edge that counts,
+ * and the walk began at an unmarked node, so it cannot come back into what it has walked), no atomics on fp64, no allocation, no host wait.  LSD_ERR_INVALID before anything
+ * is enqueued, outputs untouched: a null pointer (d_desc and d_rep may be NULL); nodes_cap outside 1..16384, edges_cap outside 1..65536;
+ * store_stride outside 1..the context's scan capacity; n_tracks < 1; cell or ang_bin not finite or <= 0, ang_bin > 360; keep < 1, max_run
+ * < 1; store or workspace not 16-byte, a record array, the descriptors or d_rep not 8-byte, lengths or d_map not 4-byte aligned.
+ * lsd_pg_reduce_workspace_bytes: 0 for arguments outside those limits (a store_stride < 1 is one). */
+typedef struct lsd_pg_reduce_par { double cell, ang_bin; int32_t keep, max_run; } lsd_pg_reduce_par;    /* 24 bytes */
+typedef struct lsd_pg_reduce_rep {         /* 48 bytes */
+    int32_t nodes_before, edges_before, nodes_after, edges_after, redundant, marked, retired, runs, runs_kept, longest_run, dropped_edges;
+    uint32_t flags;
+} lsd_pg_reduce_rep;
+#define LSD_PG_EDGE_CONTRACTED 8u
+#define LSD_PG_REDUCE_RETIRED 1u
+#define LSD_PG_REDUCE_SPLIT 2u
+size_t lsd_pg_reduce_workspace_bytes(int nodes_cap, int edges_cap, int store_stride);
+int lsd_enqueue_pg_reduce_device(lsd_ctx *ctx, lsd_pg_head *d_head, lsd_pg_node *d_nodes, int nodes_cap, lsd_pg_edge *d_edges, int edges_cap,
+                                 lsd_pg_track *d_tracks, int n_tracks, lsd_polar *d_store, int *d_store_lens, int store_stride,
+                                 lsd_pg_desc *d_desc /* may be NULL */, lsd_pg_reduce_par par, int32_t *d_map /* nodes_cap */,
+                                 lsd_pg_reduce_rep *d_rep /* may be NULL */, void *d_workspace, void *stream);
 /* Host conveniences: host arrays of any alignment, staged through the context; blocking.
+ * lsd_pg_reduce: the graph (head, nodes[nodes_cap], edges[edges_cap], tracks[n_tracks], store, store_lens, desc[nodes_cap] or NULL) makes
+ * the round trip around lsd_enqueue_pg_reduce_device; map[nodes_cap] and rep receive the map and the report.
  * lsd_pg_describe: n scans (scans[n * stride], lens[n]) -> desc_out[n], every row described; n outside 0..16384: LSD_ERR_INVALID.
  * lsd_pg_recognize: desc[n_nodes] and a query index -> recs[par.k] and rep; no selection and no gather are written, par.window is
  * checked and not used; n_nodes outside 1..16384: LSD_ERR_INVALID.
@@ -1466,6 +1526,9 @@ int lsd_pg_recognize_all(lsd_ctx *ctx, const lsd_pg_desc *desc, int n_nodes, int
                          lsd_pg_place_rec *recs, lsd_pg_place_rep *reps);
 int lsd_pg_loops(lsd_ctx *ctx, const lsd_pg_place_rec *recs, const lsd_pg_place_rep *reps, int n_q, int k, const lsd_pg_edge *edges,
                  int n_edges, lsd_pg_loops_par par, lsd_pg_loop_rec *loops, lsd_pg_loops_rep *rep);
+int lsd_pg_reduce(lsd_ctx *ctx, lsd_pg_head *head, lsd_pg_node *nodes, int nodes_cap, lsd_pg_edge *edges, int edges_cap, lsd_pg_track *tracks,
+                  int n_tracks, lsd_polar *store, int *store_lens, int store_stride, lsd_pg_desc *desc /* may be NULL */,
+                  lsd_pg_reduce_par par, int32_t *map, lsd_pg_reduce_rep *rep);
 
 /* --- introspection used by the parity tests and the bench ------------------------------- */
 /* Scaled size of a cols x rows map: w = floor(cols*sca), h = floor(rows*sca) (myLSD.cpp:132-133). */

@@ -286,6 +286,19 @@ PG_LOOPS_MAX = 64
 PG_LOOP_REC_DTYPE = np.dtype([("query", "i4"), ("anchor", "i4"), ("shift", "i4"), ("dist", "u4")])
 PG_LOOPS_REP_DTYPE = np.dtype([("n_pairs", "i4"), ("n_known", "i4"), ("n_loops", "i4"), ("reserved", "i4")])
 assert (PG_LOOP_REC_DTYPE.itemsize, PG_LOOPS_REP_DTYPE.itemsize, C.sizeof(lsd_pg_loops)) == (16, 16, 8)
+# redundant keyframes retired, the store compacted
+
+
+class lsd_pg_reduce(C.Structure):      # the C side's lsd_pg_reduce_par
+    _fields_ = [("cell", C.c_double), ("ang_bin", C.c_double), ("keep", C.c_int32), ("max_run", C.c_int32)]
+
+
+PG_REDUCE_REP_DTYPE = np.dtype([("nodes_before", "i4"), ("edges_before", "i4"), ("nodes_after", "i4"), ("edges_after", "i4"), ("redundant", "i4"),
+                                ("marked", "i4"), ("retired", "i4"), ("runs", "i4"), ("runs_kept", "i4"), ("longest_run", "i4"),
+                                ("dropped_edges", "i4"), ("flags", "u4")])
+assert (PG_REDUCE_REP_DTYPE.itemsize, C.sizeof(lsd_pg_reduce)) == (48, 24)
+PG_EDGE_CONTRACTED = 8
+PG_REDUCE_RETIRED, PG_REDUCE_SPLIT = 1, 2
 
 
 # lsd_comm (include/lsd_hip.h): rank, world, an all-gather callback of device buffers on a stream, and its user pointer
@@ -433,6 +446,9 @@ _ABI = {
     "lsd_enqueue_pg_loop_select_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lsd_pg_recognize_all": (_i, [_vp, _vp, _i, _i, _i, lsd_pg_place, _vp, _vp]),
     "lsd_pg_loops": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, lsd_pg_loops, _vp, _vp]),
+    "lsd_pg_reduce_workspace_bytes": (_sz, [_i, _i, _i]),
+    "lsd_enqueue_pg_reduce_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, lsd_pg_reduce, _vp, _vp, _vp, _vp]),
+    "lsd_pg_reduce": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, lsd_pg_reduce, _vp, _vp]),
     "lsd_debug_calibrate": (_i, [_vp, _sz]),
     "lsd_debug_eval_math": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     "lsd_debug_lines": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -1143,6 +1159,33 @@ class Context:
         self._chk(self.L.lsd_pg_loops(self.h, rc.ctypes.data if len(rc) else None, rp.ctypes.data if len(rp) else None, len(rp), int(k),
                                       ed.ctypes.data if len(ed) else None, len(ed), par, out.ctypes.data, rep.ctypes.data))
         return out, rep[0]
+
+    def enqueue_pg_reduce_device(self, d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_tracks, n_tracks, d_store, d_store_lens, store_stride,
+                                 d_desc, reduce, d_map, d_rep, d_workspace, stream=None):
+        """lsd_enqueue_pg_reduce_device on raw device addresses: the keyframes of a place that `keep` older ones already hold are
+        retired where the odometry chain can be contracted across them, and nodes, edges, ALL n_tracks track records, store rows,
+        lengths and descriptors (d_desc may be None) are compacted in place.  d_map: int32 [nodes_cap], the new index of every node or
+        -1; d_rep: one PG_REDUCE_REP_DTYPE or None; d_workspace: pg_reduce_workspace_bytes(nodes_cap, edges_cap, store_stride) bytes.
+        reduce: pg_reduce().  Asynchronous."""
+        return self._chk(self.L.lsd_enqueue_pg_reduce_device(self.h, d_head, d_nodes, int(nodes_cap), d_edges, int(edges_cap), d_tracks, int(n_tracks),
+                                                             d_store, d_store_lens, int(store_stride), d_desc, pg_reduce(reduce), d_map, d_rep,
+                                                             d_workspace, stream))
+
+    def pg_reduce(self, head, nodes, edges, tracks, store, store_lens, desc=None, reduce=None):
+        """lsd_pg_reduce from host arrays: the graph head (PG_HEAD_DTYPE), nodes [nodes_cap], edges [edges_cap], tracks (PG_TRACK_DTYPE
+        [n_tracks]), store float64 [nodes_cap, store_stride, 2], store_lens int32 [nodes_cap] and desc (PG_DESC_DTYPE [nodes_cap], or
+        None).  Returns (head, nodes, edges, tracks, store, store_lens, desc, map int32 [nodes_cap], report): new arrays.  reduce:
+        pg_reduce().  Blocking."""
+        hd, no, ed = np.array(head, PG_HEAD_DTYPE).reshape(1), np.array(nodes, PG_NODE_DTYPE).reshape(-1), np.array(edges, PG_EDGE_DTYPE).reshape(-1)
+        tr, st, sl = np.array(tracks, PG_TRACK_DTYPE).reshape(-1), np.array(store, np.float64), np.array(store_lens, np.int32).reshape(-1)
+        de = None if desc is None else np.array(desc, PG_DESC_DTYPE).reshape(-1)
+        if st.ndim != 3 or st.shape[0] != len(no) or st.shape[2] != 2 or len(sl) != len(no) or (de is not None and len(de) != len(no)):
+            raise LsdError(LSD_ERR_INVALID, "store [nodes_cap, store_stride, 2], store_lens [nodes_cap], desc [nodes_cap] or None")
+        mp, rep = np.zeros(len(no), np.int32), np.zeros(1, PG_REDUCE_REP_DTYPE)
+        self._chk(self.L.lsd_pg_reduce(self.h, hd.ctypes.data, no.ctypes.data, len(no), ed.ctypes.data, len(ed), tr.ctypes.data, len(tr), st.ctypes.data,
+                                       sl.ctypes.data, st.shape[1], None if de is None else de.ctypes.data, pg_reduce(reduce), mp.ctypes.data,
+                                       rep.ctypes.data))
+        return hd[0], no, ed, tr, st, sl, de, mp, rep[0]
 
     def enqueue_map_update_device(self, d_grid, cols, rows, res, z_occ_max_dis, d_map, d_map_cache, d_lines, max_lines, d_count,
                                   d_line_im=None, params=None, stream=None):
@@ -1936,6 +1979,27 @@ def pg_loops(loops=None, max_loops=None, spread=None):
     return lsd_pg_loops(*ints)
 
 
+PG_REDUCE_DEFAULTS = dict(cell=4.0, ang_bin=10.0, keep=1, max_run=64)
+
+
+def pg_reduce(reduce=None, cell=None, ang_bin=None, keep=None, max_run=None):
+    """An lsd_pg_reduce: a keyframe is redundant where `keep` older ones lie in its cell of `cell` pixels by `ang_bin` degrees (about the
+    append's min_dist and min_ang: the keyframe spacing); at most max_run nodes in a row are contracted into one edge.  DESIGN.md
+    8.1.21."""
+    a = _pg_par(lsd_pg_reduce, reduce, PG_REDUCE_DEFAULTS, dict(cell=cell, ang_bin=ang_bin, keep=keep, max_run=max_run))
+    if isinstance(a, lsd_pg_reduce):
+        return a
+    ints = [int(a[n]) for n in ("keep", "max_run")]
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in ints):
+        raise LsdError(LSD_ERR_INVALID, "keep and max_run are int32")
+    return lsd_pg_reduce(float(a["cell"]), float(a["ang_bin"]), *ints)
+
+
+def pg_reduce_workspace_bytes(nodes_cap, edges_cap, store_stride):
+    """lsd_pg_reduce_workspace_bytes: the workspace of enqueue_pg_reduce_device; 0 for arguments outside the limits."""
+    return int(load_library().lsd_pg_reduce_workspace_bytes(int(nodes_cap), int(edges_cap), int(store_stride)))
+
+
 def pg_loops_workspace_bytes(n_q, k, edges_cap):
     """lsd_pg_loops_workspace_bytes: the workspace of enqueue_pg_loops_device; 0 for arguments it refuses."""
     return int(load_library().lsd_pg_loops_workspace_bytes(int(n_q), int(k), int(edges_cap)))
@@ -2564,8 +2628,9 @@ class PoseGraph:
     8.1.16); close_place_device() finds the anchor of a closure by the appearance of the scan where the drift has carried the pose out of
     close_device()'s radius; close_all_device() asks that of every keyframe in one launch and closes every distinct
     loop it finds; relax_device() and optimize_device() take precond="chain" for long tracks, and
-    the workspace has that preconditioner's size from the construction on -- 432 bytes per node of nodes_cap more than the default one
-    needs, whether precond is ever used or not --, so that no enqueue allocates.  Everything but nodes(), edges(), place_records(), loop_records(), the *report() and *reports()
+    reduce_device() retires redundant keyframes and compacts the graph, so that it stops growing where a robot patrols (DESIGN.md
+    8.1.21); the workspace has that preconditioner's size from the construction on -- 432 bytes per node of nodes_cap more than the default one
+    needs, whether precond is ever used or not --, so that no enqueue allocates.  Everything but nodes(), edges(), node_map(), place_records(), loop_records(), the *report() and *reports()
     methods and disable_edges() is enqueued without waiting for the device."""
 
     def __init__(self, nodes_cap, edges_cap, n_beams, n_tracks=1, ctx=None):
@@ -2611,6 +2676,9 @@ class PoseGraph:
         new["kind"] = PG_MARG_NEW_EDGE
         self._q_every, self._q_new = (torch.from_numpy(q.view(np.int32).reshape(len(q), 4)).to(dev) for q in (every[:self.nodes_cap], new))
         self._marg_q, self._marg_n, self._marg_every, self._marg_recs, self._vet_reps, self._marg_ws = None, 0, False, None, None, None
+        # reduce: the map, the report and a workspace of its own, sized here so that no enqueue allocates
+        self._map, self._reduce_rep = z(self.nodes_cap, dtype=torch.int32), z(PG_REDUCE_REP_DTYPE.itemsize)
+        self._reduce_ws = z(max(pg_reduce_workspace_bytes(self.nodes_cap, self.edges_cap, self.n_beams), 16))
 
     def _track(self, track):
         t = int(track)
@@ -2834,6 +2902,32 @@ class PoseGraph:
         self.relax_device(relax, ts, robust=robust, precond=precond)
         self.prune_device(gate, max_reject, ts)
         self.relax_device(relax if refit is None else refit, ts, precond=precond)
+
+    def reduce_device(self, reduce=None, stream=None):
+        """Redundant keyframes retired and the graph compacted in place (lsd_enqueue_pg_reduce_device), over ALL the
+        graph's tracks, its store and its descriptors: a keyframe in a place that `keep` older ones already hold goes where it is an
+        inner node of an odometry chain, the chain is contracted across it, and a store that was refusing appends accepts them again.
+        reduce: pg_reduce().  The nodes are renumbered: node_map() gives the new index of every old one, and whatever was read back
+        EARLIER -- nodes(), edges(), loop_records(), place_records(), marginal_records(), closure reports -- names OLD indices.  The
+        graph forgets what it keeps by old index: the last recognize_all_device and find_loops_device (find_loops_device must follow
+        a new recognize_all_device), snapshot_device()'s prior (now the reduced graph) and the marginal records.  reduce_report() says
+        what was done.  On `stream`; nothing waits."""
+        ts = _cuda_stream(stream)
+        self.ctx.enqueue_pg_reduce_device(self._head.data_ptr(), self._nodes.data_ptr(), self.nodes_cap, self._edges.data_ptr(), self.edges_cap,
+                                          self._tracks.data_ptr(), self.n_tracks, *self._store_args(), self._desc.data_ptr(), reduce,
+                                          self._map.data_ptr(), self._reduce_rep.data_ptr(), self._reduce_ws.data_ptr(), ts.cuda_stream)
+        self._all_q, self._loops_max = None, 0
+        self._marg_q, self._marg_n, self._marg_every = None, 0, False
+        self.snapshot_device(ts)
+
+    def reduce_report(self):
+        """The last reduce_device's report (PG_REDUCE_REP_DTYPE): a read-back, which waits for the device."""
+        return self._read(self._reduce_rep, PG_REDUCE_REP_DTYPE)[0]
+
+    def node_map(self):
+        """The last reduce_device's map, int32 [nodes_cap]: the new index of every node there was, -1 for a retired one and behind the
+        nodes.  A read-back, which waits for the device."""
+        return self._read(self._map, np.dtype("i4"))
 
     def snapshot_device(self, stream=None):
         """An 8-byte device copy of the head on `stream`: the prior of the NEW_EDGE queries and of the matrix they are solved with --

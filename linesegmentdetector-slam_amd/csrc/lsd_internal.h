@@ -311,6 +311,11 @@ void launch_pg_loops(const lsd_pg_place_rec* recs, const lsd_pg_place_rep* reps,
 void launch_pg_loop_select(const lsd_pg_head* head, const lsd_pg_node* nodes, int nodes_cap, const lsd_polar* store, const int* store_lens,
                            int store_stride, int gap, int window, const lsd_pg_loop_rec* loops, const lsd_pg_loops_rep* loops_rep, int m,
                            PgHandOver out, hipStream_t s);
+// reduce (k_pgreduce.hip): a number of launches that nodes_cap fixes; pg_reduce_ws_bytes: its workspace (desc and rep may be null)
+size_t pg_reduce_ws_bytes(int nodes_cap, int edges_cap, int store_stride);
+void launch_pg_reduce(lsd_pg_head* head, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* tracks, int n_tracks,
+                      lsd_polar* store, int* store_lens, int store_stride, lsd_pg_desc* desc, lsd_pg_reduce_par par, int32_t* map,
+                      lsd_pg_reduce_rep* rep, void* ws, hipStream_t s);
 void launch_dbgmath(int fn, const double* a, const double* b, double* o0, double* o1, size_t n, hipStream_t s);
 
 // x86-64 cvttsd2si semantics of the reference's (int) casts: NaN, +-inf and

@@ -30,6 +30,8 @@ static_assert(sizeof(lsd_pg_desc) == 72 && sizeof(lsd_pg_place_par) == 32 && off
               offsetof(lsd_pg_place_rec, dist) == 8 && sizeof(lsd_pg_place_rep) == 16, "place recognition's records");
 static_assert(sizeof(lsd_pg_loops_par) == 8 && sizeof(lsd_pg_loop_rec) == 16 && offsetof(lsd_pg_loop_rec, dist) == 12 && sizeof(lsd_pg_loops_rep) == 16,
               "the loops' records");
+static_assert(sizeof(lsd_pg_reduce_par) == 24 && offsetof(lsd_pg_reduce_par, keep) == 16 && sizeof(lsd_pg_reduce_rep) == 48 &&
+              offsetof(lsd_pg_reduce_rep, flags) == 44, "the reduce's records");
 
 constexpr int kPgMaxNodes = 16384, kPgMaxEdges = 65536;
 
@@ -72,6 +74,10 @@ static bool pg_loops_par_bad(const lsd_pg_loops_par& p, int k) {
 }
 
 static bool pg_precond_par_bad(const lsd_pg_precond_par& p) { return p.kind < LSD_PG_PRECOND_BLOCK || p.kind > LSD_PG_PRECOND_CHAIN || p.reserved != 0; }
+
+static bool pg_reduce_par_bad(const lsd_pg_reduce_par& p) {
+    return !(std::isfinite(p.cell) && p.cell > 0) || !(std::isfinite(p.ang_bin) && p.ang_bin > 0 && p.ang_bin <= 360) || p.keep < 1 || p.max_run < 1;
+}
 
 constexpr int kPgMaxSlots = 1024, kPgMaxQueries = 65536;
 static bool pg_queries_n_bad(int n_q) { return n_q < 0 || n_q > kPgMaxQueries; }
@@ -405,6 +411,47 @@ int lsd_enqueue_pg_loop_select_device(lsd_ctx* c, const lsd_pg_head* d_head, con
     return enqueue_on(c, stream, [&](hipStream_t s) {
         launch_pg_loop_select(d_head, d_nodes, nodes_cap, d_store, d_store_lens, store_stride, gap, window, d_loops, d_loops_rep, m, out, s);
         return LSD_OK;
+    });
+}
+
+size_t lsd_pg_reduce_workspace_bytes(int nodes_cap, int edges_cap, int store_stride) {
+    return pg_caps_bad(nodes_cap, edges_cap) || store_stride < 1 ? 0 : pg_reduce_ws_bytes(nodes_cap, edges_cap, store_stride);
+}
+
+int lsd_enqueue_pg_reduce_device(lsd_ctx* c, lsd_pg_head* d_head, lsd_pg_node* d_nodes, int nodes_cap, lsd_pg_edge* d_edges, int edges_cap,
+                                 lsd_pg_track* d_tracks, int n_tracks, lsd_polar* d_store, int* d_store_lens, int store_stride, lsd_pg_desc* d_desc,
+                                 lsd_pg_reduce_par par, int32_t* d_map, lsd_pg_reduce_rep* d_rep, void* d_workspace, void* stream) {
+    if (!c || !d_head || !d_nodes || !d_edges || !d_tracks || !d_store || !d_store_lens || !d_map || !d_workspace) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_stride_bad(c, store_stride) || n_tracks < 1 || pg_reduce_par_bad(par)) return LSD_ERR_INVALID;
+    if (((addr(d_store) | addr(d_workspace)) & 15) || ((addr(d_head) | addr(d_nodes) | addr(d_edges) | addr(d_tracks) | addr(d_desc) | addr(d_rep)) & 7) ||
+        ((addr(d_store_lens) | addr(d_map)) & 3)) {
+        c->err = "pg reduce: store and workspace 16-byte, the records and descriptors 8-byte, the lengths and d_map 4-byte aligned";
+        return LSD_ERR_INVALID;
+    }
+    return enqueue_on(c, stream, [&](hipStream_t s) {
+        launch_pg_reduce(d_head, d_nodes, nodes_cap, d_edges, edges_cap, d_tracks, n_tracks, d_store, d_store_lens, store_stride, d_desc, par, d_map,
+                         d_rep, d_workspace, s);
+        return LSD_OK;
+    });
+}
+
+int lsd_pg_reduce(lsd_ctx* c, lsd_pg_head* head, lsd_pg_node* nodes, int nodes_cap, lsd_pg_edge* edges, int edges_cap, lsd_pg_track* tracks,
+                  int n_tracks, lsd_polar* store, int* store_lens, int store_stride, lsd_pg_desc* desc, lsd_pg_reduce_par par, int32_t* map,
+                  lsd_pg_reduce_rep* rep) {
+    if (!c || !head || !nodes || !edges || !tracks || !store || !store_lens || !map || !rep) return LSD_ERR_INVALID;
+    if (pg_caps_bad(nodes_cap, edges_cap) || pg_stride_bad(c, store_stride) || n_tracks < 1 || pg_reduce_par_bad(par)) return LSD_ERR_INVALID;
+    const size_t rows = (size_t)nodes_cap * store_stride;
+    lsd_pg_head* d_head; lsd_pg_node* d_no; lsd_pg_edge* d_ed; lsd_pg_track* d_tr; lsd_polar* d_store; int* d_sl; lsd_pg_desc* d_desc = nullptr;
+    int32_t* d_map; lsd_pg_reduce_rep* d_rep; uint8_t* d_ws;
+    auto plan = [&](StagePass& k) {
+        k.both(d_store, store, rows); k.scratch(d_ws, pg_reduce_ws_bytes(nodes_cap, edges_cap, store_stride)); k.both(d_head, head, 1);
+        k.both(d_no, nodes, nodes_cap); k.both(d_ed, edges, edges_cap); k.both(d_tr, tracks, n_tracks);
+        if (desc) k.both(d_desc, desc, nodes_cap);
+        k.out(d_rep, rep, 1); k.both(d_sl, store_lens, nodes_cap); k.out(d_map, map, nodes_cap);
+    };
+    return stage_round_trip(c, plan, [&] {
+        return lsd_enqueue_pg_reduce_device(c, d_head, d_no, nodes_cap, d_ed, edges_cap, d_tr, n_tracks, d_store, d_sl, store_stride, desc ? d_desc : nullptr,
+                                            par, d_map, d_rep, d_ws, c->stream);
     });
 }
 
